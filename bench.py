@@ -15,11 +15,18 @@ figures of rounds 1-5 (250 154 interactions and 8 192 rows PER GPU: --scaling we
 
 A "step" is one optimiser step of the M-step (fused gradient kernel + dense Adam) on one minibatch; every 155 steps
 (= cluster_interval 5 epochs x 31 minibatches) the E-step (+ stat_envs) over all interactions runs inside the
-timed region, as in the reference loop.  The timed region is always WHOLE cluster intervals (so the replayed HIP
-graphs and the E-step are inside it) and at least MIN_TIMED_S long: --steps / --warmup are rounded up accordingly
-and the line reports both (`steps_requested`, `steps` = timed).  Inputs are resident in HBM before the timed region;
-nothing is read back inside it.  value = interactions processed by all ranks / max-over-ranks time (EXACT: whole epochs of
-n interactions each -- the ragged last minibatch counts its 4 394 rows, not 8 192).
+timed region, as in the reference loop.  The timed region is exactly --steps optimiser steps from the start of a cluster
+interval: whole epochs replay their HIP graphs, the E-step follows every 155th step, and the minibatches of a last, partial
+epoch replay one graph of the same alternating launches, captured ahead.  The warm-up is --warmup steps rounded up to whole
+cluster intervals (at least one); the line reports both (`warmup_requested`, `warmup`).  Inputs are resident in HBM before the
+timed region; nothing is read back inside it.  value = interactions processed by all ranks / max-over-ranks time of the
+region by HIP events on the launch stream (EXACT: the rows of every minibatch stepped -- the ragged last minibatch of an
+epoch counts its 4 394 rows, not 8 192).
+
+--dump-outputs DIR (one GPU): after the timed region, what its last step handed back is written as DIR/<name>.npy in float32 /
+float64 (about 10 MB): the seven parameter tables, the six loss terms of the last optimiser step, and the environment
+assignments, counts, diff_num and class weights of the last E-step.  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 Parity gate: before the line is printed, one epoch + one E-step from a seeded state run through the timed
 path (alternating launches, fused E-step with the reference's default tie-break) and through the CPU oracle; the line carries
@@ -47,8 +54,7 @@ YAHOO = dict(lr=0.005, invariant_coe=3.351991776096847, env_aware_coe=9.98865844
              alpha=1.9053711444718746)
 CLUSTER_INTERVAL = 5          # epochs (Yahoo_InvPref_Implicit.py:27)
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: 8 TB/s spec
-MIN_TIMED_S = 0.5
-MAX_TIMED_S = 30.0
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: the files of one run together
 
 
 class StubEvaluator:
@@ -417,23 +423,82 @@ def sync_or_die(world, seconds=120.0):
         time.sleep(0.0005)
 
 
+def partial_epoch_graph(mgr, rest, steps_before):
+    """The first `rest` minibatches of an epoch as ONE graph of alternating launches + the flush -- what a replay of whole
+    epochs runs, cut short -- captured ahead of the timed region for the step it will start at (`steps_before` steps on: the
+    launches pick their schedule slot by the step's parity).  None where the manager does not replay alternating epochs."""
+    import torch
+    if getattr(mgr, '_alt', None) is None or not mgr.graphs_enabled():
+        return None
+    st = mgr.state
+    mgr._alt_prepare(1, steps=rest)
+    mgr._epoch_by_env = mgr._weights_by_env()
+    step0 = st.step
+    st.step += steps_before
+    g = torch.cuda.CUDAGraph()
+    try:
+        with torch.cuda.graph(g, capture_error_mode='thread_local'):
+            mgr._epoch_losses[0, :rest].zero_()
+            mgr._issue_epochs_alt(True, 1, steps=rest)
+    finally:
+        st.step = step0       # (capture records, it does not run)
+    return g
+
+
+def run_steps(mgr, n_steps, pending, partial=None):
+    """n_steps optimiser steps in the reference loop's order, from the start of a cluster interval: runs of whole epochs (graph
+    replays where graphs are on), cluster() + stat_envs() after every CLUSTER_INTERVAL epochs, then the minibatches of a last,
+    partial epoch -- one replay of `partial` (partial_epoch_graph), or one planned step each.  Device results are appended to
+    `pending`.  Returns (interactions stepped by all ranks, the last step: ('epochs', epochs in its run) or ('steps', k),
+    (diff_num, counts) of the last E-step or None)."""
+    nb = mgr.batch_num
+    epochs, rest = divmod(int(n_steps), nb)
+    done, last, estep = 0, None, None
+    while done < epochs:
+        out = mgr.train_epochs(min(CLUSTER_INTERVAL - done % CLUSTER_INTERVAL, epochs - done), sync=False)
+        pending.append(out)
+        done += out.shape[0]
+        last = ('epochs', out.shape[0])
+        if done % CLUSTER_INTERVAL == 0:
+            # train.py:329-330: cluster() and the stat_envs() that follows it -- ONE launch on one GPU (the kernel's epilogue
+            # folds counts, diff_num and class weights; results are views of the E-step ring, nothing is cloned behind the replay)
+            estep = mgr.cluster_and_stat_envs(sync=False)
+            pending.extend(estep)
+    if rest and partial is not None:
+        mgr._sched_prepare(rest)                  # (as in front of an epoch replay: the device-side Adam schedule)
+        partial.replay()
+        mgr.state.step += rest
+        pending.append(mgr._epoch_losses[0, :rest])
+        last = ('steps', rest)
+    elif rest:
+        mgr._epoch_by_env = mgr._weights_by_env()   # (the weights brought up to date as in front of an epoch run)
+        if not mgr._epoch_by_env:
+            mgr._materialise_sample_weights()
+        mgr._epoch_losses[0, :rest].zero_()       # (a step ADDS its six loss terms into its slot)
+        for k in range(rest):
+            mgr._raw_step(k, mgr._alpha_for(k))
+        pending.append(mgr._epoch_losses[0, :rest])
+        last = ('steps', rest)
+    return epochs * mgr.n_total + sum(mgr.shard.global_batch_len(k) for k in range(rest)), last, estep
+
+
+def last_step_losses(mgr, last):
+    """the device view of the six loss terms (LOSS_KEYS order) of the step run_steps() ended with"""
+    kind, n = last
+    if kind == 'steps':
+        return mgr._epoch_losses[0, n - 1]
+    # a graph replays the run's epochs into slots 0 .. n - 1; eagerly issued epochs use slot 0, one at a time
+    return mgr._epoch_losses[(min(n, mgr._graph_epochs) - 1) if mgr.graphs_enabled() else 0, mgr.batch_num - 1]
+
+
 def timed_run(mgr, world, steps_req, warmup_req):
-    """Warm-up + the timed region, both in whole cluster intervals (5 epochs + E-step + stat_envs).
-    Returns (seconds max-over-ranks, steps timed, steps of warm-up, pending device results)."""
+    """Warm-up in whole cluster intervals (5 epochs + E-step + stat_envs), then the timed region: exactly steps_req optimiser
+    steps (run_steps).  Returns (seconds max-over-ranks, steps timed, steps of warm-up, graphs replayed, interactions timed,
+    the last step and the last E-step as run_steps() describes them)."""
     import torch
     nb = mgr.batch_num
     per = CLUSTER_INTERVAL * nb
     pending = []
-
-    def interval():
-        left = CLUSTER_INTERVAL
-        while left > 0:
-            out = mgr.train_epochs(left, sync=False)
-            pending.append(out)
-            left -= out.shape[0]
-        # train.py:329-330: cluster() and the stat_envs() that follows it -- ONE launch on one GPU (the kernel's epilogue folds
-        # counts, diff_num and class weights; results are views of the E-step ring, nothing is cloned behind the replay)
-        pending.extend(mgr.cluster_and_stat_envs(sync=False))
 
     def barrier():
         if world > 1:
@@ -450,38 +515,50 @@ def timed_run(mgr, world, steps_req, warmup_req):
             mgr.use_graph, graphs = False, False
     n_warm = max(1, -(-warmup_req // per))
     barrier(); sync_or_die(world)
-    t0 = time.perf_counter()
-    for _ in range(n_warm):
-        interval()
+    _, _, estep_warm = run_steps(mgr, n_warm * per, pending)
+    rest = steps_req % nb
+    partial = partial_epoch_graph(mgr, rest, steps_req - rest) if rest and graphs else None
     sync_or_die(world); barrier()
-    est = (time.perf_counter() - t0) / n_warm                     # seconds per interval (first replays included)
-    if world > 1:
-        t = torch.tensor([est], dtype=torch.float64, device=mgr.device)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        est = float(t.item())
-    n_int = max(-(-steps_req // per), int(MIN_TIMED_S / est) + 1)
-    n_int = max(1, min(n_int, max(-(-steps_req // per), int(MAX_TIMED_S / est))))
     pending.clear()
     barrier(); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n_int):
-        interval()
+    # HIP events on the launch stream around the region, the stream held busy in front of it: the host's latency to the first
+    # launch is not counted (a region of --steps 20 lasts ~0.3 ms); a host that falls behind later leaves gaps, and those are
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda._sleep(int(2e6))
+    t0.record()
+    n_inter, last, estep = run_steps(mgr, steps_req, pending, partial)
+    t1.record()
     torch.cuda.synchronize(); barrier()
-    dt = time.perf_counter() - t0
-    if dt < MIN_TIMED_S and world == 1:     # the estimate included first-replay costs: top the region up
-        extra = int((MIN_TIMED_S - dt) / (dt / n_int) * 1.1) + 1
-        for _ in range(extra):
-            interval()
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        n_int += extra
-    for p in pending:  # every epoch's losses, every E-step's diff_num and env counts were really produced
+    dt = t0.elapsed_time(t1) * 1e-3
+    for p in pending:  # every epoch's / step's losses, every E-step's diff_num and env counts were really produced
         assert bool(torch.isfinite(p.double()).all()), 'non-finite training result'
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=mgr.device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    return dt, n_int * per, n_warm * per, bool(graphs and mgr._graphs)
+    return dt, int(steps_req), n_warm * per, bool(graphs and mgr._graphs), n_inter, last, estep or estep_warm
+
+
+def dump_outputs(mgr, directory, last, estep):
+    """--dump-outputs: what the timed path handed back after its last step, as DIR/<name>.npy -- the model's seven parameter
+    tables (state_dict names, float32), `step_losses` (the last optimiser step's six terms, LOSS_KEYS order, float32), and the
+    last E-step's results: `envs` (every interaction's environment), `env_counts` and `diff_num` (float64: exact) and
+    `class_weights` (float32).  Returns {name: shape}."""
+    import numpy as np
+    out = {k: v.detach().float().cpu().numpy() for k, v in mgr.model.state_dict().items()}
+    out['step_losses'] = last_step_losses(mgr, last).float().cpu().numpy()
+    diff, counts = estep
+    out['envs'] = mgr.envs.double().cpu().numpy()
+    out['env_counts'] = counts.double().cpu().numpy()
+    out['diff_num'] = diff.double().reshape(-1).cpu().numpy()
+    out['class_weights'] = mgr.class_weights.float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}')
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in out.items()}
 
 
 def device_step_times(mgr, world):
@@ -867,7 +944,13 @@ def main():
     ap.add_argument('--no-parity-gate', action='store_true', help='profiling runs only: the line then says so')
     ap.add_argument('--no-extras', action='store_true', help='skip roofline_large / eval timing (profiling runs)')
     ap.add_argument('--spawn', action='store_true', help='launch the ranks as child processes even for --gpus 1 (checks the launcher path)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='one GPU: write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.gpus != 1:
+        ap.error('--dump-outputs needs --gpus 1')
 
     if (args.gpus > 1 or args.spawn) and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args))      # (nothing in this process has touched the GPU)
@@ -898,9 +981,9 @@ def main():
         torch.cuda.synchronize()
         rccl_ranks = int(probe.item()) if torch.distributed.get_backend() == 'nccl' else 0
         assert int(probe.item()) == torch.distributed.get_world_size() == world
-    def rate(m, steps_, dt_):
-        """interactions per second, exactly: whole epochs of m.n_total interactions (the ragged last minibatch is shorter)"""
-        return steps_ / m.batch_num * m.n_total / dt_
+    def rate(n_, dt_):
+        """interactions per second, exactly: the rows of every minibatch stepped (the ragged last minibatch is shorter)"""
+        return n_ / dt_
 
     # the parity gate first: a path that does not reproduce the oracle is not timed (BASELINE.md §3.2)
     gate = None
@@ -923,8 +1006,9 @@ def main():
     mgr = build_manager(dev, rank, world, 'rows' if world > 1 else None)
     n_total, gbatch = problem_size(world)
     b_loc = gbatch // world                      # rows of a full minibatch on one rank (the byte models below are per rank)
-    dt, steps, warm_steps, graphs = timed_run(mgr, world, args.steps, args.warmup)
-    value = rate(mgr, steps, dt)
+    dt, steps, warm_steps, graphs, n_timed, last, estep = timed_run(mgr, world, args.steps, args.warmup)
+    value = rate(n_timed, dt)
+    dumped = dump_outputs(mgr, args.dump_outputs, last, estep) if args.dump_outputs else None
     ms_step_dev, ms_estep_eager, ms_estep_replay = device_step_times(mgr, world)
     n_local = mgr.users_tensor.shape[0]
     ms_estep = ms_estep_replay if ms_estep_replay else ms_estep_eager
@@ -1018,13 +1102,13 @@ def main():
                            'slots_per_round_users_items': list(mgr._alt.get('slots', ())), 'fold_flag_timeouts': mgr.alt_error()}
     out = {
         'metric': 'training interactions/sec, Yahoo-implicit InvPref', 'value': value, 'unit': 'interactions/s',
-        'n_gpus': world, 'steps': steps, 'steps_requested': args.steps, 'warmup': warm_steps,
+        'n_gpus': world, 'steps': steps, 'steps_requested': args.steps, 'interactions_timed': n_timed, 'warmup': warm_steps,
         'warmup_requested': args.warmup, 'ms_per_step': dt / steps * 1e3,
         'higher_is_better': True, 'scaling': SCALING, 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
         'config': {'workload': 'yahoo_r3_implicit_shaped', 'users': U, 'items': I, 'envs': E, 'factor_num': D,
                    'scaling': SCALING, 'interactions_total': n_total, 'global_batch': gbatch,
                    'interactions_per_gpu': n_total // world, 'batch_per_gpu': b_loc,
-                   'interactions_counted': 'exact: steps / minibatches-per-epoch x interactions_total (the last minibatch of an '
+                   'interactions_counted': 'exact: the rows of every minibatch stepped (the last minibatch of an '
                                            'epoch has 4 394 rows, not 8 192: rounds 1-5 counted steps x 8 192, +1.5 %)',
                    'estep_every_steps': CLUSTER_INTERVAL * mgr.batch_num,
                    'parallelism': (f'{mgr.shard_mode}-sharded x{world}, 1 all-reduce/step '
@@ -1033,6 +1117,8 @@ def main():
         'roofline': roofline, 'detail': detail,
     }
     out['rccl_ranks'] = rccl_ranks    # ranks that took part in an RCCL all-reduce in front of the run (None: single GPU)
+    if dumped is not None:
+        out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
     out['parity_gate'] = gate if gate is not None else {
         'pass': None, 'note': 'not run (--no-parity-gate)'}
     if world > 1:
@@ -1045,8 +1131,8 @@ def main():
         torch.cuda.empty_cache()
         os.environ['INVPREF_EXCHANGE'] = 'scatter'
         mgr_a = build_manager(dev, rank, world, 'rows')
-        dt_a, steps_a, _, _ = timed_run(mgr_a, world, args.steps, args.warmup)
-        out['detail']['rows_scatter'] = {'value': rate(mgr_a, steps_a, dt_a), 'ms_per_step': dt_a / steps_a * 1e3,
+        dt_a, steps_a, _, _, n_a, _, _ = timed_run(mgr_a, world, args.steps, args.warmup)
+        out['detail']['rows_scatter'] = {'value': rate(n_a, dt_a), 'ms_per_step': dt_a / steps_a * 1e3,
                                          'steps': steps_a, 'exchange': 'reduce-scatter(grad) + all-gather(param)',
                                          'flat_buffer_bytes': 4 * mgr_a.state.cap}
         del mgr_a
@@ -1054,8 +1140,8 @@ def main():
         # the all-reduce over the rows each GLOBAL minibatch touches + the small tables only (packed on the device)
         os.environ['INVPREF_EXCHANGE'] = 'packed'
         mgr_p = build_manager(dev, rank, world, 'rows')
-        dt_p, steps_p, _, _ = timed_run(mgr_p, world, args.steps, args.warmup)
-        out['detail']['rows_packed'] = {'value': rate(mgr_p, steps_p, dt_p), 'ms_per_step': dt_p / steps_p * 1e3,
+        dt_p, steps_p, _, _, n_p, _, _ = timed_run(mgr_p, world, args.steps, args.warmup)
+        out['detail']['rows_packed'] = {'value': rate(n_p, dt_p), 'ms_per_step': dt_p / steps_p * 1e3,
                                         'steps': steps_p, 'exchange': 'pack touched rows -> 1 all-reduce -> unpack',
                                         'all_reduce_bytes_mean': 4 * sum(mgr_p.packed_floats) / len(mgr_p.packed_floats),
                                         'flat_gradient_bytes': 4 * mgr_p.state.n}
@@ -1063,24 +1149,24 @@ def main():
         torch.cuda.empty_cache()
         os.environ.pop('INVPREF_EXCHANGE', None)
         mgr_u = build_manager(dev, rank, world, 'users')
-        dt_u, steps_u, _, _ = timed_run(mgr_u, world, args.steps, args.warmup)
-        out['detail']['user_sharded'] = {'value': rate(mgr_u, steps_u, dt_u), 'ms_per_step': dt_u / steps_u * 1e3,
+        dt_u, steps_u, _, _, n_u, _, _ = timed_run(mgr_u, world, args.steps, args.warmup)
+        out['detail']['user_sharded'] = {'value': rate(n_u, dt_u), 'ms_per_step': dt_u / steps_u * 1e3,
                                          'steps': steps_u, 'all_reduce_bytes': 4 * (mgr_u.state.n + 8 - mgr_u._ar_lo)}
         del mgr_u
         torch.cuda.empty_cache()
         # SURVEY 8(d)-4's large-batch variant: B = N, one optimiser step per epoch (the exchange amortised over 250 154 rows)
         os.environ['INVPREF_EXCHANGE'] = 'allreduce'
         mgr_b = build_manager(dev, rank, world, 'rows', batch=n_total)
-        dt_b, steps_b, _, _ = timed_run(mgr_b, world, args.steps, args.warmup)
-        out['detail']['large_batch'] = {'value': rate(mgr_b, steps_b, dt_b), 'ms_per_step': dt_b / steps_b * 1e3, 'steps': steps_b,
+        dt_b, steps_b, _, _, n_b, _, _ = timed_run(mgr_b, world, args.steps, args.warmup)
+        out['detail']['large_batch'] = {'value': rate(n_b, dt_b), 'ms_per_step': dt_b / steps_b * 1e3, 'steps': steps_b,
                                         'global_batch': n_total, 'exchange': 'allreduce'}
         del mgr_b
         torch.cuda.empty_cache()
         # ... and the other scaling mode, same exchange (strong run: the weak figures of rounds 1-5, and vice versa)
         other = 'weak' if SCALING == 'strong' else 'strong'
         mgr_w = build_manager(dev, rank, world, 'rows', scaling=other)
-        dt_w, steps_w, _, _ = timed_run(mgr_w, world, args.steps, args.warmup)
-        out['detail'][other] = {'value': rate(mgr_w, steps_w, dt_w), 'ms_per_step': dt_w / steps_w * 1e3, 'steps': steps_w,
+        dt_w, steps_w, _, _, n_w, _, _ = timed_run(mgr_w, world, args.steps, args.warmup)
+        out['detail'][other] = {'value': rate(n_w, dt_w), 'ms_per_step': dt_w / steps_w * 1e3, 'steps': steps_w,
                                 'interactions_total': mgr_w.n_total, 'global_batch': mgr_w.batch_size, 'exchange': 'allreduce'}
         os.environ.pop('INVPREF_EXCHANGE', None)
     if rank == 0 and world == 1 and not args.no_extras:

@@ -558,17 +558,19 @@ class _InvPrefTrainManager:
             #  re-homing brought us here: keep them, their slot choice and the workspace)
             self._alt.update({k: prev[k] for k in ('plans', 'ws', 'slots') if k in prev})
 
-    def _alt_keys(self, n: int):
-        """(k_prev, k, side) of every launch of a run of n epochs, the flush (k = None) last"""
-        bn, total = self.batch_num, n * self.batch_num
+    def _alt_keys(self, n: int, steps: Optional[int] = None):
+        """(k_prev, k, side) of every launch of a run of n epochs (or of its first `steps` minibatches), the flush (k = None) last"""
+        bn = self.batch_num
+        total = n * bn if steps is None else steps
         keys = [(None, 0, 0)] + [((i - 1) % bn, i % bn, i & 1) for i in range(1, min(total, 2 * bn + 1))]
         return keys + [((total - 1) % bn, None, total & 1)]     # (the plan sequence is periodic after the first launch)
 
-    def _alt_prepare(self, n: int):
-        """builds (natively, one call: csrc/invpref_plan.cpp) and uploads every plan a run of n epochs needs, and the run's
-        workspace -- BEFORE a graph capture starts: host-to-device copies and allocations are not capturable"""
+    def _alt_prepare(self, n: int, steps: Optional[int] = None):
+        """builds (natively, one call: csrc/invpref_plan.cpp) and uploads every plan a run of n epochs (or of its first `steps`
+        minibatches) needs, and the run's workspace -- BEFORE a graph capture starts: host-to-device copies and allocations
+        are not capturable"""
         A = self._alt
-        need = [key for key in dict.fromkeys(self._alt_keys(n)) if key not in A['plans']]
+        need = [key for key in dict.fromkeys(self._alt_keys(n, steps)) if key not in A['plans']]
         if need:
             t0 = time.perf_counter()
             u, v, y = self._alt_host
@@ -594,11 +596,12 @@ class _InvPrefTrainManager:
         minibatch k_prev (None: first launch of a run) and left `partials_prev` partial slabs"""
         return planlib.alt_with_partials(self._alt['plans'][(k_prev, k, side)], partials_prev)
 
-    def _issue_epochs_alt(self, sched: bool, n: int):
+    def _issue_epochs_alt(self, sched: bool, n: int, steps: Optional[int] = None):
+        """n epochs of alternating launches + the flush; `steps`: only the first `steps` minibatches of the run"""
         st, A, bn = self.state, self._alt, self.batch_num
-        total = n * bn
+        total = n * bn if steps is None else steps
         if not torch.cuda.is_current_stream_capturing():
-            self._alt_prepare(n)
+            self._alt_prepare(n, steps)
         k_prev, tasks_prev, alpha = None, 0, self.alpha
         for i in range(total):
             j, k = divmod(i, bn)

@@ -5,6 +5,7 @@ import re
 import subprocess
 import sys
 import os
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -12,12 +13,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def listing(path=None):
     if path:
         return open(path).read()
-    out = '/tmp/invpref_step_dev.s'
-    subprocess.check_call(['/opt/rocm/bin/hipcc', '-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-ffp-contract=off',
-                           '-fno-fast-math', '-Wno-unused-function', '--cuda-device-only', '-S',
-                           os.path.join(ROOT, 'invpref_kdd_2022_amd', 'csrc', 'invpref_step.hip'), '-o', out],
-                          stderr=subprocess.DEVNULL)
-    return open(out).read()
+    with tempfile.TemporaryDirectory() as tmp:   # (a private directory: no fixed path shared between users or runs)
+        out = os.path.join(tmp, 'invpref_step_dev.s')
+        subprocess.check_call(['/opt/rocm/bin/hipcc', '-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-ffp-contract=off',
+                               '-fno-fast-math', '-Wno-unused-function', '--cuda-device-only', '-S',
+                               os.path.join(ROOT, 'invpref_kdd_2022_amd', 'csrc', 'invpref_step.hip'), '-o', out],
+                              stderr=subprocess.DEVNULL)
+        return open(out).read()
 
 
 def _deep_scratch_ops(code: str, min_depth: int = 2) -> int:
