@@ -236,6 +236,60 @@ def test_g11_random_sort_cluster_through_manager():
             assert [cnt[e] for e in range(E)] == np.bincount(z[key].astype(np.int64), minlength=E).tolist()
 
 
+@pytest.mark.parametrize('E,pinned', [(4, '1'), (4, '0'), (4, 'ahead'), (6, '1'), (9, '1')])
+def test_random_sort_estep_decides_saturated_ties_through_manager(monkeypatch, E, pinned):
+    """The managers' own E-step under the reference's default tie-break (cluster_use_random_sort=True) at the Yahoo table
+    shape, batch 8 192 and 700 001 interactions, a third of them saturated positives: every environment's distance of those
+    is exactly 0 after training too (c_sigmoid rounds to 1.0), so the permutation index the manager draws decides them.
+    Three rounds of one epoch + cluster_and_stat_envs(), each against the oracle on the tables read back from the manager with
+    the same numpy draws -- envs, counts, diff_num and class weights bit for bit.  E = 4 under every INVPREF_EPS_PINNED mode
+    (read per call), E = 6 (four-byte indices read from pinned memory), E = 9 (device indices, the unrank form)."""
+    import math
+    from estep_ties import PA, PU, QA, QI, EV, perm_rows
+    monkeypatch.setenv('INVPREF_EPS_PINNED', pinned)
+    U, I, D, N, bs = 15400, 1000, 64, 700001, 8192
+    rs = np.random.RandomState(60 + E)
+    data = synth.interactions(61 + E, U, I, N, implicit=True)
+    tabs = synth.tables(62 + E, U, I, E, D)
+    # the saturated positives: users and items of their own with one large coordinate (p >= 64, every q_e >= 640: far from
+    # what a few hundred Adam steps of lr 0.005 can move)
+    Ut, It = 500, 50
+    sat = rs.random_sample(N) < 1 / 3
+    data[sat, 0], data[sat, 1], data[sat, 2] = rs.randint(0, Ut, sat.sum()), rs.randint(0, It, sat.sum()), 1
+    for k, n in ((PU, Ut), (PA, Ut), (QI, It), (QA, It)):
+        tabs[k][:n] = 0.0
+        tabs[k][:n, 0] = rs.uniform(8.0, 10.0, n)
+    tabs[EV][:, 0] = 10.0 + 0.5 * np.arange(E)
+    model = InvPrefImplicit(U, I, E, D, reg_only_embed=True, reg_env_embed=False)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in tabs.items()})
+    np.random.seed(63 + E)
+    mgr = ImplicitTrainManager(model=model, evaluator=StubEvaluator(), device=DEV, training_data=torch.from_numpy(data).to(DEV),
+                               batch_size=bs, epochs=10 ** 9, cluster_interval=5, evaluate_interval=10 ** 9, lr=0.005,
+                               invariant_coe=3.35, env_aware_coe=9.99, env_coe=9.06, L2_coe=3.14, L1_coe=0.49, alpha=1.9,
+                               use_class_re_weight=True, use_recommend_re_weight=False)
+    assert mgr.cluster_use_random_sort and mgr._fused_estep_ok()
+    mgr.stat_envs()
+    for rnd in range(3):
+        mgr.train_epochs(1)
+        tab = O.Tables({k: p.detach().cpu().numpy() for k, p in zip(O.PARAM_NAMES, mgr.state.p_views)})
+        old = mgr.envs.cpu().numpy().copy()
+        st = np.random.get_state()
+        diff, cnt = mgr.cluster_and_stat_envs()
+        np.random.set_state(st)
+        idx = np.concatenate([np.random.randint(0, math.factorial(E), mgr.shard.global_batch_len(k))
+                              for k in range(mgr.batch_num)])
+        assert len(idx) == N
+        on, oc, od, _ = O.estep(tab, data[:, 0], data[:, 1], data[:, 2], True, old_envs=old,
+                                eps_rows=perm_rows(idx, mgr._eps_base))
+        _, ocw, _ = O.stat_envs(on, E)
+        np.testing.assert_array_equal(mgr.envs.cpu().numpy(), on, err_msg=f'round {rnd}')
+        assert [cnt[e] for e in range(E)] == oc.tolist() and diff == od, rnd
+        np.testing.assert_array_equal(mgr.class_weights.cpu().numpy(), ocw)
+        # the index decided the saturated rows: without it they all go to environment 0
+        plain = O.estep(tab, data[:, 0], data[:, 1], data[:, 2], True)[0]
+        assert (plain[sat] == 0).all() and (on != plain).mean() > 0.5 * (E - 1) / E / 3, rnd
+
+
 def test_g10_movielens_like_trajectory_through_manager():
     """MovieLens-class settings (E = 8, D = 128: the one-class-per-lane / branch-free classifier paths, two row chunks;
     alpha=None: the scheduled alpha read from the device-side schedule under graph replay) through the drop-in
