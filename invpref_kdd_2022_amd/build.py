@@ -53,11 +53,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_ingest(force, verbose)
     if force or needs_build():
         os.makedirs(OBJDIR, exist_ok=True)
-        extra = os.environ.get('INVPREF_HIPCC_EXTRA', '').split()
         procs, objs = [], []
         for src in SOURCES:  # one hipcc per translation unit, in parallel
             obj = os.path.join(OBJDIR, os.path.splitext(src)[0] + '.o')
-            cmd = [_hipcc()] + FLAGS + extra + ['-c', os.path.join(CSRC, src), '-o', obj]
+            cmd = [_hipcc()] + FLAGS + ['-c', os.path.join(CSRC, src), '-o', obj]
             if verbose:
                 print(' '.join(cmd))
             procs.append((cmd, subprocess.Popen(cmd)))

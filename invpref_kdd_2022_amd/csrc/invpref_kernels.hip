@@ -616,21 +616,16 @@ __global__ __launch_bounds__(256) void eps_unrank_kernel(const IT *__restrict__ 
 // table's base + one 32-bit offset (id x D in a 32-bit multiply) instead of a 64-bit product per gathered row; the ids
 // arrive as the reference's int64 (LongTensor) either way.
 // The stat_envs half of an E-step (train.py:268-280: counts, class weights; + cluster()'s diff_num, train.py:255) as the
-// EPILOGUE of the assignment kernel (invpref_estep_fused_hip): every workgroup publishes its count slab with
-// write-through stores, drains them and takes a ticket; the workgroup whose ticket is the last one folds all the slabs.  The
+// EPILOGUE of the assignment kernel (invpref_estep_fused_hip): every workgroup adds its counts into its
+// shard's counters, drains the adds and takes a ticket; the workgroup whose ticket is the last one folds the counters.  The
 // hand-off is the guide's measured form (MI355X_MICROARCH.md, inter-workgroup visibility, first row of the sc1 table): sc1
 // stores by ONE wave of the producer, its s_waitcnt vmcnt(0), an agent-scope atomic add by a lane of that wave, the adder
 // whose add came last reads everything with sc1 loads behind a workgroup barrier.
 // The ticket is SHARDED: 2 048 workgroups that finish together would queue on one word for ~25 us (one address takes ~88
 // returning atomics per microsecond); workgroup b takes a ticket of shard b % kTicketShards (each on a 128-byte line of its own),
 // the workgroup that completes a shard takes a ticket of the top word, the one that completes that folds.
-#ifndef ESTEP_IDX_BULK
-#define ESTEP_IDX_BULK 1
-#endif
-#ifndef ESTEP_SHARD_COUNTERS
-#define ESTEP_SHARD_COUNTERS 1   // the fused epilogue's counts: 1 = integer atomics into the shard's counters (round 6, late: the fused kernel
-                                 // 51.5 -> 42.2 us plain, 62.7 -> 51.7 with the tie-break, same box); 0 = a slab per workgroup, folded by the last one
-#endif
+// (the counts as integer atomics into the shard's counters rather than a slab per workgroup folded by the last one: round 6,
+//  late, the fused kernel 51.5 -> 42.2 us plain, 62.7 -> 51.7 with the tie-break, same box)
 constexpr int kTicketShards = 32;   // (INVPREF_ESTEP_STATE_INTS = 32 + 32 * kTicketShards)
 struct EstepFin {
     int *state;          // device int32[kEstepStateInts], ZERO before the first call and left zero: [0] top ticket, [1] ring
@@ -645,13 +640,12 @@ struct EstepFin {
 __device__ __forceinline__ int ld_sc1_i(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_sc1_i(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-#ifndef ESTEP_NUM_SGPR
-#define ESTEP_NUM_SGPR 80   // 256-thread workgroups per CU are also capped by the scalar registers: <= 80 -> 8, 82-96 -> 7, 98+ -> 6
-                            // (MI355X guide, residency); left alone the compiler takes 100 and a quarter of the 2 048 workgroups
-                            // of a Yahoo-sized E-step waits for a second residency
-#endif
+// 256-thread workgroups per CU are also capped by the scalar registers: <= 80 -> 8, 82-96 -> 7, 98+ -> 6 (MI355X guide,
+// residency); left alone the compiler takes 100 and a quarter of the 2 048 workgroups of a Yahoo-sized E-step waits for a
+// second residency
+constexpr int kEstepNumSgpr = 80;
 template <int NC, bool VEC, bool NARROW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(ESTEP_NUM_SGPR))) void estep_assign_kernel(DevTables t, const int64_t *__restrict__ users,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(kEstepNumSgpr))) void estep_assign_kernel(DevTables t, const int64_t *__restrict__ users,
                                                            const int64_t *__restrict__ items,
                                                            const float *__restrict__ scores, int64_t N, uint32_t flags,
                                                            const float *__restrict__ eps_rows,
@@ -711,11 +705,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(ESTEP_NUM_SGPR)
         eps_thr = mx * 67108864.f * 1.001f;
     }
     const int64_t s_first = s_begin + (threadIdx.x >> 4);
-    // One-byte indices (E <= 5, the managers' form), ESTEP_IDX_BULK: a WAVE fetches the bytes of its four groups for sixteen passes
+    // One-byte indices (E <= 5, the managers' form): a WAVE fetches the bytes of its four groups for sixteen passes
     // with ONE load -- lane 4 k + g holds the byte of group g in pass k: four 64-byte lines instead of sixteen requests of four
     // useful bytes each -- and a group picks its pass's byte out of the wave's registers (v_readlane: indifferent to lanes that
     // have left the loop).  From pinned host memory the kernel is bound by the NUMBER of link reads, not by their latency.
-    const bool idx_bulk = ESTEP_IDX_BULK && eps_index && eps_index_bytes == 1;
+    const bool idx_bulk = eps_index && eps_index_bytes == 1;
     const int lane64 = threadIdx.x & 63, grp_w = lane64 >> 4;
     auto load_bulk = [&](int blk) -> unsigned {
         const int64_t sx = s_begin + ((threadIdx.x >> 6) * 4 + (lane64 & 3)) + rows_per_block * ((int64_t)blk * 16 + (lane64 >> 2));
@@ -813,16 +807,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(ESTEP_NUM_SGPR)
     __shared__ int s_last;
     __shared__ long long s_tot[INVPREF_MAX_ENVS + 1];
     if (threadIdx.x < 64) {
-#if ESTEP_SHARD_COUNTERS
         // (the workgroup's counts are ADDED into its shard's counters, words 1 .. E + 1 of the shard's 128-byte line, in front of its ticket)
         if ((int)threadIdx.x <= t.E) {
             const int S0 = min(kTicketShards, (int)gridDim.x);
             __hip_atomic_fetch_add(fin.state + 32 + 32 * ((int)blockIdx.x % S0) + 1 + (int)threadIdx.x, cnt[threadIdx.x], __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
-#else
-        if ((int)threadIdx.x <= t.E) st_sc1_i(slabs + (int64_t)blockIdx.x * (t.E + 1) + threadIdx.x, cnt[threadIdx.x]);
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (threadIdx.x == 0) {
             const int S = min(kTicketShards, (int)gridDim.x), sh = (int)blockIdx.x % S;
@@ -841,18 +831,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(ESTEP_NUM_SGPR)
     if (!s_last) return;
     {
         const int E1 = t.E + 1, nsl = (int)gridDim.x;
-        // (write-through stores -> cache-bypassing loads.  The slabs are ONE contiguous int array [workgroups][E + 1]: thread t of
-        //  the first `per` = 256 - 256 % (E + 1) threads reads elements t, t + per, ... -- coalesced, and all of ONE class, t %
-        //  (E + 1) -- twenty loads in flight, one accumulator; then one LDS atomic per thread.  The fold runs in one workgroup per
-        //  launch but its registers are every workgroup's: with 17 per-thread 64-bit accumulators the Yahoo instance went from
-        //  57 to 74 registers, 8 -> 6 waves per SIMD; every thread adding every count through LDS atomics on the same five words
-        //  took 138 us; one class at a time (a round trip each) 53 us)
-        const int per = (int)blockDim.x - (int)blockDim.x % E1, total = nsl * E1;
-#if ESTEP_SHARD_COUNTERS
         // (every workgroup has ADDED its counts to its shard's counters -- integer atomics: order-free, exact -- in front of its
-        //  ticket: shards x (E + 1) words, ONE round trip of cache-bypassing loads, instead of every workgroup's slab in passes of
-        //  twenty loads.  The words go back to zero for the next launch)
-        (void)per; (void)total;
+        //  ticket: shards x (E + 1) words, ONE round trip of cache-bypassing loads.  The words go back to zero for the next
+        //  launch.  The slab fold this replaced: git history)
         const int S0 = min(kTicketShards, nsl);
         for (int i = threadIdx.x; i < S0 * E1; i += blockDim.x) {
             int *w = fin.state + 32 + 32 * (i / E1) + 1 + i % E1;
@@ -860,22 +841,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(ESTEP_NUM_SGPR)
             st_sc1_i(w, 0);
             atomicAdd((unsigned long long *)&s_tot[i % E1], (unsigned long long)(long long)x);
         }
-#else
-        if ((int)threadIdx.x < per) {
-            long long a = 0;
-            for (int i0 = threadIdx.x; i0 < total; i0 += 20 * per) {
-                int x[20];
-#pragma unroll
-                for (int k = 0; k < 20; k++) {
-                    const int i = i0 + k * per;
-                    x[k] = i < total ? ld_sc1_i(slabs + i) : 0;
-                }
-#pragma unroll
-                for (int k = 0; k < 20; k++) a += x[k];
-            }
-            atomicAdd((unsigned long long *)&s_tot[(int)threadIdx.x % E1], (unsigned long long)a);
-        }
-#endif
         __syncthreads();
         int64_t *row = nullptr;
         if (fin.ring) row = fin.ring + (int64_t)((unsigned)fin.state[1] % (unsigned)fin.ring_cap) * E1;
@@ -966,7 +931,7 @@ __global__ __launch_bounds__(256) void stat_envs_kernel(const int64_t *__restric
     }
 }
 
-// The same fold as estep_assign_kernel's epilogue, as ONE workgroup of its own behind the assignment kernel (INVPREF_ESTEP_FOLD=kernel:
+// estep_assign_kernel's epilogue as ONE workgroup of its own behind the assignment kernel, from a slab per workgroup (INVPREF_ESTEP_FOLD=kernel:
 // a kernel boundary + two round trips of one workgroup, against the epilogue's chain of store drain -> shard ticket -> top
 // ticket -> fold on the assignment kernel's own tail; measured per E-step in profiles/r06).
 __global__ __launch_bounds__(256) void estep_fold_kernel(const int *__restrict__ slabs, int nslabs, int E, int64_t N, EstepFin fin) {
@@ -974,6 +939,10 @@ __global__ __launch_bounds__(256) void estep_fold_kernel(const int *__restrict__
     const int E1 = E + 1, total = nslabs * E1;
     for (int i = threadIdx.x; i <= E; i += blockDim.x) s_tot[i] = 0;
     __syncthreads();
+    // (the slabs are ONE contiguous int array [workgroups][E + 1]: thread t of the first `per` = 256 - 256 % (E + 1) threads
+    //  reads elements t, t + per, ... -- coalesced, and all of ONE class, t % (E + 1) -- twenty loads in flight, one
+    //  accumulator; then one LDS atomic per thread.  Every thread adding every count through LDS atomics on the same five
+    //  words took 138 us; one class at a time (a round trip each) 53 us)
     const int per = (int)blockDim.x - (int)blockDim.x % E1;
     if ((int)threadIdx.x < per) {
         long long a = 0;

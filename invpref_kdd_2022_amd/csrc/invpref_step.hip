@@ -220,9 +220,6 @@ __device__ __forceinline__ void store4(float *dst, float4 r) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(val) : "memory");
 }
 
-#ifndef STEP_PUSH_ST
-#define STEP_PUSH_ST 0   // (A/B knob, two-launch forms: 1 = launch 1's contribution rows leave as write-through stores)
-#endif
 __device__ __forceinline__ void adam4(float4 &p, float4 g, float4 &m, float4 &v, const AdamScalars &ad) {
     adam1f(p.x, g.x, m.x, v.x, ad); adam1f(p.y, g.y, m.y, v.y, ad);
     adam1f(p.z, g.z, m.z, v.z, ad); adam1f(p.w, g.w, m.w, v.w, ad);
@@ -274,33 +271,16 @@ struct StepArgs {
         }                                                                         \
     } while (0)
 
-// (which round of a task the per-round stamps 2 .. 5 describe: 0 = its first -- table staging included --, diagnostic builds
-//  pass -DSTAMP_ROUND_OFFSET=k for a steady-state round)
-#ifndef STAMP_ROUND_OFFSET
-#define STAMP_ROUND_OFFSET 0
-#endif
-#define STAMP_ROUND (STAMP_ROUND_OFFSET < nr ? STAMP_ROUND_OFFSET : nr - 1)
-#ifndef STEP_SLOT_ALIAS
-#define STEP_SLOT_ALIAS 1
-#endif
-#ifndef STEP_CLS_QUADS
-#define STEP_CLS_QUADS 0   // the four-class classifier of the 16-lane kernels with one class per QUAD of the group (see eval_interaction)
-#endif
-#ifndef STEP_LDS_DW
-#define STEP_LDS_DW 1   // (A/B knob: smallest instance, classifier partial sums accumulated in LDS rows too)
-#endif
-#ifndef STEP_NO_DMA
-#define STEP_NO_DMA 0   // (A/B knob: the smallest instance without the LDS-DMA landing area: 44 KB, three workgroups per CU)
-#endif
-#ifndef STEP_REG_EMAX
-#define STEP_REG_EMAX 8   // (A/B knob: the largest class count whose E x D partial sums live in registers)
-#endif
+// which round of a task the per-round stamps 2 .. 5 describe: its first, table staging included.  (The plain r == r0 is
+// not the same to the compiler: it moves the scalar-register allocation of every instance.)
+#define STAMP_ROUND (0 < nr ? 0 : nr - 1)
+
 template <int LG, int EMAX>
 struct Geo {
     static constexpr int NG = kThreads / LG;          // groups (rows in flight) per workgroup
     static constexpr int DP = 4 * LG;                 // padded row length
     static constexpr int RS = 4 + EMAX;               // floats per record: g_p, g_q, env bits, 0, gz[EMAX]
-    static constexpr bool REG = EMAX <= STEP_REG_EMAX;   // E x D partial sums in registers (else: LDS records)
+    static constexpr bool REG = EMAX <= 8;            // E x D partial sums in registers (else: LDS records)
     static constexpr int SLAB = 2 * EMAX * DP + EMAX + kLossSlots;   // dEv | dW | db | loss sums
     // the workgroup's partial sums meet in LDS as RED rows of SLAB floats: one per GROUP for the smallest instance (plain
     // stores, no lane exchanges: the 72 permlane + add pairs of a per-wave pre-reduction sat on the step's critical
@@ -322,39 +302,31 @@ struct EvalLds {
     // slice partials [NG][2][DP]: an area of their own, or (ALIAS) inside the LDS-DMA landing area of the group's OWN wave
     // -- the leader takes the row's moments out of it first, same wave, program order -- which is what lets three
     // workgroups of the smallest instance share a CU's 160 KB
-    static constexpr bool ALIAS = G::REG && STEP_SLOT_ALIAS;
+    static constexpr bool ALIAS = G::REG;
     static constexpr int scw = sb + EMAX;                           // [EMAX] class weights (INVPREF_WEIGHTS_BY_ENV; else ones)
     static constexpr int slots = scw + EMAX;
     static constexpr int mv = slots + (ALIAS ? 0 : G::NG * 2 * G::DP);   // [4 waves][4][64] float4 LDS-DMA landing area
-    static constexpr int red = mv + (STEP_NO_DMA && G::DIRECT ? 0 : kWaves * 4 * 64 * 4);            // REG: [4 waves][SLAB]; else [4 waves][8] loss sums
+    static constexpr int red = mv + kWaves * 4 * 64 * 4;            // REG: [4 waves][SLAB]; else [4 waves][8] loss sums
     static constexpr int rec = red + (G::REG ? G::RED * G::SLAB : kWaves * kLossSlots);   // E > 8: [2][NG][2][DP] x, o
     static constexpr int recs = rec + (G::REG ? 0 : 2 * G::NG * 2 * G::DP);              // E > 4: [2][NG][EMAX + 4] gz, env
     static constexpr int total = recs + (EMAX <= 4 ? 0 : 2 * G::NG * (EMAX + 4));
 };
 
 // ---- forward + analytic backward of ONE interaction on a lane group (M-step arithmetic: hardware exp/log/rcp).
-template <int LG, int EMAX>
-constexpr bool kClsQuads = LG == 16 && EMAX == 4 && STEP_CLS_QUADS;
 template <int EMAX>
 struct Eval {
     float g_p, g_q, li, le, lcls;
-    float gz[EMAX <= 4 ? EMAX : 1];   // E <= 4: every lane holds all classes -- gz[c] of class c, or (STEP_CLS_QUADS, kClsQuads) gz[j] of
-                                      // class (lg >> 2) ^ j: the lanes of quad 0 hold them in class order; lcls is then non-zero in
-                                      // the quad of the interaction's environment only
+    float gz[EMAX <= 4 ? EMAX : 1];   // E <= 4: every lane holds all classes -- gz[c] of class c
     float gz_lane;                    // E > 4: lane lg of the group holds class lg (0 beyond E)
     float4 x, gx;                     // x = Pu*Qi ; gx = sum_c gz_c W_c
 };
-// KIND -1: implicit / PureMF decided at run time (workgroup-uniform branches); 0 / 1: explicit / implicit InvPref fixed at
-// compile time -- the body is then ONE basic block, so that two calls in a row can be interleaved by the scheduler (the
-// paired evaluation of csrc/step_alt.hpp)
-template <int LG, int EMAX, int KIND = -1>
+// implicit / PureMF: workgroup-uniform run-time branches (fixed at compile time: no gain, profiles/r06/EXPERIMENTS.md)
+template <int LG, int EMAX>
 __device__ __forceinline__ void eval_interaction(Eval<EMAX> &o, float4 pu, float4 qi, float4 pa, float4 qa, float4 ev,
                                                  const float *sW, const float *sb, float *gzs, int E, int e, float y,
-                                                 float cw_rec, float cw_cls, const StepScalars &k, bool implicit_rt,
-                                                 bool pure_rt, int lg) {
+                                                 float cw_rec, float cw_cls, const StepScalars &k, bool implicit, bool pure,
+                                                 int lg) {
     constexpr int DP = 4 * LG;
-    const bool implicit = KIND < 0 ? implicit_rt : (KIND == 1);
-    const bool pure = KIND < 0 ? pure_rt : false;
     o.x = f4mul(pu, qi);
     const float p = group_sum<LG>((o.x.x + o.x.y) + (o.x.z + o.x.w));
     const float q = group_sum<LG>(dot4(f4mul(pa, qa), ev));
@@ -363,10 +335,7 @@ __device__ __forceinline__ void eval_interaction(Eval<EMAX> &o, float4 pu, float
         // (labels exactly 0 or 1 -- the implicit data, train.py:130-135 -- need one logarithm per loss; wave-uniform test)
         o.li = f_bce_binary(sp, y);
         o.le = f_bce_binary(sv, y);
-#ifndef STEP_ASSUME_BINARY
-#define STEP_ASSUME_BINARY 0   // (what-if knob, WRONG for labels other than 0 / 1)
-#endif
-        if (!STEP_ASSUME_BINARY && __builtin_amdgcn_ballot_w64(!(y == 0.0f || y == 1.0f)) != 0) {   // (never with the reference's implicit data)
+        if (__builtin_amdgcn_ballot_w64(!(y == 0.0f || y == 1.0f)) != 0) {   // (never with the reference's implicit data)
             o.li = f_bce(sp, y);
             o.le = f_bce(sv, y);
         }
@@ -390,45 +359,7 @@ __device__ __forceinline__ void eval_interaction(Eval<EMAX> &o, float4 pu, float
         for (int c = 0; c < (EMAX <= 4 ? EMAX : 1); c++) o.gz[c] = 0.f;
     }
     if (pure) return;   // PureMF: no classifier
-    if constexpr (LG == 16 && EMAX == 4 && STEP_CLS_QUADS) {
-        // One class per QUAD of the 16-lane group.  The four partial dot products are reduce-scattered over the quads -- step 1
-        // with the quad q ^ 1 (row_half_mirror), step 2 with q ^ 2 (row_ror:8): three exchanged values instead of four full
-        // butterflies -- and summed inside the quad; quad q then holds logit q in all four lanes.  Max and sum of the softmax
-        // are two exchanges each over the same partners (every lane ends with the same bits: fp addition commutes and the
-        // association (e_q + e_q^1) + (e_q^2 + e_q^3) is the same set of pairs in every quad); ONE exponential, reciprocal and
-        // logarithm per lane instead of four + 1 + 1.  The class gradients come back by three moves: gz[j] = class q ^ j.
-        const int qd = lg >> 2;
-        float d[4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) d[c] = dot4(o.x, *reinterpret_cast<const float4 *>(sW + c * DP + lg * 4));
-        const bool odd = qd & 1, hi = qd & 2;
-        float ka = odd ? d[1] : d[0], kb = odd ? d[3] : d[2];
-        const float ga = odd ? d[0] : d[1], gb = odd ? d[2] : d[3];
-        ka += dpp_move<0x141>(ga);
-        kb += dpp_move<0x141>(gb);
-        float zq = hi ? kb : ka;
-        const float gq = hi ? ka : kb;
-        zq += dpp_move<0x128>(gq);
-        zq += dpp_move<0xB1>(zq);
-        zq += dpp_move<0x4E>(zq);
-        zq = qd < E ? zq + sb[qd] : -__builtin_inff();
-        float mx = __builtin_fmaxf(zq, dpp_move<0x141>(zq));
-        mx = __builtin_fmaxf(mx, dpp_move<0x128>(mx));
-        const float dz = zq - mx;
-        const float ez = f_exp(dz);   // exp(-inf) = 0
-        float se = ez + dpp_move<0x141>(ez);
-        se += dpp_move<0x128>(se);
-        const float rse = f_rcp(se);
-        // NLL of log_softmax as the reference forms it (see below); the quad of the interaction's environment reports it
-        o.lcls = qd == e ? f_log(se) - dz : 0.f;
-        const float g0 = qd < E ? k.cc * cw_cls * (ez * rse - (qd == e ? 1.f : 0.f)) : 0.f;
-        const float g1 = dpp_move<0x141>(g0), g2 = dpp_move<0x128>(g0), g3 = dpp_move<0x128>(g1);
-        o.gz[0] = g0; o.gz[1] = g1; o.gz[2] = g2; o.gz[3] = g3;
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            f4fma(o.gx, o.gz[j], *reinterpret_cast<const float4 *>(sW + ((qd ^ j) * DP + lg * 4)));
-        return;
-    }
+    // (one class per QUAD of the 16-lane group instead: 10 % fewer instructions, no gain -- profiles/r06/EXPERIMENTS.md)
     if (EMAX <= 4) {
         // the W rows are read from LDS ONCE, unconditionally and back to back (rows c >= E are staged as zeros);
         // everything after is selects and arithmetic
@@ -471,37 +402,12 @@ __device__ __forceinline__ void stage_small(float *dst, const float *__restrict_
     }
 }
 
-// A task's FIRST descriptors through the scalar cache (A/B knob STEP_SCALAR_DESC): the wave's group slots are adjacent,
-// so their descriptors are one or two scalar loads; each lane then picks its group's words.  The scalar path is not
-// queued behind the launch's vector load burst.  (Plans are written once, before any launch reads them: the scalar
-// cache's lack of coherence with vector stores does not matter here.)
-#ifndef STEP_SCALAR_DESC
-#define STEP_SCALAR_DESC 0
-#endif
+// a task's FIRST descriptors (through the scalar cache instead: measured, no gain -- git history)
 template <int LG>
 __device__ __forceinline__ void first_desc(const int4 *desc, int r0, int grp, int4 &d, int4 &d1) {
-    constexpr int NG = kThreads / LG, GW = 64 / LG;   // groups per wave
-    if (!STEP_SCALAR_DESC) {
-        d = desc[(r0 * NG + grp) * 2];
-        d1 = desc[(r0 * NG + grp) * 2 + 1];
-        return;
-    }
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    typedef const __attribute__((address_space(4))) v4i *cptr;
-    const int wave = threadIdx.x >> 6, gw = (threadIdx.x & 63) / LG;
-    const int base = __builtin_amdgcn_readfirstlane((r0 * NG + wave * GW) * 2);
-    cptr sd = (cptr)(uintptr_t)desc;
-    v4i s[2 * GW];
-#pragma unroll
-    for (int i = 0; i < 2 * GW; i++) s[i] = sd[base + i];
-    d = make_int4(s[0].x, s[0].y, s[0].z, s[0].w); d1 = make_int4(s[1].x, s[1].y, s[1].z, s[1].w);
-#pragma unroll
-    for (int g = 1; g < GW; g++) {
-        const bool me = gw == g;
-        d.x = me ? s[2 * g].x : d.x; d.y = me ? s[2 * g].y : d.y; d.z = me ? s[2 * g].z : d.z; d.w = me ? s[2 * g].w : d.w;
-        d1.x = me ? s[2 * g + 1].x : d1.x; d1.y = me ? s[2 * g + 1].y : d1.y;
-        d1.z = me ? s[2 * g + 1].z : d1.z; d1.w = me ? s[2 * g + 1].w : d1.w;
-    }
+    constexpr int NG = kThreads / LG;
+    d = desc[(r0 * NG + grp) * 2];
+    d1 = desc[(r0 * NG + grp) * 2 + 1];
 }
 
 struct USample {
@@ -513,30 +419,20 @@ struct USample {
 // launch 1: rounds of USER jobs.  Per interaction: gather the item rows, evaluate, accumulate the user rows'
 // gradients in registers, store the record for the item side, accumulate the E x D / loss sums.
 // =====================================================================================
-#ifndef STEP_STAGE_LATE
-#define STEP_STAGE_LATE 1   // (A/B knob, FULL instances: the small tables staged behind the first gathers)
-#endif
-#ifndef STEP_EVAL_DEPTH
-#define STEP_EVAL_DEPTH 3
-#endif
-#ifndef STEP_SLOT_FROM_LIST
-#define STEP_SLOT_FROM_LIST 1   // launch 1 takes an interaction's slot from its list entry (0: always from rec_slot[position], a random read)
-#endif
-#ifndef STEP_ROW_ST
-#define STEP_ROW_ST 1   // write-through stores for the rows the two-launch jobs finish (p', m', v': nothing of them is read again before
-                        // the next step; left dirty in L2 they lengthen the kernel boundary).  Round 6, same box: 2^24 interactions at
-                        // D = 64 4.95 -> 4.59 ms (0.487 -> 0.524), Yahoo B = N 92.2 -> 90.7 us, MovieLens- / MIND-shaped level (0: plain)
-#endif
+// write-through stores (put4 MODE 1) for the rows the two-launch jobs finish (p', m', v': nothing of them is read again before
+// the next step; left dirty in L2 they lengthen the kernel boundary).  Round 6, same box: 2^24 interactions at D = 64
+// 4.95 -> 4.59 ms (0.487 -> 0.524), Yahoo B = N 92.2 -> 90.7 us, MovieLens- / MIND-shaped level (0: plain)
+constexpr int kRowSt = 1;
 template <int LG, bool VEC, int EMAX, bool FULL>
 __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a, int r0, int nr, int slab_index, float *lds) {
     using G = Geo<LG, EMAX>;
     // (rows of more than 64 floats and more than four environments run step_wide.hpp; the branches of this function for
     //  other layouts are compile-time dead)
     static_assert(LG == 16 && EMAX == 4, "user_task: the 16-lane, four-environment instances only");
-    static_assert(!kClsQuads<LG, EMAX> || (G::DIRECT && STEP_LDS_DW), "class-per-quad gradients need the classifier's LDS rows");
     // interactions in flight per group (measured: 2 for the D <= 64, E <= 4 instances -- a third slot only costs registers
     // there -- and for E > 8, whose per-interaction barrier paces the groups anyway; 3 for the other larger rows)
-    constexpr int UE = !G::REG ? 1 : ((LG == 16 && EMAX <= 4 && STEP_EVAL_DEPTH > 2) ? 2 : STEP_EVAL_DEPTH);
+    constexpr int kStepEvalDepth = 3;
+    constexpr int UE = !G::REG ? 1 : ((LG == 16 && EMAX <= 4) ? 2 : kStepEvalDepth);
     using L = EvalLds<LG, EMAX>;
     constexpr int NG = G::NG, DP = G::DP, RS = G::RS;
     float *sEv = lds + L::sEv, *sW = lds + L::sW, *sb = lds + L::sb, *scw = lds + L::scw, *slots = lds + L::slots;
@@ -550,7 +446,7 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
     const bool reg_env = a.flags & INVPREF_REG_ENV_EMBED;
     const bool pure = a.flags & INVPREF_PURE_MF;   // env-aware tables, embed_env, classifier absent: never touched
     // (E > 8: the LDS-DMA landing area holds the embed_env partial sums instead; the moments are loaded late)
-    const bool dma = VEC && a.fused && G::REG && !(STEP_NO_DMA && G::DIRECT);
+    const bool dma = VEC && a.fused && G::REG;
     const bool push = a.push_slot != nullptr;
     float *sdE = lds + L::mv;   // E > 8: [EMAX][DP] embed_env partial sums of the workgroup, rows indexed by the environment
     StepScalars k = a.k;
@@ -564,7 +460,7 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
     // the first round's descriptor goes out before anything else: every gather below hangs on it
     int4 d, d1;
     first_desc<LG>(a.desc, r0, grp, d, d1);
-    if (!STEP_STAGE_LATE || !FULL) {
+    if (!FULL) {   // (FULL instances stage them behind the first gathers, below)
         stage_small(sEv, t.Ev, t.E, t.D, EMAX, DP);
         stage_small(sW, t.W, t.E, t.D, EMAX, DP);
         if (threadIdx.x < EMAX) sb[threadIdx.x] = (threadIdx.x < t.E && t.b) ? t.b[threadIdx.x] : 0.f;
@@ -574,9 +470,9 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
     if (!G::REG)
         for (int i = threadIdx.x; i < EMAX * DP; i += kThreads) sdE[i] = 0.f;
     else {
-        // embed_env's partial sums -- in the smallest instance the classifier's too (STEP_LDS_DW) -- are accumulated IN
-        // the rows the workgroup's partial sums meet in (below)
-        constexpr int ZR = (G::DIRECT && STEP_LDS_DW) ? 2 * EMAX * DP + EMAX : EMAX * DP;
+        // embed_env's partial sums -- in the smallest instance the classifier's too -- are accumulated IN the rows the
+        // workgroup's partial sums meet in (below)
+        constexpr int ZR = G::DIRECT ? 2 * EMAX * DP + EMAX : EMAX * DP;
         for (int i = threadIdx.x; i < G::RED * ZR; i += kThreads) red[(i / ZR) * G::SLAB + i % ZR] = 0.f;
     }
     STAMP(1);
@@ -653,7 +549,7 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
                 // -- one load from a selected address again
                 const int *sp = mode == 7 ? reinterpret_cast<const int *>(a.ulist + min(s_lo + sidx, s_hi1)) + 3
                                           : reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.rec_slot) + pso * 4u);
-                q.cs = STEP_SLOT_FROM_LIST ? *sp : *reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.rec_slot) + pso * 4u);
+                q.cs = *sp;
                 return;
             }
             if (!pure) {
@@ -702,7 +598,6 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
             for (int j = 0; j < UE; j++)
                 if (UE + j < nsmp) idn[j] = sample_at(UE + j);
         }
-#ifndef STEP_DMA_LATE
         if (dma) {
             // each lane sends its 16-byte piece of the row's four moment rows straight to LDS; the destination of a
             // wave instruction is one contiguous 1 KiB block, lane-major
@@ -716,9 +611,8 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
                         (__attribute__((address_space(3))) void *)(mv_wave + tn * 64), 16, 0, 0);
             }
         }
-#endif
         if (r == r0) {
-            if (STEP_STAGE_LATE && FULL) {
+            if (FULL) {
                 // the two small tables are staged HERE, behind the first round's gathers: their load -> LDS-store loop in
                 // front of the descriptor's use put a round trip of its own ahead of the gathers
                 stage_small(sEv, t.Ev, t.E, t.D, EMAX, DP);
@@ -751,8 +645,8 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
                     // push form: the interaction's two contribution rows to its ITEM's gradient, stored at the item-sorted
                     // slot -- launch 2 then sums contiguous rows, no gathers, no classifier
                     float *cr = a.records + (unsigned)q.cs * (unsigned)(2 * DP) + lg * 4;
-                    store4<STEP_PUSH_ST>(cr, f4mul(gip, oi));
-                    store4<STEP_PUSH_ST>(cr + DP, f4scale(o.g_q, f4mul(oe, ev)));
+                    store4<0>(cr, f4mul(gip, oi));
+                    store4<0>(cr + DP, f4scale(o.g_q, f4mul(oe, ev)));
                 } else {
                     // pull form: the record the item side consumes, at the interaction's slot in the item order
                     float *rec_g = a.records + (unsigned)q.cs * (unsigned)RS;
@@ -782,14 +676,12 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
                             gzv[G::REG ? c4 + 2 : 0] = g4.z; gzv[G::REG ? c4 + 3 : 0] = g4.w;
                         }
                     }
-#ifndef DBG_NO_EXD
-                    if (G::DIRECT && STEP_LDS_DW) {
+                    if (G::DIRECT) {
                         // the classifier's partial sums as well: a read-modify-write of the group's own rows
                         float *mine = red + grp * G::SLAB;
 #pragma unroll
                         for (int c = 0; c < (G::REG ? EMAX : 1); c++) {
-                            // (kClsQuads: gzv[c] belongs to class (lg >> 2) ^ c -- every lane still visits all four rows)
-                            float4 *wr = reinterpret_cast<float4 *>(mine + EMAX * DP + (kClsQuads<LG, EMAX> ? ((lg >> 2) ^ c) : c) * DP + lg * 4);
+                            float4 *wr = reinterpret_cast<float4 *>(mine + EMAX * DP + c * DP + lg * 4);
                             float4 cur = *wr;
                             f4fma(cur, gzv[c], o.x);
                             *wr = cur;
@@ -814,7 +706,6 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
                     float4 cur = *erow;
                     f4add(cur, oo);
                     *erow = cur;
-#endif
                 }
                 // regulariser REPORTS over the item rows of the interaction (env rows weigh double: 1/(BD) vs 1/(2BD))
                 // (two fma chains for the squares, one |x| add chain for the magnitudes: 16 instructions instead of 28)
@@ -826,27 +717,10 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
                 accL2 += s2;
                 accL1 += s1;
                 if (lg == 0) { accLi += o.li * w_rec; accLe += o.le * w_rec; }
-                if (kClsQuads<LG, EMAX> ? (lg & 3) == 0 : lg == 0) accLc += o.lcls * w_cls;
+                if (lg == 0) accLc += o.lcls * w_cls;
             }
             if (EMAX > 4) it_total++;
         };
-#ifdef STEP_DMA_LATE
-        // (A/B knob: the moments are requested behind the first gathers' burst instead of inside it)
-        __builtin_amdgcn_sched_barrier(0);
-        if (dma) {
-            // each lane sends its 16-byte piece of the row's four moment rows straight to LDS; the destination of a
-            // wave instruction is one contiguous 1 KiB block, lane-major
-            const bool mine = active && leader && lg * 4 < t.D;
-#pragma unroll
-            for (int tn = 0; tn < 4; tn++) {
-                const float *src_tab = (tn & 1) ? a.v[(tn >> 1) * 2] : a.m[(tn >> 1) * 2];
-                if (mine && !(pure && tn >= 2))
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) void *)(src_tab + ((unsigned)row * (unsigned)t.D + (unsigned)lg * 4u)),
-                        (__attribute__((address_space(3))) void *)(mv_wave + tn * 64), 16, 0, 0);
-            }
-        }
-#endif
         for (int s = 0; s < iters; s += UE) {
 #pragma unroll
             for (int j = 0; j < UE; j++) {
@@ -872,12 +746,7 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
                 // one row per group: every lane stores its own pieces, nothing is exchanged
                 accLi = row16_sum(accLi); accLe = row16_sum(accLe); accLc = row16_sum(accLc);
                 accL2 = row16_sum(accL2); accL1 = row16_sum(accL1);
-                float *mine = red + grp * G::SLAB;
-#pragma unroll
-                for (int c = 0; c < ((G::REG && !STEP_LDS_DW) ? EMAX : 0); c++) {   // (the embed_env rows are there already)
-                    *reinterpret_cast<float4 *>(mine + EMAX * DP + c * DP + lg * 4) = dW[G::REG ? c : 0];
-                    if (lg == 0) mine[2 * EMAX * DP + c] = dB[G::REG ? c : 0];
-                }
+                float *mine = red + grp * G::SLAB;   // (its embed_env and classifier rows are there already)
                 if (lg == 0) {
                     float *ls = mine + 2 * EMAX * DP + EMAX;
                     ls[0] = accLi; ls[1] = accLe; ls[2] = accLc; ls[3] = accL2; ls[4] = accL1; ls[5] = ls[6] = ls[7] = 0.f;
@@ -995,14 +864,14 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
                     if (!pure) { me = row4<VEC, FULL>(a.m[2], row, t.D, lg); ve = row4<VEC, FULL>(a.v[2], row, t.D, lg); }
                 }
                 adam4(oi, gi, mi, vi, ad);
-                put4<VEC, STEP_ROW_ST, FULL>(a.np[0], row, t.D, lg, oi);
-                put4<VEC, STEP_ROW_ST, FULL>(a.m[0], row, t.D, lg, mi);
-                put4<VEC, STEP_ROW_ST, FULL>(a.v[0], row, t.D, lg, vi);
+                put4<VEC, kRowSt, FULL>(a.np[0], row, t.D, lg, oi);
+                put4<VEC, kRowSt, FULL>(a.m[0], row, t.D, lg, mi);
+                put4<VEC, kRowSt, FULL>(a.v[0], row, t.D, lg, vi);
                 if (!pure) {
                     adam4(oe, ge, me, ve, ad);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.np[2], row, t.D, lg, oe);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.m[2], row, t.D, lg, me);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.v[2], row, t.D, lg, ve);
+                    put4<VEC, kRowSt, FULL>(a.np[2], row, t.D, lg, oe);
+                    put4<VEC, kRowSt, FULL>(a.m[2], row, t.D, lg, me);
+                    put4<VEC, kRowSt, FULL>(a.v[2], row, t.D, lg, ve);
                 }
             }
         }
@@ -1017,16 +886,10 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
 struct IIn {
     float4 pu, pa, r0;
 };
-#ifndef STEP_PUSH_DEPTH
-#define STEP_PUSH_DEPTH 4
-#endif
-#ifndef STEP_ITEM_DEPTH
-#define STEP_ITEM_DEPTH 2
-#endif
 template <int LG, bool VEC, int EMAX, bool FULL>
 __device__ __forceinline__ void item_task(const DevTables &t, const StepArgs &a, int r0, int nr, float *lds) {
     using G = Geo<LG, EMAX>;
-    constexpr int U = EMAX <= 4 ? STEP_ITEM_DEPTH : 2;   // interactions in flight per group
+    constexpr int U = 2;   // interactions in flight per group
     constexpr int DP = G::DP, RS = G::RS, NG = G::NG;
     float *sEv = lds, *sW = sEv + EMAX * DP, *slots = sW + EMAX * DP;   // [EMAX][DP] x 2, [NG][2][DP]
     float4 *mv = reinterpret_cast<float4 *>(slots + NG * 2 * DP);       // [4 waves][4][64] float4 LDS-DMA landing area
@@ -1170,14 +1033,14 @@ __device__ __forceinline__ void item_task(const DevTables &t, const StepArgs &a,
                     if (!pure) { me = row4<VEC, FULL>(a.m[3], row, t.D, lg); ve = row4<VEC, FULL>(a.v[3], row, t.D, lg); }
                 }
                 adam4(oi, gi, mi, vi, ad);
-                put4<VEC, STEP_ROW_ST, FULL>(a.np[1], row, t.D, lg, oi);
-                put4<VEC, STEP_ROW_ST, FULL>(a.m[1], row, t.D, lg, mi);
-                put4<VEC, STEP_ROW_ST, FULL>(a.v[1], row, t.D, lg, vi);
+                put4<VEC, kRowSt, FULL>(a.np[1], row, t.D, lg, oi);
+                put4<VEC, kRowSt, FULL>(a.m[1], row, t.D, lg, mi);
+                put4<VEC, kRowSt, FULL>(a.v[1], row, t.D, lg, vi);
                 if (!pure) {
                     adam4(oe, ge, me, ve, ad);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.np[3], row, t.D, lg, oe);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.m[3], row, t.D, lg, me);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.v[3], row, t.D, lg, ve);
+                    put4<VEC, kRowSt, FULL>(a.np[3], row, t.D, lg, oe);
+                    put4<VEC, kRowSt, FULL>(a.m[3], row, t.D, lg, me);
+                    put4<VEC, kRowSt, FULL>(a.v[3], row, t.D, lg, ve);
                 }
             }
         }
@@ -1193,7 +1056,7 @@ template <int LG, bool VEC, int EMAX, bool FULL>
 __device__ __forceinline__ void item_task_push(const DevTables &t, const StepArgs &a, int r0, int nr, float *lds) {
     using G = Geo<LG, EMAX>;
     constexpr int DP = G::DP, NG = G::NG;
-    constexpr int PCH = LG == 16 ? STEP_PUSH_DEPTH : 3;   // contribution-row pairs in flight per group
+    constexpr int PCH = LG == 16 ? 4 : 3;   // contribution-row pairs in flight per group
     float *slots = lds;                                                  // [NG][2][DP] slice partials
     float4 *mv = reinterpret_cast<float4 *>(slots + NG * 2 * DP);       // [4 waves][4][64] float4 LDS-DMA landing area
     const int lg = threadIdx.x & (LG - 1), grp = threadIdx.x / LG, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1306,14 +1169,14 @@ __device__ __forceinline__ void item_task_push(const DevTables &t, const StepArg
                     if (!pure) { me = row4<VEC, FULL>(a.m[3], row, t.D, lg); ve = row4<VEC, FULL>(a.v[3], row, t.D, lg); }
                 }
                 adam4(oi, gi, mi, vi, ad);
-                put4<VEC, STEP_ROW_ST, FULL>(a.np[1], row, t.D, lg, oi);
-                put4<VEC, STEP_ROW_ST, FULL>(a.m[1], row, t.D, lg, mi);
-                put4<VEC, STEP_ROW_ST, FULL>(a.v[1], row, t.D, lg, vi);
+                put4<VEC, kRowSt, FULL>(a.np[1], row, t.D, lg, oi);
+                put4<VEC, kRowSt, FULL>(a.m[1], row, t.D, lg, mi);
+                put4<VEC, kRowSt, FULL>(a.v[1], row, t.D, lg, vi);
                 if (!pure) {
                     adam4(oe, ge, me, ve, ad);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.np[3], row, t.D, lg, oe);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.m[3], row, t.D, lg, me);
-                    put4<VEC, STEP_ROW_ST, FULL>(a.v[3], row, t.D, lg, ve);
+                    put4<VEC, kRowSt, FULL>(a.np[3], row, t.D, lg, oe);
+                    put4<VEC, kRowSt, FULL>(a.m[3], row, t.D, lg, me);
+                    put4<VEC, kRowSt, FULL>(a.v[3], row, t.D, lg, ve);
                 }
             }
         }
@@ -1328,20 +1191,13 @@ __device__ __forceinline__ void item_task_push(const DevTables &t, const StepArg
 // Units: s_sleep counts of 64 clocks (0: no delay).  Measured at the Yahoo shape (tools/ab.sh): 75 = about 2 us in
 // launch 1: 21.9 -> 21.3 us per step; longer delays give the gain back.  (Launch 2 in the push form: its item jobs are
 // shorter than its stream workgroups, so no delay there.)
-#ifndef STEP_STREAM_DELAY1
-#define STEP_STREAM_DELAY1 75
-#endif
-#ifndef STEP_STREAM_DELAY2
-#define STEP_STREAM_DELAY2 0
-#endif
+constexpr int kStreamDelay1 = 75, kStreamDelay2 = 0;
 template <int N>
 __device__ __forceinline__ void stream_delay() {
     if (N > 0) __builtin_amdgcn_s_sleep(N > 127 ? 127 : N);
     if (N > 127) __builtin_amdgcn_s_sleep(N - 127 > 127 ? 127 : N - 127);
 }
-#ifndef STEP_STREAM_ST
-#define STEP_STREAM_ST 1   // (A/B knob: 1 = write-through stores for the streamed rows)
-#endif
+constexpr int kStreamSt = 1;   // write-through stores (put4 MODE 1) for the streamed rows
 // (Tried in round 3: two register sets with the next rows' loads issued before the current rows' stores, so that a task
 //  of several iterations would be one round trip + work -- 128-row tasks in launch 1 ran 23-28 us per step against
 //  19.4: the rows per CU, not the iterations' round trips, pace these workgroups.  One iteration per task it is.)
@@ -1396,9 +1252,9 @@ __device__ __forceinline__ void stream_task(const DevTables &t, const StepArgs &
                 float *NP = (q & 1) ? (s ? a.np[3] : a.np[2]) : (s ? a.np[1] : a.np[0]);
                 float *M = (q & 1) ? (s ? a.m[3] : a.m[2]) : (s ? a.m[1] : a.m[0]);
                 float *V = (q & 1) ? (s ? a.v[3] : a.v[2]) : (s ? a.v[1] : a.v[0]);
-                put4<VEC, STEP_STREAM_ST, FULL>(NP, S.row[q >> 1], t.D, lg, S.p[q]);
-                put4<VEC, STEP_STREAM_ST, FULL>(M, S.row[q >> 1], t.D, lg, S.m[q]);
-                put4<VEC, STEP_STREAM_ST, FULL>(V, S.row[q >> 1], t.D, lg, S.v[q]);
+                put4<VEC, kStreamSt, FULL>(NP, S.row[q >> 1], t.D, lg, S.p[q]);
+                put4<VEC, kStreamSt, FULL>(M, S.row[q >> 1], t.D, lg, S.m[q]);
+                put4<VEC, kStreamSt, FULL>(V, S.row[q >> 1], t.D, lg, S.v[q]);
             }
         }
     };
@@ -1426,6 +1282,7 @@ struct FoldArgs {
     int sched_n;
 };
 constexpr int kFoldCols = 16, kFoldSubs = kThreads / kFoldCols;   // a fold block: 16 columns x 16 sub-rows of partials
+constexpr int kFoldCh = 32;                                        // partials per column in flight, per sub-row
 
 template <int DP, int EMAX>
 __device__ __forceinline__ void fold_block(const DevTables &t, const StepArgs &a, const FoldArgs &f, int fb, float *lds) {
@@ -1459,10 +1316,7 @@ __device__ __forceinline__ void fold_block(const DevTables &t, const StepArgs &a
     const int np = from_ev ? f.n_partials_ev : f.n_partials;
     const int64_t stride = from_ev ? EDP : SLAB;
     double acc = 0.0;
-#ifndef STEP_FOLD_CH
-#define STEP_FOLD_CH 32
-#endif
-    constexpr int CH = STEP_FOLD_CH;   // 32 x 16 sub-rows: up to 512 partials in ONE round trip
+    constexpr int CH = kFoldCh;   // 32 x 16 sub-rows: up to 512 partials in ONE round trip
     for (int s0 = sub; s0 < np; s0 += CH * kFoldSubs) {
         float x[CH];
 #pragma unroll
@@ -1542,17 +1396,10 @@ __device__ __forceinline__ void class_row(const StepArgs &a, int c, int (&q)[4])
 }
 
 // registers: the instances are held to 4 (E <= 4) / 3 workgroups per CU for launch 1 and 6 / 4 / 3 for launch 2
-#ifndef STEP_EVAL_WAVES_SMALL
-#define STEP_EVAL_WAVES_SMALL 3   // the smallest instance (D <= 64, E <= 4): 52 KB of LDS, <= 168 registers
-#endif
-#ifndef STEP_EVAL_WAVES
-#define STEP_EVAL_WAVES 2
-#endif
-#ifndef STEP_APPLY_WAVES
-#define STEP_APPLY_WAVES 4
-#endif
+constexpr int kEvalWavesSmall = 3;   // the smallest instance (D <= 64, E <= 4): 52 KB of LDS, <= 168 registers
+constexpr int kEvalWaves = 2, kApplyWaves = 4;
 template <int LG, bool VEC, int EMAX, bool FULL = false>
-__global__ __launch_bounds__(kThreads, (LG == 16 && EMAX <= 4) ? STEP_EVAL_WAVES_SMALL : STEP_EVAL_WAVES) void mstep_eval_kernel(DevTables t, StepArgs a) {
+__global__ __launch_bounds__(kThreads, (LG == 16 && EMAX <= 4) ? kEvalWavesSmall : kEvalWaves) void mstep_eval_kernel(DevTables t, StepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // Workgroup b runs the tasks of class c = b % n_cls (XCD-affine order, InvPrefRowPlan), the j-th of them with
     // j = b / n_cls: its user jobs first, then its share of the untouched rows.  Every branch is workgroup-uniform.
@@ -1564,24 +1411,20 @@ __global__ __launch_bounds__(kThreads, (LG == 16 && EMAX <= 4) ? STEP_EVAL_WAVES
     const int rpt = a.rounds_per_task, spt = a.rows_per_stream_task;
     const int tj = (q[1] + rpt - 1) / rpt;
     if (j < tj) {
-#ifndef DBG_NO_JOBS
         user_task<LG, VEC, EMAX, FULL>(t, a, q[0] + j * rpt, min(rpt, q[1] - j * rpt), q[0] / rpt + j, lds);
-#endif
         return;
     }
     j -= tj;
     if (j * spt < q[3]) {
         STAMP(0);
-#ifndef DBG_NO_STREAM
-        stream_delay<STEP_STREAM_DELAY1>();
+        stream_delay<kStreamDelay1>();
         stream_task<LG, VEC, FULL>(t, a, a.stream_rows + q[2] + j * spt, min(spt, q[3] - j * spt));
-#endif
         STAMP(7);
     }
 }
 
 template <int LG, bool VEC, int EMAX, bool FULL = false>
-__global__ __launch_bounds__(kThreads, FULL ? 3 : STEP_APPLY_WAVES) void mstep_apply_kernel(DevTables t, StepArgs a, FoldArgs f) {
+__global__ __launch_bounds__(kThreads, FULL ? 3 : kApplyWaves) void mstep_apply_kernel(DevTables t, StepArgs a, FoldArgs f) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if ((int)blockIdx.x >= f.n_task_wgs) {
         const int fb = (int)blockIdx.x - f.n_task_wgs;
@@ -1601,14 +1444,12 @@ __global__ __launch_bounds__(kThreads, FULL ? 3 : STEP_APPLY_WAVES) void mstep_a
             return;
         }
         STAMP(0);
-#ifndef DBG_NO_FOLD
         fold_block<4 * LG, EMAX>(t, a, f, fb, lds);
         constexpr int loss0 = 2 * EMAX * 4 * LG + EMAX;
         if (fb == loss0 / kFoldCols) {   // (workgroup-uniform)
             __syncthreads();
             fold_losses(t, a, f, lds);
         }
-#endif
         STAMP(7);
         return;
     }
@@ -1620,19 +1461,15 @@ __global__ __launch_bounds__(kThreads, FULL ? 3 : STEP_APPLY_WAVES) void mstep_a
     const int rpt = a.rounds_per_task, spt = a.rows_per_stream_task;
     const int tj = (q[1] + rpt - 1) / rpt;
     if (j < tj) {
-#ifndef DBG_NO_JOBS
         if (a.push_slot) item_task_push<LG, VEC, EMAX, FULL>(t, a, q[0] + j * rpt, min(rpt, q[1] - j * rpt), lds);
         else item_task<LG, VEC, EMAX, FULL>(t, a, q[0] + j * rpt, min(rpt, q[1] - j * rpt), lds);
-#endif
         return;
     }
     j -= tj;
     if (j * spt < q[3]) {
         STAMP(0);
-#ifndef DBG_NO_STREAM
-        stream_delay<STEP_STREAM_DELAY2>();
+        stream_delay<kStreamDelay2>();
         stream_task<LG, VEC, FULL>(t, a, a.stream_rows + q[2] + j * spt, min(spt, q[3] - j * spt));
-#endif
         STAMP(7);
     }
 }

@@ -81,40 +81,22 @@ __device__ __forceinline__ void st_sc1(int *p, int v) {
 #define ALT_TEST_BAD_TAG 0        // (test builds only, tests/test_alt_gpu.py: the job workgroups wait for a tag nobody publishes,
                                   //  so every wait times out -- with a small ALT_POLL_MAX -- and the managers must raise)
 #endif
-#ifndef ALT_STREAM_DELAY
-#define ALT_STREAM_DELAY 40       // s_sleep units of 64 clocks in front of a stream task (evaluating launches): ~1 us.  Round 5 measured
-                                  // no gain from it (16.0 vs 15.95 us); with the pushes written through and two pending pairs in flight
-                                  // (round 6) the rows without a job DO queue in front of the jobs' first burst: 14.08 -> 13.97 us
-#endif
-#ifndef ALT_PEND_COND
-#define ALT_PEND_COND 0           // (A/B knob: 1 = the first pending-row loads only for waves that have pending rows -- measured
-                                  //  slower, 17.0 vs 16.1 us per step: the wave-uniform branch needs the ranges before any load)
-#endif
-#ifndef ALT_EARLY_STAGE
-#define ALT_EARLY_STAGE 0         // (A/B knob: 1 = the small tables' granules requested in front of the previous step's update;
-                                  //  18 registers across that phase: needs ALT_PEND_DEPTH 2 to stay free of scratch)
-#endif
-#ifndef ALT_PUSH_ST
-#define ALT_PUSH_ST 1             // the contribution rows pushed for the other side leave as write-through stores (0: plain) -- they are
-                                  // read by the NEXT launch on other XCDs, and dirty bytes left in L2 lengthen the kernel boundary
-                                  // (round 6, same box: 14.69 -> 14.33 us per launch; write-through rows p / m / v: 14.9, slower)
-#endif
-#ifndef ALT_SLAB_ST
-#define ALT_SLAB_ST 1             // the partial slab of a job workgroup too (read by the next launch's fold blocks)
-#endif
-#ifndef ALT_ROW_ST
-#define ALT_ROW_ST 0              // (A/B knob) 1: the rows a job finishes (p, m, v) leave as write-through stores -- measured SLOWER
-                                  // here (14.9 vs 14.7 us per launch): the other side gathers them in the very next launch
-#endif
-#ifndef ALT_MV_ST
-#define ALT_MV_ST ALT_ROW_ST      // (A/B knob) 1: the Adam moments of the rows a job finishes leave as write-through stores (nobody
-                                  // reads them before the row's own job two launches on)
-#endif
-#ifndef ALT_PEND_DEPTH
-#define ALT_PEND_DEPTH 2          // pending contribution-row pairs in flight per group (two register sets).  Round 5: 4 (16.26 vs 16.43
-                                  // us); round 6, the pushed rows now written through (they come from the Infinity Cache, not from a
-                                  // neighbour's L2) and the first burst the launch's bottleneck: 2 is faster, 14.23 -> 14.08 us
-#endif
+// s_sleep units of 64 clocks in front of a stream task (evaluating launches): ~1 us.  Round 5 measured no gain from it
+// (16.0 vs 15.95 us); with the pushes written through and two pending pairs in flight (round 6) the rows without a job DO
+// queue in front of the jobs' first burst: 14.08 -> 13.97 us
+constexpr int kAltStreamDelay = 40;
+// the contribution rows pushed for the other side leave as write-through stores (store4 MODE 1) -- they are read by the
+// NEXT launch on other XCDs, and dirty bytes left in L2 lengthen the kernel boundary (round 6, same box: 14.69 -> 14.33 us
+// per launch); the partial slab of a job workgroup too (read by the next launch's fold blocks).  The rows a job finishes
+// (p, m, v) stay plain stores: written through they measured SLOWER here (14.9 vs 14.7 us per launch), the other side
+// gathers them in the very next launch
+constexpr int kAltPushSt = 1, kAltSlabSt = 1;
+// pending contribution-row pairs in flight per group (two register sets).  Round 5: 4 (16.26 vs 16.43 us); round 6, the
+// pushed rows now written through (they come from the Infinity Cache, not from a neighbour's L2) and the first burst the
+// launch's bottleneck: 2 is faster, 14.23 -> 14.08 us
+constexpr int kAltPendDepth = 2;
+// (also measured and dropped, profiles/r05-r06 EXPERIMENTS.md: the first pending-row loads only for waves that have pending
+//  rows, the small tables requested in front of the previous step's update, non-temporal loads for the streamed rows)
 
 // The small tables travel from the fold blocks to the job workgroups of the SAME launch as data-tagged granules: the fold
 // thread that finishes an entry stores {value, step number} as ONE 8-byte write-through store, wave 0 of a job workgroup
@@ -254,7 +236,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
     constexpr int LG = 16, EMAX = 4, UE = 2;
     using G = AltGeo<THREADS>;
     using L = AltGeo<THREADS>;
-    static_assert(STEP_LDS_DW && !STEP_NO_DMA && EvalLds<16, 4>::total == AltGeo<256>::total, "alt_task: the default smallest-instance layout");
+    static_assert(EvalLds<16, 4>::total == AltGeo<256>::total, "alt_task: the smallest-instance layout");
     constexpr int NG = G::NG, DP = G::DP;
     float *sEv = lds + L::sEv, *sW = lds + L::sW, *sb = lds + L::sb, *scw = lds + L::scw;
     float4 *mv = reinterpret_cast<float4 *>(lds + L::mv);
@@ -329,7 +311,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
             me = row4<VEC, FULL>(a.own_m[1], rowc, D, lg); ve = row4<VEC, FULL>(a.own_v[1], rowc, D, lg);
         }
         // pending contribution rows of this slice: contiguous pairs [pa, pb), two register sets
-        constexpr int H = ALT_PEND_DEPTH / 2;
+        constexpr int H = kAltPendDepth / 2;
         const int npend = (active && has_prev) ? pdd.y - pdd.x : 0;
         const float *pbase = a.pend_rows + (unsigned)(npend > 0 ? pdd.x : 0) * (unsigned)(2 * DP) + lg * 4;
         float4 ci[2][H], ce[2][H];
@@ -355,20 +337,15 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         for (int s = 0; s < 2; s++)
 #pragma unroll
             for (int j = 0; j < H; j++) ci[s][j] = ce[s][j] = f4zero();
-        // (wave-uniform branches: a wave whose slices have nothing pending -- most user-side waves -- adds no loads to the
-        //  launch's first burst, and the second register set only goes out for slices of more than H pairs)
+        // (a round with nothing pending -- most user-side rounds -- adds no loads to the launch's first burst; otherwise both
+        //  register sets go out at once: loading them only for waves that need them measured slower, 17.0 vs 16.1 us)
         int n_wave = 0;
         if (rpend) {
             n_wave = npend;
 #pragma unroll
             for (int g = 0; g < 64 / LG; g++) n_wave = max(n_wave, __builtin_amdgcn_readlane(npend, g * LG));
-#if ALT_PEND_COND
-            if (n_wave > 0) pfetch(0, 0);
-            if (n_wave > H) pfetch(1, H);
-#else
             pfetch(0, 0);
             pfetch(1, H);
-#endif
         }
 
         struct Slot {
@@ -436,19 +413,11 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
                     if (UE + j < nsmp) idn[j] = sample_at(UE + j);
             }
         }
-        // ---- (ii, first half) this step's small tables are requested as soon as this wave's first burst is in -- by then the
-        // fold blocks have usually published them (they end ~5 us into a launch, the burst arrives ~6 us in) -- and fly under
-        // the previous step's update; a request that comes too early is repeated at the point of use
+        // (this step's small tables, (ii) below; requested in front of the previous step's update instead: no gain, git history)
         AltStage stg;
 #pragma unroll
         for (int i = 0; i < 9; i++) stg.g[i] = 0ull;
         stg.cw = 1.f;
-#if ALT_EARLY_STAGE
-        if (has_cur && has_prev && !pure && wave == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            alt_stage_issue(a, stg);
-        }
-#endif
         // ---- (i) the previous step's update of this row
         if (has_prev) {
             if (rpend) {
@@ -537,9 +506,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         // ---- (ii) the small tables of this step
         if (r == r0) {
             if (wave == 0) {
-#if !ALT_EARLY_STAGE
                 if (has_prev && !pure) alt_stage_issue(a, stg);
-#endif
                 if (has_prev && !pure) alt_stage_finish(a, stg, gen, sEv, sW, sb, scw);
                 else alt_stage_plain(a, sEv, sW, sb, scw, pure);
             }
@@ -555,10 +522,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
                 const float w_rec = rw_rec ? wq : 1.f, w_cls = rw_cls ? wq : 1.f;
                 const float4 ev = *reinterpret_cast<const float4 *>(sEv + e * DP + lg * 4);
                 Eval<EMAX> o;
-#ifndef ALT_EVAL_KIND
-#define ALT_EVAL_KIND -1   // (what-if knob: 1 = the implicit InvPref evaluation fixed at compile time -- one basic block)
-#endif
-                eval_interaction<LG, EMAX, ALT_EVAL_KIND>(o, oi, q.qi, oe, q.qa, ev, sW, sb, nullptr, a.E, e, q.sm.y, w_rec * k.invB,
+                eval_interaction<LG, EMAX>(o, oi, q.qi, oe, q.qa, ev, sW, sb, nullptr, a.E, e, q.sm.y, w_rec * k.invB,
                                            w_cls * k.invB, k, implicit, pure, lg);
                 float4 gip;
                 gip.x = o.g_p - k.alpha * o.gx.x; gip.y = o.g_p - k.alpha * o.gx.y;
@@ -566,14 +530,14 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
                 f4add(gi, f4mul(gip, q.qi));
                 f4fma(ge, o.g_q, f4mul(q.qa, ev));
                 float *cr = a.push_rows + (unsigned)q.cs * (unsigned)(2 * DP) + lg * 4;
-                store4<ALT_PUSH_ST>(cr, f4mul(gip, oi));
-                store4<ALT_PUSH_ST>(cr + DP, f4scale(o.g_q, f4mul(oe, ev)));
+                store4<kAltPushSt>(cr, f4mul(gip, oi));
+                store4<kAltPushSt>(cr + DP, f4scale(o.g_q, f4mul(oe, ev)));
                 float4 oo = f4scale(o.g_q, f4mul(oe, q.qa));
                 if (reg_env) f4add(oo, reg_term(ev, 2.f * k.r2, 2.f * k.r1));
                 float *mine = red + grp * G::SLAB;
 #pragma unroll
                 for (int c = 0; c < EMAX; c++) {
-                    float4 *wr = reinterpret_cast<float4 *>(mine + EMAX * DP + (kClsQuads<LG, EMAX> ? ((lg >> 2) ^ c) : c) * DP + lg * 4);
+                    float4 *wr = reinterpret_cast<float4 *>(mine + EMAX * DP + c * DP + lg * 4);
                     float4 cur = *wr;
                     f4fma(cur, o.gz[c], o.x);
                     *wr = cur;
@@ -596,7 +560,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
                 accL2 += s2;
                 accL1 += s1;
                 if (lg == 0) { accLi += o.li * w_rec; accLe += o.le * w_rec; }
-                if (kClsQuads<LG, EMAX> ? (lg & 3) == 0 : lg == 0) accLc += o.lcls * w_cls;
+                if (lg == 0) accLc += o.lcls * w_cls;
             }
         };
         // (Tried in round 5: the slice's interactions evaluated two at a time in one basic block at two workgroups per CU, so
@@ -667,7 +631,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
 #pragma unroll
                     for (int j = (q0 == 0 ? 1 : 0); j < 8; j++) f4add(sum, x[j]);
                 }
-                store4<ALT_SLAB_ST>(slab + threadIdx.x * 4, sum);
+                store4<kAltSlabSt>(slab + threadIdx.x * 4, sum);
             }
         }
         if (slices > 1) {
@@ -720,14 +684,14 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
                 f4fma(ge, cnt, reg_term(oe, k.r2, k.r1));
             }
             adam4(oi, gi, mi, vi, ad_cur);
-            put4<VEC, ALT_ROW_ST, FULL>(own0, row, D, lg, oi);
-            put4<VEC, ALT_MV_ST, FULL>(a.own_m[0], row, D, lg, mi);
-            put4<VEC, ALT_MV_ST, FULL>(a.own_v[0], row, D, lg, vi);
+            put4<VEC, 0, FULL>(own0, row, D, lg, oi);
+            put4<VEC, 0, FULL>(a.own_m[0], row, D, lg, mi);
+            put4<VEC, 0, FULL>(a.own_v[0], row, D, lg, vi);
             if (!pure) {
                 adam4(oe, ge, me, ve, ad_cur);
-                put4<VEC, ALT_ROW_ST, FULL>(own1, row, D, lg, oe);
-                put4<VEC, ALT_MV_ST, FULL>(a.own_m[1], row, D, lg, me);
-                put4<VEC, ALT_MV_ST, FULL>(a.own_v[1], row, D, lg, ve);
+                put4<VEC, 0, FULL>(own1, row, D, lg, oe);
+                put4<VEC, 0, FULL>(a.own_m[1], row, D, lg, me);
+                put4<VEC, 0, FULL>(a.own_v[1], row, D, lg, ve);
             }
         }
     }
@@ -753,9 +717,6 @@ __device__ __forceinline__ void alt_stream(const AltArgs &a, const int4 *rows, i
             const int idx = grp + (it * R + q) * NG;
             on[q] = idx < n;
             e[q] = rows[on[q] ? idx : 0];
-#ifdef ALT_DIAG_SKIP_UNTOUCHED   // (what-if build, WRONG results: rows without pending pairs cost nothing -- the bound of a deferred Adam)
-            if (on[q] && e[q].z - e[q].y <= 0) { on[q] = false; e[q] = rows[0]; }
-#endif
         }
         float4 p[2 * R], m[2 * R], v[2 * R], ci[R][H], ce[R][H];
         int npend[R];
@@ -763,21 +724,9 @@ __device__ __forceinline__ void alt_stream(const AltArgs &a, const int4 *rows, i
         for (int q = 0; q < 2 * R; q++) {
             p[q] = m[q] = v[q] = f4zero();
             if (!(pure && (q & 1))) {
-#if defined(ALT_STREAM_NT)   // (A/B knob: the streamed rows are read once per two launches -- non-temporal loads)
-                if (FULL) {
-                    typedef float nt4 __attribute__((ext_vector_type(4)));
-                    const unsigned off = (unsigned)e[q >> 1].x * 256u + (unsigned)lg * 16u;
-                    const nt4 pp = __builtin_nontemporal_load(reinterpret_cast<const nt4 *>(reinterpret_cast<const char *>(a.own_p[q & 1]) + off));
-                    const nt4 mm = __builtin_nontemporal_load(reinterpret_cast<const nt4 *>(reinterpret_cast<const char *>(a.own_m[q & 1]) + off));
-                    const nt4 vv = __builtin_nontemporal_load(reinterpret_cast<const nt4 *>(reinterpret_cast<const char *>(a.own_v[q & 1]) + off));
-                    p[q] = make_float4(pp.x, pp.y, pp.z, pp.w); m[q] = make_float4(mm.x, mm.y, mm.z, mm.w); v[q] = make_float4(vv.x, vv.y, vv.z, vv.w);
-                } else
-#endif
-                {
                 p[q] = row4<VEC, FULL>(a.own_p[q & 1], e[q >> 1].x, D, lg);
                 m[q] = row4<VEC, FULL>(a.own_m[q & 1], e[q >> 1].x, D, lg);
                 v[q] = row4<VEC, FULL>(a.own_v[q & 1], e[q >> 1].x, D, lg);
-                }
             }
         }
 #pragma unroll
@@ -842,9 +791,9 @@ __device__ __forceinline__ void alt_stream(const AltArgs &a, const int4 *rows, i
 #pragma unroll
                 for (int tb = 0; tb < 2; tb++) {
                     if (pure && tb) continue;
-                    put4<VEC, STEP_STREAM_ST, FULL>(a.own_p[tb], e[q].x, D, lg, p[2 * q + tb]);
-                    put4<VEC, STEP_STREAM_ST, FULL>(a.own_m[tb], e[q].x, D, lg, m[2 * q + tb]);
-                    put4<VEC, STEP_STREAM_ST, FULL>(a.own_v[tb], e[q].x, D, lg, v[2 * q + tb]);
+                    put4<VEC, kStreamSt, FULL>(a.own_p[tb], e[q].x, D, lg, p[2 * q + tb]);
+                    put4<VEC, kStreamSt, FULL>(a.own_m[tb], e[q].x, D, lg, m[2 * q + tb]);
+                    put4<VEC, kStreamSt, FULL>(a.own_v[tb], e[q].x, D, lg, v[2 * q + tb]);
                 }
             }
         }
@@ -879,7 +828,7 @@ __device__ __forceinline__ void alt_fold_block(const AltArgs &a, int fb, float *
     const float *col = a.slabs_prev + (mine ? idx : 0);
     const int np = a.n_partials_prev;
     double acc = 0.0;
-    constexpr int CH = STEP_FOLD_CH;
+    constexpr int CH = kFoldCh;
     for (int s0 = sub; s0 < np; s0 += CH * kFoldSubs) {
         float x[CH];
 #pragma unroll
@@ -1002,7 +951,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 256 ? 3 : 1) void mstep_alt_ker
         ASTAMP(0);
         // (started a little late: the rows without a job are off the launch's critical chain, and their load burst would
         //  queue in front of the jobs' first gathers and the fold blocks' slab reads -- as in the two-launch form)
-        if (MODE & 2) stream_delay<ALT_STREAM_DELAY>();
+        if (MODE & 2) stream_delay<kAltStreamDelay>();
         alt_stream<VEC, FULL, MODE, THREADS>(a, a.stream + q[2] + j * spt, min(spt, q[3] - j * spt), ad_cur, prev2);
         ASTAMP(7);
     }

@@ -23,45 +23,17 @@
 #pragma once
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifndef WIDE_UE
-#define WIDE_UE 2      // interactions in flight per group (launch 1)
-#endif
-#ifndef WIDE_WAVES_16_2_8
-#define WIDE_WAVES_16_2_8 2
-#endif
-#ifndef WIDE_UE_16_2_8
-#define WIDE_UE_16_2_8 2
-#endif
-#ifndef WIDE_U_EVL2_16
-#define WIDE_U_EVL2_16 1   // launch 2 of the D <= 256, E = 16 instance (its slots hold 16 class gradients each)
-#endif
-#ifndef WIDE_FENCE
-#define WIDE_FENCE 1   // scheduling fences inside the classifier loops of two-chunk rows (register pressure)
-#endif
-#ifndef WIDE_STEP_FENCE_MASK
-#define WIDE_STEP_FENCE_MASK 0   // what may cross the fences between two lock-step iterations (0x8: the MFMA block)
-#endif
-#ifndef WIDE_FIRST_FROM_DESC
-#define WIDE_FIRST_FROM_DESC 1   // 16-lane rows: a slice's first gather from the descriptor's registers instead of through list_at (32-lane rows have no registers for the descriptor's second half: +3-4 %)
-#endif
-#ifndef WIDE_PUSH_DEPTH
-#define WIDE_PUSH_DEPTH 4   // (measured at the MovieLens shape: 66.7 -> 66.0 us against 2)
-#endif
-#ifndef WIDE_MFMA_FENCE
-#define WIDE_MFMA_FENCE 1   // (A/B knob) a fence between the row updates / stores and the MFMA block
-#endif
-#ifndef WIDE_FENCE_MASK
-// what may still cross a fence of the classifier loops: ALU (0x1 | VALU 0x2 | SALU 0x4 | transcendental 0x400) -- the
-// loss chains interleave with the LDS waits -- but no memory instruction: the W-row reads stay where they are
-#define WIDE_FENCE_MASK 0x407
-#endif
+// what may still cross a scheduling fence of the classifier loops of two-chunk rows (register pressure): ALU (0x1 | VALU
+// 0x2 | SALU 0x4 | transcendental 0x400) -- the loss chains interleave with the LDS waits -- but no memory instruction: the
+// W-row reads stay where they are
+constexpr int kWideFenceMask = 0x407;
 
 // per-instance launch-1 configuration: workgroups per CU the kernel is compiled for (registers: 512 / waves per SIMD)
 // and the interactions each group keeps in flight
 template <int LG, int NC, int EMAX>
 struct WideCfg {
-    static constexpr int WAVES = (LG == 16 && NC == 2 && EMAX == 8) ? WIDE_WAVES_16_2_8 : 2;
-    static constexpr int UE = (LG == 16 && NC == 2 && EMAX == 8) ? WIDE_UE_16_2_8 : ((NC == 2 && LG == 16 && EMAX == 16) ? 1 : WIDE_UE);
+    static constexpr int WAVES = 2;
+    static constexpr int UE = (LG == 16 && NC == 2 && EMAX == 16) ? 1 : 2;
 };
 
 template <int LG, int NC, int EMAX>
@@ -171,7 +143,7 @@ template <int LG, int NC, int EMAX, int C>
 __device__ __forceinline__ void gx_classes(float4 (&gx)[NC], float gzl, const float *sW, int lg) {
     if constexpr (C < EMAX) {
         constexpr int DP = 4 * LG * NC;
-        if (WIDE_FENCE && NC > 1 && (C & 3) == 0) __builtin_amdgcn_sched_barrier(WIDE_FENCE_MASK);
+        if (NC > 1 && (C & 3) == 0) __builtin_amdgcn_sched_barrier(kWideFenceMask);
         const float g = dpp_move<0x150 + C>(gzl);   // row_share:C
 #pragma unroll
         for (int j = 0; j < NC; j++) {
@@ -226,12 +198,6 @@ __device__ __forceinline__ void eval_wide(WEval<NC> &o, const float4 (&pu)[NC], 
         for (int j = 0; j < NC; j++) o.gx[j] = f4zero();
         return;
     }
-#ifdef WIDE_DIAG_NOCLS
-    o.lcls = o.gz_lane = o.gz_all = 0.f;
-#pragma unroll
-    for (int j = 0; j < NC; j++) o.gx[j] = f4zero();
-    return;
-#endif
     // all EMAX class dot products per lane (rows c >= E are staged as zeros), then ONE reduce-scatter butterfly: lane l of
     // the group ends up with the logit of class l & (EMAX - 1)
     float part[EMAX];
@@ -239,7 +205,7 @@ __device__ __forceinline__ void eval_wide(WEval<NC> &o, const float4 (&pu)[NC], 
     for (int c = 0; c < EMAX; c++) {
         // (a scheduling fence per four classes: left alone the compiler requests every W row of the loop up front and
         //  the kernel spills; two waves per SIMD cover the LDS latency instead)
-        if (WIDE_FENCE && NC > 1 && (c & 3) == 0) __builtin_amdgcn_sched_barrier(WIDE_FENCE_MASK);
+        if (NC > 1 && (c & 3) == 0) __builtin_amdgcn_sched_barrier(kWideFenceMask);
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < NC; j++) {
@@ -248,7 +214,7 @@ __device__ __forceinline__ void eval_wide(WEval<NC> &o, const float4 (&pu)[NC], 
         }
         part[c] = s;
     }
-    if (WIDE_FENCE && NC > 1) __builtin_amdgcn_sched_barrier(WIDE_FENCE_MASK);
+    if (NC > 1) __builtin_amdgcn_sched_barrier(kWideFenceMask);
     ETRACE(12);
     const float zred = group_sum_above<LG, EMAX>(class_butterfly<EMAX>(part, lg), lg);
     // (16-lane rows: the lane's class bias sits in a register; 32-lane rows have none to spare and read it from LDS)
@@ -280,7 +246,7 @@ __device__ __forceinline__ void eval_wide(WEval<NC> &o, const float4 (&pu)[NC], 
         o.gz_all = (lg & 15) < EMAX ? gzs[lg & 15] : 0.f;
 #pragma unroll
         for (int c4 = 0; c4 < EMAX; c4 += 4) {
-            if (WIDE_FENCE && NC > 1) __builtin_amdgcn_sched_barrier(WIDE_FENCE_MASK);
+            if (NC > 1) __builtin_amdgcn_sched_barrier(kWideFenceMask);
             const float4 g4 = *reinterpret_cast<const float4 *>(gzs + c4);
 #pragma unroll
             for (int j = 0; j < NC; j++) {
@@ -415,9 +381,6 @@ __device__ __forceinline__ void user_task_wide(const DevTables &t, const StepArg
         const int lo = dd.z, hi1 = max(dd.w - 1, dd.z);
         const int *dwords = reinterpret_cast<const int *>(a.desc + (r * NG + grp) * 2);
         auto list_at = [&](int sidx) {
-#ifdef WIDE_DIAG_NOLIST   // (what-if build: no list round trip in front of the gathers -- ids made up from the slice bounds)
-            return USample{(lo + sidx) & 1023, min(lo + sidx, hi1), 0.f};
-#endif
             const int *src = mode == 7 ? reinterpret_cast<const int *>(a.ulist + min(lo + sidx, hi1)) : dwords + 2 + 3 * min(sidx, 1);
             return USample{src[0], src[1], __builtin_bit_cast(float, src[2])};
         };
@@ -438,11 +401,7 @@ __device__ __forceinline__ void user_task_wide(const DevTables &t, const StepArg
         USample idn[UE];
         auto gather = [&](Slot &q, const USample &sm, int sidx) {
             q.y = sm.y;
-#ifdef WIDE_DIAG_HOT   // (what-if build: every gather hits the same few rows -- what the launch costs without gather latency)
-            const int oth = sm.oth & 15;
-#else
             const int oth = sm.oth;
-#endif
             load_row<LG, NC, VEC>(q.qi, t.Qi, oth, t.D, lg);
             const unsigned pso = (unsigned)sm.ps;   // (32-bit offsets: one address register, no 64-bit pair to copy into)
             if (!pure) {
@@ -453,7 +412,7 @@ __device__ __forceinline__ void user_task_wide(const DevTables &t, const StepArg
             // the slot: word 3 of the list entry the ids came from or, inline form, rec_slot[position] -- one load, selected address
             const int *sp = mode == 7 ? reinterpret_cast<const int *>(a.ulist + min(lo + sidx, hi1)) + 3
                                       : reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.rec_slot) + pso * 4u);
-            q.cs = STEP_SLOT_FROM_LIST ? *sp : *reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.rec_slot) + pso * 4u);
+            q.cs = *sp;
         };
         // the slice's FIRST interaction is in the descriptor's registers either way (inline form: words 2 .. 4, list form:
         // words 4 .. 6), so its gather leaves as soon as the descriptor is here -- not one list round trip later
@@ -466,7 +425,8 @@ __device__ __forceinline__ void user_task_wide(const DevTables &t, const StepArg
             sl[j].e = sl[j].cs = 0;
             sl[j].y = 0.f;
             sl[j].w = 1.f;
-            if (WIDE_FIRST_FROM_DESC && LG == 16 && j == 0) gather(sl[j], first, 0);
+            // (16-lane rows only: 32-lane rows have no registers for the descriptor's second half, +3-4 %)
+            if (LG == 16 && j == 0) gather(sl[j], first, 0);
             else gather(sl[j], list_at(j), j);
         }
 #pragma unroll
@@ -489,7 +449,7 @@ __device__ __forceinline__ void user_task_wide(const DevTables &t, const StepArg
         auto step = [&](const Slot &q, bool has) {
             // branch-free: an empty slot (the round's longest slice sets the trip count) evaluates its stale rows with
             // every gradient scalar forced to zero (eval_wide) and stores nothing
-            if (WIDE_FENCE && NC > 1) __builtin_amdgcn_sched_barrier(WIDE_STEP_FENCE_MASK);   // (the unrolled slots' evaluations stay apart)
+            if (NC > 1) __builtin_amdgcn_sched_barrier(0);   // (the unrolled slots' evaluations stay apart)
             float *gzs = lds + G::gzs + ((it_total & 1) * NG + grp) * (EMAX + 4);
             WTRACE(1);
             const int e = q.e;
@@ -522,13 +482,9 @@ __device__ __forceinline__ void user_task_wide(const DevTables &t, const StepArg
                 gip.z = o.g_p - k.alpha * o.gx[j].z; gip.w = o.g_p - k.alpha * o.gx[j].w;
                 f4add(gi[j], f4mul(gip, q.qi[j]));
                 f4fma(ge[j], o.g_q, f4mul(q.qa[j], ev[j]));
-#ifdef WIDE_DIAG_NOSTORE
-                if (false) {
-#else
                 if (push) {   // the interaction's two contribution rows to its ITEM's gradient, at the item-sorted slot
-#endif
-                    store4<STEP_PUSH_ST>(cr + 4 * (lg + LG * j), f4mul(gip, oi[j]));
-                    store4<STEP_PUSH_ST>(cr + DP + 4 * (lg + LG * j), f4scale(o.g_q, f4mul(oe[j], ev[j])));
+                    store4<0>(cr + 4 * (lg + LG * j), f4mul(gip, oi[j]));
+                    store4<0>(cr + DP + 4 * (lg + LG * j), f4scale(o.g_q, f4mul(oe[j], ev[j])));
                 }
                 if constexpr (!EVL2) {
                     // o = g_q Pa*Qa (+ env regulariser): the interaction's term of embed_env's gradient
@@ -566,15 +522,11 @@ __device__ __forceinline__ void user_task_wide(const DevTables &t, const StepArg
             const float a_gz = LG == 16 ? o.gz_lane : (lc < EMAX ? o.gz_all : 0.f);   // (every lane holds gz of class lane & 15)
             if (lg < 16) dBacc += o.gz_lane;
             WTRACE(4);
-            if (WIDE_FENCE && WIDE_MFMA_FENCE && NC > 1) __builtin_amdgcn_sched_barrier(0);
-#ifndef WIDE_DIAG_NOMFMA
+            if (NC > 1) __builtin_amdgcn_sched_barrier(0);   // (the row updates / stores stay apart from the MFMA block)
             outer_mfma<LG, NC>(accW, a_gz, o.x, lane);
-#endif
-#ifndef WIDE_DIAG_NOMFMA
             if constexpr (SH) outer_mfma<LG, NC>(accW, (has && lc == e + 8) ? 1.f : 0.f, boo, lane);
             else if constexpr (!EVL2) outer_mfma<LG, NC>(accE, (has && lc == e) ? 1.f : 0.f, boo, lane);
-#endif
-            if (WIDE_FENCE && NC > 1) __builtin_amdgcn_sched_barrier(WIDE_STEP_FENCE_MASK);
+            if (NC > 1) __builtin_amdgcn_sched_barrier(0);
             WTRACE(5);
             it_total++;
         };
@@ -723,7 +675,7 @@ template <int LG, int NC, bool VEC, int EMAX, bool EVL2>
 __device__ __forceinline__ void item_task_wide(const DevTables &t, const StepArgs &a, int r0, int nr, int slab_index, float *lds) {
     using G = WGeo<LG, NC, EMAX>;
     constexpr int NG = G::NG, DP = G::DP, RS = G::RS, TILES = G::TILES;
-    constexpr int U = (EVL2 && EMAX == 16) ? WIDE_U_EVL2_16 : 2;   // interactions in flight per group
+    constexpr int U = (EVL2 && EMAX == 16) ? 1 : 2;   // interactions in flight per group (E = 16: its slots hold 16 class gradients each)
     float *sEv = lds, *sW = sEv + EMAX * DP, *slots = sW + EMAX * DP;
     const int lg = threadIdx.x & (LG - 1), grp = threadIdx.x / LG, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const bool pure = a.flags & INVPREF_PURE_MF;
@@ -787,7 +739,7 @@ __device__ __forceinline__ void item_task_wide(const DevTables &t, const StepArg
             }
         };
         auto consume = [&](const In &in, bool has) {
-            if (WIDE_FENCE && NC > 1) __builtin_amdgcn_sched_barrier(0);   // (the unrolled slots stay apart)
+            if (NC > 1) __builtin_amdgcn_sched_barrier(0);   // (the unrolled slots stay apart)
             float a_one = 0.f;
             float4 boo[EVL2 ? NC : 1];
 #pragma unroll
@@ -799,17 +751,15 @@ __device__ __forceinline__ void item_task_wide(const DevTables &t, const StepArg
                 for (int j = 0; j < NC; j++) {
                     float4 gx = f4zero();
                     if (!pure) {
-#ifndef WIDE_DIAG_L2_NOGX   // (what-if build: launch 2 without the classifier's backward)
 #pragma unroll
                         for (int c4 = 0; c4 < EMAX / 4; c4++) {
-                            if (WIDE_FENCE && NC > 1) __builtin_amdgcn_sched_barrier(0);
+                            if (NC > 1) __builtin_amdgcn_sched_barrier(0);
                             const float *wr = sW + (c4 * 4) * DP + 4 * (lg + LG * j);
                             f4fma(gx, in.gz[c4].x, *reinterpret_cast<const float4 *>(wr));
                             f4fma(gx, in.gz[c4].y, *reinterpret_cast<const float4 *>(wr + DP));
                             f4fma(gx, in.gz[c4].z, *reinterpret_cast<const float4 *>(wr + 2 * DP));
                             f4fma(gx, in.gz[c4].w, *reinterpret_cast<const float4 *>(wr + 3 * DP));
                         }
-#endif
                         const float4 ev = *reinterpret_cast<const float4 *>(sEv + e * DP + 4 * (lg + LG * j));
                         f4fma(ge[j], g_q, f4mul(in.pa[j], ev));
                         if (EVL2) {
@@ -825,9 +775,7 @@ __device__ __forceinline__ void item_task_wide(const DevTables &t, const StepArg
                 }
                 a_one = (lane & 15) == e ? 1.f : 0.f;
             }
-#ifndef WIDE_DIAG_L2_NOMFMA   // (what-if build: launch 2 without embed_env's outer product)
             if constexpr (EVL2) outer_mfma<LG, NC>(accE, a_one, boo, lane);
-#endif
         };
         In nx[U];
         int2 idn[U];
@@ -929,7 +877,7 @@ template <int LG, int NC, bool VEC, int EMAX>
 __device__ __forceinline__ void item_task_push_wide(const DevTables &t, const StepArgs &a, int r0, int nr, float *lds) {
     using G = WGeo<LG, NC, EMAX>;
     constexpr int DP = G::DP, NG = G::NG;
-    constexpr int PCH = WIDE_PUSH_DEPTH;   // contribution-row pairs in flight per group
+    constexpr int PCH = 4;   // contribution-row pairs in flight per group (measured at the MovieLens shape: 66.7 -> 66.0 us against 2)
     float *slots = lds;      // [NG][2][DP] slice partials
     const int lg = threadIdx.x & (LG - 1), grp = threadIdx.x / LG;
     const bool pure = a.flags & INVPREF_PURE_MF;
@@ -1083,9 +1031,9 @@ __device__ __forceinline__ void stream_task_wide(const DevTables &t, const StepA
             if (tb == 1 && pure) break;
 #pragma unroll
             for (int j = 0; j < NC; j++) adam4(p[tb][j], f4zero(), m[tb][j], v[tb][j], ad);
-            store_row<LG, NC, VEC, STEP_STREAM_ST>(side ? a.np[2 * tb + 1] : a.np[2 * tb], row, t.D, lg, p[tb]);
-            store_row<LG, NC, VEC, STEP_STREAM_ST>(side ? a.m[2 * tb + 1] : a.m[2 * tb], row, t.D, lg, m[tb]);
-            store_row<LG, NC, VEC, STEP_STREAM_ST>(side ? a.v[2 * tb + 1] : a.v[2 * tb], row, t.D, lg, v[tb]);
+            store_row<LG, NC, VEC, kStreamSt>(side ? a.np[2 * tb + 1] : a.np[2 * tb], row, t.D, lg, p[tb]);
+            store_row<LG, NC, VEC, kStreamSt>(side ? a.m[2 * tb + 1] : a.m[2 * tb], row, t.D, lg, m[tb]);
+            store_row<LG, NC, VEC, kStreamSt>(side ? a.v[2 * tb + 1] : a.v[2 * tb], row, t.D, lg, v[tb]);
         }
     }
 }

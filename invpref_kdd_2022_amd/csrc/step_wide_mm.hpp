@@ -77,23 +77,8 @@ __device__ __forceinline__ void st_t(float *p, const float (&v)[T]) {
     for (int i = 0; i < T; i++) f[i] = v[i];
     *reinterpret_cast<typename VecT<T>::type *>(p) = r;
 }
-#ifndef WIDE_MM_WAVES
-#define WIDE_MM_WAVES 2
-#endif
-// what-if builds (tools/wide_whatif.sh; numerically wrong): -DMM_DIAG_NOBAR drops the iteration's three barriers,
-// -DMM_DIAG_NOMFMA the products, -DMM_DIAG_HOT makes every gather a cache hit
-#ifdef MM_DIAG_NOBAR
-#define MM_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define MM_BARRIER() __syncthreads()
-#endif
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-#ifdef MM_DIAG_NOMFMA
-    c[0] += a * b;
-    return c;
-#else
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#endif
 }
 
 template <int LG, int NC, int EMAX, bool EVL2, bool BYENV = false>
@@ -195,11 +180,7 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
         USample idn[UE];
         auto gather = [&](Slot &q, const USample &sm, int sidx) {
             q.y = sm.y;
-#ifdef MM_DIAG_HOT
-            const int oth = sm.oth & 15;
-#else
             const int oth = sm.oth;
-#endif
             load_row<LG, NC, VEC>(q.qi, t.Qi, oth, t.D, lg);
             const unsigned pso = (unsigned)sm.ps;
             load_row<LG, NC, VEC>(q.qa, t.Qa, oth, t.D, lg);
@@ -208,7 +189,7 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
             // the slot: word 3 of the list entry the ids came from or, inline form, rec_slot[position] -- one load, selected address
             const int *sp = mode == 7 ? reinterpret_cast<const int *>(a.ulist + min(lo + sidx, hi1)) + 3
                                       : reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.rec_slot) + pso * 4u);
-            q.cs = STEP_SLOT_FROM_LIST ? *sp : *reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.rec_slot) + pso * 4u);
+            q.cs = *sp;
         };
         const USample first = mode == 7 ? USample{dd2.x, dd2.y, __builtin_bit_cast(float, dd2.z)}
                                         : USample{dd.z, dd.w, __builtin_bit_cast(float, dd2.x)};
@@ -219,7 +200,7 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
             sl[j].e = sl[j].cs = 0;
             sl[j].y = 0.f;
             sl[j].w = 1.f;
-            if (WIDE_FIRST_FROM_DESC && LG == 16 && j == 0) gather(sl[j], first, 0);
+            if (LG == 16 && j == 0) gather(sl[j], first, 0);
             else gather(sl[j], list_at(j), j);
         }
 #pragma unroll
@@ -312,7 +293,7 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
                 }
             }
             WTRACE(23);
-            MM_BARRIER();
+            __syncthreads();
             WTRACE(24);
             // ---- S2: partial logits of the iteration's interactions over the wave's columns
             {
@@ -331,7 +312,7 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
                     make_float4(z[0] + z1[0], z[1] + z1[1], z[2] + z1[2], z[3] + z1[3]);
             }
             WTRACE(25);
-            MM_BARRIER();
+            __syncthreads();
             WTRACE(27);
             // ---- S3: softmax of every interaction in every wave (lane (n16, kq): classes 4 kq .. 4 kq + 3 of interaction n16)
             {
@@ -418,7 +399,7 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
                 }
             }
             WTRACE(22);
-            MM_BARRIER();
+            __syncthreads();
             WTRACE(24);
             // ---- S5: the rows' gradients with gx = gz W from LDS
             {
@@ -434,8 +415,8 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
                     f4add(gi[j], f4mul(gip, q.qi[j]));
                     f4fma(ge[j], g_q, f4mul(q.qa[j], ev[j]));
                     if (push) {   // the interaction's two contribution rows to its ITEM's gradient, at the item-sorted slot
-                        store4<STEP_PUSH_ST>(cr + 4 * (lg + LG * j), f4mul(gip, oi[j]));
-                        store4<STEP_PUSH_ST>(cr + DP + 4 * (lg + LG * j), f4scale(g_q, f4mul(oe[j], ev[j])));
+                        store4<0>(cr + 4 * (lg + LG * j), f4mul(gip, oi[j]));
+                        store4<0>(cr + DP + 4 * (lg + LG * j), f4scale(g_q, f4mul(oe[j], ev[j])));
                     }
                 }
             }
@@ -568,7 +549,7 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
 }
 
 template <int LG, int NC, int EMAX, bool EVL2, bool BYENV = false>
-__global__ __launch_bounds__(kThreads, WIDE_MM_WAVES) void mstep_eval_mm_kernel(DevTables t, StepArgs a) {
+__global__ __launch_bounds__(kThreads, 2) void mstep_eval_mm_kernel(DevTables t, StepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int ncls = a.n_cls;
     const int c = (int)blockIdx.x % ncls;

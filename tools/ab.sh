@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/ab.sh SPEC... -- the loop benchmark (tools/step_probe.py) once per SPEC (GPU box).
-# SPEC = VARIANT[,ENV=VALUE...]: an A/B build of the library (tools/build_variant.sh; "default" = the shipped one) and
+# SPEC = VARIANT[,ENV=VALUE...]: an A/B build of the library (invpref_kdd_2022_amd/variants/VARIANT.so, made by
+# build.build_variant; "default" = the shipped one) and
 # environment variables for that run (plan parameters INVPREF_PLAN_*, PROBE_SHAPE, PROBE_STAMPS ...).
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out

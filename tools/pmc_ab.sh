@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/pmc_ab.sh VARIANT... -- fabric traffic (WRITE_SIZE, FETCH_SIZE; KiB, FETCH x 2 on gfx950) of the step's kernels per library
-# variant (invpref_kdd_2022_amd/variants/NAME.so, "default" = the shipped one) at PROBE_SHAPE (default: the MIND shape)
+# variant (invpref_kdd_2022_amd/variants/NAME.so, made by build.build_variant; "default" = the shipped one) at PROBE_SHAPE
+# (default: the MIND shape)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 SHAPE=${PROBE_SHAPE:-50000x51283x16x256x262144}

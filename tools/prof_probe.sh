@@ -1,5 +1,6 @@
 #!/bin/bash
-# tools/prof_probe.sh SPEC... -- rocprofv3 per-kernel durations of tools/step_probe.py once per SPEC (see tools/ab.sh)
+# tools/prof_probe.sh SPEC... -- rocprofv3 per-kernel durations of tools/step_probe.py once per SPEC (see tools/ab.sh; the
+# variant libraries are made by build.build_variant)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
