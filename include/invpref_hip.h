@@ -338,6 +338,23 @@ int invpref_eval_topk_hip(const float *ratings, int64_t n_users, int64_t n_items
                           const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
                           float *out_hits, void *stream);
 
+/* ---- fused predict + masked top-k (evaluate.py:88-120 on the scores of models.py:393-407): the result of
+ * invpref_eval_topk_hip(invpref_predict_hip(...)) on the same inputs -- the same items in the same order, the same hit
+ * labels, and out_scores == the masked / highlighted predict values at those items -- straight from the two tables, without
+ * the [n_users, item_num] score matrix: the workspace holds O(n_users * item ranges * k) candidates
+ * (invpref_predict_topk_workspace_bytes, which never falls as n_users grows; 0 for n_users = 0).  Row j of the batch is user
+ * users[j]; mask / highlight / truth are int32 CSR over the batch rows as for invpref_eval_topk_hip, every row sorted
+ * ascending and distinct, and each of the three may be NULL (no train items / no item pool / hits 0).  out_scores and
+ * out_hits may be NULL.  1 <= k <= 64, k <= item_num < 2^31 - 16, factor_num <= INVPREF_MAX_FACTORS (any width: rows are
+ * zero padded to a multiple of 64 on the matrix cores, which keeps the canonical dot product).  Two launches, no host
+ * synchronisation, no allocation: capturable into a graph. */
+size_t invpref_predict_topk_workspace_bytes(int64_t n_users, int64_t item_num, int64_t factor_num, int32_t k);
+int invpref_predict_topk_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
+                             int64_t item_num, int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr,
+                             const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
+                             const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
+                             float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- ExplicitTestManager.evaluate (evaluate.py:187-212): out2 (device double[2]) = {sum (pred-target)^2,
  * sum |pred-target|}; mse / rmse / mae follow on the host. */
 int invpref_eval_error_sums_hip(const float *pred, const float *target, int64_t n, double *out2, void *stream);

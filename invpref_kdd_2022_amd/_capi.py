@@ -29,6 +29,7 @@ EXPORTS = [
     'invpref_adam_ranges_sched_hip', 'invpref_rows_lanes_per_group', 'invpref_estep_perm_hip',
     'invpref_pack_rows_hip', 'invpref_unpack_rows_hip', 'invpref_alt_workspace_bytes', 'invpref_alt_supported',
     'invpref_mstep_alt_hip', 'invpref_alt_error_offset', 'invpref_estep_fused_hip', 'invpref_perm_table_fill',
+    'invpref_predict_topk_workspace_bytes', 'invpref_predict_topk_hip',
 ]
 
 
@@ -121,6 +122,10 @@ def lib():
         L.invpref_estep_fused_hip.argtypes = [C.POINTER(Tables), vp, vp, vp, i64, u32, vp, C.c_int, vp, vp, vp, vp, vp,
                                               C.c_int32, vp, vp, vp, vp, C.c_size_t, vp]
         L.invpref_perm_table_fill.argtypes = [C.c_int32, vp]
+        L.invpref_predict_topk_workspace_bytes.restype = C.c_size_t
+        L.invpref_predict_topk_workspace_bytes.argtypes = [i64, i64, i64, C.c_int32]
+        L.invpref_predict_topk_hip.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp,
+                                               vp, vp, C.c_size_t, vp]
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')
         _lib = L

@@ -89,6 +89,11 @@ class PureMatrixFactorization(_PureMFBase):
         from .autograd import predict_all_items
         return predict_all_items(self.user_emb.weight.detach(), self.item_emb.weight.detach(), users_id, sigmoid=True)
 
+    def recommend(self, users_id, k: int, exclude=None, highlight=None):
+        """Each user's top-k items by the scores of predict() (InvPrefImplicit.recommend)."""
+        t = self.tables()
+        return ops.recommend(t[0], t[1], users_id, k, exclude, highlight)
+
 
 class PureExplicitMatrixFactorization(_PureMFBase):
     """baseline_models.py:652-704"""

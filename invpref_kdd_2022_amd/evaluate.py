@@ -2,8 +2,10 @@
 
 Same constructor signatures and result dictionaries.  The reference walks python lists per test
 user (mask / highlight index lists, ``x in groundTrue``) and builds a ``[n*I, D]`` tensor in
-``model.predict``; here the per-user sets are turned into CSR arrays ONCE, and a test batch is three HIP
-launches: ``predict_kernel`` (rating matrix), ``topk_mask_kernel`` (mask, highlight, top-k, hit labels).
+``model.predict``; here the per-user sets are turned into CSR arrays ONCE.  For the models whose scores are
+sigmoid(user table . item table) (``InvPrefImplicit``, ``PureMatrixFactorization``) the test users are ranked by the fused
+``predict_topk`` operator (``csrc/invpref_retrieve.hip``: scores, mask, highlight, top-k and hit labels without a score
+matrix); any other model's batch is ``model.predict`` (rating matrix) + ``topk_mask_kernel`` / ``topk_select_kernel``.
 The metric formulas (recall / precision / NDCG sums, evaluate.py:22-56) are restated in numpy float64
 on the ``[n, k]`` hit matrix.
 """
@@ -96,22 +98,50 @@ class ImplicitTestManager:
             'invpref_eval_topk_hip')
         return items, hits
 
+    def _fused_tables(self):
+        """(user table, item table) of a model that ranks by sigmoid(user . item), else None."""
+        from .baseline import PureMatrixFactorization
+        from .models import InvPrefImplicit
+        if isinstance(self.model, (InvPrefImplicit, PureMatrixFactorization)):
+            t = self.model.tables()
+            return t[0].detach().contiguous(), t[1].detach().contiguous()
+        return None
+
+    def fused_hits(self, tables) -> np.ndarray:
+        """hits fp32[n_test_users, k] of every test user, ranked by predict_topk in batches bounded by its workspace
+        (O(batch * k), about 256 MiB at most) -- the same labels topk() gives batch by batch."""
+        from .ops import predict_topk
+        d = self._dev
+        n_users, k = self._users.shape[0], max(self.top_k_list)
+        step = max(1, (1 << 28) // (8 * k))
+        out = []
+        for lo in range(0, n_users, step):
+            hi = min(lo + step, n_users)
+            hl = (d['hl_ptr'][lo:hi + 1], d['hl_items']) if self.use_item_pool else None
+            _, _, hits = predict_topk(tables[0], tables[1], self._users[lo:hi], k, True,
+                                      mask=(d['mask_ptr'][lo:hi + 1], d['mask_items']), highlight=hl,
+                                      truth=(d['truth_ptr'][lo:hi + 1], d['truth_items']))
+            out.append(hits.cpu().numpy())
+        return np.concatenate(out)
+
     def evaluate(self) -> dict:
         self.model.eval()
         device = next(self.model.parameters()).device
         if self._dev is None:
             self._prepare(device)
         n_users = self._users.shape[0]
+        tables = self._fused_tables()
+        all_hits = self.fused_hits(tables) if tables is not None else None
         sums = {m: np.zeros(len(self.top_k_list)) for m in ('ndcg', 'recall', 'precision')}
         # test_batch_size bounds the reference's [n * I, D] temporary (models.py:393-407); here a batch is one score matrix of
         # n x I floats and three launches, and the metrics are sums over users -- the same whatever the batch -- so small
-        # batches are merged up to a 1 GiB score matrix (MIND's 256-user batches: 196 launches + read-backs -> 10)
+        # batches are merged up to a 1 GiB score matrix (MIND's 256-user batches: 196 launches + read-backs -> 10).  The
+        # fused path ranks in its own batches but keeps this partition for the float64 metric sums: the same, float for float
         n_items = int(self.model.item_num) if hasattr(self.model, 'item_num') else 1
         step = max(int(self.batch_size), min(n_users, (1 << 28) // max(1, n_items)))
         for lo in range(0, n_users, step):
             hi = min(lo + step, n_users)
-            _, hits = self.topk(lo, hi)
-            h = hits.cpu().numpy()
+            h = all_hits[lo:hi] if all_hits is not None else self.topk(lo, hi)[1].cpu().numpy()
             for i, k in enumerate(self.top_k_list):
                 rec, pre, nd = recall_precision_ndcg(h, self._truth_len[lo:hi], k)
                 sums['recall'][i] += rec

@@ -99,6 +99,13 @@ class InvPrefImplicit(_InvPrefBase):
         return predict_all_items(self.embed_user_invariant.weight.detach(), self.embed_item_invariant.weight.detach(),
                                  users_id, sigmoid=True)
 
+    def recommend(self, users_id, k: int, exclude=None, highlight=None):
+        """Each user's top-k items by the scores of predict(), without the [n, item_num] score matrix: exclude / highlight
+        are CSR pairs (indptr, indices) aligned with users_id -- items set to -1024 / raised by 1024 (evaluate.py:94-111).
+        -> (items int64[n, k], scores fp32[n, k]), descending, lowest item id first among equal scores."""
+        t = self.tables()
+        return ops.recommend(t[0], t[1], users_id, k, exclude, highlight)
+
 
 class InvPrefExplicit(_InvPrefBase):
     """reference models.py:414-543"""

@@ -222,6 +222,42 @@ def predict(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Ten
     return _o().predict(user_table, item_table, users, bool(sigmoid))
 
 
+def predict_topk(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, k: int, sigmoid: bool = True,
+                 mask=None, highlight=None, truth=None):
+    """predict + train-item mask (-1024) + item-pool highlight (+= 1024) + top-k + hit labels (models.py:393-407,
+    evaluate.py:88-120) without the [n, item_num] score matrix.  mask / highlight / truth: None or an int32 CSR pair
+    (indptr[n + 1], indices) over the rows of `users`, every row sorted ascending and distinct.
+    -> (items int32[n, k], scores fp32[n, k], hits fp32[n, k]): descending score, lowest item id first among equal scores."""
+    _gpu(user_table, item_table, users)
+    (mp, mi), (hp, hi), (tp, ti) = [(None, None) if c is None else c for c in (mask, highlight, truth)]
+    return _o().predict_topk(user_table, item_table, users, int(k), bool(sigmoid), mp, mi, hp, hi, tp, ti)
+
+
+def device_csr(csr, n_rows: int, n_items: int, device):
+    """(indptr, indices) of any integer type, on any device -> int32 device CSR with every row sorted ascending (the form
+    predict_topk takes).  Item ids must lie in [0, n_items) and be distinct within a row."""
+    if csr is None:
+        return None
+    indptr, indices = (torch.as_tensor(a).to(device=device, dtype=torch.int64).reshape(-1) for a in csr)
+    if indptr.numel() != n_rows + 1:
+        raise InvPrefError(f'CSR indptr has {indptr.numel()} entries for {n_rows} rows')
+    rows = torch.repeat_interleave(torch.arange(n_rows, device=device), indptr.diff())
+    key = torch.sort(rows * n_items + indices).values    # (rows in order, each row's items ascending)
+    return indptr.to(torch.int32), (key - rows * n_items).to(torch.int32)
+
+
+def recommend(user_table: torch.Tensor, item_table: torch.Tensor, users_id: torch.Tensor, k: int, exclude=None,
+              highlight=None, sigmoid: bool = True):
+    """The top-k items of every user in users_id by sigmoid(user . item): `exclude` items score -1024, `highlight` items
+    += 1024 (evaluate.py:94-111), both CSR pairs aligned with users_id.  -> (items int64[n, k], scores fp32[n, k])."""
+    users = users_id.reshape(-1).to(torch.int64).contiguous()
+    n, I = users.numel(), item_table.shape[0]
+    ut, it = user_table.detach().contiguous(), item_table.detach().contiguous()
+    items, scores, _ = predict_topk(ut, it, users, k, sigmoid, mask=device_csr(exclude, n, I, users.device),
+                                    highlight=device_csr(highlight, n, I, users.device))
+    return items.to(torch.int64), scores
+
+
 def rows_workspace(params, dplan, workspace: Workspace, pure: bool = False) -> torch.Tensor:
     """the scratch of the planned M-step (per-interaction records + per-workgroup partial slabs)"""
     t = (_capi.make_pure_tables if (pure or len(params) == 2) else make_tables)(params)

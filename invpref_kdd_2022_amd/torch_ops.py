@@ -25,6 +25,8 @@ What replaces what in the reference:
 ``sample_weights``             its weight half from global counts (multi-GPU)
 ``forward`` / ``backward``     ``InvPref*.forward`` values (models.py:307-326, :448-467) and its backward
 ``predict``                    ``InvPrefImplicit.predict`` (models.py:393-407)
+``predict_topk``               ``predict`` + train-item mask + item-pool highlight + top-k + hit labels
+                               (models.py:393-407, evaluate.py:88-120) without the score matrix: (items, scores, hits)
 =============================  =====================================================================================
 
 Tensors are borrowed for the call and never retained.  ``workspace`` arguments are caller-owned scratch (uint8),
@@ -550,3 +552,51 @@ def _predict(user_table, item_table, users, sigmoid):
 @_fake('predict')
 def _predict_fake(user_table, item_table, users, sigmoid):
     return torch.empty(users.numel(), item_table.shape[0], dtype=torch.float32, device=users.device)
+
+
+# ------------------------------------------------------------------------------------------------ predict_topk
+_define('predict_topk(Tensor user_table, Tensor item_table, Tensor users, int k, bool sigmoid, Tensor? mask_ptr, '
+        'Tensor? mask_items, Tensor? highlight_ptr, Tensor? highlight_items, Tensor? truth_ptr, Tensor? truth_items) '
+        '-> (Tensor, Tensor, Tensor)')
+
+
+def _csr_pair(p, items, name):
+    if (p is None) != (items is None):
+        raise InvPrefError(f'{name}: give both the row pointers and the items, or neither')
+    if p is None:
+        return None, None
+    _capi._req(p, torch.int32, name + '_ptr')
+    _capi._req(items, torch.int32, name + '_items')
+    if items.numel() == 0:   # (a zero-length tensor has no valid pointer; the row pointers keep it unread)
+        items = torch.zeros(1, dtype=torch.int32, device=p.device)
+    return p, items
+
+
+@_impl('predict_topk')
+def _predict_topk(user_table, item_table, users, k, sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items,
+                  truth_ptr, truth_items):
+    _f32(user_table, 'user_table'); _f32(item_table, 'item_table')
+    n, (I, D) = users.numel(), item_table.shape
+    mp, mi = _csr_pair(mask_ptr, mask_items, 'mask')
+    hp, hi = _csr_pair(highlight_ptr, highlight_items, 'highlight')
+    tp, ti = _csr_pair(truth_ptr, truth_items, 'truth')
+    dev = users.device
+    items = torch.empty(n, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, k, dtype=torch.float32, device=dev)
+    hits = torch.empty(n, k, dtype=torch.float32, device=dev)
+    L = lib()
+    nbytes = L.invpref_predict_topk_workspace_bytes(n, I, D, k)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)   # (the caching allocator's memory)
+    check(L.invpref_predict_topk_hip(ptr(user_table), ptr(item_table), ptr(_ids(users, 'users')), n, I, D, int(bool(sigmoid)),
+                                     ptr(mp), ptr(mi), ptr(hp), ptr(hi), ptr(tp), ptr(ti), k, ptr(items), ptr(scores),
+                                     ptr(hits), ptr(ws), nbytes, stream_ptr()), 'invpref_predict_topk_hip')
+    return items, scores, hits
+
+
+@_fake('predict_topk')
+def _predict_topk_fake(user_table, item_table, users, k, sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items,
+                       truth_ptr, truth_items):
+    n = users.numel()
+    f = dict(device=users.device)
+    return (torch.empty(n, k, dtype=torch.int32, **f), torch.empty(n, k, dtype=torch.float32, **f),
+            torch.empty(n, k, dtype=torch.float32, **f))
