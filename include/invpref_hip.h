@@ -355,6 +355,23 @@ int invpref_predict_topk_hip(const float *user_table, const float *item_table, c
                              const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
                              float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the ranking metrics of ImplicitTestManager.evaluate (evaluate.py:22-56, :137-175) from the hit labels the two entry
+ * points above leave on the device.  hits: fp32 [n_users, ld] (row stride ld >= K), 0.0 / 1.0 labels of each user's top K;
+ * truth_ptr: int32 [n_users + 1], the user's ground-truth length is truth_ptr[j + 1] - truth_ptr[j] (any base).  ks: a HOST
+ * array of n_k sorted k values, 1 <= k <= K <= 64, duplicates allowed, n_k <= 64.  disc: device double [n_k, 64], row i =
+ * 1 / log2(j + 2) for j < ks[i]; idcg: device double [n_k, 65], row i entry L = the ideal DCG of min(L, ks[i]) relevant items
+ * (1.0 for L = 0) -- both computed by numpy as recall_precision_ndcg computes them, never by the device.  The users are cut
+ * into partitions of `partition` users (the last may be shorter).  out (device double [3, n_k]) = the sums over the users of
+ * recall@k, precision@k and NDCG@k, each accumulated in exactly numpy's order: per user numpy's row sum, per partition
+ * np.sum (8192-element chunks, each a pairwise sum), then the partition sums in order from +0.0.  A user
+ * without ground truth makes the recall sum NaN, as in numpy.  Workspace: invpref_rank_metrics_workspace_bytes (never
+ * falls as n_users grows; 0 for n_users = 0, which writes zeros).  Three launches, no host synchronisation, no allocation:
+ * capturable into a graph. */
+size_t invpref_rank_metrics_workspace_bytes(int64_t n_users, int32_t n_k, int64_t partition);
+int invpref_rank_metrics_hip(const float *hits, int64_t n_users, int64_t ld, int32_t K, const int32_t *truth_ptr,
+                             const int32_t *ks, int32_t n_k, const double *disc, const double *idcg, int64_t partition,
+                             double *out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- ExplicitTestManager.evaluate (evaluate.py:187-212): out2 (device double[2]) = {sum (pred-target)^2,
  * sum |pred-target|}; mse / rmse / mae follow on the host. */
 int invpref_eval_error_sums_hip(const float *pred, const float *target, int64_t n, double *out2, void *stream);

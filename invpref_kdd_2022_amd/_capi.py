@@ -29,7 +29,8 @@ EXPORTS = [
     'invpref_adam_ranges_sched_hip', 'invpref_rows_lanes_per_group', 'invpref_estep_perm_hip',
     'invpref_pack_rows_hip', 'invpref_unpack_rows_hip', 'invpref_alt_workspace_bytes', 'invpref_alt_supported',
     'invpref_mstep_alt_hip', 'invpref_alt_error_offset', 'invpref_estep_fused_hip', 'invpref_perm_table_fill',
-    'invpref_predict_topk_workspace_bytes', 'invpref_predict_topk_hip',
+    'invpref_predict_topk_workspace_bytes', 'invpref_predict_topk_hip', 'invpref_rank_metrics_workspace_bytes',
+    'invpref_rank_metrics_hip',
 ]
 
 
@@ -126,6 +127,9 @@ def lib():
         L.invpref_predict_topk_workspace_bytes.argtypes = [i64, i64, i64, C.c_int32]
         L.invpref_predict_topk_hip.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp,
                                                vp, vp, C.c_size_t, vp]
+        L.invpref_rank_metrics_workspace_bytes.restype = C.c_size_t
+        L.invpref_rank_metrics_workspace_bytes.argtypes = [i64, C.c_int32, i64]
+        L.invpref_rank_metrics_hip.argtypes = [vp, i64, i64, C.c_int32, vp, vp, C.c_int32, vp, vp, i64, vp, vp, C.c_size_t, vp]
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')
         _lib = L

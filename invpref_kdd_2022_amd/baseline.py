@@ -207,10 +207,13 @@ class _BasicTrainManager(_InvPrefTrainManager):
     def train(self, silent: bool = False, auto: bool = False):
         """train.py:428-461: ((loss dicts, epochs), (test results, epochs))."""
         test_result_list, test_epoch_list, loss_result_list, train_epoch_index_list = [], [], [], []
+        defer = bool(silent or auto)
+        # deferred: an evaluator with evaluate_async enqueues, and its results are read back at the end with the losses
+        evaluate_async = getattr(self.evaluator, 'evaluate_async', None) if defer else None
 
         def evaluate():
             self.sync_parameters()
-            res = self.evaluator.evaluate()
+            res = evaluate_async() if evaluate_async is not None else self.evaluator.evaluate()
             test_result_list.append(res)
             test_epoch_list.append(self.epoch_cnt)
             if not silent and not auto:
@@ -218,7 +221,6 @@ class _BasicTrainManager(_InvPrefTrainManager):
                 print(transfer_loss_dict_to_line_str(res))
 
         evaluate()
-        defer = bool(silent or auto)
         while self.epoch_cnt < self.epochs:
             first = self.epoch_cnt + 1
             run = self.train_epochs(self._epochs_to_next_event(), sync=not defer)
@@ -234,6 +236,8 @@ class _BasicTrainManager(_InvPrefTrainManager):
         self._check_alt_error()   # (PureMF launches wait for nothing inside a launch: the word can only be set by another user of the workspace)
         if defer and loss_result_list:
             loss_result_list = self.loss_dicts(torch.stack(loss_result_list))
+        if evaluate_async is not None:
+            test_result_list = [p.result() for p in test_result_list]
         return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
 
     # the InvPref-only parts of the engine do not exist here

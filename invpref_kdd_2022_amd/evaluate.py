@@ -6,8 +6,10 @@ user (mask / highlight index lists, ``x in groundTrue``) and builds a ``[n*I, D]
 sigmoid(user table . item table) (``InvPrefImplicit``, ``PureMatrixFactorization``) the test users are ranked by the fused
 ``predict_topk`` operator (``csrc/invpref_retrieve.hip``: scores, mask, highlight, top-k and hit labels without a score
 matrix); any other model's batch is ``model.predict`` (rating matrix) + ``topk_mask_kernel`` / ``topk_select_kernel``.
-The metric formulas (recall / precision / NDCG sums, evaluate.py:22-56) are restated in numpy float64
-on the ``[n, k]`` hit matrix.
+The hit labels stay on the device: the recall / precision / NDCG sums (evaluate.py:22-56) come from the ``rank_metrics``
+kernels (``csrc/invpref_metrics.hip``) in numpy's float64 order, and the host reads back 3 x n_k doubles.
+``recall_precision_ndcg`` keeps the numpy statement of the formulas that order is held to.  ``evaluate_async()`` enqueues
+an evaluation without waiting for it (the training loops' deferred mode).
 """
 from __future__ import annotations
 
@@ -81,6 +83,8 @@ class ImplicitTestManager:
                 self._dev[k] = torch.zeros(1, dtype=torch.int32, device=device)
         self._users = torch.as_tensor(np.asarray(users, np.int64)).to(device)
         self._truth_len = np.asarray(truth_len, np.float64)
+        from .ops import rank_metric_tables
+        rank_metric_tables(self.top_k_list, device)   # (uploaded here, once: evaluate_async() copies nothing from the host)
 
     def topk(self, lo: int, hi: int):
         """(items int32[n,k], hits fp32[n,k]) for test users [lo, hi) of the sorted list."""
@@ -107,8 +111,8 @@ class ImplicitTestManager:
             return t[0].detach().contiguous(), t[1].detach().contiguous()
         return None
 
-    def fused_hits(self, tables) -> np.ndarray:
-        """hits fp32[n_test_users, k] of every test user, ranked by predict_topk in batches bounded by its workspace
+    def _fused_hits_device(self, tables) -> torch.Tensor:
+        """hits fp32[n_test_users, k] on the device, ranked by predict_topk in batches bounded by its workspace
         (O(batch * k), about 256 MiB at most) -- the same labels topk() gives batch by batch."""
         from .ops import predict_topk
         d = self._dev
@@ -121,33 +125,62 @@ class ImplicitTestManager:
             _, _, hits = predict_topk(tables[0], tables[1], self._users[lo:hi], k, True,
                                       mask=(d['mask_ptr'][lo:hi + 1], d['mask_items']), highlight=hl,
                                       truth=(d['truth_ptr'][lo:hi + 1], d['truth_items']))
-            out.append(hits.cpu().numpy())
-        return np.concatenate(out)
+            out.append(hits)
+        if not out:
+            return torch.empty(0, k, dtype=torch.float32, device=self._users.device)
+        return out[0] if len(out) == 1 else torch.cat(out)
 
-    def evaluate(self) -> dict:
+    def fused_hits(self, tables) -> np.ndarray:
+        """hits fp32[n_test_users, k] of every test user (numpy), ranked by predict_topk (_fused_hits_device)"""
+        return self._fused_hits_device(tables).cpu().numpy()
+
+    def evaluate_async(self) -> 'PendingEvaluation':
+        """Enqueues the whole evaluation on the current stream and returns at once: the hit labels stay on the device and
+        go straight into the rank_metrics kernels (csrc/invpref_metrics.hip), whose float64 sums are numpy's, bit for bit.
+        The returned object's result() reads the 3 x n_k sums back once and builds evaluate()'s dictionary.  After the
+        first call (which uploads the CSR arrays and the metric tables) this enqueues no copy from the host and never
+        synchronises: it can be captured into a graph."""
+        from . import ops
         self.model.eval()
         device = next(self.model.parameters()).device
         if self._dev is None:
             self._prepare(device)
-        n_users = self._users.shape[0]
-        tables = self._fused_tables()
-        all_hits = self.fused_hits(tables) if tables is not None else None
-        sums = {m: np.zeros(len(self.top_k_list)) for m in ('ndcg', 'recall', 'precision')}
+        n_users, k = self._users.shape[0], max(self.top_k_list)
         # test_batch_size bounds the reference's [n * I, D] temporary (models.py:393-407); here a batch is one score matrix of
         # n x I floats and three launches, and the metrics are sums over users -- the same whatever the batch -- so small
-        # batches are merged up to a 1 GiB score matrix (MIND's 256-user batches: 196 launches + read-backs -> 10).  The
-        # fused path ranks in its own batches but keeps this partition for the float64 metric sums: the same, float for float
+        # batches are merged up to a 1 GiB score matrix (MIND's 256-user batches: 196 launches -> 10).  The fused path ranks in
+        # its own batches; the float64 metric sums keep this partition either way, so the result is the same, float for float
         n_items = int(self.model.item_num) if hasattr(self.model, 'item_num') else 1
         step = max(int(self.batch_size), min(n_users, (1 << 28) // max(1, n_items)))
-        for lo in range(0, n_users, step):
-            hi = min(lo + step, n_users)
-            h = all_hits[lo:hi] if all_hits is not None else self.topk(lo, hi)[1].cpu().numpy()
-            for i, k in enumerate(self.top_k_list):
-                rec, pre, nd = recall_precision_ndcg(h, self._truth_len[lo:hi], k)
-                sums['recall'][i] += rec
-                sums['precision'][i] += pre
-                sums['ndcg'][i] += nd
-        return {m: {k: float(v[i] / float(n_users)) for i, k in enumerate(self.top_k_list)} for m, v in sums.items()}
+        tables = self._fused_tables()
+        if tables is not None:
+            hits = self._fused_hits_device(tables)
+        else:
+            parts = [self.topk(lo, min(lo + step, n_users))[1] for lo in range(0, n_users, step)]
+            hits = (parts[0] if len(parts) == 1 else torch.cat(parts)) if parts else \
+                torch.empty(0, k, dtype=torch.float32, device=device)
+        out = ops.rank_metric_sums(hits, self._dev['truth_ptr'], self.top_k_list, step)
+        top_k_list = list(self.top_k_list)
+
+        def finish(host: torch.Tensor) -> dict:
+            s = host.numpy()   # rows recall, precision, NDCG: each the sum evaluate() accumulated in np.zeros, in order
+            sums = {'ndcg': s[2], 'recall': s[0], 'precision': s[1]}
+            return {m: {k: float(v[i] / float(n_users)) for i, k in enumerate(top_k_list)} for m, v in sums.items()}
+        return PendingEvaluation(out, finish)
+
+    def evaluate(self) -> dict:
+        return self.evaluate_async().result()
+
+
+class PendingEvaluation:
+    """An evaluation enqueued by evaluate_async(): its output buffer stays on the device until result() reads it back
+    (once per call -- after a graph replay, result() reads what the replay wrote) and builds evaluate()'s dictionary."""
+
+    def __init__(self, out: torch.Tensor, finish):
+        self._out, self._finish = out, finish
+
+    def result(self) -> dict:
+        return self._finish(self._out.cpu())
 
 
 class ExplicitTestManager:
@@ -155,16 +188,33 @@ class ExplicitTestManager:
         self.model = model
         self.data_loader = data_loader
 
-    def evaluate(self) -> dict:
+    def _test_pairs(self, device):
+        """(users, items, target) of the loader's test pairs on `device`, copied once and kept until the loader's tensors
+        are replaced or written in place (identity + _version): evaluate_async() enqueues no copy from the host"""
+        pairs, scores = self.data_loader.all_test_pairs_tensor, self.data_loader.all_test_scores_tensor
+        c = getattr(self, '_pairs_cache', None)
+        if c is None or c[0] is not pairs or c[1] is not scores or c[2] != (pairs._version, scores._version, device):
+            p = pairs.to(device)
+            users, items = p[:, 0].reshape(-1).contiguous(), p[:, 1].reshape(-1).contiguous()
+            target = scores.to(device).float().contiguous()
+            self._pairs_cache = c = (pairs, scores, (pairs._version, scores._version, device), (users, items, target))
+        return c[3]
+
+    def evaluate_async(self) -> PendingEvaluation:
+        """Enqueues the prediction and the error sums; result() reads the two sums back and builds evaluate()'s dictionary"""
         self.model.eval()
         device = next(self.model.parameters()).device
-        pairs = self.data_loader.all_test_pairs_tensor.to(device)
-        users, items = pairs[:, 0].reshape(-1).contiguous(), pairs[:, 1].reshape(-1).contiguous()
-        target = self.data_loader.all_test_scores_tensor.to(device).float().contiguous()
+        users, items, target = self._test_pairs(device)
         pred = self.model.predict(users, items)
         out = torch.empty(2, dtype=torch.float64, device=device)
         check(lib().invpref_eval_error_sums_hip(ptr(pred), ptr(target), pred.numel(), ptr(out), stream_ptr()),
               'invpref_eval_error_sums_hip')
-        s2, s1 = out.tolist()
         n = float(pred.numel())
-        return {'mse': s2 / n, 'rmse': float(np.sqrt(s2 / n)), 'mae': s1 / n}
+
+        def finish(host: torch.Tensor) -> dict:
+            s2, s1 = host.tolist()
+            return {'mse': s2 / n, 'rmse': float(np.sqrt(s2 / n)), 'mae': s1 / n}
+        return PendingEvaluation(out, finish)
+
+    def evaluate(self) -> dict:
+        return self.evaluate_async().result()

@@ -233,6 +233,43 @@ def predict_topk(user_table: torch.Tensor, item_table: torch.Tensor, users: torc
     return _o().predict_topk(user_table, item_table, users, int(k), bool(sigmoid), mp, mi, hp, hi, tp, ti)
 
 
+_RANK_TABLES = {}
+
+
+def rank_metric_tables(top_k_list, device):
+    """(disc float64[n_k, 64], idcg float64[n_k, 65]) of rank_metrics on `device`, computed by numpy exactly as
+    recall_precision_ndcg computes them (evaluate.py) and cached per k list: row i of disc is 1 / log2(j + 2) for j < k,
+    entry L of idcg row i the ideal DCG of min(L, k) relevant items (1.0 for L = 0).  The first call for a k list copies
+    to the device; later calls enqueue nothing (capturable)."""
+    import numpy as np
+    ks = tuple(int(k) for k in top_k_list)
+    device = torch.device(device)
+    key = (ks, device)
+    if key not in _RANK_TABLES:
+        disc = np.zeros((len(ks), 64))
+        idcg = np.ones((len(ks), 65))
+        for i, k in enumerate(ks):
+            if not 1 <= k <= 64:
+                raise InvPrefError(f'rank metrics take 1 <= k <= 64, got {k}')
+            d = 1.0 / np.log2(np.arange(2, k + 2))
+            ideal = (np.arange(k)[None, :] < np.arange(k + 1)[:, None]).astype(np.float64)
+            ig = (ideal * d).sum(1)
+            ig[ig == 0.] = 1.
+            disc[i, :k], idcg[i, :k + 1] = d, ig
+        _RANK_TABLES[key] = (torch.from_numpy(disc).to(device), torch.from_numpy(idcg).to(device))
+    return _RANK_TABLES[key]
+
+
+def rank_metric_sums(hits: torch.Tensor, truth_ptr: torch.Tensor, top_k_list, partition: int) -> torch.Tensor:
+    """The recall / precision / NDCG sums of ImplicitTestManager.evaluate() (evaluate.py:22-56, :137-175) over the rows of
+    hits (fp32 [n, K] 0/1 labels; row stride allowed) with truth lengths diff(truth_ptr) (int32 [n + 1], any base), the
+    users cut into partitions of `partition` rows, numpy's float64 order throughout.  -> float64 [3, n_k] on the device:
+    rows recall, precision, NDCG; column i for top_k_list[i] (sorted, duplicates allowed, k <= K <= 64)."""
+    _gpu(hits, truth_ptr)
+    disc, idcg = rank_metric_tables(top_k_list, hits.device)
+    return _o().rank_metrics(hits, truth_ptr, [int(k) for k in top_k_list], disc, idcg, int(partition))
+
+
 def device_csr(csr, n_rows: int, n_items: int, device):
     """(indptr, indices) of any integer type, on any device -> int32 device CSR with every row sorted ascending (the form
     predict_topk takes).  Item ids must lie in [0, n_items) and be distinct within a row."""

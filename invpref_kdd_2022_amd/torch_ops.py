@@ -27,6 +27,8 @@ What replaces what in the reference:
 ``predict``                    ``InvPrefImplicit.predict`` (models.py:393-407)
 ``predict_topk``               ``predict`` + train-item mask + item-pool highlight + top-k + hit labels
                                (models.py:393-407, evaluate.py:88-120) without the score matrix: (items, scores, hits)
+``rank_metrics``               the recall / precision / NDCG sums of ``evaluate()`` from the hit labels, in numpy's float64
+                               order (evaluate.py:22-56, :137-175): float64 ``[3, n_k]``
 =============================  =====================================================================================
 
 Tensors are borrowed for the call and never retained.  ``workspace`` arguments are caller-owned scratch (uint8),
@@ -600,3 +602,36 @@ def _predict_topk_fake(user_table, item_table, users, k, sigmoid, mask_ptr, mask
     f = dict(device=users.device)
     return (torch.empty(n, k, dtype=torch.int32, **f), torch.empty(n, k, dtype=torch.float32, **f),
             torch.empty(n, k, dtype=torch.float32, **f))
+
+
+# ------------------------------------------------------------------------------------------------ rank_metrics
+_define('rank_metrics(Tensor hits, Tensor truth_ptr, int[] ks, Tensor disc, Tensor idcg, int partition) -> Tensor')
+
+
+@_impl('rank_metrics')
+def _rank_metrics(hits, truth_ptr, ks, disc, idcg, partition):
+    if hits.dim() != 2 or hits.dtype != torch.float32 or not hits.is_cuda or (hits.shape[0] > 0 and hits.stride(1) != 1):
+        raise InvPrefError('hits must be a CUDA float32 [n, K] tensor with unit column stride')
+    n, K = hits.shape
+    nk = len(ks)
+    _capi._req(truth_ptr, torch.int32, 'truth_ptr')
+    if truth_ptr.numel() != n + 1:
+        raise InvPrefError(f'truth_ptr has {truth_ptr.numel()} entries for {n} users')
+    for t, name, w in ((disc, 'disc', 64), (idcg, 'idcg', 65)):
+        _capi._req(t, torch.float64, name)
+        if tuple(t.shape) != (nk, w):
+            raise InvPrefError(f'{name} must be [{nk}, {w}], got {tuple(t.shape)}')
+    out = torch.empty(3, nk, dtype=torch.float64, device=hits.device)
+    L = lib()
+    nbytes = L.invpref_rank_metrics_workspace_bytes(n, nk, partition)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=hits.device)
+    karr = (C.c_int32 * max(nk, 1))(*ks)
+    check(L.invpref_rank_metrics_hip(ptr(hits), n, hits.stride(0) if n > 0 else K, K, ptr(truth_ptr),
+                                     C.cast(karr, C.c_void_p), nk, ptr(disc), ptr(idcg), int(partition), ptr(out), ptr(ws),
+                                     nbytes, stream_ptr()), 'invpref_rank_metrics_hip')
+    return out
+
+
+@_fake('rank_metrics')
+def _rank_metrics_fake(hits, truth_ptr, ks, disc, idcg, partition):
+    return torch.empty(3, len(ks), dtype=torch.float64, device=hits.device)

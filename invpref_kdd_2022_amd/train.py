@@ -1220,10 +1220,17 @@ class _InvPrefTrainManager:
         test_result_list, test_epoch_list = [], []
         cluster_diff_num_list, cluster_epoch_list, envs_cnt_list = [], [], []
         loss_result_list, train_epoch_index_list = [], []
+        # nothing printed -> nothing is read back inside the loop (losses, diff_num, env counts and -- from an evaluator
+        # with evaluate_async -- the evaluations stay on the device until the end): the GPU never waits for the host
+        # between epochs, E-steps and evaluations.  An evaluator without evaluate_async is called synchronously.
+        defer = bool(silent or auto)
+        evaluate = getattr(self.evaluator, 'evaluate_async', None) if defer else None
+        pending = evaluate is not None
+        evaluate = evaluate or self.evaluator.evaluate
 
         if initial:
             self.sync_parameters()
-            temp_eval_result = self.evaluator.evaluate()
+            temp_eval_result = evaluate()
             test_result_list.append(temp_eval_result)
             test_epoch_list.append(self.epoch_cnt)
             self.stat_envs()
@@ -1231,10 +1238,6 @@ class _InvPrefTrainManager:
                 print('test at epoch:', self.epoch_cnt)
                 print(transfer_loss_dict_to_line_str(temp_eval_result))
 
-        # nothing printed -> nothing is read back inside the loop (losses, diff_num and env counts stay on
-        # the device until the end, or until an evaluation needs the host anyway): the GPU never waits
-        # for the host between epochs and E-steps
-        defer = bool(silent or auto)
         while self.epoch_cnt < self.epochs:
             # the epochs up to the next evaluate/cluster event are enqueued together (one read-back);
             # the records and the printed lines are the same, in the same order, as one epoch at a time
@@ -1249,7 +1252,7 @@ class _InvPrefTrainManager:
 
             if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
                 self.sync_parameters()
-                temp_eval_result = self.evaluator.evaluate()
+                temp_eval_result = evaluate()
                 test_result_list.append(temp_eval_result)
                 test_epoch_list.append(self.epoch_cnt)
                 if not silent and not auto:
@@ -1283,6 +1286,8 @@ class _InvPrefTrainManager:
             cluster_diff_num_list = [int(d.item()) if torch.is_tensor(d) else d for d in cluster_diff_num_list]
             envs_cnt_list = [{env: int(c) for env, c in enumerate(t.tolist() if torch.is_tensor(t) else t)}
                              for t in envs_cnt_list]
+            if pending:
+                test_result_list = [p.result() for p in test_result_list]
 
         return (loss_result_list, train_epoch_index_list), \
                (test_result_list, test_epoch_list), \
