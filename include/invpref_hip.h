@@ -372,6 +372,44 @@ int invpref_rank_metrics_hip(const float *hits, int64_t n_users, int64_t ld, int
                              const int32_t *ks, int32_t n_k, const double *disc, const double *idcg, int64_t partition,
                              double *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- top-k beyond 64 (evaluate.py:112 ranks with torch.topk for any k): the wide forms of the three entry points above, for
+ * 1 <= k <= INVPREF_MAX_TOPK_WIDE.  Same semantics: train items := -1024, then pool items += 1024; value descending (-0 == +0,
+ * a NaN below every number), the lowest item id first among equal values; hits looked up in the sorted truth list.
+ *
+ * invpref_topk_rows_hip: the top k of every row of a score matrix ratings[n_rows, ld] (row stride ld >= n_items; not modified).
+ * mask / highlight / truth: int32 CSR over the rows as for invpref_eval_topk_hip; each may be NULL.  Outputs [n_rows, k]:
+ * out_items, out_scores (the masked / highlighted values; may be NULL), out_hits (may be NULL; 0 without truth).
+ * k <= n_items < 2^31 - 16, no ceiling on n_items: the mask / highlight bit sets are in LDS up to 2^19 items, else in the
+ * workspace (invpref_topk_rows_workspace_bytes: 0 up to 2^19 items; never falls as n_rows grows).  One launch. */
+#define INVPREF_MAX_TOPK_WIDE 1024
+size_t invpref_topk_rows_workspace_bytes(int64_t n_rows, int64_t n_items, int32_t k);
+int invpref_topk_rows_hip(const float *ratings, int64_t n_rows, int64_t n_items, int64_t ld, const int32_t *mask_ptr,
+                          const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
+                          const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
+                          float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream);
+
+/* invpref_predict_topk_wide_hip: the arguments and output contract of invpref_predict_topk_hip for k <= INVPREF_MAX_TOPK_WIDE.
+ * The users are scored in chunks of about 256 MiB by invpref_predict_hip (the canonical dot product: out_scores are the
+ * values invpref_predict_topk_hip gives) into the workspace, then ranked by invpref_topk_rows_hip.  Workspace:
+ * invpref_predict_topk_wide_workspace_bytes -- one chunk of scores plus its bit sets; it never scales with
+ * n_users x item_num and never falls as n_users grows.  Two launches per chunk, no host synchronisation, no allocation:
+ * capturable into a graph. */
+size_t invpref_predict_topk_wide_workspace_bytes(int64_t n_users, int64_t item_num, int64_t factor_num, int32_t k);
+int invpref_predict_topk_wide_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
+                                  int64_t item_num, int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr,
+                                  const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
+                                  const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
+                                  float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream);
+
+/* invpref_rank_metrics_wide_hip: invpref_rank_metrics_hip for 1 <= k <= K <= INVPREF_MAX_TOPK_WIDE (n_k <= 64).  disc is
+ * [n_k, disc_ld] with disc_ld >= ks[n_k - 1], idcg [n_k, idcg_ld] with idcg_ld >= ks[n_k - 1] + 1, filled as for
+ * invpref_rank_metrics_hip.  The per-user dcg sum follows numpy's pairwise recursion above 128 elements (split at
+ * n2 = m / 2 - (m / 2) % 8), so the sums stay numpy's, bit for bit.  Workspace: invpref_rank_metrics_workspace_bytes. */
+int invpref_rank_metrics_wide_hip(const float *hits, int64_t n_users, int64_t ld, int32_t K, const int32_t *truth_ptr,
+                                  const int32_t *ks, int32_t n_k, const double *disc, int64_t disc_ld, const double *idcg,
+                                  int64_t idcg_ld, int64_t partition, double *out, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+
 /* ---- ExplicitTestManager.evaluate (evaluate.py:187-212): out2 (device double[2]) = {sum (pred-target)^2,
  * sum |pred-target|}; mse / rmse / mae follow on the host. */
 int invpref_eval_error_sums_hip(const float *pred, const float *target, int64_t n, double *out2, void *stream);

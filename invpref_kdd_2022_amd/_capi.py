@@ -30,8 +30,11 @@ EXPORTS = [
     'invpref_pack_rows_hip', 'invpref_unpack_rows_hip', 'invpref_alt_workspace_bytes', 'invpref_alt_supported',
     'invpref_mstep_alt_hip', 'invpref_alt_error_offset', 'invpref_estep_fused_hip', 'invpref_perm_table_fill',
     'invpref_predict_topk_workspace_bytes', 'invpref_predict_topk_hip', 'invpref_rank_metrics_workspace_bytes',
-    'invpref_rank_metrics_hip',
+    'invpref_rank_metrics_hip', 'invpref_topk_rows_workspace_bytes', 'invpref_topk_rows_hip',
+    'invpref_predict_topk_wide_workspace_bytes', 'invpref_predict_topk_wide_hip', 'invpref_rank_metrics_wide_hip',
 ]
+MAX_TOPK = 64          # k of the fused scan / k-pass / radix-select kernels and the 64-wide metric tables
+MAX_TOPK_WIDE = 1024   # INVPREF_MAX_TOPK_WIDE: the wide entry points (csrc/invpref_topk_wide.hip)
 
 
 class InvPrefError(RuntimeError):
@@ -130,6 +133,14 @@ def lib():
         L.invpref_rank_metrics_workspace_bytes.restype = C.c_size_t
         L.invpref_rank_metrics_workspace_bytes.argtypes = [i64, C.c_int32, i64]
         L.invpref_rank_metrics_hip.argtypes = [vp, i64, i64, C.c_int32, vp, vp, C.c_int32, vp, vp, i64, vp, vp, C.c_size_t, vp]
+        L.invpref_topk_rows_workspace_bytes.restype = C.c_size_t
+        L.invpref_topk_rows_workspace_bytes.argtypes = [i64, i64, C.c_int32]
+        L.invpref_topk_rows_hip.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_size_t, vp]
+        L.invpref_predict_topk_wide_workspace_bytes.restype = C.c_size_t
+        L.invpref_predict_topk_wide_workspace_bytes.argtypes = [i64, i64, i64, C.c_int32]
+        L.invpref_predict_topk_wide_hip.argtypes = L.invpref_predict_topk_hip.argtypes
+        L.invpref_rank_metrics_wide_hip.argtypes = [vp, i64, i64, C.c_int32, vp, vp, C.c_int32, vp, i64, vp, i64, i64, vp, vp,
+                                                    C.c_size_t, vp]
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')
         _lib = L

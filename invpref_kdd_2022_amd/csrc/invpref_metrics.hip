@@ -239,6 +239,22 @@ size_t bytes_for(int64_t n, int n_k, int64_t partition) {
 
 }  // namespace
 
+namespace invpref {
+// stages 2 and 3 on per-user values that another stage 1 left in the workspace (invpref_topk_wide.hip: K > 64)
+size_t rank_metrics_bytes(int64_t n_users, int n_k, int64_t partition) { return bytes_for(n_users, n_k, partition); }
+
+int rank_metrics_reduce(const double *vals, int64_t n_users, int n_k, int64_t partition, double *csum, double *out,
+                        hipStream_t st) {
+    const Geometry g = geometry(n_users, partition);
+    if (n_users > 0)
+        hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)(g.n_parts * g.chunks_per), (unsigned)(3 * n_k)), dim3(64), 0, st,
+                           vals, n_users, partition, g.chunks_per, csum);
+    hipLaunchKernelGGL(partition_sum_kernel, dim3(1), dim3(256), 0, st, csum, n_users, partition, g.n_parts, g.chunks_per,
+                       3 * n_k, out);
+    return (int)hipGetLastError();
+}
+}  // namespace invpref
+
 extern "C" {
 
 size_t invpref_rank_metrics_workspace_bytes(int64_t n_users, int32_t n_k, int64_t partition) {

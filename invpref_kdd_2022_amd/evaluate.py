@@ -6,6 +6,8 @@ user (mask / highlight index lists, ``x in groundTrue``) and builds a ``[n*I, D]
 sigmoid(user table . item table) (``InvPrefImplicit``, ``PureMatrixFactorization``) the test users are ranked by the fused
 ``predict_topk`` operator (``csrc/invpref_retrieve.hip``: scores, mask, highlight, top-k and hit labels without a score
 matrix); any other model's batch is ``model.predict`` (rating matrix) + ``topk_mask_kernel`` / ``topk_select_kernel``.
+Beyond k = 64 (or 400 000 items on the rating-matrix path) both routes rank with the radix select of
+``csrc/invpref_topk_wide.hip``, for any ``top_k_list`` up to k = 1024.
 The hit labels stay on the device: the recall / precision / NDCG sums (evaluate.py:22-56) come from the ``rank_metrics``
 kernels (``csrc/invpref_metrics.hip``) in numpy's float64 order, and the host reads back 3 x n_k doubles.
 ``recall_precision_ndcg`` keeps the numpy statement of the formulas that order is held to.  ``evaluate_async()`` enqueues
@@ -18,7 +20,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._capi import check, lib, ptr, stream_ptr
+from ._capi import MAX_TOPK, check, lib, ptr, stream_ptr
 
 
 def _csr(sets, n_items=None) -> tuple[np.ndarray, np.ndarray]:
@@ -92,6 +94,12 @@ class ImplicitTestManager:
         users = self._users[lo:hi].contiguous()
         n, k = hi - lo, max(self.top_k_list)
         ratings = self.model.predict(users)
+        if k > MAX_TOPK or ratings.shape[1] > 400000:   # beyond invpref_eval_topk_hip: the radix select of any k <= 1024
+            from .ops import topk_rows
+            hl = (d['hl_ptr'][lo:hi + 1], d['hl_items']) if self.use_item_pool else None
+            items, _, hits = topk_rows(ratings, k, mask=(d['mask_ptr'][lo:hi + 1], d['mask_items']), highlight=hl,
+                                       truth=(d['truth_ptr'][lo:hi + 1], d['truth_items']))
+            return items, hits
         items = torch.empty(n, k, dtype=torch.int32, device=users.device)
         hits = torch.empty(n, k, dtype=torch.float32, device=users.device)
         off = lambda t, o: C.c_void_p(t.data_ptr() + 4 * o)  # noqa: E731
@@ -113,7 +121,8 @@ class ImplicitTestManager:
 
     def _fused_hits_device(self, tables) -> torch.Tensor:
         """hits fp32[n_test_users, k] on the device, ranked by predict_topk in batches bounded by its workspace
-        (O(batch * k), about 256 MiB at most) -- the same labels topk() gives batch by batch."""
+        (O(batch * k), about 256 MiB at most; beyond k = 64 a 256 MiB score chunk plus the batch's [n, k] outputs) -- the
+        same labels topk() gives batch by batch."""
         from .ops import predict_topk
         d = self._dev
         n_users, k = self._users.shape[0], max(self.top_k_list)
@@ -134,6 +143,13 @@ class ImplicitTestManager:
         """hits fp32[n_test_users, k] of every test user (numpy), ranked by predict_topk (_fused_hits_device)"""
         return self._fused_hits_device(tables).cpu().numpy()
 
+    def _step(self, n_users: int, k: int) -> int:
+        """users per topk() batch and per metric partition: at least test_batch_size, at most a 1 GiB score matrix (with
+        room for the [n, k] outputs of a top-k beyond 64)"""
+        n_items = int(self.model.item_num) if hasattr(self.model, 'item_num') else 1
+        per_user = n_items + (3 * k if k > MAX_TOPK else 0)
+        return max(int(self.batch_size), min(n_users, (1 << 28) // max(1, per_user)))
+
     def evaluate_async(self) -> 'PendingEvaluation':
         """Enqueues the whole evaluation on the current stream and returns at once: the hit labels stay on the device and
         go straight into the rank_metrics kernels (csrc/invpref_metrics.hip), whose float64 sums are numpy's, bit for bit.
@@ -150,8 +166,7 @@ class ImplicitTestManager:
         # n x I floats and three launches, and the metrics are sums over users -- the same whatever the batch -- so small
         # batches are merged up to a 1 GiB score matrix (MIND's 256-user batches: 196 launches -> 10).  The fused path ranks in
         # its own batches; the float64 metric sums keep this partition either way, so the result is the same, float for float
-        n_items = int(self.model.item_num) if hasattr(self.model, 'item_num') else 1
-        step = max(int(self.batch_size), min(n_users, (1 << 28) // max(1, n_items)))
+        step = self._step(n_users, k)
         tables = self._fused_tables()
         if tables is not None:
             hits = self._fused_hits_device(tables)

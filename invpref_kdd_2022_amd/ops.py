@@ -227,30 +227,69 @@ def predict_topk(user_table: torch.Tensor, item_table: torch.Tensor, users: torc
     """predict + train-item mask (-1024) + item-pool highlight (+= 1024) + top-k + hit labels (models.py:393-407,
     evaluate.py:88-120) without the [n, item_num] score matrix.  mask / highlight / truth: None or an int32 CSR pair
     (indptr[n + 1], indices) over the rows of `users`, every row sorted ascending and distinct.
-    -> (items int32[n, k], scores fp32[n, k], hits fp32[n, k]): descending score, lowest item id first among equal scores."""
+    -> (items int32[n, k], scores fp32[n, k], hits fp32[n, k]): descending score, lowest item id first among equal scores.
+    k <= 64 runs the fused scan (predict_topk); 64 < k <= 1024 the chunked predict + radix select (predict_topk_wide)."""
     _gpu(user_table, item_table, users)
+    k = _check_topk(k)
     (mp, mi), (hp, hi), (tp, ti) = [(None, None) if c is None else c for c in (mask, highlight, truth)]
-    return _o().predict_topk(user_table, item_table, users, int(k), bool(sigmoid), mp, mi, hp, hi, tp, ti)
+    op = _o().predict_topk if k <= _capi.MAX_TOPK else _o().predict_topk_wide
+    return op(user_table, item_table, users, k, bool(sigmoid), mp, mi, hp, hi, tp, ti)
+
+
+def _check_topk(k) -> int:
+    k = int(k)
+    if k > _capi.MAX_TOPK_WIDE:
+        raise InvPrefError(f'top-k takes k <= {_capi.MAX_TOPK_WIDE} (INVPREF_MAX_TOPK_WIDE), got {k}')
+    return k
+
+
+def topk_rows(ratings: torch.Tensor, k: int, mask=None, highlight=None, truth=None):
+    """The masked / highlighted top k (1 <= k <= 1024) of every row of a score matrix (fp32 [n, I], row stride allowed; not
+    modified), any item count: csrc/invpref_topk_wide.hip.  mask / highlight / truth: None or int32 CSR pairs as for
+    predict_topk (row pointers may be a view into a longer array).  -> (items int32[n, k], scores fp32[n, k], hits fp32[n, k])."""
+    _gpu(ratings)
+    k = _check_topk(k)
+    if ratings.dim() != 2 or ratings.dtype != torch.float32 or (ratings.shape[0] > 0 and ratings.stride(1) != 1):
+        raise InvPrefError('ratings must be a float32 [n, item_num] tensor with unit column stride')
+    n, I = ratings.shape
+    dev = ratings.device
+    items = torch.empty(n, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, k, dtype=torch.float32, device=dev)
+    hits = torch.empty(n, k, dtype=torch.float32, device=dev)
+    (mp, mi), (hp, hi), (tp, ti) = [(None, None) if c is None else c for c in (mask, highlight, truth)]
+    for t in (mp, mi, hp, hi, tp, ti):
+        if t is not None:
+            _capi._req(t, torch.int32, 'CSR array')
+    L = lib()
+    nbytes = L.invpref_topk_rows_workspace_bytes(n, I, k)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    check(L.invpref_topk_rows_hip(ptr(ratings), n, I, ratings.stride(0) if n > 0 else I, ptr(mp), ptr(mi), ptr(hp), ptr(hi),
+                                  ptr(tp), ptr(ti), k, ptr(items), ptr(scores), ptr(hits), ptr(ws), nbytes, stream_ptr()),
+          'invpref_topk_rows_hip')
+    return items, scores, hits
 
 
 _RANK_TABLES = {}
 
 
 def rank_metric_tables(top_k_list, device):
-    """(disc float64[n_k, 64], idcg float64[n_k, 65]) of rank_metrics on `device`, computed by numpy exactly as
+    """(disc float64[n_k, W], idcg float64[n_k, W + 1]) of rank_metrics on `device`, computed by numpy exactly as
     recall_precision_ndcg computes them (evaluate.py) and cached per k list: row i of disc is 1 / log2(j + 2) for j < k,
-    entry L of idcg row i the ideal DCG of min(L, k) relevant items (1.0 for L = 0).  The first call for a k list copies
-    to the device; later calls enqueue nothing (capturable)."""
+    entry L of idcg row i the ideal DCG of min(L, k) relevant items (1.0 for L = 0).  W = 64 while every k <= 64 (the
+    tables of rank_metrics), else max(k) <= 1024 (rank_metrics_wide).  The first call for a k list copies to the device;
+    later calls enqueue nothing (capturable)."""
     import numpy as np
     ks = tuple(int(k) for k in top_k_list)
     device = torch.device(device)
     key = (ks, device)
     if key not in _RANK_TABLES:
-        disc = np.zeros((len(ks), 64))
-        idcg = np.ones((len(ks), 65))
+        W = max(ks, default=0)
+        W = _capi.MAX_TOPK if W <= _capi.MAX_TOPK else W
+        disc = np.zeros((len(ks), W))
+        idcg = np.ones((len(ks), W + 1))
         for i, k in enumerate(ks):
-            if not 1 <= k <= 64:
-                raise InvPrefError(f'rank metrics take 1 <= k <= 64, got {k}')
+            if not 1 <= k <= _capi.MAX_TOPK_WIDE:
+                raise InvPrefError(f'rank metrics take 1 <= k <= {_capi.MAX_TOPK_WIDE} (INVPREF_MAX_TOPK_WIDE), got {k}')
             d = 1.0 / np.log2(np.arange(2, k + 2))
             ideal = (np.arange(k)[None, :] < np.arange(k + 1)[:, None]).astype(np.float64)
             ig = (ideal * d).sum(1)
@@ -264,10 +303,13 @@ def rank_metric_sums(hits: torch.Tensor, truth_ptr: torch.Tensor, top_k_list, pa
     """The recall / precision / NDCG sums of ImplicitTestManager.evaluate() (evaluate.py:22-56, :137-175) over the rows of
     hits (fp32 [n, K] 0/1 labels; row stride allowed) with truth lengths diff(truth_ptr) (int32 [n + 1], any base), the
     users cut into partitions of `partition` rows, numpy's float64 order throughout.  -> float64 [3, n_k] on the device:
-    rows recall, precision, NDCG; column i for top_k_list[i] (sorted, duplicates allowed, k <= K <= 64)."""
+    rows recall, precision, NDCG; column i for top_k_list[i] (sorted, duplicates allowed, k <= K <= 1024: rank_metrics
+    while K <= 64, rank_metrics_wide beyond)."""
     _gpu(hits, truth_ptr)
     disc, idcg = rank_metric_tables(top_k_list, hits.device)
-    return _o().rank_metrics(hits, truth_ptr, [int(k) for k in top_k_list], disc, idcg, int(partition))
+    ks = [int(k) for k in top_k_list]
+    op = _o().rank_metrics if max(ks + [hits.shape[1]]) <= _capi.MAX_TOPK else _o().rank_metrics_wide
+    return op(hits, truth_ptr, ks, disc, idcg, int(partition))
 
 
 def device_csr(csr, n_rows: int, n_items: int, device):

@@ -29,6 +29,8 @@ What replaces what in the reference:
                                (models.py:393-407, evaluate.py:88-120) without the score matrix: (items, scores, hits)
 ``rank_metrics``               the recall / precision / NDCG sums of ``evaluate()`` from the hit labels, in numpy's float64
                                order (evaluate.py:22-56, :137-175): float64 ``[3, n_k]``
+``predict_topk_wide``          ``predict_topk`` for 1 <= k <= 1024: chunked scores + a radix select per user
+``rank_metrics_wide``          ``rank_metrics`` for k <= 1024 (disc / idcg tables ``[n_k, K]`` / ``[n_k, K + 1]``)
 =============================  =====================================================================================
 
 Tensors are borrowed for the call and never retained.  ``workspace`` arguments are caller-owned scratch (uint8),
@@ -634,4 +636,74 @@ def _rank_metrics(hits, truth_ptr, ks, disc, idcg, partition):
 
 @_fake('rank_metrics')
 def _rank_metrics_fake(hits, truth_ptr, ks, disc, idcg, partition):
+    return torch.empty(3, len(ks), dtype=torch.float64, device=hits.device)
+
+
+# ------------------------------------------------------------------------------------------------ predict_topk_wide
+_define('predict_topk_wide(Tensor user_table, Tensor item_table, Tensor users, int k, bool sigmoid, Tensor? mask_ptr, '
+        'Tensor? mask_items, Tensor? highlight_ptr, Tensor? highlight_items, Tensor? truth_ptr, Tensor? truth_items) '
+        '-> (Tensor, Tensor, Tensor)')
+
+
+@_impl('predict_topk_wide')
+def _predict_topk_wide(user_table, item_table, users, k, sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items,
+                       truth_ptr, truth_items):
+    _f32(user_table, 'user_table'); _f32(item_table, 'item_table')
+    n, (I, D) = users.numel(), item_table.shape
+    mp, mi = _csr_pair(mask_ptr, mask_items, 'mask')
+    hp, hi = _csr_pair(highlight_ptr, highlight_items, 'highlight')
+    tp, ti = _csr_pair(truth_ptr, truth_items, 'truth')
+    dev = users.device
+    items = torch.empty(n, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, k, dtype=torch.float32, device=dev)
+    hits = torch.empty(n, k, dtype=torch.float32, device=dev)
+    L = lib()
+    nbytes = L.invpref_predict_topk_wide_workspace_bytes(n, I, D, k)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    check(L.invpref_predict_topk_wide_hip(ptr(user_table), ptr(item_table), ptr(_ids(users, 'users')), n, I, D,
+                                          int(bool(sigmoid)), ptr(mp), ptr(mi), ptr(hp), ptr(hi), ptr(tp), ptr(ti), k,
+                                          ptr(items), ptr(scores), ptr(hits), ptr(ws), nbytes, stream_ptr()),
+          'invpref_predict_topk_wide_hip')
+    return items, scores, hits
+
+
+@_fake('predict_topk_wide')
+def _predict_topk_wide_fake(user_table, item_table, users, k, sigmoid, mask_ptr, mask_items, highlight_ptr,
+                            highlight_items, truth_ptr, truth_items):
+    return _predict_topk_fake(user_table, item_table, users, k, sigmoid, mask_ptr, mask_items, highlight_ptr,
+                              highlight_items, truth_ptr, truth_items)
+
+
+# ------------------------------------------------------------------------------------------------ rank_metrics_wide
+_define('rank_metrics_wide(Tensor hits, Tensor truth_ptr, int[] ks, Tensor disc, Tensor idcg, int partition) -> Tensor')
+
+
+@_impl('rank_metrics_wide')
+def _rank_metrics_wide(hits, truth_ptr, ks, disc, idcg, partition):
+    if hits.dim() != 2 or hits.dtype != torch.float32 or not hits.is_cuda or (hits.shape[0] > 0 and hits.stride(1) != 1):
+        raise InvPrefError('hits must be a CUDA float32 [n, K] tensor with unit column stride')
+    n, K = hits.shape
+    nk = len(ks)
+    _capi._req(truth_ptr, torch.int32, 'truth_ptr')
+    if truth_ptr.numel() != n + 1:
+        raise InvPrefError(f'truth_ptr has {truth_ptr.numel()} entries for {n} users')
+    kmax = max(ks) if nk else 0
+    for t, name, w in ((disc, 'disc', kmax), (idcg, 'idcg', kmax + 1)):
+        _capi._req(t, torch.float64, name)
+        if t.dim() != 2 or t.shape[0] != nk or t.shape[1] < w:
+            raise InvPrefError(f'{name} must be [{nk}, >= {w}], got {tuple(t.shape)}')
+    out = torch.empty(3, nk, dtype=torch.float64, device=hits.device)
+    L = lib()
+    nbytes = L.invpref_rank_metrics_workspace_bytes(n, nk, partition)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=hits.device)
+    karr = (C.c_int32 * max(nk, 1))(*ks)
+    check(L.invpref_rank_metrics_wide_hip(ptr(hits), n, hits.stride(0) if n > 0 else K, K, ptr(truth_ptr),
+                                          C.cast(karr, C.c_void_p), nk, ptr(disc), disc.shape[1], ptr(idcg), idcg.shape[1],
+                                          int(partition), ptr(out), ptr(ws), nbytes, stream_ptr()),
+          'invpref_rank_metrics_wide_hip')
+    return out
+
+
+@_fake('rank_metrics_wide')
+def _rank_metrics_wide_fake(hits, truth_ptr, ks, disc, idcg, partition):
     return torch.empty(3, len(ks), dtype=torch.float64, device=hits.device)
