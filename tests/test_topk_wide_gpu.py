@@ -322,6 +322,10 @@ def test_bounded_memory_at_the_mind_shape():
     want = _lexsort_topk(M, k)
     np.testing.assert_array_equal(items[:300].cpu().numpy(), want)
     np.testing.assert_array_equal(scores[:300].cpu().numpy(), np.take_along_axis(M, want, 1))
+    # every user of all 40 chunks: the k = 64 fused scan (an independent kernel) is the prefix
+    i64, s64, _ = ops.predict_topk(t[0].detach(), t[1].detach(), users, 64, True)
+    np.testing.assert_array_equal(items[:, :64].cpu().numpy(), i64.cpu().numpy())
+    np.testing.assert_array_equal(scores[:, :64].cpu().numpy(), s64.cpu().numpy())
 
 
 def test_recommend_k200_on_both_fused_models():
