@@ -521,6 +521,52 @@ int invpref_stat_envs_hip(const int64_t *envs, int64_t N, int64_t env_num, int64
 int invpref_sample_weights_hip(const int64_t *envs, int64_t N_local, const int64_t *counts, int64_t N_total,
                                int64_t env_num, float *class_weights, float *sample_weights, void *stream);
 
+/* ---- IPS-MF / SNIPS-MF weights (baseline_train.py:317-491, :800-976; csrc/invpref_propensity.hip).  Formed once, outside
+ * the step: the planned M-step reads them by position under INVPREF_PURE_MF | INVPREF_REWEIGHT_REC.  Float64 throughout in
+ * numpy's order of operations, rounded to fp32 once (torch.Tensor(np_array), baseline_train.py:382).  Ids outside
+ * [0, user_num) / [0, item_num) are not counted and get a NaN weight. */
+#define INVPREF_PROPENSITY_ITEM 0 /* basic_item_propensity_func  baseline_train.py:493-505 */
+#define INVPREF_PROPENSITY_USER 1 /* basic_user_propensity_func  baseline_train.py:508-520 */
+#define INVPREF_PROPENSITY_PAIR 2 /* basic_pair_propensity_func  baseline_train.py:523-546 */
+#define INVPREF_MAX_LABELS 256    /* distinct training labels of invpref_naive_bayes_propensity_hip */
+
+/* the interaction counts of the IPS managers' constructors (baseline_train.py:335-348: Counter + np.clip(cnt, 1, max)):
+ * user_cnt[user_num] / item_cnt[item_num] (device double) = clip(count, 1, max count); ids that never occur count 1 (all 0
+ * when n == 0, as np.clip with max 0 gives).  Integer atomics: exact. */
+size_t invpref_interaction_counts_workspace_bytes(int64_t user_num, int64_t item_num);
+int invpref_interaction_counts_hip(const int64_t *users, const int64_t *items, int64_t n, int64_t user_num,
+                                   int64_t item_num, double *user_cnt, double *item_cnt, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+
+/* basic_{item,user,pair}_propensity_func (baseline_train.py:493-546) on count arrays of any values (device double):
+ * max = max(cnt) (the builtin max), p = cnt / max, inv = 1 / p, pair: (inv_u + inv_i) / 2, then ** smooth_weight_coe
+ * (skipped when it is exactly 1.0: then weights[j] equals numpy's result rounded to fp32, bit for bit; other exponents
+ * go through the device pow, within one fp32 ulp of glibc's).  weights[j] for interaction (users[j], items[j]), fp32[n].
+ * kind INVPREF_PROPENSITY_ITEM needs no user array, INVPREF_PROPENSITY_USER no item array (NULL allowed). */
+size_t invpref_count_propensity_workspace_bytes(void);
+int invpref_count_propensity_hip(const double *user_cnt, int64_t user_num, const double *item_cnt, int64_t item_num,
+                                 const int64_t *users, const int64_t *items, int64_t n, int32_t kind,
+                                 double smooth_weight_coe, float *weights, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+
+/* naive_bayes_propensity (baseline_train.py:549-581): labels[n_labels] are the distinct training labels (compared as fp32);
+ * density = n / (user_num * item_num); per label P(y|O) = #(train == y) / n, P(y) = #(uniform == y) / m,
+ * propensity = P(y|O) * density / P(y), weight = (1 / propensity) ** smooth_weight_coe (a label absent from the uniform
+ * sample: IEEE inf propensity -> weight 0).  weights[j] = the weight of train_scores[j]'s label (fp32[n], 0 for a label not
+ * in the list); label_weights (optional, device double[n_labels]) receives the float64 per-label weights. */
+size_t invpref_naive_bayes_workspace_bytes(int32_t n_labels);
+int invpref_naive_bayes_propensity_hip(const float *train_scores, int64_t n, const float *uniform_scores, int64_t m,
+                                       const float *labels, int32_t n_labels, int64_t user_num, int64_t item_num,
+                                       double smooth_weight_coe, float *weights, double *label_weights, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+
+/* the SNIPS normaliser (SNIPSMFTrainManager.train_a_batch, baseline_train.py:457-491, :942-976: score_loss =
+ * sum(loss * w) / sum(w) over the minibatch) as a one-off pre-scaling of the weights of the static minibatches of
+ * utils.mini_batch (utils.py:12-19; the last one ragged): scaled[i] = w_i * B_b / S_b with S_b the float64 sum of the
+ * minibatch's weights and B_b its length, so that the unchanged step's mean(loss * scaled) is the SNIPS loss.  scaled may
+ * be weights (in place).  No workspace. */
+int invpref_snips_scale_hip(const float *weights, int64_t n, int64_t batch_size, float *scaled, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

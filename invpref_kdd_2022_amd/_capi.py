@@ -32,9 +32,14 @@ EXPORTS = [
     'invpref_predict_topk_workspace_bytes', 'invpref_predict_topk_hip', 'invpref_rank_metrics_workspace_bytes',
     'invpref_rank_metrics_hip', 'invpref_topk_rows_workspace_bytes', 'invpref_topk_rows_hip',
     'invpref_predict_topk_wide_workspace_bytes', 'invpref_predict_topk_wide_hip', 'invpref_rank_metrics_wide_hip',
+    'invpref_interaction_counts_workspace_bytes', 'invpref_interaction_counts_hip', 'invpref_count_propensity_workspace_bytes',
+    'invpref_count_propensity_hip', 'invpref_naive_bayes_workspace_bytes', 'invpref_naive_bayes_propensity_hip',
+    'invpref_snips_scale_hip',
 ]
 MAX_TOPK = 64          # k of the fused scan / k-pass / radix-select kernels and the 64-wide metric tables
 MAX_TOPK_WIDE = 1024   # INVPREF_MAX_TOPK_WIDE: the wide entry points (csrc/invpref_topk_wide.hip)
+PROPENSITY_ITEM, PROPENSITY_USER, PROPENSITY_PAIR = 0, 1, 2   # INVPREF_PROPENSITY_*: basic_{item,user,pair}_propensity_func
+MAX_LABELS = 256       # INVPREF_MAX_LABELS: distinct training labels of the naive-Bayes propensities
 
 
 class InvPrefError(RuntimeError):
@@ -141,6 +146,17 @@ def lib():
         L.invpref_predict_topk_wide_hip.argtypes = L.invpref_predict_topk_hip.argtypes
         L.invpref_rank_metrics_wide_hip.argtypes = [vp, i64, i64, C.c_int32, vp, vp, C.c_int32, vp, i64, vp, i64, i64, vp, vp,
                                                     C.c_size_t, vp]
+        L.invpref_interaction_counts_workspace_bytes.restype = C.c_size_t
+        L.invpref_interaction_counts_workspace_bytes.argtypes = [i64, i64]
+        L.invpref_interaction_counts_hip.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, C.c_size_t, vp]
+        L.invpref_count_propensity_workspace_bytes.restype = C.c_size_t
+        L.invpref_count_propensity_workspace_bytes.argtypes = []
+        L.invpref_count_propensity_hip.argtypes = [vp, i64, vp, i64, vp, vp, i64, C.c_int32, f64, vp, vp, C.c_size_t, vp]
+        L.invpref_naive_bayes_workspace_bytes.restype = C.c_size_t
+        L.invpref_naive_bayes_workspace_bytes.argtypes = [C.c_int32]
+        L.invpref_naive_bayes_propensity_hip.argtypes = [vp, i64, vp, i64, vp, C.c_int32, i64, i64, f64, vp, vp, vp,
+                                                         C.c_size_t, vp]
+        L.invpref_snips_scale_hip.argtypes = [vp, i64, i64, vp, vp]
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')
         _lib = L

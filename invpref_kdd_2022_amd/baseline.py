@@ -1,4 +1,4 @@
-"""PureMF baselines on the same fused HIP step.
+"""PureMF baselines on the same fused HIP step, plain and propensity-weighted (IPS-MF, SNIPS-MF).
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -11,12 +11,17 @@ classifier absent (``INVPREF_PURE_MF``: never loaded, never stored), one environ
 of train.py:389-397 (the InvPref regularisers are normalised by 2*B*D, PureMF's by B*D; see
 oracle/oracle.py ``pure_mf_*`` for the CPU statement of the same mapping, pinned by goldens g7).  The
 managers reuse the epoch engine of ``train.py`` (row plans, fused Adam, HIP-graph replay, deferred read-backs).
+
+IPS-MF / SNIPS-MF (baseline_train.py:317-581, :800-976) are the same step with a fixed per-interaction weight on the score
+loss (``INVPREF_REWEIGHT_REC``): the inverse propensities are formed once on the device (csrc/invpref_propensity.hip), and
+SNIPS's per-minibatch normaliser sum(w) is folded into the weights of the static minibatches (w' = w * B_b / S_b).
 """
 from __future__ import annotations
 
 import math
 import os
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -187,8 +192,14 @@ class _BasicTrainManager(_InvPrefTrainManager):
         """train.py:379-405 on caller-supplied tensors: the row plan of this one minibatch is built on the
         host first (the epoch loop uses the plans prepared once for the static minibatches instead).
         Single-process form; sharded runs go through train_epochs() / train()."""
+        return self._batch_step(batch_users_tensor, batch_items_tensor, batch_scores_tensor, None)
+
+    def _batch_step(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, weights) -> dict:
+        """one fused step on caller tensors; weights (fp32, device, one per interaction) are read under
+        INVPREF_REWEIGHT_REC, None runs the unweighted step"""
         if self.world_size > 1:
             raise NotImplementedError('train_a_batch on caller-supplied tensors is single-process; use train_epochs()')
+        flags = self._flags if weights is not None else self._flags & ~_capi.REWEIGHT_REC
         u = batch_users_tensor.detach().cpu().numpy()
         v = batch_items_tensor.detach().cpu().numpy()
         y = batch_scores_tensor.detach().float().contiguous()
@@ -198,8 +209,8 @@ class _BasicTrainManager(_InvPrefTrainManager):
         st.losses6.zero_()
         st.step += 1
         self._sched_synced = False
-        ops.mstep_rows_adam(st.p_views, st.p_views_alt, st.m_views, st.v_views, dp, None, y.to(self.device), None,
-                            len(u), self._coefs(0.), self._flags, st.losses6, st.step, self.lr, self.workspace,
+        ops.mstep_rows_adam(st.p_views, st.p_views_alt, st.m_views, st.v_views, dp, None, y.to(self.device), weights,
+                            len(u), self._coefs(0.), flags, st.losses6, st.step, self.lr, self.workspace,
                             pure=True)
         st.swap()
         return self.loss_dicts(st.losses6[None])[0]
@@ -282,3 +293,144 @@ class BasicUniformExplicitTrainManager(BasicExplicitTrainManager, _UniformMixin)
         super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe,
                          L1_coe, test_begin_epoch)
         self._keep_uniform(uniform_data)
+
+
+# ------------------------------------------------------------------------------------------------ IPS-MF / SNIPS-MF
+def _f32_device(a, device) -> torch.Tensor:
+    """torch.Tensor(np_array).to(device) of baseline_train.py:382: one rounding to fp32"""
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)).astype(np.float32)).to(device)
+
+
+def _count_propensity_np(kind, user_inter_cnt_np, item_inter_cnt_np, interactions, smooth_weight_coe):
+    dev = torch.device('cuda', torch.cuda.current_device())
+    inter = np.asarray(interactions)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int64)).to(dev)  # noqa: E731
+    cnt = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1)).to(dev)  # noqa: E731
+    w = ops.count_propensity(cnt(user_inter_cnt_np) if kind != _capi.PROPENSITY_ITEM else None,
+                             cnt(item_inter_cnt_np) if kind != _capi.PROPENSITY_USER else None,
+                             up(inter[:, 0]) if kind != _capi.PROPENSITY_ITEM else None,
+                             up(inter[:, 1]) if kind != _capi.PROPENSITY_USER else None, kind, smooth_weight_coe)
+    return w.cpu().numpy()
+
+
+def basic_item_propensity_func(user_inter_cnt_np, item_inter_cnt_np, interactions, smooth_weight_coe: float) -> np.ndarray:
+    """baseline_train.py:493-505 on the device: (1 / (item_cnt / max item_cnt))[item] ** smooth_weight_coe, as the fp32
+    values the managers upload (torch.Tensor(np_array), baseline_train.py:382)"""
+    return _count_propensity_np(_capi.PROPENSITY_ITEM, user_inter_cnt_np, item_inter_cnt_np, interactions, smooth_weight_coe)
+
+
+def basic_user_propensity_func(user_inter_cnt_np, item_inter_cnt_np, interactions, smooth_weight_coe: float) -> np.ndarray:
+    """baseline_train.py:508-520 on the device (fp32 result)"""
+    return _count_propensity_np(_capi.PROPENSITY_USER, user_inter_cnt_np, item_inter_cnt_np, interactions, smooth_weight_coe)
+
+
+def basic_pair_propensity_func(user_inter_cnt_np, item_inter_cnt_np, interactions, smooth_weight_coe: float) -> np.ndarray:
+    """baseline_train.py:523-546 on the device: ((inv_u + inv_i) / 2) ** smooth_weight_coe (fp32 result)"""
+    return _count_propensity_np(_capi.PROPENSITY_PAIR, user_inter_cnt_np, item_inter_cnt_np, interactions, smooth_weight_coe)
+
+
+def naive_bayes_propensity(train_data, uniform_data, user_num: int, item_num: int, smooth_weight_coe: float) -> np.ndarray:
+    """baseline_train.py:549-581 on the device: the weight of every training interaction's label (fp32 result; a label absent
+    from the uniform sample weighs 0)"""
+    dev = torch.device('cuda', torch.cuda.current_device())
+    col = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a)[:, 2], dtype=np.float32)).to(dev)  # noqa: E731
+    w, _ = ops.naive_bayes_propensity(col(train_data), col(uniform_data), user_num, item_num, smooth_weight_coe)
+    return w.cpu().numpy()
+
+
+_COUNT_KINDS = {basic_item_propensity_func: _capi.PROPENSITY_ITEM, basic_user_propensity_func: _capi.PROPENSITY_USER,
+                basic_pair_propensity_func: _capi.PROPENSITY_PAIR}
+
+
+class _PropensityMixin(_UniformMixin):
+    """IPSBasicTrainManager / SNIPSMFTrainManager and their explicit twins (baseline_train.py:317-491, :800-976) on the
+    fused PureMF step with INVPREF_REWEIGHT_REC.  The weights are counted over the GLOBAL training data before the rows
+    are sharded and then follow this rank's rows; SNIPS's normaliser is folded into them per GLOBAL minibatch."""
+    _snips = False
+
+    def __init__(self, model, propensity_func, evaluator, device, training_data: torch.Tensor, batch_size: int,
+                 epochs: int, evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
+                 smooth_weight_coe: float = 1.0, uniform_data: torch.Tensor = None, *, rank=None, world_size=None,
+                 process_group=None):
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe,
+                         L1_coe, test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        self.loss_func = nn.BCELoss(reduction='none') if self.implicit else nn.MSELoss(reduction='none')
+        self.smooth_weight_coe = smooth_weight_coe
+        self.propensity_func = propensity_func
+        dev, U, I = self.device, model.user_num, model.item_num
+        users = training_data[:, 0].to(dev).long().contiguous()     # every row, in order (not this rank's share)
+        items = training_data[:, 1].to(dev).long().contiguous()
+        self._cnt_dev = ops.interaction_counts(users, items, U, I)  # baseline_train.py:335-348
+        self._cnt_np = [None, None]
+        if uniform_data is not None:
+            self._keep_uniform(uniform_data)
+            if propensity_func is naive_bayes_propensity:
+                w, _ = ops.naive_bayes_propensity(training_data[:, 2].to(dev), self.uniform_score, U, I, smooth_weight_coe)
+            else:
+                w = _f32_device(propensity_func(training_data.cpu().detach().numpy(), uniform_data.cpu().detach().numpy(),
+                                                U, I, smooth_weight_coe), dev)
+        elif propensity_func in _COUNT_KINDS:
+            w = ops.count_propensity(*self._cnt_dev, users, items, _COUNT_KINDS[propensity_func], smooth_weight_coe)
+        else:
+            inter = np.stack([users.cpu().numpy(), items.cpu().numpy()], axis=1)
+            w = _f32_device(propensity_func(self.user_inter_cnt_np, self.item_inter_cnt_np, inter, smooth_weight_coe), dev)
+        if w.numel() != self.n_total:
+            raise ValueError(f'propensity_func returned {w.numel()} weights for {self.n_total} interactions')
+        self.inverse_propensity_tensor = w
+        # what the epochs' launches read: SNIPS-scaled per global minibatch, then this rank's rows
+        w = ops.snips_scale(w, batch_size) if self._snips else w
+        self._w_local = w.index_select(0, self.shard.local_rows().to(dev)) if self.world_size > 1 else w
+        self._flags |= _capi.REWEIGHT_REC
+
+    def _cnt(self, i):
+        if self._cnt_np[i] is None:
+            self._cnt_np[i] = self._cnt_dev[i].cpu().numpy()
+        return self._cnt_np[i]
+
+    @property
+    def user_inter_cnt_np(self) -> np.ndarray:
+        """float64 [user_num]: clip(interactions per user, 1, max) (baseline_train.py:335-347), read back on first use"""
+        return self._cnt(0)
+
+    @user_inter_cnt_np.setter
+    def user_inter_cnt_np(self, value):
+        self._cnt_np[0] = value
+
+    @property
+    def item_inter_cnt_np(self) -> np.ndarray:
+        return self._cnt(1)
+
+    @item_inter_cnt_np.setter
+    def item_inter_cnt_np(self, value):
+        self._cnt_np[1] = value
+
+    def _pure_weights(self, lo: int, hi: int):
+        return self._w_local[lo:hi]
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, weight_tensor=None) -> dict:
+        """baseline_train.py:385-416 / :457-491: mean(loss * w) (IPS) or sum(loss * w) / sum(w) (SNIPS) on caller tensors;
+        without weights both are the plain PureMF step."""
+        w = None
+        if weight_tensor is not None:
+            w = weight_tensor.detach().to(self.device).float().reshape(-1).contiguous()
+            if self._snips:
+                w = ops.snips_scale(w, max(w.numel(), 1))
+        return self._batch_step(batch_users_tensor, batch_items_tensor, batch_scores_tensor, w)
+
+
+class IPSBasicTrainManager(_PropensityMixin, BasicImplicitTrainManager):
+    """reference baseline_train.py:317-436 (BCELoss, mean(loss * inverse propensity))"""
+
+
+class SNIPSMFTrainManager(IPSBasicTrainManager):
+    """reference baseline_train.py:439-490 (sum(loss * w) / sum(w) per minibatch)"""
+    _snips = True
+
+
+class IPSBasicExplicitTrainManager(_PropensityMixin, BasicExplicitTrainManager):
+    """reference baseline_train.py:800-921 (MSELoss)"""
+
+
+class SNIPSExplicitMFTrainManager(IPSBasicExplicitTrainManager):
+    """reference baseline_train.py:924-976"""
+    _snips = True

@@ -446,3 +446,40 @@ def static_pop(users, items, envs, env_num: int, user_cnt, item_cnt, user_norm, 
                                        ptr(item_cnt), ptr(user_norm), ptr(item_norm), ptr(out), ptr(ws), ws.numel(),
                                        stream_ptr()), 'invpref_static_pop_hip')
     return out
+
+
+# ---- IPS-MF / SNIPS-MF weights (baseline_train.py:317-581; csrc/invpref_propensity.hip).  One-off, outside the step.
+def interaction_counts(users: torch.Tensor, items: torch.Tensor, user_num: int, item_num: int):
+    """The IPS managers' user / item interaction counts (baseline_train.py:335-348): float64 [user_num], [item_num] on the
+    device, each clip(count, 1, max count) -- ids that never occur count 1."""
+    _gpu(users, items)
+    return _o().interaction_counts(users, items, int(user_num), int(item_num))
+
+
+def count_propensity(user_cnt: Optional[torch.Tensor], item_cnt: Optional[torch.Tensor], users: Optional[torch.Tensor],
+                     items: Optional[torch.Tensor], kind: int, smooth_weight_coe: float) -> torch.Tensor:
+    """basic_{item,user,pair}_propensity_func (baseline_train.py:493-546), kind = _capi.PROPENSITY_{ITEM,USER,PAIR}: the fp32
+    inverse propensity of every interaction, in numpy's float64 order (bit-equal when smooth_weight_coe == 1.0)."""
+    _gpu(user_cnt, item_cnt, users, items)
+    return _o().count_propensity(user_cnt, item_cnt, users, items, int(kind), float(smooth_weight_coe))
+
+
+def naive_bayes_propensity(train_scores: torch.Tensor, uniform_scores: torch.Tensor, user_num: int, item_num: int,
+                           smooth_weight_coe: float, labels: Optional[torch.Tensor] = None):
+    """naive_bayes_propensity (baseline_train.py:549-581) from the label columns of the training data and of the uniform
+    (RCT) sample: (fp32 weight of every training interaction, float64 weight of every distinct label).  labels: the
+    distinct training labels (default: torch.unique of train_scores -- plumbing; the counts and the map are the kernels')."""
+    _gpu(train_scores, uniform_scores)
+    ts = train_scores.reshape(-1).float().contiguous()
+    us = uniform_scores.reshape(-1).float().contiguous()
+    lab = torch.unique(ts) if labels is None else labels.reshape(-1).float().contiguous()
+    if lab.numel() > _capi.MAX_LABELS:
+        raise InvPrefError(f'naive-Bayes propensities take at most {_capi.MAX_LABELS} distinct labels, got {lab.numel()}')
+    return _o().naive_bayes_propensity(ts, us, lab, int(user_num), int(item_num), float(smooth_weight_coe))
+
+
+def snips_scale(weights: torch.Tensor, batch_size: int) -> torch.Tensor:
+    """w'_i = w_i * B_b / S_b over the static minibatches [b * batch_size, (b + 1) * batch_size) (the last one ragged),
+    S_b the minibatch's float64 sum of w: mean(loss * w') is SNIPS's sum(loss * w) / sum(w) (baseline_train.py:457-491)."""
+    _gpu(weights)
+    return _o().snips_scale(weights.contiguous(), int(batch_size))

@@ -31,6 +31,10 @@ What replaces what in the reference:
                                order (evaluate.py:22-56, :137-175): float64 ``[3, n_k]``
 ``predict_topk_wide``          ``predict_topk`` for 1 <= k <= 1024: chunked scores + a radix select per user
 ``rank_metrics_wide``          ``rank_metrics`` for k <= 1024 (disc / idcg tables ``[n_k, K]`` / ``[n_k, K + 1]``)
+``interaction_counts``         the Counter + ``np.clip`` of the IPS managers' constructors (baseline_train.py:335-348)
+``count_propensity``           ``basic_{item,user,pair}_propensity_func`` (baseline_train.py:493-546): fp32 ``[n]``
+``naive_bayes_propensity``     ``naive_bayes_propensity`` (baseline_train.py:549-581): fp32 ``[n]`` + float64 per label
+``snips_scale``                the SNIPS normaliser (baseline_train.py:457-491) as a pre-scaling of the static minibatches
 =============================  =====================================================================================
 
 Tensors are borrowed for the call and never retained.  ``workspace`` arguments are caller-owned scratch (uint8),
@@ -707,3 +711,104 @@ def _rank_metrics_wide(hits, truth_ptr, ks, disc, idcg, partition):
 @_fake('rank_metrics_wide')
 def _rank_metrics_wide_fake(hits, truth_ptr, ks, disc, idcg, partition):
     return torch.empty(3, len(ks), dtype=torch.float64, device=hits.device)
+
+
+# ------------------------------------------------------------------------------------------------ IPS / SNIPS weights
+_define('interaction_counts(Tensor users, Tensor items, int user_num, int item_num) -> (Tensor, Tensor)')
+
+
+@_impl('interaction_counts')
+def _interaction_counts(users, items, user_num, item_num):
+    n, dev = users.numel(), users.device
+    if items.numel() != n:
+        raise InvPrefError('interaction_counts: users and items differ in length')
+    uc = torch.empty(user_num, dtype=torch.float64, device=dev)
+    ic = torch.empty(item_num, dtype=torch.float64, device=dev)
+    L = lib()
+    nbytes = L.invpref_interaction_counts_workspace_bytes(user_num, item_num)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    check(L.invpref_interaction_counts_hip(ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), n, int(user_num),
+                                           int(item_num), ptr(uc), ptr(ic), ptr(ws), nbytes, stream_ptr()),
+          'invpref_interaction_counts_hip')
+    return uc, ic
+
+
+@_fake('interaction_counts')
+def _interaction_counts_fake(users, items, user_num, item_num):
+    f = dict(dtype=torch.float64, device=users.device)
+    return torch.empty(user_num, **f), torch.empty(item_num, **f)
+
+
+_define('count_propensity(Tensor? user_cnt, Tensor? item_cnt, Tensor? users, Tensor? items, int kind, '
+        'float smooth_weight_coe) -> Tensor')
+
+
+@_impl('count_propensity')
+def _count_propensity(user_cnt, item_cnt, users, items, kind, smooth_weight_coe):
+    ids = users if users is not None else items
+    n, dev = ids.numel(), ids.device
+    for t, name in ((user_cnt, 'user_cnt'), (item_cnt, 'item_cnt')):
+        _capi._req(t, torch.float64, name)
+    for t, name in ((users, 'users'), (items, 'items')):
+        if t is not None:
+            _ids(t, name)
+            if t.numel() != n:
+                raise InvPrefError('count_propensity: users and items differ in length')
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    L = lib()
+    nbytes = L.invpref_count_propensity_workspace_bytes()
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.invpref_count_propensity_hip(ptr(user_cnt), 0 if user_cnt is None else user_cnt.numel(), ptr(item_cnt),
+                                         0 if item_cnt is None else item_cnt.numel(), ptr(users), ptr(items), n,
+                                         int(kind), float(smooth_weight_coe), ptr(out), ptr(ws), nbytes, stream_ptr()),
+          'invpref_count_propensity_hip')
+    return out
+
+
+@_fake('count_propensity')
+def _count_propensity_fake(user_cnt, item_cnt, users, items, kind, smooth_weight_coe):
+    ids = users if users is not None else items
+    return torch.empty(ids.numel(), dtype=torch.float32, device=ids.device)
+
+
+_define('naive_bayes_propensity(Tensor train_scores, Tensor uniform_scores, Tensor labels, int user_num, int item_num, '
+        'float smooth_weight_coe) -> (Tensor, Tensor)')
+
+
+@_impl('naive_bayes_propensity')
+def _naive_bayes_propensity(train_scores, uniform_scores, labels, user_num, item_num, smooth_weight_coe):
+    n, m, K, dev = train_scores.numel(), uniform_scores.numel(), labels.numel(), train_scores.device
+    for t, name in ((train_scores, 'train_scores'), (uniform_scores, 'uniform_scores'), (labels, 'labels')):
+        _f32(t, name)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    lw = torch.empty(K, dtype=torch.float64, device=dev)
+    L = lib()
+    nbytes = L.invpref_naive_bayes_workspace_bytes(K)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    check(L.invpref_naive_bayes_propensity_hip(ptr(train_scores), n, ptr(uniform_scores), m, ptr(labels), K, int(user_num),
+                                               int(item_num), float(smooth_weight_coe), ptr(out), ptr(lw), ptr(ws), nbytes,
+                                               stream_ptr()), 'invpref_naive_bayes_propensity_hip')
+    return out, lw
+
+
+@_fake('naive_bayes_propensity')
+def _naive_bayes_propensity_fake(train_scores, uniform_scores, labels, user_num, item_num, smooth_weight_coe):
+    return (torch.empty(train_scores.numel(), dtype=torch.float32, device=train_scores.device),
+            torch.empty(labels.numel(), dtype=torch.float64, device=train_scores.device))
+
+
+_define('snips_scale(Tensor weights, int batch_size) -> Tensor')
+
+
+@_impl('snips_scale')
+def _snips_scale(weights, batch_size):
+    _f32(weights, 'weights')
+    out = torch.empty_like(weights)
+    check(lib().invpref_snips_scale_hip(ptr(weights), weights.numel(), int(batch_size), ptr(out), stream_ptr()),
+          'invpref_snips_scale_hip')
+    return out
+
+
+@_fake('snips_scale')
+def _snips_scale_fake(weights, batch_size):
+    return torch.empty_like(weights)

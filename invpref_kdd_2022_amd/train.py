@@ -253,6 +253,11 @@ class _InvPrefTrainManager:
             return self.class_weights, self._flags | _capi.WEIGHTS_BY_ENV
         return bw, self._flags
 
+    def _pure_weights(self, lo: int, hi: int):
+        """PureMF managers: the per-interaction weights of the local rows [lo, hi) that the epochs' launches read under
+        INVPREF_REWEIGHT_REC (the IPS / SNIPS managers of baseline.py), or None (plain PureMF)"""
+        return None
+
     def _weights_by_env(self) -> bool:
         """may the epochs' launches take an interaction's weight as class_weights[env]? (one GPU, planned M-step, weights
         consistent with the environments: stat_envs() ran since they last changed, nobody was handed the array since)"""
@@ -488,10 +493,9 @@ class _InvPrefTrainManager:
         self._raw_batches = []
         for k in range(self.batch_num):
             lo, hi = self.shard.local_batch_bounds(k)
-            v = None if self._pure else (self.envs[lo:hi], self._sample_weights[lo:hi])
+            v = (None, self._pure_weights(lo, hi)) if self._pure else (self.envs[lo:hi], self._sample_weights[lo:hi])
             self._raw_batches.append((lo, hi - lo, self.shard.global_batch_len(k), self.users_tensor[lo:hi],
-                                      self.items_tensor[lo:hi], self.scores_tensor[lo:hi],
-                                      None if self._pure else v[0], None if self._pure else v[1]))
+                                      self.items_tensor[lo:hi], self.scores_tensor[lo:hi], v[0], v[1]))
         if not hasattr(self, '_adam_ranges'):
             self._adam_ranges = [(0, st.n)]
         rg = self._adam_ranges
