@@ -28,9 +28,15 @@ float64 (about 10 MB): the seven parameter tables, the six loss terms of the las
 assignments, counts, diff_num and class weights of the last E-step.  The inputs are seeded, so two builds run with the same
 arguments can be compared output for output.
 
-Parity gate: before the line is printed, one epoch + one E-step from a seeded state run through the timed
-path (alternating launches, fused E-step with the reference's default tie-break) and through the CPU oracle; the line carries
-`parity_gate` and NO `value` when the six loss terms differ by more than 1e-5 relative or a single environment assignment
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the
+line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration and `detail.timed_seconds`).
+--full adds everything else the line has carried: the parity gate, the per-step device times and per-kernel / roofline figures
+from runs of their own, the other configurations and sizes, evaluation and end-to-end timings, the CPU baseline and, at N > 1, the
+other exchanges, layouts and scaling mode.  --no-parity-gate, --no-extras and --no-cpu-baseline leave parts of a --full run out.
+
+Parity gate (--full): before the line is printed, one epoch + one E-step from a seeded state run through the
+timed path (alternating launches, fused E-step with the reference's default tie-break) and through the CPU oracle; the line
+carries `parity_gate` and NO `value` when the six loss terms differ by more than 1e-5 relative or a single environment assignment
 differs on the same tables.  An N-rank run gates ITS path the same way (sharded_parity_gate: the row-sharded epoch and E-step of
 all ranks against the oracle on the whole problem, plus bit-equal parameter replicas).
 """
@@ -932,83 +938,11 @@ def eval_timing(dev):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=1550)
-    ap.add_argument('--warmup', type=int, default=155)
-    ap.add_argument('--scaling', choices=('strong', 'weak'), default='strong',
-                    help='strong (default): 250 154 interactions and the 8 192-row global minibatch at every N (BASELINE configs[3]); '
-                         'weak: 250 154 interactions and 8 192 rows PER GPU (rounds 1-5)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity-gate', action='store_true', help='profiling runs only: the line then says so')
-    ap.add_argument('--no-extras', action='store_true', help='skip roofline_large / eval timing (profiling runs)')
-    ap.add_argument('--spawn', action='store_true', help='launch the ranks as child processes even for --gpus 1 (checks the launcher path)')
-    ap.add_argument('--dump-outputs', metavar='DIR',
-                    help='one GPU: write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64)')
-    args = ap.parse_args()
-    if args.steps < 1:
-        ap.error('--steps must be at least 1')
-    if args.dump_outputs and args.gpus != 1:
-        ap.error('--dump-outputs needs --gpus 1')
-
-    if (args.gpus > 1 or args.spawn) and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
-        sys.exit(spawn_ranks(args))      # (nothing in this process has touched the GPU)
-
-    import numpy as np  # noqa: F401
+def step_figures(mgr, world, graphs, b_loc, dt):
+    """--full: the device time of the M-step and the E-step alone and the per-kernel figures, from runs of their own after
+    the timed region, with the roofline of the step against them.  Returns (roofline, detail) of the line."""
+    import numpy as np
     import torch
-    from invpref_kdd_2022_amd import parallel
-    global SCALING
-    SCALING = args.scaling
-
-    # (INVPREF_BENCH_BACKEND=gloo INVPREF_BENCH_SAME_DEVICE=1: a rehearsal of the N-rank flow on a ONE-GPU box -- every
-    #  rank on cuda:0, collectives through gloo, so no captured collectives; never what a measurement uses)
-    rank, local, world = parallel.init_from_env(os.environ.get('INVPREF_BENCH_BACKEND', 'nccl'))
-    if world != args.gpus:
-        raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}')
-    if os.environ.get('INVPREF_BENCH_SAME_DEVICE'):
-        local = 0
-    torch.cuda.set_device(local)
-    dev = torch.device('cuda', local)
-
-    # N > 1: BASELINE.json configs[3] as written -- interactions row-sharded, ONE all-reduce of the whole flat gradient
-    # buffer per optimiser step (SURVEY 8(e)); the reduce-scatter form and the user-sharded layout are timed after it
-    rccl_ranks = None
-    if world > 1:
-        os.environ['INVPREF_EXCHANGE'] = 'allreduce'
-        probe = torch.ones(1, device=dev)
-        torch.distributed.all_reduce(probe)            # (through the backend the run uses: RCCL unless rehearsing on gloo)
-        torch.cuda.synchronize()
-        rccl_ranks = int(probe.item()) if torch.distributed.get_backend() == 'nccl' else 0
-        assert int(probe.item()) == torch.distributed.get_world_size() == world
-    def rate(n_, dt_):
-        """interactions per second, exactly: the rows of every minibatch stepped (the ragged last minibatch is shorter)"""
-        return n_ / dt_
-
-    # the parity gate first: a path that does not reproduce the oracle is not timed (BASELINE.md §3.2)
-    gate = None
-    if not args.no_parity_gate:
-        if world == 1:
-            gate = parity_gate(dev)
-            failed = not gate['pass']
-        else:
-            gate = sharded_parity_gate(dev, rank, world)
-            verdict = torch.tensor([0 if (gate is None or gate['pass']) else 1], device=dev)
-            torch.distributed.all_reduce(verdict)          # (every rank leaves together)
-            failed = bool(verdict.item())
-        if failed:
-            if rank == 0:
-                print(json.dumps({'metric': 'training interactions/sec, Yahoo-implicit InvPref', 'value': None,
-                                  'unit': 'interactions/s', 'n_gpus': world, 'error': 'parity gate failed: no value is reported',
-                                  'parity_gate': gate}))
-            sys.exit(4)
-        torch.cuda.empty_cache()
-    mgr = build_manager(dev, rank, world, 'rows' if world > 1 else None)
-    n_total, gbatch = problem_size(world)
-    b_loc = gbatch // world                      # rows of a full minibatch on one rank (the byte models below are per rank)
-    dt, steps, warm_steps, graphs, n_timed, last, estep = timed_run(mgr, world, args.steps, args.warmup)
-    value = rate(n_timed, dt)
-    dumped = dump_outputs(mgr, args.dump_outputs, last, estep) if args.dump_outputs else None
     ms_step_dev, ms_estep_eager, ms_estep_replay = device_step_times(mgr, world)
     n_local = mgr.users_tensor.shape[0]
     ms_estep = ms_estep_replay if ms_estep_replay else ms_estep_eager
@@ -1100,6 +1034,91 @@ def main():
                                               'once per two steps and passes the other side\'s gradient through contribution rows'}
         roofline['alt'] = {'plans': len(mgr._alt['plans']), 'plan_build_s': mgr._alt['build_s'],
                            'slots_per_round_users_items': list(mgr._alt.get('slots', ())), 'fold_flag_timeouts': mgr.alt_error()}
+    return roofline, detail
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--gpus', type=int, default=1)
+    ap.add_argument('--steps', type=int, default=1550)
+    ap.add_argument('--warmup', type=int, default=155)
+    ap.add_argument('--scaling', choices=('strong', 'weak'), default='strong',
+                    help='strong (default): 250 154 interactions and the 8 192-row global minibatch at every N (BASELINE configs[3]); '
+                         'weak: 250 154 interactions and 8 192 rows PER GPU (rounds 1-5)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the parity gate, per-kernel / roofline figures, other configurations, '
+                         'evaluation and end-to-end timings, the CPU baseline (N > 1: the other exchanges and layouts)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-parity-gate', action='store_true', help='--full without the parity gate (profiling runs only: '
+                                                                  'the line then says so)')
+    ap.add_argument('--no-extras', action='store_true', help='--full without roofline_large / eval timing (profiling runs)')
+    ap.add_argument('--spawn', action='store_true', help='launch the ranks as child processes even for --gpus 1 (checks the launcher path)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='one GPU: write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.gpus != 1:
+        ap.error('--dump-outputs needs --gpus 1')
+
+    if (args.gpus > 1 or args.spawn) and 'RANK' not in os.environ and 'WORLD_SIZE' not in os.environ:
+        sys.exit(spawn_ranks(args))      # (nothing in this process has touched the GPU)
+
+    import numpy as np  # noqa: F401
+    import torch
+    from invpref_kdd_2022_amd import parallel
+    global SCALING
+    SCALING = args.scaling
+
+    # (INVPREF_BENCH_BACKEND=gloo INVPREF_BENCH_SAME_DEVICE=1: a rehearsal of the N-rank flow on a ONE-GPU box -- every
+    #  rank on cuda:0, collectives through gloo, so no captured collectives; never what a measurement uses)
+    rank, local, world = parallel.init_from_env(os.environ.get('INVPREF_BENCH_BACKEND', 'nccl'))
+    if world != args.gpus:
+        raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}')
+    if os.environ.get('INVPREF_BENCH_SAME_DEVICE'):
+        local = 0
+    torch.cuda.set_device(local)
+    dev = torch.device('cuda', local)
+
+    # N > 1: BASELINE.json configs[3] as written -- interactions row-sharded, ONE all-reduce of the whole flat gradient
+    # buffer per optimiser step (SURVEY 8(e)); the reduce-scatter form and the user-sharded layout are timed after it
+    rccl_ranks = None
+    if world > 1:
+        os.environ['INVPREF_EXCHANGE'] = 'allreduce'
+        probe = torch.ones(1, device=dev)
+        torch.distributed.all_reduce(probe)            # (through the backend the run uses: RCCL unless rehearsing on gloo)
+        torch.cuda.synchronize()
+        rccl_ranks = int(probe.item()) if torch.distributed.get_backend() == 'nccl' else 0
+        assert int(probe.item()) == torch.distributed.get_world_size() == world
+    def rate(n_, dt_):
+        """interactions per second, exactly: the rows of every minibatch stepped (the ragged last minibatch is shorter)"""
+        return n_ / dt_
+
+    # --full: the parity gate first, a path that does not reproduce the oracle is not timed (BASELINE.md §3.2)
+    gate = None
+    if args.full and not args.no_parity_gate:
+        if world == 1:
+            gate = parity_gate(dev)
+            failed = not gate['pass']
+        else:
+            gate = sharded_parity_gate(dev, rank, world)
+            verdict = torch.tensor([0 if (gate is None or gate['pass']) else 1], device=dev)
+            torch.distributed.all_reduce(verdict)          # (every rank leaves together)
+            failed = bool(verdict.item())
+        if failed:
+            if rank == 0:
+                print(json.dumps({'metric': 'training interactions/sec, Yahoo-implicit InvPref', 'value': None,
+                                  'unit': 'interactions/s', 'n_gpus': world, 'error': 'parity gate failed: no value is reported',
+                                  'parity_gate': gate}))
+            sys.exit(4)
+        torch.cuda.empty_cache()
+    mgr = build_manager(dev, rank, world, 'rows' if world > 1 else None)
+    n_total, gbatch = problem_size(world)
+    b_loc = gbatch // world                      # rows of a full minibatch on one rank (the byte models below are per rank)
+    dt, steps, warm_steps, graphs, n_timed, last, estep = timed_run(mgr, world, args.steps, args.warmup)
+    value = rate(n_timed, dt)
+    dumped = dump_outputs(mgr, args.dump_outputs, last, estep) if args.dump_outputs else None
+    roofline, detail = step_figures(mgr, world, graphs, b_loc, dt) if args.full else (None, {'timed_seconds': dt})
     out = {
         'metric': 'training interactions/sec, Yahoo-implicit InvPref', 'value': value, 'unit': 'interactions/s',
         'n_gpus': world, 'steps': steps, 'steps_requested': args.steps, 'interactions_timed': n_timed, 'warmup': warm_steps,
@@ -1114,19 +1133,23 @@ def main():
                    'parallelism': (f'{mgr.shard_mode}-sharded x{world}, 1 all-reduce/step '
                                    f'({4 * (mgr.state.n + 8 - mgr._ar_lo)} B)' if world > 1 else 'single GPU')},
         'timed_path': 'graph' if graphs else 'eager', 'plan_build_s': getattr(mgr, 'plan_build_s', None),
-        'roofline': roofline, 'detail': detail,
+        'full': bool(args.full),
     }
+    if roofline is not None:
+        out['roofline'] = roofline
+    out['detail'] = detail
     out['rccl_ranks'] = rccl_ranks    # ranks that took part in an RCCL all-reduce in front of the run (None: single GPU)
     if dumped is not None:
         out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
     out['parity_gate'] = gate if gate is not None else {
-        'pass': None, 'note': 'not run (--no-parity-gate)'}
+        'pass': None, 'note': 'not run (--no-parity-gate)' if args.full else 'not run (a plain run; --full runs it)'}
     if world > 1:
+        out['config']['parallelism'] = (f'rows-sharded x{world}, exchange {mgr.exchange}: 1 all-reduce of the flat gradient per '
+                                        f'optimiser step ({4 * (mgr.state.n + 8 - mgr._ar_lo)} B)')
+    if world > 1 and args.full:
         # the headline is the literal form BASELINE.json configs[3] names (rows + one all-reduce); beside it: the same
         # split with the exchange as reduce-scatter -> Adam on the rank's slice -> all-gather, and the xGMI-first
         # user-sharded layout.  UNMEASURED on hardware until a SCALE record exists.
-        out['config']['parallelism'] = (f'rows-sharded x{world}, exchange {mgr.exchange}: 1 all-reduce of the flat gradient per '
-                                        f'optimiser step ({4 * (mgr.state.n + 8 - mgr._ar_lo)} B)')
         del mgr
         torch.cuda.empty_cache()
         os.environ['INVPREF_EXCHANGE'] = 'scatter'
@@ -1169,7 +1192,7 @@ def main():
         out['detail'][other] = {'value': rate(n_w, dt_w), 'ms_per_step': dt_w / steps_w * 1e3, 'steps': steps_w,
                                 'interactions_total': mgr_w.n_total, 'global_batch': mgr_w.batch_size, 'exchange': 'allreduce'}
         os.environ.pop('INVPREF_EXCHANGE', None)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         del mgr
         torch.cuda.empty_cache()
         out['roofline_large'] = roofline_large(dev)
@@ -1187,7 +1210,7 @@ def main():
         out['detail']['end_to_end'] = {
             'reference_yahoo_config_E2_D40': end_to_end(dev, 2, 40),
             'baseline_config_E4_D64': end_to_end(dev, E, D)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out))

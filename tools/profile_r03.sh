@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_r03
 mkdir -p $OUT
-B="--steps 1550 --warmup 155 --no-cpu-baseline --no-extras"
+B="--steps 1550 --warmup 155 --full --no-cpu-baseline --no-extras"
 # per-kernel time of the bench command: the tracer sees the kernel nodes of the replayed graphs
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py $B > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 # the same command with every step issued eagerly
@@ -12,14 +12,14 @@ INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format 
 # L2 <-> fabric traffic of the step's two kernels (eager launches: one record per launch), and of the large launches
 for c in FETCH_SIZE WRITE_SIZE; do
   n=$(echo $c | cut -d_ -f1 | tr A-Z a-z)
-  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$n -- python3 $R/bench.py --steps 155 --warmup 155 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_$n.log
+  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$n -- python3 $R/bench.py --steps 155 --warmup 155 --full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_$n.log
   for shape in 400000x100000x4x64x1048576 400000x100000x8x128x1048576 400000x100000x16x256x1048576 6040x3706x8x128x65536 50000x51283x16x256x262144; do
     PROBE_EAGER=1 PROBE_SHAPE=$shape PROBE_STEPS=2 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/large_pmc_${n}_$shape -- python3 $R/tools/step_probe.py > $OUT/large_${n}_$shape.log 2>&1
   done
 done
 for c in "VALUBusy" "MemUnitStalled" "TCC_HIT_sum TCC_MISS_sum" "TCP_PENDING_STALL_CYCLES_sum" "TA_BUSY_avr"; do
   n=$(echo $c | tr ' ' '_')
-  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/extra_$n -- python3 $R/bench.py --steps 155 --warmup 155 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/extra_$n.log || echo "failed: $c"
+  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/extra_$n -- python3 $R/bench.py --steps 155 --warmup 155 --full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/extra_$n.log || echo "failed: $c"
 done
 # phase stamps of one full-size step and the loop benchmark
 PROBE_STAMPS=1 PROBE_TOP=6 timeout 120 python3 $R/tools/step_probe.py > $OUT/stamps_default_plan.txt 2>&1

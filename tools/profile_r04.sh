@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_r04
 rm -rf $OUT; mkdir -p $OUT
-B="--steps 1550 --warmup 155 --no-cpu-baseline --no-extras"
+B="--steps 1550 --warmup 155 --full --no-cpu-baseline --no-extras"
 ML=6040x3706x8x128x65536
 MIND=50000x51283x16x256x262144
 # per-kernel time of the bench command: the tracer sees the kernel nodes of the replayed graphs
@@ -14,7 +14,7 @@ INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format 
 # L2 <-> fabric traffic of the step's two kernels (eager launches: one record per launch), and of the other shapes
 for c in FETCH_SIZE WRITE_SIZE; do
   n=$(echo $c | cut -d_ -f1 | tr A-Z a-z)
-  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$n -- python3 $R/bench.py --steps 155 --warmup 155 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_$n.log
+  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$n -- python3 $R/bench.py --steps 155 --warmup 155 --full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_$n.log
   for shape in 400000x100000x4x64x1048576 400000x100000x8x128x1048576 400000x100000x16x256x1048576 $ML $MIND; do
     PROBE_EAGER=1 PROBE_SHAPE=$shape PROBE_STEPS=2 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/large_pmc_${n}_$shape -- python3 $R/tools/step_probe.py > $OUT/large_${n}_$shape.log 2>&1
   done
@@ -22,7 +22,7 @@ done
 # the Yahoo step's other counters
 for c in "VALUBusy" "MemUnitStalled" "TCC_HIT_sum TCC_MISS_sum" "TA_BUSY_avr"; do
   n=$(echo $c | tr ' ' '_')
-  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/extra_$n -- python3 $R/bench.py --steps 155 --warmup 155 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/extra_$n.log || echo "failed: $c"
+  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/extra_$n -- python3 $R/bench.py --steps 155 --warmup 155 --full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/extra_$n.log || echo "failed: $c"
 done
 # the wide-row instances (MovieLens: 16 lanes x 2 float4, E = 8; MIND: 32 lanes x 2, E = 16) and a cache-exceeding launch
 for shape in $ML $MIND 400000x100000x16x256x1048576; do

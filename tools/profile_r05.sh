@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_r05
 rm -rf $OUT; mkdir -p $OUT
-B="--steps 1550 --warmup 155 --no-cpu-baseline --no-extras"
+B="--steps 1550 --warmup 155 --full --no-cpu-baseline --no-extras"
 # per-kernel time of the bench command: the tracer sees the kernel nodes of the replayed graphs
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py $B > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 # the same command with every launch issued eagerly (the alternating launches, eager)
@@ -14,7 +14,7 @@ INVPREF_ALT=0 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -
 # L2 <-> fabric traffic of the step's kernel (eager launches: one record per launch)
 for c in FETCH_SIZE WRITE_SIZE; do
   n=$(echo $c | cut -d_ -f1 | tr A-Z a-z)
-  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$n -- python3 $R/bench.py --steps 155 --warmup 155 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_$n.log
+  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$n -- python3 $R/bench.py --steps 155 --warmup 155 --full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/pmc_$n.log
   # SURVEY 8(d)'s roofline launch at ITS size: 2^24 interactions, D = 64 (the two-launch form: the shape is not Yahoo-class ... it is, E = 4: both forms exist; the bench's sweep runs the two-launch form)
   PROBE_EAGER=1 PROBE_SHAPE=400000x100000x4x64x16777216 PROBE_STEPS=1 timeout 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/large24_pmc_${n}_D64 -- python3 $R/tools/step_probe.py > $OUT/large24_${n}.log 2>&1
 done
@@ -22,7 +22,7 @@ PROBE_EAGER=1 PROBE_SHAPE=400000x100000x4x64x16777216 PROBE_STEPS=1 timeout 600 
 # the alternating launch's other counters
 for c in "VALUBusy" "MemUnitStalled" "TCC_HIT_sum TCC_MISS_sum" "SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVES"; do
   n=$(echo $c | tr ' ' '_')
-  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/extra_$n -- python3 $R/bench.py --steps 155 --warmup 155 --no-cpu-baseline --no-extras > /dev/null 2> $OUT/extra_$n.log || echo "failed: $c"
+  INVPREF_NO_GRAPH=1 timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/extra_$n -- python3 $R/bench.py --steps 155 --warmup 155 --full --no-cpu-baseline --no-extras > /dev/null 2> $OUT/extra_$n.log || echo "failed: $c"
 done
 # the E-step kernel to kernel: plain instance vs the default tie-break instance, pinned-host indices vs a copy first
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/estep_stats -- python3 $R/tools/estep_prof.py > $OUT/estep_prof.log 2>&1

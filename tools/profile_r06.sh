@@ -4,8 +4,8 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_r06
 rm -rf $OUT; mkdir -p $OUT
-B="--steps 1550 --warmup 155 --no-cpu-baseline --no-extras"
-BQ="--steps 155 --warmup 155 --no-cpu-baseline --no-extras --no-parity-gate"   # counter passes: no gate epoch in the counters
+B="--steps 1550 --warmup 155 --full --no-cpu-baseline --no-extras"
+BQ="--steps 155 --warmup 155 --full --no-cpu-baseline --no-extras --no-parity-gate"   # counter passes: no gate epoch in the counters
 # per-kernel time of the bench command: the tracer sees the kernel nodes of the replayed graphs
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py $B > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 # the same command with every launch issued eagerly (the alternating launches, eager)
