@@ -12,7 +12,7 @@ import os
 import torch
 
 PKG = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('INVPREF_LIB') or os.path.join(PKG, 'libinvpref_hip.so')  # INVPREF_LIB: kernel A/B builds
+LIB_PATH = os.environ.get('INVPREF_LIB') or os.path.join(PKG, 'libinvpref_hip.so')  # INVPREF_LIB: variant builds (tests, tools)
 
 IMPLICIT, REWEIGHT_REC, REWEIGHT_CLS, REG_ONLY_EMBED, REG_ENV_EMBED, DENSE_REG, NO_GRAD, PURE_MF = 1, 2, 4, 8, 16, 32, 64, 128
 WEIGHTS_BY_ENV = 256   # INVPREF_WEIGHTS_BY_ENV: `sample_weights` holds class_weights[env_num], weight of i = class_weights[envs[i]]

@@ -380,10 +380,8 @@ int invpref_eval_topk_hip(const float *ratings, int64_t n_users, int64_t n_items
     if (k > kMaxK || k > n_items || n_items > 400000) return INVPREF_EUNSUPPORTED;
     if (n_users == 0) return 0;
     const size_t lds = sizeof(float) * 4 * (size_t)n_items;
-    // INVPREF_TOPK_SELECT=0: the k-pass kernels for every size (A/B, tests); default: the radix select beyond 4 096 items
-    static const bool sel_off = getenv("INVPREF_TOPK_SELECT") != nullptr && getenv("INVPREF_TOPK_SELECT")[0] == '0';
-    static const bool sel_all = getenv("INVPREF_TOPK_SELECT") != nullptr && getenv("INVPREF_TOPK_SELECT")[0] == '2';
-    if (!sel_off && (n_items > 4096 || sel_all) && n_items <= (1 << 20)) {
+    // the radix select beyond 4 096 items; the k-pass kernels below it
+    if (n_items > 4096 && n_items <= (1 << 20)) {
         const size_t lds_sel = sizeof(unsigned) * 2 * (((size_t)n_items + 31) / 32);
         if (lds_sel > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(topk_select_kernel),

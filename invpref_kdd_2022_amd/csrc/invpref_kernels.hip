@@ -931,51 +931,6 @@ __global__ __launch_bounds__(256) void stat_envs_kernel(const int64_t *__restric
     }
 }
 
-// estep_assign_kernel's epilogue as ONE workgroup of its own behind the assignment kernel, from a slab per workgroup (INVPREF_ESTEP_FOLD=kernel:
-// a kernel boundary + two round trips of one workgroup, against the epilogue's chain of store drain -> shard ticket -> top
-// ticket -> fold on the assignment kernel's own tail; measured per E-step in profiles/r06).
-__global__ __launch_bounds__(256) void estep_fold_kernel(const int *__restrict__ slabs, int nslabs, int E, int64_t N, EstepFin fin) {
-    __shared__ long long s_tot[INVPREF_MAX_ENVS + 1];
-    const int E1 = E + 1, total = nslabs * E1;
-    for (int i = threadIdx.x; i <= E; i += blockDim.x) s_tot[i] = 0;
-    __syncthreads();
-    // (the slabs are ONE contiguous int array [workgroups][E + 1]: thread t of the first `per` = 256 - 256 % (E + 1) threads
-    //  reads elements t, t + per, ... -- coalesced, and all of ONE class, t % (E + 1) -- twenty loads in flight, one
-    //  accumulator; then one LDS atomic per thread.  Every thread adding every count through LDS atomics on the same five
-    //  words took 138 us; one class at a time (a round trip each) 53 us)
-    const int per = (int)blockDim.x - (int)blockDim.x % E1;
-    if ((int)threadIdx.x < per) {
-        long long a = 0;
-        for (int i0 = threadIdx.x; i0 < total; i0 += 20 * per) {
-            int x[20];
-#pragma unroll
-            for (int k = 0; k < 20; k++) {
-                const int i = i0 + k * per;
-                x[k] = i < total ? slabs[i] : 0;
-            }
-#pragma unroll
-            for (int k = 0; k < 20; k++) a += x[k];
-        }
-        atomicAdd((unsigned long long *)&s_tot[(int)threadIdx.x % E1], (unsigned long long)a);
-    }
-    __syncthreads();
-    int64_t *row = nullptr;
-    if (fin.ring) row = fin.ring + (int64_t)((unsigned)fin.state[1] % (unsigned)fin.ring_cap) * E1;
-    if ((int)threadIdx.x < E) {
-        const long long c = s_tot[threadIdx.x];
-        const long long r = (c + 1 < N - 1) ? c + 1 : N - 1;
-        if (fin.counts) fin.counts[threadIdx.x] = c;
-        if (fin.class_w) fin.class_w[threadIdx.x] = (float)((double)r / (double)N);
-        if (row) row[threadIdx.x] = c;
-    }
-    if (threadIdx.x == 0) {
-        if (fin.diff) *fin.diff = s_tot[E];
-        if (row) row[E] = s_tot[E];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && fin.ring) fin.state[1] = fin.state[1] + 1;
-}
-
 // =====================================================================================
 // predict (models.py:393-407): scores[n, I] = f(Pu[users[n]] . Qi[i]) for ALL items, f = sigmoid
 // (implicit) or identity.  One 16-lane row keeps its user row in registers and sweeps the item
@@ -1129,7 +1084,8 @@ inline int mstep_blocks(int64_t B) {
 }
 inline int estep_blocks(int64_t N) {
     int64_t nb = (N + (kEstepThreads / kRow) - 1) / (kEstepThreads / kRow);
-    static const int cap_env = std::getenv("INVPREF_ESTEP_BLOCKS") ? atoi(std::getenv("INVPREF_ESTEP_BLOCKS")) : 0;   // (A/B knob)
+    // (INVPREF_ESTEP_BLOCKS, test hook: a smaller grid -- many passes per workgroup, which only multi-GB inputs reach otherwise)
+    static const int cap_env = std::getenv("INVPREF_ESTEP_BLOCKS") ? atoi(std::getenv("INVPREF_ESTEP_BLOCKS")) : 0;
     const int cap = cap_env > 0 && cap_env < kEstepMaxBlocks ? cap_env : kEstepMaxBlocks;
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
@@ -1365,7 +1321,8 @@ int invpref_predict_hip(const float *user_table, const float *item_table, const 
     gy = (unsigned)((item_num + per - 1) / per);
     hipStream_t st = (hipStream_t)stream;
     // full 64-float chunks (factor_num 64 / 128 / 256) on 16-byte-aligned tables: the dense contraction on the matrix cores
-    // (predict_mm_kernel: fp32 MFMA, the canonical summation order); INVPREF_PREDICT_MM=0 keeps the vector-ALU sweep
+    // (predict_mm_kernel: fp32 MFMA, the canonical summation order); INVPREF_PREDICT_MM=0 (test hook) keeps the vector-ALU
+    // sweep that other row lengths and unaligned tables take
     static const bool mm_off = std::getenv("INVPREF_PREDICT_MM") != nullptr && std::getenv("INVPREF_PREDICT_MM")[0] == '0';
     if (vec && !mm_off && (factor_num == 64 || factor_num == 128 || factor_num == 256) && n_users >= 16 && item_num >= 16) {
         const unsigned ux = (unsigned)((n_users + 63) / 64);
@@ -1571,12 +1528,9 @@ static int estep_launch(const InvPrefTables *tables, const int64_t *users, const
             hipLaunchKernelGGL(eps_unrank_kernel<int64_t>, dim3((unsigned)ub), dim3(256), 0, st, (const int64_t *)perm_index, N, t.E, fac, eps_packed);
     }
     EstepFin fin{};
-    // INVPREF_ESTEP_FOLD=epilogue (default) | kernel: where the fused entry point folds the count slabs (see estep_fold_kernel)
-    static const bool fold_kernel = std::getenv("INVPREF_ESTEP_FOLD") != nullptr && std::getenv("INVPREF_ESTEP_FOLD")[0] == 'k';
     if (fused) {
         fin = *fused;
         if (!table_form) fin.perm_table = nullptr;
-        if (fold_kernel) fin.state = nullptr;          // (the assignment kernel stores plain slabs and takes no ticket)
     }
 #define ECALL1(NCV, VECV, NARV)                                                                                   \
     hipLaunchKernelGGL((estep_assign_kernel<NCV, VECV, NARV>), dim3(nb), dim3(kEstepThreads), lds + lds_extra, st, t, users, items, \
@@ -1591,10 +1545,6 @@ static int estep_launch(const InvPrefTables *tables, const int64_t *users, const
 #undef ECALL1
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return (int)err;
-    if (fused && fold_kernel) {
-        hipLaunchKernelGGL(estep_fold_kernel, dim3(1), dim3(256), 0, st, slabs, nb, t.E, N, *fused);
-        return (int)hipGetLastError();
-    }
     if (fused) return 0;   // (counts, diff and class weights came out of the kernel's epilogue; no sample-weight array)
     // every workgroup of stat_envs folds ALL the count slabs for itself before it gathers its share of the sample weights:
     // at most 256 of them (one per CU, a grid-stride share of rows each) -- a thousand workgroups read 40 MB of slabs for

@@ -6,8 +6,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <cstdio>
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
@@ -242,14 +240,6 @@ InvPrefHostPlan *build(const int64_t *users, const int64_t *items, const float *
         p.rounds_per_task < 1 || p.item_rounds_per_task < 1 || p.rows_per_stream_task < 1 ||
         (p.lanes_per_group != 16 && p.lanes_per_group != 32 && p.lanes_per_group != 64) || (n > 0 && (!users || !items || !scores)))
         return nullptr;
-    const bool timing = std::getenv("INVPREF_PLAN_TIMING") != nullptr;   // phase times on stderr
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[invpref_plan] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
     const int ng = kThreads / p.lanes_per_group, ncls = p.n_classes;
     // a big minibatch spreads its pieces (validation, the two sorts, then 2 x n_classes round lists) over threads
     const int nt = n >= (1 << 18) ? std::max(1, threads) : 1;
@@ -259,7 +249,6 @@ InvPrefHostPlan *build(const int64_t *users, const int64_t *items, const float *
     // slot), item_list [n][2] = (user, slot); rec_slot[position] = the interaction's slot = its index in the item order
     int32_t *const ul = hp->alloc(3, (size_t)n * 4), *const il = hp->alloc(4, (size_t)n * 2);
     int32_t *const ps = hp->alloc(6, (size_t)n);
-    lap("allocate lists");
     Side us, is;
     const int half = std::max(1, nt / 2);
     bool ok[2] = {true, true};
@@ -285,7 +274,6 @@ InvPrefHostPlan *build(const int64_t *users, const int64_t *items, const float *
         delete hp;
         return nullptr;
     }
-    lap("sort both sides");
     {   // the slot of every entry of the user list (the item side's sort has placed them all by now)
         const int chunks = nt > 1 ? nt * 4 : 1;
         parallel_for(chunks, nt, [&](int c) {
@@ -293,14 +281,12 @@ InvPrefHostPlan *build(const int64_t *users, const int64_t *items, const float *
             for (int64_t k = lo; k < hi; k++) ul[(size_t)k * 4 + 3] = ps[(size_t)ul[(size_t)k * 4 + 1]];
         });
     }
-    lap("slots into the user list");
     // touched rows of every class, in increasing order
     std::vector<std::vector<int32_t>> urows((size_t)ncls), irows((size_t)ncls);
     for (int64_t r = 0; r < U; r++)
         if (us.cnt[(size_t)r]) urows[(size_t)((r >> kClassShift) % ncls)].push_back((int32_t)r);
     for (int64_t r = 0; r < I; r++)
         if (is.cnt[(size_t)r]) irows[(size_t)((r >> kClassShift) % ncls)].push_back((int32_t)r);
-    lap("class rows");
     std::vector<std::vector<int32_t>> cd((size_t)(2 * ncls)), cit((size_t)(2 * ncls));
     parallel_for(2 * ncls, nt, [&](int q) {
         const int c = q >> 1;
@@ -310,7 +296,6 @@ InvPrefHostPlan *build(const int64_t *users, const int64_t *items, const float *
             class_rounds(is, n, il, 2, 2, ng, p.item_per_slice, p.item_rounds_per_task, p.push ? 0 : 3, irows[(size_t)c],
                          cd[(size_t)q], cit[(size_t)q], 0);
     });
-    lap("rounds of the classes");
     int32_t cls[8][8];
     std::memset(cls, 0, sizeof(cls));
     // untouched rows: streamed, no job
@@ -367,7 +352,6 @@ InvPrefHostPlan *build(const int64_t *users, const int64_t *items, const float *
     }
     for (int c = 0; c < ncls; c++) sr.insert(sr.end(), s1[(size_t)c].begin(), s1[(size_t)c].end());
     for (int c = 0; c < ncls; c++) sr.insert(sr.end(), s2[(size_t)c].begin(), s2[(size_t)c].end());
-    lap("concatenate + stream rows");
     hp->arr[7].assign(&cls[0][0], &cls[0][0] + 64);
     return hp;
 }

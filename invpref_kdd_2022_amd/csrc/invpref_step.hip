@@ -1674,11 +1674,13 @@ int launch_step(const InvPrefTables *tables, const InvPrefRowPlan *plan, const i
 #define CALL_W1(LGV, NCV, VECV, EMAXV, EV2, BYE)                                                                  \
     do {                                                                                                          \
         if ((rc = ensure_lds(mstep_apply_wide_kernel<LGV, NCV, VECV, EMAXV, EV2>, lds2))) return rc;            \
-        if (VECV && use_mm) {   /* full rows: the classifier as products over the workgroup's interactions (step_wide_mm.hpp) */ \
-            const size_t ldsm = sizeof(float) * MGeo<LGV, NCV, EMAXV, EV2>::total;                                \
-            if ((rc = ensure_lds(mstep_eval_mm_kernel<LGV, NCV, EMAXV, EV2, BYE>, ldsm))) return rc;             \
-            if (wg1 > 0)                                                                                          \
-                hipLaunchKernelGGL((mstep_eval_mm_kernel<LGV, NCV, EMAXV, EV2, BYE>), dim3(wg1), dim3(kThreads), ldsm, st, t, a1); \
+        if (VECV && LGV == 32 && use_mm) {   /* full rows: the classifier as products over the workgroup's interactions */ \
+            if constexpr (VECV && LGV == 32) {   /* (step_wide_mm.hpp; instantiated for rows on 32 lanes only) */     \
+                const size_t ldsm = sizeof(float) * MGeo<LGV, NCV, EMAXV, EV2>::total;                            \
+                if ((rc = ensure_lds(mstep_eval_mm_kernel<LGV, NCV, EMAXV, EV2, BYE>, ldsm))) return rc;         \
+                if (wg1 > 0)                                                                                      \
+                    hipLaunchKernelGGL((mstep_eval_mm_kernel<LGV, NCV, EMAXV, EV2, BYE>), dim3(wg1), dim3(kThreads), ldsm, st, t, a1); \
+            }                                                                                                     \
         } else {                                                                                                  \
             if ((rc = ensure_lds(mstep_eval_wide_kernel<LGV, NCV, VECV, EMAXV, EV2, BYE>, lds1))) return rc;    \
             if (wg1 > 0)                                                                                          \
@@ -1704,12 +1706,13 @@ int launch_step(const InvPrefTables *tables, const InvPrefRowPlan *plan, const i
     do {                                                                                           \
         if (emax == 8) CALL_W(LGV, NCV, VECV, 8, EV2); else CALL_W(LGV, NCV, VECV, 16, EV2);       \
     } while (0)
-    // INVPREF_WIDE_MM=0 (diagnostics / A-B): the per-interaction classifier of step_wide.hpp for full rows too
-    // (default: rows on 32 lanes -- D = 256: launch 1 14.4 vs 18.1 ms at 2^24 interactions; rows on 16 lanes measured level
-    //  or slower, profiles/r05/EXPERIMENTS.md; INVPREF_WIDE_MM=1 takes the form for every full-row wide instance)
-    const char *mm_env = getenv("INVPREF_WIDE_MM");   // (read per call: the tests switch forms inside one process)
-    const bool mm_want = mm_env ? mm_env[0] == '1' : shp.lg == 32;
-    const bool use_mm = mm_want && !pure && t.b != nullptr && (reinterpret_cast<uintptr_t>(t.W) & 15u) == 0;
+    // the MFMA classifier for full rows on 32 lanes (D = 256: launch 1 14.4 vs 18.1 ms at 2^24 interactions; rows on 16 lanes
+    // measured level or slower, profiles/r05/EXPERIMENTS.md).  INVPREF_WIDE_MM=0 (test hook): the per-interaction classifier of
+    // step_wide.hpp, the form PureMF and unaligned classifier weights take, for those rows too -- read per call: the tests
+    // compare the two forms inside one process
+    const char *mm_env = getenv("INVPREF_WIDE_MM");
+    const bool use_mm = shp.lg == 32 && !(mm_env && mm_env[0] == '0') && !pure && t.b != nullptr &&
+                        (reinterpret_cast<uintptr_t>(t.W) & 15u) == 0;
     if (shp.wide) {
         // (the wide kernels' vector form is for FULL rows only -- factor_num 64 / 128 / 256: no clamps or selects behind a
         //  load; any other row length takes their element-wise form)
@@ -1732,10 +1735,8 @@ int launch_step(const InvPrefTables *tables, const InvPrefRowPlan *plan, const i
         if (profile_event && hipEventRecord((hipEvent_t)profile_event, st) != hipSuccess) return INVPREF_EINVAL; \
         hipLaunchKernelGGL((mstep_apply_kernel<LGV, VECV, EMAXV>), dim3(grid2), dim3(kThreads), lds2, st, t, a2, f); \
     } while (0)
-    // rows of exactly 64 floats: loads with nothing behind them (row4<VEC, FULL>); INVPREF_NO_FULL=1 (diagnostics) takes the
-    // element-wise-guarded instances instead
-    static const bool no_full = getenv("INVPREF_NO_FULL") != nullptr && getenv("INVPREF_NO_FULL")[0] == '1';
-    const bool full = vec && t.D == 64 && !no_full;
+    // rows of exactly 64 floats: loads with nothing behind them (row4<VEC, FULL>)
+    const bool full = vec && t.D == 64;
     if (full) {
         if ((rc = ensure_lds(mstep_eval_kernel<16, true, 4, true>, lds1))) return rc;
         if ((rc = ensure_lds(mstep_apply_kernel<16, true, 4, true>, lds2))) return rc;

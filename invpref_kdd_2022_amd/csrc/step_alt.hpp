@@ -1078,8 +1078,7 @@ int launch_alt(const InvPrefTables *tables, const InvPrefTables *exp_avg, const 
     const size_t lds = lds_job > lds_fold ? lds_job : lds_fold;
     const int grid = a.first_task_block + per_class * ncls;
     const bool vec = vec_ok(tables) && vec_ok(exp_avg) && vec_ok(exp_avg_sq);
-    static const bool no_full = getenv("INVPREF_NO_FULL") != nullptr && getenv("INVPREF_NO_FULL")[0] == '1';
-    const bool full = vec && D == 64 && !no_full;
+    const bool full = vec && D == 64;
 #define CALL_ALT_M(VECV, FULLV, MODEV, THR)                                                                      \
     do {                                                                                                         \
         if ((rc = ensure_lds(mstep_alt_kernel<VECV, FULLV, MODEV, THR>, lds))) return rc;                        \

@@ -1,7 +1,7 @@
-// step_wide_mm.hpp -- launch 1 of the planned M-step for FULL wide rows (factor_num = 128 / 256 -- and 64 with more than
-// four environments) with the classifier as three small GEMMs over the WORKGROUP's interactions of a lock-step iteration
-// (round 5).  Included by invpref_step.hip behind step_wide.hpp, whose plans, records, contribution rows, slabs, launch 2
-// and fold it shares unchanged.
+// step_wide_mm.hpp -- launch 1 of the planned M-step for FULL rows on 32 lanes (factor_num = 256) with the classifier as
+// three small GEMMs over the WORKGROUP's interactions of a lock-step iteration (round 5; rows on 16 lanes measured level or
+// slower: invpref_step.hip instantiates the kernel for 32 lanes only).  Included by invpref_step.hip behind step_wide.hpp,
+// whose plans, records, contribution rows, slabs, launch 2 and fold it shares unchanged.
 //
 // step_wide.hpp evaluates the classifier (models.py:206-209: logits Z = W x + b, their backward G = gz W) per
 // interaction on the vector ALU: every lane group reads all of W from LDS twice per interaction (D = 256, E = 16: 64

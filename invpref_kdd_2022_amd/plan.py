@@ -296,7 +296,7 @@ def build_row_plans(users: np.ndarray, items: np.ndarray, scores: np.ndarray, of
     offsets = np.ascontiguousarray(offsets, np.int64)
     nb = len(offsets) - 1
     L = _native_lib()
-    if L is None or kw.get('native') is False or os.environ.get('INVPREF_PLAN_NATIVE', '1') == '0':
+    if L is None or kw.get('native') is False:
         return [build_row_plan(users[offsets[k]:offsets[k + 1]], items[offsets[k]:offsets[k + 1]],
                                scores[offsets[k]:offsets[k + 1]], user_num, item_num, **kw) for k in range(nb)]
     kw.pop('native', None)
@@ -319,13 +319,13 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
                    rounds_per_task: int | None = None, item_rounds_per_task: int | None = None, user_range=None,
                    n_classes: int | None = None, rows_per_stream_task: int | None = None,
                    stream_split: float | None = None, push: bool | None = None, env_num: int | None = None,
-                   native: bool | None = None, _resolve_only: bool = False) -> dict:
+                   native: bool = True, _resolve_only: bool = False) -> dict:
     """users/items/scores: ONE minibatch (or this rank's slice of it); scores as the fp32 labels.
     factor_num: decides the row layout the plan is built for (lanes_of).
     per_slice / item_per_slice: interactions one group walks for a user / an item row (more interactions: more slices).
     user_range: (lo, hi) user rows this rank is responsible for (user-sharded runs): untouched user rows
     outside it are not streamed (nobody reads their gradient or updates them here).
-    n_classes: XCD-affine task order (default 8 = the XCDs of an MI355X; INVPREF_PLAN_CLASSES): table rows are dealt
+    n_classes: XCD-affine task order (default 8 = the XCDs of an MI355X): table rows are dealt
     to the classes in blocks of 64 rows, and every job / streamed row of class c is run by a workgroup with
     blockIdx.x % n_classes == c -- under the round-robin placement of workgroups the SAME XCD step after step, so
     the row's parameters and Adam moments are still in that XCD's L2 when the next step reads them (measured,
@@ -340,8 +340,10 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
     push: the "push" form of the item side (InvPrefRowPlan.push_slot): launch 1 stores every interaction's two
     contribution rows to its item's gradient at the interaction's item-sorted slot and launch 2 sums contiguous rows
     instead of gathering partner rows + records.  One extra row write + read per interaction and table; default
-    (INVPREF_PLAN_PUSH): on while the step's working set is cache-resident or that traffic is a small share of the
-    step's bytes (the item jobs become one burst of contiguous loads -- no hot-row tail)."""
+    on while the step's working set is cache-resident or that traffic is a small share of the
+    step's bytes (the item jobs become one burst of contiguous loads -- no hot-row tail).
+    native: build the arrays with the native builder (the default, when the library is there) or with the numpy reference
+    (False; tests/test_plan_native.py holds the two equal)."""
     users = np.asarray(users, dtype=np.int64)
     items = np.asarray(items, dtype=np.int64)
     scores = np.asarray(scores, dtype=np.float32)
@@ -356,7 +358,7 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
     # throughput-bound and get long slices (measured at 65 536 .. 1 048 576 interactions: 16 per slice beats 2 .. 8 -- a
     # slice walks its interactions with the next gathers in flight, while every further slot, round and workgroup pays
     # its own start-up round trips), then more rounds per task.
-    target = int(os.environ.get('INVPREF_PLAN_TARGET_WGS', str(TARGET_WORKGROUPS)))
+    target = TARGET_WORKGROUPS
     _cnt = {}
     def counts(side):          # interactions per row of a side (one pass over the minibatch each, on first use)
         if side not in _cnt:
@@ -374,8 +376,6 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
         c = cnt[cnt > 0]
         need = np.maximum(1, -(-c // ps))
         return int(np.minimum(ng, 1 << np.ceil(np.log2(need)).astype(np.int64)).sum()) // ng + 1
-    if per_slice is None and 'INVPREF_PLAN_PER_SLICE' in os.environ:
-        per_slice = int(os.environ['INVPREF_PLAN_PER_SLICE'])
     if per_slice is None:
         # shortest slices while launch 1's jobs are resident at once (one latency chain: a Yahoo step); otherwise the
         # shortest slice that costs no more than 5 % more rounds than 16 per slice does (measured at 32 768 Yahoo-shaped
@@ -399,7 +399,7 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
                 if r16 > 6 * resident:
                     fewest = rounds_for(ucnt0, 96)
                     per_slice = next((ps for ps in (24, 32, 40, 48, 56, 64) if rounds_for(ucnt0, ps) <= 1.05 * fewest), 96)
-            if r16 <= 6 * resident and os.environ.get('INVPREF_PLAN_SIMULATE', '1') == '1':
+            if r16 <= 6 * resident:
                 # a launch of a few residencies: where its last workgroup ends depends on how the task lengths pack
                 # into the resident slots.  Estimate that for each slice length (list scheduling of the tasks in launch
                 # order) and take the shortest slice within 2 % of the best (measured: MovieLens-shaped steps 85.5 us at 12
@@ -409,23 +409,18 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
                 best = min(est.values())
                 per_slice = min(ps for ps, t in est.items() if t <= 1.02 * best)
     if push is None:
-        env = os.environ.get('INVPREF_PLAN_PUSH')
-        if env is not None:
-            push = env == '1'
-        else:
-            # measured (tools/ab.sh, push vs pull): push wins wherever the step's working set sits in the 256 MiB Infinity
-            # Cache (Yahoo 19.4 vs 20.4 us, Yahoo with B = N 134 vs 178, MovieLens 100 vs 111) and wherever the contribution
-            # rows are a small share of the bytes (a 1/8 MIND minibatch 457 vs 534); it loses on cache-exceeding launches
-            # whose rows dominate (2^20 interactions over 500 000 rows: 768 vs 732)
-            p_floats = 2 * (user_num + item_num) * factor_num
-            contrib = n * padded_row(factor_num) * 16               # two padded rows written and read per interaction
-            total = n * (32 + 16 * factor_num) + 24 * p_floats       # algorithmic bytes of the step
-            resident = 20 * p_floats + contrib // 2 <= 200e6       # p, p', m, v, g-free: five flat buffers + the rows
-            push = n > 0 and (resident or contrib <= 0.2 * total)
-            # (Round 6, records at the interaction's slot: on UNIFORM ids at the Yahoo tables the pull form overtakes push from
-            #  65 536 interactions on -- B = N 82.5 vs 87.3 us -- but on skewed ids, Zipf or the Yahoo-like popularity, push stays
-            #  12-21 % ahead at every size (B = N 100-103 vs 118-125 us): its hot items sum contiguous rows.  The rule stands;
-            #  tools/ab_pushpull.sh, ab_pushpull2.sh)
+        # measured (push vs pull): push wins wherever the step's working set sits in the 256 MiB Infinity Cache (Yahoo 19.4
+        # vs 20.4 us, Yahoo with B = N 134 vs 178, MovieLens 100 vs 111) and wherever the contribution rows are a small share
+        # of the bytes (a 1/8 MIND minibatch 457 vs 534); it loses on cache-exceeding launches whose rows dominate (2^20
+        # interactions over 500 000 rows: 768 vs 732)
+        p_floats = 2 * (user_num + item_num) * factor_num
+        contrib = n * padded_row(factor_num) * 16               # two padded rows written and read per interaction
+        total = n * (32 + 16 * factor_num) + 24 * p_floats       # algorithmic bytes of the step
+        resident = 20 * p_floats + contrib // 2 <= 200e6       # p, p', m, v, g-free: five flat buffers + the rows
+        push = n > 0 and (resident or contrib <= 0.2 * total)
+        # (Round 6, records at the interaction's slot: on UNIFORM ids at the Yahoo tables the pull form overtakes push from
+        #  65 536 interactions on -- B = N 82.5 vs 87.3 us -- but on skewed ids, Zipf or the Yahoo-like popularity, push stays
+        #  12-21 % ahead at every size (B = N 100-103 vs 118-125 us): its hot items sum contiguous rows.  The rule stands.)
     if lanes == 32:
         # rows of more than 128 floats: embed_env's outer product runs in launch 2's item jobs, which need the partner
         # rows and the records -- the pull form (csrc/step_wide.hpp, EVL2)
@@ -435,30 +430,28 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
         # (wide rows, push form, minibatches of several residencies: longer item slices, fewer item workgroups -- MovieLens-
         #  shaped steps 66.7 -> 64.9 us at 16 per slice instead of 4)
         floor = (16 if (factor_num > 64 and n > 16384) else 4) if push else 2
-        item_per_slice = int(os.environ.get('INVPREF_PLAN_ITEM_PER_SLICE',
-                                            str(min(32, max(floor, -(-n // (ng * 2 * target)))))))
+        item_per_slice = min(32, max(floor, -(-n // (ng * 2 * target))))
 
     if rounds_per_task is None:
         # (at most 8 rounds per task for rows on 16 lanes -- measured on cache-exceeding launches of 2^20 .. 2^24 interactions:
         #  D = 64 +4 %, D = 128 +2 .. +5 % over 16 -- and 16 for rows on 32 lanes, whose tasks stage 32 KB of tables first: -3 % at 8)
         # (long slices, round 6: about 200 interactions per group and task -- 4 rounds at 48-56 per slice: +2-3 % over 8 at 2^24)
-        #  (rows on 32 lanes, 56 per slice at 2^24: 4 rounds 20.6 ms, 8 20.8, 16 21.1, 2 21.0 -- tools/ab_plan24c.sh)
+        #  (rows on 32 lanes, 56 per slice at 2^24: 4 rounds 20.6 ms, 8 20.8, 16 21.1, 2 21.0)
         cap = (16 if per_slice < 40 else 4) if lanes == 32 else min(8, max(2, 224 // max(per_slice, 1)))
         # (rows on 32 lanes: about 800 tasks -- not quite two residencies of 512 -- instead of 1 536: measured at MIND's tables
         #  with minibatches of 32 768 .. 262 144, best at 4 / 6 / 6 / 4-8 rounds per task: +5 % at the rank share of eight GPUs)
         tgt = target * 800 // TARGET_WORKGROUPS if lanes == 32 else target
-        rounds_per_task = int(os.environ.get('INVPREF_PLAN_ROUNDS', '0')) or \
-            min(cap, max(1, round(rounds_for(counts('u'), per_slice) / tgt)))
+        rounds_per_task = min(cap, max(1, round(rounds_for(counts('u'), per_slice) / tgt)))
     if item_rounds_per_task is None:
         # (rows of up to 1 KB, pull form: an item task first stages two [E, D] tables of up to 16 KB each, holds only eight
         #  rows and leaves a 16 KB partial slab of embed_env's gradient -- fewer, longer tasks: MIND-shaped steps 898 -> 769 us
         #  at 8 rounds per task instead of 1)
         few = lanes == 32
-        item_rounds_per_task = int(os.environ.get('INVPREF_PLAN_ITEM_ROUNDS', '0')) or \
-            min(16, max(1, round(rounds_for(counts('i'), item_per_slice) / (target // 2 if few else 4 * target))))
+        item_rounds_per_task = min(16, max(1, round(rounds_for(counts('i'), item_per_slice) /
+                                                    (target // 2 if few else 4 * target))))
     if rows_per_stream_task is None:
-        rows_per_stream_task = int(os.environ.get('INVPREF_PLAN_STREAM_ROWS', str(stream_rows_default(factor_num))))
-    rows_per_stream_task2 = int(os.environ.get('INVPREF_PLAN_STREAM_ROWS2', str(rows_per_stream_task)))  # one iteration of a workgroup
+        rows_per_stream_task = stream_rows_default(factor_num)
+    rows_per_stream_task2 = rows_per_stream_task     # (launch 2's own field of the struct: the same number)
     ucnt, icnt = counts('u'), counts('i')
     if n and max(ucnt.max(), icnt.max()) >= MAX_ROW_COUNT:
         raise ValueError(f'a row with {max(ucnt.max(), icnt.max())} interactions in one minibatch overflows the job descriptor')
@@ -471,25 +464,22 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
     stream_u = np.flatnonzero(untouched_u).astype(np.int32)     # untouched rows: streamed, no job
     stream_i = np.flatnonzero(icnt == 0).astype(np.int32)
     if n_classes is None:
-        n_classes = int(os.environ.get('INVPREF_PLAN_CLASSES', str(N_CLASSES)))
+        n_classes = N_CLASSES
     n_classes = max(1, min(8, n_classes))
-    if stream_split is None and 'INVPREF_PLAN_STREAM_SPLIT' in os.environ:
-        stream_split = float(os.environ['INVPREF_PLAN_STREAM_SPLIT'])
     n_stream = len(stream_u) + len(stream_i)
     fill_cap = 0   # launch 1 residency (workgroups) the default split fills with stream tasks; 0 = plain balance
     if stream_split is None:
-        if small and os.environ.get('INVPREF_PLAN_FILL', '1') == '1':
+        if small:
             fill_cap = RESIDENT_SMALL
         # row moves (one row read or written in both tables of a side = 2): a touched or streamed row costs 12 (p, m, v
         # in, p', m', v' out), an interaction 4 gathered rows per launch; launch 1 also evaluates, hence the bias
         tu, ti = int((ucnt > 0).sum()), int((icnt > 0).sum())
-        bias = float(os.environ.get('INVPREF_PLAN_EVAL_COST', '3.0'))
-        s1 = (12.0 * ti - 12.0 * tu - bias * n + 12.0 * n_stream) / 24.0
+        s1 = (12.0 * ti - 12.0 * tu - 3.0 * n + 12.0 * n_stream) / 24.0
         stream_split = min(1.0, max(0.0, s1 / n_stream)) if n_stream else 0.0
     # wide-row instances, one round per task: launch 1's rounds in co-residency order (_side_rounds: snake)
-    snake_user = int(os.environ.get('INVPREF_PLAN_SNAKE', str(CUS_PER_XCD if (not small and rounds_per_task == 1) else 0)))
+    snake_user = CUS_PER_XCD if (not small and rounds_per_task == 1) else 0
     # ---- every parameter is resolved: the arrays themselves come from the native builder (csrc/invpref_plan.cpp, the same
-    # arrays byte for byte: tests/test_plan_native.py) unless INVPREF_PLAN_NATIVE=0 or `_resolve_only`
+    # arrays byte for byte: tests/test_plan_native.py) unless native=False or `_resolve_only`
     resolved = dict(lanes=lanes, per_slice=int(per_slice), item_per_slice=int(item_per_slice),
                     rounds_per_task=int(rounds_per_task), item_rounds_per_task=int(item_rounds_per_task),
                     n_classes=int(n_classes), rows_per_stream_task=int(rows_per_stream_task),
@@ -499,8 +489,6 @@ def build_row_plan(users: np.ndarray, items: np.ndarray, scores: np.ndarray, use
                     user_hi=int(user_num) if user_range is None else int(user_range[1]), factor_num=factor_num, n=n)
     if _resolve_only:
         return resolved
-    if native is None:
-        native = os.environ.get('INVPREF_PLAN_NATIVE', '1') != '0'
     if native and _native_lib() is not None:
         return _native_build(users, items, scores, user_num, item_num, resolved)
     pu = np.argsort(users, kind='stable')
@@ -675,6 +663,7 @@ class AltPlanStruct(C.Structure):
 
 
 ALT_ARRAYS = ('desc', 'pend', 'list', 'push_slot', 'stream')
+ALT_PER_SLICE = 2          # interactions per slice of an evaluating side's jobs (both sides; train.py picks the slots with it)
 ALT_PEND_JOB_MIN = 9       # rows WITHOUT a current interaction and at least this many pending rows get a (sliced) job
 ALT_PEND_PER_SLICE = 4
 
@@ -685,7 +674,7 @@ def alt_supported(factor_num: int, env_num: int) -> bool:
 
 def build_alt_plan(cur, prev, side: int, user_num: int, item_num: int, factor_num: int = 64, per_slice: int | None = None,
                    rounds_per_task: int = 1, n_classes: int | None = None, rows_per_stream_task: int | None = None,
-                   n_partials_prev: int = 0, native: bool | None = None, slots: int = 16) -> dict:
+                   n_partials_prev: int = 0, native: bool = True, slots: int = 16) -> dict:
     """cur: (users, items, scores) of the minibatch this launch evaluates, or None (a flush launch); prev: (users, items)
     of the minibatch the previous launch evaluated (from the OTHER side), or None (first launch of a run); side: 0 = the
     user tables evaluate / are updated, 1 = the item tables.  n_partials_prev: job tasks of the previous launch (its
@@ -696,15 +685,13 @@ def build_alt_plan(cur, prev, side: int, user_num: int, item_num: int, factor_nu
     ng = slots
     own_num = user_num if side == 0 else item_num
     if per_slice is None:
-        per_slice = int(os.environ.get('INVPREF_ALT_PER_SLICE_I' if side else 'INVPREF_ALT_PER_SLICE_U', '2'))
+        per_slice = ALT_PER_SLICE
     if n_classes is None:
-        n_classes = int(os.environ.get('INVPREF_PLAN_CLASSES', str(N_CLASSES)))
+        n_classes = N_CLASSES
     n_classes = max(1, min(8, n_classes))
     if rows_per_stream_task is None:
-        rows_per_stream_task = int(os.environ.get('INVPREF_PLAN_STREAM_ROWS', str(stream_rows_default(factor_num))))
+        rows_per_stream_task = stream_rows_default(factor_num)
     has_cur, has_prev = cur is not None, prev is not None
-    if native is None:
-        native = os.environ.get('INVPREF_PLAN_NATIVE', '1') != '0'
     if native and _native_lib() is not None and rounds_per_task == 1:
         L = _native_lib()
         z64 = np.zeros(0, np.int64)
@@ -831,9 +818,6 @@ def alt_slots_for(own_rows: np.ndarray, n_rows: int, per_slice: int, n_classes: 
     """Group slots per round for a side's evaluating launches: 32 (workgroups of 512 threads, one per CU: a hot row's
     interactions spread over up to 32 slices) while such a launch still fits ONE residency of the 256 CUs, else 16 (256
     threads, three per CU).  own_rows: the side's row of every interaction of a representative minibatch."""
-    forced = os.environ.get('INVPREF_ALT_SLOTS')
-    if forced in ('16', '32'):
-        return int(forced)
     cnt = np.bincount(np.asarray(own_rows, np.int64), minlength=n_rows)
     c = cnt[cnt > 0]
     if len(c) == 0:
@@ -855,19 +839,19 @@ def build_alt_plans(users: np.ndarray, items: np.ndarray, scores: np.ndarray, sp
     users, items = np.ascontiguousarray(users, np.int64), np.ascontiguousarray(items, np.int64)
     scores = np.ascontiguousarray(scores, np.float32)
     if per_slice_u is None:
-        per_slice_u = int(os.environ.get('INVPREF_ALT_PER_SLICE_U', '2'))
+        per_slice_u = ALT_PER_SLICE
     if per_slice_i is None:
-        per_slice_i = int(os.environ.get('INVPREF_ALT_PER_SLICE_I', '2'))
+        per_slice_i = ALT_PER_SLICE
     if n_classes is None:
-        n_classes = int(os.environ.get('INVPREF_PLAN_CLASSES', str(N_CLASSES)))
+        n_classes = N_CLASSES
     n_classes = max(1, min(8, n_classes))
     if rows_per_stream_task is None:
-        rows_per_stream_task = int(os.environ.get('INVPREF_PLAN_STREAM_ROWS', str(stream_rows_default(factor_num))))
+        rows_per_stream_task = stream_rows_default(factor_num)
 
     def rng(r):
         return None if r is None else (users[r[0]:r[0] + r[1]], items[r[0]:r[0] + r[1]], scores[r[0]:r[0] + r[1]])
     L = _native_lib()
-    if L is not None and os.environ.get('INVPREF_PLAN_NATIVE', '1') != '0' and (per_slice_u != per_slice_i or slots_u != slots_i):
+    if L is not None and (per_slice_u != per_slice_i or slots_u != slots_i):
         # the sides differ in slice length or slots per round (the Yahoo shape: rounds of 16 slots for the users' launches, of
         # 32 for the items'): ONE threaded native call per side instead of one serial call per plan
         out = [None] * len(specs)
@@ -881,7 +865,7 @@ def build_alt_plans(users: np.ndarray, items: np.ndarray, scores: np.ndarray, sp
                                                       slots_i=sl)):
                     out[j] = pl
         return out
-    if L is None or os.environ.get('INVPREF_PLAN_NATIVE', '1') == '0':
+    if L is None:
         return [build_alt_plan(rng(c), None if pv is None else rng(pv)[:2], side, user_num, item_num, factor_num=factor_num,
                                per_slice=per_slice_i if side else per_slice_u, n_classes=n_classes,
                                rows_per_stream_task=rows_per_stream_task, slots=slots_i if side else slots_u)

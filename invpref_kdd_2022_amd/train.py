@@ -132,7 +132,8 @@ class _InvPrefTrainManager:
         self.batch_size = batch_size
         self.batch_num = math.ceil(n_total / batch_size)
         # multi-GPU: the literal row split of SURVEY 8(e) / north_star by default (parallel.RowShard, parameters replicated);
-        # INVPREF_SHARD=users partitions the users instead (parallel.UserShard: only the item-side gradient is all-reduced)
+        # INVPREF_SHARD=users partitions the users instead (parallel.UserShard: only the item-side gradient is all-reduced;
+        # bench.py sets the variable)
         # (testing aid INVPREF_FORCE_SHARDED_PATH=1: the sharded step sequence, either layout, on one rank)
         forced = os.environ.get('INVPREF_FORCE_SHARDED_PATH', '0') == '1'
         self.shard_mode = os.environ.get('INVPREF_SHARD', 'rows') if (self.world_size > 1 or forced) else 'rows'
@@ -185,9 +186,9 @@ class _InvPrefTrainManager:
         self.model.to(self.device)
         # user-sharded: [Pu | Pa | Qi | Qa | Ev | W | b]: the replicated part (items + small tables) and the loss
         # tail form one contiguous range for the all-reduce, the owned user rows two ranges for Adam
-        # row-sharded exchange (INVPREF_EXCHANGE): "scatter" = reduce-scatter of the flat gradient, Adam on this rank's 1/G
-        # slice of the flat buffers, all-gather of the new parameters (same bytes on the wire as the all-reduce, the dense
-        # Adam stream cut G-fold); "allreduce" = SURVEY 8(e) as written: every rank reduces and updates everything; "packed" =
+        # row-sharded exchange (INVPREF_EXCHANGE; bench.py sets it): "scatter" = reduce-scatter of the flat gradient, Adam on
+        # this rank's 1/G slice of the flat buffers, all-gather of the new parameters (same bytes on the wire as the
+        # all-reduce, the dense Adam stream cut G-fold); "allreduce" = SURVEY 8(e) as written: every rank reduces and updates everything; "packed" =
         # the all-reduce over the rows the GLOBAL minibatch touches only (+ the small tables): every other gradient row is
         # zero on every rank, so nothing else needs the wire (_setup_packed)
         self.exchange = os.environ.get('INVPREF_EXCHANGE', 'allreduce') if self.shard_mode == 'rows' else 'allreduce'
@@ -202,7 +203,8 @@ class _InvPrefTrainManager:
         self.workspace = ops.Workspace(self.device)
         self._flags = ops.flags_of(self.implicit, use_recommend_re_weight, use_class_re_weight,
                                    model.reg_only_embed, model.reg_env_embed, dense_reg=(self.rank == 0))
-        # atomic-free planned M-step (plan.py) unless INVPREF_NO_PLAN=1 (then: float-atomic scatter-add)
+        # atomic-free planned M-step (plan.py) unless INVPREF_NO_PLAN=1 (then: float-atomic scatter-add, the path of
+        # train_a_batch on minibatches without a plan -- the test hook that runs it for whole epochs)
         self.use_plan = os.environ.get('INVPREF_NO_PLAN', '0') != '1'
         # (measured, tools/kbench.py, planned fused step vs plan-free gradient + Adam: Yahoo class 19 vs 78 us,
         #  MovieLens class -- E = 8, D = 128, 65 536 interactions -- 110 vs 181 us, MIND class -- E = 16, D = 256,
@@ -213,7 +215,8 @@ class _InvPrefTrainManager:
         self._plans = None
         self._batch_plans, self.planned_batch_steps = {}, 0   # train_a_batch on caller tensors: see _cached_batch_plan
         self._batch_plans_foreign = {}
-        # runs of whole epochs as one HIP graph launch (single GPU, planned path); INVPREF_NO_GRAPH=1 disables
+        # runs of whole epochs as one HIP graph launch (single GPU, planned path); INVPREF_NO_GRAPH=1 disables (test hook:
+        # the eager launches that sharded runs and single calls take, against the replay)
         self.use_graph = os.environ.get('INVPREF_NO_GRAPH', '0') != '1'
         # testing aid: run the multi-GPU step sequence (gradient pass -> all-reduce -> stand-alone Adam) on one rank
         self._force_sharded_path = os.environ.get('INVPREF_FORCE_SHARDED_PATH', '0') == '1'
@@ -260,7 +263,8 @@ class _InvPrefTrainManager:
 
     def _weights_by_env(self) -> bool:
         """may the epochs' launches take an interaction's weight as class_weights[env]? (one GPU, planned M-step, weights
-        consistent with the environments: stat_envs() ran since they last changed, nobody was handed the array since)"""
+        consistent with the environments: stat_envs() ran since they last changed, nobody was handed the array since);
+        INVPREF_WEIGHTS_BY_ENV=0 (test hook): the per-interaction array, which the other states read, regardless"""
         return bool(self._by_env and self.world_size == 1 and self.use_plan and not self._pure
                     and os.environ.get('INVPREF_WEIGHTS_BY_ENV', '1') == '1')
 
@@ -425,6 +429,7 @@ class _InvPrefTrainManager:
     _BATCH_PLAN_CACHE_MAX_FOREIGN = 128
 
     def _cached_batch_plan(self, users, items, scores):
+        # (INVPREF_NO_BATCH_PLAN_CACHE=1, test hook: every caller-supplied minibatch plan-free, as an unseen one runs)
         if not (self.use_plan and self.world_size == 1 and not self._unfused and not self._force_sharded_path
                 and users.is_cuda and users.numel() > 0 and users.is_contiguous() and items.is_contiguous()
                 and os.environ.get('INVPREF_NO_BATCH_PLAN_CACHE', '0') != '1'):
@@ -506,7 +511,7 @@ class _InvPrefTrainManager:
             u, v = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy()
             y = self.scores_tensor.cpu().numpy()
             # every minibatch's plan in one call: parameters resolved per minibatch, the arrays built natively on a thread
-            # pool (csrc/invpref_plan.cpp; plan.py's numpy builder is the reference implementation, INVPREF_PLAN_NATIVE=0)
+            # pool (csrc/invpref_plan.cpp; plan.py's numpy builder, native=False, is the reference implementation)
             offs = np.array([b[0] for b in self._raw_batches] + [self._raw_batches[-1][0] + self._raw_batches[-1][1]], np.int64)
             contiguous = all(offs[k] + self._raw_batches[k][1] == offs[k + 1] for k in range(len(self._raw_batches)))
             kw = dict(factor_num=self.model.factor_num, user_range=self.shard.user_range(self.model.user_num),
@@ -534,9 +539,7 @@ class _InvPrefTrainManager:
     def _alt_setup(self):
         st = self.state
         prev, self._alt = self._alt, None
-        # (eagerly issued epochs run the same launches as captured ones: graph replay == eager launches, bit for bit;
-        #  INVPREF_ALT_EAGER=0 keeps eagerly issued epochs on the two-launch form)
-        self._alt_eager = os.environ.get('INVPREF_ALT_EAGER', '1') == '1'
+        # (INVPREF_ALT=0, test hook: the two-launch form, which every other shape takes, at the alternating form's shapes)
         if not (self.use_plan and self._plans and self.users_tensor.is_cuda and self._fused_seq()
                 and os.environ.get('INVPREF_ALT', '1') == '1' and ops.alt_supported(st.p_views)):
             return
@@ -550,7 +553,7 @@ class _InvPrefTrainManager:
         # hottest item has 60-77 interactions -- three per slice; with one minibatch per epoch (SURVEY 8(d)-4's B = N variant:
         # 250 interactions per item on average) the chains are tens of evaluations long and the two-launch form, whose item
         # side only SUMS contribution rows, is twice as fast (measured: 199 vs 101 us per step).  Decided on the first
-        # minibatch's heaviest row; INVPREF_ALT_MAX_CHAIN overrides the bound.
+        # minibatch's heaviest row; INVPREF_ALT_MAX_CHAIN overrides the bound (test hook: either form at one shape).
         lo0, n0 = self._raw_batches[0][0], self._raw_batches[0][1]
         heavy = max(int(np.bincount(host[0][lo0:lo0 + n0]).max(initial=0)), int(np.bincount(host[1][lo0:lo0 + n0]).max(initial=0)))
         if -(-heavy // 32) > int(os.environ.get('INVPREF_ALT_MAX_CHAIN', '6')):
@@ -581,9 +584,8 @@ class _InvPrefTrainManager:
             rng = lambda k: None if k is None else (self._raw_batches[k][0], self._raw_batches[k][1])   # noqa: E731
             if 'slots' not in A:   # group slots per round of either side's launches, from the first minibatch
                 lo, n0 = self._raw_batches[0][0], self._raw_batches[0][1]
-                ps = (int(os.environ.get('INVPREF_ALT_PER_SLICE_U', '2')), int(os.environ.get('INVPREF_ALT_PER_SLICE_I', '2')))
-                A['slots'] = (planlib.alt_slots_for(u[lo:lo + n0], self.model.user_num, ps[0]),
-                              planlib.alt_slots_for(v[lo:lo + n0], self.model.item_num, ps[1]))
+                A['slots'] = (planlib.alt_slots_for(u[lo:lo + n0], self.model.user_num, planlib.ALT_PER_SLICE),
+                              planlib.alt_slots_for(v[lo:lo + n0], self.model.item_num, planlib.ALT_PER_SLICE))
             hps = planlib.build_alt_plans(u, v, y, [(rng(k), rng(kp), side) for kp, k, side in need], self.model.user_num,
                                           self.model.item_num, factor_num=self.model.factor_num, slots_u=A['slots'][0],
                                           slots_i=A['slots'][1])
@@ -745,7 +747,8 @@ class _InvPrefTrainManager:
     def _issue_epochs(self, stream, sched: bool, n: int):
         self._epoch_losses[:n].zero_()
         st = self.state
-        if getattr(self, '_alt', None) is not None and (sched or self._alt_eager):
+        # (eagerly issued epochs run the same launches as captured ones: graph replay == eager launches, bit for bit)
+        if getattr(self, '_alt', None) is not None:
             self._issue_epochs_alt(sched, n)
             return
         for j in range(n):
@@ -867,7 +870,7 @@ class _InvPrefTrainManager:
 
     def _graph_collectives(self) -> bool:
         """May the step's all-reduce be captured?  Yes on the RCCL backend (or when there is none to capture);
-        INVPREF_NO_COLLECTIVE_GRAPH=1 keeps the sharded loop eager."""
+        INVPREF_NO_COLLECTIVE_GRAPH=1 keeps the sharded loop eager (bench.py names it where a capture fails)."""
         if os.environ.get('INVPREF_NO_COLLECTIVE_GRAPH', '0') == '1':
             return False
         if self.world_size == 1 and not self._collective_ok:
@@ -981,6 +984,7 @@ class _InvPrefTrainManager:
     # kernel's epilogue folds the counts, cluster()'s diff_num and the class weights; nothing N-long is produced (the M-step
     # looks class_weights[env] up itself) and nothing is cloned behind a replay (results land in a ring the kernel advances)
     def _fused_estep_ok(self) -> bool:
+        # (INVPREF_ESTEP_FUSED=0, test hook: the two-launch E-step that sharded runs take, on one GPU)
         return bool(self.world_size == 1 and self.envs.is_cuda and not self._pure and self.use_plan
                     and os.environ.get('INVPREF_ESTEP_FUSED', '1') == '1')
 
@@ -1084,13 +1088,9 @@ class _InvPrefTrainManager:
             if with_eps:
                 dt = torch.from_numpy(np.zeros(0, self._perm_index_dtype())).dtype
                 n_loc = self.users_tensor.shape[0]
-                # INVPREF_EPS_PINNED: 1 (default) = the kernel reads PINNED HOST memory in place (up to seven environments), 0 = a
-                # device buffer filled by a copy in front of the replay, "ahead" = a device buffer filled by a copy on a SIDE stream
-                # while the epochs enqueued before the E-step still run (_fill_eps).  Round 6 measured "ahead": the kernel 61.9 ->
-                # 54.8 us, the replay 69.9 -> 63.8 us -- and the bench's interval 80 us LONGER (15.15 vs 14.63 us per step): the copy's
-                # blit kernel and the cross-stream waits sit among launches that fill the chip exactly
-                mode = os.environ.get('INVPREF_EPS_PINNED', '1')
-                pinned = self.envs_num <= 7 and mode == '1'
+                # (test hook INVPREF_EPS_PINNED=0: the device buffer that eight or more environments take anyway, at any E.
+                #  A copy on a side stream, ahead of the replay, was measured slower: the bench's interval 80 us longer)
+                pinned = self.envs_num <= 7 and os.environ.get('INVPREF_EPS_PINNED', '1') == '1'
                 eps_buf = torch.zeros(n_loc, dtype=dt, pin_memory=True) if pinned \
                     else torch.zeros(n_loc, dtype=dt, device=self.device)
 
@@ -1127,34 +1127,11 @@ class _InvPrefTrainManager:
             if done is not None:
                 done.synchronize()                 # (the previous replay has read the buffer)
             eps_buf.numpy()[:] = self._eps_index()
-        elif eps_buf is not None and os.environ.get('INVPREF_EPS_PINNED', '1') == 'ahead':
-            # the draws are host work that overlaps the epochs the GPU is still running; so does their copy: on a side stream,
-            # behind the previous replay's read of the buffer, in front of this replay (one event each way)
-            idx = self._eps_index()
-            stage = getattr(self, '_eps_stage', None)
-            if stage is None or stage.numel() != len(idx) or stage.dtype != eps_buf.dtype:
-                stage = self._eps_stage = torch.empty(len(idx), dtype=eps_buf.dtype, pin_memory=True)
-                self._eps_stage_done = None
-            if self._eps_stage_done is not None:
-                self._eps_stage_done.synchronize()      # (the previous copy has left the staging buffer)
-            stage.numpy()[:] = idx
-            side = getattr(self, '_eps_stream', None)
-            if side is None:
-                side = self._eps_stream = torch.cuda.Stream(device=self.device)
-            done = getattr(self, '_eps_read_done', None)
-            if done is not None:
-                side.wait_event(done)                   # (the previous replay has read the device buffer)
-            with torch.cuda.stream(side):
-                eps_buf.copy_(stage, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            torch.cuda.current_stream().wait_event(ev)
-            self._eps_stage_done = ev
         elif eps_buf is not None:
             self._eps_index_device(out=eps_buf)
 
     def _eps_replayed(self, eps_buf):
-        if eps_buf is not None and (not eps_buf.is_cuda or os.environ.get('INVPREF_EPS_PINNED', '1') == 'ahead'):
+        if eps_buf is not None and not eps_buf.is_cuda:
             self._eps_read_done = torch.cuda.Event()
             self._eps_read_done.record()
 

@@ -176,7 +176,6 @@ KNOB_CASES = [
     ('INVPREF_ESTEP_BLOCKS', '32', 100003),      # 196 passes
     ('INVPREF_ESTEP_BLOCKS', '33', 100003),      # 190 passes, two workgroups on shard 0
     ('INVPREF_ESTEP_BLOCKS', '257', 100003),     # 25 passes, 6 empty workgroups
-    ('INVPREF_ESTEP_FOLD', 'kernel', 700001),    # the fold as a launch of its own
 ]
 # what each knob child runs: (kind, E, index dtype, memory of the fused call)
 KNOB_RUNS = [('implicit_saturated', 4, 'uint8', 'pinned'), ('explicit_zero', 7, 'int32', 'device'),

@@ -171,25 +171,19 @@ def test_random_plan_parameters_and_shapes(seed):
     rw_rec, rw_cls = (False, False) if pure else (bool(rs.randint(2)), bool(rs.randint(2)))
     roe, ree = (True, False) if pure else (bool(rs.randint(2)), bool(rs.randint(2)))
     coefs = O.pure_mf_coefs(0.3, 0.05) if pure else np.array(COEFS[:6], np.float64)
-    os_env = dict(INVPREF_PLAN_STREAM_ROWS=str(int(rs.choice([1, 16, 64, 200]))))
-    old = {k: os.environ.get(k) for k in os_env}
-    os.environ.update(os_env)
-    try:
-        lo = int(rs.randint(0, U)) if rs.randint(2) else 0
-        user_range = (lo, int(rs.randint(lo, U)) + 1) if rs.randint(2) else None
-        defaults = rs.randint(3) == 0   # a third of the cases: the plan's own slice length / stream split (env_num given)
-        pl = planlib.build_row_plan(u, v, y, U, I, factor_num=D,
-                                    per_slice=None if defaults else int(rs.choice([1, 2, 3, 8, 16])),
-                                    item_per_slice=int(rs.choice([1, 2, 3, 5, 40])),
-                                    rounds_per_task=int(rs.choice([1, 1, 2, 3])),
-                                    item_rounds_per_task=int(rs.choice([1, 1, 2, 3])),
-                                    n_classes=int(rs.choice([1, 3, 8])),
-                                    stream_split=None if defaults else float(rs.choice([0.0, 0.4, 1.0])),
-                                    push=bool(rs.randint(2)), env_num=E if defaults else None,
-                                    user_range=user_range)
-    finally:
-        for k, val in old.items():
-            os.environ.pop(k, None) if val is None else os.environ.__setitem__(k, val)
+    stream_rows = int(rs.choice([1, 16, 64, 200]))
+    lo = int(rs.randint(0, U)) if rs.randint(2) else 0
+    user_range = (lo, int(rs.randint(lo, U)) + 1) if rs.randint(2) else None
+    defaults = rs.randint(3) == 0   # a third of the cases: the plan's own slice length / stream split (env_num given)
+    pl = planlib.build_row_plan(u, v, y, U, I, factor_num=D,
+                                per_slice=None if defaults else int(rs.choice([1, 2, 3, 8, 16])),
+                                item_per_slice=int(rs.choice([1, 2, 3, 5, 40])),
+                                rounds_per_task=int(rs.choice([1, 1, 2, 3])),
+                                item_rounds_per_task=int(rs.choice([1, 1, 2, 3])),
+                                n_classes=int(rs.choice([1, 3, 8])), rows_per_stream_task=stream_rows,
+                                stream_split=None if defaults else float(rs.choice([0.0, 0.4, 1.0])),
+                                push=bool(rs.randint(2)), env_num=E if defaults else None,
+                                user_range=user_range)
     dp = planlib.upload(pl, DEV)
     tab, ws = O.Tables(tabs), ops.Workspace(DEV)
     oflags = O.flags_of(implicit, rw_rec, rw_cls, roe, ree)
@@ -386,10 +380,10 @@ def test_step_scratch_and_plan_lists_stay_inside_their_bounds(U, I, E, D, B):
 @pytest.mark.parametrize('D,E,mm', [(64, 8, '1'), (64, 16, '1'), (128, 8, '1'), (128, 16, '1'), (128, 5, '1'), (256, 16, '1'),
                                     (256, 9, '1'), (256, 5, '1'), (256, 16, '0'), (256, 8, '0')])
 def test_mfma_classifier_form_of_launch_1(D, E, mm, monkeypatch):
-    """csrc/step_wide_mm.hpp (full wide rows: the classifier as MFMA products over the workgroup's interactions) forced on for
-    every instance it is compiled for -- it is the default only for rows on 32 lanes -- and forced off for those: gradient pass
-    against the oracle entry by entry, the fused pass, pull and push forms, run-to-run bitwise; and the two forms against
-    each other (float reordering only)."""
+    """csrc/step_wide_mm.hpp (full rows on 32 lanes: the classifier as MFMA products over the workgroup's interactions, the
+    default there) and the per-interaction classifier (INVPREF_WIDE_MM=0), `mm` first: gradient pass against the oracle entry
+    by entry, the fused pass, run-to-run bitwise; and the two forms against each other (float reordering only).  Rows on 16
+    lanes (D <= 128) have the per-interaction form only: every check of it, pull and push forms."""
     rs = np.random.RandomState(100 * D + E)
     U, I, B = 700, 300, 9000
     data = synth.interactions(77 + D + E, U, I, B, implicit=True, zipf=True)
@@ -404,8 +398,11 @@ def test_mfma_classifier_form_of_launch_1(D, E, mm, monkeypatch):
     for push in ((False, True) if D <= 128 else (False,)):
         dp = planlib.upload(planlib.build_row_plan(u, v, y, U, I, factor_num=D, env_num=E, push=push), DEV)
         res = {}
-        for form in (mm, '0' if mm == '1' else '1'):
-            monkeypatch.setenv('INVPREF_WIDE_MM', form)
+        for form in (mm, '0' if mm == '1' else '1') if D == 256 else ('0',):
+            if form == '0':
+                monkeypatch.setenv('INVPREF_WIDE_MM', '0')
+            else:
+                monkeypatch.delenv('INVPREF_WIDE_MM', raising=False)
             outs = []
             for _ in range(2):
                 G = [torch.full_like(p, 7.0) for p in P]
@@ -423,6 +420,8 @@ def test_mfma_classifier_form_of_launch_1(D, E, mm, monkeypatch):
             ops.mstep_rows_adam(P, P2, M, V, dp, t64(e), t32(y), t32(w), B, coefs, flags, losses, 1, 0.01, ws)
             np.testing.assert_allclose(losses.cpu().numpy(), ol, rtol=3e-5, atol=1e-7)
             res[form] = (outs[0][0], [x.cpu().numpy() for x in P2 + M + V])
+        if D < 256:
+            continue
         for k, a, b in zip(ops.PARAM_NAMES, res['0'][0], res['1'][0]):
             scale = max(np.abs(a).max(), 1e-4)
             assert np.abs(a - b).max() <= 2e-5 * scale, (k, push)

@@ -148,9 +148,9 @@ np.savez(path, **res)
 
 @pytest.mark.parametrize('var,val,N', T.KNOB_CASES, ids=[f'{v}={x}' for v, x, _ in T.KNOB_CASES])
 def test_read_once_knob_in_a_child(var, val, N):
-    """INVPREF_ESTEP_BLOCKS (grids below, at and above the 32 ticket shards; up to 313 passes per workgroup) and
-    INVPREF_ESTEP_FOLD=kernel are read once per process: each in a fresh child of its own, which writes its results; the
-    parent checks them against expected_assign."""
+    """INVPREF_ESTEP_BLOCKS (grids below, at and above the 32 ticket shards; up to 313 passes per workgroup) is read once
+    per process: each value in a fresh child of its own, which writes its results; the parent checks them against
+    expected_assign."""
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, 'r.npz')
         env = dict(os.environ, **{var: val})

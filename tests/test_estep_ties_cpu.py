@@ -162,5 +162,5 @@ def test_gpu_case_list_reaches_its_edges():
     assert {k for (k, *_) in T.GPU_CASES} == {'explicit_zero', 'implicit_saturated'}
     big = max(T.GPU_CASES, key=lambda c: c[3])
     assert big[1:3] == (4, 'uint8') and sorted(c[3] for c in T.GPU_CASES)[-2] < 1100000
-    assert {var for var, _, _ in T.KNOB_CASES} == {'INVPREF_ESTEP_BLOCKS', 'INVPREF_ESTEP_FOLD'}
+    assert {var for var, _, _ in T.KNOB_CASES} == {'INVPREF_ESTEP_BLOCKS'}
     assert {val for var, val, _ in T.KNOB_CASES if var == 'INVPREF_ESTEP_BLOCKS'} == {'1', '3', '31', '32', '33', '257'}

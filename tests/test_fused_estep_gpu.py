@@ -194,10 +194,14 @@ def test_weights_by_environment_equal_gathered_weights(U, I, E, D, B, alt, fl):
 
 
 def test_wide_mm_forms_by_environment(monkeypatch):
-    # both forms of launch 1 for full wide rows (per-interaction classifier / MFMA classifier), forced either way
+    # both forms of launch 1 for full rows on 32 lanes (the MFMA classifier by default, the per-interaction classifier under
+    # INVPREF_WIDE_MM=0); rows on 16 lanes have the per-interaction form only
     for mm in ('0', '1'):
-        monkeypatch.setenv('INVPREF_WIDE_MM', mm)
-        for (E, D) in ((8, 128), (16, 256)):
+        if mm == '0':
+            monkeypatch.setenv('INVPREF_WIDE_MM', '0')
+        else:
+            monkeypatch.delenv('INVPREF_WIDE_MM', raising=False)
+        for (E, D) in ((8, 128), (16, 256)) if mm == '0' else ((16, 256),):
             a, b = _mstep_pair(800, 300, E, D, 7000, False, (True, True, False, True))
             for x, z in zip(a, b):
                 np.testing.assert_array_equal(x, z)

@@ -236,13 +236,13 @@ def test_g11_random_sort_cluster_through_manager():
             assert [cnt[e] for e in range(E)] == np.bincount(z[key].astype(np.int64), minlength=E).tolist()
 
 
-@pytest.mark.parametrize('E,pinned', [(4, '1'), (4, '0'), (4, 'ahead'), (6, '1'), (9, '1')])
+@pytest.mark.parametrize('E,pinned', [(4, '1'), (4, '0'), (6, '1'), (9, '1')])
 def test_random_sort_estep_decides_saturated_ties_through_manager(monkeypatch, E, pinned):
     """The managers' own E-step under the reference's default tie-break (cluster_use_random_sort=True) at the Yahoo table
     shape, batch 8 192 and 700 001 interactions, a third of them saturated positives: every environment's distance of those
     is exactly 0 after training too (c_sigmoid rounds to 1.0), so the permutation index the manager draws decides them.
     Three rounds of one epoch + cluster_and_stat_envs(), each against the oracle on the tables read back from the manager with
-    the same numpy draws -- envs, counts, diff_num and class weights bit for bit.  E = 4 under every INVPREF_EPS_PINNED mode
+    the same numpy draws -- envs, counts, diff_num and class weights bit for bit.  E = 4 under both INVPREF_EPS_PINNED modes
     (read per call), E = 6 (four-byte indices read from pinned memory), E = 9 (device indices, the unrank form)."""
     import math
     from estep_ties import PA, PU, QA, QI, EV, perm_rows

@@ -2,7 +2,7 @@
 # tools/ab.sh SPEC... -- the loop benchmark (tools/step_probe.py) once per SPEC (GPU box).
 # SPEC = VARIANT[,ENV=VALUE...]: an A/B build of the library (invpref_kdd_2022_amd/variants/VARIANT.so, made by
 # build.build_variant; "default" = the shipped one) and
-# environment variables for that run (plan parameters INVPREF_PLAN_*, PROBE_SHAPE, PROBE_STAMPS ...).
+# environment variables for that run (PROBE_SHAPE, PROBE_STAMPS ...: tools/step_probe.py).
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for spec in "$@"; do

@@ -3,8 +3,7 @@
 training loop -- ping-pong parameter buffers, a different plan every step.
   * per-step time of NB steps captured in one HIP graph (what bench.py times, without the manager around it);
   * with PROBE_STAMPS=1: phase time stamps of the LAST step of a run, per task kind, for both launches.
-Shape: PROBE_SHAPE="U,I,E,D,B" (default the Yahoo shape on synth.yahoo_like()); plan parameters through the
-INVPREF_PLAN_* environment variables (plan.py)."""
+Shape: PROBE_SHAPE="U,I,E,D,B" (default the Yahoo shape on synth.yahoo_like()); the plans take plan.py's defaults."""
 import os
 import sys
 
