@@ -567,6 +567,38 @@ int invpref_naive_bayes_propensity_hip(const float *train_scores, int64_t n, con
  * be weights (in place).  No workspace. */
 int invpref_snips_scale_hip(const float *weights, int64_t n, int64_t batch_size, float *scaled, void *stream);
 
+/* ---- ExpoMF exposure model (baseline_models.py:252-256, baseline_train.py:43-99; csrc/invpref_exposure.hip).  The
+ * posterior of user u and item i: s = sigmoid(Pu[u] . Qi[i]) (the canonical dot product), p_ex = c * exp((-lam_y * s^2) / 2)
+ * with c = fp32(sqrt(lam_y / 2 * pi)), prob = (p_ex + eps) / ((p_ex + eps) + (1 - mu_i) / mu_i), in fp32 (lam_y, eps and c
+ * rounded to fp32 as torch's scalar ops round them).  Neither entry point allocates, synchronises or keeps a U x I matrix:
+ * both can be captured into a graph.  Ids outside [0, user_num) / [0, item_num) are never used as addresses: their
+ * entries are NaN. */
+
+/* workspace of invpref_exposure_hip's prior form: float64 [R, item_num] column-sum partials, R a function of
+ * (n_users, item_num) alone (never of the device); non-decreasing in n_users.  0 for bad sizes. */
+size_t invpref_exposure_workspace_bytes(int64_t n_users, int64_t item_num);
+
+/* the exposure pass over users[n_users] (NULL: 0 .. n_users - 1) x every item, on the matrix cores.  Two optional outputs
+ * (at least one):
+ *   mu_out[item_num]            the prior update of upd_mu (baseline_train.py:63-79): fp32((a + S_i - 1) /
+ *                               (a + b + user_num - 2)), S_i = sum over the listed users of prob(u, i), accumulated in
+ *                               float64 in a fixed order (bitwise reproducible); may alias mu; needs the workspace
+ *   prob_out[n_users, item_num] the posterior matrix (store mode; workspace not needed)
+ * n_users = 0 is allowed (mu_out = (a - 1) / (a + b + user_num - 2)).  factor_num <= INVPREF_MAX_FACTORS, any width. */
+int invpref_exposure_hip(const float *user_table, int64_t user_num, const float *item_table, int64_t item_num,
+                         int64_t factor_num, const int64_t *users, int64_t n_users, double lam_y, double eps,
+                         const float *mu, double a, double b, float *mu_out, float *prob_out, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
+/* the ExpoMF step weights (baseline_train.py:57-61, :88-99) of n pairs (users[j], items[j]): 1.0 where positive[j] != 0
+ * (positive may be NULL: no positives), otherwise prob ** weight_exp -- the pow is skipped at weight_exp == 1.0 (then the
+ * weight equals invpref_exposure_hip's store-mode entry bit for bit), other exponents use the device powf (within one fp32
+ * ulp of numpy's float32 power).  weights: fp32[n].  No workspace. */
+int invpref_exposure_weights_hip(const float *user_table, int64_t user_num, const float *item_table, int64_t item_num,
+                                 int64_t factor_num, const int64_t *users, const int64_t *items, const uint8_t *positive,
+                                 int64_t n, double lam_y, double eps, const float *mu, double weight_exp, float *weights,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

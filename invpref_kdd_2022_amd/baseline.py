@@ -1,4 +1,4 @@
-"""PureMF baselines on the same fused HIP step, plain and propensity-weighted (IPS-MF, SNIPS-MF).
+"""PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF) and ExpoMF.
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -434,3 +434,171 @@ class IPSBasicExplicitTrainManager(_PropensityMixin, BasicExplicitTrainManager):
 class SNIPSExplicitMFTrainManager(IPSBasicExplicitTrainManager):
     """reference baseline_train.py:924-976"""
     _snips = True
+
+
+# ------------------------------------------------------------------------------------------------ ExpoMF
+class ExposureMatrixFactorization(PureMatrixFactorization):
+    """baseline_models.py:237-256: PureMF with per-interaction BCE losses and the exposure posterior.  Same parameters and
+    initialisation; ImplicitTestManager ranks it through the fused route like any PureMatrixFactorization."""
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int):
+        super().__init__(user_num, item_num, factor_num)
+        self.loss_func = nn.BCELoss(reduction='none')
+
+    def forward(self, users_id, items_id, ground_truth):  # baseline_models.py:244-250: one loss per interaction
+        return self.loss_func(self._scores(users_id, items_id), ground_truth)
+
+    def calculate_exposure_probability(self, user_id, lam_y: float, mu, eps: float) -> torch.Tensor:
+        """baseline_models.py:252-256: the detached fp32 posterior [n, I] of the given users on the device (the store mode of
+        csrc/invpref_exposure.hip's pass)"""
+        P, Q = self.user_emb.weight.detach(), self.item_emb.weight.detach()
+        mu = torch.as_tensor(mu).to(device=P.device, dtype=torch.float32).reshape(-1).contiguous()
+        return ops.exposure_probability(P, Q, torch.as_tensor(user_id).to(P.device), mu, lam_y, eps)
+
+
+def _zero_pow(e: float) -> float:
+    """an entry of the reference's float64 np.zeros matrix ** e (what every weight is before the first recompute)"""
+    with np.errstate(divide='ignore'):
+        return float(np.float64(0.0) ** e)
+
+
+class ExpoMFTrainManager(BasicImplicitTrainManager):
+    """reference baseline_train.py:16-154 on the fused PureMF step with INVPREF_REWEIGHT_REC: the loss is
+    mean(BCE * w) + the PureMF regularisers, w = prob ** expo_weight_exp at the minibatch's pairs (1.0 at pairs with a
+    positive training row).
+
+    The reference keeps the posterior as a dense [U, I] host array, rebuilt every upd_expo_interval epochs, gathered and
+    copied to the device at every step.  Here nothing U x I exists during training:
+      - every recompute copies the two tables and mu into a device snapshot and refreshes ONE fp32[N] weight buffer in place
+        (the epochs' launches read slices of it, so the captured epoch graphs stay valid);
+      - the prior update after every epoch is one exposure pass whose epilogue reduces to per-item float64 column sums,
+        updating the device buffer mu in place.
+    ``exposure_probability`` materialises the reference's matrix from the snapshot on request only."""
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
+                 lam_y: float = 1.0, init_mu: float = 1e-2, a: float = 1.0, b: float = 1.0, expo_weight_exp: float = 1.0,
+                 eps: float = 1e-8, upd_expo_interval: int = 10, *, rank=None, world_size=None, process_group=None):
+        if int(upd_expo_interval) < 1:
+            raise ValueError(f'upd_expo_interval must be at least 1, got {upd_expo_interval}')
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        if self.world_size > 1:
+            raise NotImplementedError('ExpoMF runs on one GPU (a sharded exposure pass is not implemented)')
+        self.model = model
+        self.lam_y, self.a, self.b = float(lam_y), float(a), float(b)
+        self.expo_weight_exp, self.eps = float(expo_weight_exp), float(eps)
+        self.upd_expo_interval = int(upd_expo_interval)
+        dev, U, I = self.device, model.user_num, model.item_num
+        self._mu = torch.full((I,), float(init_mu), dtype=torch.float32, device=dev)   # torch.Tensor(init_mu * ones): fp32
+        self.user_id_tensor = torch.arange(U, dtype=torch.int64, device=dev)
+        # a row is positive when ANY training row of its (u, i) has a nonzero label (baseline_train.py:57-61)
+        keys = self.users_tensor * I + self.items_tensor
+        self._pos_keys = torch.unique(keys[self.scores_tensor != 0])           # sorted
+        self._positive = torch.isin(keys, self._pos_keys)
+        # the reference's np.zeros matrix before the first recompute: every weight is 0.0 ** e
+        self._w = torch.full((self.n_total,), _zero_pow(self.expo_weight_exp), dtype=torch.float32, device=dev)
+        P, Q = self.state.p_views[0], self.state.p_views[1]
+        self._snap = (torch.empty_like(P), torch.empty_like(Q), torch.empty_like(self._mu))
+        self._snapped = False
+        self._expo_ws = ops.Workspace(dev)
+        self._expo_ws.get(max(ops.exposure_workspace_bytes(U, I), 1))           # sized once: graph-capturable passes
+        self._flags |= _capi.REWEIGHT_REC
+
+    @property
+    def mu(self) -> torch.Tensor:
+        """the item priors: a device fp32 [item_num] buffer, updated in place"""
+        return self._mu
+
+    @mu.setter
+    def mu(self, value):
+        self._mu.copy_(torch.as_tensor(value).reshape(-1))
+
+    def _pure_weights(self, lo: int, hi: int):
+        return self._w[lo:hi]
+
+    def calculate_exposure_probability(self):
+        """baseline_train.py:43-61: snapshot the tables and mu, then refresh the weights of every training row (positives 1.0)
+        in place.  Enqueued on the current stream; nothing is read back."""
+        self.model.eval()
+        P, Q = self.state.p_views[0], self.state.p_views[1]
+        for dst, src in zip(self._snap, (P, Q, self._mu)):
+            dst.copy_(src)
+        self._snapped = True
+        sP, sQ, smu = self._snap
+        ops.exposure_weights(sP, sQ, self.users_tensor, self.items_tensor, self._positive, smu, self.lam_y, self.eps,
+                             self.expo_weight_exp, out=self._w)
+
+    def upd_mu(self):
+        """baseline_train.py:63-79: mu <- (a + sum_u prob(u, i) - 1) / (a + b + U - 2) over every user, from the current tables
+        and mu (no positive override), in place.  One exposure pass + a fold; nothing [U, I] is stored."""
+        self.model.eval()
+        ops.exposure_prior_(self.state.p_views[0], self.state.p_views[1], None, self._mu, self.lam_y, self.eps, self.a, self.b,
+                            self._expo_ws)
+
+    @property
+    def exposure_probability(self) -> np.ndarray:
+        """The reference's [U, I] matrix (baseline_train.py:40, :55-61), materialised from the last recompute's snapshot in
+        chunks of users, positives set to 1.0: float32, or float64 zeros before the first recompute.  Costs U * I * 4 bytes of
+        host memory and as much device traffic -- for inspection; training never builds it."""
+        U, I = self.model.user_num, self.model.item_num
+        if not self._snapped:
+            return np.zeros([U, I])
+        sP, sQ, smu = self._snap
+        out = np.empty((U, I), dtype=np.float32)
+        step = max(1, min(U, (64 << 20) // (4 * I)))
+        for lo in range(0, U, step):
+            hi = min(U, lo + step)
+            out[lo:hi] = ops.exposure_probability(sP, sQ, self.user_id_tensor[lo:hi], smu, self.lam_y, self.eps).cpu().numpy()
+        k = self._pos_keys.cpu().numpy()
+        out[k // I, k % I] = 1.0
+        return out
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor) -> dict:
+        """baseline_train.py:81-116 on caller tensors: the weights of ANY pair from the last recompute's snapshot (1.0 at pairs
+        with a positive training row), or 0.0 ** e before the first recompute."""
+        u = batch_users_tensor.detach().to(self.device).long().reshape(-1).contiguous()
+        v = batch_items_tensor.detach().to(self.device).long().reshape(-1).contiguous()
+        if not self._snapped:
+            w = torch.full((u.numel(),), _zero_pow(self.expo_weight_exp), dtype=torch.float32, device=self.device)
+        else:
+            pos = torch.isin(u * self.model.item_num + v, self._pos_keys)
+            sP, sQ, smu = self._snap
+            w = ops.exposure_weights(sP, sQ, u, v, pos, smu, self.lam_y, self.eps, self.expo_weight_exp)
+        return self._batch_step(u, v, batch_scores_tensor, w)
+
+    def train(self, silent: bool = False, auto: bool = False):
+        """baseline_train.py:118-154: ((loss dicts, epochs), (test results, epochs)).  One-epoch runs (graph replays; the
+        alternating form flushes at the end of each, so the tables are consistent between runs): the weight refresh is
+        enqueued before the due epochs, the prior update after every run.  silent / auto: no per-epoch host sync."""
+        test_result_list, test_epoch_list, loss_result_list, train_epoch_index_list = [], [], [], []
+        defer = bool(silent or auto)
+        evaluate_async = getattr(self.evaluator, 'evaluate_async', None) if defer else None
+
+        def evaluate():
+            res = evaluate_async() if evaluate_async is not None else self.evaluator.evaluate()
+            test_result_list.append(res)
+            test_epoch_list.append(self.epoch_cnt)
+            if not silent and not auto:
+                print('test at epoch:', self.epoch_cnt)
+                print(transfer_loss_dict_to_line_str(res))
+
+        evaluate()
+        while self.epoch_cnt < self.epochs:
+            if self.epoch_cnt % self.upd_expo_interval == 0:
+                self.calculate_exposure_probability()
+            run = self.train_epochs(1, sync=not defer)
+            self.upd_mu()
+            train_epoch_index_list.append(self.epoch_cnt)
+            loss_result_list.append(run[0])
+            if not defer:
+                print('train epoch:', self.epoch_cnt)
+                print(transfer_loss_dict_to_line_str(run[0]))
+            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
+                evaluate()
+        self._check_alt_error()
+        if defer and loss_result_list:
+            loss_result_list = self.loss_dicts(torch.stack(loss_result_list))
+        if evaluate_async is not None:
+            test_result_list = [p.result() for p in test_result_list]
+        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)

@@ -483,3 +483,49 @@ def snips_scale(weights: torch.Tensor, batch_size: int) -> torch.Tensor:
     S_b the minibatch's float64 sum of w: mean(loss * w') is SNIPS's sum(loss * w) / sum(w) (baseline_train.py:457-491)."""
     _gpu(weights)
     return _o().snips_scale(weights.contiguous(), int(batch_size))
+
+
+# ---- ExpoMF exposure model (baseline_models.py:252-256, baseline_train.py:43-99; csrc/invpref_exposure.hip)
+def exposure_workspace_bytes(n_users: int, item_num: int) -> int:
+    """float64 [R, item_num] column-sum partials of the prior form; non-decreasing in n_users"""
+    return int(_capi.lib().invpref_exposure_workspace_bytes(int(n_users), int(item_num)))
+
+
+def _expo_users(users, user_table):
+    if users is None:
+        return None, user_table.shape[0]
+    users = users.reshape(-1).long().contiguous()
+    return users, users.numel()
+
+
+def exposure_probability(user_table: torch.Tensor, item_table: torch.Tensor, users: Optional[torch.Tensor], mu: torch.Tensor,
+                         lam_y: float, eps: float) -> torch.Tensor:
+    """calculate_exposure_probability (baseline_models.py:252-256): the fp32 posterior [n, I] of the listed users (None: every
+    user, in order) x every item -- the store mode of the exposure pass."""
+    _gpu(user_table, item_table, users, mu)
+    users, n = _expo_users(users, user_table)
+    return _o().exposure_probability(user_table, item_table, users, n, mu, float(lam_y), float(eps))
+
+
+def exposure_prior_(user_table: torch.Tensor, item_table: torch.Tensor, users: Optional[torch.Tensor], mu: torch.Tensor,
+                    lam_y: float, eps: float, a: float, b: float, workspace: Optional[Workspace] = None) -> torch.Tensor:
+    """upd_mu (baseline_train.py:63-79) in place: mu <- fp32((a + S_i - 1) / (a + b + user_num - 2)), S_i the float64 sum of the
+    posterior over the listed users (None: every user) under the current mu.  No [n, I] matrix is stored; bitwise
+    reproducible; no host sync (graph-capturable once the workspace is sized)."""
+    _gpu(user_table, item_table, users, mu)
+    users, n = _expo_users(users, user_table)
+    ws = (workspace or Workspace(mu.device)).get(max(exposure_workspace_bytes(n, item_table.shape[0]), 1))
+    _o().exposure_prior_(user_table, item_table, users, n, mu, float(lam_y), float(eps), float(a), float(b), ws)
+    return mu
+
+
+def exposure_weights(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, items: torch.Tensor,
+                     positive: Optional[torch.Tensor], mu: torch.Tensor, lam_y: float, eps: float, weight_exp: float,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ExpoMF's step weights (baseline_train.py:88-99) at pairs (users[j], items[j]): 1.0 where positive[j], otherwise
+    prob ** weight_exp (fp32; at weight_exp == 1.0 the store-mode entry bit for bit).  out: refreshed in place if given."""
+    _gpu(user_table, item_table, users, items, positive, mu, out)
+    if out is None:
+        out = torch.empty(users.numel(), dtype=torch.float32, device=users.device)
+    _o().exposure_weights_(user_table, item_table, users, items, positive, mu, float(lam_y), float(eps), float(weight_exp), out)
+    return out

@@ -35,6 +35,9 @@ What replaces what in the reference:
 ``count_propensity``           ``basic_{item,user,pair}_propensity_func`` (baseline_train.py:493-546): fp32 ``[n]``
 ``naive_bayes_propensity``     ``naive_bayes_propensity`` (baseline_train.py:549-581): fp32 ``[n]`` + float64 per label
 ``snips_scale``                the SNIPS normaliser (baseline_train.py:457-491) as a pre-scaling of the static minibatches
+``exposure_probability``       ExpoMF's posterior matrix (baseline_models.py:252-256): fp32 ``[n, I]`` (store mode)
+``exposure_prior_``            ExpoMF's prior update (baseline_train.py:63-79) in place on ``mu``; nothing ``[n, I]`` is stored
+``exposure_weights_``          ExpoMF's step weights ``prob ** e`` (1.0 at positives) at given pairs (baseline_train.py:88-99)
 =============================  =====================================================================================
 
 Tensors are borrowed for the call and never retained.  ``workspace`` arguments are caller-owned scratch (uint8),
@@ -812,3 +815,87 @@ def _snips_scale(weights, batch_size):
 @_fake('snips_scale')
 def _snips_scale_fake(weights, batch_size):
     return torch.empty_like(weights)
+
+
+# ------------------------------------------------------------------------------------------------ ExpoMF exposure model
+def _expo_tables(user_table, item_table):
+    _f32(user_table, 'user_table')
+    _f32(item_table, 'item_table')
+    if user_table.dim() != 2 or item_table.dim() != 2 or user_table.shape[1] != item_table.shape[1]:
+        raise InvPrefError('exposure: user_table [U, D] and item_table [I, D] must share D')
+    return user_table.shape[0], item_table.shape[0], user_table.shape[1]
+
+
+def _expo_pass(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, mu_out, prob_out, ws):
+    U, I, D = _expo_tables(user_table, item_table)
+    _f32(mu, 'mu')
+    if mu.numel() != I:
+        raise InvPrefError(f'exposure: mu has {mu.numel()} entries for {I} items')
+    if users is not None:
+        _ids(users, 'users')
+        n_users = users.numel()
+    check(lib().invpref_exposure_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(users), int(n_users), float(lam_y),
+                                     float(eps), ptr(mu), float(a), float(b), ptr(mu_out), ptr(prob_out), ptr(ws),
+                                     0 if ws is None else ws.numel(), stream_ptr()), 'invpref_exposure_hip')
+
+
+_define('exposure_probability(Tensor user_table, Tensor item_table, Tensor? users, int n_users, Tensor mu, float lam_y, '
+        'float eps) -> Tensor')
+
+
+@_impl('exposure_probability')
+def _exposure_probability(user_table, item_table, users, n_users, mu, lam_y, eps):
+    n = users.numel() if users is not None else int(n_users)
+    out = torch.empty(n, item_table.shape[0], dtype=torch.float32, device=user_table.device)
+    if n > 0:
+        _expo_pass(user_table, item_table, users, n, mu, lam_y, eps, 0., 0., None, out, None)
+    return out
+
+
+@_fake('exposure_probability')
+def _exposure_probability_fake(user_table, item_table, users, n_users, mu, lam_y, eps):
+    n = users.numel() if users is not None else int(n_users)
+    return torch.empty(n, item_table.shape[0], dtype=torch.float32, device=user_table.device)
+
+
+_define('exposure_prior_(Tensor user_table, Tensor item_table, Tensor? users, int n_users, Tensor(a!) mu, float lam_y, '
+        'float eps, float a, float b, Tensor(b!) workspace) -> ()')
+
+
+@_impl('exposure_prior_')
+def _exposure_prior(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, workspace):
+    _capi._req(workspace, torch.uint8, 'workspace')
+    _expo_pass(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, mu, None, workspace)
+
+
+@_fake('exposure_prior_')
+def _exposure_prior_fake(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, workspace):
+    return None
+
+
+_define('exposure_weights_(Tensor user_table, Tensor item_table, Tensor users, Tensor items, Tensor? positive, Tensor mu, '
+        'float lam_y, float eps, float weight_exp, Tensor(a!) out) -> ()')
+
+
+@_impl('exposure_weights_')
+def _exposure_weights(user_table, item_table, users, items, positive, mu, lam_y, eps, weight_exp, out):
+    U, I, D = _expo_tables(user_table, item_table)
+    _ids(users, 'users')
+    _ids(items, 'items')
+    _f32(mu, 'mu')
+    _f32(out, 'out')
+    n = users.numel()
+    if items.numel() != n or out.numel() != n or (positive is not None and positive.numel() != n):
+        raise InvPrefError('exposure_weights: users, items, positive and out differ in length')
+    if mu.numel() != I:
+        raise InvPrefError(f'exposure_weights: mu has {mu.numel()} entries for {I} items')
+    if positive is not None:
+        _capi._req(positive, torch.bool, 'positive')
+    check(lib().invpref_exposure_weights_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(items), ptr(positive),
+                                             n, float(lam_y), float(eps), ptr(mu), float(weight_exp), ptr(out),
+                                             stream_ptr()), 'invpref_exposure_weights_hip')
+
+
+@_fake('exposure_weights_')
+def _exposure_weights_fake(user_table, item_table, users, items, positive, mu, lam_y, eps, weight_exp, out):
+    return None
