@@ -599,6 +599,26 @@ int invpref_exposure_weights_hip(const float *user_table, int64_t user_num, cons
                                  int64_t n, double lam_y, double eps, const float *mu, double weight_exp, float *weights,
                                  void *stream);
 
+/* ---- WMF imputation term (baseline_train.py:157-228; csrc/invpref_impute.hip).  Over the block sel_users x sel_items
+ * (int32 ids, distinct within a side, any order, 1 .. 2^24 each):
+ *   term = mean of -max(log(1 - sigmoid(Pu[a] . Qi[b])), -100)            (BCE against label 0, aten's clamp)
+ *   grad_user[a] += c * sum_b g_ab Qi[b],  grad_item[b] += c * sum_a g_ab Pu[a],   c = imputation_coe / (n_u * n_i),
+ * g_ab the derivative of that BCE with respect to the raw score, from the PureMF step's own per-interaction definitions (a
+ * pair whose fp32 sigmoid is exactly 1 adds 100 to the sum and nothing to a gradient).  Both products and the scores run on
+ * the matrix cores; no pair list, no gathered matrix and no score matrix exists in memory.  The gradients are ADDED into the
+ * rows of the selection only ([user_num, D] / [item_num, D] tables); every row has one writer and every sum a fixed order:
+ * bitwise reproducible, no float atomics.  loss_out (may be NULL): *loss_out += imputation_coe * term; term_out (may be NULL):
+ * *term_out = term.  An id outside its table is never used as an address: its pairs are skipped and the term is NaN.
+ * The selections are read on the device when the kernel runs, so a captured launch sees whatever the two arrays hold at
+ * replay time.  Two launches, no allocation, no synchronisation.
+ * workspace: float64 loss partials, ceil(n_sel_users / 16) of them -- a function of the sizes alone, non-decreasing; 0 for
+ * bad sizes. */
+size_t invpref_impute_workspace_bytes(int64_t n_sel_users, int64_t n_sel_items, int64_t factor_num);
+int invpref_impute_grad_hip(const float *user_table, int64_t user_num, const float *item_table, int64_t item_num,
+                            int64_t factor_num, const int32_t *sel_users, int64_t n_sel_users, const int32_t *sel_items,
+                            int64_t n_sel_items, double imputation_coe, float *grad_user, float *grad_item, float *loss_out,
+                            float *term_out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -602,3 +602,151 @@ class ExpoMFTrainManager(BasicImplicitTrainManager):
         if evaluate_async is not None:
             test_result_list = [p.result() for p in test_result_list]
         return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
+
+
+# ------------------------------------------------------------------------------------------------ WMF
+def wmf_distinct(users: np.ndarray, items: np.ndarray, batch_size: int) -> list:
+    """per static minibatch of utils.mini_batch (unshuffled slices) the ascending distinct users and items, as torch.unique
+    gives them (baseline_train.py:192-193): [(uu, ui), ...]"""
+    users, items = np.asarray(users).reshape(-1), np.asarray(items).reshape(-1)
+    return [(np.unique(users[lo:lo + batch_size]), np.unique(items[lo:lo + batch_size]))
+            for lo in range(0, len(users), batch_size)]
+
+
+def wmf_draw(uu: np.ndarray, ui: np.ndarray, user_batch_size: int, item_batch_size: int):
+    """one step's selection (baseline_train.py:195-202): two np.random.shuffle calls on numpy's GLOBAL generator, users first,
+    each permutation cut to its batch size and mapped through the distinct ids.  Host only."""
+    ru = np.arange(len(uu))
+    np.random.shuffle(ru)
+    ri = np.arange(len(ui))
+    np.random.shuffle(ri)
+    return uu[ru[:user_batch_size]], ui[ri[:item_batch_size]]
+
+
+def wmf_draw_epochs(distinct: list, user_batch_size: int, item_batch_size: int, epochs: int) -> list:
+    """the selections of `epochs` whole epochs in the reference's order (step by step, users then items): [(Su, Si), ...]"""
+    return [wmf_draw(uu, ui, user_batch_size, item_batch_size) for _ in range(epochs) for uu, ui in distinct]
+
+
+class WMFTrainManager(BasicImplicitTrainManager):
+    """reference baseline_train.py:157-228: the PureMF step plus imputation_coe * BCE(sigmoid(Pu[a] . Qi[b]), 0) averaged over
+    a block Su x Si drawn per step from the minibatch's distinct users and items (target 0, as the reference's `zero_tensor`
+    is named -- the reference allocates it uninitialised).
+
+    The step is the engine's unfused sequence with one call between the gradient pass and Adam: planned PureMF gradient
+    pass -> torch.ops.invpref.impute_grad_ (csrc/invpref_impute.hip: adds into the same gradient buffer and into the step's
+    `loss`) -> dense / ranged Adam.  Nothing of the block is materialised.
+
+    The draws: the minibatches are static, so their distinct ids are listed once; before a run of epochs is enqueued every
+    step's two permutations are drawn on the host with np.random.shuffle in the reference's order and the run's selections
+    go to the device in one stream-ordered copy into ONE int32 buffer, row = the step's position in the run.  The launches
+    read their row when they run, so a captured run of epochs is replayed with new selections without re-capture.
+
+    selections= (keyword-only) replaces numpy's global generator: a callable (uu, ui, user_batch_size, item_batch_size) ->
+    (Su, Si) called once per step in order, or an iterable of (Su, Si) pairs consumed in that order (recorded draws).  A
+    step's Su / Si must hold min(distinct, batch size) ids of the minibatch."""
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
+                 imputation_coe: float = 1.0, user_batch_size: int = 1000, item_batch_size: int = 1000, *, selections=None,
+                 rank=None, world_size=None, process_group=None):
+        if int(user_batch_size) < 1 or int(item_batch_size) < 1:
+            raise ValueError('user_batch_size and item_batch_size must be at least 1')
+        single = 'WMF runs in a single process (a sharded form would all-reduce the summed gradient before the imputation ' \
+                 'term is added; not implemented)'
+        if world_size is not None and int(world_size) > 1:
+            raise NotImplementedError(single)
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        if self.world_size > 1:
+            raise NotImplementedError(single)
+        self.imputation_coe = float(imputation_coe)
+        self.user_batch_size, self.item_batch_size = int(user_batch_size), int(item_batch_size)
+        self._unfused = True        # always gradient pass -> _after_gradient_pass -> Adam (never the fused / alternating step)
+        self._distinct = wmf_distinct(self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy(), batch_size)
+        self._counts = [(min(len(uu), self.user_batch_size), min(len(ui), self.item_batch_size)) for uu, ui in self._distinct]
+        self._cap_u = max(c[0] for c in self._counts)
+        self._cap_i = max(c[1] for c in self._counts)
+        self._selections = selections
+        self._sel_iter = iter(selections) if selections is not None and not callable(selections) else None
+        self._queue = []            # drawn, not yet consumed: whole epochs of (Su, Si) in step order
+        self._sel = None            # device int32 [steps of the longest run, cap_u + cap_i]
+        self._imp_ws = ops.Workspace(self.device)
+        self._imp_ws.get(max(ops.impute_workspace_bytes(max(self._cap_u, self.user_batch_size), self._cap_i,
+                                                        model.factor_num), 8))   # sized once: capturable launches
+
+    def _draw(self, uu, ui):
+        if self._selections is None:
+            su, si = wmf_draw(uu, ui, self.user_batch_size, self.item_batch_size)
+        elif self._sel_iter is not None:
+            su, si = next(self._sel_iter)
+        else:
+            su, si = self._selections(uu, ui, self.user_batch_size, self.item_batch_size)
+        su, si = np.asarray(su).reshape(-1), np.asarray(si).reshape(-1)
+        want = (min(len(uu), self.user_batch_size), min(len(ui), self.item_batch_size))
+        if (len(su), len(si)) != want:
+            raise ValueError(f'a selection of {len(su)} users x {len(si)} items where the step takes {want[0]} x {want[1]}')
+        return su.astype(np.int32), si.astype(np.int32)
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        rows = self._graph_epochs * self.batch_num
+        if self._sel is None or self._sel.shape[0] != rows:
+            self._sel = torch.zeros(rows, self._cap_u + self._cap_i, dtype=torch.int32, device=self.device)
+
+    def _stage_selections(self, n: int):
+        """the selections of the next n epochs: drawn (those not yet drawn), laid out one row per step, one copy"""
+        while len(self._queue) < n * self.batch_num:
+            self._queue.extend(self._draw(uu, ui) for uu, ui in self._distinct)
+        host = np.zeros((n * self.batch_num, self._cap_u + self._cap_i), np.int32)
+        for s in range(n * self.batch_num):
+            su, si = self._queue[s]
+            host[s, :len(su)] = su
+            host[s, self._cap_u:self._cap_u + len(si)] = si
+        src = torch.from_numpy(host)
+        if self._sel.is_cuda:
+            src = src.pin_memory()
+        self._sel[:len(host)].copy_(src, non_blocking=True)
+
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        n = min(want, self._graph_epochs) if (self.graphs_enabled() and self._graph_warm) else 1
+        self._stage_selections(n)
+        before = self.epoch_cnt
+        out = super()._enqueue_epochs(want)
+        del self._queue[:(self.epoch_cnt - before) * self.batch_num]   # (a failed capture runs one eager epoch of the n)
+        return out
+
+    def prepare_graphs(self, run_lengths) -> None:
+        if self._sel is None:
+            raise RuntimeError('prepare_graphs(): run one epoch first (train_epochs(1))')
+        super().prepare_graphs(run_lengths)
+
+    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
+        st = self.state
+        row = self._sel[self._loss_slot * self.batch_num + k]
+        nu, ni = self._counts[k]
+        ops.impute_grad_(st.p_views[0], st.p_views[1], row[:nu], row[self._cap_u:self._cap_u + ni], self.imputation_coe,
+                         st.g_views[0], st.g_views[1], losses6[5:6], None, self._imp_ws)
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """baseline_train.py:179-228 on caller tensors: the distinct ids of THIS batch, two draws, one step."""
+        u = batch_users_tensor.detach().cpu().numpy().reshape(-1)
+        v = batch_items_tensor.detach().cpu().numpy().reshape(-1)
+        y = batch_scores_tensor.detach().float().contiguous()
+        su, si = self._draw(np.unique(u), np.unique(v))
+        dp = planlib.upload(planlib.build_row_plan(u, v, y.cpu().numpy(), self.model.user_num, self.model.item_num,
+                                                   factor_num=self.model.factor_num, env_num=0), self.device)
+        st = self.state
+        st.losses6.zero_()
+        st.step += 1
+        self._sched_synced = False
+        ops.mstep_rows_grad(st.p_views, st.g_views, dp, None, y.to(self.device), None, len(u), self._coefs(0.),
+                            self._flags & ~_capi.REWEIGHT_REC, st.losses6, self.workspace)
+        ops.impute_grad_(st.p_views[0], st.p_views[1], torch.from_numpy(su).to(self.device),
+                         torch.from_numpy(si).to(self.device), self.imputation_coe, st.g_views[0], st.g_views[1],
+                         st.losses6[5:6], None, self._imp_ws)
+        self._grad_stale = True     # (the planned pass overwrote every row: nothing to zero, see _step())
+        for o, ln in getattr(self, '_adam_ranges', [(0, st.n)]):
+            ops.adam_(st.param[o:o + ln], st.grad[o:o + ln], st.exp_avg[o:o + ln], st.exp_avg_sq[o:o + ln], st.step, self.lr,
+                      zero_grad=False)
+        return self.loss_dicts(st.losses6[None])[0]

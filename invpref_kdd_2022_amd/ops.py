@@ -529,3 +529,25 @@ def exposure_weights(user_table: torch.Tensor, item_table: torch.Tensor, users: 
         out = torch.empty(users.numel(), dtype=torch.float32, device=users.device)
     _o().exposure_weights_(user_table, item_table, users, items, positive, mu, float(lam_y), float(eps), float(weight_exp), out)
     return out
+
+
+# ---- WMF imputation term (baseline_train.py:157-228; csrc/invpref_impute.hip)
+def impute_workspace_bytes(n_sel_users: int, n_sel_items: int, factor_num: int) -> int:
+    """float64 loss partials, one per 16 selected users: a function of the sizes alone, non-decreasing"""
+    return int(_capi.lib().invpref_impute_workspace_bytes(int(n_sel_users), int(n_sel_items), int(factor_num)))
+
+
+def impute_grad_(user_table: torch.Tensor, item_table: torch.Tensor, sel_users: torch.Tensor, sel_items: torch.Tensor,
+                 imputation_coe: float, grad_user: torch.Tensor, grad_item: torch.Tensor,
+                 loss_out: Optional[torch.Tensor] = None, term_out: Optional[torch.Tensor] = None,
+                 workspace: Optional[Workspace] = None) -> None:
+    """WMF's imputation term over the block sel_users x sel_items (int32 ids, distinct within a side): ADDS
+    imputation_coe / (n_u n_i) * d BCE(sigmoid(Pu[a] . Qi[b]), 0) into the selection's rows of grad_user / grad_item, adds
+    imputation_coe * mean to loss_out[0] and writes the plain mean to term_out[0] (either may be None).  No pair list or score
+    matrix is formed; bitwise reproducible; no host sync (graph-capturable once the workspace is sized; a replay reads the
+    selection tensors' current contents)."""
+    _gpu(user_table, item_table, sel_users, sel_items, grad_user, grad_item, loss_out, term_out)
+    ws = (workspace or Workspace(user_table.device)).get(
+        max(impute_workspace_bytes(sel_users.numel(), sel_items.numel(), user_table.shape[1]), 8))
+    _o().impute_grad_(user_table, item_table, sel_users, sel_items, float(imputation_coe), grad_user, grad_item, loss_out,
+                      term_out, ws)

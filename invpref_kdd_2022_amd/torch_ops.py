@@ -38,6 +38,8 @@ What replaces what in the reference:
 ``exposure_probability``       ExpoMF's posterior matrix (baseline_models.py:252-256): fp32 ``[n, I]`` (store mode)
 ``exposure_prior_``            ExpoMF's prior update (baseline_train.py:63-79) in place on ``mu``; nothing ``[n, I]`` is stored
 ``exposure_weights_``          ExpoMF's step weights ``prob ** e`` (1.0 at positives) at given pairs (baseline_train.py:88-99)
+``impute_grad_``               WMF's imputation term over a block of users x items (baseline_train.py:204-216): adds its gradient
+                               into the selection's rows and its value into the step's loss; no pair list
 =============================  =====================================================================================
 
 Tensors are borrowed for the call and never retained.  ``workspace`` arguments are caller-owned scratch (uint8),
@@ -898,4 +900,34 @@ def _exposure_weights(user_table, item_table, users, items, positive, mu, lam_y,
 
 @_fake('exposure_weights_')
 def _exposure_weights_fake(user_table, item_table, users, items, positive, mu, lam_y, eps, weight_exp, out):
+    return None
+
+
+# ---- WMF imputation term (baseline_train.py:157-228; csrc/invpref_impute.hip)
+_define('impute_grad_(Tensor user_table, Tensor item_table, Tensor sel_users, Tensor sel_items, float imputation_coe, '
+        'Tensor(a!) grad_user, Tensor(b!) grad_item, Tensor(c!)? loss_out, Tensor(d!)? term_out, Tensor(e!) workspace) -> ()')
+
+
+@_impl('impute_grad_')
+def _impute_grad(user_table, item_table, sel_users, sel_items, imputation_coe, grad_user, grad_item, loss_out, term_out,
+                 workspace):
+    U, I, D = _expo_tables(user_table, item_table)
+    _f32(grad_user, 'grad_user')
+    _f32(grad_item, 'grad_item')
+    if tuple(grad_user.shape) != (U, D) or tuple(grad_item.shape) != (I, D):
+        raise InvPrefError('impute_grad: grad_user / grad_item must have the shapes of user_table / item_table')
+    _capi._req(sel_users, torch.int32, 'sel_users')
+    _capi._req(sel_items, torch.int32, 'sel_items')
+    _f32(loss_out, 'loss_out')
+    _f32(term_out, 'term_out')
+    _capi._req(workspace, torch.uint8, 'workspace')
+    check(lib().invpref_impute_grad_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(sel_users), sel_users.numel(),
+                                        ptr(sel_items), sel_items.numel(), float(imputation_coe), ptr(grad_user),
+                                        ptr(grad_item), ptr(loss_out), ptr(term_out), ptr(workspace), workspace.numel(),
+                                        stream_ptr()), 'invpref_impute_grad_hip')
+
+
+@_fake('impute_grad_')
+def _impute_grad_fake(user_table, item_table, sel_users, sel_items, imputation_coe, grad_user, grad_item, loss_out, term_out,
+                      workspace):
     return None

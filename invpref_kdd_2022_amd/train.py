@@ -682,6 +682,7 @@ class _InvPrefTrainManager:
         if multi:
             if self.world_size > 1 or self._collective_ok:
                 self._exchange_gradient(k)   # all-reduce (whole or packed), or reduce-scatter (this rank keeps its slice of the sum)
+        self._after_gradient_pass(k, lp)
         if mid_event is not None:
             mid_event.record()
         # the planned gradient pass overwrites every row it is responsible for, so the gradient buffer needs no zeroing
@@ -699,6 +700,11 @@ class _InvPrefTrainManager:
             if zero and self.exchange == 'scatter' and self.world_size > 1:
                 st.grad.zero_()   # plan-free gradients ADD: the slices this rank's Adam did not clear must start from zero too
             self._exchange_parameters()
+
+    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
+        """Hook of the unfused sequence (gradient pass -> [exchange] -> HERE -> Adam), minibatch k of epoch slot
+        self._loss_slot: a manager whose loss has a term the step does not know adds its gradient into state.g_views and its
+        value into losses6 (baseline.py: WMFTrainManager).  Nothing is launched here."""
 
     def _alpha_for(self, k: int) -> float:
         if self.update_alpha:  # train.py:214-217
