@@ -619,6 +619,46 @@ int invpref_impute_grad_hip(const float *user_table, int64_t user_num, const flo
                             int64_t n_sel_items, double imputation_coe, float *grad_user, float *grad_item, float *loss_out,
                             float *term_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- CVIB information term (baseline_train.py:584-647 implicit, :978-1044 explicit; csrc/invpref_cvib.hip).  Per step, with
+ * p_i the prediction at the minibatch's pairs (users[i], items[i]), i < batch, and q_j at the step's drawn pairs
+ * (draw_users[j], draw_items[j]), j < batch (sigmoid(Pu[u] . Qi[v]) under INVPREF_IMPLICIT, else the dot product):
+ *   info = alpha * (-pbar * log(qbar) - (1 - pbar) * log(1 - qbar)) + gamma * mean(p_i * log(p_i)),
+ * the three logarithms' arguments clipped from below at eps in the explicit form (eps is rounded to fp32 once, as the
+ * reference clips fp32 tensors, and that one value is used by every clip; it is not read in the implicit form), and
+ * info_coe * d info / d table is ADDED into grad_user / grad_item: one writer per row, every sum in a fixed order, no float
+ * atomics, bitwise reproducible, rows without a contribution untouched.  *loss_out += info_coe * info; info_out / pbar_out /
+ * qbar_out receive info and the two means (all four may be NULL).  A pair with an id outside its table is skipped on both
+ * sides (never an address) and info is NaN.  The scores, the sigmoid, the logarithms and the row sums of this term are
+ * evaluated in float64 (log p + 1 cancels near p = 1/2); each pair's factor and each row sum is rounded to fp32 once.
+ * Implicit p_i == 0 or qbar in {0, 1}: NaN / inf as in the reference (no clip).
+ *
+ * The contributions reach their rows through an inverted index, which a run of steps builds once in one batched pass:
+ *   1. invpref_cvib_index_keys_hip: int64 keys [steps][2][2 * batch_cap] -- step s takes the step_n[s] pairs of users / items
+ *      from position step_lo[s] and its drawn pairs from draws[s][0] (users) / draws[s][1] (items), int32 [steps][2][batch_cap];
+ *      the key orders (step, side, destination row, position); padding and skipped pairs go under a sentinel row.  The
+ *      step table lives on the device, so the CALLER guarantees 0 <= step_n[s] <= batch_cap and that
+ *      users / items hold step_lo[s] + step_n[s] entries: users[] and items[] are read at those positions;
+ *   2. ANY ascending sort of the whole key array (the keys are unique, so every sort gives the same array);
+ *   3. invpref_cvib_index_hip: the sorted keys -> index, int32 [steps][2][2 * batch_cap][2] = (destination row, position).
+ * invpref_cvib_grad_hip takes the index of ITS step (index + s * 2 * index_stride * 2, index_stride = 2 * batch_cap >= 2 * batch)
+ * and reads it, the ids and the draws when its kernels run: a captured launch sees what the buffers hold at replay time.
+ * Four launches, no allocation, no synchronisation.  workspace (16-byte aligned): the record, two factors per pair, float64
+ * partials and the chunk slots -- a function of (batch, factor_num) alone, non-decreasing in batch; 0 for bad sizes.
+ * steps <= 65535, batch <= 2^24, and the largest key, 2 * steps * (max(user_num, item_num) + 1) * 2 * batch_cap, must fit an
+ * int64: INVPREF_EUNSUPPORTED otherwise. */
+size_t invpref_cvib_workspace_bytes(int64_t batch, int64_t factor_num);
+int invpref_cvib_index_keys_hip(const int64_t *users, const int64_t *items, const int64_t *step_lo, const int32_t *step_n,
+                                int64_t steps, const int32_t *draws, int64_t batch_cap, int64_t user_num, int64_t item_num,
+                                int64_t *keys, void *stream);
+int invpref_cvib_index_hip(const int64_t *sorted_keys, int64_t steps, int64_t batch_cap, int64_t user_num, int64_t item_num,
+                           int32_t *index, void *stream);
+int invpref_cvib_grad_hip(const float *user_table, int64_t user_num, const float *item_table, int64_t item_num, int64_t factor_num,
+                          const int64_t *users, const int64_t *items, int64_t batch, const int32_t *draw_users,
+                          const int32_t *draw_items, const int32_t *index, int64_t index_stride, uint32_t flags, double alpha,
+                          double gamma, double info_coe, double eps, float *grad_user, float *grad_item, float *loss_out,
+                          float *info_out, float *pbar_out, float *qbar_out, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,8 @@ EXPORTS = [
     'invpref_interaction_counts_workspace_bytes', 'invpref_interaction_counts_hip', 'invpref_count_propensity_workspace_bytes',
     'invpref_count_propensity_hip', 'invpref_naive_bayes_workspace_bytes', 'invpref_naive_bayes_propensity_hip',
     'invpref_snips_scale_hip', 'invpref_exposure_workspace_bytes', 'invpref_exposure_hip', 'invpref_exposure_weights_hip',
-    'invpref_impute_workspace_bytes', 'invpref_impute_grad_hip',
+    'invpref_impute_workspace_bytes', 'invpref_impute_grad_hip', 'invpref_cvib_workspace_bytes', 'invpref_cvib_index_keys_hip',
+    'invpref_cvib_index_hip', 'invpref_cvib_grad_hip',
 ]
 MAX_TOPK = 64          # k of the fused scan / k-pass / radix-select kernels and the 64-wide metric tables
 MAX_TOPK_WIDE = 1024   # INVPREF_MAX_TOPK_WIDE: the wide entry points (csrc/invpref_topk_wide.hip)
@@ -165,6 +166,12 @@ def lib():
         L.invpref_impute_workspace_bytes.restype = C.c_size_t
         L.invpref_impute_workspace_bytes.argtypes = [i64, i64, i64]
         L.invpref_impute_grad_hip.argtypes = [vp, i64, vp, i64, i64, vp, i64, vp, i64, f64, vp, vp, vp, vp, vp, C.c_size_t, vp]
+        L.invpref_cvib_workspace_bytes.restype = C.c_size_t
+        L.invpref_cvib_workspace_bytes.argtypes = [i64, i64]
+        L.invpref_cvib_index_keys_hip.argtypes = [vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, vp]
+        L.invpref_cvib_index_hip.argtypes = [vp, i64, i64, i64, i64, vp, vp]
+        L.invpref_cvib_grad_hip.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, u32, f64, f64, f64, f64, vp, vp, vp,
+                                            vp, vp, vp, vp, C.c_size_t, vp]
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')
         _lib = L

@@ -1,4 +1,5 @@
-"""PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF) and ExpoMF.
+"""PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF
+and CVIB-MF.
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -750,3 +751,187 @@ class WMFTrainManager(BasicImplicitTrainManager):
             ops.adam_(st.param[o:o + ln], st.grad[o:o + ln], st.exp_avg[o:o + ln], st.exp_avg_sq[o:o + ln], st.step, self.lr,
                       zero_grad=False)
         return self.loss_dicts(st.losses6[None])[0]
+
+
+# ------------------------------------------------------------------------------------------------ CVIB-MF
+def cvib_draw(user_num: int, item_num: int, n: int):
+    """one step's drawn pairs (baseline_train.py:617-620 / :1013-1016): two np.random.randint calls on numpy's GLOBAL
+    generator, users first.  Host only."""
+    ru = np.random.randint(0, user_num, n)
+    rv = np.random.randint(0, item_num, n)
+    return ru, rv
+
+
+def cvib_draw_epochs(user_num: int, item_num: int, batch_lens, epochs: int) -> list:
+    """the drawn pairs of `epochs` whole epochs in the reference's order (step by step, as many pairs as the minibatch has
+    rows): [(ru, rv), ...]"""
+    return [cvib_draw(user_num, item_num, n) for _ in range(epochs) for n in batch_lens]
+
+
+class _CVIBMixin:
+    """CVIBTrainManager / CVIBExplicitTrainManager (baseline_train.py:584-647, :978-1044): the PureMF step plus
+    info_coe * info, info = alpha * (-pbar log qbar - (1 - pbar) log(1 - qbar)) + gamma * mean(p log p), p the predictions at
+    the minibatch's pairs, qbar the mean prediction at as many uniformly drawn (user, item) pairs (the explicit form clips the
+    logarithms' arguments at eps).  `info` is visible inside 'loss' only.
+
+    The step is the engine's unfused sequence with one call between the gradient pass and Adam: planned PureMF gradient pass ->
+    torch.ops.invpref.cvib_grad_ (csrc/invpref_cvib.hip: means, fold, scatter, boundary; adds into the same gradient buffer
+    and into the step's `loss`) -> dense / ranged Adam.
+
+    The draws: before a run of epochs is enqueued every step's pairs are drawn on the host in the reference's order
+    (np.random.randint, users then items, B = the minibatch's rows), copied to the device once into ONE int32 buffer (row = the
+    step's position in the run) and indexed there in one batched pass (ops.cvib_index: destination row -> pair positions of
+    the minibatch and drawn pairs together).  The captured launches read their row of both buffers when they run, so a
+    captured run of epochs is replayed with new draws without re-capture.
+
+    draws= (keyword-only) replaces numpy's global generator: a callable (user_num, item_num, n) -> (ru, rv) called once per
+    step in order, or an iterable of (ru, rv) pairs consumed in that order (recorded draws)."""
+    # bytes of the run's index: longer runs are replayed as several shorter graphs.  Building it takes four to five times as
+    # much for a moment (keys, sorted keys, the sort's permutation and temporaries: ops.cvib_index), freed before the run starts
+    _INDEX_BUDGET = 512 << 20
+
+    def _cvib_init(self, alpha, gamma, info_coe, eps, draws):
+        if self.world_size > 1:
+            raise NotImplementedError(_CVIB_SINGLE)
+        # (the engine's `alpha` is InvPref's environment weight, which a PureMF step never reads: the attribute is CVIB's here,
+        #  as in the reference)
+        self.alpha, self.gamma, self.info_coe, self.eps = float(alpha), float(gamma), float(info_coe), float(eps)
+        self._unfused = True        # always gradient pass -> _after_gradient_pass -> Adam (never the fused / alternating step)
+        n, bs = self.n_total, self.batch_size
+        self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]
+        self._cap = max(self._batch_lens)
+        self._draw_source = draws
+        self._draw_iter = iter(draws) if draws is not None and not callable(draws) else None
+        self._queue = []            # drawn, not yet consumed: whole epochs of (ru, rv) in step order
+        self._draws = self._index = None
+        self._cvib_ws = ops.Workspace(self.device)
+        self._cvib_ws.get(max(ops.cvib_workspace_bytes(self._cap, self.model.factor_num), 16))   # sized once: capturable launches
+
+    def _draw(self, n: int):
+        if self._draw_source is None:
+            ru, rv = cvib_draw(self.model.user_num, self.model.item_num, n)
+        elif self._draw_iter is not None:
+            ru, rv = next(self._draw_iter)
+        else:
+            ru, rv = self._draw_source(self.model.user_num, self.model.item_num, n)
+        ru, rv = np.asarray(ru).reshape(-1), np.asarray(rv).reshape(-1)
+        if (len(ru), len(rv)) != (n, n):
+            raise ValueError(f'a draw of {len(ru)} users and {len(rv)} items where the step takes {n} pairs')
+        return ru.astype(np.int32), rv.astype(np.int32)
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        per_epoch = self.batch_num * self._cap * 32          # int32 (row, position) x two sides x 2 B entries per step
+        self._graph_epochs = max(1, min(self._graph_epochs, self._INDEX_BUDGET // per_epoch))
+        rows = self._graph_epochs * self.batch_num
+        if self._draws is None or self._draws.shape[0] != rows:
+            dev = self.device
+            self._draws = torch.zeros(rows, 2, self._cap, dtype=torch.int32, device=dev)
+            self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
+            lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
+            self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
+            self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
+
+    def _stage_draws(self, n: int):
+        """the pairs of the next n epochs: drawn (those not yet drawn), laid out one row per step, one copy, one index pass"""
+        steps = n * self.batch_num
+        while len(self._queue) < steps:
+            self._queue.extend(self._draw(b) for b in self._batch_lens)
+        host = np.zeros((steps, 2, self._cap), np.int32)
+        for s in range(steps):
+            ru, rv = self._queue[s]
+            host[s, 0, :len(ru)] = ru
+            host[s, 1, :len(rv)] = rv
+        src = torch.from_numpy(host)
+        if self._draws.is_cuda:
+            src = src.pin_memory()
+        self._draws[:steps].copy_(src, non_blocking=True)
+        ops.cvib_index(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._draws[:steps],
+                       self.model.user_num, self.model.item_num, out=self._index[:steps])
+
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        if getattr(self, '_raw_ptrs', None) is None or self._draws is None:
+            self._raw_setup()
+        n = min(want, self._graph_epochs) if (self.graphs_enabled() and self._graph_warm) else 1
+        self._stage_draws(n)
+        before = self.epoch_cnt
+        out = super()._enqueue_epochs(want)
+        del self._queue[:(self.epoch_cnt - before) * self.batch_num]   # (a failed capture runs one eager epoch of the n)
+        return out
+
+    def prepare_graphs(self, run_lengths) -> None:
+        if self._draws is None:
+            raise RuntimeError('prepare_graphs(): run one epoch first (train_epochs(1))')
+        super().prepare_graphs(run_lengths)
+
+    def _info_term(self, users, items, draw_users, draw_items, index, loss_slot):
+        st = self.state
+        ops.cvib_grad_(st.p_views[0], st.p_views[1], users, items, draw_users, draw_items, index, self.implicit, self.alpha,
+                       self.gamma, self.info_coe, self.eps, st.g_views[0], st.g_views[1], loss_slot, None, None, None,
+                       self._cvib_ws)
+
+    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
+        s = self._loss_slot * self.batch_num + k
+        n, bu, bi = self._raw_batches[k][1], self._raw_batches[k][3], self._raw_batches[k][4]
+        self._info_term(bu, bi, self._draws[s, 0, :n], self._draws[s, 1, :n], self._index[s], losses6[5:6])
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """baseline_train.py:606-647 / :1002-1044 on caller tensors: as many drawn pairs as the batch has rows, one step."""
+        u = batch_users_tensor.detach().cpu().numpy().reshape(-1)
+        v = batch_items_tensor.detach().cpu().numpy().reshape(-1)
+        y = batch_scores_tensor.detach().float().contiguous()
+        ru, rv = self._draw(len(u))
+        dev = self.device
+        dp = planlib.upload(planlib.build_row_plan(u, v, y.cpu().numpy(), self.model.user_num, self.model.item_num,
+                                                   factor_num=self.model.factor_num, env_num=0), dev)
+        ud = torch.from_numpy(np.ascontiguousarray(u, dtype=np.int64)).to(dev)
+        vd = torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64)).to(dev)
+        draws = torch.from_numpy(np.stack([ru, rv])[None]).to(dev)
+        index = ops.cvib_index(ud, vd, torch.zeros(1, dtype=torch.int64, device=dev),
+                               torch.full((1,), len(u), dtype=torch.int32, device=dev), draws, self.model.user_num,
+                               self.model.item_num)
+        self._cvib_ws.get(max(ops.cvib_workspace_bytes(len(u), self.model.factor_num), 16))
+        st = self.state
+        st.losses6.zero_()
+        st.step += 1
+        self._sched_synced = False
+        ops.mstep_rows_grad(st.p_views, st.g_views, dp, None, y.to(dev), None, len(u), self._coefs(0.),
+                            self._flags & ~_capi.REWEIGHT_REC, st.losses6, self.workspace)
+        self._info_term(ud, vd, draws[0, 0], draws[0, 1], index[0], st.losses6[5:6])
+        self._grad_stale = True     # (the planned pass overwrote every row: nothing to zero, see _step())
+        for o, ln in getattr(self, '_adam_ranges', [(0, st.n)]):
+            ops.adam_(st.param[o:o + ln], st.grad[o:o + ln], st.exp_avg[o:o + ln], st.exp_avg_sq[o:o + ln], st.step, self.lr,
+                      zero_grad=False)
+        return self.loss_dicts(st.losses6[None])[0]
+
+
+_CVIB_SINGLE = 'CVIB runs in a single process (a sharded form would all-reduce the two means and the summed gradient; ' \
+               'not implemented)'
+
+
+class CVIBTrainManager(_CVIBMixin, BasicImplicitTrainManager):
+    """reference baseline_train.py:584-647 (BCELoss + the information term; no clip)"""
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
+                 alpha: float = 0.1, gamma: float = 0.01, info_coe: float = 1.0, *, draws=None, rank=None, world_size=None,
+                 process_group=None):
+        if world_size is not None and int(world_size) > 1:
+            raise NotImplementedError(_CVIB_SINGLE)
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        self._cvib_init(alpha, gamma, info_coe, 0.0, draws)
+
+
+class CVIBExplicitTrainManager(_CVIBMixin, BasicExplicitTrainManager):
+    """reference baseline_train.py:978-1044 (MSELoss + the information term, logarithms clipped at eps)"""
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
+                 alpha: float = 0.1, gamma: float = 0.01, info_coe: float = 1.0, eps: float = 1e-1, *, draws=None, rank=None,
+                 world_size=None, process_group=None):
+        if world_size is not None and int(world_size) > 1:
+            raise NotImplementedError(_CVIB_SINGLE)
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        self._cvib_init(alpha, gamma, info_coe, eps, draws)

@@ -551,3 +551,43 @@ def impute_grad_(user_table: torch.Tensor, item_table: torch.Tensor, sel_users: 
         max(impute_workspace_bytes(sel_users.numel(), sel_items.numel(), user_table.shape[1]), 8))
     _o().impute_grad_(user_table, item_table, sel_users, sel_items, float(imputation_coe), grad_user, grad_item, loss_out,
                       term_out, ws)
+
+
+# ---- CVIB information term (baseline_train.py:584-647, :978-1044; csrc/invpref_cvib.hip)
+def cvib_workspace_bytes(batch: int, factor_num: int) -> int:
+    """record + two factors per pair + float64 partials + chunk slots of one step: a function of the sizes alone, non-decreasing in batch"""
+    return int(_capi.lib().invpref_cvib_workspace_bytes(int(batch), int(factor_num)))
+
+
+def cvib_index(users: torch.Tensor, items: torch.Tensor, step_lo: torch.Tensor, step_n: torch.Tensor, draws: torch.Tensor,
+               user_num: int, item_num: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inverted index of a run of steps in one batched pass: step s holds the step_n[s] (int32) pairs of users / items
+    (int64) from position step_lo[s] (int64) and the drawn pairs draws[s, 0] / draws[s, 1] (int32 [steps, 2, batch_cap]).
+    Returns int32 [steps, 2, 2 * batch_cap, 2]: per step and side (0: user rows, 1: item rows) the positions sorted by
+    destination row, as (row, position); written into `out` if given (the buffer captured launches read).  The caller
+    guarantees step_n[s] <= batch_cap and step_lo[s] + step_n[s] <= len(users) (device values: not checked here).  Allocates:
+    the keys, their sorted copy and the sort's int64 permutation -- three arrays of the index's own size (8 bytes per entry)
+    -- plus the radix sort's temporaries are alive at once, so the transient peak is four to five times the index.  Call it
+    outside a graph capture."""
+    _gpu(users, items, step_lo, step_n, draws, out)
+    if out is None:
+        out = torch.empty(draws.shape[0], 2, 2 * draws.shape[2], 2, dtype=torch.int32, device=draws.device)
+    _o().cvib_index_(users, items, step_lo, step_n, draws, int(user_num), int(item_num), out)
+    return out
+
+
+def cvib_grad_(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, items: torch.Tensor,
+               draw_users: torch.Tensor, draw_items: torch.Tensor, index: torch.Tensor, implicit: bool, alpha: float,
+               gamma: float, info_coe: float, eps: float, grad_user: torch.Tensor, grad_item: torch.Tensor,
+               loss_out: Optional[torch.Tensor] = None, info_out: Optional[torch.Tensor] = None,
+               pbar_out: Optional[torch.Tensor] = None, qbar_out: Optional[torch.Tensor] = None,
+               workspace: Optional[Workspace] = None) -> None:
+    """CVIB's information term of one step over the minibatch pairs (users, items: int64 [B]) and the drawn pairs (int32 [B]):
+    ADDS info_coe * d info into grad_user / grad_item through `index` (this step's slice of cvib_index), adds info_coe * info
+    to loss_out[0] and writes info / pbar / qbar to the optional outputs.  Bitwise reproducible, no float atomics, no host
+    sync (graph-capturable once the workspace is sized; a replay reads the ids, draws and index as they are then)."""
+    _gpu(user_table, item_table, users, items, draw_users, draw_items, index, grad_user, grad_item, loss_out, info_out,
+         pbar_out, qbar_out)
+    ws = (workspace or Workspace(user_table.device)).get(max(cvib_workspace_bytes(users.numel(), user_table.shape[1]), 16))
+    _o().cvib_grad_(user_table, item_table, users, items, draw_users, draw_items, index, bool(implicit), float(alpha),
+                    float(gamma), float(info_coe), float(eps), grad_user, grad_item, loss_out, info_out, pbar_out, qbar_out, ws)

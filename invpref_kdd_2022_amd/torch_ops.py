@@ -40,6 +40,10 @@ What replaces what in the reference:
 ``exposure_weights_``          ExpoMF's step weights ``prob ** e`` (1.0 at positives) at given pairs (baseline_train.py:88-99)
 ``impute_grad_``               WMF's imputation term over a block of users x items (baseline_train.py:204-216): adds its gradient
                                into the selection's rows and its value into the step's loss; no pair list
+``cvib_index_``                the inverted index (destination row -> pair positions) of the minibatch and drawn pairs of a run
+                               of steps, one batched pass; what replaces autograd's scatter-add of two gathered matrices
+``cvib_grad_``                 CVIB's information term (baseline_train.py:614-635, :1010-1032): adds its gradient into both
+                               gradient tables and its value into the step's loss
 =============================  =====================================================================================
 
 Tensors are borrowed for the call and never retained.  ``workspace`` arguments are caller-owned scratch (uint8),
@@ -930,4 +934,86 @@ def _impute_grad(user_table, item_table, sel_users, sel_items, imputation_coe, g
 @_fake('impute_grad_')
 def _impute_grad_fake(user_table, item_table, sel_users, sel_items, imputation_coe, grad_user, grad_item, loss_out, term_out,
                       workspace):
+    return None
+
+
+# ---- CVIB information term (baseline_train.py:584-647, :978-1044; csrc/invpref_cvib.hip)
+_define('cvib_index_(Tensor users, Tensor items, Tensor step_lo, Tensor step_n, Tensor draws, int user_num, int item_num, '
+        'Tensor(a!) index) -> ()')
+
+
+def _cvib_index_shapes(step_lo, step_n, draws, index):
+    if draws.dim() != 3 or draws.shape[1] != 2 or draws.shape[0] < 1 or draws.shape[2] < 1:
+        raise InvPrefError('cvib_index: draws must be int32 [steps, 2, batch_cap]')
+    steps, _, cap = draws.shape
+    if step_lo.numel() != steps or step_n.numel() != steps:
+        raise InvPrefError(f'cvib_index: step_lo / step_n must have one entry per step ({steps})')
+    if tuple(index.shape) != (steps, 2, 2 * cap, 2):
+        raise InvPrefError(f'cvib_index: index must be int32 [{steps}, 2, {2 * cap}, 2]')
+    return steps, cap
+
+
+@_impl('cvib_index_')
+def _cvib_index(users, items, step_lo, step_n, draws, user_num, item_num, index):
+    _ids(users, 'users')
+    _ids(items, 'items')
+    _ids(step_lo, 'step_lo')
+    _capi._req(step_n, torch.int32, 'step_n')
+    _capi._req(draws, torch.int32, 'draws')
+    _capi._req(index, torch.int32, 'index')
+    steps, cap = _cvib_index_shapes(step_lo, step_n, draws, index)
+    if users.numel() != items.numel():
+        raise InvPrefError('cvib_index: users and items must have the same length')
+    keys = torch.empty(steps * 2 * 2 * cap, dtype=torch.int64, device=users.device)
+    check(lib().invpref_cvib_index_keys_hip(ptr(users), ptr(items), ptr(step_lo), ptr(step_n), steps, ptr(draws), cap,
+                                            int(user_num), int(item_num), ptr(keys), stream_ptr()), 'invpref_cvib_index_keys_hip')
+    # unique keys: the result does not depend on the sort.  torch.sort also returns an int64 permutation, which nothing here
+    # needs: it is dropped at once, but it and the unsorted keys are alive during the sort (see ops.cvib_index)
+    keys = torch.sort(keys).values
+    check(lib().invpref_cvib_index_hip(ptr(keys), steps, cap, int(user_num), int(item_num), ptr(index), stream_ptr()),
+          'invpref_cvib_index_hip')
+
+
+@_fake('cvib_index_')
+def _cvib_index_fake(users, items, step_lo, step_n, draws, user_num, item_num, index):
+    return None
+
+
+_define('cvib_grad_(Tensor user_table, Tensor item_table, Tensor users, Tensor items, Tensor draw_users, Tensor draw_items, '
+        'Tensor index, bool implicit, float alpha, float gamma, float info_coe, float eps, Tensor(a!) grad_user, '
+        'Tensor(b!) grad_item, Tensor(c!)? loss_out, Tensor(d!)? info_out, Tensor(e!)? pbar_out, Tensor(f!)? qbar_out, '
+        'Tensor(g!) workspace) -> ()')
+
+
+@_impl('cvib_grad_')
+def _cvib_grad(user_table, item_table, users, items, draw_users, draw_items, index, implicit, alpha, gamma, info_coe, eps,
+               grad_user, grad_item, loss_out, info_out, pbar_out, qbar_out, workspace):
+    U, I, D = _expo_tables(user_table, item_table)
+    _f32(grad_user, 'grad_user')
+    _f32(grad_item, 'grad_item')
+    if tuple(grad_user.shape) != (U, D) or tuple(grad_item.shape) != (I, D):
+        raise InvPrefError('cvib_grad: grad_user / grad_item must have the shapes of user_table / item_table')
+    _ids(users, 'users')
+    _ids(items, 'items')
+    _capi._req(draw_users, torch.int32, 'draw_users')
+    _capi._req(draw_items, torch.int32, 'draw_items')
+    _capi._req(index, torch.int32, 'index')
+    B = users.numel()
+    if items.numel() != B or draw_users.numel() != B or draw_items.numel() != B:
+        raise InvPrefError(f'cvib_grad: items, draw_users and draw_items must have the {B} entries of users')
+    if index.dim() != 3 or index.shape[0] != 2 or index.shape[2] != 2 or index.shape[1] < 2 * B:
+        raise InvPrefError(f'cvib_grad: index must be int32 [2, at least {2 * B}, 2] (one step of cvib_index_)')
+    for n, x in (('loss_out', loss_out), ('info_out', info_out), ('pbar_out', pbar_out), ('qbar_out', qbar_out)):
+        _f32(x, n)
+    _capi._req(workspace, torch.uint8, 'workspace')
+    check(lib().invpref_cvib_grad_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(items), B, ptr(draw_users),
+                                      ptr(draw_items), ptr(index), index.shape[1], _capi.IMPLICIT if implicit else 0,
+                                      float(alpha), float(gamma), float(info_coe), float(eps), ptr(grad_user), ptr(grad_item),
+                                      ptr(loss_out), ptr(info_out), ptr(pbar_out), ptr(qbar_out), ptr(workspace),
+                                      workspace.numel(), stream_ptr()), 'invpref_cvib_grad_hip')
+
+
+@_fake('cvib_grad_')
+def _cvib_grad_fake(user_table, item_table, users, items, draw_users, draw_items, index, implicit, alpha, gamma, info_coe, eps,
+                    grad_user, grad_item, loss_out, info_out, pbar_out, qbar_out, workspace):
     return None
