@@ -19,16 +19,12 @@ SNIPS's per-minibatch normaliser sum(w) is folded into the weights of the static
 """
 from __future__ import annotations
 
-import math
-import os
-
 import numpy as np
 import torch
 from torch import nn
 
-from . import _capi, ops, plan as planlib
-from .parallel import RowShard, UserShard
-from .train import FlatState, _InvPrefTrainManager, transfer_loss_dict_to_line_str
+from . import _capi, ops
+from .train import _InvPrefTrainManager
 
 PURE_LOSS_KEYS = ['score_loss', 'L2_reg', 'L1_reg', 'loss']  # train.py:399-404
 
@@ -125,61 +121,16 @@ class _BasicTrainManager(_InvPrefTrainManager):
         """rank / world_size / process_group (keyword-only, beyond the reference's signature): one process per GPU,
         sharded like the InvPref managers (parallel.py; INVPREF_SHARD=users|rows): every rank keeps its share of
         every minibatch, one all-reduce per optimiser step, every mean() over the GLOBAL minibatch."""
-        if model.implicit != self.implicit:
-            raise TypeError(f'{type(self).__name__} needs an {"implicit" if self.implicit else "explicit"} model')
-        self.model, self.evaluator, self.device = model, evaluator, torch.device(device)
-        self.process_group = process_group
-        if world_size is None:
-            import torch.distributed as dist
-            world_size = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
-            rank = dist.get_rank(process_group) if world_size > 1 else 0
-        self.rank, self.world_size = int(rank or 0), int(world_size)
-        n_total = training_data.shape[0]
-        self.n_total, self.batch_size = n_total, batch_size
-        self.batch_num = math.ceil(n_total / batch_size)
-        forced = os.environ.get('INVPREF_FORCE_SHARDED_PATH', '0') == '1'
-        self.shard_mode = os.environ.get('INVPREF_SHARD', 'rows') if (self.world_size > 1 or forced) else 'rows'
-        if self.shard_mode == 'users':
-            self.shard = UserShard(training_data[:, 0].cpu().numpy(), n_total, batch_size, model.user_num, self.rank,
-                                   self.world_size)
-        else:
-            self.shard = RowShard(n_total, batch_size, self.rank, self.world_size)
-        training_data_full = training_data
-        if self.world_size > 1:
-            training_data = training_data.index_select(0, self.shard.local_rows().to(training_data.device))
-        self.users_tensor = training_data[:, 0].contiguous().to(self.device)
-        self.items_tensor = training_data[:, 1].contiguous().to(self.device)
-        self.scores_tensor = training_data[:, 2].float().contiguous().to(self.device)
-        self.evaluate_interval, self.epochs, self.lr = evaluate_interval, epochs, lr
-        self.L2_coe, self.L1_coe = L2_coe, L1_coe
-        self.epoch_cnt = 0
-        self.test_begin_epoch = test_begin_epoch
+        self._init_engine(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                          test_begin_epoch, rank, world_size, process_group,
+                          flags=ops.flags_of(self.implicit, False, False, True, False, dense_reg=False) | _capi.PURE_MF,
+                          users_first=None,     # [user table | item table]: the shared part is last as listed
+                          env_switches=False)
         # no environments: the engine's env / weight pointers are never dereferenced under INVPREF_PURE_MF
         self.envs = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.sample_weights = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.alpha, self.update_alpha = 0., False
         self.cluster_interval = 1 << 62
-        self.model.to(self.device)
-        # (row-sharded: reduce-scatter / slice Adam / all-gather exchange like the InvPref managers, train.py)
-        self.exchange = os.environ.get('INVPREF_EXCHANGE', 'allreduce') if self.shard_mode == 'rows' else 'allreduce'
-        self.state = FlatState(model.tables(), self.device,     # [user table | item table]: the shared part is last
-                               chunks=self.world_size if self.exchange == 'scatter' else 1)
-        self._setup_ranges(model)
-        if self.exchange == 'packed':
-            self._setup_packed(training_data_full[:, 0], training_data_full[:, 1])
-        self.workspace = ops.Workspace(self.device)
-        self._flags = ops.flags_of(self.implicit, False, False, True, False, dense_reg=False) | _capi.PURE_MF
-        self.use_plan, self._plans = True, None
-        self._batch_plans, self.planned_batch_steps = {}, 0
-        self.use_graph = os.environ.get('INVPREF_NO_GRAPH', '0') != '1'
-        import torch.distributed as _dist
-        self._force_sharded_path, self._unfused = forced, False
-        self._collective_ok = _dist.is_available() and _dist.is_initialized()
-        self._graphs, self._graph_warm = {}, False
-        self._estep_graphs = {}
-        self._grad_stale = False
-        self._sched, self._sched_synced = None, False
-        self._alt = None
 
     def _coefs(self, alpha):
         return (1., 0., 0., 2. * self.L2_coe, 2. * self.L1_coe, 0.)
@@ -195,62 +146,39 @@ class _BasicTrainManager(_InvPrefTrainManager):
         Single-process form; sharded runs go through train_epochs() / train()."""
         return self._batch_step(batch_users_tensor, batch_items_tensor, batch_scores_tensor, None)
 
-    def _batch_step(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, weights) -> dict:
-        """one fused step on caller tensors; weights (fp32, device, one per interaction) are read under
-        INVPREF_REWEIGHT_REC, None runs the unweighted step"""
+    def _batch_step(self, batch_users, batch_items, batch_scores_tensor, weights, term=None) -> dict:
+        """one step on caller-supplied ids (tensors or host arrays) and labels; weights (fp32, device, one per interaction) are
+        read under INVPREF_REWEIGHT_REC, None runs the unweighted step.  term None: the fused step.  term, a callable that adds
+        a further loss term's gradient into state.g_views and its value into state.losses6: the unfused sequence, gradient
+        pass -> term() -> Adam over this rank's ranges."""
         if self.world_size > 1:
             raise NotImplementedError('train_a_batch on caller-supplied tensors is single-process; use train_epochs()')
         flags = self._flags if weights is not None else self._flags & ~_capi.REWEIGHT_REC
-        u = batch_users_tensor.detach().cpu().numpy()
-        v = batch_items_tensor.detach().cpu().numpy()
+        u, v = (x if isinstance(x, np.ndarray) else x.detach().cpu().numpy() for x in (batch_users, batch_items))
         y = batch_scores_tensor.detach().float().contiguous()
-        dp = planlib.upload(planlib.build_row_plan(u, v, y.cpu().numpy(), self.model.user_num, self.model.item_num,
-                                                   factor_num=self.model.factor_num, env_num=0), self.device)
+        dp = self._batch_plan(u, v, y.cpu().numpy())
         st = self.state
         st.losses6.zero_()
         st.step += 1
         self._sched_synced = False
-        ops.mstep_rows_adam(st.p_views, st.p_views_alt, st.m_views, st.v_views, dp, None, y.to(self.device), weights,
-                            len(u), self._coefs(0.), flags, st.losses6, st.step, self.lr, self.workspace,
-                            pure=True)
-        st.swap()
+        if term is None:
+            ops.mstep_rows_adam(st.p_views, st.p_views_alt, st.m_views, st.v_views, dp, None, y.to(self.device), weights,
+                                len(u), self._coefs(0.), flags, st.losses6, st.step, self.lr, self.workspace,
+                                pure=True)
+            st.swap()
+        else:
+            ops.mstep_rows_grad(st.p_views, st.g_views, dp, None, y.to(self.device), weights, len(u), self._coefs(0.), flags,
+                                st.losses6, self.workspace)
+            term()
+            self._grad_stale = True     # (the planned pass overwrote every row: nothing to zero, see _step())
+            for o, ln in self._adam_ranges:
+                ops.adam_(st.param[o:o + ln], st.grad[o:o + ln], st.exp_avg[o:o + ln], st.exp_avg_sq[o:o + ln], st.step,
+                          self.lr, zero_grad=False)
         return self.loss_dicts(st.losses6[None])[0]
 
     def train(self, silent: bool = False, auto: bool = False):
-        """train.py:428-461: ((loss dicts, epochs), (test results, epochs))."""
-        test_result_list, test_epoch_list, loss_result_list, train_epoch_index_list = [], [], [], []
-        defer = bool(silent or auto)
-        # deferred: an evaluator with evaluate_async enqueues, and its results are read back at the end with the losses
-        evaluate_async = getattr(self.evaluator, 'evaluate_async', None) if defer else None
-
-        def evaluate():
-            self.sync_parameters()
-            res = evaluate_async() if evaluate_async is not None else self.evaluator.evaluate()
-            test_result_list.append(res)
-            test_epoch_list.append(self.epoch_cnt)
-            if not silent and not auto:
-                print('test at epoch:', self.epoch_cnt)
-                print(transfer_loss_dict_to_line_str(res))
-
-        evaluate()
-        while self.epoch_cnt < self.epochs:
-            first = self.epoch_cnt + 1
-            run = self.train_epochs(self._epochs_to_next_event(), sync=not defer)
-            for i in range(len(run)):
-                train_epoch_index_list.append(first + i)
-                loss_result_list.append(run[i])
-                if not defer:
-                    print('train epoch:', first + i)
-                    print(transfer_loss_dict_to_line_str(run[i]))
-            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
-                evaluate()
-        self.sync_parameters()
-        self._check_alt_error()   # (PureMF launches wait for nothing inside a launch: the word can only be set by another user of the workspace)
-        if defer and loss_result_list:
-            loss_result_list = self.loss_dicts(torch.stack(loss_result_list))
-        if evaluate_async is not None:
-            test_result_list = [p.result() for p in test_result_list]
-        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
+        """train.py:428-461: ((loss dicts, epochs), (test results, epochs)) of the engine's outer loop."""
+        return self._train_span(silent, auto, initial=True)[:2]
 
     # the InvPref-only parts of the engine do not exist here
     def cluster(self, *a, **k):
@@ -568,41 +496,123 @@ class ExpoMFTrainManager(BasicImplicitTrainManager):
             w = ops.exposure_weights(sP, sQ, u, v, pos, smu, self.lam_y, self.eps, self.expo_weight_exp)
         return self._batch_step(u, v, batch_scores_tensor, w)
 
-    def train(self, silent: bool = False, auto: bool = False):
-        """baseline_train.py:118-154: ((loss dicts, epochs), (test results, epochs)).  One-epoch runs (graph replays; the
-        alternating form flushes at the end of each, so the tables are consistent between runs): the weight refresh is
-        enqueued before the due epochs, the prior update after every run.  silent / auto: no per-epoch host sync."""
-        test_result_list, test_epoch_list, loss_result_list, train_epoch_index_list = [], [], [], []
-        defer = bool(silent or auto)
-        evaluate_async = getattr(self.evaluator, 'evaluate_async', None) if defer else None
+    # baseline_train.py:118-154 on the engine's outer loop: one-epoch runs (graph replays; the alternating form flushes at the
+    # end of each, so the tables are consistent between runs), the weight refresh enqueued before the due epochs, the prior
+    # update after every run.  silent / auto: no per-epoch host sync.
+    def _epochs_to_next_event(self) -> int:
+        return 1
 
-        def evaluate():
-            res = evaluate_async() if evaluate_async is not None else self.evaluator.evaluate()
-            test_result_list.append(res)
-            test_epoch_list.append(self.epoch_cnt)
-            if not silent and not auto:
-                print('test at epoch:', self.epoch_cnt)
-                print(transfer_loss_dict_to_line_str(res))
+    def _before_run(self) -> None:
+        if self.epoch_cnt % self.upd_expo_interval == 0:
+            self.calculate_exposure_probability()
 
-        evaluate()
-        while self.epoch_cnt < self.epochs:
-            if self.epoch_cnt % self.upd_expo_interval == 0:
-                self.calculate_exposure_probability()
-            run = self.train_epochs(1, sync=not defer)
-            self.upd_mu()
-            train_epoch_index_list.append(self.epoch_cnt)
-            loss_result_list.append(run[0])
-            if not defer:
-                print('train epoch:', self.epoch_cnt)
-                print(transfer_loss_dict_to_line_str(run[0]))
-            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
-                evaluate()
-        self._check_alt_error()
-        if defer and loss_result_list:
-            loss_result_list = self.loss_dicts(torch.stack(loss_result_list))
-        if evaluate_async is not None:
-            test_result_list = [p.result() for p in test_result_list]
-        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
+    def _after_run(self) -> None:
+        self.upd_mu()
+
+
+# ------------------------------------------------------------------------------------------------ drawn terms
+class _DrawnTermMixin:
+    """A PureMF step with one further loss term over ids DRAWN per step on the host (the WMF and CVIB managers below), in
+    front of a _BasicTrainManager.  The step is the engine's unfused sequence with one call between the gradient pass and
+    Adam: planned PureMF gradient pass -> the term (adds into the same gradient buffer and into the step's `loss`) -> dense /
+    ranged Adam.  Single process.
+
+    A draw is a pair of id arrays.  The minibatches are static, so what every step draws from is listed once (_draw_specs);
+    before a run of epochs is enqueued every step's draw is made on the host in the reference's order and the run's draws go
+    to the device in one stream-ordered copy into ONE int32 buffer, row = the step's position in the run.  The launches read
+    their row when they run, so a captured run of epochs is replayed with new draws without re-capture.
+
+    The draw source replaces numpy's global generator: a callable taking _draw_default's arguments, called once per step in
+    order, or an iterable of pairs consumed in that order (recorded draws).
+
+    A manager supplies: _SINGLE and _WHAT (the error texts), _draw_default, _draw_specs, _row_layout, _term(), and, where the
+    staged rows need a pass of their own on the device, _limit_run() / _staging_resized() / _after_staging()."""
+    _SINGLE = None                  # why the manager runs in a single process
+    _WHAT = None                    # what a draw is called in the size check's error
+    _draw_default = None            # staticmethod: one step's draw from numpy's global generator
+
+    def _require_single_process(self, world_size) -> None:
+        """called with the constructor's argument before the engine is built, and with the resolved size after"""
+        if world_size is not None and int(world_size) > 1:
+            raise NotImplementedError(self._SINGLE)
+
+    def _init_draws(self, source, specs, second_at: int, width: int) -> None:
+        """source: the constructor's keyword; specs: per static minibatch (the arguments of its draw, the lengths (first,
+        second) a draw of it must have); second_at / width: a staging row holds the first array from 0 and the second from
+        second_at, zero-padded to width"""
+        self._require_single_process(self.world_size)
+        self._unfused = True        # always gradient pass -> _after_gradient_pass -> Adam (never the fused / alternating step)
+        self._draw_source = source
+        self._draw_iter = iter(source) if source is not None and not callable(source) else None
+        self._draw_specs, self._row_layout = specs, (second_at, width)
+        self._queue = []            # drawn, not yet consumed: whole epochs of pairs in step order
+        self._staged = None         # device int32 [steps of the longest run, width]
+
+    def _draw(self, args, want):
+        if self._draw_source is None:
+            a, b = self._draw_default(*args)
+        elif self._draw_iter is not None:
+            a, b = next(self._draw_iter)
+        else:
+            a, b = self._draw_source(*args)
+        a, b = np.asarray(a).reshape(-1), np.asarray(b).reshape(-1)
+        if (len(a), len(b)) != want:
+            raise ValueError(f'a {self._WHAT} of {len(a)} and {len(b)} ids where the step takes {want[0]} and {want[1]}')
+        return a.astype(np.int32), b.astype(np.int32)
+
+    def _limit_run(self) -> None:
+        """may lower self._graph_epochs before the staging buffer is sized for it"""
+
+    def _staging_resized(self, rows: int) -> None:
+        """the staging buffer was (re)allocated with `rows` rows: size what goes with it"""
+
+    def _after_staging(self, steps: int) -> None:
+        """enqueued behind the copy of a run's first `steps` rows"""
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        self._limit_run()
+        rows = self._graph_epochs * self.batch_num
+        if self._staged is None or self._staged.shape[0] != rows:
+            self._staged = torch.zeros(rows, self._row_layout[1], dtype=torch.int32, device=self.device)
+            self._staging_resized(rows)
+
+    def _stage_draws(self, n: int):
+        """the draws of the next n epochs: made (those not yet made), laid out one row per step, one copy"""
+        steps = n * self.batch_num
+        while len(self._queue) < steps:
+            self._queue.extend(self._draw(args, want) for args, want in self._draw_specs)
+        at, width = self._row_layout
+        host = np.zeros((steps, width), np.int32)
+        for s in range(steps):
+            a, b = self._queue[s]
+            host[s, :len(a)] = a
+            host[s, at:at + len(b)] = b
+        src = torch.from_numpy(host)
+        if self._staged.is_cuda:
+            src = src.pin_memory()
+        self._staged[:steps].copy_(src, non_blocking=True)
+        self._after_staging(steps)
+
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        n = min(want, self._graph_epochs) if (self.graphs_enabled() and self._graph_warm) else 1
+        self._stage_draws(n)
+        before = self.epoch_cnt
+        out = super()._enqueue_epochs(want)
+        del self._queue[:(self.epoch_cnt - before) * self.batch_num]   # (a failed capture runs one eager epoch of the n)
+        return out
+
+    def prepare_graphs(self, run_lengths) -> None:
+        if self._staged is None:
+            raise RuntimeError('prepare_graphs(): run one epoch first (train_epochs(1))')
+        super().prepare_graphs(run_lengths)
+
+    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
+        self._term(k, self._loss_slot * self.batch_num + k, losses6[5:6])
+
+    def _term(self, k: int, s: int, loss: torch.Tensor) -> None:
+        """the term of static minibatch k from staging row s: gradient into state.g_views, value added into loss"""
+        raise NotImplementedError
 
 
 # ------------------------------------------------------------------------------------------------ WMF
@@ -629,23 +639,21 @@ def wmf_draw_epochs(distinct: list, user_batch_size: int, item_batch_size: int, 
     return [wmf_draw(uu, ui, user_batch_size, item_batch_size) for _ in range(epochs) for uu, ui in distinct]
 
 
-class WMFTrainManager(BasicImplicitTrainManager):
+class WMFTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
     """reference baseline_train.py:157-228: the PureMF step plus imputation_coe * BCE(sigmoid(Pu[a] . Qi[b]), 0) averaged over
     a block Su x Si drawn per step from the minibatch's distinct users and items (target 0, as the reference's `zero_tensor`
     is named -- the reference allocates it uninitialised).
 
-    The step is the engine's unfused sequence with one call between the gradient pass and Adam: planned PureMF gradient
-    pass -> torch.ops.invpref.impute_grad_ (csrc/invpref_impute.hip: adds into the same gradient buffer and into the step's
-    `loss`) -> dense / ranged Adam.  Nothing of the block is materialised.
+    The term is torch.ops.invpref.impute_grad_ (csrc/invpref_impute.hip) on the drawn-term step of _DrawnTermMixin; nothing of
+    the block is materialised.  A step's draw: two np.random.shuffle permutations of the minibatch's distinct users and items
+    (listed once), users first, each cut to its batch size.
 
-    The draws: the minibatches are static, so their distinct ids are listed once; before a run of epochs is enqueued every
-    step's two permutations are drawn on the host with np.random.shuffle in the reference's order and the run's selections
-    go to the device in one stream-ordered copy into ONE int32 buffer, row = the step's position in the run.  The launches
-    read their row when they run, so a captured run of epochs is replayed with new selections without re-capture.
-
-    selections= (keyword-only) replaces numpy's global generator: a callable (uu, ui, user_batch_size, item_batch_size) ->
-    (Su, Si) called once per step in order, or an iterable of (Su, Si) pairs consumed in that order (recorded draws).  A
-    step's Su / Si must hold min(distinct, batch size) ids of the minibatch."""
+    selections= (keyword-only) is the mixin's draw source: a callable (uu, ui, user_batch_size, item_batch_size) -> (Su, Si),
+    or an iterable of (Su, Si) pairs.  A step's Su / Si must hold min(distinct, batch size) ids of the minibatch."""
+    _SINGLE = 'WMF runs in a single process (a sharded form would all-reduce the summed gradient before the imputation ' \
+              'term is added; not implemented)'
+    _WHAT = 'selection'
+    _draw_default = staticmethod(wmf_draw)
 
     def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
                  evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
@@ -653,104 +661,42 @@ class WMFTrainManager(BasicImplicitTrainManager):
                  rank=None, world_size=None, process_group=None):
         if int(user_batch_size) < 1 or int(item_batch_size) < 1:
             raise ValueError('user_batch_size and item_batch_size must be at least 1')
-        single = 'WMF runs in a single process (a sharded form would all-reduce the summed gradient before the imputation ' \
-                 'term is added; not implemented)'
-        if world_size is not None and int(world_size) > 1:
-            raise NotImplementedError(single)
+        self._require_single_process(world_size)
         super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
-        if self.world_size > 1:
-            raise NotImplementedError(single)
         self.imputation_coe = float(imputation_coe)
         self.user_batch_size, self.item_batch_size = int(user_batch_size), int(item_batch_size)
-        self._unfused = True        # always gradient pass -> _after_gradient_pass -> Adam (never the fused / alternating step)
-        self._distinct = wmf_distinct(self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy(), batch_size)
-        self._counts = [(min(len(uu), self.user_batch_size), min(len(ui), self.item_batch_size)) for uu, ui in self._distinct]
+        distinct = wmf_distinct(self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy(), batch_size)
+        self._counts = [self._count(uu, ui) for uu, ui in distinct]
         self._cap_u = max(c[0] for c in self._counts)
         self._cap_i = max(c[1] for c in self._counts)
-        self._selections = selections
-        self._sel_iter = iter(selections) if selections is not None and not callable(selections) else None
-        self._queue = []            # drawn, not yet consumed: whole epochs of (Su, Si) in step order
-        self._sel = None            # device int32 [steps of the longest run, cap_u + cap_i]
+        self._init_draws(selections, [((uu, ui, self.user_batch_size, self.item_batch_size), c)
+                                      for (uu, ui), c in zip(distinct, self._counts)], self._cap_u, self._cap_u + self._cap_i)
         self._imp_ws = ops.Workspace(self.device)
         self._imp_ws.get(max(ops.impute_workspace_bytes(max(self._cap_u, self.user_batch_size), self._cap_i,
                                                         model.factor_num), 8))   # sized once: capturable launches
 
-    def _draw(self, uu, ui):
-        if self._selections is None:
-            su, si = wmf_draw(uu, ui, self.user_batch_size, self.item_batch_size)
-        elif self._sel_iter is not None:
-            su, si = next(self._sel_iter)
-        else:
-            su, si = self._selections(uu, ui, self.user_batch_size, self.item_batch_size)
-        su, si = np.asarray(su).reshape(-1), np.asarray(si).reshape(-1)
-        want = (min(len(uu), self.user_batch_size), min(len(ui), self.item_batch_size))
-        if (len(su), len(si)) != want:
-            raise ValueError(f'a selection of {len(su)} users x {len(si)} items where the step takes {want[0]} x {want[1]}')
-        return su.astype(np.int32), si.astype(np.int32)
+    def _count(self, uu, ui):
+        return min(len(uu), self.user_batch_size), min(len(ui), self.item_batch_size)
 
-    def _raw_setup(self):
-        super()._raw_setup()
-        rows = self._graph_epochs * self.batch_num
-        if self._sel is None or self._sel.shape[0] != rows:
-            self._sel = torch.zeros(rows, self._cap_u + self._cap_i, dtype=torch.int32, device=self.device)
-
-    def _stage_selections(self, n: int):
-        """the selections of the next n epochs: drawn (those not yet drawn), laid out one row per step, one copy"""
-        while len(self._queue) < n * self.batch_num:
-            self._queue.extend(self._draw(uu, ui) for uu, ui in self._distinct)
-        host = np.zeros((n * self.batch_num, self._cap_u + self._cap_i), np.int32)
-        for s in range(n * self.batch_num):
-            su, si = self._queue[s]
-            host[s, :len(su)] = su
-            host[s, self._cap_u:self._cap_u + len(si)] = si
-        src = torch.from_numpy(host)
-        if self._sel.is_cuda:
-            src = src.pin_memory()
-        self._sel[:len(host)].copy_(src, non_blocking=True)
-
-    def _enqueue_epochs(self, want: int) -> torch.Tensor:
-        n = min(want, self._graph_epochs) if (self.graphs_enabled() and self._graph_warm) else 1
-        self._stage_selections(n)
-        before = self.epoch_cnt
-        out = super()._enqueue_epochs(want)
-        del self._queue[:(self.epoch_cnt - before) * self.batch_num]   # (a failed capture runs one eager epoch of the n)
-        return out
-
-    def prepare_graphs(self, run_lengths) -> None:
-        if self._sel is None:
-            raise RuntimeError('prepare_graphs(): run one epoch first (train_epochs(1))')
-        super().prepare_graphs(run_lengths)
-
-    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
+    def _impute(self, su, si, loss):
         st = self.state
-        row = self._sel[self._loss_slot * self.batch_num + k]
+        ops.impute_grad_(st.p_views[0], st.p_views[1], su, si, self.imputation_coe, st.g_views[0], st.g_views[1], loss, None,
+                         self._imp_ws)
+
+    def _term(self, k: int, s: int, loss: torch.Tensor) -> None:
+        row = self._staged[s]
         nu, ni = self._counts[k]
-        ops.impute_grad_(st.p_views[0], st.p_views[1], row[:nu], row[self._cap_u:self._cap_u + ni], self.imputation_coe,
-                         st.g_views[0], st.g_views[1], losses6[5:6], None, self._imp_ws)
+        self._impute(row[:nu], row[self._cap_u:self._cap_u + ni], loss)
 
     def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
         """baseline_train.py:179-228 on caller tensors: the distinct ids of THIS batch, two draws, one step."""
         u = batch_users_tensor.detach().cpu().numpy().reshape(-1)
         v = batch_items_tensor.detach().cpu().numpy().reshape(-1)
-        y = batch_scores_tensor.detach().float().contiguous()
-        su, si = self._draw(np.unique(u), np.unique(v))
-        dp = planlib.upload(planlib.build_row_plan(u, v, y.cpu().numpy(), self.model.user_num, self.model.item_num,
-                                                   factor_num=self.model.factor_num, env_num=0), self.device)
-        st = self.state
-        st.losses6.zero_()
-        st.step += 1
-        self._sched_synced = False
-        ops.mstep_rows_grad(st.p_views, st.g_views, dp, None, y.to(self.device), None, len(u), self._coefs(0.),
-                            self._flags & ~_capi.REWEIGHT_REC, st.losses6, self.workspace)
-        ops.impute_grad_(st.p_views[0], st.p_views[1], torch.from_numpy(su).to(self.device),
-                         torch.from_numpy(si).to(self.device), self.imputation_coe, st.g_views[0], st.g_views[1],
-                         st.losses6[5:6], None, self._imp_ws)
-        self._grad_stale = True     # (the planned pass overwrote every row: nothing to zero, see _step())
-        for o, ln in getattr(self, '_adam_ranges', [(0, st.n)]):
-            ops.adam_(st.param[o:o + ln], st.grad[o:o + ln], st.exp_avg[o:o + ln], st.exp_avg_sq[o:o + ln], st.step, self.lr,
-                      zero_grad=False)
-        return self.loss_dicts(st.losses6[None])[0]
+        uu, ui = np.unique(u), np.unique(v)
+        su, si = self._draw((uu, ui, self.user_batch_size, self.item_batch_size), self._count(uu, ui))
+        return self._batch_step(u, v, batch_scores_tensor, None, lambda: self._impute(
+            torch.from_numpy(su).to(self.device), torch.from_numpy(si).to(self.device), self.state.losses6[5:6]))
 
 
 # ------------------------------------------------------------------------------------------------ CVIB-MF
@@ -768,101 +714,55 @@ def cvib_draw_epochs(user_num: int, item_num: int, batch_lens, epochs: int) -> l
     return [cvib_draw(user_num, item_num, n) for _ in range(epochs) for n in batch_lens]
 
 
-class _CVIBMixin:
+class _CVIBMixin(_DrawnTermMixin):
     """CVIBTrainManager / CVIBExplicitTrainManager (baseline_train.py:584-647, :978-1044): the PureMF step plus
     info_coe * info, info = alpha * (-pbar log qbar - (1 - pbar) log(1 - qbar)) + gamma * mean(p log p), p the predictions at
     the minibatch's pairs, qbar the mean prediction at as many uniformly drawn (user, item) pairs (the explicit form clips the
     logarithms' arguments at eps).  `info` is visible inside 'loss' only.
 
-    The step is the engine's unfused sequence with one call between the gradient pass and Adam: planned PureMF gradient pass ->
-    torch.ops.invpref.cvib_grad_ (csrc/invpref_cvib.hip: means, fold, scatter, boundary; adds into the same gradient buffer
-    and into the step's `loss`) -> dense / ranged Adam.
+    The term is torch.ops.invpref.cvib_grad_ (csrc/invpref_cvib.hip: means, fold, scatter, boundary) on the drawn-term step of
+    _DrawnTermMixin.  A step's draw: np.random.randint, users then items, B = the minibatch's rows.  Behind the copy of a
+    run's draws they are indexed on the device in one batched pass (ops.cvib_index: destination row -> pair positions of the
+    minibatch and drawn pairs together); the captured launches read their row of both buffers when they run.
 
-    The draws: before a run of epochs is enqueued every step's pairs are drawn on the host in the reference's order
-    (np.random.randint, users then items, B = the minibatch's rows), copied to the device once into ONE int32 buffer (row = the
-    step's position in the run) and indexed there in one batched pass (ops.cvib_index: destination row -> pair positions of
-    the minibatch and drawn pairs together).  The captured launches read their row of both buffers when they run, so a
-    captured run of epochs is replayed with new draws without re-capture.
-
-    draws= (keyword-only) replaces numpy's global generator: a callable (user_num, item_num, n) -> (ru, rv) called once per
-    step in order, or an iterable of (ru, rv) pairs consumed in that order (recorded draws)."""
+    draws= (keyword-only) is the mixin's draw source: a callable (user_num, item_num, n) -> (ru, rv), or an iterable of
+    (ru, rv) pairs."""
+    _SINGLE = 'CVIB runs in a single process (a sharded form would all-reduce the two means and the summed gradient; ' \
+              'not implemented)'
+    _WHAT = 'draw'
+    _draw_default = staticmethod(cvib_draw)
     # bytes of the run's index: longer runs are replayed as several shorter graphs.  Building it takes four to five times as
     # much for a moment (keys, sorted keys, the sort's permutation and temporaries: ops.cvib_index), freed before the run starts
     _INDEX_BUDGET = 512 << 20
 
     def _cvib_init(self, alpha, gamma, info_coe, eps, draws):
-        if self.world_size > 1:
-            raise NotImplementedError(_CVIB_SINGLE)
         # (the engine's `alpha` is InvPref's environment weight, which a PureMF step never reads: the attribute is CVIB's here,
         #  as in the reference)
         self.alpha, self.gamma, self.info_coe, self.eps = float(alpha), float(gamma), float(info_coe), float(eps)
-        self._unfused = True        # always gradient pass -> _after_gradient_pass -> Adam (never the fused / alternating step)
         n, bs = self.n_total, self.batch_size
         self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]
         self._cap = max(self._batch_lens)
-        self._draw_source = draws
-        self._draw_iter = iter(draws) if draws is not None and not callable(draws) else None
-        self._queue = []            # drawn, not yet consumed: whole epochs of (ru, rv) in step order
+        self._init_draws(draws, [((self.model.user_num, self.model.item_num, b), (b, b)) for b in self._batch_lens],
+                         self._cap, 2 * self._cap)
         self._draws = self._index = None
         self._cvib_ws = ops.Workspace(self.device)
         self._cvib_ws.get(max(ops.cvib_workspace_bytes(self._cap, self.model.factor_num), 16))   # sized once: capturable launches
 
-    def _draw(self, n: int):
-        if self._draw_source is None:
-            ru, rv = cvib_draw(self.model.user_num, self.model.item_num, n)
-        elif self._draw_iter is not None:
-            ru, rv = next(self._draw_iter)
-        else:
-            ru, rv = self._draw_source(self.model.user_num, self.model.item_num, n)
-        ru, rv = np.asarray(ru).reshape(-1), np.asarray(rv).reshape(-1)
-        if (len(ru), len(rv)) != (n, n):
-            raise ValueError(f'a draw of {len(ru)} users and {len(rv)} items where the step takes {n} pairs')
-        return ru.astype(np.int32), rv.astype(np.int32)
-
-    def _raw_setup(self):
-        super()._raw_setup()
+    def _limit_run(self) -> None:
         per_epoch = self.batch_num * self._cap * 32          # int32 (row, position) x two sides x 2 B entries per step
         self._graph_epochs = max(1, min(self._graph_epochs, self._INDEX_BUDGET // per_epoch))
-        rows = self._graph_epochs * self.batch_num
-        if self._draws is None or self._draws.shape[0] != rows:
-            dev = self.device
-            self._draws = torch.zeros(rows, 2, self._cap, dtype=torch.int32, device=dev)
-            self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
-            lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
-            self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
-            self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
 
-    def _stage_draws(self, n: int):
-        """the pairs of the next n epochs: drawn (those not yet drawn), laid out one row per step, one copy, one index pass"""
-        steps = n * self.batch_num
-        while len(self._queue) < steps:
-            self._queue.extend(self._draw(b) for b in self._batch_lens)
-        host = np.zeros((steps, 2, self._cap), np.int32)
-        for s in range(steps):
-            ru, rv = self._queue[s]
-            host[s, 0, :len(ru)] = ru
-            host[s, 1, :len(rv)] = rv
-        src = torch.from_numpy(host)
-        if self._draws.is_cuda:
-            src = src.pin_memory()
-        self._draws[:steps].copy_(src, non_blocking=True)
+    def _staging_resized(self, rows: int) -> None:
+        dev = self.device
+        self._draws = self._staged.view(rows, 2, self._cap)
+        self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
+        lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
+        self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
+        self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
+
+    def _after_staging(self, steps: int) -> None:
         ops.cvib_index(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._draws[:steps],
                        self.model.user_num, self.model.item_num, out=self._index[:steps])
-
-    def _enqueue_epochs(self, want: int) -> torch.Tensor:
-        if getattr(self, '_raw_ptrs', None) is None or self._draws is None:
-            self._raw_setup()
-        n = min(want, self._graph_epochs) if (self.graphs_enabled() and self._graph_warm) else 1
-        self._stage_draws(n)
-        before = self.epoch_cnt
-        out = super()._enqueue_epochs(want)
-        del self._queue[:(self.epoch_cnt - before) * self.batch_num]   # (a failed capture runs one eager epoch of the n)
-        return out
-
-    def prepare_graphs(self, run_lengths) -> None:
-        if self._draws is None:
-            raise RuntimeError('prepare_graphs(): run one epoch first (train_epochs(1))')
-        super().prepare_graphs(run_lengths)
 
     def _info_term(self, users, items, draw_users, draw_items, index, loss_slot):
         st = self.state
@@ -870,20 +770,16 @@ class _CVIBMixin:
                        self.gamma, self.info_coe, self.eps, st.g_views[0], st.g_views[1], loss_slot, None, None, None,
                        self._cvib_ws)
 
-    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
-        s = self._loss_slot * self.batch_num + k
-        n, bu, bi = self._raw_batches[k][1], self._raw_batches[k][3], self._raw_batches[k][4]
-        self._info_term(bu, bi, self._draws[s, 0, :n], self._draws[s, 1, :n], self._index[s], losses6[5:6])
+    def _term(self, k: int, s: int, loss: torch.Tensor) -> None:
+        b = self._raw_batches[k]
+        self._info_term(b.users, b.items, self._draws[s, 0, :b.n], self._draws[s, 1, :b.n], self._index[s], loss)
 
     def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
         """baseline_train.py:606-647 / :1002-1044 on caller tensors: as many drawn pairs as the batch has rows, one step."""
         u = batch_users_tensor.detach().cpu().numpy().reshape(-1)
         v = batch_items_tensor.detach().cpu().numpy().reshape(-1)
-        y = batch_scores_tensor.detach().float().contiguous()
-        ru, rv = self._draw(len(u))
+        ru, rv = self._draw((self.model.user_num, self.model.item_num, len(u)), (len(u), len(u)))
         dev = self.device
-        dp = planlib.upload(planlib.build_row_plan(u, v, y.cpu().numpy(), self.model.user_num, self.model.item_num,
-                                                   factor_num=self.model.factor_num, env_num=0), dev)
         ud = torch.from_numpy(np.ascontiguousarray(u, dtype=np.int64)).to(dev)
         vd = torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64)).to(dev)
         draws = torch.from_numpy(np.stack([ru, rv])[None]).to(dev)
@@ -891,22 +787,8 @@ class _CVIBMixin:
                                torch.full((1,), len(u), dtype=torch.int32, device=dev), draws, self.model.user_num,
                                self.model.item_num)
         self._cvib_ws.get(max(ops.cvib_workspace_bytes(len(u), self.model.factor_num), 16))
-        st = self.state
-        st.losses6.zero_()
-        st.step += 1
-        self._sched_synced = False
-        ops.mstep_rows_grad(st.p_views, st.g_views, dp, None, y.to(dev), None, len(u), self._coefs(0.),
-                            self._flags & ~_capi.REWEIGHT_REC, st.losses6, self.workspace)
-        self._info_term(ud, vd, draws[0, 0], draws[0, 1], index[0], st.losses6[5:6])
-        self._grad_stale = True     # (the planned pass overwrote every row: nothing to zero, see _step())
-        for o, ln in getattr(self, '_adam_ranges', [(0, st.n)]):
-            ops.adam_(st.param[o:o + ln], st.grad[o:o + ln], st.exp_avg[o:o + ln], st.exp_avg_sq[o:o + ln], st.step, self.lr,
-                      zero_grad=False)
-        return self.loss_dicts(st.losses6[None])[0]
-
-
-_CVIB_SINGLE = 'CVIB runs in a single process (a sharded form would all-reduce the two means and the summed gradient; ' \
-               'not implemented)'
+        return self._batch_step(u, v, batch_scores_tensor, None, lambda: self._info_term(
+            ud, vd, draws[0, 0], draws[0, 1], index[0], self.state.losses6[5:6]))
 
 
 class CVIBTrainManager(_CVIBMixin, BasicImplicitTrainManager):
@@ -916,8 +798,7 @@ class CVIBTrainManager(_CVIBMixin, BasicImplicitTrainManager):
                  evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
                  alpha: float = 0.1, gamma: float = 0.01, info_coe: float = 1.0, *, draws=None, rank=None, world_size=None,
                  process_group=None):
-        if world_size is not None and int(world_size) > 1:
-            raise NotImplementedError(_CVIB_SINGLE)
+        self._require_single_process(world_size)
         super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
         self._cvib_init(alpha, gamma, info_coe, 0.0, draws)
@@ -930,8 +811,7 @@ class CVIBExplicitTrainManager(_CVIBMixin, BasicExplicitTrainManager):
                  evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
                  alpha: float = 0.1, gamma: float = 0.01, info_coe: float = 1.0, eps: float = 1e-1, *, draws=None, rank=None,
                  world_size=None, process_group=None):
-        if world_size is not None and int(world_size) > 1:
-            raise NotImplementedError(_CVIB_SINGLE)
+        self._require_single_process(world_size)
         super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
         self._cvib_init(alpha, gamma, info_coe, eps, draws)

@@ -21,11 +21,13 @@ buffers reproduces the single-GPU gradient.
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import itertools
 import math
 import os
 import time
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -43,6 +45,20 @@ _ALIGN = 64  # floats; every table starts on a 256-byte boundary of the flat buf
 
 def transfer_loss_dict_to_line_str(d: dict) -> str:
     return ', '.join(f'{k}: {v}' for k, v in d.items())  # utils.py:254-260
+
+
+@contextlib.contextmanager
+def _gc_paused():
+    """No cyclic garbage collection inside a stream capture.  torch.cuda.graph no longer collects on entry, so a collection
+    that falls into the capture may run the destructor of an unrelated dead object that owns a graph, an event or pinned
+    memory: calls a capturing thread must not make (seen as an abort of the process).  It runs after the capture instead."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 class FlatState:
@@ -100,6 +116,18 @@ class FlatState:
         return [flat[o:o + int(np.prod(s))].view(s) for o, s in zip(self.offsets, self.shapes)]
 
 
+class RawBatch(NamedTuple):
+    """one static minibatch as the epochs' launches read it: views of this rank's resident arrays"""
+    lo: int                             # first local row
+    n: int                              # local rows
+    global_n: int                       # rows of the GLOBAL minibatch: the denominator of every mean()
+    users: torch.Tensor
+    items: torch.Tensor
+    scores: torch.Tensor
+    envs: Optional[torch.Tensor]        # None: PureMF
+    weights: Optional[torch.Tensor]     # InvPref: the slice of sample_weights; PureMF: _pure_weights() or None
+
+
 class _InvPrefTrainManager:
     implicit = True
     _pure = False                       # PureMF managers (baseline.py) reuse the epoch engine below
@@ -114,52 +142,21 @@ class _InvPrefTrainManager:
             use_recommend_re_weight: bool = True, *, rank: Optional[int] = None, world_size: Optional[int] = None,
             process_group=None,
     ):
-        if model.implicit != self.implicit:
-            raise TypeError(f'{type(self).__name__} needs an {"implicit" if self.implicit else "explicit"} model')
-        self.model = model
-        self.evaluator = evaluator
         self.envs_num: int = model.env_num
-        self.device = torch.device(device)
-        self.process_group = process_group
-        if world_size is None:
-            import torch.distributed as dist
-            world_size = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
-            rank = dist.get_rank(process_group) if world_size > 1 else 0
-        self.rank, self.world_size = int(rank or 0), int(world_size)
-
-        n_total = training_data.shape[0]
-        self.n_total = n_total
-        self.batch_size = batch_size
-        self.batch_num = math.ceil(n_total / batch_size)
-        # multi-GPU: the literal row split of SURVEY 8(e) / north_star by default (parallel.RowShard, parameters replicated);
-        # INVPREF_SHARD=users partitions the users instead (parallel.UserShard: only the item-side gradient is all-reduced;
-        # bench.py sets the variable)
-        # (testing aid INVPREF_FORCE_SHARDED_PATH=1: the sharded step sequence, either layout, on one rank)
-        forced = os.environ.get('INVPREF_FORCE_SHARDED_PATH', '0') == '1'
-        self.shard_mode = os.environ.get('INVPREF_SHARD', 'rows') if (self.world_size > 1 or forced) else 'rows'
-        if self.shard_mode not in ('users', 'rows'):
-            raise ValueError('INVPREF_SHARD must be "users" or "rows"')
-        if self.shard_mode == 'users':
-            self.shard = UserShard(training_data[:, 0].cpu().numpy(), n_total, batch_size, model.user_num, self.rank,
-                                   self.world_size)
-        else:
-            self.shard = RowShard(n_total, batch_size, self.rank, self.world_size)
-        rows = self.shard.local_rows().to(training_data.device)
-        td = training_data.index_select(0, rows) if self.world_size > 1 else training_data
-        # full tensors keep the reference attribute names; *_local are what the kernels read
-        self.users_tensor = td[:, 0].contiguous().to(self.device)
-        self.items_tensor = td[:, 1].contiguous().to(self.device)
-        self.scores_tensor = td[:, 2].float().contiguous().to(self.device)
+        self._init_engine(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                          test_begin_epoch, rank, world_size, process_group,
+                          flags=ops.flags_of(self.implicit, use_recommend_re_weight, use_class_re_weight,
+                                             model.reg_only_embed, model.reg_env_embed),
+                          # user-sharded: [Pu | Pa | Qi | Qa | Ev | W | b]: the replicated part (items + small tables) and the
+                          # loss tail form one contiguous range for the all-reduce, the owned user rows two ranges for Adam
+                          users_first=[0, 2, 1, 3, 4, 5, 6], env_switches=True)
         # initial environments: one numpy draw over ALL rows, like the reference (train.py:34),
         # then this rank keeps its rows -> identical to the single-GPU run for any world size
-        envs_all = torch.from_numpy(np.random.randint(0, self.envs_num, n_total).astype(np.int64))
-        self.envs = (envs_all.index_select(0, rows.cpu()) if self.world_size > 1 else envs_all).to(self.device)
+        envs_all = torch.from_numpy(np.random.randint(0, self.envs_num, self.n_total).astype(np.int64))
+        self.envs = (envs_all.index_select(0, self.shard.local_rows()) if self.world_size > 1 else envs_all).to(self.device)
 
-        self.cluster_interval, self.evaluate_interval, self.epochs = cluster_interval, evaluate_interval, epochs
-        self.lr = lr
+        self.cluster_interval = cluster_interval
         self.invariant_coe, self.env_aware_coe, self.env_coe = invariant_coe, env_aware_coe, env_coe
-        self.L2_coe, self.L1_coe = L2_coe, L1_coe
-        self.epoch_cnt = 0
         self.each_env_count = dict()
         if alpha is None:
             self.alpha, self.update_alpha = 0., True
@@ -177,15 +174,64 @@ class _InvPrefTrainManager:
         self._counts_dev = torch.zeros(self.envs_num, dtype=torch.int64, device=self.device)
         self._es = None              # ops.EstepState of the fused E-step (one GPU)
         self.class_weights = torch.zeros(self.envs_num, dtype=torch.float32, device=self.device)
-        self.test_begin_epoch = test_begin_epoch
         self.begin_cluster_epoch, self.stop_cluster_epoch = begin_cluster_epoch, stop_cluster_epoch
         self.cluster_use_random_sort = cluster_use_random_sort
         self._eps_base = np.array([1e-10 * (1e-1 ** i) for i in range(self.envs_num)], dtype=np.float32)
         self._eps_rows_cnt = math.factorial(self.envs_num)
 
+    def _init_engine(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                     evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int, rank, world_size,
+                     process_group, *, flags: int, users_first, env_switches: bool):
+        """What every manager's constructor does (the PureMF managers of baseline.py included): this rank's share of the
+        interactions, the flat state and the bookkeeping of the plan, graph, schedule and alternating machinery.
+        flags: the step's INVPREF_* flags on rank 0 (the dense regulariser is added once: the other ranks drop DENSE_REG);
+        users_first: the tables' placement in the flat buffers of a user-sharded run (None: as listed);
+        env_switches: honour INVPREF_NO_PLAN / INVPREF_UNFUSED (the PureMF managers always take the planned fused step)."""
+        if model.implicit != self.implicit:
+            raise TypeError(f'{type(self).__name__} needs an {"implicit" if self.implicit else "explicit"} model')
+        self.model = model
+        self.evaluator = evaluator
+        self.device = torch.device(device)
+        self.process_group = process_group
+        if world_size is None:
+            import torch.distributed as dist
+            world_size = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+            rank = dist.get_rank(process_group) if world_size > 1 else 0
+        self.rank, self.world_size = int(rank or 0), int(world_size)
+
+        n_total = training_data.shape[0]
+        self.n_total = n_total
+        self.batch_size = batch_size
+        self.batch_num = math.ceil(n_total / batch_size)
+        # multi-GPU: the literal row split of SURVEY 8(e) / north_star by default (parallel.RowShard, parameters replicated);
+        # INVPREF_SHARD=users partitions the users instead (parallel.UserShard: only the item-side gradient is all-reduced;
+        # bench.py sets the variable)
+        # (testing aid INVPREF_FORCE_SHARDED_PATH=1: the sharded step sequence -- gradient pass -> all-reduce -> stand-alone
+        #  Adam --, either layout, on one rank)
+        self._force_sharded_path = os.environ.get('INVPREF_FORCE_SHARDED_PATH', '0') == '1'
+        self.shard_mode = os.environ.get('INVPREF_SHARD', 'rows') if (self.world_size > 1 or self._force_sharded_path) else 'rows'
+        if self.shard_mode not in ('users', 'rows'):
+            raise ValueError('INVPREF_SHARD must be "users" or "rows"')
+        if self.shard_mode == 'users':
+            self.shard = UserShard(training_data[:, 0].cpu().numpy(), n_total, batch_size, model.user_num, self.rank,
+                                   self.world_size)
+        else:
+            self.shard = RowShard(n_total, batch_size, self.rank, self.world_size)
+        td = training_data
+        if self.world_size > 1:
+            td = training_data.index_select(0, self.shard.local_rows().to(training_data.device))
+        # the reference's attribute names, holding this rank's rows: what the kernels read
+        self.users_tensor = td[:, 0].contiguous().to(self.device)
+        self.items_tensor = td[:, 1].contiguous().to(self.device)
+        self.scores_tensor = td[:, 2].float().contiguous().to(self.device)
+
+        self.evaluate_interval, self.epochs = evaluate_interval, epochs
+        self.lr = lr
+        self.L2_coe, self.L1_coe = L2_coe, L1_coe
+        self.epoch_cnt = 0
+        self.test_begin_epoch = test_begin_epoch
+
         self.model.to(self.device)
-        # user-sharded: [Pu | Pa | Qi | Qa | Ev | W | b]: the replicated part (items + small tables) and the loss
-        # tail form one contiguous range for the all-reduce, the owned user rows two ranges for Adam
         # row-sharded exchange (INVPREF_EXCHANGE; bench.py sets it): "scatter" = reduce-scatter of the flat gradient, Adam on
         # this rank's 1/G slice of the flat buffers, all-gather of the new parameters (same bytes on the wire as the
         # all-reduce, the dense Adam stream cut G-fold); "allreduce" = SURVEY 8(e) as written: every rank reduces and updates everything; "packed" =
@@ -194,32 +240,28 @@ class _InvPrefTrainManager:
         self.exchange = os.environ.get('INVPREF_EXCHANGE', 'allreduce') if self.shard_mode == 'rows' else 'allreduce'
         if self.exchange not in ('scatter', 'allreduce', 'packed'):
             raise ValueError('INVPREF_EXCHANGE must be "scatter", "allreduce" or "packed"')
-        self.state = FlatState(model.tables(), self.device,
-                               order=[0, 2, 1, 3, 4, 5, 6] if self.shard_mode == 'users' else None,
+        self.state = FlatState(model.tables(), self.device, order=users_first if self.shard_mode == 'users' else None,
                                chunks=self.world_size if self.exchange == 'scatter' else 1)
         self._setup_ranges(model)
         if self.exchange == 'packed':
             self._setup_packed(training_data[:, 0], training_data[:, 1])
         self.workspace = ops.Workspace(self.device)
-        self._flags = ops.flags_of(self.implicit, use_recommend_re_weight, use_class_re_weight,
-                                   model.reg_only_embed, model.reg_env_embed, dense_reg=(self.rank == 0))
+        self._flags = flags if self.rank == 0 else flags & ~_capi.DENSE_REG
         # atomic-free planned M-step (plan.py) unless INVPREF_NO_PLAN=1 (then: float-atomic scatter-add, the path of
         # train_a_batch on minibatches without a plan -- the test hook that runs it for whole epochs)
-        self.use_plan = os.environ.get('INVPREF_NO_PLAN', '0') != '1'
+        self.use_plan = not (env_switches and os.environ.get('INVPREF_NO_PLAN', '0') == '1')
         # (measured, tools/kbench.py, planned fused step vs plan-free gradient + Adam: Yahoo class 19 vs 78 us,
         #  MovieLens class -- E = 8, D = 128, 65 536 interactions -- 110 vs 181 us, MIND class -- E = 16, D = 256,
         #  262 144 interactions -- 1.1 vs 1.66 ms: the plan wins everywhere, so it is the default for every shape)
         # INVPREF_UNFUSED=1: gradient pass + flat Adam kernel instead of the fused pass on one GPU (the sequence a sharded
         # rank runs, without the exchange); every row length takes the fused pass by default
-        self._unfused = self.use_plan and os.environ.get('INVPREF_UNFUSED', '') == '1'
+        self._unfused = env_switches and self.use_plan and os.environ.get('INVPREF_UNFUSED', '') == '1'
         self._plans = None
         self._batch_plans, self.planned_batch_steps = {}, 0   # train_a_batch on caller tensors: see _cached_batch_plan
         self._batch_plans_foreign = {}
         # runs of whole epochs as one HIP graph launch (single GPU, planned path); INVPREF_NO_GRAPH=1 disables (test hook:
         # the eager launches that sharded runs and single calls take, against the replay)
         self.use_graph = os.environ.get('INVPREF_NO_GRAPH', '0') != '1'
-        # testing aid: run the multi-GPU step sequence (gradient pass -> all-reduce -> stand-alone Adam) on one rank
-        self._force_sharded_path = os.environ.get('INVPREF_FORCE_SHARDED_PATH', '0') == '1'
         import torch.distributed as _dist
         self._collective_ok = _dist.is_available() and _dist.is_initialized()
         self._graphs, self._graph_warm = {}, False
@@ -474,13 +516,15 @@ class _InvPrefTrainManager:
                 return None
             hit = 1
         if hit == 1:                            # invert the scatter pattern once (host side)
-            hit = planlib.upload(planlib.build_row_plan(users.cpu().numpy(), items.cpu().numpy(),
-                                                        scores.float().cpu().numpy(), self.model.user_num,
-                                                        self.model.item_num, factor_num=self.model.factor_num,
-                                                        env_num=getattr(self.model, 'env_num', 0)),
-                                 self.device)
+            hit = self._batch_plan(users.cpu().numpy(), items.cpu().numpy(), scores.float().cpu().numpy())
             cache[key] = hit if resident else (hit, users.clone(), items.clone(), scores.float().clone())
         return hit
+
+    def _batch_plan(self, users: np.ndarray, items: np.ndarray, scores: np.ndarray):
+        """the row plan of ONE caller-supplied minibatch (host arrays), built and uploaded"""
+        return planlib.upload(planlib.build_row_plan(users, items, scores, self.model.user_num, self.model.item_num,
+                                                     factor_num=self.model.factor_num,
+                                                     env_num=getattr(self.model, 'env_num', 0)), self.device)
 
     # ---- the epoch loop: every per-minibatch argument (views of the resident interaction arrays, the row plan,
     #      the zero-initialised scratch) is prepared once; a step is one or two torch.ops.invpref.* calls
@@ -499,8 +543,8 @@ class _InvPrefTrainManager:
         for k in range(self.batch_num):
             lo, hi = self.shard.local_batch_bounds(k)
             v = (None, self._pure_weights(lo, hi)) if self._pure else (self.envs[lo:hi], self._sample_weights[lo:hi])
-            self._raw_batches.append((lo, hi - lo, self.shard.global_batch_len(k), self.users_tensor[lo:hi],
-                                      self.items_tensor[lo:hi], self.scores_tensor[lo:hi], v[0], v[1]))
+            self._raw_batches.append(RawBatch(lo, hi - lo, self.shard.global_batch_len(k), self.users_tensor[lo:hi],
+                                              self.items_tensor[lo:hi], self.scores_tensor[lo:hi], v[0], v[1]))
         if not hasattr(self, '_adam_ranges'):
             self._adam_ranges = [(0, st.n)]
         rg = self._adam_ranges
@@ -512,15 +556,16 @@ class _InvPrefTrainManager:
             y = self.scores_tensor.cpu().numpy()
             # every minibatch's plan in one call: parameters resolved per minibatch, the arrays built natively on a thread
             # pool (csrc/invpref_plan.cpp; plan.py's numpy builder, native=False, is the reference implementation)
-            offs = np.array([b[0] for b in self._raw_batches] + [self._raw_batches[-1][0] + self._raw_batches[-1][1]], np.int64)
-            contiguous = all(offs[k] + self._raw_batches[k][1] == offs[k + 1] for k in range(len(self._raw_batches)))
+            last = self._raw_batches[-1]
+            offs = np.array([b.lo for b in self._raw_batches] + [last.lo + last.n], np.int64)
+            contiguous = all(offs[k] + b.n == offs[k + 1] for k, b in enumerate(self._raw_batches))
             kw = dict(factor_num=self.model.factor_num, user_range=self.shard.user_range(self.model.user_num),
                       env_num=getattr(self.model, 'env_num', 0))
             if contiguous:
                 pls = planlib.build_row_plans(u, v, y, offs, self.model.user_num, self.model.item_num, **kw)
             else:
-                pls = [planlib.build_row_plan(u[lo:lo + n], v[lo:lo + n], y[lo:lo + n], self.model.user_num,
-                                              self.model.item_num, **kw) for lo, n, *_ in self._raw_batches]
+                pls = [planlib.build_row_plan(u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], y[b.lo:b.lo + b.n], self.model.user_num,
+                                              self.model.item_num, **kw) for b in self._raw_batches]
             self._plans = [planlib.upload(pl, self.device) for pl in pls]
             self.plan_build_s = time.perf_counter() - t0     # host-side, once per run (reported by bench.py)
         self._alt_setup()
@@ -543,7 +588,7 @@ class _InvPrefTrainManager:
         if not (self.use_plan and self._plans and self.users_tensor.is_cuda and self._fused_seq()
                 and os.environ.get('INVPREF_ALT', '1') == '1' and ops.alt_supported(st.p_views)):
             return
-        n_cap = max(b[1] for b in self._raw_batches)
+        n_cap = max(b.n for b in self._raw_batches)
         host = getattr(self, '_alt_host', None)
         if host is None:
             host = self._alt_host = (self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy(),
@@ -554,7 +599,7 @@ class _InvPrefTrainManager:
         # 250 interactions per item on average) the chains are tens of evaluations long and the two-launch form, whose item
         # side only SUMS contribution rows, is twice as fast (measured: 199 vs 101 us per step).  Decided on the first
         # minibatch's heaviest row; INVPREF_ALT_MAX_CHAIN overrides the bound (test hook: either form at one shape).
-        lo0, n0 = self._raw_batches[0][0], self._raw_batches[0][1]
+        lo0, n0 = self._raw_batches[0].lo, self._raw_batches[0].n
         heavy = max(int(np.bincount(host[0][lo0:lo0 + n0]).max(initial=0)), int(np.bincount(host[1][lo0:lo0 + n0]).max(initial=0)))
         if -(-heavy // 32) > int(os.environ.get('INVPREF_ALT_MAX_CHAIN', '6')):
             return
@@ -581,9 +626,9 @@ class _InvPrefTrainManager:
         if need:
             t0 = time.perf_counter()
             u, v, y = self._alt_host
-            rng = lambda k: None if k is None else (self._raw_batches[k][0], self._raw_batches[k][1])   # noqa: E731
+            rng = lambda k: None if k is None else (self._raw_batches[k].lo, self._raw_batches[k].n)   # noqa: E731
             if 'slots' not in A:   # group slots per round of either side's launches, from the first minibatch
-                lo, n0 = self._raw_batches[0][0], self._raw_batches[0][1]
+                lo, n0 = self._raw_batches[0].lo, self._raw_batches[0].n
                 A['slots'] = (planlib.alt_slots_for(u[lo:lo + n0], self.model.user_num, planlib.ALT_PER_SLICE),
                               planlib.alt_slots_for(v[lo:lo + n0], self.model.item_num, planlib.ALT_PER_SLICE))
             hps = planlib.build_alt_plans(u, v, y, [(rng(k), rng(kp), side) for kp, k, side in need], self.model.user_num,
@@ -613,20 +658,20 @@ class _InvPrefTrainManager:
             j, k = divmod(i, bn)
             self._loss_slot = j
             dp = self._alt_plan(k_prev, k, i & 1, tasks_prev)
-            lo, nloc, bnorm, bu, bi, by, be, bw = self._raw_batches[k]
+            b = self._raw_batches[k]
             alpha = self._alpha_for(k)
             st.step += 1
             sc = (self._sched['state'], self._sched['table'], st.step & 1) if sched else None
             lp = self._epoch_losses[(i - 1) // bn, (i - 1) % bn] if i else None
-            wts, flags = self._step_weights(bw)
-            ops.mstep_alt(st.p_views, st.m_views, st.v_views, dp, be, wts, bnorm,
-                          self._raw_batches[k_prev][2] if k_prev is not None else bnorm, self._coefs(alpha), flags, lp,
+            wts, flags = self._step_weights(b.weights)
+            ops.mstep_alt(st.p_views, st.m_views, st.v_views, dp, b.envs, wts, b.global_n,
+                          self._raw_batches[k_prev].global_n if k_prev is not None else b.global_n, self._coefs(alpha), flags, lp,
                           st.step, self.lr, A['ws'], i & 1, pure=self._pure, sched=sc)
             k_prev, tasks_prev = k, dp.n_tasks
         # the flush: the other side's rows take the last step's update, the last fold (in the LAST step's schedule slot)
         dp = self._alt_plan(k_prev, None, total & 1, tasks_prev)
         sc = (self._sched['state'], self._sched['table'], st.step & 1) if sched else None
-        bnorm = self._raw_batches[k_prev][2]
+        bnorm = self._raw_batches[k_prev].global_n
         ops.mstep_alt(st.p_views, st.m_views, st.v_views, dp, None, None, bnorm, bnorm, self._coefs(alpha), self._flags,
                       self._epoch_losses[(total - 1) // bn, (total - 1) % bn], st.step, self.lr, A['ws'], total & 1,
                       pure=self._pure, sched=sc)
@@ -653,7 +698,7 @@ class _InvPrefTrainManager:
         st = self.state
         if not sched:
             self._sched_synced = False
-        lo, n, bn, bu, bi, by, be, bw = self._raw_batches[k]
+        b = self._raw_batches[k]
         coefs = self._coefs(alpha)
         multi = self.world_size > 1 or self._force_sharded_path or self._unfused
         # every step's six loss terms go straight into the epoch's loss buffer (this rank's partial sums in a
@@ -663,9 +708,9 @@ class _InvPrefTrainManager:
             # fused M-step + Adam: one pass, gradient never stored, parameters ping-pong
             st.step += 1
             sc = (self._sched['state'], self._sched['table'], st.step & 1) if sched else None
-            wts, flags = self._step_weights(bw)
-            ops.mstep_rows_adam(st.p_views, st.p_views_alt, st.m_views, st.v_views, self._plans[k], be, by, wts, bn,
-                                coefs, flags, lp, st.step, self.lr, self.workspace, pure=self._pure, sched=sc,
+            wts, flags = self._step_weights(b.weights)
+            ops.mstep_rows_adam(st.p_views, st.p_views_alt, st.m_views, st.v_views, self._plans[k], b.envs, b.scores, wts,
+                                b.global_n, coefs, flags, lp, st.step, self.lr, self.workspace, pure=self._pure, sched=sc,
                                 mid_event=mid_event)   # (profiling: recorded between the step's two launches)
             st.swap()
             return
@@ -674,11 +719,12 @@ class _InvPrefTrainManager:
         # schedule, read by the gradient pass and moved on by the ranged Adam launch that ends the step
         sc = (self._sched['state'], self._sched['table'], st.step & 1) if sched else None
         if self.use_plan:
-            wts, flags = self._step_weights(bw)
-            ops.mstep_rows_grad(st.p_views, st.g_views, self._plans[k], be, by, wts, bn, coefs, flags, lp,
+            wts, flags = self._step_weights(b.weights)
+            ops.mstep_rows_grad(st.p_views, st.g_views, self._plans[k], b.envs, b.scores, wts, b.global_n, coefs, flags, lp,
                                 self.workspace, sched=sc)
         else:
-            ops.mstep_grad(st.p_views, st.g_views, bu, bi, be, by, bw, bn, coefs, self._flags, lp, self.workspace)
+            ops.mstep_grad(st.p_views, st.g_views, b.users, b.items, b.envs, b.scores, b.weights, b.global_n, coefs,
+                           self._flags, lp, self.workspace)
         if multi:
             if self.world_size > 1 or self._collective_ok:
                 self._exchange_gradient(k)   # all-reduce (whole or packed), or reduce-scatter (this rank keeps its slice of the sum)
@@ -704,7 +750,7 @@ class _InvPrefTrainManager:
     def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
         """Hook of the unfused sequence (gradient pass -> [exchange] -> HERE -> Adam), minibatch k of epoch slot
         self._loss_slot: a manager whose loss has a term the step does not know adds its gradient into state.g_views and its
-        value into losses6 (baseline.py: WMFTrainManager).  Nothing is launched here."""
+        value into losses6 (baseline.py: _DrawnTermMixin, the base of the WMF and CVIB managers).  Nothing is launched here."""
 
     def _alpha_for(self, k: int) -> float:
         if self.update_alpha:  # train.py:214-217
@@ -899,7 +945,7 @@ class _InvPrefTrainManager:
             g = torch.cuda.CUDAGraph()
             try:
                 # (thread-local capture mode: the RCCL watchdog thread of a process group may query events meanwhile)
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                with _gc_paused(), torch.cuda.graph(g, capture_error_mode='thread_local'):
                     self._issue_epochs(None, True, n)
             finally:
                 # capture records, it does not run: put the host-side bookkeeping back
@@ -937,6 +983,12 @@ class _InvPrefTrainManager:
                     self._estep_graph(self.cluster_use_random_sort)
                 if self._fused_seq():
                     self.state.swap()
+
+    def _before_run(self) -> None:
+        """Hook of the outer loop: enqueued in front of every run of epochs (baseline.py: ExpoMFTrainManager)."""
+
+    def _after_run(self) -> None:
+        """Hook of the outer loop: enqueued behind every run of epochs, before its records are taken."""
 
     def _epochs_to_next_event(self) -> int:
         """How many epochs train() may enqueue before the next evaluate / cluster / end of training."""
@@ -1121,7 +1173,7 @@ class _InvPrefTrainManager:
                 self._es.state[1] -= 1
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with _gc_paused(), torch.cuda.graph(g):
                 outs = run()
             ent = self._estep_graphs[key] = (g, eps_buf, outs)
         return ent
@@ -1220,7 +1272,8 @@ class _InvPrefTrainManager:
             temp_eval_result = evaluate()
             test_result_list.append(temp_eval_result)
             test_epoch_list.append(self.epoch_cnt)
-            self.stat_envs()
+            if not self._pure:
+                self.stat_envs()
             if not silent and not auto:
                 print('test at epoch:', self.epoch_cnt)
                 print(transfer_loss_dict_to_line_str(temp_eval_result))
@@ -1229,7 +1282,9 @@ class _InvPrefTrainManager:
             # the epochs up to the next evaluate/cluster event are enqueued together (one read-back);
             # the records and the printed lines are the same, in the same order, as one epoch at a time
             first = self.epoch_cnt + 1
+            self._before_run()
             run = self.train_epochs(self._epochs_to_next_event(), sync=not defer)
+            self._after_run()
             for i in range(len(run)):
                 train_epoch_index_list.append(first + i)
                 loss_result_list.append(run[i])
@@ -1268,8 +1323,7 @@ class _InvPrefTrainManager:
         self.sync_parameters()  # (user-sharded runs: every rank ends with the complete model)
         self._check_alt_error()
         if defer:  # one read-back for everything
-            loss_result_list = [dict(zip(LOSS_KEYS, v)) for v in torch.stack(loss_result_list).tolist()] \
-                if loss_result_list else []
+            loss_result_list = self.loss_dicts(torch.stack(loss_result_list)) if loss_result_list else []
             cluster_diff_num_list = [int(d.item()) if torch.is_tensor(d) else d for d in cluster_diff_num_list]
             envs_cnt_list = [{env: int(c) for env, c in enumerate(t.tolist() if torch.is_tensor(t) else t)}
                              for t in envs_cnt_list]
