@@ -768,7 +768,12 @@ class _InvPrefTrainManager:
     def _sched_prepare(self, steps_ahead: int):
         """Device-side schedule for graph replay (InvPrefAdamSchedule): one row per optimiser step with the Adam
         scalars and, under the alpha schedule of train.py:214-217, that step's alpha.  Called at an epoch
-        boundary: row j belongs to minibatch j % batch_num of epoch epoch_cnt + j // batch_num."""
+        boundary: row j belongs to minibatch j % batch_num of epoch epoch_cnt + j // batch_num.
+        A run of `steps_ahead` steps must fit into ONE table: the launch of a table's last step leaves its successor's
+        scalars as they are (the kernels' `idx < sched_n` guard), so a longer run would go on with stale ones."""
+        if steps_ahead > self._SCHED_N:
+            raise _capi.InvPrefError(f'a replayed run of {steps_ahead} optimiser steps does not fit into the device-side '
+                                     f'Adam schedule of {self._SCHED_N} rows (graphs_enabled() / _graph_epochs bound it)')
         st, L = self.state, _capi.lib()
         if self._sched is None:
             table = torch.zeros(self._SCHED_N, 8, dtype=torch.float32, device=self.device)

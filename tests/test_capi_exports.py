@@ -82,6 +82,50 @@ def test_argument_validation_without_a_device(lib):
     assert L.invpref_alt_workspace_bytes(C.byref(t), 8, 8) > L.invpref_alt_error_offset(C.byref(t), 8, 8) > 0
 
 
+@pytest.mark.parametrize('first_step', [1, 2, 999, 8193, 1_000_000])
+def test_adam_schedule_fill_rows(lib, first_step):
+    """invpref_adam_schedule_fill: row i holds the Adam scalars of step first_step + i as the eager entry points form them --
+    lr / (1 - beta1**t) and sqrt(1 - beta2**t) in double, rounded to float32 -- then a NaN alpha and a zero.  The C library's
+    pow and numpy's may differ in the last bit of the double, which can move the rounded float32 to its neighbour: the two
+    step-dependent scalars are held to one float32 spacing, the four constants exactly."""
+    import numpy as np
+    n, lr, beta1, beta2, eps = 64, 0.01, 0.9, 0.999, 1e-8
+    lib.invpref_adam_schedule_fill.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_double] * 4
+    lib.invpref_adam_schedule_fill.restype = C.c_int
+    guard = np.float32(-77.0)
+    host = np.full((n + 2, 8), guard, np.float32)           # a guard row in front of and behind the table
+    assert lib.invpref_adam_schedule_fill(host[1:].ctypes.data, first_step, n, lr, beta1, beta2, eps) == 0
+    assert (host[0] == guard).all() and (host[n + 1] == guard).all()
+    rows = host[1:n + 1]
+    t = np.arange(first_step, first_step + n, dtype=np.float64)
+    step_size = (lr / (1.0 - np.power(beta1, t))).astype(np.float32)
+    bc2_sqrt = np.sqrt(1.0 - np.power(beta2, t)).astype(np.float32)
+    assert (np.abs(rows[:, 0] - step_size) <= np.spacing(step_size)).all()
+    assert (np.abs(rows[:, 1] - bc2_sqrt) <= np.spacing(bc2_sqrt)).all()
+    assert (rows[:, 0] > 0).all() and (rows[:, 1] > 0).all() and (rows[:, 1] <= 1).all()
+    for col, want in ((2, 1.0 - beta1), (3, beta2), (4, 1.0 - beta2), (5, eps)):
+        np.testing.assert_array_equal(rows[:, col], np.full(n, np.float32(want)))
+    assert np.isnan(rows[:, 6]).all()
+    np.testing.assert_array_equal(rows[:, 7], np.zeros(n, np.float32))
+
+
+def test_adam_schedule_fill_edges(lib):
+    import numpy as np
+    lib.invpref_adam_schedule_fill.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_double] * 4
+    lib.invpref_adam_schedule_fill.restype = C.c_int
+    host = np.full((4, 8), -77.0, np.float32)
+    assert lib.invpref_adam_schedule_fill(host.ctypes.data, 5, 0, 0.01, 0.9, 0.999, 1e-8) == 0     # n = 0: nothing written
+    assert (host == np.float32(-77.0)).all()
+    assert lib.invpref_adam_schedule_fill(host.ctypes.data, 0, 4, 0.01, 0.9, 0.999, 1e-8) == -1    # steps are 1-based
+    assert lib.invpref_adam_schedule_fill(None, 1, 4, 0.01, 0.9, 0.999, 1e-8) == -1                # INVPREF_EINVAL
+    assert (host == np.float32(-77.0)).all()
+    # rows of consecutive tables agree where they overlap: a refill based at any step continues the one before it
+    a, b = np.zeros((8, 8), np.float32), np.zeros((8, 8), np.float32)
+    assert lib.invpref_adam_schedule_fill(a.ctypes.data, 100, 8, 0.01, 0.9, 0.999, 1e-8) == 0
+    assert lib.invpref_adam_schedule_fill(b.ctypes.data, 104, 8, 0.01, 0.9, 0.999, 1e-8) == 0
+    np.testing.assert_array_equal(a[4:, :6], b[:4, :6])
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_capi, '_lib', None)
     monkeypatch.setattr(_capi, 'LIB_PATH', '/nonexistent/libinvpref_hip.so')
