@@ -659,6 +659,33 @@ int invpref_cvib_grad_hip(const float *user_table, int64_t user_num, const float
                           float *info_out, float *pbar_out, float *qbar_out, void *workspace, size_t workspace_bytes,
                           void *stream);
 
+/* ---- fairness-MF item-popularity term (baseline_train.py:279-313; csrc/invpref_fairness.hip).  Per step, with u_a the
+ * minibatch's DISTINCT users (users, int32, 1 .. 2^24) and m_a their multiplicities in it (user_mult, int32), idx_j the step's
+ * n_draw item ids AS DRAWN, duplicates included (draw_items, int32, 1 .. 2^20), cnt the training rows per item (item_counts,
+ * int32 [item_num]) and tab the 1-D distance table (table, fp32 [table_len], tab[d] = (d / range) ** weight_smooth_coe):
+ *   R[a][j] = sigmoid(Pu[u_a] . Qi[idx_j]),   S[j][k] = tab[min(|cnt[idx_j] - cnt[idx_k]|, table_len - 1)],   T = R S,
+ *   term = (1 / batch) sum_a m_a sum_j R[a][j] T[a][j]                  (= trace(R S R^T) / batch over the minibatch's rows)
+ *   dX[a][j] = (2 fairness_coe m_a / batch) T[a][j] R[a][j] (1 - R[a][j])
+ *   grad_user[u_a] += sum_j dX[a][j] Qi[idx_j],   grad_item[i] += sum over the positions j of item i, in position order, of
+ *   sum_a dX[a][j] Pu[u_a].
+ * All four products run on the matrix cores in fp32.  Neither an item_num x item_num nor a [batch, item_num] array exists: S
+ * is formed from the counts and the table where it is consumed (the table in LDS up to INVPREF_FAIRNESS_TABLE_LDS entries,
+ * read from global memory beyond).  The gradients are ADDED into the touched rows only; every row has one writer and every sum a
+ * fixed order (T and the row sums in two levels): bitwise reproducible, no float atomics.  loss_out (may be NULL): *loss_out +=
+ * fairness_coe * term; term_out (may be NULL): *term_out = term.  An id outside its table is never used as an address: its
+ * row / positions are skipped and the term is NaN.  The id arrays are read on the device when the kernels run, so a captured
+ * launch sees whatever they hold at replay time.  Six launches, no allocation, no synchronisation.
+ * workspace (16-byte aligned): R and dX, fp32 [n_users up to 32][n_draw up to 16] each, the per-position item rows, fp32
+ * [ceil(n_users / 1024)][n_draw up to 16][factor_num], three int32 per position and one float64 loss partial per 32 x 256 block
+ * -- a function of (n_users, n_draw, factor_num) alone, non-decreasing in each; 0 for bad sizes. */
+#define INVPREF_FAIRNESS_TABLE_LDS 8192
+size_t invpref_fairness_workspace_bytes(int64_t n_users, int64_t n_draw, int64_t factor_num);
+int invpref_fairness_grad_hip(const float *user_table, int64_t user_num, const float *item_table, int64_t item_num,
+                              int64_t factor_num, const int32_t *users, const int32_t *user_mult, int64_t n_users,
+                              const int32_t *draw_items, int64_t n_draw, const int32_t *item_counts, const float *table,
+                              int64_t table_len, double fairness_coe, int64_t batch, float *grad_user, float *grad_item,
+                              float *loss_out, float *term_out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,10 @@
+"""InvPref (KDD 2022) and its PureMF baselines on hand-written HIP kernels for gfx950."""
+
+_FAIRNESS = ('FairnessMFTrainManager', 'fairness_item_table', 'fairness_draw', 'fairness_draw_epochs')
+
+
+def __getattr__(name):   # resolved on first use: importing the package loads neither torch nor the HIP library
+    if name in _FAIRNESS:
+        from . import baseline
+        return getattr(baseline, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

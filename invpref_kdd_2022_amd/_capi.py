@@ -36,12 +36,13 @@ EXPORTS = [
     'invpref_count_propensity_hip', 'invpref_naive_bayes_workspace_bytes', 'invpref_naive_bayes_propensity_hip',
     'invpref_snips_scale_hip', 'invpref_exposure_workspace_bytes', 'invpref_exposure_hip', 'invpref_exposure_weights_hip',
     'invpref_impute_workspace_bytes', 'invpref_impute_grad_hip', 'invpref_cvib_workspace_bytes', 'invpref_cvib_index_keys_hip',
-    'invpref_cvib_index_hip', 'invpref_cvib_grad_hip',
+    'invpref_cvib_index_hip', 'invpref_cvib_grad_hip', 'invpref_fairness_workspace_bytes', 'invpref_fairness_grad_hip',
 ]
 MAX_TOPK = 64          # k of the fused scan / k-pass / radix-select kernels and the 64-wide metric tables
 MAX_TOPK_WIDE = 1024   # INVPREF_MAX_TOPK_WIDE: the wide entry points (csrc/invpref_topk_wide.hip)
 PROPENSITY_ITEM, PROPENSITY_USER, PROPENSITY_PAIR = 0, 1, 2   # INVPREF_PROPENSITY_*: basic_{item,user,pair}_propensity_func
 MAX_LABELS = 256       # INVPREF_MAX_LABELS: distinct training labels of the naive-Bayes propensities
+FAIRNESS_TABLE_LDS = 8192   # INVPREF_FAIRNESS_TABLE_LDS: distance-table entries the fairness product keeps in LDS
 
 
 class InvPrefError(RuntimeError):
@@ -172,6 +173,10 @@ def lib():
         L.invpref_cvib_index_hip.argtypes = [vp, i64, i64, i64, i64, vp, vp]
         L.invpref_cvib_grad_hip.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, u32, f64, f64, f64, f64, vp, vp, vp,
                                             vp, vp, vp, vp, C.c_size_t, vp]
+        L.invpref_fairness_workspace_bytes.restype = C.c_size_t
+        L.invpref_fairness_workspace_bytes.argtypes = [i64, i64, i64]
+        L.invpref_fairness_grad_hip.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, i64, f64, i64, vp, vp, vp, vp, vp,
+                                                C.c_size_t, vp]
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')
         _lib = L

@@ -1,5 +1,5 @@
-"""PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF
-and CVIB-MF.
+"""PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF,
+CVIB-MF and fairness-MF.
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -517,7 +517,7 @@ class _DrawnTermMixin:
     Adam: planned PureMF gradient pass -> the term (adds into the same gradient buffer and into the step's `loss`) -> dense /
     ranged Adam.  Single process.
 
-    A draw is a pair of id arrays.  The minibatches are static, so what every step draws from is listed once (_draw_specs);
+    A draw is a pair of id arrays (one array under _ONE_ARRAY).  The minibatches are static, so what every step draws from is listed once (_draw_specs);
     before a run of epochs is enqueued every step's draw is made on the host in the reference's order and the run's draws go
     to the device in one stream-ordered copy into ONE int32 buffer, row = the step's position in the run.  The launches read
     their row when they run, so a captured run of epochs is replayed with new draws without re-capture.
@@ -530,6 +530,7 @@ class _DrawnTermMixin:
     _SINGLE = None                  # why the manager runs in a single process
     _WHAT = None                    # what a draw is called in the size check's error
     _draw_default = None            # staticmethod: one step's draw from numpy's global generator
+    _ONE_ARRAY = False              # a draw is ONE id array (the pair's second stays empty: lengths (n, 0))
 
     def _require_single_process(self, world_size) -> None:
         """called with the constructor's argument before the engine is built, and with the resolved size after"""
@@ -550,13 +551,16 @@ class _DrawnTermMixin:
 
     def _draw(self, args, want):
         if self._draw_source is None:
-            a, b = self._draw_default(*args)
+            d = self._draw_default(*args)
         elif self._draw_iter is not None:
-            a, b = next(self._draw_iter)
+            d = next(self._draw_iter)
         else:
-            a, b = self._draw_source(*args)
+            d = self._draw_source(*args)
+        a, b = (d, np.zeros(0, np.int32)) if self._ONE_ARRAY else d
         a, b = np.asarray(a).reshape(-1), np.asarray(b).reshape(-1)
         if (len(a), len(b)) != want:
+            if self._ONE_ARRAY:
+                raise ValueError(f'a {self._WHAT} of {len(a)} ids where the step takes {want[0]}')
             raise ValueError(f'a {self._WHAT} of {len(a)} and {len(b)} ids where the step takes {want[0]} and {want[1]}')
         return a.astype(np.int32), b.astype(np.int32)
 
@@ -815,3 +819,94 @@ class CVIBExplicitTrainManager(_CVIBMixin, BasicExplicitTrainManager):
         super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
         self._cvib_init(alpha, gamma, info_coe, eps, draws)
+
+
+# ------------------------------------------------------------------------------------------------ fairness-MF
+def fairness_item_table(items, item_num: int, weight_smooth_coe: float):
+    """(counts int32 [item_num], table float32 [range + 1]) of init_item_distance (baseline_train.py:251-277): the reference's
+    item_num x item_num matrix is a function of |cnt_x - cnt_y| alone, S[x][y] == table[|counts[x] - counts[y]|] bit for bit
+    (float64 (d / range) ** w, then float32; 0 ** 0 = 1 at w = 0).  counts = bincount(minlength=item_num): the reference's own
+    whenever the largest item id occurs in training (where it does not, the reference's draw indexes past its matrix and
+    raises).  Equal counts everywhere: ValueError (the reference divides 0 by 0)."""
+    items = np.asarray(items).reshape(-1).astype(np.int64)
+    if len(items) == 0 or items.min() < 0 or items.max() >= item_num:
+        raise ValueError(f'item ids must lie in [0, {item_num})')
+    counts = np.bincount(items, minlength=int(item_num))
+    span = int(counts.max() - counts.min())
+    if span == 0:
+        raise ValueError('every item has the same number of training rows: the distance |cnt_x - cnt_y| / (max - min) is 0 / 0')
+    table = ((np.arange(span + 1, dtype=np.float64) / float(span)) ** float(weight_smooth_coe)).astype(np.float32)
+    return counts.astype(np.int32), table
+
+
+def fairness_draw(item_num: int, n: int) -> np.ndarray:
+    """one step's drawn items (baseline_train.py:291): one np.random.randint call on numpy's GLOBAL generator, WITH
+    replacement.  Host only."""
+    return np.random.randint(0, item_num, size=n)
+
+
+def fairness_draw_epochs(item_num: int, n: int, batch_num: int, epochs: int) -> list:
+    """the draws of `epochs` whole epochs of batch_num steps in the reference's order: [idx, ...]"""
+    return [fairness_draw(item_num, n) for _ in range(epochs * batch_num)]
+
+
+class FairnessMFTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
+    """reference baseline_train.py:231-313: the PureMF step plus fairness_coe * trace(R S R^T) / B, R = the predictions of the
+    minibatch's users (one row per interaction) at item_batch_size items drawn per step with replacement, S the items'
+    popularity distance (|cnt_x - cnt_y| / (max cnt - min cnt)) ** weight_smooth_coe.  The term is visible inside 'loss' only.
+
+    The term is torch.ops.invpref.fairness_grad_ (csrc/invpref_fairness.hip) on the drawn-term step of _DrawnTermMixin.  Rows of
+    one user are identical, so a minibatch is its distinct users with their multiplicities (listed once per static minibatch);
+    S is never built: the kernel forms it from the per-item counts and the 1-D table of fairness_item_table().  Neither a
+    [B, item_num] prediction matrix nor an item_num x item_num matrix exists, on the device or the host.
+
+    draws= (keyword-only) is the mixin's draw source: a callable (item_num, n) -> ids, or an iterable of recorded draws."""
+    _SINGLE = 'fairness-MF runs in a single process (a sharded form would all-reduce the summed gradient before the fairness ' \
+              'term is added; not implemented)'
+    _WHAT = 'draw'
+    _ONE_ARRAY = True
+    _draw_default = staticmethod(fairness_draw)
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
+                 fairness_coe: float = 1.0, weight_smooth_coe: float = 1.0, item_batch_size: int = 1000, *, draws=None,
+                 rank=None, world_size=None, process_group=None):
+        if int(item_batch_size) < 1:
+            raise ValueError('item_batch_size must be at least 1')
+        self._require_single_process(world_size)
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        self.fairness_coe, self.weight_smooth_coe = float(fairness_coe), float(weight_smooth_coe)
+        self.item_batch_size = J = int(item_batch_size)
+        counts, table = fairness_item_table(self.items_tensor.cpu().numpy(), model.item_num, weight_smooth_coe)
+        self.item_counts = torch.from_numpy(counts).to(self.device)
+        self.item_distance_table = torch.from_numpy(table).to(self.device)
+        users = self.users_tensor.cpu().numpy().reshape(-1)
+        self._users = [self._distinct(users[lo:lo + batch_size]) for lo in range(0, len(users), batch_size)]
+        self._init_draws(draws, [((model.item_num, J), (J, 0))] * len(self._users), J, J)
+        self._fair_ws = ops.Workspace(self.device)
+        self._fair_ws.get(max(ops.fairness_workspace_bytes(max(len(u) for u, _, _ in self._users), J, model.factor_num),
+                              16))   # sized once: capturable launches
+
+    def _distinct(self, users: np.ndarray):
+        """(distinct users, their multiplicities, rows) of one minibatch, int32 on the device"""
+        uu, m = np.unique(users, return_counts=True)
+        return (torch.from_numpy(uu.astype(np.int32)).to(self.device), torch.from_numpy(m.astype(np.int32)).to(self.device),
+                len(users))
+
+    def _fairness(self, users, mult, rows, idx, loss):
+        st = self.state
+        ops.fairness_grad_(st.p_views[0], st.p_views[1], users, mult, idx, self.item_counts, self.item_distance_table,
+                           self.fairness_coe, rows, st.g_views[0], st.g_views[1], loss, None, self._fair_ws)
+
+    def _term(self, k: int, s: int, loss: torch.Tensor) -> None:
+        self._fairness(*self._users[k], self._staged[s], loss)
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """baseline_train.py:279-313 on caller tensors: the distinct users of THIS batch, one draw, one step."""
+        u = batch_users_tensor.detach().cpu().numpy().reshape(-1)
+        v = batch_items_tensor.detach().cpu().numpy().reshape(-1)
+        idx, _ = self._draw((self.model.item_num, self.item_batch_size), (self.item_batch_size, 0))
+        uu, m, rows = self._distinct(u)
+        return self._batch_step(u, v, batch_scores_tensor, None, lambda: self._fairness(
+            uu, m, rows, torch.from_numpy(idx).to(self.device), self.state.losses6[5:6]))

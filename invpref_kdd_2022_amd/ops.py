@@ -553,6 +553,33 @@ def impute_grad_(user_table: torch.Tensor, item_table: torch.Tensor, sel_users: 
                       term_out, ws)
 
 
+# ---- fairness-MF item-popularity term (baseline_train.py:279-313; csrc/invpref_fairness.hip)
+FAIRNESS_TABLE_LDS = _capi.FAIRNESS_TABLE_LDS   # distance tables longer than this are read from global memory
+
+
+def fairness_workspace_bytes(n_users: int, n_draw: int, factor_num: int) -> int:
+    """R and dX ([users x draw] fp32, padded to 32 x 16), the per-position item rows, the position index and the float64 loss
+    partials: a function of the sizes alone, non-decreasing in each"""
+    return int(_capi.lib().invpref_fairness_workspace_bytes(int(n_users), int(n_draw), int(factor_num)))
+
+
+def fairness_grad_(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, user_mult: torch.Tensor,
+                   draw_items: torch.Tensor, item_counts: torch.Tensor, table: torch.Tensor, fairness_coe: float, batch: int,
+                   grad_user: torch.Tensor, grad_item: torch.Tensor, loss_out: Optional[torch.Tensor] = None,
+                   term_out: Optional[torch.Tensor] = None, workspace: Optional[Workspace] = None) -> None:
+    """The fairness-MF term trace(R S R^T) / batch, R = sigmoid(Pu[minibatch users] Qi[draw_items]^T), S[j][k] =
+    table[|item_counts[draw_j] - item_counts[draw_k]|], given the minibatch's DISTINCT users with their multiplicities (int32)
+    and the step's item ids as drawn (int32, duplicates included): ADDS fairness_coe * d term into the touched rows of grad_user /
+    grad_item, adds fairness_coe * term to loss_out[0] and writes the plain term to term_out[0] (either may be None).  No
+    item x item or [batch, items] array is formed; bitwise reproducible; no host sync (graph-capturable once the workspace is
+    sized; a replay reads the id tensors' current contents)."""
+    _gpu(user_table, item_table, users, user_mult, draw_items, item_counts, table, grad_user, grad_item, loss_out, term_out)
+    ws = (workspace or Workspace(user_table.device)).get(
+        max(fairness_workspace_bytes(users.numel(), draw_items.numel(), user_table.shape[1]), 16))
+    _o().fairness_grad_(user_table, item_table, users, user_mult, draw_items, item_counts, table, float(fairness_coe),
+                        int(batch), grad_user, grad_item, loss_out, term_out, ws)
+
+
 # ---- CVIB information term (baseline_train.py:584-647, :978-1044; csrc/invpref_cvib.hip)
 def cvib_workspace_bytes(batch: int, factor_num: int) -> int:
     """record + two factors per pair + float64 partials + chunk slots of one step: a function of the sizes alone, non-decreasing in batch"""

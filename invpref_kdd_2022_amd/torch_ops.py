@@ -40,6 +40,8 @@ What replaces what in the reference:
 ``exposure_weights_``          ExpoMF's step weights ``prob ** e`` (1.0 at positives) at given pairs (baseline_train.py:88-99)
 ``impute_grad_``               WMF's imputation term over a block of users x items (baseline_train.py:204-216): adds its gradient
                                into the selection's rows and its value into the step's loss; no pair list
+``fairness_grad_``             the fairness-MF term trace(R S R^T) / B over a step's drawn items (baseline_train.py:291-301): adds
+                               its gradient into the touched rows and its value into the step's loss; S never stored
 ``cvib_index_``                the inverted index (destination row -> pair positions) of the minibatch and drawn pairs of a run
                                of steps, one batched pass; what replaces autograd's scatter-add of two gathered matrices
 ``cvib_grad_``                 CVIB's information term (baseline_train.py:614-635, :1010-1032): adds its gradient into both
@@ -934,6 +936,43 @@ def _impute_grad(user_table, item_table, sel_users, sel_items, imputation_coe, g
 @_fake('impute_grad_')
 def _impute_grad_fake(user_table, item_table, sel_users, sel_items, imputation_coe, grad_user, grad_item, loss_out, term_out,
                       workspace):
+    return None
+
+
+# ---- fairness-MF item-popularity term (baseline_train.py:279-313; csrc/invpref_fairness.hip)
+_define('fairness_grad_(Tensor user_table, Tensor item_table, Tensor users, Tensor user_mult, Tensor draw_items, '
+        'Tensor item_counts, Tensor table, float fairness_coe, int batch, Tensor(a!) grad_user, Tensor(b!) grad_item, '
+        'Tensor(c!)? loss_out, Tensor(d!)? term_out, Tensor(e!) workspace) -> ()')
+
+
+@_impl('fairness_grad_')
+def _fairness_grad(user_table, item_table, users, user_mult, draw_items, item_counts, table, fairness_coe, batch, grad_user,
+                   grad_item, loss_out, term_out, workspace):
+    U, I, D = _expo_tables(user_table, item_table)
+    _f32(grad_user, 'grad_user')
+    _f32(grad_item, 'grad_item')
+    if tuple(grad_user.shape) != (U, D) or tuple(grad_item.shape) != (I, D):
+        raise InvPrefError('fairness_grad: grad_user / grad_item must have the shapes of user_table / item_table')
+    for x, name in ((users, 'users'), (user_mult, 'user_mult'), (draw_items, 'draw_items'), (item_counts, 'item_counts')):
+        _capi._req(x, torch.int32, name)
+    if user_mult.numel() != users.numel():
+        raise InvPrefError('fairness_grad: users and user_mult differ in length')
+    if item_counts.numel() != I:
+        raise InvPrefError(f'fairness_grad: item_counts has {item_counts.numel()} entries for {I} items')
+    _f32(table, 'table')
+    _f32(loss_out, 'loss_out')
+    _f32(term_out, 'term_out')
+    _capi._req(workspace, torch.uint8, 'workspace')
+    check(lib().invpref_fairness_grad_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(user_mult), users.numel(),
+                                          ptr(draw_items), draw_items.numel(), ptr(item_counts), ptr(table), table.numel(),
+                                          float(fairness_coe), int(batch), ptr(grad_user), ptr(grad_item), ptr(loss_out),
+                                          ptr(term_out), ptr(workspace), workspace.numel(), stream_ptr()),
+          'invpref_fairness_grad_hip')
+
+
+@_fake('fairness_grad_')
+def _fairness_grad_fake(user_table, item_table, users, user_mult, draw_items, item_counts, table, fairness_coe, batch, grad_user,
+                        grad_item, loss_out, term_out, workspace):
     return None
 
 
