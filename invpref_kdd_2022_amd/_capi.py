@@ -8,41 +8,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('INVPREF_LIB') or os.path.join(PKG, 'libinvpref_hip.so')  # INVPREF_LIB: variant builds (tests, tools)
 
-IMPLICIT, REWEIGHT_REC, REWEIGHT_CLS, REG_ONLY_EMBED, REG_ENV_EMBED, DENSE_REG, NO_GRAD, PURE_MF = 1, 2, 4, 8, 16, 32, 64, 128
-WEIGHTS_BY_ENV = 256   # INVPREF_WEIGHTS_BY_ENV: `sample_weights` holds class_weights[env_num], weight of i = class_weights[envs[i]]
-ABI_VERSION = 6
-
-EXPORTS = [
-    'invpref_abi_version', 'invpref_device_name', 'invpref_forward_hip', 'invpref_mstep_workspace_bytes',
-    'invpref_mstep_grad_hip', 'invpref_adam_hip', 'invpref_estep_workspace_bytes', 'invpref_estep_hip',
-    'invpref_stat_envs_hip', 'invpref_sample_weights_hip', 'invpref_backward_hip', 'invpref_predict_hip',
-    'invpref_rows_workspace_bytes', 'invpref_mstep_rows_grad_hip', 'invpref_mstep_rows_adam_hip',
-    'invpref_adam_schedule_fill', 'invpref_mstep_rows_adam_sched_hip', 'invpref_eval_topk_hip',
-    'invpref_eval_error_sums_hip', 'invpref_mstep_rows_adam_profiled_hip', 'invpref_static_pop_workspace_bytes',
-    'invpref_static_pop_hip', 'invpref_adam_ranges_hip', 'invpref_mstep_rows_grad_sched_hip',
-    'invpref_adam_ranges_sched_hip', 'invpref_rows_lanes_per_group', 'invpref_estep_perm_hip',
-    'invpref_pack_rows_hip', 'invpref_unpack_rows_hip', 'invpref_alt_workspace_bytes', 'invpref_alt_supported',
-    'invpref_mstep_alt_hip', 'invpref_alt_error_offset', 'invpref_estep_fused_hip', 'invpref_perm_table_fill',
-    'invpref_predict_topk_workspace_bytes', 'invpref_predict_topk_hip', 'invpref_rank_metrics_workspace_bytes',
-    'invpref_rank_metrics_hip', 'invpref_topk_rows_workspace_bytes', 'invpref_topk_rows_hip',
-    'invpref_predict_topk_wide_workspace_bytes', 'invpref_predict_topk_wide_hip', 'invpref_rank_metrics_wide_hip',
-    'invpref_interaction_counts_workspace_bytes', 'invpref_interaction_counts_hip', 'invpref_count_propensity_workspace_bytes',
-    'invpref_count_propensity_hip', 'invpref_naive_bayes_workspace_bytes', 'invpref_naive_bayes_propensity_hip',
-    'invpref_snips_scale_hip', 'invpref_exposure_workspace_bytes', 'invpref_exposure_hip', 'invpref_exposure_weights_hip',
-    'invpref_impute_workspace_bytes', 'invpref_impute_grad_hip', 'invpref_cvib_workspace_bytes', 'invpref_cvib_index_keys_hip',
-    'invpref_cvib_index_hip', 'invpref_cvib_grad_hip', 'invpref_fairness_workspace_bytes', 'invpref_fairness_grad_hip',
-]
-MAX_TOPK = 64          # k of the fused scan / k-pass / radix-select kernels and the 64-wide metric tables
-MAX_TOPK_WIDE = 1024   # INVPREF_MAX_TOPK_WIDE: the wide entry points (csrc/invpref_topk_wide.hip)
-PROPENSITY_ITEM, PROPENSITY_USER, PROPENSITY_PAIR = 0, 1, 2   # INVPREF_PROPENSITY_*: basic_{item,user,pair}_propensity_func
-MAX_LABELS = 256       # INVPREF_MAX_LABELS: distinct training labels of the naive-Bayes propensities
-FAIRNESS_TABLE_LDS = 8192   # INVPREF_FAIRNESS_TABLE_LDS: distance-table entries the fairness product keeps in LDS
+HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_hip.h')   # the one statement of the C ABI; build.py compiles against it
 
 
 class InvPrefError(RuntimeError):
@@ -67,6 +40,61 @@ class AdamSchedule(C.Structure):
     _fields_ = [('state', C.c_void_p), ('table', C.c_void_p), ('n', C.c_int32), ('slot', C.c_int32)]
 
 
+_SCALARS = {'int64_t': C.c_int64, 'int32_t': C.c_int32, 'int': C.c_int, 'uint32_t': C.c_uint32, 'size_t': C.c_size_t,
+            'double': C.c_double, 'float': C.c_float}
+# pointers to the structs mirrored above and host strings; every other pointer (device memory, host arrays, the plan structs
+# that plan.py mirrors, the stream) travels as c_void_p
+_POINTERS = {'const InvPrefTables': C.POINTER(Tables), 'const InvPrefCoefs': C.POINTER(Coefs),
+             'const InvPrefAdamSchedule': C.POINTER(AdamSchedule), 'char': C.c_char_p}
+
+
+def parse_header(text: str):
+    """(functions, defines) of a header in the style of include/invpref_hip.h: functions maps every `invpref_*` prototype,
+    in header order, to (restype, argtypes); defines maps NAME to the value of every `#define INVPREF_NAME <integer>[u]`
+    (other defines, such as parenthesised expressions, are skipped).  A type outside the tables above raises."""
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    defines = {n: int(v) for n, v in re.findall(r'^[ \t]*#[ \t]*define[ \t]+INVPREF_(\w+)[ \t]+(\d+)[uU]?[ \t]*$', text, re.M)}
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+    text = re.sub(r'typedef\s+struct\s*\w*\s*\{.*?\}\s*\w+\s*;', '', text, flags=re.S)
+    functions = {}
+    for ret, name, params in re.findall(r'([\w\s*]+?)\b(invpref_\w+)\s*\(([^()]*)\)\s*;', text):
+        if ret.strip() not in ('int', 'size_t'):
+            raise InvPrefError(f'{name}: return type `{ret.strip()}` has no ctypes mapping')
+        argtypes = []
+        for param in ([] if params.strip() == 'void' else params.split(',')):
+            base, star, pname = (w.strip() for w in param.rpartition('*'))
+            if star:
+                argtypes.append(_POINTERS.get(base, C.c_void_p))
+                continue
+            words = [w for w in pname.split() if w != 'const']
+            if len(words) != 2 or words[0] not in _SCALARS:
+                raise InvPrefError(f'{name}: parameter `{pname}` has no ctypes mapping')
+            argtypes.append(_SCALARS[words[0]])
+        functions[name] = (_SCALARS[ret.strip()], argtypes)
+    return functions, defines
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as exc:
+        raise InvPrefError(f'{HEADER_PATH} is missing ({exc}): the ctypes signatures are derived from it') from None
+
+
+SIGNATURES, DEFINES = _read_header()
+EXPORTS = list(SIGNATURES)
+ABI_VERSION = DEFINES['ABI_VERSION']
+IMPLICIT, REWEIGHT_REC, REWEIGHT_CLS, REG_ONLY_EMBED, REG_ENV_EMBED, DENSE_REG, NO_GRAD, PURE_MF = (
+    DEFINES[n] for n in ('IMPLICIT', 'REWEIGHT_REC', 'REWEIGHT_CLS', 'REG_ONLY_EMBED', 'REG_ENV_EMBED', 'DENSE_REG', 'NO_GRAD',
+                         'PURE_MF'))
+WEIGHTS_BY_ENV = DEFINES['WEIGHTS_BY_ENV']   # `sample_weights` holds class_weights[env_num], weight of i = class_weights[envs[i]]
+MAX_TOPK = 64          # k of the fused scan / k-pass / radix-select kernels and the 64-wide metric tables (no define)
+MAX_TOPK_WIDE = DEFINES['MAX_TOPK_WIDE']   # the wide entry points (csrc/invpref_topk_wide.hip)
+PROPENSITY_ITEM, PROPENSITY_USER, PROPENSITY_PAIR = (DEFINES['PROPENSITY_' + n] for n in ('ITEM', 'USER', 'PAIR'))
+MAX_LABELS = DEFINES['MAX_LABELS']         # distinct training labels of the naive-Bayes propensities
+FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries the fairness product keeps in LDS
+
 _lib = None
 
 
@@ -79,104 +107,11 @@ def lib():
                 f'{LIB_PATH} is missing: build it with `python -m invpref_kdd_2022_amd.build` '
                 '(or __graft_entry__.build()); the InvPref hot path has no fallback implementation')
         L = C.CDLL(LIB_PATH)
-        L.invpref_mstep_workspace_bytes.restype = C.c_size_t
-        L.invpref_estep_workspace_bytes.restype = C.c_size_t
-        L.invpref_mstep_workspace_bytes.argtypes = [C.POINTER(Tables), C.c_int64]
-        L.invpref_estep_workspace_bytes.argtypes = [C.POINTER(Tables), C.c_int64]
-        vp, i64, u32, f64 = C.c_void_p, C.c_int64, C.c_uint32, C.c_double
-        L.invpref_forward_hip.argtypes = [C.POINTER(Tables), vp, vp, vp, i64, u32, vp, vp, vp, vp]
-        L.invpref_mstep_grad_hip.argtypes = [C.POINTER(Tables), C.POINTER(Tables), vp, vp, vp, vp, vp, i64, i64,
-                                             C.POINTER(Coefs), u32, vp, vp, C.c_size_t, vp]
-        L.invpref_adam_hip.argtypes = [vp, vp, vp, vp, i64, i64, f64, f64, f64, f64, C.c_int, vp]
-        L.invpref_pack_rows_hip.argtypes = [vp, vp, i64, C.c_int32, i64, i64, vp, C.c_int, vp]
-        L.invpref_unpack_rows_hip.argtypes = [vp, vp, i64, C.c_int32, i64, i64, vp, C.c_int, vp]
-        L.invpref_estep_hip.argtypes = [C.POINTER(Tables), vp, vp, vp, i64, u32, vp, vp, vp, vp, vp, vp, vp, vp,
-                                        C.c_size_t, vp]
-        L.invpref_estep_perm_hip.argtypes = [C.POINTER(Tables), vp, vp, vp, i64, u32, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp,
-                                             vp, C.c_size_t, vp]
-        L.invpref_stat_envs_hip.argtypes = [vp, i64, i64, vp, vp, vp, vp, C.c_size_t, vp]
-        L.invpref_sample_weights_hip.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp]
-        L.invpref_backward_hip.argtypes = [C.POINTER(Tables), C.POINTER(Tables), vp, vp, vp, i64, u32, C.c_float, vp,
-                                           vp, vp, vp, C.c_size_t, vp]
-        L.invpref_predict_hip.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, vp, vp]
-        L.invpref_rows_workspace_bytes.restype = C.c_size_t
-        L.invpref_rows_workspace_bytes.argtypes = [C.POINTER(Tables), vp]
-        L.invpref_mstep_rows_grad_hip.argtypes = [C.POINTER(Tables), C.POINTER(Tables), vp, vp, vp, vp, i64,
-                                                   C.POINTER(Coefs), u32, vp, vp, C.c_size_t, vp]
-        L.invpref_mstep_rows_adam_hip.argtypes = [C.POINTER(Tables), C.POINTER(Tables), C.POINTER(Tables),
-                                                   C.POINTER(Tables), vp, vp, vp, vp, i64, C.POINTER(Coefs), u32, vp,
-                                                   i64, f64, f64, f64, f64, vp, C.c_size_t, vp]
-        L.invpref_adam_ranges_hip.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, i64, f64, f64, f64, f64, C.c_int, vp]
-        L.invpref_adam_schedule_fill.argtypes = [vp, i64, i64, f64, f64, f64, f64]
-        L.invpref_mstep_rows_grad_sched_hip.argtypes = [C.POINTER(Tables), C.POINTER(Tables), vp, vp, vp, vp, i64,
-                                                         C.POINTER(Coefs), u32, vp, C.POINTER(AdamSchedule), vp,
-                                                         C.c_size_t, vp]
-        L.invpref_adam_ranges_sched_hip.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, C.POINTER(AdamSchedule), C.c_int, vp]
-        L.invpref_mstep_rows_adam_sched_hip.argtypes = [C.POINTER(Tables), C.POINTER(Tables), C.POINTER(Tables),
-                                                        C.POINTER(Tables), vp, vp, vp, vp, i64, C.POINTER(Coefs), u32,
-                                                        vp, C.POINTER(AdamSchedule), vp, C.c_size_t, vp]
-        L.invpref_eval_topk_hip.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp]
-        L.invpref_eval_error_sums_hip.argtypes = [vp, vp, i64, vp, vp]
-        L.invpref_mstep_rows_adam_profiled_hip.argtypes = L.invpref_mstep_rows_adam_hip.argtypes + [vp]
-        L.invpref_rows_lanes_per_group.argtypes = [C.POINTER(Tables)]
-        L.invpref_static_pop_workspace_bytes.argtypes = [i64, i64, i64]
-        L.invpref_static_pop_workspace_bytes.restype = C.c_size_t
-        L.invpref_static_pop_hip.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-        L.invpref_device_name.argtypes = [C.c_char_p, C.c_size_t]
-        L.invpref_alt_workspace_bytes.restype = C.c_size_t
-        L.invpref_alt_workspace_bytes.argtypes = [C.POINTER(Tables), C.c_int32, C.c_int32]
-        L.invpref_alt_error_offset.restype = C.c_size_t
-        L.invpref_alt_error_offset.argtypes = [C.POINTER(Tables), C.c_int32, C.c_int32]
-        L.invpref_alt_supported.argtypes = [C.POINTER(Tables)]
-        L.invpref_mstep_alt_hip.argtypes = [C.POINTER(Tables), C.POINTER(Tables), C.POINTER(Tables), vp, vp, vp, i64, i64,
-                                            C.POINTER(Coefs), u32, vp, i64, f64, f64, f64, f64, C.POINTER(AdamSchedule), vp,
-                                            C.c_size_t, C.c_int32, C.c_int32, C.c_int32, vp]
-        L.invpref_estep_fused_hip.argtypes = [C.POINTER(Tables), vp, vp, vp, i64, u32, vp, C.c_int, vp, vp, vp, vp, vp,
-                                              C.c_int32, vp, vp, vp, vp, C.c_size_t, vp]
-        L.invpref_perm_table_fill.argtypes = [C.c_int32, vp]
-        L.invpref_predict_topk_workspace_bytes.restype = C.c_size_t
-        L.invpref_predict_topk_workspace_bytes.argtypes = [i64, i64, i64, C.c_int32]
-        L.invpref_predict_topk_hip.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp,
-                                               vp, vp, C.c_size_t, vp]
-        L.invpref_rank_metrics_workspace_bytes.restype = C.c_size_t
-        L.invpref_rank_metrics_workspace_bytes.argtypes = [i64, C.c_int32, i64]
-        L.invpref_rank_metrics_hip.argtypes = [vp, i64, i64, C.c_int32, vp, vp, C.c_int32, vp, vp, i64, vp, vp, C.c_size_t, vp]
-        L.invpref_topk_rows_workspace_bytes.restype = C.c_size_t
-        L.invpref_topk_rows_workspace_bytes.argtypes = [i64, i64, C.c_int32]
-        L.invpref_topk_rows_hip.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_size_t, vp]
-        L.invpref_predict_topk_wide_workspace_bytes.restype = C.c_size_t
-        L.invpref_predict_topk_wide_workspace_bytes.argtypes = [i64, i64, i64, C.c_int32]
-        L.invpref_predict_topk_wide_hip.argtypes = L.invpref_predict_topk_hip.argtypes
-        L.invpref_rank_metrics_wide_hip.argtypes = [vp, i64, i64, C.c_int32, vp, vp, C.c_int32, vp, i64, vp, i64, i64, vp, vp,
-                                                    C.c_size_t, vp]
-        L.invpref_interaction_counts_workspace_bytes.restype = C.c_size_t
-        L.invpref_interaction_counts_workspace_bytes.argtypes = [i64, i64]
-        L.invpref_interaction_counts_hip.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, C.c_size_t, vp]
-        L.invpref_count_propensity_workspace_bytes.restype = C.c_size_t
-        L.invpref_count_propensity_workspace_bytes.argtypes = []
-        L.invpref_count_propensity_hip.argtypes = [vp, i64, vp, i64, vp, vp, i64, C.c_int32, f64, vp, vp, C.c_size_t, vp]
-        L.invpref_naive_bayes_workspace_bytes.restype = C.c_size_t
-        L.invpref_naive_bayes_workspace_bytes.argtypes = [C.c_int32]
-        L.invpref_naive_bayes_propensity_hip.argtypes = [vp, i64, vp, i64, vp, C.c_int32, i64, i64, f64, vp, vp, vp,
-                                                         C.c_size_t, vp]
-        L.invpref_snips_scale_hip.argtypes = [vp, i64, i64, vp, vp]
-        L.invpref_exposure_workspace_bytes.restype = C.c_size_t
-        L.invpref_exposure_workspace_bytes.argtypes = [i64, i64]
-        L.invpref_exposure_hip.argtypes = [vp, i64, vp, i64, i64, vp, i64, f64, f64, vp, f64, f64, vp, vp, vp, C.c_size_t, vp]
-        L.invpref_exposure_weights_hip.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, i64, f64, f64, vp, f64, vp, vp]
-        L.invpref_impute_workspace_bytes.restype = C.c_size_t
-        L.invpref_impute_workspace_bytes.argtypes = [i64, i64, i64]
-        L.invpref_impute_grad_hip.argtypes = [vp, i64, vp, i64, i64, vp, i64, vp, i64, f64, vp, vp, vp, vp, vp, C.c_size_t, vp]
-        L.invpref_cvib_workspace_bytes.restype = C.c_size_t
-        L.invpref_cvib_workspace_bytes.argtypes = [i64, i64]
-        L.invpref_cvib_index_keys_hip.argtypes = [vp, vp, vp, vp, i64, vp, i64, i64, i64, vp, vp]
-        L.invpref_cvib_index_hip.argtypes = [vp, i64, i64, i64, i64, vp, vp]
-        L.invpref_cvib_grad_hip.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, u32, f64, f64, f64, f64, vp, vp, vp,
-                                            vp, vp, vp, vp, C.c_size_t, vp]
-        L.invpref_fairness_workspace_bytes.restype = C.c_size_t
-        L.invpref_fairness_workspace_bytes.argtypes = [i64, i64, i64]
-        L.invpref_fairness_grad_hip.argtypes = [vp, i64, vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, i64, f64, i64, vp, vp, vp, vp, vp,
-                                                C.c_size_t, vp]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_hip.h declares')
+            fn.restype, fn.argtypes = restype, argtypes
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')
         _lib = L
@@ -188,6 +123,11 @@ def check(rc: int, what: str):
         kind = {-1: 'invalid argument', -2: 'unsupported factor_num/env_num', -3: 'workspace too small'}.get(
             rc, f'hipError_t {rc}' if rc > 0 else f'error {rc}')
         raise InvPrefError(f'{what} failed: {kind}')
+
+
+def call(name: str, *args):
+    """One checked call of an `int` entry point: a non-zero return code raises InvPrefError naming it."""
+    check(getattr(lib(), name)(*args), name)
 
 
 def ptr(t):
@@ -237,5 +177,5 @@ def make_pure_tables(tensors) -> Tables:
 
 def device_name() -> str:
     buf = C.create_string_buffer(256)
-    check(lib().invpref_device_name(buf, 256), 'invpref_device_name')
+    call('invpref_device_name', buf, 256)
     return buf.value.decode()

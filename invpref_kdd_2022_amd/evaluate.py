@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._capi import MAX_TOPK, check, lib, ptr, stream_ptr
+from ._capi import MAX_TOPK, call, ptr, stream_ptr
 
 
 def _csr(sets, n_items=None) -> tuple[np.ndarray, np.ndarray]:
@@ -103,11 +103,9 @@ class ImplicitTestManager:
         items = torch.empty(n, k, dtype=torch.int32, device=users.device)
         hits = torch.empty(n, k, dtype=torch.float32, device=users.device)
         off = lambda t, o: C.c_void_p(t.data_ptr() + 4 * o)  # noqa: E731
-        check(lib().invpref_eval_topk_hip(
-            ptr(ratings), n, ratings.shape[1], off(d['mask_ptr'], lo), ptr(d['mask_items']),
-            off(d['hl_ptr'], lo) if self.use_item_pool else None, ptr(d['hl_items']) if self.use_item_pool else None,
-            off(d['truth_ptr'], lo), ptr(d['truth_items']), k, ptr(items), ptr(hits), stream_ptr()),
-            'invpref_eval_topk_hip')
+        call('invpref_eval_topk_hip', ptr(ratings), n, ratings.shape[1], off(d['mask_ptr'], lo), ptr(d['mask_items']),
+             off(d['hl_ptr'], lo) if self.use_item_pool else None, ptr(d['hl_items']) if self.use_item_pool else None,
+             off(d['truth_ptr'], lo), ptr(d['truth_items']), k, ptr(items), ptr(hits), stream_ptr())
         return items, hits
 
     def _fused_tables(self):
@@ -222,8 +220,7 @@ class ExplicitTestManager:
         users, items, target = self._test_pairs(device)
         pred = self.model.predict(users, items)
         out = torch.empty(2, dtype=torch.float64, device=device)
-        check(lib().invpref_eval_error_sums_hip(ptr(pred), ptr(target), pred.numel(), ptr(out), stream_ptr()),
-              'invpref_eval_error_sums_hip')
+        call('invpref_eval_error_sums_hip', ptr(pred), ptr(target), pred.numel(), ptr(out), stream_ptr())
         n = float(pred.numel())
 
         def finish(host: torch.Tensor) -> dict:

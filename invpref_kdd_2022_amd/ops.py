@@ -15,7 +15,7 @@ import torch
 from . import _capi
 from . import torch_ops  # noqa: F401  (registers torch.ops.invpref.*)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
-                    InvPrefError, check, lib, make_tables, ptr, stream_ptr)
+                    InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
 PARAM_NAMES = [
     'embed_user_invariant.weight', 'embed_item_invariant.weight',
@@ -263,9 +263,8 @@ def topk_rows(ratings: torch.Tensor, k: int, mask=None, highlight=None, truth=No
     L = lib()
     nbytes = L.invpref_topk_rows_workspace_bytes(n, I, k)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    check(L.invpref_topk_rows_hip(ptr(ratings), n, I, ratings.stride(0) if n > 0 else I, ptr(mp), ptr(mi), ptr(hp), ptr(hi),
-                                  ptr(tp), ptr(ti), k, ptr(items), ptr(scores), ptr(hits), ptr(ws), nbytes, stream_ptr()),
-          'invpref_topk_rows_hip')
+    call('invpref_topk_rows_hip', ptr(ratings), n, I, ratings.stride(0) if n > 0 else I, ptr(mp), ptr(mi), ptr(hp), ptr(hi),
+         ptr(tp), ptr(ti), k, ptr(items), ptr(scores), ptr(hits), ptr(ws), nbytes, stream_ptr())
     return items, scores, hits
 
 
@@ -372,11 +371,10 @@ def mstep_rows_adam(params, new_params, exp_avg, exp_avg_sq, dplan, envs, scores
         t, tn, tm, tv = mk(params), mk(new_params), mk(exp_avg), mk(exp_avg_sq)
         cf = _capi.Coefs(*[float(c) for c in coefs[:6]])
         mid_event.record()   # (creates the underlying hipEvent_t; re-recorded by the library between the launches)
-        check(lib().invpref_mstep_rows_adam_profiled_hip(
-            C.byref(t), C.byref(tn), C.byref(tm), C.byref(tv), C.byref(dplan.struct), ptr(envs), ptr(scores),
-            ptr(sample_weights), int(batch_norm), C.byref(cf), int(flags), ptr(losses6), int(step), float(lr),
-            float(beta1), float(beta2), float(eps), ptr(ws), ws.numel(), stream_ptr(), C.c_void_p(mid_event.cuda_event)),
-            'invpref_mstep_rows_adam_profiled_hip')
+        call('invpref_mstep_rows_adam_profiled_hip', C.byref(t), C.byref(tn), C.byref(tm), C.byref(tv),
+             C.byref(dplan.struct), ptr(envs), ptr(scores), ptr(sample_weights), int(batch_norm), C.byref(cf), int(flags),
+             ptr(losses6), int(step), float(lr), float(beta1), float(beta2), float(eps), ptr(ws), ws.numel(), stream_ptr(),
+             C.c_void_p(mid_event.cuda_event))
         return
     s_state, s_table, s_slot = sched if sched is not None else (None, None, 0)
     _o().train_step_planned_adam_(list(params), list(new_params), list(exp_avg), list(exp_avg_sq), dplan.buf, dplan.meta,
@@ -442,9 +440,8 @@ def static_pop(users, items, envs, env_num: int, user_cnt, item_cnt, user_norm, 
         raise InvPrefError('static_pop: inconsistent sizes')
     out = torch.empty(env_num, 10, dtype=torch.float64, device=users.device)
     ws = workspace.get(lib().invpref_static_pop_workspace_bytes(U, I, env_num))
-    check(lib().invpref_static_pop_hip(ptr(users), ptr(items), ptr(envs), users.numel(), U, I, env_num, ptr(user_cnt),
-                                       ptr(item_cnt), ptr(user_norm), ptr(item_norm), ptr(out), ptr(ws), ws.numel(),
-                                       stream_ptr()), 'invpref_static_pop_hip')
+    call('invpref_static_pop_hip', ptr(users), ptr(items), ptr(envs), users.numel(), U, I, env_num, ptr(user_cnt),
+         ptr(item_cnt), ptr(user_norm), ptr(item_norm), ptr(out), ptr(ws), ws.numel(), stream_ptr())
     return out
 
 

@@ -59,15 +59,23 @@ import ctypes as C
 import torch
 
 from . import _capi
-from ._capi import Coefs, InvPrefError, check, lib, make_pure_tables, make_tables, ptr, stream_ptr
+from ._capi import Coefs, InvPrefError, call, lib, make_pure_tables, make_tables, ptr, stream_ptr
 
 _LIB = torch.library.Library('invpref', 'DEF')
 NAMES = []
 
 
+def _fake(name: str):
+    return torch.library.register_fake(f'invpref::{name}', lib=_LIB)
+
+
 def _define(schema: str):
+    """Declare an operator.  One that returns nothing (it only mutates its arguments) gets its fake here: nothing to shape."""
     _LIB.define(schema)
-    NAMES.append(schema.split('(')[0])
+    name = schema.split('(')[0]
+    NAMES.append(name)
+    if schema.endswith('-> ()'):
+        _fake(name)(lambda *args, **kwargs: None)
 
 
 def _impl(name: str):
@@ -75,10 +83,6 @@ def _impl(name: str):
         _LIB.impl(name, fn, 'CUDA')
         return fn
     return deco
-
-
-def _fake(name: str):
-    return torch.library.register_fake(f'invpref::{name}', lib=_LIB)
 
 
 def _ids(t, name):
@@ -118,9 +122,8 @@ def _forward(tables, users, items, envs, implicit):
     inv = torch.empty(B, dtype=torch.float32, device=dev)
     env = torch.empty(B, dtype=torch.float32, device=dev)
     out = torch.empty(B, t.env_num, dtype=torch.float32, device=dev)
-    check(lib().invpref_forward_hip(C.byref(t), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')),
-                                    ptr(_ids(envs, 'envs')), B, _capi.IMPLICIT if implicit else 0, ptr(inv), ptr(env),
-                                    ptr(out), stream_ptr()), 'invpref_forward_hip')
+    call('invpref_forward_hip', C.byref(t), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), ptr(_ids(envs, 'envs')), B,
+         _capi.IMPLICIT if implicit else 0, ptr(inv), ptr(env), ptr(out), stream_ptr())
     return inv, env, out
 
 
@@ -141,15 +144,9 @@ def _backward(tables, grads, users, items, envs, implicit, alpha, d_inv, d_env, 
     B = users.numel()
     for n, x in (('d_inv', d_inv), ('d_env', d_env), ('d_out', d_out)):
         _capi._req(x, torch.float32, n)
-    check(lib().invpref_backward_hip(C.byref(t), C.byref(g), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')),
-                                     ptr(_ids(envs, 'envs')), B, _capi.IMPLICIT if implicit else 0, float(alpha),
-                                     ptr(d_inv), ptr(d_env), ptr(d_out), ptr(workspace), workspace.numel(),
-                                     stream_ptr()), 'invpref_backward_hip')
-
-
-@_fake('backward')
-def _backward_fake(tables, grads, users, items, envs, implicit, alpha, d_inv, d_env, d_out, workspace):
-    return None
+    call('invpref_backward_hip', C.byref(t), C.byref(g), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')),
+         ptr(_ids(envs, 'envs')), B, _capi.IMPLICIT if implicit else 0, float(alpha), ptr(d_inv), ptr(d_env), ptr(d_out),
+         ptr(workspace), workspace.numel(), stream_ptr())
 
 
 # ------------------------------------------------------------------------------------------------ M-step
@@ -164,16 +161,9 @@ def _train_step_fused(tables, grads, users, items, envs, scores, sample_weights,
     B = users.numel()
     _f32(scores, 'scores'); _f32(sample_weights, 'sample_weights'); _f32(losses6, 'losses6')
     cf = _coefs(coefs)
-    check(lib().invpref_mstep_grad_hip(C.byref(t), C.byref(g), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')),
-                                       ptr(_ids(envs, 'envs')), ptr(scores), ptr(sample_weights), B, int(batch_norm),
-                                       C.byref(cf), int(flags), ptr(losses6), ptr(workspace), workspace.numel(),
-                                       stream_ptr()), 'invpref_mstep_grad_hip')
-
-
-@_fake('train_step_fused')
-def _train_step_fused_fake(tables, grads, users, items, envs, scores, sample_weights, batch_norm, coefs, flags, losses6,
-                           workspace):
-    return None
+    call('invpref_mstep_grad_hip', C.byref(t), C.byref(g), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')),
+         ptr(_ids(envs, 'envs')), ptr(scores), ptr(sample_weights), B, int(batch_norm), C.byref(cf), int(flags),
+         ptr(losses6), ptr(workspace), workspace.numel(), stream_ptr())
 
 
 _define('train_step_planned_grad_(Tensor[] tables, Tensor(a!)[] grads, Tensor plan_buf, Tensor plan_meta, Tensor? envs, '
@@ -198,23 +188,13 @@ def _planned_grad(tables, grads, plan_buf, plan_meta, envs, scores, sample_weigh
     ps = _plan_struct(plan_buf, plan_meta)
     if sched_state is not None:   # graph replay: a scheduled alpha comes from the device-side schedule
         sc = _sched_struct(sched_state, sched_table, sched_slot)
-        check(lib().invpref_mstep_rows_grad_sched_hip(C.byref(t), C.byref(g), C.byref(ps),
-                                                      ptr(None if envs is None else _ids(envs, 'envs')), ptr(scores),
-                                                      ptr(sample_weights), int(batch_norm), C.byref(cf), int(flags),
-                                                      ptr(losses6), C.byref(sc), ptr(workspace), workspace.numel(),
-                                                      stream_ptr()), 'invpref_mstep_rows_grad_sched_hip')
+        call('invpref_mstep_rows_grad_sched_hip', C.byref(t), C.byref(g), C.byref(ps),
+             ptr(None if envs is None else _ids(envs, 'envs')), ptr(scores), ptr(sample_weights), int(batch_norm),
+             C.byref(cf), int(flags), ptr(losses6), C.byref(sc), ptr(workspace), workspace.numel(), stream_ptr())
         return
-    check(lib().invpref_mstep_rows_grad_hip(C.byref(t), C.byref(g), C.byref(ps),
-                                             ptr(None if envs is None else _ids(envs, 'envs')), ptr(scores),
-                                             ptr(sample_weights), int(batch_norm), C.byref(cf), int(flags),
-                                             ptr(losses6), ptr(workspace), workspace.numel(), stream_ptr()),
-          'invpref_mstep_rows_grad_hip')
-
-
-@_fake('train_step_planned_grad_')
-def _planned_grad_fake(tables, grads, plan_buf, plan_meta, envs, scores, sample_weights, batch_norm, coefs, flags,
-                       losses6, sched_state, sched_table, sched_slot, workspace):
-    return None
+    call('invpref_mstep_rows_grad_hip', C.byref(t), C.byref(g), C.byref(ps),
+         ptr(None if envs is None else _ids(envs, 'envs')), ptr(scores), ptr(sample_weights), int(batch_norm), C.byref(cf),
+         int(flags), ptr(losses6), ptr(workspace), workspace.numel(), stream_ptr())
 
 
 _define('train_step_planned_adam_(Tensor[] tables, Tensor(a!)[] new_tables, Tensor(b!)[] exp_avg, Tensor(c!)[] exp_avg_sq, '
@@ -235,24 +215,13 @@ def _planned_adam(tables, new_tables, exp_avg, exp_avg_sq, plan_buf, plan_meta, 
     if sched_state is not None:
         # Adam scalars (and a scheduled alpha) come from the device-side schedule: graph replay freezes arguments
         sc = _sched_struct(sched_state, sched_table, sched_slot)
-        check(lib().invpref_mstep_rows_adam_sched_hip(C.byref(t), C.byref(tn), C.byref(tm), C.byref(tv), C.byref(ps), pe,
-                                                      ptr(scores), ptr(sample_weights), int(batch_norm), C.byref(cf),
-                                                      int(flags), ptr(losses6), C.byref(sc), ptr(workspace),
-                                                      workspace.numel(), stream_ptr()),
-              'invpref_mstep_rows_adam_sched_hip')
+        call('invpref_mstep_rows_adam_sched_hip', C.byref(t), C.byref(tn), C.byref(tm), C.byref(tv), C.byref(ps), pe,
+             ptr(scores), ptr(sample_weights), int(batch_norm), C.byref(cf), int(flags), ptr(losses6), C.byref(sc),
+             ptr(workspace), workspace.numel(), stream_ptr())
         return
-    check(lib().invpref_mstep_rows_adam_hip(C.byref(t), C.byref(tn), C.byref(tm), C.byref(tv), C.byref(ps), pe,
-                                             ptr(scores), ptr(sample_weights), int(batch_norm), C.byref(cf), int(flags),
-                                             ptr(losses6), int(step), float(lr), float(beta1), float(beta2), float(eps),
-                                             ptr(workspace), workspace.numel(), stream_ptr()),
-          'invpref_mstep_rows_adam_hip')
-
-
-@_fake('train_step_planned_adam_')
-def _planned_adam_fake(tables, new_tables, exp_avg, exp_avg_sq, plan_buf, plan_meta, envs, scores, sample_weights,
-                       batch_norm, coefs, flags, losses6, step, lr, beta1, beta2, eps, sched_state, sched_table,
-                       sched_slot, workspace):
-    return None
+    call('invpref_mstep_rows_adam_hip', C.byref(t), C.byref(tn), C.byref(tm), C.byref(tv), C.byref(ps), pe, ptr(scores),
+         ptr(sample_weights), int(batch_norm), C.byref(cf), int(flags), ptr(losses6), int(step), float(lr), float(beta1),
+         float(beta2), float(eps), ptr(workspace), workspace.numel(), stream_ptr())
 
 
 _define('train_step_alt_(Tensor(a!)[] tables, Tensor(b!)[] exp_avg, Tensor(c!)[] exp_avg_sq, Tensor plan_buf, Tensor plan_meta, '
@@ -274,20 +243,10 @@ def _step_alt(tables, exp_avg, exp_avg_sq, plan_buf, plan_meta, envs, sample_wei
     ps = alt_struct_from_meta(plan_buf, plan_meta)
     pe = ptr(None if envs is None else _ids(envs, 'envs'))
     sc = None if sched_state is None else C.byref(_sched_struct(sched_state, sched_table, sched_slot))
-    check(lib().invpref_mstep_alt_hip(C.byref(t), C.byref(tm), C.byref(tv), C.byref(ps), pe, ptr(sample_weights),
-                                      int(batch_norm), int(batch_norm_prev), C.byref(cf), int(flags), ptr(losses6_prev),
-                                      int(step), float(lr), float(beta1), float(beta2), float(eps), sc, ptr(workspace),
-                                      workspace.numel(), int(n_cap), int(partials_cap), int(parity), stream_ptr()),
-          'invpref_mstep_alt_hip')
-
-
-@_fake('train_step_alt_')
-def _step_alt_fake(tables, exp_avg, exp_avg_sq, plan_buf, plan_meta, envs, sample_weights, batch_norm, batch_norm_prev, coefs,
-                   flags, losses6_prev, step, lr, beta1, beta2, eps, sched_state, sched_table, sched_slot, workspace, n_cap,
-                   partials_cap, parity):
-    return None
-
-
+    call('invpref_mstep_alt_hip', C.byref(t), C.byref(tm), C.byref(tv), C.byref(ps), pe, ptr(sample_weights),
+         int(batch_norm), int(batch_norm_prev), C.byref(cf), int(flags), ptr(losses6_prev), int(step), float(lr),
+         float(beta1), float(beta2), float(eps), sc, ptr(workspace), workspace.numel(), int(n_cap), int(partials_cap),
+         int(parity), stream_ptr())
 
 
 # ------------------------------------------------------------------------------------------------ Adam
@@ -307,14 +266,8 @@ def _adam_check(param, grad, exp_avg, exp_avg_sq):
 @_impl('adam_dense_')
 def _adam_dense(param, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, zero_grad):
     n = _adam_check(param, grad, exp_avg, exp_avg_sq)
-    check(lib().invpref_adam_hip(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), n, int(step), float(lr),
-                                 float(beta1), float(beta2), float(eps), int(bool(zero_grad)), stream_ptr()),
-          'invpref_adam_hip')
-
-
-@_fake('adam_dense_')
-def _adam_dense_fake(param, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, zero_grad):
-    return None
+    call('invpref_adam_hip', ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), n, int(step), float(lr), float(beta1),
+         float(beta2), float(eps), int(bool(zero_grad)), stream_ptr())
 
 
 # ------------------------------------------------------------------------------------------------ packed exchange
@@ -336,25 +289,15 @@ def _pack_check(flat, row_offsets, D, tail_offset, tail_len, packed):
 @_impl('pack_rows_')
 def _pack_rows(flat, row_offsets, D, tail_offset, tail_len, packed, vec_ok):
     n = _pack_check(flat, row_offsets, D, tail_offset, tail_len, packed)
-    check(lib().invpref_pack_rows_hip(ptr(flat), ptr(row_offsets), n, int(D), int(tail_offset), int(tail_len), ptr(packed),
-                                      int(bool(vec_ok)), stream_ptr()), 'invpref_pack_rows_hip')
+    call('invpref_pack_rows_hip', ptr(flat), ptr(row_offsets), n, int(D), int(tail_offset), int(tail_len), ptr(packed),
+         int(bool(vec_ok)), stream_ptr())
 
 
 @_impl('unpack_rows_')
 def _unpack_rows(flat, row_offsets, D, tail_offset, tail_len, packed, vec_ok):
     n = _pack_check(flat, row_offsets, D, tail_offset, tail_len, packed)
-    check(lib().invpref_unpack_rows_hip(ptr(flat), ptr(row_offsets), n, int(D), int(tail_offset), int(tail_len), ptr(packed),
-                                        int(bool(vec_ok)), stream_ptr()), 'invpref_unpack_rows_hip')
-
-
-@_fake('pack_rows_')
-def _pack_rows_fake(flat, row_offsets, D, tail_offset, tail_len, packed, vec_ok):
-    return None
-
-
-@_fake('unpack_rows_')
-def _unpack_rows_fake(flat, row_offsets, D, tail_offset, tail_len, packed, vec_ok):
-    return None
+    call('invpref_unpack_rows_hip', ptr(flat), ptr(row_offsets), n, int(D), int(tail_offset), int(tail_len), ptr(packed),
+         int(bool(vec_ok)), stream_ptr())
 
 
 _define('adam_ranges_(Tensor(a!) param, Tensor(b!) grad, Tensor(c!) exp_avg, Tensor(d!) exp_avg_sq, int[] offsets, '
@@ -372,19 +315,11 @@ def _adam_ranges(param, grad, exp_avg, exp_avg_sq, offsets, lengths, step, lr, b
     offs, lens = (C.c_int64 * k)(*offsets), (C.c_int64 * k)(*lengths)
     if sched_state is not None:   # graph replay: scalars from the device-side schedule, which this launch moves on
         sc = _sched_struct(sched_state, sched_table, sched_slot)
-        check(lib().invpref_adam_ranges_sched_hip(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), offs, lens, k,
-                                                  C.byref(sc), int(bool(zero_grad)), stream_ptr()),
-              'invpref_adam_ranges_sched_hip')
+        call('invpref_adam_ranges_sched_hip', ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), offs, lens, k,
+             C.byref(sc), int(bool(zero_grad)), stream_ptr())
         return
-    check(lib().invpref_adam_ranges_hip(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), offs, lens, k, int(step),
-                                        float(lr), float(beta1), float(beta2), float(eps), int(bool(zero_grad)),
-                                        stream_ptr()), 'invpref_adam_ranges_hip')
-
-
-@_fake('adam_ranges_')
-def _adam_ranges_fake(param, grad, exp_avg, exp_avg_sq, offsets, lengths, step, lr, beta1, beta2, eps, zero_grad,
-                      sched_state, sched_table, sched_slot):
-    return None
+    call('invpref_adam_ranges_hip', ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), offs, lens, k, int(step),
+         float(lr), float(beta1), float(beta2), float(eps), int(bool(zero_grad)), stream_ptr())
 
 
 # ------------------------------------------------------------------------------------------------ E-step
@@ -411,11 +346,10 @@ def _estep_call(tables, users, items, scores, implicit, eps_rows, old_envs, new_
         cw = torch.empty(t.env_num if want_weights else 0, dtype=torch.float32, device=dev)
         sw = torch.empty(N if want_weights else 0, dtype=torch.float32, device=dev)
         base = (C.c_float * t.env_num)(*[float(x) for x in eps_base])
-        check(lib().invpref_estep_perm_hip(C.byref(t), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), ptr(scores), N,
-                                           _capi.IMPLICIT if implicit else 0, ptr(perm_index), _PERM_BYTES[perm_index.dtype],
-                                           base, ptr(old_envs), ptr(new_envs), ptr(counts), ptr(diff),
-                                           ptr(cw) if want_weights else None, ptr(sw) if want_weights else None,
-                                           ptr(workspace), workspace.numel(), stream_ptr()), 'invpref_estep_perm_hip')
+        call('invpref_estep_perm_hip', C.byref(t), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), ptr(scores), N,
+             _capi.IMPLICIT if implicit else 0, ptr(perm_index), _PERM_BYTES[perm_index.dtype], base, ptr(old_envs),
+             ptr(new_envs), ptr(counts), ptr(diff), ptr(cw) if want_weights else None, ptr(sw) if want_weights else None,
+             ptr(workspace), workspace.numel(), stream_ptr())
         return counts, diff, cw, sw
     if old_envs is not None:
         _ids(old_envs, 'old_envs')
@@ -423,11 +357,10 @@ def _estep_call(tables, users, items, scores, implicit, eps_rows, old_envs, new_
     diff = torch.zeros(1, dtype=torch.int64, device=dev)
     cw = torch.empty(t.env_num if want_weights else 0, dtype=torch.float32, device=dev)
     sw = torch.empty(N if want_weights else 0, dtype=torch.float32, device=dev)
-    check(lib().invpref_estep_hip(C.byref(t), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), ptr(scores), N,
-                                  _capi.IMPLICIT if implicit else 0, ptr(eps_rows), ptr(old_envs), ptr(new_envs),
-                                  ptr(counts), ptr(diff), ptr(cw) if want_weights else None,
-                                  ptr(sw) if want_weights else None, ptr(workspace), workspace.numel(), stream_ptr()),
-          'invpref_estep_hip')
+    call('invpref_estep_hip', C.byref(t), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), ptr(scores), N,
+         _capi.IMPLICIT if implicit else 0, ptr(eps_rows), ptr(old_envs), ptr(new_envs), ptr(counts), ptr(diff),
+         ptr(cw) if want_weights else None, ptr(sw) if want_weights else None, ptr(workspace), workspace.numel(),
+         stream_ptr())
     return counts, diff, cw, sw
 
 
@@ -499,17 +432,10 @@ def _estep_fused(tables, users, items, scores, envs, implicit, perm_index, eps_b
         base, nbytes = (C.c_float * t.env_num)(*[float(x) for x in eps_base]), _PERM_BYTES[perm_index.dtype]
     if perm_table is not None:
         _capi._req(perm_table, torch.int32, 'perm_table')
-    check(lib().invpref_estep_fused_hip(C.byref(t), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), ptr(scores), N,
-                                        _capi.IMPLICIT if implicit else 0, ptr(perm_index), nbytes, base, ptr(perm_table),
-                                        ptr(envs), ptr(state), ptr(ring), 0 if ring is None else int(ring.shape[0]),
-                                        ptr(counts), ptr(diff), ptr(class_weights), ptr(workspace), workspace.numel(),
-                                        stream_ptr()), 'invpref_estep_fused_hip')
-
-
-@_fake('estep_fused_')
-def _estep_fused_fake(tables, users, items, scores, envs, implicit, perm_index, eps_base, perm_table, state, ring, counts, diff,
-                      class_weights, workspace):
-    return None
+    call('invpref_estep_fused_hip', C.byref(t), ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), ptr(scores), N,
+         _capi.IMPLICIT if implicit else 0, ptr(perm_index), nbytes, base, ptr(perm_table), ptr(envs), ptr(state), ptr(ring),
+         0 if ring is None else int(ring.shape[0]), ptr(counts), ptr(diff), ptr(class_weights), ptr(workspace),
+         workspace.numel(), stream_ptr())
 
 
 _define('stat_envs(Tensor envs, int env_num, bool want_sample_weights, Tensor(a!) workspace) -> (Tensor, Tensor, Tensor)')
@@ -521,9 +447,8 @@ def _stat_envs(envs, env_num, want_sample_weights, workspace):
     counts = torch.empty(env_num, dtype=torch.int64, device=dev)
     cw = torch.empty(env_num, dtype=torch.float32, device=dev)
     sw = torch.empty(N if want_sample_weights else 0, dtype=torch.float32, device=dev)
-    check(lib().invpref_stat_envs_hip(ptr(_ids(envs, 'envs')), N, int(env_num), ptr(counts), ptr(cw),
-                                      ptr(sw) if want_sample_weights else None, ptr(workspace), workspace.numel(),
-                                      stream_ptr()), 'invpref_stat_envs_hip')
+    call('invpref_stat_envs_hip', ptr(_ids(envs, 'envs')), N, int(env_num), ptr(counts), ptr(cw),
+         ptr(sw) if want_sample_weights else None, ptr(workspace), workspace.numel(), stream_ptr())
     return counts, cw, sw
 
 
@@ -543,8 +468,8 @@ def _sample_weights(envs, counts, n_total, env_num):
     _capi._req(counts, torch.int64, 'counts')
     cw = torch.empty(env_num, dtype=torch.float32, device=dev)
     sw = torch.empty(N, dtype=torch.float32, device=dev)
-    check(lib().invpref_sample_weights_hip(ptr(_ids(envs, 'envs')), N, ptr(counts), int(n_total), int(env_num), ptr(cw),
-                                           ptr(sw), stream_ptr()), 'invpref_sample_weights_hip')
+    call('invpref_sample_weights_hip', ptr(_ids(envs, 'envs')), N, ptr(counts), int(n_total), int(env_num), ptr(cw), ptr(sw),
+         stream_ptr())
     return cw, sw
 
 
@@ -563,8 +488,8 @@ def _predict(user_table, item_table, users, sigmoid):
     _f32(user_table, 'user_table'); _f32(item_table, 'item_table')
     n, (I, D) = users.numel(), item_table.shape
     out = torch.empty(n, I, dtype=torch.float32, device=users.device)
-    check(lib().invpref_predict_hip(ptr(user_table), ptr(item_table), ptr(_ids(users, 'users')), n, I, D,
-                                    int(bool(sigmoid)), ptr(out), stream_ptr()), 'invpref_predict_hip')
+    call('invpref_predict_hip', ptr(user_table), ptr(item_table), ptr(_ids(users, 'users')), n, I, D, int(bool(sigmoid)),
+         ptr(out), stream_ptr())
     return out
 
 
@@ -603,12 +528,11 @@ def _predict_topk(user_table, item_table, users, k, sigmoid, mask_ptr, mask_item
     items = torch.empty(n, k, dtype=torch.int32, device=dev)
     scores = torch.empty(n, k, dtype=torch.float32, device=dev)
     hits = torch.empty(n, k, dtype=torch.float32, device=dev)
-    L = lib()
-    nbytes = L.invpref_predict_topk_workspace_bytes(n, I, D, k)
+    nbytes = lib().invpref_predict_topk_workspace_bytes(n, I, D, k)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)   # (the caching allocator's memory)
-    check(L.invpref_predict_topk_hip(ptr(user_table), ptr(item_table), ptr(_ids(users, 'users')), n, I, D, int(bool(sigmoid)),
-                                     ptr(mp), ptr(mi), ptr(hp), ptr(hi), ptr(tp), ptr(ti), k, ptr(items), ptr(scores),
-                                     ptr(hits), ptr(ws), nbytes, stream_ptr()), 'invpref_predict_topk_hip')
+    call('invpref_predict_topk_hip', ptr(user_table), ptr(item_table), ptr(_ids(users, 'users')), n, I, D,
+         int(bool(sigmoid)), ptr(mp), ptr(mi), ptr(hp), ptr(hi), ptr(tp), ptr(ti), k, ptr(items), ptr(scores), ptr(hits),
+         ptr(ws), nbytes, stream_ptr())
     return items, scores, hits
 
 
@@ -639,13 +563,11 @@ def _rank_metrics(hits, truth_ptr, ks, disc, idcg, partition):
         if tuple(t.shape) != (nk, w):
             raise InvPrefError(f'{name} must be [{nk}, {w}], got {tuple(t.shape)}')
     out = torch.empty(3, nk, dtype=torch.float64, device=hits.device)
-    L = lib()
-    nbytes = L.invpref_rank_metrics_workspace_bytes(n, nk, partition)
+    nbytes = lib().invpref_rank_metrics_workspace_bytes(n, nk, partition)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=hits.device)
     karr = (C.c_int32 * max(nk, 1))(*ks)
-    check(L.invpref_rank_metrics_hip(ptr(hits), n, hits.stride(0) if n > 0 else K, K, ptr(truth_ptr),
-                                     C.cast(karr, C.c_void_p), nk, ptr(disc), ptr(idcg), int(partition), ptr(out), ptr(ws),
-                                     nbytes, stream_ptr()), 'invpref_rank_metrics_hip')
+    call('invpref_rank_metrics_hip', ptr(hits), n, hits.stride(0) if n > 0 else K, K, ptr(truth_ptr),
+         C.cast(karr, C.c_void_p), nk, ptr(disc), ptr(idcg), int(partition), ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -672,13 +594,11 @@ def _predict_topk_wide(user_table, item_table, users, k, sigmoid, mask_ptr, mask
     items = torch.empty(n, k, dtype=torch.int32, device=dev)
     scores = torch.empty(n, k, dtype=torch.float32, device=dev)
     hits = torch.empty(n, k, dtype=torch.float32, device=dev)
-    L = lib()
-    nbytes = L.invpref_predict_topk_wide_workspace_bytes(n, I, D, k)
+    nbytes = lib().invpref_predict_topk_wide_workspace_bytes(n, I, D, k)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    check(L.invpref_predict_topk_wide_hip(ptr(user_table), ptr(item_table), ptr(_ids(users, 'users')), n, I, D,
-                                          int(bool(sigmoid)), ptr(mp), ptr(mi), ptr(hp), ptr(hi), ptr(tp), ptr(ti), k,
-                                          ptr(items), ptr(scores), ptr(hits), ptr(ws), nbytes, stream_ptr()),
-          'invpref_predict_topk_wide_hip')
+    call('invpref_predict_topk_wide_hip', ptr(user_table), ptr(item_table), ptr(_ids(users, 'users')), n, I, D,
+         int(bool(sigmoid)), ptr(mp), ptr(mi), ptr(hp), ptr(hi), ptr(tp), ptr(ti), k, ptr(items), ptr(scores), ptr(hits),
+         ptr(ws), nbytes, stream_ptr())
     return items, scores, hits
 
 
@@ -708,14 +628,12 @@ def _rank_metrics_wide(hits, truth_ptr, ks, disc, idcg, partition):
         if t.dim() != 2 or t.shape[0] != nk or t.shape[1] < w:
             raise InvPrefError(f'{name} must be [{nk}, >= {w}], got {tuple(t.shape)}')
     out = torch.empty(3, nk, dtype=torch.float64, device=hits.device)
-    L = lib()
-    nbytes = L.invpref_rank_metrics_workspace_bytes(n, nk, partition)
+    nbytes = lib().invpref_rank_metrics_workspace_bytes(n, nk, partition)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=hits.device)
     karr = (C.c_int32 * max(nk, 1))(*ks)
-    check(L.invpref_rank_metrics_wide_hip(ptr(hits), n, hits.stride(0) if n > 0 else K, K, ptr(truth_ptr),
-                                          C.cast(karr, C.c_void_p), nk, ptr(disc), disc.shape[1], ptr(idcg), idcg.shape[1],
-                                          int(partition), ptr(out), ptr(ws), nbytes, stream_ptr()),
-          'invpref_rank_metrics_wide_hip')
+    call('invpref_rank_metrics_wide_hip', ptr(hits), n, hits.stride(0) if n > 0 else K, K, ptr(truth_ptr),
+         C.cast(karr, C.c_void_p), nk, ptr(disc), disc.shape[1], ptr(idcg), idcg.shape[1], int(partition), ptr(out), ptr(ws),
+         nbytes, stream_ptr())
     return out
 
 
@@ -735,12 +653,10 @@ def _interaction_counts(users, items, user_num, item_num):
         raise InvPrefError('interaction_counts: users and items differ in length')
     uc = torch.empty(user_num, dtype=torch.float64, device=dev)
     ic = torch.empty(item_num, dtype=torch.float64, device=dev)
-    L = lib()
-    nbytes = L.invpref_interaction_counts_workspace_bytes(user_num, item_num)
+    nbytes = lib().invpref_interaction_counts_workspace_bytes(user_num, item_num)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    check(L.invpref_interaction_counts_hip(ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), n, int(user_num),
-                                           int(item_num), ptr(uc), ptr(ic), ptr(ws), nbytes, stream_ptr()),
-          'invpref_interaction_counts_hip')
+    call('invpref_interaction_counts_hip', ptr(_ids(users, 'users')), ptr(_ids(items, 'items')), n, int(user_num),
+         int(item_num), ptr(uc), ptr(ic), ptr(ws), nbytes, stream_ptr())
     return uc, ic
 
 
@@ -766,13 +682,11 @@ def _count_propensity(user_cnt, item_cnt, users, items, kind, smooth_weight_coe)
             if t.numel() != n:
                 raise InvPrefError('count_propensity: users and items differ in length')
     out = torch.empty(n, dtype=torch.float32, device=dev)
-    L = lib()
-    nbytes = L.invpref_count_propensity_workspace_bytes()
+    nbytes = lib().invpref_count_propensity_workspace_bytes()
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(L.invpref_count_propensity_hip(ptr(user_cnt), 0 if user_cnt is None else user_cnt.numel(), ptr(item_cnt),
-                                         0 if item_cnt is None else item_cnt.numel(), ptr(users), ptr(items), n,
-                                         int(kind), float(smooth_weight_coe), ptr(out), ptr(ws), nbytes, stream_ptr()),
-          'invpref_count_propensity_hip')
+    call('invpref_count_propensity_hip', ptr(user_cnt), 0 if user_cnt is None else user_cnt.numel(), ptr(item_cnt),
+         0 if item_cnt is None else item_cnt.numel(), ptr(users), ptr(items), n, int(kind), float(smooth_weight_coe),
+         ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -793,12 +707,10 @@ def _naive_bayes_propensity(train_scores, uniform_scores, labels, user_num, item
         _f32(t, name)
     out = torch.empty(n, dtype=torch.float32, device=dev)
     lw = torch.empty(K, dtype=torch.float64, device=dev)
-    L = lib()
-    nbytes = L.invpref_naive_bayes_workspace_bytes(K)
+    nbytes = lib().invpref_naive_bayes_workspace_bytes(K)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    check(L.invpref_naive_bayes_propensity_hip(ptr(train_scores), n, ptr(uniform_scores), m, ptr(labels), K, int(user_num),
-                                               int(item_num), float(smooth_weight_coe), ptr(out), ptr(lw), ptr(ws), nbytes,
-                                               stream_ptr()), 'invpref_naive_bayes_propensity_hip')
+    call('invpref_naive_bayes_propensity_hip', ptr(train_scores), n, ptr(uniform_scores), m, ptr(labels), K, int(user_num),
+         int(item_num), float(smooth_weight_coe), ptr(out), ptr(lw), ptr(ws), nbytes, stream_ptr())
     return out, lw
 
 
@@ -815,8 +727,7 @@ _define('snips_scale(Tensor weights, int batch_size) -> Tensor')
 def _snips_scale(weights, batch_size):
     _f32(weights, 'weights')
     out = torch.empty_like(weights)
-    check(lib().invpref_snips_scale_hip(ptr(weights), weights.numel(), int(batch_size), ptr(out), stream_ptr()),
-          'invpref_snips_scale_hip')
+    call('invpref_snips_scale_hip', ptr(weights), weights.numel(), int(batch_size), ptr(out), stream_ptr())
     return out
 
 
@@ -826,25 +737,36 @@ def _snips_scale_fake(weights, batch_size):
 
 
 # ------------------------------------------------------------------------------------------------ ExpoMF exposure model
-def _expo_tables(user_table, item_table):
+def _pair_tables(op, user_table, item_table, grad_user=None, grad_item=None, outs=(), workspace=None):
+    """The opening checks of the terms on a user and an item table: fp32 [U, D] and [I, D]; gradient tables (if the term has
+    them) of those shapes; optional fp32 scalar outputs `outs` = (name, tensor)...; a uint8 workspace.  Returns (U, I, D)."""
     _f32(user_table, 'user_table')
     _f32(item_table, 'item_table')
     if user_table.dim() != 2 or item_table.dim() != 2 or user_table.shape[1] != item_table.shape[1]:
-        raise InvPrefError('exposure: user_table [U, D] and item_table [I, D] must share D')
-    return user_table.shape[0], item_table.shape[0], user_table.shape[1]
+        raise InvPrefError(f'{op}: user_table [U, D] and item_table [I, D] must share D')
+    U, I, D = user_table.shape[0], item_table.shape[0], user_table.shape[1]
+    if grad_user is not None:
+        _f32(grad_user, 'grad_user')
+        _f32(grad_item, 'grad_item')
+        if tuple(grad_user.shape) != (U, D) or tuple(grad_item.shape) != (I, D):
+            raise InvPrefError(f'{op}: grad_user / grad_item must have the shapes of user_table / item_table')
+    for name, x in outs:
+        _f32(x, name)
+    _capi._req(workspace, torch.uint8, 'workspace')
+    return U, I, D
 
 
 def _expo_pass(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, mu_out, prob_out, ws):
-    U, I, D = _expo_tables(user_table, item_table)
+    U, I, D = _pair_tables('exposure', user_table, item_table, workspace=ws)
     _f32(mu, 'mu')
     if mu.numel() != I:
         raise InvPrefError(f'exposure: mu has {mu.numel()} entries for {I} items')
     if users is not None:
         _ids(users, 'users')
         n_users = users.numel()
-    check(lib().invpref_exposure_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(users), int(n_users), float(lam_y),
-                                     float(eps), ptr(mu), float(a), float(b), ptr(mu_out), ptr(prob_out), ptr(ws),
-                                     0 if ws is None else ws.numel(), stream_ptr()), 'invpref_exposure_hip')
+    call('invpref_exposure_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(users), int(n_users), float(lam_y),
+         float(eps), ptr(mu), float(a), float(b), ptr(mu_out), ptr(prob_out), ptr(ws), 0 if ws is None else ws.numel(),
+         stream_ptr())
 
 
 _define('exposure_probability(Tensor user_table, Tensor item_table, Tensor? users, int n_users, Tensor mu, float lam_y, '
@@ -872,13 +794,7 @@ _define('exposure_prior_(Tensor user_table, Tensor item_table, Tensor? users, in
 
 @_impl('exposure_prior_')
 def _exposure_prior(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, workspace):
-    _capi._req(workspace, torch.uint8, 'workspace')
     _expo_pass(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, mu, None, workspace)
-
-
-@_fake('exposure_prior_')
-def _exposure_prior_fake(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, workspace):
-    return None
 
 
 _define('exposure_weights_(Tensor user_table, Tensor item_table, Tensor users, Tensor items, Tensor? positive, Tensor mu, '
@@ -887,11 +803,10 @@ _define('exposure_weights_(Tensor user_table, Tensor item_table, Tensor users, T
 
 @_impl('exposure_weights_')
 def _exposure_weights(user_table, item_table, users, items, positive, mu, lam_y, eps, weight_exp, out):
-    U, I, D = _expo_tables(user_table, item_table)
+    U, I, D = _pair_tables('exposure_weights', user_table, item_table, outs=(('out', out),))
     _ids(users, 'users')
     _ids(items, 'items')
     _f32(mu, 'mu')
-    _f32(out, 'out')
     n = users.numel()
     if items.numel() != n or out.numel() != n or (positive is not None and positive.numel() != n):
         raise InvPrefError('exposure_weights: users, items, positive and out differ in length')
@@ -899,14 +814,8 @@ def _exposure_weights(user_table, item_table, users, items, positive, mu, lam_y,
         raise InvPrefError(f'exposure_weights: mu has {mu.numel()} entries for {I} items')
     if positive is not None:
         _capi._req(positive, torch.bool, 'positive')
-    check(lib().invpref_exposure_weights_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(items), ptr(positive),
-                                             n, float(lam_y), float(eps), ptr(mu), float(weight_exp), ptr(out),
-                                             stream_ptr()), 'invpref_exposure_weights_hip')
-
-
-@_fake('exposure_weights_')
-def _exposure_weights_fake(user_table, item_table, users, items, positive, mu, lam_y, eps, weight_exp, out):
-    return None
+    call('invpref_exposure_weights_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(items), ptr(positive), n,
+         float(lam_y), float(eps), ptr(mu), float(weight_exp), ptr(out), stream_ptr())
 
 
 # ---- WMF imputation term (baseline_train.py:157-228; csrc/invpref_impute.hip)
@@ -917,26 +826,13 @@ _define('impute_grad_(Tensor user_table, Tensor item_table, Tensor sel_users, Te
 @_impl('impute_grad_')
 def _impute_grad(user_table, item_table, sel_users, sel_items, imputation_coe, grad_user, grad_item, loss_out, term_out,
                  workspace):
-    U, I, D = _expo_tables(user_table, item_table)
-    _f32(grad_user, 'grad_user')
-    _f32(grad_item, 'grad_item')
-    if tuple(grad_user.shape) != (U, D) or tuple(grad_item.shape) != (I, D):
-        raise InvPrefError('impute_grad: grad_user / grad_item must have the shapes of user_table / item_table')
+    U, I, D = _pair_tables('impute_grad', user_table, item_table, grad_user, grad_item,
+                           (('loss_out', loss_out), ('term_out', term_out)), workspace)
     _capi._req(sel_users, torch.int32, 'sel_users')
     _capi._req(sel_items, torch.int32, 'sel_items')
-    _f32(loss_out, 'loss_out')
-    _f32(term_out, 'term_out')
-    _capi._req(workspace, torch.uint8, 'workspace')
-    check(lib().invpref_impute_grad_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(sel_users), sel_users.numel(),
-                                        ptr(sel_items), sel_items.numel(), float(imputation_coe), ptr(grad_user),
-                                        ptr(grad_item), ptr(loss_out), ptr(term_out), ptr(workspace), workspace.numel(),
-                                        stream_ptr()), 'invpref_impute_grad_hip')
-
-
-@_fake('impute_grad_')
-def _impute_grad_fake(user_table, item_table, sel_users, sel_items, imputation_coe, grad_user, grad_item, loss_out, term_out,
-                      workspace):
-    return None
+    call('invpref_impute_grad_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(sel_users), sel_users.numel(),
+         ptr(sel_items), sel_items.numel(), float(imputation_coe), ptr(grad_user), ptr(grad_item), ptr(loss_out),
+         ptr(term_out), ptr(workspace), workspace.numel(), stream_ptr())
 
 
 # ---- fairness-MF item-popularity term (baseline_train.py:279-313; csrc/invpref_fairness.hip)
@@ -948,11 +844,8 @@ _define('fairness_grad_(Tensor user_table, Tensor item_table, Tensor users, Tens
 @_impl('fairness_grad_')
 def _fairness_grad(user_table, item_table, users, user_mult, draw_items, item_counts, table, fairness_coe, batch, grad_user,
                    grad_item, loss_out, term_out, workspace):
-    U, I, D = _expo_tables(user_table, item_table)
-    _f32(grad_user, 'grad_user')
-    _f32(grad_item, 'grad_item')
-    if tuple(grad_user.shape) != (U, D) or tuple(grad_item.shape) != (I, D):
-        raise InvPrefError('fairness_grad: grad_user / grad_item must have the shapes of user_table / item_table')
+    U, I, D = _pair_tables('fairness_grad', user_table, item_table, grad_user, grad_item,
+                           (('loss_out', loss_out), ('term_out', term_out)), workspace)
     for x, name in ((users, 'users'), (user_mult, 'user_mult'), (draw_items, 'draw_items'), (item_counts, 'item_counts')):
         _capi._req(x, torch.int32, name)
     if user_mult.numel() != users.numel():
@@ -960,20 +853,9 @@ def _fairness_grad(user_table, item_table, users, user_mult, draw_items, item_co
     if item_counts.numel() != I:
         raise InvPrefError(f'fairness_grad: item_counts has {item_counts.numel()} entries for {I} items')
     _f32(table, 'table')
-    _f32(loss_out, 'loss_out')
-    _f32(term_out, 'term_out')
-    _capi._req(workspace, torch.uint8, 'workspace')
-    check(lib().invpref_fairness_grad_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(user_mult), users.numel(),
-                                          ptr(draw_items), draw_items.numel(), ptr(item_counts), ptr(table), table.numel(),
-                                          float(fairness_coe), int(batch), ptr(grad_user), ptr(grad_item), ptr(loss_out),
-                                          ptr(term_out), ptr(workspace), workspace.numel(), stream_ptr()),
-          'invpref_fairness_grad_hip')
-
-
-@_fake('fairness_grad_')
-def _fairness_grad_fake(user_table, item_table, users, user_mult, draw_items, item_counts, table, fairness_coe, batch, grad_user,
-                        grad_item, loss_out, term_out, workspace):
-    return None
+    call('invpref_fairness_grad_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(user_mult), users.numel(),
+         ptr(draw_items), draw_items.numel(), ptr(item_counts), ptr(table), table.numel(), float(fairness_coe), int(batch),
+         ptr(grad_user), ptr(grad_item), ptr(loss_out), ptr(term_out), ptr(workspace), workspace.numel(), stream_ptr())
 
 
 # ---- CVIB information term (baseline_train.py:584-647, :978-1044; csrc/invpref_cvib.hip)
@@ -1004,18 +886,12 @@ def _cvib_index(users, items, step_lo, step_n, draws, user_num, item_num, index)
     if users.numel() != items.numel():
         raise InvPrefError('cvib_index: users and items must have the same length')
     keys = torch.empty(steps * 2 * 2 * cap, dtype=torch.int64, device=users.device)
-    check(lib().invpref_cvib_index_keys_hip(ptr(users), ptr(items), ptr(step_lo), ptr(step_n), steps, ptr(draws), cap,
-                                            int(user_num), int(item_num), ptr(keys), stream_ptr()), 'invpref_cvib_index_keys_hip')
+    call('invpref_cvib_index_keys_hip', ptr(users), ptr(items), ptr(step_lo), ptr(step_n), steps, ptr(draws), cap,
+         int(user_num), int(item_num), ptr(keys), stream_ptr())
     # unique keys: the result does not depend on the sort.  torch.sort also returns an int64 permutation, which nothing here
     # needs: it is dropped at once, but it and the unsorted keys are alive during the sort (see ops.cvib_index)
     keys = torch.sort(keys).values
-    check(lib().invpref_cvib_index_hip(ptr(keys), steps, cap, int(user_num), int(item_num), ptr(index), stream_ptr()),
-          'invpref_cvib_index_hip')
-
-
-@_fake('cvib_index_')
-def _cvib_index_fake(users, items, step_lo, step_n, draws, user_num, item_num, index):
-    return None
+    call('invpref_cvib_index_hip', ptr(keys), steps, cap, int(user_num), int(item_num), ptr(index), stream_ptr())
 
 
 _define('cvib_grad_(Tensor user_table, Tensor item_table, Tensor users, Tensor items, Tensor draw_users, Tensor draw_items, '
@@ -1027,11 +903,9 @@ _define('cvib_grad_(Tensor user_table, Tensor item_table, Tensor users, Tensor i
 @_impl('cvib_grad_')
 def _cvib_grad(user_table, item_table, users, items, draw_users, draw_items, index, implicit, alpha, gamma, info_coe, eps,
                grad_user, grad_item, loss_out, info_out, pbar_out, qbar_out, workspace):
-    U, I, D = _expo_tables(user_table, item_table)
-    _f32(grad_user, 'grad_user')
-    _f32(grad_item, 'grad_item')
-    if tuple(grad_user.shape) != (U, D) or tuple(grad_item.shape) != (I, D):
-        raise InvPrefError('cvib_grad: grad_user / grad_item must have the shapes of user_table / item_table')
+    U, I, D = _pair_tables('cvib_grad', user_table, item_table, grad_user, grad_item,
+                           (('loss_out', loss_out), ('info_out', info_out), ('pbar_out', pbar_out), ('qbar_out', qbar_out)),
+                           workspace)
     _ids(users, 'users')
     _ids(items, 'items')
     _capi._req(draw_users, torch.int32, 'draw_users')
@@ -1042,17 +916,7 @@ def _cvib_grad(user_table, item_table, users, items, draw_users, draw_items, ind
         raise InvPrefError(f'cvib_grad: items, draw_users and draw_items must have the {B} entries of users')
     if index.dim() != 3 or index.shape[0] != 2 or index.shape[2] != 2 or index.shape[1] < 2 * B:
         raise InvPrefError(f'cvib_grad: index must be int32 [2, at least {2 * B}, 2] (one step of cvib_index_)')
-    for n, x in (('loss_out', loss_out), ('info_out', info_out), ('pbar_out', pbar_out), ('qbar_out', qbar_out)):
-        _f32(x, n)
-    _capi._req(workspace, torch.uint8, 'workspace')
-    check(lib().invpref_cvib_grad_hip(ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(items), B, ptr(draw_users),
-                                      ptr(draw_items), ptr(index), index.shape[1], _capi.IMPLICIT if implicit else 0,
-                                      float(alpha), float(gamma), float(info_coe), float(eps), ptr(grad_user), ptr(grad_item),
-                                      ptr(loss_out), ptr(info_out), ptr(pbar_out), ptr(qbar_out), ptr(workspace),
-                                      workspace.numel(), stream_ptr()), 'invpref_cvib_grad_hip')
-
-
-@_fake('cvib_grad_')
-def _cvib_grad_fake(user_table, item_table, users, items, draw_users, draw_items, index, implicit, alpha, gamma, info_coe, eps,
-                    grad_user, grad_item, loss_out, info_out, pbar_out, qbar_out, workspace):
-    return None
+    call('invpref_cvib_grad_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(items), B, ptr(draw_users),
+         ptr(draw_items), ptr(index), index.shape[1], _capi.IMPLICIT if implicit else 0, float(alpha), float(gamma),
+         float(info_coe), float(eps), ptr(grad_user), ptr(grad_item), ptr(loss_out), ptr(info_out), ptr(pbar_out),
+         ptr(qbar_out), ptr(workspace), workspace.numel(), stream_ptr())

@@ -774,7 +774,7 @@ class _InvPrefTrainManager:
         if steps_ahead > self._SCHED_N:
             raise _capi.InvPrefError(f'a replayed run of {steps_ahead} optimiser steps does not fit into the device-side '
                                      f'Adam schedule of {self._SCHED_N} rows (graphs_enabled() / _graph_epochs bound it)')
-        st, L = self.state, _capi.lib()
+        st = self.state
         if self._sched is None:
             table = torch.zeros(self._SCHED_N, 8, dtype=torch.float32, device=self.device)
             state = torch.zeros(32, dtype=torch.int32, device=self.device)
@@ -785,8 +785,7 @@ class _InvPrefTrainManager:
         stale_alpha = self.update_alpha and not self._sched_synced   # the step -> (epoch, minibatch) mapping moved
         if first < sc['base'] or first + steps_ahead > sc['base'] + self._SCHED_N or stale_alpha:
             host = np.zeros((self._SCHED_N, 8), np.float32)
-            _capi.check(L.invpref_adam_schedule_fill(host.ctypes.data, first, self._SCHED_N, self.lr, 0.9, 0.999, 1e-8),
-                        'invpref_adam_schedule_fill')
+            _capi.call('invpref_adam_schedule_fill', host.ctypes.data, first, self._SCHED_N, self.lr, 0.9, 0.999, 1e-8)
             if self.update_alpha:
                 j = np.arange(self._SCHED_N)
                 e1 = (self.epoch_cnt + j // self.batch_num + 1).astype(np.float64) * self.batch_num

@@ -4,8 +4,8 @@ it: per-user row sums, np.sum in 8192-element pairwise chunks, partition sums in
 device, a workspace that never falls as the batch grows, and every kernel instance scratch-free.  If a numpy release
 changes its summation order, the first tests here fail -- not the GPU tests, as drift."""
 import ctypes as C
+import json
 import os
-import re
 import subprocess
 import sys
 import tempfile
@@ -22,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_regs  # noqa: E402
 import rank_order as R  # noqa: E402
 
-HEADER = open(os.path.join(ROOT, 'include', 'invpref_hip.h')).read()
+with open(os.path.join(ROOT, 'tests', 'abi_signatures.json')) as _f:
+    ABI = json.load(_f)['functions']   # ABI version 6 as recorded; test_capi_exports.py holds the header to it
 EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -2, -3
 NAMES = ('invpref_rank_metrics_workspace_bytes', 'invpref_rank_metrics_hip')
 SIZES = (1, 7, 8, 127, 128, 129, 8191, 8192, 8193, 50000)
@@ -98,26 +99,12 @@ def lib():
     return _capi.lib()
 
 
-def _params(name):
-    code = re.sub(r'/\*.*?\*/', '', HEADER, flags=re.S)
-    m = re.search(r'(\w+)\s+' + name + r'\s*\((.*?)\);', code, re.S)
-    return m.group(1), [p.strip() for p in m.group(2).split(',')]
-
-
-def _ctype_of(param):
-    if '*' in param:
-        return C.c_void_p
-    t = param.rsplit(' ', 1)[0].replace('const ', '').strip()
-    return {'int64_t': C.c_int64, 'int32_t': C.c_int32, 'int': C.c_int, 'size_t': C.c_size_t}[t]
-
-
 def test_exported_with_header_signatures(lib):
     for name in NAMES:
         assert name in _capi.EXPORTS
-        ret, params = _params(name)
-        fn = getattr(lib, name)
-        assert [_ctype_of(p) for p in params] == list(fn.argtypes), name
-        assert fn.restype == {'size_t': C.c_size_t, 'int': C.c_int}[ret], name
+        fn, want = getattr(lib, name), ABI[name]
+        assert [t.__name__ for t in fn.argtypes] == want['argtypes'], name
+        assert fn.restype.__name__ == want['restype'], name
     assert lib.invpref_abi_version() == 6
 
 

@@ -2,6 +2,7 @@
 include/invpref_hip.h, argument validation without a device, workspace sizes that never fall as the batch grows, the
 Python layer's limits and tables, and both kernels scratch-free in the cross-compiled listing."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -18,6 +19,8 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import kernel_regs  # noqa: E402
 
 HEADER = open(os.path.join(ROOT, 'include', 'invpref_hip.h')).read()
+with open(os.path.join(ROOT, 'tests', 'abi_signatures.json')) as _f:
+    ABI = json.load(_f)['functions']   # ABI version 6 as recorded; test_capi_exports.py holds the header to it
 EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -2, -3
 NAMES = ('invpref_topk_rows_workspace_bytes', 'invpref_topk_rows_hip', 'invpref_predict_topk_wide_workspace_bytes',
          'invpref_predict_topk_wide_hip', 'invpref_rank_metrics_wide_hip')
@@ -29,26 +32,12 @@ def lib():
     return _capi.lib()
 
 
-def _params(name):
-    code = re.sub(r'/\*.*?\*/', '', HEADER, flags=re.S)
-    m = re.search(r'(\w+)\s+' + name + r'\s*\((.*?)\);', code, re.S)
-    return m.group(1), [p.strip() for p in m.group(2).split(',')]
-
-
-def _ctype_of(param):
-    if '*' in param:
-        return C.c_void_p
-    t = param.rsplit(' ', 1)[0].replace('const ', '').strip()
-    return {'int64_t': C.c_int64, 'int32_t': C.c_int32, 'int': C.c_int, 'size_t': C.c_size_t}[t]
-
-
 def test_exported_with_header_signatures(lib):
     for name in NAMES:
         assert name in _capi.EXPORTS
-        ret, params = _params(name)
-        fn = getattr(lib, name)
-        assert [_ctype_of(p) for p in params] == list(fn.argtypes), name
-        assert fn.restype == {'size_t': C.c_size_t, 'int': C.c_int}[ret], name
+        fn, want = getattr(lib, name), ABI[name]
+        assert [t.__name__ for t in fn.argtypes] == want['argtypes'], name
+        assert fn.restype.__name__ == want['restype'], name
     assert re.search(r'#define INVPREF_MAX_TOPK_WIDE 1024\b', HEADER)
     assert _capi.MAX_TOPK_WIDE == 1024
     assert lib.invpref_abi_version() == 6
