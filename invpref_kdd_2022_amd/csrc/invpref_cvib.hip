@@ -46,7 +46,7 @@
 // p_i and log p_i are float64, so that happens below x = -745 only (NaN in `info` and in that pair's two rows, as there);
 // between the two the term is finite where the reference's is not.  A qbar of exactly 0 or 1 gives infinite coefficients in
 // both.
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -458,35 +458,28 @@ int invpref_cvib_grad_hip(const float *user_table, int64_t user_num, const float
     const int U = (int)user_num, I = (int)item_num, D = (int)factor_num, B = (int)batch;
     const int implicit = (flags & INVPREF_IMPLICIT) ? 1 : 0;
     const float eps32 = (float)eps;   // the one value of every clip: the per-pair kernel and the fold both take this
-    const bool vec = D % 4 == 0 && !((reinterpret_cast<uintptr_t>(user_table) | reinterpret_cast<uintptr_t>(item_table) |
-                                      reinterpret_cast<uintptr_t>(grad_user) | reinterpret_cast<uintptr_t>(grad_item)) & 15u);
-    const int nc = nc_of(D);
+    const bool vec = rows_vec_ok(D, user_table, item_table, grad_user, grad_item);
     const int2 *idx = reinterpret_cast<const int2 *>(index);
     const unsigned sgrid = (unsigned)((2 * L.nchunk + 15) / 16);
-    int rc = 0;
     auto run = [&](auto NCt, auto VECt) {
+        int rc;
         constexpr int NC = decltype(NCt)::value;
         constexpr bool VEC = decltype(VECt)::value;
         hipLaunchKernelGGL((cvib_means_kernel<NC, VEC>), dim3((unsigned)L.nwg), dim3(256), 0, st, user_table, U, item_table, I, D,
                            users, items, B, draw_users, draw_items, implicit, eps32, wt, partials);
-        if ((rc = (int)hipGetLastError())) return;
+        if ((rc = (int)hipGetLastError())) return rc;
         hipLaunchKernelGGL(cvib_fold_kernel, dim3(1), dim3(64), 0, st, partials, L.nwg, (double)batch, implicit, alpha, gamma,
                            info_coe, (double)eps32, rec, loss_out, info_out, pbar_out, qbar_out);
-        if ((rc = (int)hipGetLastError())) return;
+        if ((rc = (int)hipGetLastError())) return rc;
         hipLaunchKernelGGL((cvib_scatter_kernel<NC, VEC>), dim3(sgrid), dim3(256), 0, st, user_table, U, item_table, I, D, users,
                            items, B, draw_users, draw_items, idx, index_stride, L.C, L.nchunk, rec, wt,
                            grad_user, grad_item, part, L.Dp);
-        if ((rc = (int)hipGetLastError())) return;
+        if ((rc = (int)hipGetLastError())) return rc;
         hipLaunchKernelGGL((cvib_boundary_kernel<NC, VEC>), dim3(sgrid), dim3(256), 0, st, idx, index_stride, B, L.C, L.nchunk, U,
                            I, D, L.Dp, part, grad_user, grad_item);
-        rc = (int)hipGetLastError();
+        return (int)hipGetLastError();
     };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (nc == 1) vec ? run(std::integral_constant<int, 1>{}, T{}) : run(std::integral_constant<int, 1>{}, F{});
-    else if (nc == 2) vec ? run(std::integral_constant<int, 2>{}, T{}) : run(std::integral_constant<int, 2>{}, F{});
-    else vec ? run(std::integral_constant<int, 4>{}, T{}) : run(std::integral_constant<int, 4>{}, F{});
-    return rc;
+    return with_int<1, 2, 4>(nc_of(D), [&](auto nc_c) { return with_bool(vec, [&](auto vec_c) { return run(nc_c, vec_c); }); });
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // per test user on the rating matrix -- train-item masking, item-pool highlighting, top-k selection and
 // the hit labels (evaluate.py:88-112, :11-19) -- and the error sums of the explicit evaluator
 // (evaluate.py:199-210).  The rating matrix itself comes from predict_kernel (invpref_kernels.hip).
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 using namespace invpref;
 
@@ -383,11 +383,7 @@ int invpref_eval_topk_hip(const float *ratings, int64_t n_users, int64_t n_items
     // the radix select beyond 4 096 items; the k-pass kernels below it
     if (n_items > 4096 && n_items <= (1 << 20)) {
         const size_t lds_sel = sizeof(unsigned) * 2 * (((size_t)n_items + 31) / 32);
-        if (lds_sel > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(topk_select_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sel);
-            if (e != hipSuccess) return (int)e;
-        }
+        if (hipError_t e = ensure_lds(topk_select_kernel, lds_sel)) return (int)e;
         hipLaunchKernelGGL(topk_select_kernel, dim3((unsigned)n_users), dim3(256), lds_sel, (hipStream_t)stream, ratings, n_users,
                            (int)n_items, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, (int)k,
                            out_items, out_hits);
@@ -395,21 +391,13 @@ int invpref_eval_topk_hip(const float *ratings, int64_t n_users, int64_t n_items
     }
     if (lds > 160 * 1024) {   // the four staged rows exceed the CU's LDS: bit-set form, one workgroup per user
         const size_t lds_bits = sizeof(unsigned) * 3 * (((size_t)n_items + 31) / 32);
-        if (lds_bits > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(topk_mask_big_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bits);
-            if (e != hipSuccess) return (int)e;
-        }
+        if (hipError_t e = ensure_lds(topk_mask_big_kernel, lds_bits)) return (int)e;
         hipLaunchKernelGGL(topk_mask_big_kernel, dim3((unsigned)n_users), dim3(256), lds_bits, (hipStream_t)stream, ratings,
                            n_users, (int)n_items, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr,
                            truth_items, (int)k, out_items, out_hits);
         return (int)hipGetLastError();
     }
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(topk_mask_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (hipError_t e = ensure_lds(topk_mask_kernel, lds)) return (int)e;
     const unsigned nb = (unsigned)((n_users + 3) / 4);
     hipLaunchKernelGGL(topk_mask_kernel, dim3(nb), dim3(256), lds, (hipStream_t)stream, ratings, n_users, (int)n_items,
                        mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, (int)k, out_items,

@@ -14,7 +14,7 @@
 // for bit; the rest of the posterior uses the hardware exponential (nothing here feeds an argmin).  No float atomics: the
 // column sums are per-lane float64 chains over a range's users, one fixed butterfly, per-range partials in the workspace and a
 // fold in range order -- the same bits on every device and every run.
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -234,31 +234,6 @@ Geometry geometry(int64_t n_users, int64_t item_num) {
     return g;
 }
 
-template <int DC, bool VEC>
-int launch_pass(const Geometry &g, const float *ut, int64_t U, const float *it, int I, int D, const int64_t *users, int64_t n,
-                const float *mu, ExpoConsts kc, double *partials, float *prob_out, hipStream_t st) {
-    constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(exposure_pass_kernel<DC, VEC>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return (int)attr;
-    hipLaunchKernelGGL((exposure_pass_kernel<DC, VEC>), dim3((unsigned)g.gx, (unsigned)g.ranges), dim3(256), lds, st, ut, U,
-                       it, I, D, users, n, mu, kc, g.tiles_per, partials, prob_out);
-    return (int)hipGetLastError();
-}
-
-template <int NC, bool VEC>
-int launch_weights(const float *ut, int64_t U, const float *it, int64_t I, int D, const int64_t *users, const int64_t *items,
-                   const uint8_t *positive, int64_t n, const float *mu, ExpoConsts kc, float e, float *w, hipStream_t st) {
-    const int64_t blocks = (n + kThreads / kRow - 1) / (kThreads / kRow);
-    hipLaunchKernelGGL((exposure_weights_kernel<NC, VEC>), dim3((unsigned)blocks), dim3(kThreads), 0, st, ut, U, it, I, D,
-                       users, items, positive, n, mu, kc, e, w);
-    return (int)hipGetLastError();
-}
-
-bool aligned16(const void *a, const void *b) {
-    return !((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u);
-}
-
 }  // namespace
 
 extern "C" {
@@ -284,15 +259,16 @@ int invpref_exposure_hip(const float *user_table, int64_t user_num, const float 
     auto *partials = mu_out ? reinterpret_cast<double *>(workspace) : nullptr;
     if (n_users > 0) {
         const ExpoConsts kc = expo_consts(lam_y, eps);
-        const bool vec = D % 4 == 0 && aligned16(user_table, item_table);
-        const int dc = nc_of(D);
-        int rc;
-        if (dc == 1) rc = vec ? launch_pass<1, true>(g, user_table, user_num, item_table, I, D, users, n_users, mu, kc, partials, prob_out, st)
-                              : launch_pass<1, false>(g, user_table, user_num, item_table, I, D, users, n_users, mu, kc, partials, prob_out, st);
-        else if (dc == 2) rc = vec ? launch_pass<2, true>(g, user_table, user_num, item_table, I, D, users, n_users, mu, kc, partials, prob_out, st)
-                                   : launch_pass<2, false>(g, user_table, user_num, item_table, I, D, users, n_users, mu, kc, partials, prob_out, st);
-        else rc = vec ? launch_pass<4, true>(g, user_table, user_num, item_table, I, D, users, n_users, mu, kc, partials, prob_out, st)
-                      : launch_pass<4, false>(g, user_table, user_num, item_table, I, D, users, n_users, mu, kc, partials, prob_out, st);
+        const int rc = with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
+            return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
+                constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * decltype(dc_c)::value + 4);
+                const auto pass = exposure_pass_kernel<decltype(dc_c)::value, decltype(vec_c)::value>;
+                if (hipError_t e = ensure_lds(pass, lds)) return (int)e;
+                hipLaunchKernelGGL(pass, dim3((unsigned)g.gx, (unsigned)g.ranges), dim3(256), lds, st, user_table, user_num,
+                                   item_table, I, D, users, n_users, mu, kc, g.tiles_per, partials, prob_out);
+                return (int)hipGetLastError();
+            });
+        });
         if (rc) return rc;
     }
     if (mu_out) {
@@ -317,13 +293,15 @@ int invpref_exposure_weights_hip(const float *user_table, int64_t user_num, cons
     const ExpoConsts kc = expo_consts(lam_y, eps);
     const float e = (float)weight_exp;
     const int D = (int)factor_num;
-    const bool vec = D % 4 == 0 && aligned16(user_table, item_table);
-    const int nc = nc_of(D);
-#define INVPREF_EXPO_W(NC, V) launch_weights<NC, V>(user_table, user_num, item_table, item_num, D, users, items, positive, n, mu, kc, e, weights, st)
-    if (nc == 1) return vec ? INVPREF_EXPO_W(1, true) : INVPREF_EXPO_W(1, false);
-    if (nc == 2) return vec ? INVPREF_EXPO_W(2, true) : INVPREF_EXPO_W(2, false);
-    return vec ? INVPREF_EXPO_W(4, true) : INVPREF_EXPO_W(4, false);
-#undef INVPREF_EXPO_W
+    const int64_t blocks = (n + kThreads / kRow - 1) / (kThreads / kRow);
+    return with_int<1, 2, 4>(nc_of(D), [&](auto nc_c) {
+        return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
+            hipLaunchKernelGGL((exposure_weights_kernel<decltype(nc_c)::value, decltype(vec_c)::value>), dim3((unsigned)blocks),
+                               dim3(kThreads), 0, st, user_table, user_num, item_table, item_num, D, users, items, positive, n, mu,
+                               kc, e, weights);
+            return (int)hipGetLastError();
+        });
+    });
 }
 
 }  // extern "C"

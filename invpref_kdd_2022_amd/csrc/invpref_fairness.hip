@@ -20,7 +20,7 @@
 //                  over a segment of the users) as dX . W on the matrix cores, two-level sums, waves folded in order
 //   6. fold        item rows: segments in order, positions of one item in position order, ONE writer per row; the loss
 // No float atomics, every sum in a fixed order: the same bits on every run.
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 #include <algorithm>
 
@@ -369,38 +369,14 @@ __global__ __launch_bounds__(256) void fair_fold_kernel(const float *__restrict_
     }
 }
 
-template <int DC>
-int launch_scores(const float *Pu, int U, const float *Qi, int I, int D, bool vec, const int32_t *users, int nu,
-                  const int32_t *idx, int J, const Layout &l, float *R, hipStream_t st) {
-    hipLaunchKernelGGL((fair_scores_kernel<DC>), dim3((unsigned)(l.nuP / 16)), dim3(256), 0, st, Pu, U, Qi, I, D, vec, users, nu,
-                       idx, J, (int)l.JP, R);
-    return (int)hipGetLastError();
-}
-
 template <int DC, bool USER>
 int launch_side(const float *dX, const Layout &l, const float *W, int n_rows, int D, const int32_t *sids, int n_sids,
                 const int32_t *oids, int n_o, int lim_o, float *out, hipStream_t st) {
     constexpr size_t lds = sizeof(float) * 4 * 16 * (64 * DC + 4);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(fair_side_kernel<DC, USER>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return (int)attr;
+    if (hipError_t e = ensure_lds(fair_side_kernel<DC, USER>, lds)) return (int)e;
     const dim3 grid((unsigned)((n_o + 15) / 16), USER ? 1u : (unsigned)l.nseg);
     hipLaunchKernelGGL((fair_side_kernel<DC, USER>), grid, dim3(256), lds, st, dX, (int)l.JP, (int)l.nuP, W, n_rows, D, sids,
                        n_sids, oids, n_o, lim_o, out);
-    return (int)hipGetLastError();
-}
-
-template <bool TAB_LDS>
-int launch_product(const float *R, const Layout &l, const int32_t *cpos, const float *tab, int tab_len, const int32_t *mult,
-                   int nu, float scale, float *dX, double *partials, hipStream_t st) {
-    const size_t lds = sizeof(float) * (32 * (kKC + 4) + kKC + (TAB_LDS ? tab_len : 0));
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(fair_product_kernel<TAB_LDS>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)(sizeof(float) * (32 * (kKC + 4) + kKC + kTabLds)));
-    if (attr != hipSuccess) return (int)attr;
-    const dim3 grid((unsigned)(l.nuP / 32), (unsigned)((l.JP + kJB - 1) / kJB));
-    hipLaunchKernelGGL((fair_product_kernel<TAB_LDS>), grid, dim3(256), lds, st, R, (int)l.JP, cpos, tab, tab_len, mult, nu,
-                       scale, dX, partials);
     return (int)hipGetLastError();
 }
 
@@ -440,26 +416,34 @@ int invpref_fairness_grad_hip(const float *user_table, int64_t user_num, const f
     int32_t *next = reinterpret_cast<int32_t *>(ws + l.next);
     double *partials = reinterpret_cast<double *>(ws + l.partials);
     const int n_partials = (int)((l.nuP / 32) * ((l.JP + kJB - 1) / kJB));
-    const bool vec = D % 4 == 0 && !((reinterpret_cast<uintptr_t>(user_table) | reinterpret_cast<uintptr_t>(item_table)) & 15u);
+    const bool vec = rows_vec_ok(D, user_table, item_table);
     const int dc = nc_of(D);
     int rc;
     hipLaunchKernelGGL(fair_positions_kernel, dim3((unsigned)((JP + 255) / 256)), dim3(256), 0, st, draw_items, J, JP, I,
                        item_counts, cpos, first, next);
     if ((rc = (int)hipGetLastError())) return rc;
-    rc = dc == 1 ? launch_scores<1>(user_table, U, item_table, I, D, vec, users, nu, draw_items, J, l, R, st)
-         : dc == 2 ? launch_scores<2>(user_table, U, item_table, I, D, vec, users, nu, draw_items, J, l, R, st)
-                   : launch_scores<4>(user_table, U, item_table, I, D, vec, users, nu, draw_items, J, l, R, st);
+    rc = with_int<1, 2, 4>(dc, [&](auto dc_c) {
+        hipLaunchKernelGGL((fair_scores_kernel<decltype(dc_c)::value>), dim3((unsigned)(l.nuP / 16)), dim3(256), 0, st, user_table,
+                           U, item_table, I, D, vec, users, nu, draw_items, J, JP, R);
+        return (int)hipGetLastError();
+    });
     if (rc) return rc;
     const float scale = (float)(2.0 * fairness_coe / (double)batch);
-    rc = tl <= kTabLds ? launch_product<true>(R, l, cpos, table, tl, user_mult, nu, scale, dX, partials, st)
-                       : launch_product<false>(R, l, cpos, table, tl, user_mult, nu, scale, dX, partials, st);
+    rc = with_bool(tl <= kTabLds, [&](auto tab_c) {   // (the table of a small one sits in LDS)
+        constexpr bool TAB_LDS = decltype(tab_c)::value;
+        const size_t lds = sizeof(float) * (32 * (kKC + 4) + kKC + (TAB_LDS ? tl : 0));
+        if (hipError_t e = ensure_lds(fair_product_kernel<TAB_LDS>, sizeof(float) * (32 * (kKC + 4) + kKC + kTabLds))) return (int)e;
+        const dim3 grid((unsigned)(l.nuP / 32), (unsigned)((l.JP + kJB - 1) / kJB));
+        hipLaunchKernelGGL((fair_product_kernel<TAB_LDS>), grid, dim3(256), lds, st, R, JP, cpos, table, tl, user_mult, nu, scale,
+                           dX, partials);
+        return (int)hipGetLastError();
+    });
     if (rc) return rc;
-#define INVPREF_FAIR_SIDES(DC)                                                                                            \
-    ((rc = launch_side<DC, true>(dX, l, item_table, I, D, draw_items, J, users, nu, U, grad_user, st))                     \
-         ? rc                                                                                                              \
-         : launch_side<DC, false>(dX, l, user_table, U, D, users, nu, nullptr, J, 0, G, st))
-    rc = dc == 1 ? INVPREF_FAIR_SIDES(1) : dc == 2 ? INVPREF_FAIR_SIDES(2) : INVPREF_FAIR_SIDES(4);
-#undef INVPREF_FAIR_SIDES
+    rc = with_int<1, 2, 4>(dc, [&](auto dc_c) {
+        constexpr int DC = decltype(dc_c)::value;
+        if ((rc = launch_side<DC, true>(dX, l, item_table, I, D, draw_items, J, users, nu, U, grad_user, st))) return rc;
+        return launch_side<DC, false>(dX, l, user_table, U, D, users, nu, nullptr, J, 0, G, st);
+    });
     if (rc) return rc;
     const unsigned fold_blocks = (unsigned)(((int64_t)J * D + 255) / 256);
     hipLaunchKernelGGL(fair_fold_kernel, dim3(fold_blocks + 1), dim3(256), 0, st, G, (int)l.nseg, JP, D, draw_items, J, I, first,

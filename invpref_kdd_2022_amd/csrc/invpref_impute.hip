@@ -17,7 +17,7 @@
 // owning workgroup, which then adds into its 16 rows.  No float atomics; the same bits on every run and every device.
 // The loss is summed by the user-side workgroups only: float64 per lane, one fixed butterfly, waves in order, one partial per
 // workgroup in the workspace, folded in workgroup order by a second, one-wave launch.
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 #include <algorithm>
 
@@ -212,22 +212,6 @@ __global__ __launch_bounds__(64) void impute_fold_kernel(const double *__restric
     }
 }
 
-template <int DC, bool VEC>
-int launch_impute(const float *ut, int U, const float *it, int I, int D, const int32_t *su, int nu, const int32_t *si, int ni,
-                  float c, float *gu, float *gi, double *partials, hipStream_t st) {
-    // rows of at most 64 floats leave registers for eight waves (256 per lane): half the tiles per wave of a sweep that is
-    // bound by the latency of its gathers, not by arithmetic
-    constexpr int NW = DC == 1 ? 8 : 4;
-    constexpr size_t lds = sizeof(float) * NW * 16 * (64 * DC + 4);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(impute_grad_kernel<DC, VEC, NW>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return (int)attr;
-    const int tu = (nu + 15) / 16, ti = (ni + 15) / 16;
-    hipLaunchKernelGGL((impute_grad_kernel<DC, VEC, NW>), dim3((unsigned)(tu + ti)), dim3(64 * NW), lds, st, ut, U, it, I, D, su, nu,
-                       si, ni, tu, c, gu, gi, partials);
-    return (int)hipGetLastError();
-}
-
 constexpr int64_t kMaxSel = 1 << 24;   // rows of one side of a block (the grid and the int32 row indices hold far more)
 
 }  // namespace
@@ -255,14 +239,20 @@ int invpref_impute_grad_hip(const float *user_table, int64_t user_num, const flo
     const double pairs = (double)n_sel_users * (double)n_sel_items;
     const float c = (float)(imputation_coe / pairs);
     auto *partials = reinterpret_cast<double *>(workspace);
-    const bool vec = D % 4 == 0 && !((reinterpret_cast<uintptr_t>(user_table) | reinterpret_cast<uintptr_t>(item_table)) & 15u);
-    const int dc = nc_of(D);
-    int rc;
-#define INVPREF_IMPUTE(DC, V) launch_impute<DC, V>(user_table, U, item_table, I, D, sel_users, nu, sel_items, ni, c, grad_user, grad_item, partials, st)
-    if (dc == 1) rc = vec ? INVPREF_IMPUTE(1, true) : INVPREF_IMPUTE(1, false);
-    else if (dc == 2) rc = vec ? INVPREF_IMPUTE(2, true) : INVPREF_IMPUTE(2, false);
-    else rc = vec ? INVPREF_IMPUTE(4, true) : INVPREF_IMPUTE(4, false);
-#undef INVPREF_IMPUTE
+    const int rc = with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
+        return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
+            // rows of at most 64 floats leave registers for eight waves (256 per lane): half the tiles per wave of a sweep
+            // that is bound by the latency of its gathers, not by arithmetic
+            constexpr int DC = decltype(dc_c)::value, NW = DC == 1 ? 8 : 4;
+            constexpr size_t lds = sizeof(float) * NW * 16 * (64 * DC + 4);
+            const auto kernel = impute_grad_kernel<DC, decltype(vec_c)::value, NW>;
+            if (hipError_t e = ensure_lds(kernel, lds)) return (int)e;
+            const int tu = (nu + 15) / 16, ti = (ni + 15) / 16;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(tu + ti)), dim3(64 * NW), lds, st, user_table, U, item_table, I, D, sel_users,
+                               nu, sel_items, ni, tu, c, grad_user, grad_item, partials);
+            return (int)hipGetLastError();
+        });
+    });
     if (rc) return rc;
     hipLaunchKernelGGL(impute_fold_kernel, dim3(1), dim3(64), 0, st, partials, (nu + 15) / 16, pairs, imputation_coe, loss_out,
                        term_out);

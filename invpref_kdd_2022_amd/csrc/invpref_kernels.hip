@@ -7,7 +7,7 @@
 // 256-byte global_load_dwordx4 across the 16 lanes, dot products are a per-lane fma chain plus a
 // 4-step DPP butterfly (canon_math.hpp), and no LDS is needed for the reductions.  The E x D
 // environment table and classifier live in LDS for the whole workgroup.
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 using namespace invpref;
 
@@ -500,27 +500,22 @@ struct AdamRanges {
     int64_t off4[4], end4[4];   // piece r covers float4 indices [off4[r], off4[r] + len4[r]); end4 = running total
     int n;
 };
-// one row of the device-side schedule, as laid out in include/invpref_hip.h (InvPrefAdamSchedule)
-struct SchedRowK {
-    AdamScalars ad;
-    float alpha, pad;
-};
 // sched_state != nullptr (HIP-graph replay: kernel arguments are frozen): the Adam scalars are read from slot
 // `sched_slot` of the device-side schedule, and one thread fills the other slot for the step after this one
 // (in the gradient-pass + stand-alone-Adam sequence THIS kernel is the step's last, so it moves the schedule on).
 __global__ __launch_bounds__(256) void adam_ranges_kernel(float *__restrict__ p, float *__restrict__ g, float *__restrict__ m,
                                                           float *__restrict__ v, AdamRanges r, AdamScalars a, int zero_grad,
-                                                          int *sched_state, const SchedRowK *sched_table, int sched_n,
+                                                          int *sched_state, const SchedRow *sched_table, int sched_n,
                                                           int sched_slot) {
     if (sched_state) {
-        a = reinterpret_cast<const SchedRowK *>(sched_state + 16 * sched_slot + 2)->ad;
+        a = reinterpret_cast<const SchedRow *>(sched_state + 16 * sched_slot + 2)->ad;
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             const int *cur = sched_state + 16 * sched_slot;
             int *nxt = sched_state + 16 * (sched_slot ^ 1);
             const int next = cur[0] + 1, base = cur[1], idx = next - base;
             nxt[0] = next;
             nxt[1] = base;
-            if (idx >= 0 && idx < sched_n) *reinterpret_cast<SchedRowK *>(nxt + 2) = sched_table[idx];
+            if (idx >= 0 && idx < sched_n) *reinterpret_cast<SchedRow *>(nxt + 2) = sched_table[idx];
         }
     }
     const int64_t total = r.end4[r.n - 1];
@@ -1090,19 +1085,22 @@ inline int estep_blocks(int64_t N) {
     return (int)(nb < 1 ? 1 : (nb > cap ? cap : nb));
 }
 
-// dispatch over (NC, VEC, EMAX): VEC=false only exists at NC=4 (any D <= 256)
-#define DISPATCH_NVE(NCV, VECV, EMAXV, CALL)                                             \
-    do {                                                                                  \
-        if (!(VECV)) {                                                                    \
-            if ((EMAXV) == 4) { CALL(4, false, 4); } else if ((EMAXV) == 8) { CALL(4, false, 8); } else { CALL(4, false, 16); } \
-        } else if ((NCV) == 1) {                                                          \
-            if ((EMAXV) == 4) { CALL(1, true, 4); } else if ((EMAXV) == 8) { CALL(1, true, 8); } else { CALL(1, true, 16); } \
-        } else if ((NCV) == 2) {                                                          \
-            if ((EMAXV) == 4) { CALL(2, true, 4); } else if ((EMAXV) == 8) { CALL(2, true, 8); } else { CALL(2, true, 16); } \
-        } else {                                                                          \
-            if ((EMAXV) == 4) { CALL(4, true, 4); } else if ((EMAXV) == 8) { CALL(4, true, 8); } else { CALL(4, true, 16); } \
-        }                                                                                 \
-    } while (0)
+// dispatch over (NC, VEC) and (NC, VEC, EMAX): VEC=false only exists at NC=4 (any D <= 256)
+template <typename F>
+int with_nv(int nc, bool vec, F &&f) {
+    return with_bool(vec, [&](auto vec_c) {
+        return with_int<1, 2, 4>(nc, [&](auto nc_c) {
+            if constexpr (!decltype(vec_c)::value && decltype(nc_c)::value != 4) return (int)INVPREF_EUNSUPPORTED;
+            else return f(nc_c, vec_c);
+        });
+    });
+}
+template <typename F>
+int with_nve(int nc, bool vec, int emax, F &&f) {
+    return with_nv(nc, vec, [&](auto nc_c, auto vec_c) {
+        return with_int<4, 8, 16>(emax, [&](auto emax_c) { return f(nc_c, vec_c, emax_c); });
+    });
+}
 
 }  // namespace
 
@@ -1153,12 +1151,49 @@ static int pack_rows_launch(bool unpack, float *flat, const int64_t *row_offsets
     const int64_t items = n_rows * (D / (vec ? 4 : 1)) + (tail_len + (vec ? 3 : 0)) / (vec ? 4 : 1);
     int64_t nb = (items + 255) / 256;
     nb = nb < 1 ? 1 : (nb > 4096 ? 4096 : nb);
-#define PK(U, V)                                                                                                         \
-    hipLaunchKernelGGL((pack_rows_kernel<U, V>), dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, flat, row_offsets, \
-                       n_rows, D, tail_offset, tail_len, packed)
-    if (unpack) { if (vec) PK(true, true); else PK(true, false); }
-    else { if (vec) PK(false, true); else PK(false, false); }
-#undef PK
+    return with_bool(unpack, [&](auto unpack_c) {
+        return with_bool(vec, [&](auto vec_c) {
+            hipLaunchKernelGGL((pack_rows_kernel<decltype(unpack_c)::value, decltype(vec_c)::value>), dim3((unsigned)nb), dim3(256),
+                               0, (hipStream_t)stream, flat, row_offsets, n_rows, D, tail_offset, tail_len, packed);
+            return (int)hipGetLastError();
+        });
+    });
+}
+
+// the atomic M-step's two launches, for the training gradient (BACKWARD = false) and forward()'s backward pass: the
+// per-interaction kernel into per-workgroup slabs, then the finish kernel over the slabs
+template <bool BACKWARD>
+static int launch_mstep_atomic(const InvPrefTables *tables, const InvPrefTables *grads, const int64_t *users,
+                               const int64_t *items, const int64_t *envs, const float *scores, const float *sample_weights,
+                               int64_t B, const StepScalars &k, uint32_t flags, const Upstream &up, float l2, float l1,
+                               int64_t batch_norm, float *losses6, void *workspace, hipStream_t st) {
+    const DevTables t = dev_tables(tables);
+    const DevGrads g = dev_grads(grads);
+    const bool vec = vec_ok(tables) && vec_ok(grads);
+    const int nc = vec ? nc_of(t.D) : 4, emax = emax_of(t.E);
+    const int DP = nc * 64, EDP = t.E * DP;
+    const int nb = mstep_blocks(B);
+    float *slabs = (float *)workspace;
+    const int rc = with_nve(nc, vec, emax, [&](auto nc_c, auto vec_c, auto emax_c) {
+        constexpr int NC = decltype(nc_c)::value, EMAX = decltype(emax_c)::value;
+        constexpr bool DCOL = NC * EMAX > 4;
+        constexpr size_t threads = DCOL ? 256 : kMstepThreads, G = threads / kRow, nwaves = threads / 64;
+        const size_t R = DCOL ? (2 * (size_t)EDP > G * 2 * DP ? 2 * (size_t)EDP : G * 2 * DP) : 2 * (size_t)EDP;
+        const size_t lds = sizeof(float) * (2 * (size_t)EDP + R + 2 * EMAX + kLossSlots + (DCOL ? G * (EMAX + 1) : 0) +
+                                            nwaves * 4 * DP) + 8 * nwaves * 4 + 8;
+        const auto kernel = mstep_atomic_kernel<NC, decltype(vec_c)::value, EMAX, BACKWARD, DCOL>;
+        if (hipError_t e = ensure_lds(kernel, lds)) return (int)e;
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(threads), lds, st, t, g, users, items, envs, scores, sample_weights, B, k,
+                           flags, slabs, up);
+        return (int)hipGetLastError();
+    });
+    if (rc) return rc;
+    const int slab_len = 2 * EDP + emax + kLossSlots;
+    // the loss tail (kLossSlots) must sit entirely inside the last 64-column block
+    const int nfb = (slab_len + 63) / 64;
+    if ((nfb - 1) * 64 > 2 * EDP + emax) return INVPREF_EUNSUPPORTED;
+    hipLaunchKernelGGL((mstep_finish_kernel<0>), dim3(nfb), dim3(1024), 0, st, t, g, slabs, nb, DP, emax, k, l2, l1, batch_norm,
+                       flags, losses6);
     return (int)hipGetLastError();
 }
 
@@ -1192,12 +1227,11 @@ int invpref_forward_hip(const InvPrefTables *tables, const int64_t *users, const
     const int nb = estep_blocks(B);
     const size_t lds = sizeof(float) * (2 * (size_t)t.E * nc * 64 + t.E);
     hipStream_t st = (hipStream_t)stream;
-#define CALL(NCV, VECV, EMAXV)                                                                               \
-    hipLaunchKernelGGL((forward_kernel<NCV, VECV, EMAXV>), dim3(nb), dim3(256), lds, st, t, users, items, envs, B, \
-                       flags, invariant_score, env_aware_score, env_outputs)
-    DISPATCH_NVE(nc, vec, emax, CALL);
-#undef CALL
-    return (int)hipGetLastError();
+    return with_nve(nc, vec, emax, [&](auto nc_c, auto vec_c, auto emax_c) {
+        hipLaunchKernelGGL((forward_kernel<decltype(nc_c)::value, decltype(vec_c)::value, decltype(emax_c)::value>), dim3(nb),
+                           dim3(256), lds, st, t, users, items, envs, B, flags, invariant_score, env_aware_score, env_outputs);
+        return (int)hipGetLastError();
+    });
 }
 
 size_t invpref_mstep_workspace_bytes(const InvPrefTables *tables, int64_t B) {
@@ -1220,40 +1254,10 @@ int invpref_mstep_grad_hip(const InvPrefTables *tables, const InvPrefTables *gra
     if (B > 0 && (!users || !items || !envs || !scores)) return INVPREF_EINVAL;
     if ((flags & (INVPREF_REWEIGHT_REC | INVPREF_REWEIGHT_CLS)) && B > 0 && !sample_weights) return INVPREF_EINVAL;
     if (workspace_bytes < invpref_mstep_workspace_bytes(tables, B)) return INVPREF_EWORKSPACE;
-    const DevTables t = dev_tables(tables);
-    const DevGrads g = dev_grads(grads);
-    const bool vec = vec_ok(tables) && vec_ok(grads);
-    const int nc = vec ? nc_of(t.D) : 4, emax = emax_of(t.E);
-    const int DP = nc * 64, EDP = t.E * DP;
-    const int nb = mstep_blocks(B);
-    StepScalars k;
-    k.ca = coefs->invariant_coe; k.cb = coefs->env_aware_coe; k.cc = coefs->env_coe; k.alpha = coefs->alpha;
-    k.invB = 1.0f / (float)batch_norm;
-    k.r2 = coefs->L2_coe / ((float)batch_norm * (float)t.D);
-    k.r1 = coefs->L1_coe / (2.0f * (float)batch_norm * (float)t.D);
-    const bool dcol = nc * emax > 4;
-    const size_t G = (dcol ? 256 : kMstepThreads) / kRow;
-    const size_t R = dcol ? (2 * (size_t)EDP > G * 2 * DP ? 2 * (size_t)EDP : G * 2 * DP) : 2 * (size_t)EDP;
-    const size_t nwaves = (dcol ? 256 : kMstepThreads) / 64;
-    const size_t lds = sizeof(float) * (2 * (size_t)EDP + R + 2 * emax + kLossSlots + (dcol ? G * (emax + 1) : 0) +
-                                        nwaves * 4 * DP) + 8 * nwaves * 4 + 8;
-    hipStream_t st = (hipStream_t)stream;
-    float *slabs = (float *)workspace;
-#define CALL(NCV, VECV, EMAXV)                                                                                       \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mstep_atomic_kernel<NCV, VECV, EMAXV, false, (NCV * EMAXV > 4)>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((mstep_atomic_kernel<NCV, VECV, EMAXV, false, (NCV * EMAXV > 4)>), dim3(nb), dim3((NCV * EMAXV > 4) ? 256 : kMstepThreads), lds, st, t, g, users, \
-                       items, envs, scores, sample_weights, B, k, flags, slabs, Upstream{nullptr, nullptr, nullptr})
-    DISPATCH_NVE(nc, vec, emax, CALL);
-#undef CALL
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
-    const int slab_len = 2 * EDP + emax + kLossSlots;
-    // the loss tail (kLossSlots) must sit entirely inside the last 64-column block
-    const int nfb = (slab_len + 63) / 64;
-    if ((nfb - 1) * 64 > 2 * EDP + emax) return INVPREF_EUNSUPPORTED;
-    hipLaunchKernelGGL((mstep_finish_kernel<0>), dim3(nfb), dim3(1024), 0, st, t, g, slabs, nb, DP, emax, k,
-                       coefs->L2_coe, coefs->L1_coe, batch_norm, flags, losses6);
-    return (int)hipGetLastError();
+    return launch_mstep_atomic<false>(tables, grads, users, items, envs, scores, sample_weights, B,
+                                      step_scalars(coefs, batch_norm, (int)tables->factor_num), flags,
+                                      Upstream{nullptr, nullptr, nullptr}, coefs->L2_coe, coefs->L1_coe, batch_norm, losses6,
+                                      workspace, (hipStream_t)stream);
 }
 
 int invpref_backward_hip(const InvPrefTables *tables, const InvPrefTables *grads, const int64_t *users,
@@ -1267,38 +1271,12 @@ int invpref_backward_hip(const InvPrefTables *tables, const InvPrefTables *grads
     if (!workspace || B < 0 || (B > 0 && (!users || !items || !envs))) return INVPREF_EINVAL;
     if (workspace_bytes < invpref_mstep_workspace_bytes(tables, B)) return INVPREF_EWORKSPACE;
     if (B == 0) return 0;
-    const DevTables t = dev_tables(tables);
-    const DevGrads g = dev_grads(grads);
-    const bool vec = vec_ok(tables) && vec_ok(grads);
-    const int nc = vec ? nc_of(t.D) : 4, emax = emax_of(t.E);
-    const int DP = nc * 64, EDP = t.E * DP;
-    const int nb = mstep_blocks(B);
     StepScalars k{};
     k.alpha = alpha;
     k.invB = 1.f;
-    const uint32_t fl = flags & INVPREF_IMPLICIT;
-    const bool dcol = nc * emax > 4;
-    const size_t G = (dcol ? 256 : kMstepThreads) / kRow;
-    const size_t R = dcol ? (2 * (size_t)EDP > G * 2 * DP ? 2 * (size_t)EDP : G * 2 * DP) : 2 * (size_t)EDP;
-    const size_t nwaves = (dcol ? 256 : kMstepThreads) / 64;
-    const size_t lds = sizeof(float) * (2 * (size_t)EDP + R + 2 * emax + kLossSlots + (dcol ? G * (emax + 1) : 0) +
-                                        nwaves * 4 * DP) + 8 * nwaves * 4 + 8;
-    hipStream_t st = (hipStream_t)stream;
-    float *slabs = (float *)workspace;
-    const Upstream up{d_invariant_score, d_env_aware_score, d_env_outputs};
-#define CALL(NCV, VECV, EMAXV)                                                                                            \
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mstep_atomic_kernel<NCV, VECV, EMAXV, true, (NCV * EMAXV > 4)>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((mstep_atomic_kernel<NCV, VECV, EMAXV, true, (NCV * EMAXV > 4)>), dim3(nb), dim3((NCV * EMAXV > 4) ? 256 : kMstepThreads), lds, st, t, g, users, \
-                       items, envs, (const float *)nullptr, (const float *)nullptr, B, k, fl, slabs, up)
-    DISPATCH_NVE(nc, vec, emax, CALL);
-#undef CALL
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
-    const int slab_len = 2 * EDP + emax + kLossSlots;
-    const int nfb = (slab_len + 63) / 64;
-    hipLaunchKernelGGL((mstep_finish_kernel<0>), dim3(nfb), dim3(1024), 0, st, t, g, slabs, nb, DP, emax, k, 0.f, 0.f,
-                       (int64_t)1, fl, (float *)nullptr);
-    return (int)hipGetLastError();
+    return launch_mstep_atomic<true>(tables, grads, users, items, envs, nullptr, nullptr, B, k, flags & INVPREF_IMPLICIT,
+                                     Upstream{d_invariant_score, d_env_aware_score, d_env_outputs}, 0.f, 0.f, 1, nullptr,
+                                     workspace, (hipStream_t)stream);
 }
 
 int invpref_predict_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
@@ -1307,7 +1285,7 @@ int invpref_predict_hip(const float *user_table, const float *item_table, const 
     if (factor_num > INVPREF_MAX_FACTORS) return INVPREF_EUNSUPPORTED;
     if (n_users == 0) return 0;
     if (!users) return INVPREF_EINVAL;
-    const bool vec = (factor_num % 4 == 0) && !((reinterpret_cast<uintptr_t>(user_table) | reinterpret_cast<uintptr_t>(item_table)) & 15u);
+    const bool vec = rows_vec_ok(factor_num, user_table, item_table);
     const int nc = vec ? nc_of((int)factor_num) : 4;
     const int64_t rows_per_block = 256 / kRow;
     const unsigned gx = (unsigned)((n_users + rows_per_block - 1) / rows_per_block);
@@ -1333,22 +1311,19 @@ int invpref_predict_hip(const float *user_table, const float *item_table, const 
         if (ig < 1) ig = 1;
         const int steps_per = (int)((steps_total + ig - 1) / ig);
         ig = (steps_total + steps_per - 1) / steps_per;
-#define MCALL(DCV)                                                                                                   \
-        do {                                                                                                         \
-            const size_t lds = sizeof(float) * 2 * 16 * (64 * DCV + 4);                                              \
-            hipLaunchKernelGGL((predict_mm_kernel<DCV>), dim3(ux, ig), dim3(256), lds, st, user_table, item_table, users, n_users, \
-                               (int)item_num, apply_sigmoid, out, steps_per);                                        \
-        } while (0)
-        if (factor_num == 64) MCALL(1); else if (factor_num == 128) MCALL(2); else MCALL(4);
-#undef MCALL
-        return (int)hipGetLastError();
+        return with_int<1, 2, 4>(nc, [&](auto dc_c) {
+            constexpr int DC = decltype(dc_c)::value;
+            const size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4);
+            hipLaunchKernelGGL((predict_mm_kernel<DC>), dim3(ux, ig), dim3(256), lds, st, user_table, item_table, users, n_users,
+                               (int)item_num, apply_sigmoid, out, steps_per);
+            return (int)hipGetLastError();
+        });
     }
-#define PCALL(NCV, VECV)                                                                                   \
-    hipLaunchKernelGGL((predict_kernel<NCV, VECV>), dim3(gx, gy), dim3(256), 0, st, user_table, item_table, users, \
-                       n_users, (int)item_num, (int)factor_num, apply_sigmoid, out, per)
-    if (!vec) { PCALL(4, false); } else if (nc == 1) { PCALL(1, true); } else if (nc == 2) { PCALL(2, true); } else { PCALL(4, true); }
-#undef PCALL
-    return (int)hipGetLastError();
+    return with_nv(nc, vec, [&](auto nc_c, auto vec_c) {
+        hipLaunchKernelGGL((predict_kernel<decltype(nc_c)::value, decltype(vec_c)::value>), dim3(gx, gy), dim3(256), 0, st,
+                           user_table, item_table, users, n_users, (int)item_num, (int)factor_num, apply_sigmoid, out, per);
+        return (int)hipGetLastError();
+    });
 }
 
 int invpref_adam_hip(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, double lr,
@@ -1362,14 +1337,7 @@ int invpref_adam_hip(float *param, float *grad, float *exp_avg, float *exp_avg_s
     int64_t head = ((16u - (ap & 15u)) & 15u) >> 2;
     if ((ag & 15u) != (ap & 15u) || (am & 15u) != (ap & 15u) || (av & 15u) != (ap & 15u)) head = n > 4 ? n : 4;
     if (head < 4 && head > n) head = n;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    AdamScalars a;
-    a.step_size = (float)(lr / bc1);
-    a.bc2_sqrt = (float)sqrt(bc2);
-    a.w1 = (float)(1.0 - beta1);
-    a.b2 = (float)beta2;
-    a.w2 = (float)(1.0 - beta2);
-    a.eps = (float)eps;
+    const AdamScalars a = adam_scalars(step, lr, beta1, beta2, eps);
     int64_t nb = (((head >= 4 ? n : n >> 2)) + 255) / 256;
     if (nb < 1) nb = 1;
     if (nb > 2048) nb = 2048;
@@ -1412,7 +1380,7 @@ static int adam_ranges_launch(float *param, float *grad, float *exp_avg, float *
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(adam_ranges_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
                        exp_avg_sq, r, a, zero_grad, sched ? sched->state : nullptr,
-                       sched ? reinterpret_cast<const SchedRowK *>(sched->table) : nullptr, sched ? sched->n : 0,
+                       sched ? reinterpret_cast<const SchedRow *>(sched->table) : nullptr, sched ? sched->n : 0,
                        sched ? (sched->slot & 1) : 0);
     return (int)hipGetLastError();
 }
@@ -1421,15 +1389,8 @@ int invpref_adam_ranges_hip(float *param, float *grad, float *exp_avg, float *ex
                             const int64_t *lengths, int32_t n_ranges, int64_t step, double lr, double beta1, double beta2,
                             double eps, int zero_grad, void *stream) {
     if (step < 1) return INVPREF_EINVAL;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    AdamScalars a;
-    a.step_size = (float)(lr / bc1);
-    a.bc2_sqrt = (float)sqrt(bc2);
-    a.w1 = (float)(1.0 - beta1);
-    a.b2 = (float)beta2;
-    a.w2 = (float)(1.0 - beta2);
-    a.eps = (float)eps;
-    return adam_ranges_launch(param, grad, exp_avg, exp_avg_sq, offsets, lengths, n_ranges, a, zero_grad, nullptr, stream);
+    return adam_ranges_launch(param, grad, exp_avg, exp_avg_sq, offsets, lengths, n_ranges,
+                              adam_scalars(step, lr, beta1, beta2, eps), zero_grad, nullptr, stream);
 }
 
 int invpref_adam_ranges_sched_hip(float *param, float *grad, float *exp_avg, float *exp_avg_sq, const int64_t *offsets,
@@ -1520,31 +1481,31 @@ static int estep_launch(const InvPrefTables *tables, const int64_t *users, const
                                                            sizeof(int) * (size_t)(t.E + 1) * kEstepMaxBlocks);
         int64_t ub = (N + 255) / 256;
         if (ub > 4096) ub = 4096;
-        if (index_bytes == 1)
-            hipLaunchKernelGGL(eps_unrank_kernel<uint8_t>, dim3((unsigned)ub), dim3(256), 0, st, (const uint8_t *)perm_index, N, t.E, fac, eps_packed);
-        else if (index_bytes == 4)
-            hipLaunchKernelGGL(eps_unrank_kernel<int32_t>, dim3((unsigned)ub), dim3(256), 0, st, (const int32_t *)perm_index, N, t.E, fac, eps_packed);
-        else
-            hipLaunchKernelGGL(eps_unrank_kernel<int64_t>, dim3((unsigned)ub), dim3(256), 0, st, (const int64_t *)perm_index, N, t.E, fac, eps_packed);
+        with_int<1, 4, 8>(index_bytes, [&](auto bytes_c) {   // (an error of this launch shows at the next one's check)
+            constexpr int W = decltype(bytes_c)::value;
+            using IT = std::conditional_t<W == 1, uint8_t, std::conditional_t<W == 4, int32_t, int64_t>>;
+            hipLaunchKernelGGL(eps_unrank_kernel<IT>, dim3((unsigned)ub), dim3(256), 0, st, (const IT *)perm_index, N, t.E, fac,
+                               eps_packed);
+            return 0;
+        });
     }
     EstepFin fin{};
     if (fused) {
         fin = *fused;
         if (!table_form) fin.perm_table = nullptr;
     }
-#define ECALL1(NCV, VECV, NARV)                                                                                   \
-    hipLaunchKernelGGL((estep_assign_kernel<NCV, VECV, NARV>), dim3(nb), dim3(kEstepThreads), lds + lds_extra, st, t, users, items, \
-                       scores, N, flags, eps_rows, eps_packed, eps_base, eps_index, index_bytes, eps_rows_n, fac, old_envs, \
-                       new_envs, slabs, fin)
-#define ECALL(NCV, VECV) do { if (narrow) ECALL1(NCV, VECV, true); else ECALL1(NCV, VECV, false); } while (0)
     // (INVPREF_ESTEP_OFFSETS64=1: the 64-bit form regardless -- the only way a test reaches it short of a 4 GB table)
     static const bool force64 = std::getenv("INVPREF_ESTEP_OFFSETS64") != nullptr && std::getenv("INVPREF_ESTEP_OFFSETS64")[0] == '1';
     const bool narrow = !force64 && (uint64_t)std::max(t.U, t.I) * (uint64_t)t.D * 4u < (1ull << 32);
-    if (!vec) { ECALL(4, false); } else if (nc == 1) { ECALL(1, true); } else if (nc == 2) { ECALL(2, true); } else { ECALL(4, true); }
-#undef ECALL
-#undef ECALL1
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
+    rc = with_nv(nc, vec, [&](auto nc_c, auto vec_c) {
+        return with_bool(narrow, [&](auto narrow_c) {
+            hipLaunchKernelGGL((estep_assign_kernel<decltype(nc_c)::value, decltype(vec_c)::value, decltype(narrow_c)::value>),
+                               dim3(nb), dim3(kEstepThreads), lds + lds_extra, st, t, users, items, scores, N, flags, eps_rows,
+                               eps_packed, eps_base, eps_index, index_bytes, eps_rows_n, fac, old_envs, new_envs, slabs, fin);
+            return (int)hipGetLastError();
+        });
+    });
+    if (rc) return rc;
     if (fused) return 0;   // (counts, diff and class weights came out of the kernel's epilogue; no sample-weight array)
     // every workgroup of stat_envs folds ALL the count slabs for itself before it gathers its share of the sample weights:
     // at most 256 of them (one per CU, a grid-stride share of rows each) -- a thousand workgroups read 40 MB of slabs for

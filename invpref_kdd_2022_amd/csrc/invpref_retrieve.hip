@@ -15,7 +15,7 @@
 // The range's top k (padded with empty entries) goes to the workspace.
 // Phase 2 (retrieve_merge_kernel): one wave per user merges the ranges' lists with the full (key, id) comparison and looks the
 // winners up in the sorted ground truth.
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 using namespace invpref;
 
@@ -326,19 +326,6 @@ size_t bytes_for(int64_t n_users, int64_t item_num, int64_t k) {
     return (size_t)n_users * (size_t)geometry(n_users, item_num).ranges * (size_t)k * 8u;
 }
 
-template <int DC, bool VEC>
-int launch_scan(const Geometry &g, const float *ut, const float *it, const int64_t *users, int64_t n, int I, int D, int sig,
-                const int32_t *mp, const int32_t *mi, const int32_t *hp, const int32_t *hi, int K, unsigned *wk, int *wi,
-                hipStream_t st) {
-    constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4) + (size_t)64 * kCand * 8;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(retrieve_scan_kernel<DC, VEC>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return (int)attr;
-    hipLaunchKernelGGL((retrieve_scan_kernel<DC, VEC>), dim3((unsigned)g.ux, (unsigned)g.ranges), dim3(256), lds, st, ut, it,
-                       users, n, I, D, sig, mp, mi, hp, hi, K, g.steps_per, wk, wi);
-    return (int)hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" {
@@ -371,14 +358,17 @@ int invpref_predict_topk_hip(const float *user_table, const float *item_table, c
     int *wi = reinterpret_cast<int *>(wk + slots);
     hipStream_t st = (hipStream_t)stream;
     const int I = (int)item_num, D = (int)factor_num;
-    const bool vec = (D % 4 == 0) && !((reinterpret_cast<uintptr_t>(user_table) | reinterpret_cast<uintptr_t>(item_table)) & 15u);
-    int rc;
-#define SCAN(DCV, VECV) launch_scan<DCV, VECV>(g, user_table, item_table, users, n_users, I, D, apply_sigmoid, mask_ptr, mask_items, \
-                                               highlight_ptr, highlight_items, k, wk, wi, st)
-    if (D <= 64) rc = vec ? SCAN(1, true) : SCAN(1, false);
-    else if (D <= 128) rc = vec ? SCAN(2, true) : SCAN(2, false);
-    else rc = vec ? SCAN(4, true) : SCAN(4, false);
-#undef SCAN
+    const int rc = with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
+        return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
+            constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * decltype(dc_c)::value + 4) + (size_t)64 * kCand * 8;
+            const auto scan = retrieve_scan_kernel<decltype(dc_c)::value, decltype(vec_c)::value>;
+            if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
+            hipLaunchKernelGGL(scan, dim3((unsigned)g.ux, (unsigned)g.ranges), dim3(256), lds, st, user_table, item_table, users,
+                               n_users, I, D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k,
+                               g.steps_per, wk, wi);
+            return (int)hipGetLastError();
+        });
+    });
     if (rc != 0) return rc;
     hipLaunchKernelGGL(retrieve_merge_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, n_users, g.ranges, (int)k,
                        wk, wi, truth_ptr, truth_items, out_items, out_scores, out_hits);

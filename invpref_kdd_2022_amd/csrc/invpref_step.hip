@@ -33,7 +33,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 using namespace invpref;
 
@@ -42,12 +42,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
-// one row of the device-side schedule (include/invpref_hip.h: InvPrefAdamSchedule)
-struct SchedRow {
-    AdamScalars ad;
-    float alpha;   // gradient-reversal alpha of the step; NaN: use the one of the call's coefficient block
-    float pad;
-};
 __device__ __forceinline__ const SchedRow *sched_slot_ptr(const int *state, int slot) {
     return reinterpret_cast<const SchedRow *>(state + 16 * slot + 2);
 }
@@ -1484,19 +1478,17 @@ struct Shape {
     int lg, nc, dp, emax;
     bool wide, evl2;   // evl2: embed_env's outer product runs in launch 2 (pull form only) and a third launch folds
 };
-inline int emax4_of(int E) { return E <= 4 ? 4 : (E <= 8 ? 8 : 16); }
 inline Shape shape_of(int D, int E) {
     Shape s;
     s.lg = D <= 128 ? 16 : 32;
     s.nc = D <= 64 ? 1 : 2;
     s.dp = 4 * s.lg * s.nc;
-    const int e4 = emax4_of(E);
+    const int e4 = emax_of(E);
     s.wide = !(s.nc == 1 && e4 == 4);
     s.emax = s.wide ? (e4 < 8 ? 8 : e4) : 4;
     s.evl2 = s.lg == 32;
     return s;
 }
-inline int lanes_of(int D) { return D <= 128 ? 16 : 32; }
 inline size_t slab_floats(const Shape &s) { return (size_t)2 * s.emax * s.dp + s.emax + kLossSlots; }
 inline size_t eval_lds_bytes(const Shape &s) {
     if (!s.wide) return sizeof(float) * EvalLds<16, 4>::total;
@@ -1513,12 +1505,6 @@ inline size_t apply_lds_bytes(const Shape &s) {
     const size_t DP = s.dp, NG = kThreads / s.lg;
     const size_t job = (2 * s.emax * DP + NG * 2 * DP + (s.wide ? 0 : kWaves * 4 * 64 * 4)) * sizeof(float);
     return job > fold_lds_bytes() ? job : fold_lds_bytes();
-}
-
-template <typename K>
-int ensure_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return 0;
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 inline size_t record_floats(const InvPrefRowPlan *plan, const Shape &s) {
@@ -1612,12 +1598,7 @@ int launch_step(const InvPrefTables *tables, const InvPrefRowPlan *plan, const i
     const size_t rec_floats = record_floats(plan, shp);
     if (workspace_bytes < sizeof(float) * workspace_floats(plan, shp)) return INVPREF_EWORKSPACE;
     if (shp.evl2 && plan->push_slot) return INVPREF_EINVAL;   // rows on 32 lanes: pull form only (step_wide.hpp)
-    StepScalars k;
-    k.ca = coefs->invariant_coe; k.cb = coefs->env_aware_coe; k.cc = coefs->env_coe; k.alpha = coefs->alpha;
-    k.invB = 1.0f / (float)batch_norm;
-    k.r2 = coefs->L2_coe / ((float)batch_norm * (float)t.D);
-    k.r1 = coefs->L1_coe / (2.0f * (float)batch_norm * (float)t.D);
-    a.envs = envs; a.weights = weights; a.k = k; a.flags = flags; a.fused = fused; a.ad = ad;
+    a.envs = envs; a.weights = weights; a.k = step_scalars(coefs, batch_norm, t.D); a.flags = flags; a.fused = fused; a.ad = ad;
     a.rows_per_stream_task = plan->rows_per_stream_task; a.n_cls = ncls;
     a.records = (float *)workspace; a.slabs = (float *)workspace + rec_floats;
     a.slabs_ev = a.slabs + slab * (size_t)(n_partials > 0 ? n_partials : 1);
@@ -1669,43 +1650,6 @@ int launch_step(const InvPrefTables *tables, const InvPrefRowPlan *plan, const i
     f.sched_n = sched ? sched->n : 0;
     const int grid2 = wg2 + f.fold_blocks + 1;
     if (shp.evl2) { f.slabs_ev = a.slabs_ev; f.n_partials_ev = plan->n_item_rounds / plan->item_rounds_per_task; }
-    // wide rows / more than four environments (step_wide.hpp).  evl2: launch 2 = the item jobs alone (they produce embed_env's
-    // partial slabs), launch 3 = the fold blocks alone
-#define CALL_W1(LGV, NCV, VECV, EMAXV, EV2, BYE)                                                                  \
-    do {                                                                                                          \
-        if ((rc = ensure_lds(mstep_apply_wide_kernel<LGV, NCV, VECV, EMAXV, EV2>, lds2))) return rc;            \
-        if (VECV && LGV == 32 && use_mm) {   /* full rows: the classifier as products over the workgroup's interactions */ \
-            if constexpr (VECV && LGV == 32) {   /* (step_wide_mm.hpp; instantiated for rows on 32 lanes only) */     \
-                const size_t ldsm = sizeof(float) * MGeo<LGV, NCV, EMAXV, EV2>::total;                            \
-                if ((rc = ensure_lds(mstep_eval_mm_kernel<LGV, NCV, EMAXV, EV2, BYE>, ldsm))) return rc;         \
-                if (wg1 > 0)                                                                                      \
-                    hipLaunchKernelGGL((mstep_eval_mm_kernel<LGV, NCV, EMAXV, EV2, BYE>), dim3(wg1), dim3(kThreads), ldsm, st, t, a1); \
-            }                                                                                                     \
-        } else {                                                                                                  \
-            if ((rc = ensure_lds(mstep_eval_wide_kernel<LGV, NCV, VECV, EMAXV, EV2, BYE>, lds1))) return rc;    \
-            if (wg1 > 0)                                                                                          \
-                hipLaunchKernelGGL((mstep_eval_wide_kernel<LGV, NCV, VECV, EMAXV, EV2, BYE>), dim3(wg1), dim3(kThreads), lds1, st, t, a1); \
-        }                                                                                                         \
-        if (profile_event && hipEventRecord((hipEvent_t)profile_event, st) != hipSuccess) return INVPREF_EINVAL; \
-        if (!EV2) {                                                                                               \
-            hipLaunchKernelGGL((mstep_apply_wide_kernel<LGV, NCV, VECV, EMAXV, EV2>), dim3(grid2), dim3(kThreads), lds2, st, t, a2, f); \
-        } else {                                                                                                  \
-            if (wg2 > 0)                                                                                          \
-                hipLaunchKernelGGL((mstep_apply_wide_kernel<LGV, NCV, VECV, EMAXV, EV2>), dim3(wg2), dim3(kThreads), lds2, st, t, a2, f); \
-            FoldArgs f3 = f;                                                                                      \
-            f3.n_task_wgs = 0;                                                                                    \
-            hipLaunchKernelGGL((mstep_apply_wide_kernel<LGV, NCV, VECV, EMAXV, EV2>), dim3(f.fold_blocks + 1), dim3(kThreads), fold_lds_bytes(), st, t, a2, f3); \
-        }                                                                                                         \
-    } while (0)
-    /* (INVPREF_WEIGHTS_BY_ENV is a compile-time property of the full-row instances: step_wide.hpp) */
-#define CALL_W(LGV, NCV, VECV, EMAXV, EV2)                                                                        \
-    do {                                                                                                          \
-        if (VECV && (flags & INVPREF_WEIGHTS_BY_ENV)) CALL_W1(LGV, NCV, VECV, EMAXV, EV2, (VECV)); else CALL_W1(LGV, NCV, VECV, EMAXV, EV2, false); \
-    } while (0)
-#define CALL_WE(LGV, NCV, VECV, EV2)                                                               \
-    do {                                                                                           \
-        if (emax == 8) CALL_W(LGV, NCV, VECV, 8, EV2); else CALL_W(LGV, NCV, VECV, 16, EV2);       \
-    } while (0)
     // the MFMA classifier for full rows on 32 lanes (D = 256: launch 1 14.4 vs 18.1 ms at 2^24 interactions; rows on 16 lanes
     // measured level or slower, profiles/r05/EXPERIMENTS.md).  INVPREF_WIDE_MM=0 (test hook): the per-interaction classifier of
     // step_wide.hpp, the form PureMF and unaligned classifier weights take, for those rows too -- read per call: the tests
@@ -1713,56 +1657,75 @@ int launch_step(const InvPrefTables *tables, const InvPrefRowPlan *plan, const i
     const char *mm_env = getenv("INVPREF_WIDE_MM");
     const bool use_mm = shp.lg == 32 && !(mm_env && mm_env[0] == '0') && !pure && t.b != nullptr &&
                         (reinterpret_cast<uintptr_t>(t.W) & 15u) == 0;
-    if (shp.wide) {
+    // instances: rows on 32 lanes hold two float4 per lane and fold in a third launch (EV2); by-environment weights
+    // (INVPREF_WEIGHTS_BY_ENV) are a compile-time property of the full-row instances alone (step_wide.hpp)
+    auto wide = [&](auto lg_c, auto nc_c, auto vec_c, auto emax_c, auto bye_c) {
+        constexpr int LG = decltype(lg_c)::value, NC = decltype(nc_c)::value, EMAX = decltype(emax_c)::value;
+        constexpr bool VEC = decltype(vec_c)::value, BYE = decltype(bye_c)::value, EV2 = LG == 32;
+        if constexpr ((LG == 32 && NC != 2) || (BYE && !VEC)) {
+            return (int)INVPREF_EUNSUPPORTED;
+        } else {
+            const auto apply = mstep_apply_wide_kernel<LG, NC, VEC, EMAX, EV2>;
+            if ((rc = (int)ensure_lds(apply, lds2))) return rc;
+            bool mm = false;
+            if constexpr (VEC && LG == 32) {   // full rows: the classifier as products over the workgroup's interactions
+                if ((mm = use_mm)) {           // (step_wide_mm.hpp; instantiated for rows on 32 lanes only)
+                    const size_t ldsm = sizeof(float) * MGeo<LG, NC, EMAX, EV2>::total;
+                    const auto eval = mstep_eval_mm_kernel<LG, NC, EMAX, EV2, BYE>;
+                    if ((rc = (int)ensure_lds(eval, ldsm))) return rc;
+                    if (wg1 > 0) hipLaunchKernelGGL(eval, dim3(wg1), dim3(kThreads), ldsm, st, t, a1);
+                }
+            }
+            if (!mm) {
+                const auto eval = mstep_eval_wide_kernel<LG, NC, VEC, EMAX, EV2, BYE>;
+                if ((rc = (int)ensure_lds(eval, lds1))) return rc;
+                if (wg1 > 0) hipLaunchKernelGGL(eval, dim3(wg1), dim3(kThreads), lds1, st, t, a1);
+            }
+            if (profile_event && hipEventRecord((hipEvent_t)profile_event, st) != hipSuccess) return INVPREF_EINVAL;
+            if (!EV2) {
+                hipLaunchKernelGGL(apply, dim3(grid2), dim3(kThreads), lds2, st, t, a2, f);
+            } else {   // launch 2 = the item jobs alone (they produce embed_env's partial slabs), launch 3 = the fold blocks alone
+                if (wg2 > 0) hipLaunchKernelGGL(apply, dim3(wg2), dim3(kThreads), lds2, st, t, a2, f);
+                FoldArgs f3 = f;
+                f3.n_task_wgs = 0;
+                hipLaunchKernelGGL(apply, dim3(f.fold_blocks + 1), dim3(kThreads), fold_lds_bytes(), st, t, a2, f3);
+            }
+            return (int)hipGetLastError();
+        }
+    };
+    if (shp.wide) {   // wide rows / more than four environments (step_wide.hpp)
         // (the wide kernels' vector form is for FULL rows only -- factor_num 64 / 128 / 256: no clamps or selects behind a
         //  load; any other row length takes their element-wise form)
-        if (vec && t.D == shp.dp) {
-            if (shp.lg == 32) CALL_WE(32, 2, true, true); else if (shp.nc == 2) CALL_WE(16, 2, true, false); else CALL_WE(16, 1, true, false);
-        } else {
-            if (shp.lg == 32) CALL_WE(32, 2, false, true); else if (shp.nc == 2) CALL_WE(16, 2, false, false); else CALL_WE(16, 1, false, false);
-        }
-        return (int)hipGetLastError();
+        const bool vecw = vec && t.D == shp.dp, bye = vecw && (flags & INVPREF_WEIGHTS_BY_ENV);
+        return with_int<16, 32>(shp.lg, [&](auto lg_c) {
+            return with_int<1, 2>(shp.nc, [&](auto nc_c) {
+                return with_bool(vecw, [&](auto vec_c) {
+                    return with_int<8, 16>(emax, [&](auto emax_c) {
+                        return with_bool(bye, [&](auto bye_c) { return wide(lg_c, nc_c, vec_c, emax_c, bye_c); });
+                    });
+                });
+            });
+        });
     }
-#undef CALL_WE
-#undef CALL_W
-#undef CALL_W1
-#define CALL(LGV, VECV, EMAXV)                                                                                  \
-    do {                                                                                                        \
-        if ((rc = ensure_lds(mstep_eval_kernel<LGV, VECV, EMAXV>, lds1))) return rc;                            \
-        if ((rc = ensure_lds(mstep_apply_kernel<LGV, VECV, EMAXV>, lds2))) return rc;                           \
-        if (wg1 > 0)                                                                                            \
-            hipLaunchKernelGGL((mstep_eval_kernel<LGV, VECV, EMAXV>), dim3(wg1), dim3(kThreads), lds1, st, t, a1); \
-        if (profile_event && hipEventRecord((hipEvent_t)profile_event, st) != hipSuccess) return INVPREF_EINVAL; \
-        hipLaunchKernelGGL((mstep_apply_kernel<LGV, VECV, EMAXV>), dim3(grid2), dim3(kThreads), lds2, st, t, a2, f); \
-    } while (0)
-    // rows of exactly 64 floats: loads with nothing behind them (row4<VEC, FULL>)
-    const bool full = vec && t.D == 64;
-    if (full) {
-        if ((rc = ensure_lds(mstep_eval_kernel<16, true, 4, true>, lds1))) return rc;
-        if ((rc = ensure_lds(mstep_apply_kernel<16, true, 4, true>, lds2))) return rc;
-        if (wg1 > 0)
-            hipLaunchKernelGGL((mstep_eval_kernel<16, true, 4, true>), dim3(wg1), dim3(kThreads), lds1, st, t, a1);
-        if (profile_event && hipEventRecord((hipEvent_t)profile_event, st) != hipSuccess) return INVPREF_EINVAL;
-        hipLaunchKernelGGL((mstep_apply_kernel<16, true, 4, true>), dim3(grid2), dim3(kThreads), lds2, st, t, a2, f);
-    } else if (!vec) {
-        CALL(16, false, 4);
-    } else {
-        CALL(16, true, 4);
-    }
-#undef CALL
-    return (int)hipGetLastError();
-}
-
-AdamScalars adam_scalars(int64_t step, double lr, double beta1, double beta2, double eps) {
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    AdamScalars ad;
-    ad.step_size = (float)(lr / bc1);
-    ad.bc2_sqrt = (float)sqrt(bc2);
-    ad.w1 = (float)(1.0 - beta1);
-    ad.b2 = (float)beta2;
-    ad.w2 = (float)(1.0 - beta2);
-    ad.eps = (float)eps;
-    return ad;
+    // rows of up to 64 floats, up to four environments; FULL: rows of exactly 64 floats, loads with nothing behind them
+    // (row4<VEC, FULL>)
+    return with_bool(vec, [&](auto vec_c) {
+        return with_bool(vec && t.D == 64, [&](auto full_c) {
+            constexpr bool VEC = decltype(vec_c)::value, FULL = decltype(full_c)::value;
+            if constexpr (FULL && !VEC) {
+                return (int)INVPREF_EUNSUPPORTED;
+            } else {
+                const auto eval = mstep_eval_kernel<16, VEC, 4, FULL>;
+                const auto apply = mstep_apply_kernel<16, VEC, 4, FULL>;
+                if ((rc = (int)ensure_lds(eval, lds1))) return rc;
+                if ((rc = (int)ensure_lds(apply, lds2))) return rc;
+                if (wg1 > 0) hipLaunchKernelGGL(eval, dim3(wg1), dim3(kThreads), lds1, st, t, a1);
+                if (profile_event && hipEventRecord((hipEvent_t)profile_event, st) != hipSuccess) return INVPREF_EINVAL;
+                hipLaunchKernelGGL(apply, dim3(grid2), dim3(kThreads), lds2, st, t, a2, f);
+                return (int)hipGetLastError();
+            }
+        });
+    });
 }
 
 #include "step_alt.hpp"
@@ -1809,7 +1772,7 @@ size_t invpref_rows_workspace_bytes(const InvPrefTables *tables, const InvPrefRo
 
 int invpref_rows_lanes_per_group(const InvPrefTables *tables) {
     if (!tables || tables->factor_num <= 0 || tables->factor_num > INVPREF_MAX_FACTORS) return INVPREF_EUNSUPPORTED;
-    return lanes_of((int)tables->factor_num);
+    return shape_of((int)tables->factor_num, (int)tables->env_num).lg;
 }
 
 int invpref_mstep_rows_grad_hip(const InvPrefTables *tables, const InvPrefTables *grads, const InvPrefRowPlan *plan,

@@ -17,7 +17,7 @@
 //
 // user_values_wide_kernel: stage 1 of invpref_rank_metrics_hip for K <= 1024: the per-user dcg row sum follows numpy's
 // pairwise recursion above 128 elements; stages 2 and 3 are invpref_metrics.hip's (invpref::rank_metrics_reduce).
-#include "kernel_common.hpp"
+#include "launch.hpp"
 
 using namespace invpref;
 
@@ -263,11 +263,7 @@ int launch_rows(const float *ratings, int64_t n, int64_t I, int64_t ld, const in
         grid = std::min<int64_t>(n, kGlobalSlots);
     } else {
         lds = sizeof(unsigned) * 2 * (size_t)((I + 31) / 32);
-        if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(topk_wide_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
+        if (hipError_t e = ensure_lds(topk_wide_kernel, lds)) return (int)e;
     }
     hipLaunchKernelGGL(topk_wide_kernel, dim3((unsigned)grid), dim3(kThreads), lds, st, ratings, n, (int)I, ld, mp, mi, hp, hi,
                        tp, ti, k, out_items, out_scores, out_hits, gbits);

@@ -124,33 +124,4 @@ __device__ __forceinline__ void adam1f(float &p, float g, float &m, float &v, co
     p = p + ((-a.step_size) * m) * __builtin_amdgcn_rcpf(denom);
 }
 
-// host-side helpers
-inline int check_tables(const InvPrefTables *t, bool pure_mf = false) {
-    if (!t) return INVPREF_EINVAL;
-    if (t->user_num <= 0 || t->item_num <= 0 || t->env_num <= 0 || t->factor_num <= 0) return INVPREF_EINVAL;
-    if (t->factor_num > INVPREF_MAX_FACTORS || t->env_num > INVPREF_MAX_ENVS) return INVPREF_EUNSUPPORTED;
-    if (!t->embed_user_invariant || !t->embed_item_invariant) return INVPREF_EINVAL;
-    if (pure_mf) return t->env_num == 1 ? 0 : INVPREF_EINVAL;  // INVPREF_PURE_MF: the other five tables are ignored
-    if (!t->embed_user_env_aware || !t->embed_item_env_aware || !t->embed_env || !t->classifier_weight ||
-        !t->classifier_bias)
-        return INVPREF_EINVAL;
-    return 0;
-}
-inline DevTables dev_tables(const InvPrefTables *t) {
-    return DevTables{t->embed_user_invariant, t->embed_item_invariant, t->embed_user_env_aware, t->embed_item_env_aware,
-                     t->embed_env, t->classifier_weight, t->classifier_bias,
-                     (int)t->user_num, (int)t->item_num, (int)t->env_num, (int)t->factor_num};
-}
-inline DevGrads dev_grads(const InvPrefTables *t) {
-    return DevGrads{t->embed_user_invariant, t->embed_item_invariant, t->embed_user_env_aware, t->embed_item_env_aware,
-                    t->embed_env, t->classifier_weight, t->classifier_bias};
-}
-inline bool vec_ok(const InvPrefTables *t) {
-    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    return (t->factor_num % 4 == 0) && al(t->embed_user_invariant) && al(t->embed_item_invariant) &&
-           al(t->embed_user_env_aware) && al(t->embed_item_env_aware);  // (null pointers count as aligned)
-}
-inline int nc_of(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : 4); }
-inline int emax_of(int E) { return E <= 4 ? 4 : (E <= 8 ? 8 : 16); }
-
 }  // namespace invpref

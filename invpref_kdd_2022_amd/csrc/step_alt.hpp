@@ -1031,14 +1031,8 @@ int launch_alt(const InvPrefTables *tables, const InvPrefTables *exp_avg, const 
     a.rounds_per_task = plan->rounds_per_task; a.rows_per_stream_task = plan->rows_per_stream_task; a.n_cls = ncls;
     for (int c = 0; c < 8; c++) for (int i = 0; i < 4; i++) a.cls[c][i] = c < ncls ? plan->cls[c][i] : 0;
     a.envs = envs; a.weights = weights;
-    StepScalars k{};
-    k.ca = coefs->invariant_coe; k.cb = coefs->env_aware_coe; k.cc = coefs->env_coe; k.alpha = coefs->alpha;
-    if (has_cur) {
-        k.invB = 1.0f / (float)batch_norm;
-        k.r2 = coefs->L2_coe / ((float)batch_norm * (float)D);
-        k.r1 = coefs->L1_coe / (2.0f * (float)batch_norm * (float)D);
-    }
-    a.k = k;
+    a.k = step_scalars(coefs, batch_norm, D);
+    if (!has_cur) a.k.invB = a.k.r2 = a.k.r1 = 0.f;   // (a flush launch evaluates nothing; batch_norm is not checked then)
     if (has_prev) {
         a.r2_prev = coefs->L2_coe / ((float)batch_norm_prev * (float)D);
         a.r1_prev = coefs->L1_coe / (2.0f * (float)batch_norm_prev * (float)D);
@@ -1079,26 +1073,22 @@ int launch_alt(const InvPrefTables *tables, const InvPrefTables *exp_avg, const 
     const int grid = a.first_task_block + per_class * ncls;
     const bool vec = vec_ok(tables) && vec_ok(exp_avg) && vec_ok(exp_avg_sq);
     const bool full = vec && D == 64;
-#define CALL_ALT_M(VECV, FULLV, MODEV, THR)                                                                      \
-    do {                                                                                                         \
-        if ((rc = ensure_lds(mstep_alt_kernel<VECV, FULLV, MODEV, THR>, lds))) return rc;                        \
-        hipLaunchKernelGGL((mstep_alt_kernel<VECV, FULLV, MODEV, THR>), dim3(grid), dim3(THR), lds, st, a);      \
-    } while (0)
-#define CALL_ALT_T(VECV, FULLV, THR)                                                 \
-    do {                                                                             \
-        if (a.mode == 3) CALL_ALT_M(VECV, FULLV, 3, THR);                            \
-        else if (a.mode == 2) CALL_ALT_M(VECV, FULLV, 2, THR);                       \
-        else CALL_ALT_M(VECV, FULLV, 1, THR);                                        \
-    } while (0)
-#define CALL_ALT(VECV, FULLV)                                                        \
-    do {                                                                             \
-        if (slots == 32) CALL_ALT_T(VECV, FULLV, 512); else CALL_ALT_T(VECV, FULLV, 256); \
-    } while (0)
-    if (full) CALL_ALT(true, true);
-    else if (vec) CALL_ALT(true, false);
-    else CALL_ALT(false, false);
-#undef CALL_ALT
-#undef CALL_ALT_T
-#undef CALL_ALT_M
-    return (int)hipGetLastError();
+    return with_bool(vec, [&](auto vec_c) {
+        return with_bool(full, [&](auto full_c) {
+            return with_int<256, 512>(slots * 16, [&](auto thr_c) {
+                return with_int<1, 2, 3>(a.mode, [&](auto mode_c) {
+                    constexpr bool VEC = decltype(vec_c)::value, FULL = decltype(full_c)::value;
+                    constexpr int THR = decltype(thr_c)::value;
+                    if constexpr (FULL && !VEC) {
+                        return (int)INVPREF_EUNSUPPORTED;
+                    } else {
+                        const auto kernel = mstep_alt_kernel<VEC, FULL, decltype(mode_c)::value, THR>;
+                        if ((rc = (int)ensure_lds(kernel, lds))) return rc;
+                        hipLaunchKernelGGL(kernel, dim3(grid), dim3(THR), lds, st, a);
+                        return (int)hipGetLastError();
+                    }
+                });
+            });
+        });
+    });
 }

@@ -94,6 +94,7 @@ def make_case(D, B, U, I, dist, implicit, seed, shift=0.0):
 # (D, B, U, I, dist, implicit, shift of the explicit tables)
 KERNEL_CASES = [(D, 1000, 300, 200, 'half', True, 0.0) for D in (24, 30, 40, 64, 128, 256)] + \
                [(D, 8192, 15400, 1000, 'skew', D in (24, 40, 128), 0.08) for D in (24, 30, 40, 64, 128, 256)] + \
+               [(98, 1000, 300, 200, 'half', True, 0.0), (202, 1000, 300, 200, 'half', True, 0.0)] + \
                [(24, 1, 50, 40, 'uniform', True, 0.0), (256, 1, 50, 40, 'uniform', False, 0.08),
                 (30, 37, 50, 40, 'uniform', True, 0.0), (64, 8192, 3000, 2500, 'hot', True, 0.0),
                 (40, 8192, 3000, 2500, 'hot', False, 0.08), (64, 262144, 50000, 51283, 'uniform', True, 0.0),

@@ -32,7 +32,10 @@ def relerr(a, b):
 
 
 @pytest.mark.parametrize('U,I,E,D,B', [(1, 1, 1, 4, 1), (3, 2, 2, 1, 5), (7, 5, 16, 256, 17), (9, 4, 3, 255, 33),
-                                        (50, 40, 4, 64, 1), (50, 40, 4, 64, 4097)])
+                                        (50, 40, 4, 64, 1), (50, 40, 4, 64, 4097),
+                                        # the plan-free M-step's other (chunks per lane, float4 rows, class count) instances
+                                        (48, 40, 12, 64, 96), (48, 40, 12, 96, 96), (48, 40, 3, 96, 96), (48, 40, 12, 6, 96),
+                                        (48, 40, 6, 6, 96), (48, 40, 6, 200, 96)])
 @pytest.mark.parametrize('implicit', [True, False])
 def test_ragged_and_extreme_shapes(U, I, E, D, B, implicit):
     rs = np.random.RandomState(U * 1000 + B)

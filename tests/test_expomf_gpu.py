@@ -84,7 +84,7 @@ def test_store_mode_ragged(D):
 
 
 # ------------------------------------------------------------------------------------------------ 2. prior form
-@pytest.mark.parametrize('D', [24, 30, 40, 64, 256])
+@pytest.mark.parametrize('D', [24, 30, 40, 64, 256, 96, 98, 202])   # (96 / 98 / 202: two chunks per lane, and the scalar loads at two and four)
 def test_prior_form(D):
     rs = np.random.RandomState(100 + D)
     U, I = 1037, 515
@@ -158,7 +158,7 @@ def test_prior_form_no_users_and_bitwise_replay():
 
 
 # ------------------------------------------------------------------------------------------------ 3. pair weights
-@pytest.mark.parametrize('D', [24, 30, 40, 64, 256])
+@pytest.mark.parametrize('D', [24, 30, 40, 64, 256, 96, 98, 202])
 def test_pair_weights(D):
     rs = np.random.RandomState(200 + D)
     U, I, n = 300, 257, 5000

@@ -121,8 +121,8 @@ def _check_vs_float64(D, nu, J, span):
     assert abs(loss2 - want) <= 2 * 2 * F32_HALF_ULP * max(abs(want), 1.0)     # two fp32 roundings
 
 
-@pytest.mark.parametrize('shape', SHAPES, ids=lambda b: f'{b[0]}x{b[1]}')
-@pytest.mark.parametrize('D', [24, 30, 40, 64, 256])
+@pytest.mark.parametrize('D,shape', [(D, s) for s in SHAPES for D in (24, 30, 40, 64, 256)] + [(96, (37, 250))],   # (96: two chunks per lane)
+                         ids=lambda v: f'{v[0]}x{v[1]}' if isinstance(v, tuple) else str(v))
 def test_kernel_vs_float64(D, shape):
     """Tolerance: fp32 sums of up to J = 1000 terms per entry of T and up to 300 / 1000 per gradient row against float64.  A torch
     fp32 restatement of the reference's step (autograd, same GPU) evaluates the same sums in another order; the kernel may be at

@@ -201,7 +201,7 @@ def test_wide_mm_forms_by_environment(monkeypatch):
             monkeypatch.setenv('INVPREF_WIDE_MM', '0')
         else:
             monkeypatch.delenv('INVPREF_WIDE_MM', raising=False)
-        for (E, D) in ((8, 128), (16, 256)) if mm == '0' else ((16, 256),):
+        for (E, D) in ((8, 128), (16, 256), (8, 256)) if mm == '0' else ((16, 256),):
             a, b = _mstep_pair(800, 300, E, D, 7000, False, (True, True, False, True))
             for x, z in zip(a, b):
                 np.testing.assert_array_equal(x, z)

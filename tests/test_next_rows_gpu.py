@@ -278,7 +278,7 @@ def test_estep_permutation_index_at_a_ragged_large_count():
 def test_estep_row_offsets_32_and_64_bit_agree():
     """estep_assign_kernel addresses rows with 32-bit offsets whenever every table is under 4 GB and with 64-bit products
     otherwise; INVPREF_ESTEP_OFFSETS64=1 (read once per process: a child process here) forces the second form -- the same
-    assignments, counts and weights bit for bit, at a row length that takes the float4 path and one that does not."""
+    assignments, counts and weights bit for bit, at a row length that takes the float4 path (one, two and four chunks per lane) and one that does not."""
     import subprocess
     import sys
     code = (
@@ -286,7 +286,7 @@ def test_estep_row_offsets_32_and_64_bit_agree():
         "from invpref_kdd_2022_amd import ops, synth\n"
         "dev = torch.device('cuda:0')\n"
         "out = []\n"
-        "for D, E in ((64, 4), (30, 3), (256, 16)):\n"
+        "for D, E in ((64, 4), (30, 3), (256, 16), (128, 8)):\n"
         "    U, I, N = 700, 300, 30000\n"
         "    rs = np.random.RandomState(D)\n"
         "    tabs = synth.tables(D + 1, U, I, E, D, std=0.3)\n"
@@ -305,6 +305,6 @@ def test_estep_row_offsets_32_and_64_bit_agree():
             subprocess.run([sys.executable, '-c', code, path], check=True, env=env, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
             z = np.load(path)
             res.append([z[k] for k in z.files])
-    assert len(res[0]) == len(res[1]) >= 12
+    assert len(res[0]) == len(res[1]) >= 16
     for a, b in zip(*res):
         np.testing.assert_array_equal(a, b)

@@ -74,8 +74,9 @@ def seeded_block(D, nu, ni, seed):
 BLOCKS = [(1, 1), (16, 16), (37, 250), (1000, 1000), (4096, 333)]
 
 
-@pytest.mark.parametrize('block', BLOCKS, ids=lambda b: f'{b[0]}x{b[1]}')
-@pytest.mark.parametrize('D', [24, 30, 40, 64, 128, 256])
+@pytest.mark.parametrize('D,block', [(D, b) for b in BLOCKS for D in (24, 30, 40, 64, 128, 256)] +
+                         [(98, (37, 250)), (202, (37, 250))],   # (98 / 202: the scalar loads at two and four chunks per lane)
+                         ids=lambda v: f'{v[0]}x{v[1]}' if isinstance(v, tuple) else str(v))
 def test_kernel_vs_float64(D, block):
     """Tolerance: an fp32 sum of up to 4 096 terms per row against float64.  The existing PureMF gradient pass evaluates the
     same sums on the explicit pair list in fp32 in another order; the kernel may be at most twice as far from float64 (per
