@@ -91,10 +91,10 @@ constexpr int kAltStreamDelay = 40;
 // (p, m, v) stay plain stores: written through they measured SLOWER here (14.9 vs 14.7 us per launch), the other side
 // gathers them in the very next launch
 constexpr int kAltPushSt = 1, kAltSlabSt = 1;
-// pending contribution-row pairs in flight per group (two register sets).  Round 5: 4 (16.26 vs 16.43 us); round 6, the
-// pushed rows now written through (they come from the Infinity Cache, not from a neighbour's L2) and the first burst the
-// launch's bottleneck: 2 is faster, 14.23 -> 14.08 us
-constexpr int kAltPendDepth = 2;
+// pending contribution-row pairs a slice lands in LDS per batch: the wave's four partial-sum rows (idle until the first
+// evaluation) hold 4 pairs x 2 tables x one 1 KiB wave-wide LDS-DMA store.  No registers, and only the pairs a slice has
+// (rounds 5-6 held them in two register sets, two pairs per round trip, the loads clamped and issued for every slice)
+constexpr int kAltPendBatch = 4;
 // (also measured and dropped, profiles/r05-r06 EXPERIMENTS.md: the first pending-row loads only for waves that have pending
 //  rows, the small tables requested in front of the previous step's update, non-temporal loads for the streamed rows)
 
@@ -259,12 +259,6 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
     // (the round's pending ranges travel with its descriptor: one round trip, not two)
     int4 pd = make_int4(0, 0, 0, 0);
     if (has_prev) pd = a.pend[r0 * NG + grp];
-    if (has_cur) {
-        constexpr int ZR4 = (2 * EMAX * DP + EMAX) / 4;   // (dEv | dW | db: 516 floats, SLAB = 524: both multiples of 4)
-        static_assert((2 * EMAX * DP + EMAX) % 4 == 0 && G::SLAB % 4 == 0, "16-byte zeroing");
-        for (int i = threadIdx.x; i < NG * ZR4; i += THREADS)
-            *reinterpret_cast<float4 *>(red + (i / ZR4) * G::SLAB + (i % ZR4) * 4) = f4zero();
-    }
     ASTAMP(1);
     float accLi = 0.f, accLe = 0.f, accLc = 0.f, accL2 = 0.f, accL1 = 0.f;
     float *slab = a.slabs + (int64_t)slab_index * G::SLAB;
@@ -301,7 +295,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
             return sm;
         };
         // ---- everything that depends only on the descriptor goes out together: own rows + moments, the first pending
-        // rows, the first interactions' partner rows
+        // rows, the first interactions' ids (listed ones) -- then their partner rows
         const int rowc = active ? row : 0;
         float4 oi = row4<VEC, FULL>(own0, rowc, D, lg), oe = f4zero();
         float4 mi = row4<VEC, FULL>(a.own_m[0], rowc, D, lg), vi = row4<VEC, FULL>(a.own_v[0], rowc, D, lg);
@@ -310,42 +304,36 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
             oe = row4<VEC, FULL>(own1, rowc, D, lg);
             me = row4<VEC, FULL>(a.own_m[1], rowc, D, lg); ve = row4<VEC, FULL>(a.own_v[1], rowc, D, lg);
         }
-        // pending contribution rows of this slice: contiguous pairs [pa, pb), two register sets
-        constexpr int H = kAltPendDepth / 2;
+        // pending contribution rows of this slice: contiguous pairs [pa, pb).  They land in the wave's own four partial-sum
+        // rows, read as [pair][table][64 lanes x 16 B]: each lane sends its 16-byte piece of a pair the slice HAS straight
+        // to LDS (the destination of a wave instruction is one contiguous 1 KiB block, lane-major; masked lanes write
+        // nothing), up to kAltPendBatch pairs at once
+        constexpr int PB = kAltPendBatch;
+        static_assert(PB * 2 * 64 * 4 <= 4 * G::SLAB && (4 * G::SLAB) % 4 == 0 && G::red % 4 == 0, "landing block: the wave's four slab rows");
         const int npend = (active && has_prev) ? pdd.y - pdd.x : 0;
         const float *pbase = a.pend_rows + (unsigned)(npend > 0 ? pdd.x : 0) * (unsigned)(2 * DP) + lg * 4;
-        float4 ci[2][H], ce[2][H];
-        auto pfetch = [&](int set, int s0) {
+        float *land = red + wave * 4 * G::SLAB;
+        auto pland = [&](int s0) {
 #pragma unroll
-            for (int j = 0; j < H; j++) {
-                const int sj = s0 + j < npend ? s0 + j : (npend > 0 ? npend - 1 : 0);
-                const float *p = pbase + (unsigned)sj * (unsigned)(2 * DP);
-                ci[set][j] = *reinterpret_cast<const float4 *>(p);
-                ce[set][j] = pure ? f4zero() : *reinterpret_cast<const float4 *>(p + DP);
+            for (int j = 0; j < PB; j++) {
+                if (s0 + j < npend) {
+                    const float *p = pbase + (unsigned)(s0 + j) * (unsigned)(2 * DP);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)p,
+                                                     (__attribute__((address_space(3))) void *)(land + (2 * j) * 256), 16, 0, 0);
+                    if (!pure)
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(p + DP),
+                                                         (__attribute__((address_space(3))) void *)(land + (2 * j + 1) * 256), 16, 0, 0);
+                }
             }
         };
         float4 gpi = f4zero(), gpe = f4zero();
-        auto padd = [&](int set, int s0) {
-#pragma unroll
-            for (int j = 0; j < H; j++) {
-                const bool has = s0 + j < npend;
-                f4add(gpi, has ? ci[set][j] : f4zero());
-                if (!pure) f4add(gpe, has ? ce[set][j] : f4zero());
-            }
-        };
-#pragma unroll
-        for (int s = 0; s < 2; s++)
-#pragma unroll
-            for (int j = 0; j < H; j++) ci[s][j] = ce[s][j] = f4zero();
-        // (a round with nothing pending -- most user-side rounds -- adds no loads to the launch's first burst; otherwise both
-        //  register sets go out at once: loading them only for waves that need them measured slower, 17.0 vs 16.1 us)
+        // (a round with nothing pending -- most user-side rounds -- adds no loads to the launch's first burst)
         int n_wave = 0;
         if (rpend) {
             n_wave = npend;
 #pragma unroll
             for (int g = 0; g < 64 / LG; g++) n_wave = max(n_wave, __builtin_amdgcn_readlane(npend, g * LG));
-            pfetch(0, 0);
-            pfetch(1, H);
+            pland(0);
         }
 
         struct Slot {
@@ -384,11 +372,11 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
             sl[j].w = 1.f;
             idn[j] = USample{0, 0, 0.f};
         }
+        USample ls[2 * UE];
+#pragma unroll
+        for (int j = 0; j < 2 * UE; j++) ls[j] = USample{0, 0, 0.f};
         if (has_cur) {   // (workgroup-uniform)
             if (FULL) {
-                USample ls[2 * UE];
-#pragma unroll
-                for (int j = 0; j < 2 * UE; j++) ls[j] = USample{0, 0, 0.f};
                 if (__builtin_amdgcn_ballot_w64(mode == 7) != 0) {
 #pragma unroll
                     for (int j = 0; j < 2 * UE; j++) {
@@ -396,21 +384,45 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
                         ls[j] = USample{q.x, q.y, __builtin_bit_cast(float, q.z)};
                     }
                 }
+            } else {
 #pragma unroll
-                for (int j = 0; j < UE; j++) {
+                for (int j = 0; j < 2 * UE; j++)
+                    if (j < nsmp) ls[j] = sample_at(j);
+            }
+        }
+        // The landed pairs are added in index order; a slice with more than a batch: wait, sum, refill (the loop count is
+        // wave-uniform; every lane reads back the 16 bytes it sent).  The FIRST batch is summed here, in front of the
+        // gathers: they hang on the listed ids, whose wait covers the whole burst -- behind the gathers the wait for the
+        // landed pieces would be a wait for the partner rows too, a round trip the update does not need
+        auto psum = [&](int s0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA pieces have landed
+            float4 xi[PB], xe[PB];
+#pragma unroll
+            for (int j = 0; j < PB; j++) {
+                xi[j] = *reinterpret_cast<const float4 *>(land + (2 * j) * 256 + lane * 4);
+                xe[j] = pure ? f4zero() : *reinterpret_cast<const float4 *>(land + (2 * j + 1) * 256 + lane * 4);
+            }
+#pragma unroll
+            for (int j = 0; j < PB; j++) {
+                const bool has = s0 + j < npend;
+                f4add(gpi, has ? xi[j] : f4zero());
+                if (!pure) f4add(gpe, has ? xe[j] : f4zero());
+            }
+            if (s0 + PB < n_wave) pland(s0 + PB);
+        };
+        if (n_wave > 0) psum(0);
+        if (has_cur) {
+#pragma unroll
+            for (int j = 0; j < UE; j++) {
+                if (FULL) {
                     USample sm = ls[j];
                     if (mode != 7) sm = j == 0 ? USample{dd.z, dd.w, __builtin_bit_cast(float, dd1.x)} : USample{dd1.y, dd1.z, __builtin_bit_cast(float, dd1.w)};
                     if (mode == 0 || !active) sm = USample{0, 0, 0.f};   // (a job without interactions: entry 0's rows, unused)
                     gather(sl[j], sm);
-                    idn[j] = ls[UE + j];
+                } else if (j < nsmp) {
+                    gather(sl[j], ls[j]);
                 }
-            } else {
-#pragma unroll
-                for (int j = 0; j < UE; j++)
-                    if (j < nsmp) gather(sl[j], sample_at(j));
-#pragma unroll
-                for (int j = 0; j < UE; j++)
-                    if (UE + j < nsmp) idn[j] = sample_at(UE + j);
+                idn[j] = ls[UE + j];
             }
         }
         // (this step's small tables, (ii) below; requested in front of the previous step's update instead: no gain, git history)
@@ -421,12 +433,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         // ---- (i) the previous step's update of this row
         if (has_prev) {
             if (rpend) {
-                for (int s0 = 0; s0 < n_wave; s0 += 2 * H) {
-                    padd(0, s0);
-                    if (s0 + 2 * H < n_wave) pfetch(0, s0 + 2 * H);
-                    padd(1, s0 + H);
-                    if (s0 + 3 * H < n_wave) pfetch(1, s0 + 3 * H);
-                }
+                for (int s0 = PB; s0 < n_wave; s0 += PB) psum(s0);   // (slices with more than one batch: few)
                 if (slices > 1) {   // the slices' shares meet: every slice forms the same fixed-order total
                     float *mine = slot_of(grp);
                     *reinterpret_cast<float4 *>(mine + lg * 4) = gpi;
@@ -442,10 +449,12 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
 #pragma nounroll
                             for (int s = 0; s < slices; s += 8) {
                                 float4 xi[8], xe[8];
+                                // (lead + s is a multiple of 8: the eight slots at constant offsets from ONE address)
+                                const float *s8 = slot_of(lead + s) + lg * 4;
 #pragma unroll
                                 for (int j = 0; j < 8; j++) {
-                                    xi[j] = *reinterpret_cast<const float4 *>(slot_of(lead + s + j) + lg * 4);
-                                    xe[j] = *reinterpret_cast<const float4 *>(slot_of(lead + s + j) + DP + lg * 4);
+                                    xi[j] = *reinterpret_cast<const float4 *>(s8 + (j / 4) * (4 * 64 * 4) + (j % 4) * 2 * DP);
+                                    xe[j] = *reinterpret_cast<const float4 *>(s8 + (j / 4) * (4 * 64 * 4) + (j % 4) * 2 * DP + DP);
                                 }
 #pragma unroll
                                 for (int j = 0; j < 8; j++) { f4add(gpi, xi[j]); f4add(gpe, xe[j]); }
@@ -505,7 +514,17 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         if (!pure) { mv_wave[2 * 64 + lane] = me; mv_wave[3 * 64 + lane] = ve; }
         // ---- (ii) the small tables of this step
         if (r == r0) {
-            if (wave == 0) {
+            {   // the wave's four partial-sum rows (dEv | dW | db: 516 floats each; the loss slots are stored whole at the end)
+                // back to zero: nothing lands in them any more, and only this wave touches them before the final slab sum
+                constexpr int ZR4 = (2 * EMAX * DP + EMAX) / 4;
+                static_assert((2 * EMAX * DP + EMAX) % 4 == 0 && G::SLAB % 4 == 0, "16-byte zeroing");
+#pragma unroll
+                for (int t = 0; t < (4 * ZR4 + 63) / 64; t++) {
+                    const int i = lane + 64 * t;
+                    if (i < 4 * ZR4) *reinterpret_cast<float4 *>(land + (i / ZR4) * G::SLAB + (i % ZR4) * 4) = f4zero();
+                }
+            }
+            if (wave == 0) {   // (stages the small tables while the other waves zero)
                 if (has_prev && !pure) alt_stage_issue(a, stg);
                 if (has_prev && !pure) alt_stage_finish(a, stg, gen, sEv, sW, sb, scw);
                 else alt_stage_plain(a, sEv, sW, sb, scw, pure);
