@@ -2,9 +2,11 @@
 
 _FAIRNESS = ('FairnessMFTrainManager', 'fairness_item_table', 'fairness_draw', 'fairness_draw_epochs')
 
+_MACR = ('MACRMatrixFactorization', 'MACRTrainManager')
+
 
 def __getattr__(name):   # resolved on first use: importing the package loads neither torch nor the HIP library
-    if name in _FAIRNESS:
+    if name in _FAIRNESS or name in _MACR:
         from . import baseline
         return getattr(baseline, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

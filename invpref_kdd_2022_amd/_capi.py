@@ -74,12 +74,13 @@ def parse_header(text: str):
     return functions, defines
 
 
-def _read_header():
+def _read_header(path=None):
+    path = HEADER_PATH if path is None else path
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return parse_header(f.read())
     except OSError as exc:
-        raise InvPrefError(f'{HEADER_PATH} is missing ({exc}): the ctypes signatures are derived from it') from None
+        raise InvPrefError(f'{path} is missing ({exc}): the ctypes signatures are derived from it') from None
 
 
 SIGNATURES, DEFINES = _read_header()
@@ -94,6 +95,11 @@ MAX_TOPK_WIDE = DEFINES['MAX_TOPK_WIDE']   # the wide entry points (csrc/invpref
 PROPENSITY_ITEM, PROPENSITY_USER, PROPENSITY_PAIR = (DEFINES['PROPENSITY_' + n] for n in ('ITEM', 'USER', 'PAIR'))
 MAX_LABELS = DEFINES['MAX_LABELS']         # distinct training labels of the naive-Bayes propensities
 FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries the fairness product keeps in LDS
+
+# the MACR baseline's entry points (include/invpref_macr.h, csrc/invpref_macr.hip): the same library, a header and a table of
+# their own -- SIGNATURES / EXPORTS above are include/invpref_hip.h's alone
+MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
+MACR_SIGNATURES, MACR_DEFINES = _read_header(MACR_HEADER_PATH)
 
 _lib = None
 
@@ -111,6 +117,11 @@ def lib():
             fn = getattr(L, name, None)
             if fn is None:
                 raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_hip.h declares')
+            fn.restype, fn.argtypes = restype, argtypes
+        for name, (restype, argtypes) in MACR_SIGNATURES.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_macr.h declares')
             fn.restype, fn.argtypes = restype, argtypes
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')

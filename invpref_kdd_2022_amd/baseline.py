@@ -1,5 +1,5 @@
 """PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF,
-CVIB-MF and fairness-MF.
+CVIB-MF and fairness-MF; and MACR-MF, whose step is a gradient pass of its own (csrc/invpref_macr.hip).
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -167,8 +167,8 @@ class _BasicTrainManager(_InvPrefTrainManager):
                                 pure=True)
             st.swap()
         else:
-            ops.mstep_rows_grad(st.p_views, st.g_views, dp, None, y.to(self.device), weights, len(u), self._coefs(0.), flags,
-                                st.losses6, self.workspace)
+            self._gradient_pass(None, dp, None, None, None, y.to(self.device), weights, len(u), self._coefs(0.), flags,
+                                st.losses6)
             term()
             self._grad_stale = True     # (the planned pass overwrote every row: nothing to zero, see _step())
             for o, ln in self._adam_ranges:
@@ -910,3 +910,169 @@ class FairnessMFTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
         uu, m, rows = self._distinct(u)
         return self._batch_step(u, v, batch_scores_tensor, None, lambda: self._fairness(
             uu, m, rows, torch.from_numpy(idx).to(self.device), self.state.losses6[5:6]))
+
+
+# ------------------------------------------------------------------------------------------------ MACR-MF
+class LinearImplicitScorePredictor(nn.Module):
+    """models.py:223-246: sigmoid(linear_map(x)), the weight xavier-uniform, the bias nn.Linear's default"""
+
+    def __init__(self, factor_dim: int):
+        super().__init__()
+        self.linear_map = nn.Linear(factor_dim, 1)
+        self.output_func = nn.Sigmoid()
+        nn.init.xavier_uniform_(self.linear_map.weight)
+        self.elements_num = float(factor_dim)
+
+    def forward(self, invariant_preferences):
+        """one value per row, on the device kernel of the MACR pass (values only: training goes through MACR's forward)"""
+        x = invariant_preferences.detach().float().contiguous()
+        return ops.macr_branch(x.reshape(-1, x.shape[-1]), self.linear_map.weight.detach(),
+                               self.linear_map.bias.detach()).reshape(*x.shape[:-1], 1)
+
+
+class _MACRLoss(torch.autograd.Function):
+    """score_loss of MACR's forward through ops.macr_grad: the pass forms the loss and the gradients of all six tensors at
+    once, backward() scales them by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, users, items, scores, user_coe, item_coe, *tables):
+        data = [t.detach().contiguous() for t in tables]
+        dev = data[0].device
+        users, items = users.reshape(-1).long().contiguous(), items.reshape(-1).long().contiguous()
+        index = [torch.from_numpy(a).to(dev) for a in ops.macr_index(users, items, data[0].shape[0], data[1].shape[0])]
+        grads = [torch.empty_like(t) for t in data]
+        losses = torch.empty(4, dtype=torch.float32, device=dev)
+        ops.macr_grad(data, grads, users, items, scores.detach().reshape(-1).float().contiguous(), index, user_coe, item_coe,
+                      0., 0., losses)
+        ctx.save_for_backward(*grads)
+        return losses[0].clone()
+
+    @staticmethod
+    def backward(ctx, gs):
+        scale = gs.detach().to(torch.float32)
+        return (None, None, None, None, None, *[g * scale for g in ctx.saved_tensors])
+
+
+class MACRMatrixFactorization(nn.Module):
+    """baseline_models.py:139-234: MF whose training score is sigmoid(u . i) * sigmoid(wu . u + bu) * sigmoid(wi . i + bi) --
+    the interaction, user and item branches -- and whose ranking score is the counterfactual
+    (sigmoid(u . i) - const_c) * user branch * item branch.  The reference's constructor order (the same torch.manual_seed
+    gives the same initial state_dict), parameter and attribute names.
+
+    Not a PureMatrixFactorization: ImplicitTestManager ranks it through predict() + top-k like any other model, never by
+    sigmoid(u . i).  forward / predict / recommend run on csrc/invpref_macr.hip; forward builds the minibatch's inverted index
+    on the host per call (the unfused surface -- MACRTrainManager prepares it once per static minibatch)."""
+    implicit = True
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int, const_c: float, item_coe: float, user_coe: float):
+        super().__init__()
+        self.user_num, self.item_num, self.factor_num = user_num, item_num, factor_num
+        self.user_emb = nn.Embedding(user_num, factor_num)
+        self.item_emb = nn.Embedding(item_num, factor_num)
+        self.output_func = nn.Sigmoid()
+        self.const_c = const_c
+        self.user_predictor = LinearImplicitScorePredictor(factor_num)
+        self.item_predictor = LinearImplicitScorePredictor(factor_num)
+        self.loss_func = nn.BCELoss()
+        self.item_coe, self.user_coe = item_coe, user_coe
+        nn.init.normal_(self.user_emb.weight, std=0.01)  # baseline_models.py:160-162
+        nn.init.normal_(self.item_emb.weight, std=0.01)
+        self._absent = None
+
+    def tables(self):
+        """the six parameters in state_dict order"""
+        return [self.user_emb.weight, self.item_emb.weight, self.user_predictor.linear_map.weight,
+                self.user_predictor.linear_map.bias, self.item_predictor.linear_map.weight, self.item_predictor.linear_map.bias]
+
+    def forward(self, users_id, items_id, ground_truth):  # baseline_models.py:164-182: the three-branch score loss
+        return _MACRLoss.apply(users_id, items_id, ground_truth, float(self.user_coe), float(self.item_coe), *self.tables())
+
+    # PureMF's regularisers over the gathered embedding rows (baseline_models.py:184-208; the predictors are not covered)
+    _seven = _PureMFBase._seven
+    _reg = _PureMFBase._reg
+    get_L1_reg = _PureMFBase.get_L1_reg
+    get_L2_reg = _PureMFBase.get_L2_reg
+
+    def branches(self):
+        """(user branch [user_num], item branch [item_num]): sigmoid(w . row + b) of every row"""
+        up, ip = self.user_predictor.linear_map, self.item_predictor.linear_map
+        return (ops.macr_branch(self.user_emb.weight.detach(), up.weight.detach(), up.bias.detach()),
+                ops.macr_branch(self.item_emb.weight.detach(), ip.weight.detach(), ip.bias.detach()))
+
+    def predict(self, users_id):  # baseline_models.py:210-234
+        a, c = self.branches()
+        users = torch.as_tensor(users_id).to(self.user_emb.weight.device).reshape(-1).to(torch.int64).contiguous()
+        return ops.macr_predict(self.user_emb.weight.detach(), self.item_emb.weight.detach(), users, a, c, self.const_c)
+
+    def recommend(self, users_id, k: int, exclude=None, highlight=None):
+        """Each user's top-k items by the scores of predict() (which may be negative), `exclude` items scoring -1024 and
+        `highlight` items += 1024 (CSR pairs aligned with users_id): the score matrix, then ops.topk_rows.
+        -> (items int64[n, k], scores fp32[n, k])"""
+        ratings = self.predict(users_id)
+        n, I = ratings.shape
+        items, scores, _ = ops.topk_rows(ratings, k, mask=ops.device_csr(exclude, n, I, ratings.device),
+                                         highlight=ops.device_csr(highlight, n, I, ratings.device))
+        return items.to(torch.int64), scores
+
+
+class MACRTrainManager(BasicImplicitTrainManager):
+    """MACR (baseline/special_bias/macr_mf_main.py) under the reference's plain BasicImplicitTrainManager (train.py:345-461):
+    loss = model(users, items, scores) + L2_coe * L2_reg + L1_coe * L1_reg, Adam over all six tensors.
+
+    Always the engine's unfused sequence: MACR's own gradient pass (ops.macr_grad, csrc/invpref_macr.hip: every row of every
+    gradient overwritten) -> the dense / ranged Adam over the whole flat state, which holds the six tensors.  The minibatches
+    are static, so each one's inverted index is built once on the host and kept on the device; the pass reads ids and index
+    when it runs, and the ranged Adam launch carries the device-side schedule, so whole epochs replay as graphs.  Single
+    process."""
+    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    _SINGLE = 'MACR runs in a single process (a sharded form would all-reduce the gradients of all six tensors; not implemented)'
+
+    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, rank=None,
+                 world_size=None, process_group=None):
+        if world_size is not None and int(world_size) > 1:
+            raise NotImplementedError(self._SINGLE)
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        if self.world_size > 1:
+            raise NotImplementedError(self._SINGLE)
+        self._unfused = True        # gradient pass -> Adam, never the fused / alternating step
+        self._macr_index = None     # per static minibatch: (user_ptr, user_pos, item_ptr, item_pos) on the device
+        self._caller = None         # train_a_batch: (users, items, index) of the caller's minibatch
+        self._macr_ws = ops.Workspace(self.device)
+        self._macr_ws.get(max(ops.macr_workspace_bytes(model.user_num, model.item_num, min(batch_size, self.n_total),
+                                                       model.factor_num), 16))   # sized once: capturable launches
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        if self._macr_index is None:
+            u, v = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy()
+            self._macr_index = [tuple(torch.from_numpy(a).to(self.device) for a in ops.macr_index(
+                u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], self.model.user_num, self.model.item_num)) for b in self._raw_batches]
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        st, m = self.state, self.model
+        if k is None:
+            users, items, index = self._caller
+        else:
+            index = self._macr_index[k]
+        ops.macr_grad(st.p_views, st.g_views, users, items, scores, index, m.user_coe, m.item_coe, self.L2_coe, self.L1_coe,
+                      losses6[:4], self._macr_ws)
+
+    @staticmethod
+    def loss_dicts(dev_losses: torch.Tensor) -> list:
+        """the pass writes the reference's four terms (train.py:399-404) into the first four slots"""
+        return [dict(zip(PURE_LOSS_KEYS, v[:4])) for v in dev_losses.tolist()]
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """train.py:379-405 on caller tensors: this minibatch's index is built here, then one step."""
+        dev = self.device
+        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        index = tuple(torch.from_numpy(a).to(dev) for a in ops.macr_index(ud, vd, self.model.user_num, self.model.item_num))
+        self._caller = (ud, vd, index)
+        try:
+            return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
+        finally:
+            self._caller = None

@@ -14,6 +14,7 @@ import torch
 
 from . import _capi
 from . import torch_ops  # noqa: F401  (registers torch.ops.invpref.*)
+from . import torch_ops_macr  # noqa: F401  (the MACR fragment: torch.ops.invpref.macr_*)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -615,3 +616,61 @@ def cvib_grad_(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.
     ws = (workspace or Workspace(user_table.device)).get(max(cvib_workspace_bytes(users.numel(), user_table.shape[1]), 16))
     _o().cvib_grad_(user_table, item_table, users, items, draw_users, draw_items, index, bool(implicit), float(alpha),
                     float(gamma), float(info_coe), float(eps), grad_user, grad_item, loss_out, info_out, pbar_out, qbar_out, ws)
+
+
+# ---- MACR-MF (baseline_models.py:139-234; include/invpref_macr.h, csrc/invpref_macr.hip)
+def macr_workspace_bytes(user_num: int, item_num: int, batch: int, factor_num: int) -> int:
+    """records + float64 partials of one gradient pass: a function of the sizes alone, non-decreasing in each; 0: not taken"""
+    return int(_capi.lib().invpref_macr_workspace_bytes(int(user_num), int(item_num), int(batch), int(factor_num)))
+
+
+def macr_index(users, items, user_num: int, item_num: int):
+    """The inverted index of one minibatch, on the host (numpy; a stable argsort per side): (user_ptr int32 [user_num + 1],
+    user_pos int32 [B], item_ptr int32 [item_num + 1], item_pos int32 [B]).  Row r of a side lists the positions of the
+    minibatch that name it, ascending, in pos[ptr[r]:ptr[r + 1]]; a position whose id lies outside the table is in none of
+    that side's lists (pos is zero padded behind ptr[-1]).  Built once per static minibatch and uploaded."""
+    import numpy as np
+    out = []
+    for ids, n in ((users, user_num), (items, item_num)):
+        ids = (ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)).reshape(-1).astype(np.int64)
+        keep = np.flatnonzero((ids >= 0) & (ids < n))
+        order = keep[np.argsort(ids[keep], kind='stable')]
+        ptr = np.zeros(int(n) + 1, np.int64)
+        np.cumsum(np.bincount(ids[keep], minlength=int(n)), out=ptr[1:])
+        pos = np.zeros(len(ids), np.int32)
+        pos[:len(order)] = order
+        out += [ptr.astype(np.int32), pos]
+    return tuple(out)
+
+
+def macr_grad(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], users: torch.Tensor, items: torch.Tensor,
+              scores: torch.Tensor, index: Sequence[torch.Tensor], user_coe: float, item_coe: float, L2_coe: float,
+              L1_coe: float, losses4: torch.Tensor, workspace: Optional[Workspace] = None) -> None:
+    """The gradient pass of one MACR step.  params / grads: the six tensors in state_dict order (user table, item table, user
+    predictor weight and bias, item predictor weight and bias); index: macr_index's four arrays on the device.  OVERWRITES
+    every row of every gradient (rows without an interaction get zeros) and losses4 = (score_loss, L2_reg, L1_reg, loss).
+    Bitwise reproducible, no float atomics, no host sync (capturable once the workspace is sized; a replay reads ids and
+    index as they are then).  An id outside its table: the interaction is skipped and the four losses are NaN."""
+    _gpu(users, items, scores, losses4, *params, *grads, *index)
+    P, Q = params[0], params[1]
+    nbytes = macr_workspace_bytes(P.shape[0], Q.shape[0], users.numel(), P.shape[1])
+    if nbytes == 0:
+        raise InvPrefError(f'macr_grad: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
+                           f'{users.numel()} interactions)')
+    ws = (workspace or Workspace(P.device)).get(nbytes)
+    _o().macr_grad_(P, Q, params[2], params[3], params[4], params[5], users, items, scores, *index, float(user_coe),
+                    float(item_coe), float(L2_coe), float(L1_coe), *grads, losses4, ws)
+
+
+def macr_branch(table: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """sigmoid(w . table[r] + b) of every row (LinearImplicitScorePredictor.forward, models.py:232-235) -> fp32 [n_rows]"""
+    _gpu(table, w, b)
+    return _o().macr_branch(table, w, b)
+
+
+def macr_predict(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, user_branch: torch.Tensor,
+                 item_branch: torch.Tensor, const_c: float) -> torch.Tensor:
+    """MACR's ranking scores (baseline_models.py:210-234): ((sigmoid(Pu[users] Qi^T) - const_c) * user_branch[users]) *
+    item_branch -> fp32 [n, item_num]"""
+    _gpu(user_table, item_table, users, user_branch, item_branch)
+    return _o().macr_predict(user_table, item_table, users, user_branch, item_branch, float(const_c))

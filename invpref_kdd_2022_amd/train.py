@@ -720,11 +720,9 @@ class _InvPrefTrainManager:
         sc = (self._sched['state'], self._sched['table'], st.step & 1) if sched else None
         if self.use_plan:
             wts, flags = self._step_weights(b.weights)
-            ops.mstep_rows_grad(st.p_views, st.g_views, self._plans[k], b.envs, b.scores, wts, b.global_n, coefs, flags, lp,
-                                self.workspace, sched=sc)
+            self._gradient_pass(k, self._plans[k], b.users, b.items, b.envs, b.scores, wts, b.global_n, coefs, flags, lp, sc)
         else:
-            ops.mstep_grad(st.p_views, st.g_views, b.users, b.items, b.envs, b.scores, b.weights, b.global_n, coefs,
-                           self._flags, lp, self.workspace)
+            self._gradient_pass(k, None, b.users, b.items, b.envs, b.scores, b.weights, b.global_n, coefs, self._flags, lp, None)
         if multi:
             if self.world_size > 1 or self._collective_ok:
                 self._exchange_gradient(k)   # all-reduce (whole or packed), or reduce-scatter (this rank keeps its slice of the sum)
@@ -746,6 +744,20 @@ class _InvPrefTrainManager:
             if zero and self.exchange == 'scatter' and self.world_size > 1:
                 st.grad.zero_()   # plan-free gradients ADD: the slices this rank's Adam did not clear must start from zero too
             self._exchange_parameters()
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        """The gradient pass of the unfused sequence: the gradient of one minibatch into state.g_views, its loss terms into
+        losses6.  k: the static minibatch, None for a caller-supplied one (baseline.py: _batch_step).  plan: its row plan
+        (the planned pass OVERWRITES every row), None: the plan-free pass over users / items, which ADDS.  A manager whose
+        loss is not the step's own overrides this (baseline.py: MACRTrainManager)."""
+        st = self.state
+        if plan is not None:
+            ops.mstep_rows_grad(st.p_views, st.g_views, plan, envs, scores, weights, batch_norm, coefs, flags, losses6,
+                                self.workspace, sched=sched)
+        else:
+            ops.mstep_grad(st.p_views, st.g_views, users, items, envs, scores, weights, batch_norm, coefs, flags, losses6,
+                           self.workspace)
 
     def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
         """Hook of the unfused sequence (gradient pass -> [exchange] -> HERE -> Adam), minibatch k of epoch slot
