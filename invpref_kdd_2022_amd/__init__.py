@@ -4,9 +4,11 @@ _FAIRNESS = ('FairnessMFTrainManager', 'fairness_item_table', 'fairness_draw', '
 
 _MACR = ('MACRMatrixFactorization', 'MACRTrainManager')
 
+_CAUSE = ('CausEMatrixFactorization', 'CausEExplicitMatrixFactorization', 'CausETrainManager', 'CausEExplicitTrainManager')
+
 
 def __getattr__(name):   # resolved on first use: importing the package loads neither torch nor the HIP library
-    if name in _FAIRNESS or name in _MACR:
+    if name in _FAIRNESS or name in _MACR or name in _CAUSE:
         from . import baseline
         return getattr(baseline, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -101,6 +101,11 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 MACR_SIGNATURES, MACR_DEFINES = _read_header(MACR_HEADER_PATH)
 
+# the CausE baselines' entry points (include/invpref_cause.h, csrc/invpref_cause.hip): likewise a header and a table of their own
+CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
+CAUSE_SIGNATURES, CAUSE_DEFINES = _read_header(CAUSE_HEADER_PATH)
+CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
+
 _lib = None
 
 
@@ -122,6 +127,11 @@ def lib():
             fn = getattr(L, name, None)
             if fn is None:
                 raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_macr.h declares')
+            fn.restype, fn.argtypes = restype, argtypes
+        for name, (restype, argtypes) in CAUSE_SIGNATURES.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_cause.h declares')
             fn.restype, fn.argtypes = restype, argtypes
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')

@@ -1,5 +1,6 @@
 """PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF,
-CVIB-MF and fairness-MF; and MACR-MF, whose step is a gradient pass of its own (csrc/invpref_macr.hip).
+CVIB-MF and fairness-MF; and MACR-MF and CausE, whose steps are gradient passes of their own (csrc/invpref_macr.hip,
+csrc/invpref_cause.hip).
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -1076,3 +1077,201 @@ class MACRTrainManager(BasicImplicitTrainManager):
             return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
         finally:
             self._caller = None
+
+
+# ------------------------------------------------------------------------------------------------ CausE
+CAUSE_LOSS_KEYS = ['train_score_loss', 'uniform_score_loss', 'teacher_reg', 'L2_reg', 'loss']  # baseline_train.py:715-721
+
+
+class _CausEModelMixin:
+    """What CausEMatrixFactorization and its explicit twin share (baseline_models.py:555-649, :706-794): a student pair and a
+    teacher pair of tables, created and re-drawn in the reference's order (user_emb, item_emb, teacher_user_emb,
+    teacher_item_emb: the same torch.manual_seed gives the same state_dict), and the reference's methods with their
+    `train_teacher` switch on the unfused forward / regulariser functions, applied to the chosen pair."""
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int):
+        nn.Module.__init__(self)
+        self.user_num, self.item_num, self.factor_num = user_num, item_num, factor_num
+        self.user_emb = nn.Embedding(user_num, factor_num)
+        self.item_emb = nn.Embedding(item_num, factor_num)
+        self.teacher_user_emb = nn.Embedding(user_num, factor_num)
+        self.teacher_item_emb = nn.Embedding(item_num, factor_num)
+        if self.implicit:
+            self.output_func = nn.Sigmoid()
+            self.loss_func = nn.BCELoss()
+        else:
+            self.loss_func = nn.MSELoss()
+        for emb in (self.user_emb, self.item_emb, self.teacher_user_emb, self.teacher_item_emb):
+            nn.init.normal_(emb.weight, std=0.01)
+        self._absent = None
+
+    def tables(self):
+        """the four tables in state_dict order: the student's first, so whatever ranks tables()[0] . tables()[1] ranks the
+        student"""
+        return [self.user_emb.weight, self.item_emb.weight, self.teacher_user_emb.weight, self.teacher_item_emb.weight]
+
+    def _pair(self, train_teacher: bool):
+        return ((self.teacher_user_emb.weight, self.teacher_item_emb.weight) if train_teacher
+                else (self.user_emb.weight, self.item_emb.weight))
+
+    def _stand_ins(self, rows_user: int, rows_item: int):
+        w = self.user_emb.weight
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=w.device)  # noqa: E731
+        D = self.factor_num
+        return [z(rows_user, D), z(rows_item, D), z(1, D), z(1, D), z(1)]
+
+    def _seven(self, train_teacher: bool = False):
+        w = self.user_emb.weight
+        if self._absent is None or self._absent[0].device != w.device:
+            self._absent = self._stand_ins(self.user_num, self.item_num)
+        return list(self._pair(train_teacher)) + self._absent
+
+    def _scores(self, users_id, items_id, train_teacher: bool = False):
+        from .autograd import InvPrefForward
+        inv, _, _ = InvPrefForward.apply(users_id, items_id, torch.zeros_like(users_id), 0., self.implicit,
+                                         *self._seven(train_teacher))
+        return inv
+
+    def forward(self, users_id, items_id, train_teacher, ground_truth=None):  # baseline_models.py:574-593 / :724-742
+        final_ratings = self._scores(users_id, items_id, bool(train_teacher)).reshape(-1)
+        if ground_truth is not None:
+            return self.loss_func(final_ratings, ground_truth)
+        return final_ratings
+
+    def _reg(self, users_id, items_id, norm: int, train_teacher: bool = False):
+        from .autograd import InvPrefReg
+        if not self.implicit:
+            return 2. * InvPrefReg.apply(users_id, items_id, torch.zeros_like(users_id), norm, True, False,
+                                         *self._seven(train_teacher))
+        # baseline_models.py:608-619: the implicit model's get_items_reg gathers the USER table of the chosen pair with the
+        # ITEM ids -- the regulariser runs over (user table, user table), and an item id beyond it is the reference's IndexError
+        if items_id.numel() and int(items_id.max()) >= self.user_num:
+            raise IndexError(f'index out of range in self: item id {int(items_id.max())} indexes the user table '
+                             f'({self.user_num} rows) in get_items_reg')
+        w = self._pair(train_teacher)[0]
+        return 2. * InvPrefReg.apply(users_id, items_id, torch.zeros_like(users_id), norm, True, False, w, w,
+                                     *self._stand_ins(self.user_num, self.user_num))
+
+    def get_L1_reg(self, users_id, items_id, train_teacher):  # baseline_models.py:621-622 / :770-771
+        return self._reg(users_id, items_id, 1, bool(train_teacher))
+
+    def get_L2_reg(self, users_id, items_id, train_teacher):  # baseline_models.py:624-625 / :773-774
+        return self._reg(users_id, items_id, 2, bool(train_teacher))
+
+    # the pull of the student towards the detached teacher (baseline_models.py:634-649): plain tensor expressions -- the
+    # managers never call them, their step forms the term inside csrc/invpref_cause.hip
+    def item_teacher_reg(self, items_id):
+        return torch.mean((self.item_emb(items_id) - self.teacher_item_emb(items_id).detach()) ** 2)
+
+    def user_teacher_reg(self, users_id):
+        return torch.mean((self.user_emb(users_id) - self.teacher_user_emb(users_id).detach()) ** 2)
+
+
+class CausEMatrixFactorization(_CausEModelMixin, PureMatrixFactorization):
+    """baseline_models.py:555-649.  A PureMatrixFactorization whose tables() lists the student pair first: predict(),
+    recommend() and ImplicitTestManager's fused predict_topk route rank the student, as the reference's predict() does.
+    get_L1_reg / get_L2_reg keep the reference's quirk: the item ids index the user table."""
+    implicit = True
+
+
+class CausEExplicitMatrixFactorization(_CausEModelMixin, PureExplicitMatrixFactorization):
+    """baseline_models.py:706-794; predict(users, items) scores the student pair."""
+    implicit = False
+
+
+class _CausEManagerMixin(_UniformMixin):
+    """CausETrainManager / CausEExplicitTrainManager (baseline_train.py:650-797):
+        loss = train_score_loss + uniform_loss_coe * uniform_score_loss + L2_reg + teacher_reg_coe * teacher_reg
+    with the student's score loss over the minibatch, the teacher's over the WHOLE uniform set at every step, L2_reg already
+    weighted by L2_coe / teacher_L2_coe, and the student pulled towards the detached teacher ('i': item rows, 'u': user rows).
+    Adam over all four tables; L1_coe is accepted and unused, like the reference's.
+
+    Always the engine's unfused sequence: CausE's own gradient pass (ops.cause_grad, csrc/invpref_cause.hip: every row of all
+    four gradients overwritten) -> the dense / ranged Adam over the whole flat state.  The minibatches are static, so each
+    one's inverted index is built once on the host and kept on the device, and the uniform set's once in the constructor; the
+    pass reads ids and index when it runs, so whole epochs replay as graphs.  Single process."""
+    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    _SINGLE = 'CausE runs in a single process (a sharded form would all-reduce the gradients of all four tables; not implemented)'
+    _QUIRK = ('the reference\'s implicit CausE model indexes the user table ({U} rows) with item ids in get_items_reg and raises '
+              'IndexError on {what} item id {i}; use item ids below user_num')
+
+    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, uniform_data: torch.Tensor,
+                 batch_size: int, epochs: int, evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float,
+                 test_begin_epoch: int = 0, uniform_loss_coe: float = 1.0, teacher_reg_coe: float = 1.0,
+                 teacher_reg_mode: str = 'i', teacher_L2_coe: float = 5., *, rank=None, world_size=None, process_group=None):
+        if teacher_reg_mode not in ('i', 'u', 'ui'):
+            raise ValueError(f'teacher_reg_mode must be \'i\', \'u\' or \'ui\', got {teacher_reg_mode!r}')
+        if world_size is not None and int(world_size) > 1:
+            raise NotImplementedError(self._SINGLE)
+        if uniform_data is None or uniform_data.shape[0] == 0:
+            raise ValueError('CausE needs a non-empty uniform set: its teacher trains on all of it at every step')
+        if self.implicit:
+            self._check_item_ids(model, training_data[:, 1], 'a training')
+            self._check_item_ids(model, uniform_data[:, 1], 'a uniform')
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        if self.world_size > 1:
+            raise NotImplementedError(self._SINGLE)
+        self.uniform_loss_coe, self.teacher_reg_coe = uniform_loss_coe, teacher_reg_coe
+        self.teacher_reg_mode, self.teacher_L2_coe = teacher_reg_mode, teacher_L2_coe
+        self._keep_uniform(uniform_data)
+        self.uniform_user, self.uniform_item = self.uniform_user.contiguous(), self.uniform_item.contiguous()
+        self.uniform_score = self.uniform_score.contiguous()
+        self._unfused = True         # gradient pass -> Adam, never the fused / alternating step
+        self._cause_index = None     # per static minibatch: (user_ptr, user_pos, item_ptr, item_pos) on the device
+        self._uni_index = tuple(torch.from_numpy(a).to(self.device) for a in ops.macr_index(
+            self.uniform_user, self.uniform_item, model.user_num, model.item_num))
+        self._caller = None          # train_a_batch: (users, items, index) of the caller's minibatch
+        self._cause_ws = ops.Workspace(self.device)
+        self._cause_ws.get(max(ops.cause_workspace_bytes(model.user_num, model.item_num, min(batch_size, self.n_total),
+                                                         self.uniform_user.numel(), model.factor_num), 16))   # sized once
+
+    @classmethod
+    def _check_item_ids(cls, model, items, what: str) -> None:
+        if items.numel() and int(items.max()) >= model.user_num:
+            raise ValueError(cls._QUIRK.format(U=model.user_num, what=what, i=int(items.max())))
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        if self._cause_index is None:
+            u, v = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy()
+            self._cause_index = [tuple(torch.from_numpy(a).to(self.device) for a in ops.macr_index(
+                u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], self.model.user_num, self.model.item_num)) for b in self._raw_batches]
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        st = self.state
+        if k is None:
+            users, items, index = self._caller
+        else:
+            index = self._cause_index[k]
+        ops.cause_grad(st.p_views, st.g_views, users, items, scores, index, self.uniform_user, self.uniform_item,
+                       self.uniform_score, self._uni_index, self.implicit, self.teacher_reg_mode, self.L2_coe,
+                       self.teacher_L2_coe, self.uniform_loss_coe, self.teacher_reg_coe, losses6[:5], self._cause_ws)
+
+    @staticmethod
+    def loss_dicts(dev_losses: torch.Tensor) -> list:
+        """the pass writes the reference's five terms (baseline_train.py:715-721) into the first five slots"""
+        return [dict(zip(CAUSE_LOSS_KEYS, v[:5])) for v in dev_losses.tolist()]
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """baseline_train.py:674-722 on caller tensors: this minibatch's index is built here, then one step."""
+        dev = self.device
+        if self.implicit:
+            self._check_item_ids(self.model, batch_items_tensor, 'a minibatch')
+        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        index = tuple(torch.from_numpy(a).to(dev) for a in ops.macr_index(ud, vd, self.model.user_num, self.model.item_num))
+        self._caller = (ud, vd, index)
+        try:
+            return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
+        finally:
+            self._caller = None
+
+
+class CausETrainManager(_CausEManagerMixin, BasicImplicitTrainManager):
+    """baseline_train.py:650-722 (baseline/general_bias_with_rct/CausE_mf_main.py)"""
+
+
+class CausEExplicitTrainManager(_CausEManagerMixin, BasicExplicitTrainManager):
+    """baseline_train.py:725-797 (baseline_explicit/general_bias_with_rct/CausE_mf_main.py)"""

@@ -15,6 +15,7 @@ import torch
 from . import _capi
 from . import torch_ops  # noqa: F401  (registers torch.ops.invpref.*)
 from . import torch_ops_macr  # noqa: F401  (the MACR fragment: torch.ops.invpref.macr_*)
+from . import torch_ops_cause  # noqa: F401  (the CausE fragment: torch.ops.invpref.cause_grad_)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -674,3 +675,37 @@ def macr_predict(user_table: torch.Tensor, item_table: torch.Tensor, users: torc
     item_branch -> fp32 [n, item_num]"""
     _gpu(user_table, item_table, users, user_branch, item_branch)
     return _o().macr_predict(user_table, item_table, users, user_branch, item_branch, float(const_c))
+
+
+# ---- CausE (baseline_models.py:555-649, :706-794; include/invpref_cause.h, csrc/invpref_cause.hip)
+CAUSE_MODES = {'i': _capi.CAUSE_MODE_ITEM, 'u': _capi.CAUSE_MODE_USER, 'ui': _capi.CAUSE_MODE_ITEM | _capi.CAUSE_MODE_USER}
+
+
+def cause_workspace_bytes(user_num: int, item_num: int, batch: int, uniform_num: int, factor_num: int) -> int:
+    """records + float64 partials of one gradient pass: a function of the sizes alone, non-decreasing in each; 0: not taken"""
+    return int(_capi.lib().invpref_cause_workspace_bytes(int(user_num), int(item_num), int(batch), int(uniform_num),
+                                                         int(factor_num)))
+
+
+def cause_grad(params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor], users: torch.Tensor, items: torch.Tensor,
+               scores: torch.Tensor, index: Sequence[torch.Tensor], uni_users: torch.Tensor, uni_items: torch.Tensor,
+               uni_scores: torch.Tensor, uni_index: Sequence[torch.Tensor], implicit: bool, mode, L2_coe: float,
+               teacher_L2_coe: float, uniform_loss_coe: float, teacher_reg_coe: float, losses5: torch.Tensor,
+               workspace: Optional[Workspace] = None) -> None:
+    """The gradient pass of one CausE step.  params4 / grads4: the four tables in state_dict order (student user, student item,
+    teacher user, teacher item); index / uni_index: macr_index's four arrays of the minibatch / of the uniform set, on the
+    device; mode: 'i', 'u', 'ui' or the bit mask (item 1, user 2).  OVERWRITES every row of every gradient (rows without a term
+    get zeros) and losses5 = (train_score_loss, uniform_score_loss, teacher_reg, L2_reg, loss).  implicit: the reference's L2
+    term indexes the USER tables with the item ids (include/invpref_cause.h).  Bitwise reproducible, no float atomics, no host
+    sync (capturable once the workspace is sized; a replay reads ids and index as they are then).  An id outside its table --
+    implicit: also an item id >= user_num --: the five losses are NaN."""
+    _gpu(users, items, scores, uni_users, uni_items, uni_scores, losses5, *params4, *grads4, *index, *uni_index)
+    P, Q = params4[0], params4[1]
+    nbytes = cause_workspace_bytes(P.shape[0], Q.shape[0], users.numel(), uni_users.numel(), P.shape[1])
+    if nbytes == 0:
+        raise InvPrefError(f'cause_grad: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
+                           f'{users.numel()} + {uni_users.numel()} positions)')
+    ws = (workspace or Workspace(P.device)).get(nbytes)
+    _o().cause_grad_(*params4, users, items, scores, *index, uni_users, uni_items, uni_scores, *uni_index, bool(implicit),
+                     CAUSE_MODES[mode] if isinstance(mode, str) else int(mode), float(L2_coe), float(teacher_L2_coe),
+                     float(uniform_loss_coe), float(teacher_reg_coe), *grads4, losses5, ws)

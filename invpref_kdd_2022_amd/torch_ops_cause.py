@@ -1,0 +1,73 @@
+"""``torch.ops.invpref.cause_grad_``: the CausE baselines' operator (include/invpref_cause.h, csrc/invpref_cause.hip),
+registered as a FRAGMENT of the ``invpref`` library with a name list of its own -- ``torch_ops.NAMES`` is the main header's
+operators, ``torch_ops_macr.NAMES`` MACR's.
+
+``cause_grad_``    the gradient pass of one CausE step: overwrites the gradients of the student and the teacher tables and the
+                   five loss values
+
+Registered for the CUDA/HIP dispatch key only (no eager implementation exists); the fake of this void operator returns
+nothing.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _capi
+from . import torch_ops  # noqa: F401  (the library this one is a fragment of)
+from ._capi import InvPrefError, call, ptr, stream_ptr
+
+_LIB = torch.library.Library('invpref', 'FRAGMENT')
+NAMES = []
+
+
+def _define(schema: str):
+    _LIB.define(schema)
+    name = schema.split('(')[0]
+    NAMES.append(name)
+    if schema.endswith('-> ()'):
+        torch.library.register_fake(f'invpref::{name}', lib=_LIB)(lambda *args, **kwargs: None)
+
+
+def _req(t, dtype, name, shape=None):
+    _capi._req(t, dtype, name)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise InvPrefError(f'{name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
+
+
+_define('cause_grad_(Tensor user_table, Tensor item_table, Tensor teacher_user_table, Tensor teacher_item_table, '
+        'Tensor users, Tensor items, Tensor scores, Tensor user_ptr, Tensor user_pos, Tensor item_ptr, Tensor item_pos, '
+        'Tensor uni_users, Tensor uni_items, Tensor uni_scores, Tensor uni_user_ptr, Tensor uni_user_pos, '
+        'Tensor uni_item_ptr, Tensor uni_item_pos, bool implicit, int reg_mode, float L2_coe, float teacher_L2_coe, '
+        'float uniform_loss_coe, float teacher_reg_coe, Tensor(a!) grad_user, Tensor(b!) grad_item, '
+        'Tensor(c!) grad_teacher_user, Tensor(d!) grad_teacher_item, Tensor(e!) losses5, Tensor(f!) workspace) -> ()')
+
+
+def _cause_grad(user_table, item_table, teacher_user_table, teacher_item_table, users, items, scores, user_ptr, user_pos,
+                item_ptr, item_pos, uni_users, uni_items, uni_scores, uni_user_ptr, uni_user_pos, uni_item_ptr, uni_item_pos,
+                implicit, reg_mode, L2_coe, teacher_L2_coe, uniform_loss_coe, teacher_reg_coe, grad_user, grad_item,
+                grad_teacher_user, grad_teacher_item, losses5, workspace):
+    U, I, D = torch_ops._pair_tables('cause_grad', user_table, item_table, grad_user, grad_item, workspace=workspace)
+    for t, n, rows in ((teacher_user_table, 'teacher_user_table', U), (grad_teacher_user, 'grad_teacher_user', U),
+                       (teacher_item_table, 'teacher_item_table', I), (grad_teacher_item, 'grad_teacher_item', I)):
+        _req(t, torch.float32, n, (rows, D))
+    B, Nu = users.numel(), uni_users.numel()
+    for pre, n, ids_u, ids_i, y, up, upos, ip, ipos in (
+            ('', B, users, items, scores, user_ptr, user_pos, item_ptr, item_pos),
+            ('uni_', Nu, uni_users, uni_items, uni_scores, uni_user_ptr, uni_user_pos, uni_item_ptr, uni_item_pos)):
+        _req(ids_u, torch.int64, pre + 'users', (n,))
+        _req(ids_i, torch.int64, pre + 'items', (n,))
+        _req(y, torch.float32, pre + 'scores', (n,))
+        _req(up, torch.int32, pre + 'user_ptr', (U + 1,))
+        _req(ip, torch.int32, pre + 'item_ptr', (I + 1,))
+        _req(upos, torch.int32, pre + 'user_pos', (n,))
+        _req(ipos, torch.int32, pre + 'item_pos', (n,))
+    _req(losses5, torch.float32, 'losses5', (5,))
+    call('invpref_cause_grad_hip', ptr(user_table), ptr(item_table), ptr(teacher_user_table), ptr(teacher_item_table), U, I, D,
+         ptr(users), ptr(items), ptr(scores), B, ptr(user_ptr), ptr(user_pos), ptr(item_ptr), ptr(item_pos), ptr(uni_users),
+         ptr(uni_items), ptr(uni_scores), Nu, ptr(uni_user_ptr), ptr(uni_user_pos), ptr(uni_item_ptr), ptr(uni_item_pos),
+         int(bool(implicit)), int(reg_mode), float(L2_coe), float(teacher_L2_coe), float(uniform_loss_coe), float(teacher_reg_coe),
+         ptr(grad_user), ptr(grad_item), ptr(grad_teacher_user), ptr(grad_teacher_item), ptr(losses5), ptr(workspace),
+         workspace.numel(), stream_ptr())
+
+
+_LIB.impl('cause_grad_', _cause_grad, 'CUDA')
