@@ -106,6 +106,11 @@ CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 CAUSE_SIGNATURES, CAUSE_DEFINES = _read_header(CAUSE_HEADER_PATH)
 CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 
+# the scaled retrieval's entry points (include/invpref_retrieve_scaled.h; csrc/invpref_retrieve.hip, invpref_topk_wide.hip):
+# likewise a header and a table of their own
+SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
+SCALED_SIGNATURES, SCALED_DEFINES = _read_header(SCALED_HEADER_PATH)
+
 _lib = None
 
 
@@ -132,6 +137,11 @@ def lib():
             fn = getattr(L, name, None)
             if fn is None:
                 raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_cause.h declares')
+            fn.restype, fn.argtypes = restype, argtypes
+        for name, (restype, argtypes) in SCALED_SIGNATURES.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_retrieve_scaled.h declares')
             fn.restype, fn.argtypes = restype, argtypes
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')

@@ -960,8 +960,9 @@ class MACRMatrixFactorization(nn.Module):
     (sigmoid(u . i) - const_c) * user branch * item branch.  The reference's constructor order (the same torch.manual_seed
     gives the same initial state_dict), parameter and attribute names.
 
-    Not a PureMatrixFactorization: ImplicitTestManager ranks it through predict() + top-k like any other model, never by
-    sigmoid(u . i).  forward / predict / recommend run on csrc/invpref_macr.hip; forward builds the minibatch's inverted index
+    Not a PureMatrixFactorization: ImplicitTestManager never ranks it by sigmoid(u . i) alone but by rank_fn(), the scaled scan
+    of csrc/invpref_retrieve.hip (its topk() keeps the predict() + top-k route of any other model).  forward / predict run on
+    csrc/invpref_macr.hip; forward builds the minibatch's inverted index
     on the host per call (the unfused surface -- MACRTrainManager prepares it once per static minibatch)."""
     implicit = True
 
@@ -1005,15 +1006,23 @@ class MACRMatrixFactorization(nn.Module):
         users = torch.as_tensor(users_id).to(self.user_emb.weight.device).reshape(-1).to(torch.int64).contiguous()
         return ops.macr_predict(self.user_emb.weight.detach(), self.item_emb.weight.detach(), users, a, c, self.const_c)
 
+    def rank_fn(self):
+        """ImplicitTestManager's fused route: f(users, k, mask, highlight, truth) -> (items, scores, hits) ranking by the
+        scores of predict() without their matrix -- the two branch launches here, then one scaled scan per call of f"""
+        a, c = self.branches()
+        P, Q = self.user_emb.weight.detach().contiguous(), self.item_emb.weight.detach().contiguous()
+        return lambda users, k, mask, highlight, truth: ops.predict_topk_scaled(
+            P, Q, users, k, a, c, self.const_c, True, mask=mask, highlight=highlight, truth=truth)
+
     def recommend(self, users_id, k: int, exclude=None, highlight=None):
         """Each user's top-k items by the scores of predict() (which may be negative), `exclude` items scoring -1024 and
-        `highlight` items += 1024 (CSR pairs aligned with users_id): the score matrix, then ops.topk_rows.
-        -> (items int64[n, k], scores fp32[n, k])"""
-        ratings = self.predict(users_id)
-        n, I = ratings.shape
-        items, scores, _ = ops.topk_rows(ratings, k, mask=ops.device_csr(exclude, n, I, ratings.device),
-                                         highlight=ops.device_csr(highlight, n, I, ratings.device))
-        return items.to(torch.int64), scores
+        `highlight` items += 1024 (CSR pairs aligned with users_id): the branches once, then the scaled scan
+        (ops.predict_topk_scaled with shift = const_c) -- no rating matrix; the ranking of predict()'s matrix item for item
+        and score for score.  -> (items int64[n, k], scores fp32[n, k])"""
+        a, c = self.branches()
+        users = torch.as_tensor(users_id).to(self.user_emb.weight.device)
+        return ops.recommend(self.user_emb.weight, self.item_emb.weight, users, k, exclude=exclude, highlight=highlight,
+                             user_scale=a, item_scale=c, shift=self.const_c)
 
 
 class MACRTrainManager(BasicImplicitTrainManager):

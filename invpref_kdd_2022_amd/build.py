@@ -17,8 +17,10 @@ SOURCES = ['invpref_kernels.hip', 'invpref_step.hip', 'invpref_eval.hip', 'invpr
            'invpref_topk_wide.hip', 'invpref_propensity.hip',
            'invpref_exposure.hip', 'invpref_impute.hip', 'invpref_cvib.hip', 'invpref_fairness.hip', 'invpref_macr.hip',
            'invpref_cause.hip']
-HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'step_wide.hpp', os.path.join('..', '..', 'include', 'invpref_hip.h'),
-           os.path.join('..', '..', 'include', 'invpref_macr.h'), os.path.join('..', '..', 'include', 'invpref_cause.h')]
+HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp',
+           os.path.join('..', '..', 'include', 'invpref_hip.h'),
+           os.path.join('..', '..', 'include', 'invpref_macr.h'), os.path.join('..', '..', 'include', 'invpref_cause.h'),
+           os.path.join('..', '..', 'include', 'invpref_retrieve_scaled.h')]
 # -ffp-contract=off: every fma of the canonical arithmetic is written explicitly
 FLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-ffp-contract=off',
          '-fno-fast-math', '-Wall', '-Wno-unused-function']

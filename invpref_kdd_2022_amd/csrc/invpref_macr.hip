@@ -368,6 +368,17 @@ int with_row_shape(int D, bool vec, F &&f) {
 
 }  // namespace
 
+namespace invpref {
+// the epilogue over [n, I] scores in place (also the scale pass of invpref_predict_topk_scaled_wide_hip, invpref_topk_wide.hip)
+int scale_rows(float *scores, const int64_t *users, int64_t n, int64_t I, const float *user_scale, const float *item_scale,
+               float shift, hipStream_t st) {
+    const unsigned gy = (unsigned)(n < 4096 ? n : 4096);
+    hipLaunchKernelGGL(macr_epilogue_kernel, dim3((unsigned)((I + 255) / 256), gy), dim3(256), 0, st, scores, users, n, I,
+                       user_scale, item_scale, shift);
+    return (int)hipGetLastError();
+}
+}  // namespace invpref
+
 extern "C" {
 
 size_t invpref_macr_workspace_bytes(int64_t user_num, int64_t item_num, int64_t batch, int64_t factor_num) {
@@ -442,10 +453,7 @@ int invpref_macr_predict_hip(const float *user_table, const float *item_table, c
     if (!user_branch || !item_branch) return INVPREF_EINVAL;
     if (int rc = invpref_predict_hip(user_table, item_table, users, n_users, item_num, factor_num, 1, out, stream)) return rc;
     if (n_users == 0) return 0;
-    const unsigned gy = (unsigned)(n_users < 4096 ? n_users : 4096);
-    hipLaunchKernelGGL(macr_epilogue_kernel, dim3((unsigned)((item_num + 255) / 256), gy), dim3(256), 0,
-                       (hipStream_t)stream, out, users, n_users, item_num, user_branch, item_branch, (float)const_c);
-    return (int)hipGetLastError();
+    return scale_rows(out, users, n_users, item_num, user_branch, item_branch, (float)const_c, (hipStream_t)stream);
 }
 
 }  // extern "C"

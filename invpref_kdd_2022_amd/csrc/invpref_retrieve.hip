@@ -15,7 +15,14 @@
 // The range's top k (padded with empty entries) goes to the workspace.
 // Phase 2 (retrieve_merge_kernel): one wave per user merges the ranges' lists with the full (key, id) comparison and looks the
 // winners up in the sorted ground truth.
+//
+// The scaled form (include/invpref_retrieve_scaled.h; retrieve_scaled_scan_kernel, the second form of retrieve_scan_body.hpp):
+// between the sigmoid and the mask each score becomes ((p - shift) * user_scale[users[row]]) * item_scale[item] --
+// macr_epilogue_kernel's three fp32 operations, in its order, so the scores are that kernel's bit for bit.
+// retrieve_scan_kernel is the text without it: the code it was, under the signature it had.
 #include "launch.hpp"
+
+#include "../../include/invpref_retrieve_scaled.h"
 
 using namespace invpref;
 
@@ -69,180 +76,17 @@ __device__ __forceinline__ int lower_bound(const int *__restrict__ a, int lo, in
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-// VEC: factor_num % 4 == 0 and 16-byte aligned tables (float4 staging); otherwise one float at a time (D = 30: 120-byte rows).
-template <int DC, bool VEC>
-__global__ __launch_bounds__(256, 2) void retrieve_scan_kernel(const float *__restrict__ Pu, const float *__restrict__ Qi,
-                                                               const int64_t *__restrict__ users, int64_t n, int I, int D,
-                                                               int apply_sigmoid, const int *__restrict__ mask_ptr,
-                                                               const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
-                                                               const int *__restrict__ hl_items, int K, int steps_per,
-                                                               unsigned *__restrict__ ws_keys, int *__restrict__ ws_ids) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int DP = 64 * DC, RS = DP + 4, TILE = 16 * RS;
-    unsigned *ckeys = reinterpret_cast<unsigned *>(lds + 2 * TILE);   // [64 users][kCand]
-    int *cids = reinterpret_cast<int *>(ckeys + 64 * kCand);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int m = lane & 15, k = lane >> 4;
-    const int ranges = (int)gridDim.y;
-    // ---- A operands: a[c][s] = Pu[user m][64 c + 4 s + k], zero beyond D (loads from a clamped address, then a select)
-    const int64_t urow = (int64_t)blockIdx.x * 64 + wave * 16 + m;
-    const int64_t uid = users[urow < n ? urow : n - 1];
-    const float *pu = Pu + uid * (int64_t)D;
-    float a[DC][16];
-#pragma unroll
-    for (int c = 0; c < DC; c++)
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-            const int e = 64 * c + 4 * s + k;
-            const float v = pu[e < D ? e : D - 1];
-            a[c][s] = e < D ? v : 0.f;
-        }
-    const int tiles = (I + 15) / 16;
-    const int t0 = (int)blockIdx.y * steps_per, t1 = min(tiles, t0 + steps_per);
-    // ---- per-user state: lane (k, m) serves users 4 k + r of the wave (r = 0..3), the same for its 16 lanes
-    int mcur[4], mend[4], mnext[4], hcur[4], hend[4], hnext[4], cnt[4];
-    unsigned tau[4];   // survivors need key >= tau
-    bool valid[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int64_t row = (int64_t)blockIdx.x * 64 + wave * 16 + 4 * k + r;
-        valid[r] = row < n;
-        const int64_t rr = valid[r] ? row : 0;
-        mcur[r] = mend[r] = hcur[r] = hend[r] = 0;
-        if (mask_ptr && valid[r]) { mend[r] = mask_ptr[rr + 1]; mcur[r] = lower_bound(mask_items, mask_ptr[rr], mend[r], t0 * 16); }
-        if (hl_ptr && valid[r]) { hend[r] = hl_ptr[rr + 1]; hcur[r] = lower_bound(hl_items, hl_ptr[rr], hend[r], t0 * 16); }
-        mnext[r] = mcur[r] < mend[r] ? mask_items[mcur[r]] : INT32_MAX;
-        hnext[r] = hcur[r] < hend[r] ? hl_items[hcur[r]] : INT32_MAX;
-        cnt[r] = 0;
-        tau[r] = 0u;
-    }
-    // ---- staging: a tile is 16 rows x DP floats; thread th moves element (or float4) th + 256 j of it
-    constexpr int EPR = VEC ? DP / 4 : DP;           // elements (floats or float4) per padded row
-    constexpr int PER = 16 * EPR / 256;              // per thread and tile
-    int rr_[PER], col[PER], dst[PER];
-#pragma unroll
-    for (int j = 0; j < PER; j++) {
-        const int f = threadIdx.x + 256 * j;
-        rr_[j] = f / EPR;
-        col[j] = (VEC ? 4 : 1) * (f - rr_[j] * EPR);
-        dst[j] = rr_[j] * RS + col[j];
-    }
-    // every load and LDS store of the loop is unconditional (as in predict_mm_kernel): the tile after the last is the last
-    // one again, a column beyond D loads the row's last element (or float4) and stores zeros
-    auto load = [&](int t, float4 (&st)[PER]) {
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            const float *src = Qi + (int64_t)min(t * 16 + rr_[j], I - 1) * D;
-            if (VEC) {
-                const float4 v = *reinterpret_cast<const float4 *>(src + min(col[j], D - 4));
-                st[j] = col[j] < D ? v : f4zero();
-            } else {
-                const float v = src[min(col[j], D - 1)];
-                st[j].x = col[j] < D ? v : 0.f;
-            }
-        }
-    };
-    auto store = [&](int buf, const float4 (&st)[PER]) {
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            if (VEC) *reinterpret_cast<float4 *>(lds + buf * TILE + dst[j]) = st[j];
-            else lds[buf * TILE + dst[j]] = st[j].x;
-        }
-    };
-    float4 st[PER];
-    load(min(t0, tiles - 1), st);
-    store(0, st);
-    __syncthreads();
-    for (int t = t0; t < t1; t++) {
-        const int buf = (t - t0) & 1;
-        load(min(t + 1, t1 - 1), st);
-        const float *bt = lds + buf * TILE + m * RS + k;
-        f32x4_t acc[16];
-#pragma unroll
-        for (int s = 0; s < 16; s++) acc[s] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < DC; c++)
-#pragma unroll
-            for (int s = 0; s < 16; s++)
-                acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][s], bt[64 * c + 4 * s], acc[s], 0, 0, 0);
-#pragma unroll
-        for (int s = 0; s < 16; s += 2) acc[s] = acc[s] + acc[s + 1];
-#pragma unroll
-        for (int s = 0; s < 16; s += 4) acc[s] = acc[s] + acc[s + 2];
-#pragma unroll
-        for (int s = 0; s < 16; s += 8) acc[s] = acc[s] + acc[s + 4];
-        acc[0] = acc[0] + acc[8];
-        const int base = t * 16, item = base + m;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            float p = acc[0][r];
-            if (apply_sigmoid) p = c_sigmoid(p);
-            // mask / highlight bits of this tile for user 4 k + r (the 16 lanes of the group walk the same cursor)
-            unsigned mb = 0u, hb = 0u;
-            while (mnext[r] < base + 16) {
-                if (mnext[r] >= base) mb |= 1u << (mnext[r] - base);
-                mcur[r]++;
-                mnext[r] = mcur[r] < mend[r] ? mask_items[mcur[r]] : INT32_MAX;
-            }
-            while (hnext[r] < base + 16) {
-                if (hnext[r] >= base) hb |= 1u << (hnext[r] - base);
-                hcur[r]++;
-                hnext[r] = hcur[r] < hend[r] ? hl_items[hcur[r]] : INT32_MAX;
-            }
-            float v = ((mb >> m) & 1u) ? -1024.0f : p;
-            if ((hb >> m) & 1u) v += 1024.0f;
-            const unsigned key = order_key(v);
-            const bool surv = valid[r] && item < I && key >= tau[r];
-            const uint64_t bal = __ballot(surv);
-            const unsigned gm = (unsigned)(bal >> (16 * k)) & 0xffffu;
-            const int uloc = wave * 16 + 4 * k + r;
-            if (surv) {
-                const int pos = cnt[r] + __builtin_popcount(gm & ((1u << m) - 1u));
-                ckeys[uloc * kCand + pos] = key;
-                cids[uloc * kCand + pos] = item;
-            }
-            cnt[r] += __builtin_popcount(gm);
-        }
-        // lists that may not take another tile: compacted by the whole wave, one user at a time
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            uint64_t need = __ballot(cnt[r] > kCand - 16);
-            while (need) {
-                const int g = __builtin_ctzll(need) >> 4;        // (wave-uniform)
-                const int uloc = wave * 16 + 4 * g + r;
-                const int c = __builtin_amdgcn_readlane(cnt[r], 16 * g);
-                WAVE_LDS_FENCE();
-                __builtin_amdgcn_wave_barrier();
-                wave_compact(ckeys + uloc * kCand, cids + uloc * kCand, c, K, lane);
-                const unsigned nt = ckeys[uloc * kCand + K - 1] + 1u;   // (c > 64 >= k; the largest key, +inf's, is < ~0u)
-                if (k == g) { cnt[r] = K; tau[r] = nt; }
-                need &= ~(0xffffull << (16 * g));
-            }
-        }
-        store(buf ^ 1, st);
-        __syncthreads();
-    }
-    // ---- the range's top k of each of the wave's 16 users to the workspace, in any order (empty entries beyond the list; a
-    // list of at most k entries goes as it is)
-    for (int u = 0; u < 16; u++) {
-        const int r = u & 3, g = u >> 2;
-        int c = cnt[0];
-#pragma unroll
-        for (int q = 1; q < 4; q++) c = (r == q) ? cnt[q] : c;
-        c = __builtin_amdgcn_readlane(c, 16 * g);
-        const int uloc = wave * 16 + u;
-        WAVE_LDS_FENCE();
-        __builtin_amdgcn_wave_barrier();
-        if (c > K) wave_compact(ckeys + uloc * kCand, cids + uloc * kCand, c, K, lane);   // (wave-uniform)
-        const int64_t row = (int64_t)blockIdx.x * 64 + uloc;
-        if (row < n && lane < K) {
-            const int64_t o = (row * ranges + blockIdx.y) * K + lane;
-            const bool have = lane < c;
-            ws_keys[o] = have ? ckeys[uloc * kCand + lane] : 0u;
-            ws_ids[o] = have ? cids[uloc * kCand + lane] : kEmptyId;
-        }
-    }
-}
+// the scan kernel, in its two forms (retrieve_scan_body.hpp)
+#define RETRIEVE_SCAN_NAME retrieve_scan_kernel
+#define RETRIEVE_SCAN_SCALED 0
+#include "retrieve_scan_body.hpp"
+#undef RETRIEVE_SCAN_NAME
+#undef RETRIEVE_SCAN_SCALED
+#define RETRIEVE_SCAN_NAME retrieve_scaled_scan_kernel
+#define RETRIEVE_SCAN_SCALED 1
+#include "retrieve_scan_body.hpp"
+#undef RETRIEVE_SCAN_NAME
+#undef RETRIEVE_SCAN_SCALED
 
 // One wave per user: the ranges' lists (ranges * K entries, in any order) merged with the full (key desc, id asc) comparison,
 // then the winners' values, items and hit labels.
@@ -326,6 +170,57 @@ size_t bytes_for(int64_t n_users, int64_t item_num, int64_t k) {
     return (size_t)n_users * (size_t)geometry(n_users, item_num).ranges * (size_t)k * 8u;
 }
 
+// both entry points: every check before any launch; `scaled` picks the scan's epilogue instances
+int predict_topk(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users, int64_t item_num,
+                 int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr, const int32_t *mask_items,
+                 const int32_t *highlight_ptr, const int32_t *highlight_items, const int32_t *truth_ptr,
+                 const int32_t *truth_items, int32_t k, int32_t *out_items, float *out_scores, float *out_hits, void *workspace,
+                 size_t workspace_bytes, void *stream, bool scaled, const float *user_scale, const float *item_scale,
+                 double shift) {
+    if (!user_table || !item_table || n_users < 0 || item_num <= 0 || factor_num <= 0 || k <= 0)
+        return INVPREF_EINVAL;
+    if (scaled && (!user_scale || !item_scale)) return INVPREF_EINVAL;
+    if ((mask_ptr && !mask_items) || (highlight_ptr && !highlight_items) || (truth_ptr && !truth_items)) return INVPREF_EINVAL;
+    if (k > kMaxK || k > item_num || factor_num > INVPREF_MAX_FACTORS || item_num > INT32_MAX - 16) return INVPREF_EUNSUPPORTED;
+    if (n_users == 0) return 0;
+    if (!users || !out_items) return INVPREF_EINVAL;
+    if (!workspace || workspace_bytes < bytes_for(n_users, item_num, k)) return INVPREF_EWORKSPACE;
+    const Geometry g = geometry(n_users, item_num);
+    const int64_t slots = n_users * (int64_t)g.ranges * k;
+    unsigned *wk = reinterpret_cast<unsigned *>(workspace);
+    int *wi = reinterpret_cast<int *>(wk + slots);
+    hipStream_t st = (hipStream_t)stream;
+    const int I = (int)item_num, D = (int)factor_num;
+    const int rc = with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
+        return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
+            return with_bool(scaled, [&](auto scaled_c) {
+                constexpr int DC = decltype(dc_c)::value;
+                constexpr bool VEC = decltype(vec_c)::value;
+                constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4) + (size_t)64 * kCand * 8;
+                const dim3 grid((unsigned)g.ux, (unsigned)g.ranges);
+                if constexpr (decltype(scaled_c)::value) {
+                    const auto scan = retrieve_scaled_scan_kernel<DC, VEC>;
+                    if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
+                    hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D,
+                                       apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k, g.steps_per,
+                                       wk, wi, user_scale, item_scale, (float)shift);
+                } else {
+                    const auto scan = retrieve_scan_kernel<DC, VEC>;
+                    if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
+                    hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D,
+                                       apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k, g.steps_per,
+                                       wk, wi);
+                }
+                return (int)hipGetLastError();
+            });
+        });
+    });
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(retrieve_merge_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, n_users, g.ranges, (int)k,
+                       wk, wi, truth_ptr, truth_items, out_items, out_scores, out_hits);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -345,34 +240,20 @@ int invpref_predict_topk_hip(const float *user_table, const float *item_table, c
                              const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
                              const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
                              float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!user_table || !item_table || n_users < 0 || item_num <= 0 || factor_num <= 0 || k <= 0)
-        return INVPREF_EINVAL;
-    if ((mask_ptr && !mask_items) || (highlight_ptr && !highlight_items) || (truth_ptr && !truth_items)) return INVPREF_EINVAL;
-    if (k > kMaxK || k > item_num || factor_num > INVPREF_MAX_FACTORS || item_num > INT32_MAX - 16) return INVPREF_EUNSUPPORTED;
-    if (n_users == 0) return 0;
-    if (!users || !out_items) return INVPREF_EINVAL;
-    if (!workspace || workspace_bytes < bytes_for(n_users, item_num, k)) return INVPREF_EWORKSPACE;
-    const Geometry g = geometry(n_users, item_num);
-    const int64_t slots = n_users * (int64_t)g.ranges * k;
-    unsigned *wk = reinterpret_cast<unsigned *>(workspace);
-    int *wi = reinterpret_cast<int *>(wk + slots);
-    hipStream_t st = (hipStream_t)stream;
-    const int I = (int)item_num, D = (int)factor_num;
-    const int rc = with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
-        return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
-            constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * decltype(dc_c)::value + 4) + (size_t)64 * kCand * 8;
-            const auto scan = retrieve_scan_kernel<decltype(dc_c)::value, decltype(vec_c)::value>;
-            if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
-            hipLaunchKernelGGL(scan, dim3((unsigned)g.ux, (unsigned)g.ranges), dim3(256), lds, st, user_table, item_table, users,
-                               n_users, I, D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k,
-                               g.steps_per, wk, wi);
-            return (int)hipGetLastError();
-        });
-    });
-    if (rc != 0) return rc;
-    hipLaunchKernelGGL(retrieve_merge_kernel, dim3((unsigned)((n_users + 3) / 4)), dim3(256), 0, st, n_users, g.ranges, (int)k,
-                       wk, wi, truth_ptr, truth_items, out_items, out_scores, out_hits);
-    return (int)hipGetLastError();
+    return predict_topk(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                        highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits, workspace,
+                        workspace_bytes, stream, false, nullptr, nullptr, 0.0);
+}
+
+int invpref_predict_topk_scaled_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
+                                    int64_t item_num, int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr,
+                                    const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
+                                    const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
+                                    float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream,
+                                    const float *user_scale, const float *item_scale, double shift) {
+    return predict_topk(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                        highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits, workspace,
+                        workspace_bytes, stream, true, user_scale, item_scale, shift);
 }
 
 }  // extern "C"

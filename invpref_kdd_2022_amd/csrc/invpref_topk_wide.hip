@@ -15,9 +15,15 @@
 // invpref_predict_topk_wide_hip: the users in chunks of about kChunkBytes of scores: invpref_predict_hip (the canonical dot
 // product the fused scan also computes, so the values agree bit for bit) into the workspace, then topk_wide_kernel on it.
 //
+// invpref_predict_topk_scaled_wide_hip (include/invpref_retrieve_scaled.h): the same loop with invpref::scale_rows
+// (invpref_macr.hip: macr_epilogue_kernel, ((s - shift) * user_scale[user]) * item_scale[item]) over each chunk of scores
+// before the select.
+//
 // user_values_wide_kernel: stage 1 of invpref_rank_metrics_hip for K <= 1024: the per-user dcg row sum follows numpy's
 // pairwise recursion above 128 elements; stages 2 and 3 are invpref_metrics.hip's (invpref::rank_metrics_reduce).
 #include "launch.hpp"
+
+#include "../../include/invpref_retrieve_scaled.h"
 
 using namespace invpref;
 
@@ -26,6 +32,9 @@ namespace invpref {
 int rank_metrics_reduce(const double *vals, int64_t n_users, int n_k, int64_t partition, double *csum, double *out,
                         hipStream_t st);
 size_t rank_metrics_bytes(int64_t n_users, int n_k, int64_t partition);
+// invpref_macr.hip: scores[r][j] = ((scores[r][j] - shift) * user_scale[users[r]]) * item_scale[j] over [n, I] scores
+int scale_rows(float *scores, const int64_t *users, int64_t n, int64_t I, const float *user_scale, const float *item_scale,
+               float shift, hipStream_t st);
 }  // namespace invpref
 
 namespace {
@@ -280,6 +289,42 @@ size_t scores_bytes(int64_t rows, int64_t I) { return ((size_t)rows * (size_t)I 
 
 bool half_pair(const void *p, const void *items) { return (p != nullptr) != (items != nullptr); }
 
+// both chunked entry points: every check before any launch; `scaled` adds the scale pass between the predict and the select
+int predict_topk_wide(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users, int64_t item_num,
+                      int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr, const int32_t *mask_items,
+                      const int32_t *highlight_ptr, const int32_t *highlight_items, const int32_t *truth_ptr,
+                      const int32_t *truth_items, int32_t k, int32_t *out_items, float *out_scores, float *out_hits,
+                      void *workspace, size_t workspace_bytes, void *stream, bool scaled, const float *user_scale,
+                      const float *item_scale, double shift) {
+    if (!user_table || !item_table || n_users < 0 || item_num <= 0 || factor_num <= 0 || k <= 0) return INVPREF_EINVAL;
+    if (scaled && (!user_scale || !item_scale)) return INVPREF_EINVAL;
+    if (half_pair(mask_ptr, mask_items) || half_pair(highlight_ptr, highlight_items) || half_pair(truth_ptr, truth_items))
+        return INVPREF_EINVAL;
+    if (k > kMaxK || k > item_num || factor_num > INVPREF_MAX_FACTORS || item_num > INT32_MAX - 16) return INVPREF_EUNSUPPORTED;
+    if (n_users == 0) return 0;
+    if (!users || !out_items) return INVPREF_EINVAL;
+    const int64_t R = chunk_rows(n_users, item_num);
+    const size_t sb = scores_bytes(R, item_num);
+    if (!workspace || workspace_bytes < sb + rows_bytes(R, item_num)) return INVPREF_EWORKSPACE;
+    float *scores = reinterpret_cast<float *>(workspace);
+    void *bits = reinterpret_cast<char *>(workspace) + sb;
+    hipStream_t st = (hipStream_t)stream;
+    auto at = [](const int32_t *p, int64_t o) { return p ? p + o : nullptr; };
+    for (int64_t lo = 0; lo < n_users; lo += R) {
+        const int64_t m = std::min(R, n_users - lo);
+        int rc = invpref_predict_hip(user_table, item_table, users + lo, m, item_num, factor_num, apply_sigmoid, scores, stream);
+        if (rc != 0) return rc;
+        if (scaled) {
+            if ((rc = scale_rows(scores, users + lo, m, item_num, user_scale, item_scale, (float)shift, st)) != 0) return rc;
+        }
+        rc = launch_rows(scores, m, item_num, item_num, at(mask_ptr, lo), mask_items, at(highlight_ptr, lo), highlight_items,
+                         at(truth_ptr, lo), truth_items, k, out_items + lo * k, out_scores ? out_scores + lo * k : nullptr,
+                         out_hits ? out_hits + lo * k : nullptr, bits, st);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -316,29 +361,21 @@ int invpref_predict_topk_wide_hip(const float *user_table, const float *item_tab
                                   const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
                                   const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
                                   float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!user_table || !item_table || n_users < 0 || item_num <= 0 || factor_num <= 0 || k <= 0) return INVPREF_EINVAL;
-    if (half_pair(mask_ptr, mask_items) || half_pair(highlight_ptr, highlight_items) || half_pair(truth_ptr, truth_items))
-        return INVPREF_EINVAL;
-    if (k > kMaxK || k > item_num || factor_num > INVPREF_MAX_FACTORS || item_num > INT32_MAX - 16) return INVPREF_EUNSUPPORTED;
-    if (n_users == 0) return 0;
-    if (!users || !out_items) return INVPREF_EINVAL;
-    const int64_t R = chunk_rows(n_users, item_num);
-    const size_t sb = scores_bytes(R, item_num);
-    if (!workspace || workspace_bytes < sb + rows_bytes(R, item_num)) return INVPREF_EWORKSPACE;
-    float *scores = reinterpret_cast<float *>(workspace);
-    void *bits = reinterpret_cast<char *>(workspace) + sb;
-    hipStream_t st = (hipStream_t)stream;
-    auto at = [](const int32_t *p, int64_t o) { return p ? p + o : nullptr; };
-    for (int64_t lo = 0; lo < n_users; lo += R) {
-        const int64_t m = std::min(R, n_users - lo);
-        int rc = invpref_predict_hip(user_table, item_table, users + lo, m, item_num, factor_num, apply_sigmoid, scores, stream);
-        if (rc != 0) return rc;
-        rc = launch_rows(scores, m, item_num, item_num, at(mask_ptr, lo), mask_items, at(highlight_ptr, lo), highlight_items,
-                         at(truth_ptr, lo), truth_items, k, out_items + lo * k, out_scores ? out_scores + lo * k : nullptr,
-                         out_hits ? out_hits + lo * k : nullptr, bits, st);
-        if (rc != 0) return rc;
-    }
-    return 0;
+    return predict_topk_wide(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                             highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits,
+                             workspace, workspace_bytes, stream, false, nullptr, nullptr, 0.0);
+}
+
+int invpref_predict_topk_scaled_wide_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
+                                         int64_t item_num, int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr,
+                                         const int32_t *mask_items, const int32_t *highlight_ptr,
+                                         const int32_t *highlight_items, const int32_t *truth_ptr, const int32_t *truth_items,
+                                         int32_t k, int32_t *out_items, float *out_scores, float *out_hits, void *workspace,
+                                         size_t workspace_bytes, void *stream, const float *user_scale, const float *item_scale,
+                                         double shift) {
+    return predict_topk_wide(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                             highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits,
+                             workspace, workspace_bytes, stream, true, user_scale, item_scale, shift);
 }
 
 int invpref_rank_metrics_wide_hip(const float *hits, int64_t n_users, int64_t ld, int32_t K, const int32_t *truth_ptr,

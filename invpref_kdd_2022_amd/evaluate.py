@@ -5,7 +5,8 @@ user (mask / highlight index lists, ``x in groundTrue``) and builds a ``[n*I, D]
 ``model.predict``; here the per-user sets are turned into CSR arrays ONCE.  For the models whose scores are
 sigmoid(user table . item table) (``InvPrefImplicit``, ``PureMatrixFactorization``) the test users are ranked by the fused
 ``predict_topk`` operator (``csrc/invpref_retrieve.hip``: scores, mask, highlight, top-k and hit labels without a score
-matrix); any other model's batch is ``model.predict`` (rating matrix) + ``topk_mask_kernel`` / ``topk_select_kernel``.
+matrix), and ``MACRMatrixFactorization`` by the same scan with its counterfactual epilogue (``predict_topk_scaled``); any
+other model's batch is ``model.predict`` (rating matrix) + ``topk_mask_kernel`` / ``topk_select_kernel``.
 Beyond k = 64 (or 400 000 items on the rating-matrix path) both routes rank with the radix select of
 ``csrc/invpref_topk_wide.hip``, for any ``top_k_list`` up to k = 1024.
 The hit labels stay on the device: the recall / precision / NDCG sums (evaluate.py:22-56) come from the ``rank_metrics``
@@ -117,11 +118,27 @@ class ImplicitTestManager:
             return t[0].detach().contiguous(), t[1].detach().contiguous()
         return None
 
+    def _fused_rank(self):
+        """The fused route of the model: a callable f(users, k, mask, highlight, truth) -> (items, scores, hits) that ranks
+        without a score matrix, else None (topk() batch by batch).  predict_topk on _fused_tables() for the models that rank
+        by sigmoid(user . item); a model with scores of its own offers rank_fn() (MACRMatrixFactorization: its two branch
+        launches, then the scaled scan)."""
+        from .ops import predict_topk
+        tables = self._fused_tables()
+        if tables is not None:
+            return lambda users, k, mask, highlight, truth: predict_topk(tables[0], tables[1], users, k, True, mask=mask,
+                                                                         highlight=highlight, truth=truth)
+        fn = getattr(self.model, 'rank_fn', None)
+        return fn() if fn is not None else None
+
     def _fused_hits_device(self, tables) -> torch.Tensor:
         """hits fp32[n_test_users, k] on the device, ranked by predict_topk in batches bounded by its workspace
         (O(batch * k), about 256 MiB at most; beyond k = 64 a 256 MiB score chunk plus the batch's [n, k] outputs) -- the
-        same labels topk() gives batch by batch."""
+        same labels topk() gives batch by batch.  tables: _fused_tables()'s pair, or _fused_rank()'s callable."""
         from .ops import predict_topk
+        rank = tables if callable(tables) else (
+            lambda users, k, mask, highlight, truth: predict_topk(tables[0], tables[1], users, k, True, mask=mask,
+                                                                  highlight=highlight, truth=truth))
         d = self._dev
         n_users, k = self._users.shape[0], max(self.top_k_list)
         step = max(1, (1 << 28) // (8 * k))
@@ -129,9 +146,8 @@ class ImplicitTestManager:
         for lo in range(0, n_users, step):
             hi = min(lo + step, n_users)
             hl = (d['hl_ptr'][lo:hi + 1], d['hl_items']) if self.use_item_pool else None
-            _, _, hits = predict_topk(tables[0], tables[1], self._users[lo:hi], k, True,
-                                      mask=(d['mask_ptr'][lo:hi + 1], d['mask_items']), highlight=hl,
-                                      truth=(d['truth_ptr'][lo:hi + 1], d['truth_items']))
+            _, _, hits = rank(self._users[lo:hi], k, (d['mask_ptr'][lo:hi + 1], d['mask_items']), hl,
+                              (d['truth_ptr'][lo:hi + 1], d['truth_items']))
             out.append(hits)
         if not out:
             return torch.empty(0, k, dtype=torch.float32, device=self._users.device)
@@ -165,9 +181,9 @@ class ImplicitTestManager:
         # batches are merged up to a 1 GiB score matrix (MIND's 256-user batches: 196 launches -> 10).  The fused path ranks in
         # its own batches; the float64 metric sums keep this partition either way, so the result is the same, float for float
         step = self._step(n_users, k)
-        tables = self._fused_tables()
-        if tables is not None:
-            hits = self._fused_hits_device(tables)
+        rank = self._fused_rank()
+        if rank is not None:
+            hits = self._fused_hits_device(rank)
         else:
             parts = [self.topk(lo, min(lo + step, n_users))[1] for lo in range(0, n_users, step)]
             hits = (parts[0] if len(parts) == 1 else torch.cat(parts)) if parts else \

@@ -16,6 +16,7 @@ from . import _capi
 from . import torch_ops  # noqa: F401  (registers torch.ops.invpref.*)
 from . import torch_ops_macr  # noqa: F401  (the MACR fragment: torch.ops.invpref.macr_*)
 from . import torch_ops_cause  # noqa: F401  (the CausE fragment: torch.ops.invpref.cause_grad_)
+from . import torch_ops_scaled  # noqa: F401  (the scaled retrieval's fragment: torch.ops.invpref.predict_topk_scaled*)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -238,6 +239,22 @@ def predict_topk(user_table: torch.Tensor, item_table: torch.Tensor, users: torc
     return op(user_table, item_table, users, k, bool(sigmoid), mp, mi, hp, hi, tp, ti)
 
 
+def predict_topk_scaled(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, k: int,
+                        user_scale: torch.Tensor, item_scale: torch.Tensor, shift: float, sigmoid: bool = True, mask=None,
+                        highlight=None, truth=None):
+    """predict_topk on the scores ((s - shift) * user_scale[users]) * item_scale, s = sigmoid(user . item) (the plain dot
+    product if not sigmoid): three fp32 operations in this order, then mask, highlight, top-k and hit labels as in
+    predict_topk -- no [n, item_num] matrix.  user_scale fp32 [user_num], indexed by user id; item_scale fp32 [item_num].  With
+    the two MACR branches and shift = const_c these are ops.macr_predict's scores bit for bit; scores may be negative, and a
+    user whose scale is 0 gets the lowest item ids.  -> (items int32[n, k], scores fp32[n, k], hits fp32[n, k]).
+    k <= 64 runs the fused scan (predict_topk_scaled); 64 < k <= 1024 the chunked form (predict_topk_scaled_wide)."""
+    _gpu(user_table, item_table, users, user_scale, item_scale)
+    k = _check_topk(k)
+    (mp, mi), (hp, hi), (tp, ti) = [(None, None) if c is None else c for c in (mask, highlight, truth)]
+    op = _o().predict_topk_scaled if k <= _capi.MAX_TOPK else _o().predict_topk_scaled_wide
+    return op(user_table, item_table, users, k, bool(sigmoid), mp, mi, hp, hi, tp, ti, user_scale, item_scale, float(shift))
+
+
 def _check_topk(k) -> int:
     k = int(k)
     if k > _capi.MAX_TOPK_WIDE:
@@ -327,14 +344,21 @@ def device_csr(csr, n_rows: int, n_items: int, device):
 
 
 def recommend(user_table: torch.Tensor, item_table: torch.Tensor, users_id: torch.Tensor, k: int, exclude=None,
-              highlight=None, sigmoid: bool = True):
+              highlight=None, sigmoid: bool = True, *, user_scale=None, item_scale=None, shift: float = 0.0):
     """The top-k items of every user in users_id by sigmoid(user . item): `exclude` items score -1024, `highlight` items
-    += 1024 (evaluate.py:94-111), both CSR pairs aligned with users_id.  -> (items int64[n, k], scores fp32[n, k])."""
+    += 1024 (evaluate.py:94-111), both CSR pairs aligned with users_id.  -> (items int64[n, k], scores fp32[n, k]).
+    With user_scale (fp32 [user_num], by user id), item_scale (fp32 [item_num]) or a non-zero shift the ranking score is
+    ((sigmoid(user . item) - shift) * user_scale[user]) * item_scale[item] (predict_topk_scaled; an absent scale is ones)."""
     users = users_id.reshape(-1).to(torch.int64).contiguous()
     n, I = users.numel(), item_table.shape[0]
     ut, it = user_table.detach().contiguous(), item_table.detach().contiguous()
-    items, scores, _ = predict_topk(ut, it, users, k, sigmoid, mask=device_csr(exclude, n, I, users.device),
-                                    highlight=device_csr(highlight, n, I, users.device))
+    mask, hl = device_csr(exclude, n, I, users.device), device_csr(highlight, n, I, users.device)
+    if user_scale is None and item_scale is None and float(shift) == 0.0:
+        items, scores, _ = predict_topk(ut, it, users, k, sigmoid, mask=mask, highlight=hl)
+    else:
+        us, cs = (torch.ones(t.shape[0], dtype=torch.float32, device=t.device) if s is None else
+                  s.detach().reshape(-1).to(torch.float32).contiguous() for s, t in ((user_scale, ut), (item_scale, it)))
+        items, scores, _ = predict_topk_scaled(ut, it, users, k, us, cs, shift, sigmoid, mask=mask, highlight=hl)
     return items.to(torch.int64), scores
 
 
