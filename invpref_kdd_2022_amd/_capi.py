@@ -96,20 +96,19 @@ PROPENSITY_ITEM, PROPENSITY_USER, PROPENSITY_PAIR = (DEFINES['PROPENSITY_' + n] 
 MAX_LABELS = DEFINES['MAX_LABELS']         # distinct training labels of the naive-Bayes propensities
 FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries the fairness product keeps in LDS
 
-# the MACR baseline's entry points (include/invpref_macr.h, csrc/invpref_macr.hip): the same library, a header and a table of
-# their own -- SIGNATURES / EXPORTS above are include/invpref_hip.h's alone
+# Entry points beyond include/invpref_hip.h: the same library, a header and a table of their own each -- SIGNATURES / EXPORTS
+# above are include/invpref_hip.h's alone.  The MACR baseline (csrc/invpref_macr.hip), the CausE baselines
+# (csrc/invpref_cause.hip) and the scaled retrieval (csrc/invpref_retrieve.hip, csrc/invpref_topk_wide.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
-MACR_SIGNATURES, MACR_DEFINES = _read_header(MACR_HEADER_PATH)
-
-# the CausE baselines' entry points (include/invpref_cause.h, csrc/invpref_cause.hip): likewise a header and a table of their own
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
-CAUSE_SIGNATURES, CAUSE_DEFINES = _read_header(CAUSE_HEADER_PATH)
-CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
-
-# the scaled retrieval's entry points (include/invpref_retrieve_scaled.h; csrc/invpref_retrieve.hip, invpref_topk_wide.hip):
-# likewise a header and a table of their own
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
+MACR_SIGNATURES, MACR_DEFINES = _read_header(MACR_HEADER_PATH)
+CAUSE_SIGNATURES, CAUSE_DEFINES = _read_header(CAUSE_HEADER_PATH)
 SCALED_SIGNATURES, SCALED_DEFINES = _read_header(SCALED_HEADER_PATH)
+CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
+# (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
+EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
+                 (SCALED_HEADER_PATH, 'SCALED_SIGNATURES', 'SCALED_DEFINES'))
 
 _lib = None
 
@@ -123,26 +122,12 @@ def lib():
                 f'{LIB_PATH} is missing: build it with `python -m invpref_kdd_2022_amd.build` '
                 '(or __graft_entry__.build()); the InvPref hot path has no fallback implementation')
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_hip.h declares')
-            fn.restype, fn.argtypes = restype, argtypes
-        for name, (restype, argtypes) in MACR_SIGNATURES.items():
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_macr.h declares')
-            fn.restype, fn.argtypes = restype, argtypes
-        for name, (restype, argtypes) in CAUSE_SIGNATURES.items():
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_cause.h declares')
-            fn.restype, fn.argtypes = restype, argtypes
-        for name, (restype, argtypes) in SCALED_SIGNATURES.items():
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/invpref_retrieve_scaled.h declares')
-            fn.restype, fn.argtypes = restype, argtypes
+        for path, signatures, _ in ((HEADER_PATH, 'SIGNATURES', 'DEFINES'),) + EXTRA_HEADERS:
+            for name, (restype, argtypes) in globals()[signatures].items():
+                fn = getattr(L, name, None)
+                if fn is None:
+                    raise InvPrefError(f'{LIB_PATH} does not export {name}, which include/{os.path.basename(path)} declares')
+                fn.restype, fn.argtypes = restype, argtypes
         if L.invpref_abi_version() != ABI_VERSION:
             raise InvPrefError('libinvpref_hip.so ABI version mismatch')
         _lib = L

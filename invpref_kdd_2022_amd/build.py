@@ -17,7 +17,7 @@ SOURCES = ['invpref_kernels.hip', 'invpref_step.hip', 'invpref_eval.hip', 'invpr
            'invpref_topk_wide.hip', 'invpref_propensity.hip',
            'invpref_exposure.hip', 'invpref_impute.hip', 'invpref_cvib.hip', 'invpref_fairness.hip', 'invpref_macr.hip',
            'invpref_cause.hip']
-HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp',
+HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp', 'row_pass.hpp',
            os.path.join('..', '..', 'include', 'invpref_hip.h'),
            os.path.join('..', '..', 'include', 'invpref_macr.h'), os.path.join('..', '..', 'include', 'invpref_cause.h'),
            os.path.join('..', '..', 'include', 'invpref_retrieve_scaled.h')]

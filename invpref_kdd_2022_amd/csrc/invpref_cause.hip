@@ -1,30 +1,21 @@
 // invpref_cause.hip -- the CausE baselines (baseline_models.py:555-649, :706-794 under baseline_train.py:650-797;
-// include/invpref_cause.h) on the device: the gradient pass of one optimiser step over the student tables P, Q (the minibatch)
-// and the teacher tables Tu, Ti (the uniform set, the same whole set at every step).
+// include/invpref_cause.h) on the device: the gradient pass of one optimiser step, on the pairs / rows / fold recipe of
+// row_pass.hpp, over the student tables P, Q (the minibatch) and the teacher tables Tu, Ti (the uniform set, the same whole set
+// at every step).
 //
-//   pairs   one 16-lane group per position of the B + Nu positions: minibatch positions gather P[u] and Q[i], uniform positions
-//           Tu[uu] and Ti[ui] (lane l owns the float4 chunks l, l + 16, ...: kernel_common.hpp), form x = row . row in
-//           float64, the prediction, the loss partial (float64 per workgroup) and the record of the position -- ONE float,
-//           d loss / d x with 1 / B or uniform_loss_coe / Nu folded in
-//   rows    one 16-lane group per row of each of the four tables: walks the row's positions in ascending order (its set's
-//           inverted index), gathers the partner rows, accumulates dx . partner in that order, adds the closed-form L2 and
-//           teacher terms from the index counts and stores the row -- ONE writer per row, rows without a term store zeros.
-//           The row's share of L2_reg and teacher_reg goes to float64 per-workgroup partials
-//   fold    the partials of both kernels: one fp64 chain per lane over the workgroups in order, then a fixed butterfly
-// No float atomics, every sum in a fixed order: the same bits on every run.  Everything between the fp32 tables and the fp32
-// outputs is float64 -- the dot product (a product of two floats is exact there), the sigmoid, bce and its backward, the sums
-// over positions, rows and workgroups -- and rounded to fp32 once where it is stored.  A loss term of ONE position (B = 1 or
-// Nu = 1) has no mean to average roundings away: with the canonical fp32 row dot and the sigmoid rounded to fp32 it measured
-// 1.37e-7 from float64 against 1.19e-7 allowed (D = 256), and the rounding of the sigmoid alone can cost 2^-24 / loss.  The
-// fp32 sigmoid's saturation is kept, because the reference's gradients depend on it: exactly 1 where the correctly rounded
-// fp32 value is 1 (from about +17.3), exactly 0 where the fp32 exp(-x) overflows.
+//   pairs   the B + Nu positions: minibatch positions gather P[u] and Q[i], uniform positions Tu[uu] and Ti[ui]; x = row . row
+//           in float64, the prediction and the loss partial; the record of a position is ONE float, d loss / d x with 1 / B or
+//           uniform_loss_coe / Nu folded in
+//   rows    each of the four tables: sum dx . partner over the row's positions (its set's inverted index) plus the closed-form
+//           L2 and teacher terms from the index counts.  The row's share of L2_reg and teacher_reg goes to float64
+//           per-workgroup partials
+//   fold    the five loss values
+// Everything between the fp32 tables and the fp32 outputs is float64 -- the dot product (a product of two floats is exact
+// there), the sigmoid (sigmoid_f64), bce and its backward, the sums -- and rounded to fp32 once where it is stored.
 //
 // The implicit model's regulariser indexes the USER tables with ITEM ids (baseline_models.py:608-619): user row r is counted
 // once per position whose user is r and once per position whose item id is r, and the item tables carry no L2 term.
-//
-// A hot row is ONE serial chain of its group in the rows kernel; the next position's partner row is in flight while the current
-// one is accumulated.
-#include "launch.hpp"
+#include "row_pass.hpp"
 
 #include "../../include/invpref_cause.h"
 
@@ -32,11 +23,8 @@ using namespace invpref;
 
 namespace {
 
-constexpr int kGroups = 256 / kRow;   // positions (pairs) or rows (rows) per workgroup
 constexpr int kPairSums = 3;          // minibatch loss sum, uniform loss sum, poisoned positions
 constexpr int kRowSums = 2;           // L2_reg share (weighted), teacher_reg share
-
-__host__ __device__ inline int64_t up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 struct Layout {   // of the workspace, every part 16-byte aligned
     int64_t npb, nbu, nbi;   // workgroups of the pairs kernel, workgroups per user table and per item table of the rows kernel
@@ -47,86 +35,12 @@ inline Layout layout_of(int64_t U, int64_t I, int64_t B, int64_t Nu) {
     l.npb = (B + Nu + kGroups - 1) / kGroups;
     l.nbu = (U + kGroups - 1) / kGroups;
     l.nbi = (I + kGroups - 1) / kGroups;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += (size_t)up((int64_t)bytes, 16);
-        return o;
-    };
-    l.rec = take(sizeof(float) * (B + Nu));
-    l.pair_part = take(sizeof(double) * kPairSums * l.npb);
-    l.row_part = take(sizeof(double) * kRowSums * 2 * (l.nbu + l.nbi));   // [sum][workgroup of the rows kernel]
-    l.bytes = at;
+    Carver ws;
+    l.rec = ws.take(sizeof(float) * (B + Nu));
+    l.pair_part = ws.take(sizeof(double) * kPairSums * l.npb);
+    l.row_part = ws.take(sizeof(double) * kRowSums * 2 * (l.nbu + l.nbi));   // [sum][workgroup of the rows kernel]
+    l.bytes = ws.bytes();
     return l;
-}
-
-// the sigmoid in float64 with the saturation of an fp32 evaluation (csrc/invpref_macr.hip's, which stays as it is): exactly 1
-// where the correctly rounded fp32 value is 1, exactly 0 where the fp32 exp(-x) overflows -- a saturated sigmoid passes no
-// gradient and its bce against the opposite label is the clamp value 100, as in the reference
-__device__ __forceinline__ double cause_sigmoid(double x) {
-    const double r = 1.0 / (1.0 + exp(-x));
-    return x < -88.72283 ? 0.0 : ((float)r == 1.0f ? 1.0 : r);
-}
-// aten's binary_cross_entropy and its backward, evaluated in float64
-__device__ __forceinline__ double bce64(double p, double y) {
-    const double a = fmax(log1p(-p), -100.0), b = fmax(log(p), -100.0);
-    return (y - 1.0) * a - y * b;
-}
-__device__ __forceinline__ double dbce64(double p, double y) { return (p - y) / fmax((1.0 - p) * p, 1e-12); }
-__device__ __forceinline__ double row16_sum64(double x) {
-#pragma unroll
-    for (int m = 1; m < kRow; m <<= 1) x = x + __shfl_xor(x, m, 64);
-    return x;
-}
-struct double4_t {
-    double x, y, z, w;
-};
-// the row dot in float64: each lane's chunks in order, then the 16 lanes by a fixed butterfly
-template <int NC>
-__device__ __forceinline__ double dot64(const float4 (&a)[NC], const float4 (&b)[NC]) {
-    double s = 0.0;
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        s = s + (double)a[c].x * (double)b[c].x;
-        s = s + (double)a[c].y * (double)b[c].y;
-        s = s + (double)a[c].z * (double)b[c].z;
-        s = s + (double)a[c].w * (double)b[c].w;
-    }
-    return row16_sum64(s);
-}
-
-template <int NC>
-__device__ __forceinline__ void zero_row(float4 (&r)[NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) r[c] = f4zero();
-}
-// acc += k * r, element by element, in float64 (the product of two floats is exact there)
-template <int NC>
-__device__ __forceinline__ void axpy_row(double4_t (&acc)[NC], float k, const float4 (&r)[NC]) {
-    const double kd = (double)k;
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        acc[c].x = acc[c].x + kd * (double)r[c].x;
-        acc[c].y = acc[c].y + kd * (double)r[c].y;
-        acc[c].z = acc[c].z + kd * (double)r[c].z;
-        acc[c].w = acc[c].w + kd * (double)r[c].w;
-    }
-}
-template <int NC, bool VEC>
-__device__ __forceinline__ void store_row(float *__restrict__ base, int64_t row, int D, int l16, const float4 (&r)[NC]) {
-    float *p = base + row * (int64_t)D;
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int i0 = (l16 + kRow * c) * 4;
-        if (VEC) {
-            if (i0 < D) *reinterpret_cast<float4 *>(p + i0) = r[c];
-        } else {
-            if (i0 + 0 < D) p[i0 + 0] = r[c].x;
-            if (i0 + 1 < D) p[i0 + 1] = r[c].y;
-            if (i0 + 2 < D) p[i0 + 2] = r[c].z;
-            if (i0 + 3 < D) p[i0 + 3] = r[c].w;
-        }
-    }
 }
 
 // one set of positions with its inverted index: the minibatch on the student tables, the uniform set on the teacher's
@@ -147,7 +61,6 @@ struct PassArgs {
 template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void cause_pair_kernel(PassArgs a, double uniform_loss_coe, float *__restrict__ rec,
                                                          double *__restrict__ partials, int npb) {
-    __shared__ double sums[kGroups][kPairSums];
     const int l16 = threadIdx.x & (kRow - 1), g = threadIdx.x / kRow;
     const int B = a.set[0].n, Nu = a.set[1].n;
     const int p = blockIdx.x * kGroups + g;
@@ -167,7 +80,7 @@ __global__ __launch_bounds__(256) void cause_pair_kernel(PassArgs a, double unif
             const double k = side ? uniform_loss_coe / (double)Nu : 1.0 / (double)B;
             double loss, dx;
             if (a.implicit) {
-                const double sg = cause_sigmoid(x);
+                const double sg = sigmoid_f64(x);
                 loss = bce64(sg, y);
                 dx = (dbce64(sg, y) * k) * ((1.0 - sg) * sg);
             } else {
@@ -183,22 +96,7 @@ __global__ __launch_bounds__(256) void cause_pair_kernel(PassArgs a, double unif
         }
         if (l16 == 0) rec[p] = r;
     }
-    if (l16 == 0) {
-#pragma unroll
-        for (int k = 0; k < kPairSums; k++) sums[g][k] = mine[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kPairSums) {
-        double t = 0.0;
-        for (int q = 0; q < kGroups; q++) t = t + sums[q][threadIdx.x];
-        partials[(int64_t)threadIdx.x * npb + blockIdx.x] = t;
-    }
-}
-
-// the number of entries of list `row` of a CSR whose lists lie inside [0, n)
-__device__ __forceinline__ int list_range(const int32_t *__restrict__ ptr, int row, int n, int &lo) {
-    lo = min(max(ptr[row], 0), n);
-    return min(max(ptr[row + 1], lo), n);
+    group_sums<kPairSums>(mine, partials, npb);
 }
 
 // ---- rows: workgroups [0, nbu) own 16 rows of P each, [nbu, nbu + nbi) of Q, then Tu and Ti likewise
@@ -206,7 +104,6 @@ template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void cause_row_kernel(PassArgs a, const float *__restrict__ rec, double l2_student,
                                                         double l2_teacher, double pull, double *__restrict__ partials, int nbu,
                                                         int nbi) {
-    __shared__ double sums[kGroups][kRowSums];
     const int l16 = threadIdx.x & (kRow - 1), g = threadIdx.x / kRow;
     const int per = nbu + nbi;
     const int side = (int)blockIdx.x >= per ? 1 : 0;          // 0: student tables / minibatch, 1: teacher tables / uniform set
@@ -298,25 +195,8 @@ __global__ __launch_bounds__(256) void cause_row_kernel(PassArgs a, const float 
         }
         store_row<NC, VEC>(a.grad[2 * side + (user_tab ? 0 : 1)], row, a.D, l16, out);
     }
-    if (l16 == 0) {
-        sums[g][0] = l2_share;
-        sums[g][1] = pull_share;
-    }
-    __syncthreads();
-    if (threadIdx.x < kRowSums) {
-        double t = 0.0;
-        for (int q = 0; q < kGroups; q++) t = t + sums[q][threadIdx.x];
-        partials[(int64_t)threadIdx.x * (2 * per) + blockIdx.x] = t;
-    }
-}
-
-// one wave: lane l adds entries l, l + 64, ... in order, then the lanes are folded by a fixed butterfly
-__device__ __forceinline__ double fold64(const double *__restrict__ v, int n) {
-    double t = 0.0;
-    for (int i = threadIdx.x; i < n; i += 64) t = t + v[i];
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) t = t + __shfl_xor(t, m, 64);
-    return t;
+    const double mine[kRowSums] = {l2_share, pull_share};
+    group_sums<kRowSums>(mine, partials, 2 * per);
 }
 
 // ---- fold: one wave, the five loss values
@@ -339,11 +219,6 @@ __global__ __launch_bounds__(64) void cause_fold_kernel(const double *__restrict
         losses5[3] = (float)l2;
         losses5[4] = (float)loss;
     }
-}
-
-template <typename F>
-int with_row_shape(int D, bool vec, F &&f) {
-    return with_int<1, 2, 4>(nc_of(D), [&](auto nc_c) { return with_bool(vec, [&](auto vec_c) { return f(nc_c, vec_c); }); });
 }
 
 bool sizes_ok(int64_t U, int64_t I, int64_t B, int64_t Nu, int64_t D) {

@@ -72,12 +72,15 @@ inline Layout layout_of(int64_t B, int64_t D) {
     L.nwg = (int)((n2 + kTile - 1) / kTile);
     L.nchunk = (int)((n2 + L.C - 1) / L.C);
     L.Dp = (int)((D + 3) / 4 * 4);
-    L.pq = sizeof(double) * kRec;
-    L.partials = L.pq + sizeof(double) * 2 * (size_t)n2;
-    L.part = L.partials + sizeof(double) * 4 * (size_t)L.nwg;
+    // (every part's size is a multiple of 16 bytes already)
+    Carver ws;
+    ws.take(sizeof(double) * kRec);   // the record, at the head
+    L.pq = ws.take(sizeof(double) * 2 * (size_t)n2);
+    L.partials = ws.take(sizeof(double) * 4 * (size_t)L.nwg);
     // (the chunk grows from 16 to 128 entries beyond 65 536 positions: keep the size non-decreasing across that step)
     const size_t slots = n2 <= 65536 ? (size_t)L.nchunk : (size_t)std::max(L.nchunk, 4096);
-    L.total = L.part + sizeof(float) * 2 * slots * 2 * (size_t)L.Dp;
+    L.part = ws.take(sizeof(float) * 2 * slots * 2 * (size_t)L.Dp);
+    L.total = ws.bytes();
     return L;
 }
 

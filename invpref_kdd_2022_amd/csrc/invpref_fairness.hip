@@ -37,8 +37,6 @@ constexpr int kSeg = 1024;                            // users per item-side swe
 constexpr int kFlush = 4;                             // 16-row blocks per first-level sum of the side products
 constexpr int64_t kMaxUsers = 1 << 24, kMaxDraw = 1 << 20;
 
-__host__ __device__ inline int64_t up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
 struct Layout {   // of the workspace, every part 16-byte aligned
     int64_t nuP, JP, nseg;
     size_t r, dx, g, cpos, first, next, partials, bytes;
@@ -48,20 +46,15 @@ inline Layout layout_of(int64_t nu, int64_t J, int64_t D) {
     l.nuP = up(nu, 32);
     l.JP = up(J, 16);
     l.nseg = (l.nuP + kSeg - 1) / kSeg;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += (size_t)up((int64_t)bytes, 16);
-        return o;
-    };
-    l.r = take(sizeof(float) * l.nuP * l.JP);
-    l.dx = take(sizeof(float) * l.nuP * l.JP);
-    l.g = take(sizeof(float) * l.nseg * l.JP * D);
-    l.cpos = take(sizeof(int32_t) * l.JP);
-    l.first = take(sizeof(int32_t) * l.JP);
-    l.next = take(sizeof(int32_t) * l.JP);
-    l.partials = take(sizeof(double) * (l.nuP / 32) * ((l.JP + kJB - 1) / kJB));
-    l.bytes = at;
+    Carver ws;
+    l.r = ws.take(sizeof(float) * l.nuP * l.JP);
+    l.dx = ws.take(sizeof(float) * l.nuP * l.JP);
+    l.g = ws.take(sizeof(float) * l.nseg * l.JP * D);
+    l.cpos = ws.take(sizeof(int32_t) * l.JP);
+    l.first = ws.take(sizeof(int32_t) * l.JP);
+    l.next = ws.take(sizeof(int32_t) * l.JP);
+    l.partials = ws.take(sizeof(double) * (l.nuP / 32) * ((l.JP + kJB - 1) / kJB));
+    l.bytes = ws.bytes();
     return l;
 }
 

@@ -1,24 +1,16 @@
 // invpref_macr.hip -- the MACR-MF baseline (baseline_models.py:139-234; include/invpref_macr.h) on the device: the gradient
-// pass of one optimiser step, the branch vectors and the counterfactual predict.
+// pass of one optimiser step on the pairs / rows / fold recipe of row_pass.hpp, the branch vectors and the counterfactual
+// predict.
 //
-//   pairs   one 16-lane group per interaction p = (u, i, y): gathers Pu[u] and Qi[i] (lane l owns the float4 chunks l, l + 16,
-//           ...: kernel_common.hpp), forms x = Pu[u] . Qi[i], zu = wu . Pu[u] + bu, zi = wi . Qi[i] + bi, the three sigmoids,
-//           f = (s a) c, the three bce values and the two regulariser sums (float64 partials per workgroup) and the record
-//           (dx, dzu, dzi) of the position -- four floats, no [batch, D] copy of anything
-//   rows    one 16-lane group per row of either table: walks the row's positions in ascending order (the minibatch's
-//           inverted index), gathers the partner rows, accumulates dx . partner and sum dz in that order, adds sum dz . w and
-//           the regulariser and stores the row -- ONE writer per row, rows without an interaction store zeros.  The row's
+//   pairs   x = Pu[u] . Qi[i], zu = wu . Pu[u] + bu, zi = wi . Qi[i] + bi, the three sigmoids, f = (s a) c, the three bce values
+//           and the two regulariser sums; the record of a position is (dx, dzu, dzi) -- four floats
+//   rows    either table: sum dx . partner and sum dz over the row's positions, plus sum dz . w and the regulariser.  The row's
 //           share sum dz . row of the predictor gradient goes to float64 per-workgroup partials
-//   fold    the partials of both kernels: one fp64 chain per lane over the workgroups in order, then a fixed butterfly
-// No float atomics, every sum in a fixed order: the same bits on every run.  The chain through the three sigmoids is the one
-// autograd runs, not its algebraic cancellation: where an fp32 sigmoid is exactly 0 or 1 the gradient through it is zero and
-// the clamped loss is 100.  The dot products are fp32 (the canonical row dot of canon_math.hpp); the sigmoids are fp32 values,
-// correctly rounded; everything behind them -- bce, the chain, the sums over positions, rows and workgroups -- is float64,
-// rounded to fp32 once where it is stored.
-//
-// A hot row (an item named by thousands of one minibatch's interactions) is ONE serial chain of its group in the rows kernel;
-// the next position's partner row is in flight while the current one is accumulated.
-#include "launch.hpp"
+//   fold    the predictor gradients and the four loss values
+// The chain through the three sigmoids is the one autograd runs, not its algebraic cancellation: where an fp32 sigmoid is
+// exactly 0 or 1 the gradient through it is zero and the clamped loss is 100.  The dot products are fp32 (the canonical row dot
+// of canon_math.hpp) and the sigmoids fp32 values (sigmoid_f32).
+#include "row_pass.hpp"
 
 #include "../../include/invpref_macr.h"
 
@@ -26,10 +18,7 @@ using namespace invpref;
 
 namespace {
 
-constexpr int kGroups = 256 / kRow;   // interactions (pairs) or rows (rows) per workgroup
 constexpr int kPairSums = 6;          // bce(f), bce(a), bce(c), sum of squares, sum of magnitudes, skipped interactions
-
-__host__ __device__ inline int64_t up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 struct Layout {   // of the workspace, every part 16-byte aligned
     int64_t npb, nbu, nbi;   // workgroups of the pairs kernel, user-side and item-side workgroups of the rows kernel
@@ -40,77 +29,12 @@ inline Layout layout_of(int64_t U, int64_t I, int64_t B, int64_t D) {
     l.npb = (B + kGroups - 1) / kGroups;
     l.nbu = (U + kGroups - 1) / kGroups;
     l.nbi = (I + kGroups - 1) / kGroups;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += (size_t)up((int64_t)bytes, 16);
-        return o;
-    };
-    l.rec = take(sizeof(float4) * B);
-    l.pair_part = take(sizeof(double) * kPairSums * l.npb);
-    l.row_part = take(sizeof(double) * (D + 1) * (l.nbu + l.nbi));   // [side][e = 0 .. D][workgroup], e = D: the bias
-    l.bytes = at;
+    Carver ws;
+    l.rec = ws.take(sizeof(float4) * B);
+    l.pair_part = ws.take(sizeof(double) * kPairSums * l.npb);
+    l.row_part = ws.take(sizeof(double) * (D + 1) * (l.nbu + l.nbi));   // [side][e = 0 .. D][workgroup], e = D: the bias
+    l.bytes = ws.bytes();
     return l;
-}
-
-// The three sigmoids as fp32 values, correctly rounded (float64 inside, one rounding): f = (s a) c feeds a logarithm, and three
-// factors of one to two ulps each (c_sigmoid) put a single interaction's loss further from float64 than twice an fp32 torch
-// evaluation is (measured at B = 1: 1.28e-7 relative against a bound of 1.19e-7).  The saturation is an fp32 evaluation's:
-// exactly 1 from about +17, exactly 0 where the fp32 exp(-x) overflows.
-__device__ __forceinline__ float macr_sigmoid(float x) {
-    const float r = (float)(1.0 / (1.0 + exp(-(double)x)));
-    return x < -88.72283f ? 0.0f : r;
-}
-// aten's binary_cross_entropy and its backward on fp32 probabilities, evaluated in float64
-__device__ __forceinline__ double bce64(float p, double y) {
-    const double a = fmax(log1p(-(double)p), -100.0), b = fmax(log((double)p), -100.0);
-    return (y - 1.0) * a - y * b;
-}
-__device__ __forceinline__ double dbce64(float p, double y) {
-    const double q = (double)p;
-    return (q - y) / fmax((1.0 - q) * q, 1e-12);
-}
-__device__ __forceinline__ double row16_sum64(double x) {
-#pragma unroll
-    for (int m = 1; m < kRow; m <<= 1) x = x + __shfl_xor(x, m, 64);
-    return x;
-}
-struct double4_t {
-    double x, y, z, w;
-};
-
-template <int NC>
-__device__ __forceinline__ void zero_row(float4 (&r)[NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) r[c] = f4zero();
-}
-// acc += k * r, element by element, in float64 (the product of two floats is exact there)
-template <int NC>
-__device__ __forceinline__ void axpy_row(double4_t (&acc)[NC], float k, const float4 (&r)[NC]) {
-    const double kd = (double)k;
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        acc[c].x = acc[c].x + kd * (double)r[c].x;
-        acc[c].y = acc[c].y + kd * (double)r[c].y;
-        acc[c].z = acc[c].z + kd * (double)r[c].z;
-        acc[c].w = acc[c].w + kd * (double)r[c].w;
-    }
-}
-template <int NC, bool VEC>
-__device__ __forceinline__ void store_row(float *__restrict__ base, int64_t row, int D, int l16, const float4 (&r)[NC]) {
-    float *p = base + row * (int64_t)D;
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int i0 = (l16 + kRow * c) * 4;
-        if (VEC) {
-            if (i0 < D) *reinterpret_cast<float4 *>(p + i0) = r[c];
-        } else {
-            if (i0 + 0 < D) p[i0 + 0] = r[c].x;
-            if (i0 + 1 < D) p[i0 + 1] = r[c].y;
-            if (i0 + 2 < D) p[i0 + 2] = r[c].z;
-            if (i0 + 3 < D) p[i0 + 3] = r[c].w;
-        }
-    }
 }
 
 // ---- pairs
@@ -121,7 +45,6 @@ __global__ __launch_bounds__(256) void macr_pair_kernel(const float *__restrict_
                                                         const int64_t *__restrict__ users, const int64_t *__restrict__ items,
                                                         const float *__restrict__ scores, int B, double user_coe, double item_coe,
                                                         float4 *__restrict__ rec, double *__restrict__ partials, int npb) {
-    __shared__ double sums[kGroups][kPairSums];
     const int l16 = threadIdx.x & (kRow - 1), g = threadIdx.x / kRow;
     const int p = blockIdx.x * kGroups + g;
     double mine[kPairSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -151,7 +74,7 @@ __global__ __launch_bounds__(256) void macr_pair_kernel(const float *__restrict_
             sq = row16_sum64(sq);
             mag = row16_sum64(mag);
             const double y = (double)scores[p], Bd = (double)B;
-            const float s = macr_sigmoid(x), a = macr_sigmoid(zu), c = macr_sigmoid(zi);
+            const float s = sigmoid_f32(x), a = sigmoid_f32(zu), c = sigmoid_f32(zi);
             const float sa = s * a, f = sa * c;
             // autograd's chain on the fp32 values s, a, c, f = (s a) c, in float64 and rounded once per record entry: the
             // mean's 1 / B reaches every bce first; a sigmoid that is exactly 0 or 1 passes exactly nothing
@@ -171,16 +94,7 @@ __global__ __launch_bounds__(256) void macr_pair_kernel(const float *__restrict_
         }
         if (l16 == 0) rec[p] = r;
     }
-    if (l16 == 0) {
-#pragma unroll
-        for (int k = 0; k < kPairSums; k++) sums[g][k] = mine[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kPairSums) {
-        double t = 0.0;
-        for (int q = 0; q < kGroups; q++) t = t + sums[q][threadIdx.x];
-        partials[(int64_t)threadIdx.x * npb + blockIdx.x] = t;
-    }
+    group_sums<kPairSums>(mine, partials, npb);
 }
 
 // ---- rows: workgroups [0, nbu) own 16 user rows each, [nbu, nbu + nbi) 16 item rows
@@ -209,7 +123,8 @@ __global__ __launch_bounds__(256) void macr_row_kernel(const float *__restrict__
     double sdz = 0.0;
     if (row < n_rows) {
         load_row<NC, VEC>(own_tab, row, D, l16, own);
-        const int lo = min(max(ptr[row], 0), B), hi = min(max(ptr[row + 1], lo), B);
+        int lo;
+        const int hi = list_range(ptr, row, B, lo);
         double4_t acc[NC];
         float4 cur[NC], nxt[NC];
 #pragma unroll
@@ -288,15 +203,6 @@ __global__ __launch_bounds__(256) void macr_row_kernel(const float *__restrict__
     }
 }
 
-// one wave: lane l adds entries l, l + 64, ... in order, then the lanes are folded by a fixed butterfly
-__device__ __forceinline__ double fold64(const double *__restrict__ v, int n) {
-    double t = 0.0;
-    for (int i = threadIdx.x; i < n; i += 64) t = t + v[i];
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) t = t + __shfl_xor(t, m, 64);
-    return t;
-}
-
 // ---- fold: blocks 0 .. D: grad_wu | grad_bu, D + 1 .. 2 D + 1: grad_wi | grad_bi, the last: the four loss values
 __global__ __launch_bounds__(64) void macr_fold_kernel(const double *__restrict__ pair_part, int npb,
                                                        const double *__restrict__ row_part, int nbu, int nbi, int D, double B,
@@ -344,7 +250,7 @@ __global__ __launch_bounds__(256) void macr_branch_kernel(const float *__restric
     load_row<NC, VEC>(table, row, D, l16, r);
     load_row<NC, false>(w, 0, D, l16, wv);
     const float z = dot2<NC>(wv, r) + b[0];
-    if (l16 == 0) out[row] = macr_sigmoid(z);
+    if (l16 == 0) out[row] = sigmoid_f32(z);
 }
 
 // ---- predict epilogue over the sigmoid scores: out[r][j] = ((out[r][j] - const_c) * a[users[r]]) * c[j]
@@ -359,11 +265,6 @@ __global__ __launch_bounds__(256) void macr_epilogue_kernel(float *__restrict__ 
         float *o = out + r * I + j;
         *o = ((*o - const_c) * au) * cj;
     }
-}
-
-template <typename F>
-int with_row_shape(int D, bool vec, F &&f) {
-    return with_int<1, 2, 4>(nc_of(D), [&](auto nc_c) { return with_bool(vec, [&](auto vec_c) { return f(nc_c, vec_c); }); });
 }
 
 }  // namespace

@@ -62,6 +62,23 @@ inline bool vec_ok(const InvPrefTables *t) {
 }
 inline int nc_of(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : 4); }
 inline int emax_of(int E) { return E <= 4 ? 4 : (E <= 8 ? 8 : 16); }
+// with_int / with_bool for kernels over rows of D floats: `f` takes the float4 chunks per lane and whether rows are read as float4
+template <typename F>
+int with_row_shape(int D, bool vec, F &&f) {
+    return with_int<1, 2, 4>(nc_of(D), [&](auto nc_c) { return with_bool(vec, [&](auto vec_c) { return f(nc_c, vec_c); }); });
+}
+
+inline int64_t up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+// carves a workspace into parts, every part 16-byte aligned: take() returns the offset of the next part, bytes() the size so far
+struct Carver {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t o = at;
+        at += (size_t)up((int64_t)bytes, 16);
+        return o;
+    }
+    size_t bytes() const { return at; }
+};
 
 // one row of the device-side schedule, as laid out in include/invpref_hip.h (InvPrefAdamSchedule); the kernels read it too
 struct SchedRow {

@@ -61,28 +61,44 @@ import torch
 from . import _capi
 from ._capi import Coefs, InvPrefError, call, lib, make_pure_tables, make_tables, ptr, stream_ptr
 
+def _registrars(library, names):
+    """(define, impl, fake) of one torch.library.Library; `names` collects the operators it defines"""
+    def fake(name: str):
+        return torch.library.register_fake(f'invpref::{name}', lib=library)
+
+    def define(schema: str):
+        """Declare an operator.  One that returns nothing (it only mutates its arguments) gets its fake here: nothing to shape."""
+        library.define(schema)
+        name = schema.split('(')[0]
+        names.append(name)
+        if schema.endswith('-> ()'):
+            fake(name)(lambda *args, **kwargs: None)
+
+    def impl(name: str):
+        def deco(fn):
+            library.impl(name, fn, 'CUDA')
+            return fn
+        return deco
+    return define, impl, fake
+
+
 _LIB = torch.library.Library('invpref', 'DEF')
 NAMES = []
+_define, _impl, _fake = _registrars(_LIB, NAMES)
 
 
-def _fake(name: str):
-    return torch.library.register_fake(f'invpref::{name}', lib=_LIB)
+def fragment():
+    """A FRAGMENT of the ``invpref`` library, for the operators of a header of its own: (NAMES, define, impl, fake), the name
+    list the fragment's own"""
+    names = []
+    return (names,) + _registrars(torch.library.Library('invpref', 'FRAGMENT'), names)
 
 
-def _define(schema: str):
-    """Declare an operator.  One that returns nothing (it only mutates its arguments) gets its fake here: nothing to shape."""
-    _LIB.define(schema)
-    name = schema.split('(')[0]
-    NAMES.append(name)
-    if schema.endswith('-> ()'):
-        _fake(name)(lambda *args, **kwargs: None)
-
-
-def _impl(name: str):
-    def deco(fn):
-        _LIB.impl(name, fn, 'CUDA')
-        return fn
-    return deco
+def _req(t, dtype, name, shape=None):
+    """_capi._req, and the exact shape where one is given"""
+    _capi._req(t, dtype, name)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise InvPrefError(f'{name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
 
 
 def _ids(t, name):

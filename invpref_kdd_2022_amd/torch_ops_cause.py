@@ -12,27 +12,11 @@ from __future__ import annotations
 
 import torch
 
-from . import _capi
-from . import torch_ops  # noqa: F401  (the library this one is a fragment of)
-from ._capi import InvPrefError, call, ptr, stream_ptr
+from . import torch_ops
+from ._capi import call, ptr, stream_ptr
+from .torch_ops import _req
 
-_LIB = torch.library.Library('invpref', 'FRAGMENT')
-NAMES = []
-
-
-def _define(schema: str):
-    _LIB.define(schema)
-    name = schema.split('(')[0]
-    NAMES.append(name)
-    if schema.endswith('-> ()'):
-        torch.library.register_fake(f'invpref::{name}', lib=_LIB)(lambda *args, **kwargs: None)
-
-
-def _req(t, dtype, name, shape=None):
-    _capi._req(t, dtype, name)
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise InvPrefError(f'{name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
-
+NAMES, _define, _impl, _fake = torch_ops.fragment()
 
 _define('cause_grad_(Tensor user_table, Tensor item_table, Tensor teacher_user_table, Tensor teacher_item_table, '
         'Tensor users, Tensor items, Tensor scores, Tensor user_ptr, Tensor user_pos, Tensor item_ptr, Tensor item_pos, '
@@ -42,6 +26,7 @@ _define('cause_grad_(Tensor user_table, Tensor item_table, Tensor teacher_user_t
         'Tensor(c!) grad_teacher_user, Tensor(d!) grad_teacher_item, Tensor(e!) losses5, Tensor(f!) workspace) -> ()')
 
 
+@_impl('cause_grad_')
 def _cause_grad(user_table, item_table, teacher_user_table, teacher_item_table, users, items, scores, user_ptr, user_pos,
                 item_ptr, item_pos, uni_users, uni_items, uni_scores, uni_user_ptr, uni_user_pos, uni_item_ptr, uni_item_pos,
                 implicit, reg_mode, L2_coe, teacher_L2_coe, uniform_loss_coe, teacher_reg_coe, grad_user, grad_item,
@@ -68,6 +53,3 @@ def _cause_grad(user_table, item_table, teacher_user_table, teacher_item_table, 
          int(bool(implicit)), int(reg_mode), float(L2_coe), float(teacher_L2_coe), float(uniform_loss_coe), float(teacher_reg_coe),
          ptr(grad_user), ptr(grad_item), ptr(grad_teacher_user), ptr(grad_teacher_item), ptr(losses5), ptr(workspace),
          workspace.numel(), stream_ptr())
-
-
-_LIB.impl('cause_grad_', _cause_grad, 'CUDA')

@@ -12,38 +12,11 @@ from __future__ import annotations
 
 import torch
 
-from . import _capi
-from . import torch_ops  # noqa: F401  (the library this one is a fragment of)
+from . import torch_ops
 from ._capi import InvPrefError, call, ptr, stream_ptr
+from .torch_ops import _req
 
-_LIB = torch.library.Library('invpref', 'FRAGMENT')
-NAMES = []
-
-
-def _define(schema: str):
-    _LIB.define(schema)
-    name = schema.split('(')[0]
-    NAMES.append(name)
-    if schema.endswith('-> ()'):
-        torch.library.register_fake(f'invpref::{name}', lib=_LIB)(lambda *args, **kwargs: None)
-
-
-def _impl(name: str):
-    def deco(fn):
-        _LIB.impl(name, fn, 'CUDA')
-        return fn
-    return deco
-
-
-def _fake(name: str):
-    return torch.library.register_fake(f'invpref::{name}', lib=_LIB)
-
-
-def _req(t, dtype, name, shape=None):
-    _capi._req(t, dtype, name)
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise InvPrefError(f'{name} must have the shape {tuple(shape)}, got {tuple(t.shape)}')
-
+NAMES, _define, _impl, _fake = torch_ops.fragment()
 
 _define('macr_grad_(Tensor user_table, Tensor item_table, Tensor user_w, Tensor user_b, Tensor item_w, Tensor item_b, '
         'Tensor users, Tensor items, Tensor scores, Tensor user_ptr, Tensor user_pos, Tensor item_ptr, Tensor item_pos, '

@@ -12,12 +12,11 @@ from __future__ import annotations
 
 import torch
 
-from . import _capi
 from . import torch_ops
 from ._capi import InvPrefError, call, lib, ptr, stream_ptr
+from .torch_ops import _req
 
-_LIB = torch.library.Library('invpref', 'FRAGMENT')
-NAMES = []
+NAMES, _define, _impl, _fake = torch_ops.fragment()
 
 _ARGS = ('(Tensor user_table, Tensor item_table, Tensor users, int k, bool sigmoid, Tensor? mask_ptr, Tensor? mask_items, '
          'Tensor? highlight_ptr, Tensor? highlight_items, Tensor? truth_ptr, Tensor? truth_items, Tensor user_scale, '
@@ -26,15 +25,14 @@ _ARGS = ('(Tensor user_table, Tensor item_table, Tensor users, int k, bool sigmo
 
 def _scaled(name: str, entry: str, workspace_bytes: str):
     """Define one of the two operators: the C entry point `entry`, its workspace sized by the plain form's function"""
-    _LIB.define(name + _ARGS)
-    NAMES.append(name)
+    _define(name + _ARGS)
 
     def impl(user_table, item_table, users, k, sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr,
              truth_items, user_scale, item_scale, shift):
         torch_ops._f32(user_table, 'user_table'); torch_ops._f32(item_table, 'item_table')
         n, (I, D) = users.numel(), item_table.shape
-        _capi._req(user_scale, torch.float32, 'user_scale')
-        _capi._req(item_scale, torch.float32, 'item_scale')
+        _req(user_scale, torch.float32, 'user_scale')
+        _req(item_scale, torch.float32, 'item_scale')
         if user_scale.numel() != user_table.shape[0] or item_scale.numel() != I:
             raise InvPrefError(f'{name}: user_scale holds one float per row of user_table ({user_table.shape[0]}) and item_scale '
                                f'one per row of item_table ({I}), got {user_scale.numel()} and {item_scale.numel()}')
@@ -59,8 +57,8 @@ def _scaled(name: str, entry: str, workspace_bytes: str):
         return (torch.empty(n, k, dtype=torch.int32, **f), torch.empty(n, k, dtype=torch.float32, **f),
                 torch.empty(n, k, dtype=torch.float32, **f))
 
-    _LIB.impl(name, impl, 'CUDA')
-    torch.library.register_fake(f'invpref::{name}', lib=_LIB)(fake)
+    _impl(name)(impl)
+    _fake(name)(fake)
 
 
 _scaled('predict_topk_scaled', 'invpref_predict_topk_scaled_hip', 'invpref_predict_topk_workspace_bytes')
