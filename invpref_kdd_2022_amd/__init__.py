@@ -4,11 +4,13 @@ _FAIRNESS = ('FairnessMFTrainManager', 'fairness_item_table', 'fairness_draw', '
 
 _MACR = ('MACRMatrixFactorization', 'MACRTrainManager')
 
+_LINTRANS = ('LinearTransMatrixFactorization', 'LinearTransTrainManager')
+
 _CAUSE = ('CausEMatrixFactorization', 'CausEExplicitMatrixFactorization', 'CausETrainManager', 'CausEExplicitTrainManager')
 
 
 def __getattr__(name):   # resolved on first use: importing the package loads neither torch nor the HIP library
-    if name in _FAIRNESS or name in _MACR or name in _CAUSE:
+    if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE:
         from . import baseline
         return getattr(baseline, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

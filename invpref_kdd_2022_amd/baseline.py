@@ -1,6 +1,6 @@
 """PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF,
-CVIB-MF and fairness-MF; and MACR-MF and CausE, whose steps are gradient passes of their own (csrc/invpref_macr.hip,
-csrc/invpref_cause.hip).
+CVIB-MF and fairness-MF; and MACR-MF, LinearTrans-MF and CausE, whose steps are gradient passes of their own
+(csrc/invpref_macr.hip, csrc/invpref_lintrans.hip, csrc/invpref_cause.hip).
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -1069,6 +1069,167 @@ class MACRTrainManager(BasicImplicitTrainManager):
             index = self._macr_index[k]
         ops.macr_grad(st.p_views, st.g_views, users, items, scores, index, m.user_coe, m.item_coe, self.L2_coe, self.L1_coe,
                       losses6[:4], self._macr_ws)
+
+    @staticmethod
+    def loss_dicts(dev_losses: torch.Tensor) -> list:
+        """the pass writes the reference's four terms (train.py:399-404) into the first four slots"""
+        return [dict(zip(PURE_LOSS_KEYS, v[:4])) for v in dev_losses.tolist()]
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """train.py:379-405 on caller tensors: this minibatch's index is built here, then one step."""
+        dev = self.device
+        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        index = tuple(torch.from_numpy(a).to(dev) for a in ops.macr_index(ud, vd, self.model.user_num, self.model.item_num))
+        self._caller = (ud, vd, index)
+        try:
+            return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
+        finally:
+            self._caller = None
+
+
+# ------------------------------------------------------------------------------------------------ LinearTrans-MF
+class _LinearTransLoss(torch.autograd.Function):
+    """score_loss of LinearTrans-MF's forward through ops.lintrans_grad: the pass forms the loss and the gradients of all four
+    tensors at once, backward() scales them by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, users, items, scores, *tables):
+        data = [t.detach().contiguous() for t in tables]
+        dev = data[0].device
+        users, items = users.reshape(-1).long().contiguous(), items.reshape(-1).long().contiguous()
+        index = [torch.from_numpy(a).to(dev) for a in ops.macr_index(users, items, data[0].shape[0], data[1].shape[0])]
+        grads = [torch.empty_like(t) for t in data]
+        losses = torch.empty(4, dtype=torch.float32, device=dev)
+        ops.lintrans_grad(data, grads, users, items, scores.detach().reshape(-1).float().contiguous(), index, 0., 0., losses)
+        ctx.save_for_backward(*grads)
+        return losses[0].clone()
+
+    @staticmethod
+    def backward(ctx, gs):
+        scale = gs.detach().to(torch.float32)
+        return (None, None, None, *[g * scale for g in ctx.saved_tensors])
+
+
+class LinearTransMatrixFactorization(nn.Module):
+    """baseline_models.py:72-136: MF whose score is sigmoid(w . (u (*) i) + b) -- InvPref's LinearImplicitScorePredictor over the
+    element-wise product of ONE pair of tables: the single-branch ablation of InvPref, trained with its predictor under the plain
+    BasicImplicitTrainManager.  The reference's constructor order (the same torch.manual_seed gives the same initial
+    state_dict), parameter and attribute names.
+
+    Not a PureMatrixFactorization: ImplicitTestManager ranks it by rank_fn(), the weighted scan of csrc/invpref_retrieve.hip
+    (its topk() keeps the predict() + top-k route of any other model).  forward / predict run on csrc/invpref_lintrans.hip;
+    predict() never builds the reference's [n item_num, D] temporary.  forward builds the minibatch's inverted index on the
+    host per call (the unfused surface -- LinearTransTrainManager prepares it once per static minibatch)."""
+    implicit = True
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int):
+        super().__init__()
+        self.user_num, self.item_num, self.factor_num = user_num, item_num, factor_num
+        self.user_emb = nn.Embedding(user_num, factor_num)
+        self.item_emb = nn.Embedding(item_num, factor_num)
+        self.linear_predictor = LinearImplicitScorePredictor(factor_num)
+        self.loss_func = nn.BCELoss()
+        nn.init.normal_(self.user_emb.weight, std=0.01)  # baseline_models.py:83-85
+        nn.init.normal_(self.item_emb.weight, std=0.01)
+        self._absent = None
+
+    def tables(self):
+        """the four parameters in state_dict order"""
+        return [self.user_emb.weight, self.item_emb.weight, self.linear_predictor.linear_map.weight,
+                self.linear_predictor.linear_map.bias]
+
+    def forward(self, users_id, items_id, ground_truth):  # baseline_models.py:87-93: the score loss
+        return _LinearTransLoss.apply(users_id, items_id, ground_truth, *self.tables())
+
+    # PureMF's regularisers over the gathered embedding rows plus the predictor's own terms (baseline_models.py:95-119,
+    # models.py:237-243) -- D + 1 numbers, summed by torch as the reference does; the training pass has them in its kernels
+    _seven = _PureMFBase._seven
+    _reg = _PureMFBase._reg
+
+    def get_L1_reg(self, users_id, items_id):
+        lm = self.linear_predictor.linear_map
+        return self._reg(users_id, items_id, 1) + torch.norm(lm.weight, 1) / float(self.factor_num) + torch.norm(lm.bias, 1)
+
+    def get_L2_reg(self, users_id, items_id):
+        lm = self.linear_predictor.linear_map
+        return (self._reg(users_id, items_id, 2) + torch.norm(lm.weight, 2).pow(2) / float(self.factor_num)
+                + torch.norm(lm.bias, 2).pow(2))
+
+    def _frozen(self):
+        """(user table, item table, weight [D], bias [1]) detached and contiguous"""
+        lm = self.linear_predictor.linear_map
+        return (self.user_emb.weight.detach().contiguous(), self.item_emb.weight.detach().contiguous(),
+                lm.weight.detach().reshape(-1).contiguous(), lm.bias.detach().contiguous())
+
+    def predict(self, users_id):  # baseline_models.py:121-136
+        P, Q, w, b = self._frozen()
+        users = torch.as_tensor(users_id).to(P.device).reshape(-1).to(torch.int64).contiguous()
+        return ops.lintrans_predict(P, Q, users, w, b)
+
+    def rank_fn(self):
+        """ImplicitTestManager's fused route: f(users, k, mask, highlight, truth) -> (items, scores, hits) ranking by the
+        scores of predict() without their matrix -- one weighted scan per call of f; weight and bias stay on the device, so a
+        captured evaluation follows them"""
+        P, Q, w, b = self._frozen()
+        return lambda users, k, mask, highlight, truth: ops.predict_topk_weighted(
+            P, Q, users, k, w, b, True, mask=mask, highlight=highlight, truth=truth)
+
+    def recommend(self, users_id, k: int, exclude=None, highlight=None):
+        """Each user's top-k items by the scores of predict(), `exclude` items scoring -1024 and `highlight` items += 1024
+        (CSR pairs aligned with users_id): the weighted scan (ops.predict_topk_weighted) -- no rating matrix; the ranking of
+        predict()'s matrix item for item and score for score.  -> (items int64[n, k], scores fp32[n, k])"""
+        P, Q, w, b = self._frozen()
+        users = torch.as_tensor(users_id).to(P.device)
+        return ops.recommend(P, Q, users, k, exclude=exclude, highlight=highlight, dim_weight=w, logit_bias=b)
+
+
+class LinearTransTrainManager(BasicImplicitTrainManager):
+    """LinearTrans-MF under the reference's plain BasicImplicitTrainManager (train.py:345-461):
+    loss = model(users, items, scores) + L2_coe * L2_reg + L1_coe * L1_reg with the predictor inside both regularisers, Adam over
+    all four tensors.
+
+    Always the engine's unfused sequence: the model's own gradient pass (ops.lintrans_grad, csrc/invpref_lintrans.hip: every row
+    of every gradient overwritten) -> the dense / ranged Adam over the whole flat state, which holds the four tensors.  The
+    minibatches are static, so each one's inverted index is built once on the host and kept on the device; the pass reads ids
+    and index when it runs, and the ranged Adam launch carries the device-side schedule, so whole epochs replay as graphs.
+    Single process."""
+    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    _SINGLE = ('LinearTrans-MF runs in a single process (a sharded form would all-reduce the gradients of all four tensors; '
+               'not implemented)')
+
+    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, rank=None,
+                 world_size=None, process_group=None):
+        if world_size is not None and int(world_size) > 1:
+            raise NotImplementedError(self._SINGLE)
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        if self.world_size > 1:
+            raise NotImplementedError(self._SINGLE)
+        self._unfused = True        # gradient pass -> Adam, never the fused / alternating step
+        self._lt_index = None       # per static minibatch: (user_ptr, user_pos, item_ptr, item_pos) on the device
+        self._caller = None         # train_a_batch: (users, items, index) of the caller's minibatch
+        self._lt_ws = ops.Workspace(self.device)
+        self._lt_ws.get(max(ops.lintrans_workspace_bytes(model.user_num, model.item_num, min(batch_size, self.n_total),
+                                                         model.factor_num), 16))   # sized once: capturable launches
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        if self._lt_index is None:
+            u, v = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy()
+            self._lt_index = [tuple(torch.from_numpy(a).to(self.device) for a in ops.macr_index(
+                u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], self.model.user_num, self.model.item_num)) for b in self._raw_batches]
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        st = self.state
+        if k is None:
+            users, items, index = self._caller
+        else:
+            index = self._lt_index[k]
+        ops.lintrans_grad(st.p_views, st.g_views, users, items, scores, index, self.L2_coe, self.L1_coe, losses6[:4],
+                          self._lt_ws)
 
     @staticmethod
     def loss_dicts(dev_losses: torch.Tensor) -> list:

@@ -20,8 +20,13 @@
 // between the sigmoid and the mask each score becomes ((p - shift) * user_scale[users[row]]) * item_scale[item] --
 // macr_epilogue_kernel's three fp32 operations, in its order, so the scores are that kernel's bit for bit.
 // retrieve_scan_kernel is the text without it: the code it was, under the signature it had.
+//
+// The weighted form (include/invpref_lintrans.h; retrieve_weighted_scan_kernel, the third form): the A operands are the user
+// rows multiplied by dim_weight as they are loaded -- fp32(Pu[u][e] * w[e]), one rounding -- and logit_bias[0] is added in front of
+// the sigmoid: LinearTrans-MF's score, bit for bit what invpref_lintrans_predict_hip writes into its matrix.
 #include "launch.hpp"
 
+#include "../../include/invpref_lintrans.h"
 #include "../../include/invpref_retrieve_scaled.h"
 
 using namespace invpref;
@@ -76,7 +81,7 @@ __device__ __forceinline__ int lower_bound(const int *__restrict__ a, int lo, in
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-// the scan kernel, in its two forms (retrieve_scan_body.hpp)
+// the scan kernel, in its three forms (retrieve_scan_body.hpp)
 #define RETRIEVE_SCAN_NAME retrieve_scan_kernel
 #define RETRIEVE_SCAN_SCALED 0
 #include "retrieve_scan_body.hpp"
@@ -84,6 +89,11 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 #undef RETRIEVE_SCAN_SCALED
 #define RETRIEVE_SCAN_NAME retrieve_scaled_scan_kernel
 #define RETRIEVE_SCAN_SCALED 1
+#include "retrieve_scan_body.hpp"
+#undef RETRIEVE_SCAN_NAME
+#undef RETRIEVE_SCAN_SCALED
+#define RETRIEVE_SCAN_NAME retrieve_weighted_scan_kernel
+#define RETRIEVE_SCAN_SCALED 2
 #include "retrieve_scan_body.hpp"
 #undef RETRIEVE_SCAN_NAME
 #undef RETRIEVE_SCAN_SCALED
@@ -170,16 +180,17 @@ size_t bytes_for(int64_t n_users, int64_t item_num, int64_t k) {
     return (size_t)n_users * (size_t)geometry(n_users, item_num).ranges * (size_t)k * 8u;
 }
 
-// both entry points: every check before any launch; `scaled` picks the scan's epilogue instances
+// the three entry points: every check before any launch; `form` (0 plain, 1 scaled, 2 weighted) picks the scan's instances
 int predict_topk(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users, int64_t item_num,
                  int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr, const int32_t *mask_items,
                  const int32_t *highlight_ptr, const int32_t *highlight_items, const int32_t *truth_ptr,
                  const int32_t *truth_items, int32_t k, int32_t *out_items, float *out_scores, float *out_hits, void *workspace,
-                 size_t workspace_bytes, void *stream, bool scaled, const float *user_scale, const float *item_scale,
-                 double shift) {
+                 size_t workspace_bytes, void *stream, int form, const float *user_scale, const float *item_scale,
+                 double shift, const float *dim_weight = nullptr, const float *logit_bias = nullptr) {
     if (!user_table || !item_table || n_users < 0 || item_num <= 0 || factor_num <= 0 || k <= 0)
         return INVPREF_EINVAL;
-    if (scaled && (!user_scale || !item_scale)) return INVPREF_EINVAL;
+    if (form == 1 && (!user_scale || !item_scale)) return INVPREF_EINVAL;
+    if (form == 2 && (!dim_weight || !logit_bias)) return INVPREF_EINVAL;
     if ((mask_ptr && !mask_items) || (highlight_ptr && !highlight_items) || (truth_ptr && !truth_items)) return INVPREF_EINVAL;
     if (k > kMaxK || k > item_num || factor_num > INVPREF_MAX_FACTORS || item_num > INT32_MAX - 16) return INVPREF_EUNSUPPORTED;
     if (n_users == 0) return 0;
@@ -193,12 +204,18 @@ int predict_topk(const float *user_table, const float *item_table, const int64_t
     const int I = (int)item_num, D = (int)factor_num;
     const int rc = with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
         return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
-            return with_bool(scaled, [&](auto scaled_c) {
+            return with_int<0, 1, 2>(form, [&](auto form_c) {
                 constexpr int DC = decltype(dc_c)::value;
                 constexpr bool VEC = decltype(vec_c)::value;
                 constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4) + (size_t)64 * kCand * 8;
                 const dim3 grid((unsigned)g.ux, (unsigned)g.ranges);
-                if constexpr (decltype(scaled_c)::value) {
+                if constexpr (decltype(form_c)::value == 2) {
+                    const auto scan = retrieve_weighted_scan_kernel<DC, VEC>;
+                    if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
+                    hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D,
+                                       apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k, g.steps_per,
+                                       wk, wi, dim_weight, logit_bias);
+                } else if constexpr (decltype(form_c)::value == 1) {
                     const auto scan = retrieve_scaled_scan_kernel<DC, VEC>;
                     if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
                     hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D,
@@ -242,7 +259,7 @@ int invpref_predict_topk_hip(const float *user_table, const float *item_table, c
                              float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream) {
     return predict_topk(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
                         highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits, workspace,
-                        workspace_bytes, stream, false, nullptr, nullptr, 0.0);
+                        workspace_bytes, stream, 0, nullptr, nullptr, 0.0);
 }
 
 int invpref_predict_topk_scaled_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
@@ -253,7 +270,18 @@ int invpref_predict_topk_scaled_hip(const float *user_table, const float *item_t
                                     const float *user_scale, const float *item_scale, double shift) {
     return predict_topk(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
                         highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits, workspace,
-                        workspace_bytes, stream, true, user_scale, item_scale, shift);
+                        workspace_bytes, stream, 1, user_scale, item_scale, shift);
+}
+
+int invpref_predict_topk_weighted_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
+                                      int64_t item_num, int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr,
+                                      const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
+                                      const int32_t *truth_ptr, const int32_t *truth_items, int32_t k, int32_t *out_items,
+                                      float *out_scores, float *out_hits, void *workspace, size_t workspace_bytes, void *stream,
+                                      const float *dim_weight, const float *logit_bias) {
+    return predict_topk(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                        highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits, workspace,
+                        workspace_bytes, stream, 2, nullptr, nullptr, 0.0, dim_weight, logit_bias);
 }
 
 }  // extern "C"

@@ -19,10 +19,14 @@
 // (invpref_macr.hip: macr_epilogue_kernel, ((s - shift) * user_scale[user]) * item_scale[item]) over each chunk of scores
 // before the select.
 //
+// invpref_predict_topk_weighted_wide_hip (include/invpref_lintrans.h): the same loop with each chunk of scores written by
+// invpref::lintrans_scores (invpref_lintrans.hip: the sweep of invpref_lintrans_predict_hip) instead of invpref_predict_hip.
+//
 // user_values_wide_kernel: stage 1 of invpref_rank_metrics_hip for K <= 1024: the per-user dcg row sum follows numpy's
 // pairwise recursion above 128 elements; stages 2 and 3 are invpref_metrics.hip's (invpref::rank_metrics_reduce).
 #include "launch.hpp"
 
+#include "../../include/invpref_lintrans.h"
 #include "../../include/invpref_retrieve_scaled.h"
 
 using namespace invpref;
@@ -35,6 +39,9 @@ size_t rank_metrics_bytes(int64_t n_users, int n_k, int64_t partition);
 // invpref_macr.hip: scores[r][j] = ((scores[r][j] - shift) * user_scale[users[r]]) * item_scale[j] over [n, I] scores
 int scale_rows(float *scores, const int64_t *users, int64_t n, int64_t I, const float *user_scale, const float *item_scale,
                float shift, hipStream_t st);
+// invpref_lintrans.hip: the weighted score matrix, c_sigmoid(fp32(Pu[users[r]] (*) w) . Qi[j] + bias)
+int lintrans_scores(const float *user_table, const float *item_table, const int64_t *users, int64_t n, int64_t I, int64_t D,
+                    const float *dim_weight, const float *bias, int apply_sigmoid, float *out, hipStream_t st);
 }  // namespace invpref
 
 namespace {
@@ -289,13 +296,16 @@ size_t scores_bytes(int64_t rows, int64_t I) { return ((size_t)rows * (size_t)I 
 
 bool half_pair(const void *p, const void *items) { return (p != nullptr) != (items != nullptr); }
 
-// both chunked entry points: every check before any launch; `scaled` adds the scale pass between the predict and the select
+// the chunked entry points: every check before any launch; `scaled` adds the scale pass between the predict and the select, a
+// dim_weight replaces the predict by the weighted sweep
 int predict_topk_wide(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users, int64_t item_num,
                       int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr, const int32_t *mask_items,
                       const int32_t *highlight_ptr, const int32_t *highlight_items, const int32_t *truth_ptr,
                       const int32_t *truth_items, int32_t k, int32_t *out_items, float *out_scores, float *out_hits,
                       void *workspace, size_t workspace_bytes, void *stream, bool scaled, const float *user_scale,
-                      const float *item_scale, double shift) {
+                      const float *item_scale, double shift, bool weighted = false, const float *dim_weight = nullptr,
+                      const float *logit_bias = nullptr) {
+    if (weighted && (!dim_weight || !logit_bias)) return INVPREF_EINVAL;
     if (!user_table || !item_table || n_users < 0 || item_num <= 0 || factor_num <= 0 || k <= 0) return INVPREF_EINVAL;
     if (scaled && (!user_scale || !item_scale)) return INVPREF_EINVAL;
     if (half_pair(mask_ptr, mask_items) || half_pair(highlight_ptr, highlight_items) || half_pair(truth_ptr, truth_items))
@@ -312,7 +322,10 @@ int predict_topk_wide(const float *user_table, const float *item_table, const in
     auto at = [](const int32_t *p, int64_t o) { return p ? p + o : nullptr; };
     for (int64_t lo = 0; lo < n_users; lo += R) {
         const int64_t m = std::min(R, n_users - lo);
-        int rc = invpref_predict_hip(user_table, item_table, users + lo, m, item_num, factor_num, apply_sigmoid, scores, stream);
+        int rc = weighted ? lintrans_scores(user_table, item_table, users + lo, m, item_num, factor_num, dim_weight, logit_bias,
+                                            apply_sigmoid, scores, st)
+                          : invpref_predict_hip(user_table, item_table, users + lo, m, item_num, factor_num, apply_sigmoid, scores,
+                                                stream);
         if (rc != 0) return rc;
         if (scaled) {
             if ((rc = scale_rows(scores, users + lo, m, item_num, user_scale, item_scale, (float)shift, st)) != 0) return rc;
@@ -376,6 +389,18 @@ int invpref_predict_topk_scaled_wide_hip(const float *user_table, const float *i
     return predict_topk_wide(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
                              highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits,
                              workspace, workspace_bytes, stream, true, user_scale, item_scale, shift);
+}
+
+int invpref_predict_topk_weighted_wide_hip(const float *user_table, const float *item_table, const int64_t *users,
+                                           int64_t n_users, int64_t item_num, int64_t factor_num, int apply_sigmoid,
+                                           const int32_t *mask_ptr, const int32_t *mask_items, const int32_t *highlight_ptr,
+                                           const int32_t *highlight_items, const int32_t *truth_ptr, const int32_t *truth_items,
+                                           int32_t k, int32_t *out_items, float *out_scores, float *out_hits, void *workspace,
+                                           size_t workspace_bytes, void *stream, const float *dim_weight,
+                                           const float *logit_bias) {
+    return predict_topk_wide(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                             highlight_ptr, highlight_items, truth_ptr, truth_items, k, out_items, out_scores, out_hits,
+                             workspace, workspace_bytes, stream, false, nullptr, nullptr, 0.0, true, dim_weight, logit_bias);
 }
 
 int invpref_rank_metrics_wide_hip(const float *hits, int64_t n_users, int64_t ld, int32_t K, const int32_t *truth_ptr,

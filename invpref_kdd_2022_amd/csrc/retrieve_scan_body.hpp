@@ -1,8 +1,10 @@
 // retrieve_scan_body.hpp -- the scan kernel of invpref_retrieve.hip, included there once per form (no include guard):
 //   RETRIEVE_SCAN_NAME    the kernel's name
 //   RETRIEVE_SCAN_SCALED  0: the plain scan; 1: three more arguments and the epilogue
-//                         p = ((p - shift) * user_scale[users[row]]) * item_scale[item] between the sigmoid and the mask
-// Two kernels from one text rather than one kernel with a third template parameter or a shared __device__ body: the plain
+//                         p = ((p - shift) * user_scale[users[row]]) * item_scale[item] between the sigmoid and the mask;
+//                         2: the weighted scan (include/invpref_lintrans.h): two more arguments, the A operands are
+//                         fp32(Pu[user][e] * dim_weight[e]) and p = p + logit_bias[0] in front of the sigmoid
+// Three kernels from one text rather than one kernel with a third template parameter or a shared __device__ body: the plain
 // kernel keeps its name, its signature and, instruction for instruction, its code (an inlined body compiles to other
 // registers, and spills in one instance).
 //
@@ -14,10 +16,14 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
                                                              const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
                                                              const int *__restrict__ hl_items, int K, int steps_per,
                                                              unsigned *__restrict__ ws_keys, int *__restrict__ ws_ids
-#if RETRIEVE_SCAN_SCALED
+#if RETRIEVE_SCAN_SCALED == 1
                                                              ,
                                                              const float *__restrict__ user_scale,
                                                              const float *__restrict__ item_scale, float shift
+#endif
+#if RETRIEVE_SCAN_SCALED == 2
+                                                             ,
+                                                             const float *__restrict__ dim_weight, const float *__restrict__ logit_bias_ptr
 #endif
 ) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -37,23 +43,30 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
 #pragma unroll
         for (int s = 0; s < 16; s++) {
             const int e = 64 * c + 4 * s + k;
+#if RETRIEVE_SCAN_SCALED == 2
+            const float v = pu[e < D ? e : D - 1] * dim_weight[e < D ? e : D - 1];
+#else
             const float v = pu[e < D ? e : D - 1];
+#endif
             a[c][s] = e < D ? v : 0.f;
         }
+#if RETRIEVE_SCAN_SCALED == 2
+    const float logit_bias = logit_bias_ptr[0];
+#endif
     const int tiles = (I + 15) / 16;
     const int t0 = (int)blockIdx.y * steps_per, t1 = min(tiles, t0 + steps_per);
     // ---- per-user state: lane (k, m) serves users 4 k + r of the wave (r = 0..3), the same for its 16 lanes
     int mcur[4], mend[4], mnext[4], hcur[4], hend[4], hnext[4], cnt[4];
     unsigned tau[4];   // survivors need key >= tau
     bool valid[4];
-#if RETRIEVE_SCAN_SCALED
+#if RETRIEVE_SCAN_SCALED == 1
     float us[4];       // the four users' scales, by user id (a row beyond n reads the last user's)
 #endif
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int64_t row = (int64_t)blockIdx.x * 64 + wave * 16 + 4 * k + r;
         valid[r] = row < n;
-#if RETRIEVE_SCAN_SCALED
+#if RETRIEVE_SCAN_SCALED == 1
         us[r] = user_scale[users[valid[r] ? row : n - 1]];
 #endif
         const int64_t rr = valid[r] ? row : 0;
@@ -100,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
     };
     float4 st[PER];
     load(min(t0, tiles - 1), st);
-#if RETRIEVE_SCAN_SCALED
+#if RETRIEVE_SCAN_SCALED == 1
     // item_scale of this lane's item, clamped like the rows; the next tile's is issued with its rows and waited for with them
     auto load_scale = [&](int t) { return item_scale[min(t * 16 + m, I - 1)]; };
     float isc = load_scale(min(t0, tiles - 1)), isc_next;
@@ -110,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
     for (int t = t0; t < t1; t++) {
         const int buf = (t - t0) & 1;
         load(min(t + 1, t1 - 1), st);
-#if RETRIEVE_SCAN_SCALED
+#if RETRIEVE_SCAN_SCALED == 1
         isc_next = load_scale(min(t + 1, t1 - 1));
 #endif
         const float *bt = lds + buf * TILE + m * RS + k;
@@ -133,8 +146,11 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             float p = acc[0][r];
+#if RETRIEVE_SCAN_SCALED == 2
+            p = p + logit_bias;
+#endif
             if (apply_sigmoid) p = c_sigmoid(p);
-#if RETRIEVE_SCAN_SCALED
+#if RETRIEVE_SCAN_SCALED == 1
             p = ((p - shift) * us[r]) * isc;
 #endif
             // mask / highlight bits of this tile for user 4 k + r (the 16 lanes of the group walk the same cursor)
@@ -180,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
             }
         }
         store(buf ^ 1, st);
-#if RETRIEVE_SCAN_SCALED
+#if RETRIEVE_SCAN_SCALED == 1
         isc = isc_next;
 #endif
         __syncthreads();

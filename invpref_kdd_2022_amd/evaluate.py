@@ -122,7 +122,7 @@ class ImplicitTestManager:
         """The fused route of the model: a callable f(users, k, mask, highlight, truth) -> (items, scores, hits) that ranks
         without a score matrix, else None (topk() batch by batch).  predict_topk on _fused_tables() for the models that rank
         by sigmoid(user . item); a model with scores of its own offers rank_fn() (MACRMatrixFactorization: its two branch
-        launches, then the scaled scan)."""
+        launches, then the scaled scan; LinearTransMatrixFactorization: the weighted scan)."""
         from .ops import predict_topk
         tables = self._fused_tables()
         if tables is not None:

@@ -17,6 +17,7 @@ from . import torch_ops  # noqa: F401  (registers torch.ops.invpref.*)
 from . import torch_ops_macr  # noqa: F401  (the MACR fragment: torch.ops.invpref.macr_*)
 from . import torch_ops_cause  # noqa: F401  (the CausE fragment: torch.ops.invpref.cause_grad_)
 from . import torch_ops_scaled  # noqa: F401  (the scaled retrieval's fragment: torch.ops.invpref.predict_topk_scaled*)
+from . import torch_ops_lintrans  # noqa: F401  (the LinearTrans fragment: torch.ops.invpref.lintrans_*, predict_topk_weighted*)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -255,6 +256,27 @@ def predict_topk_scaled(user_table: torch.Tensor, item_table: torch.Tensor, user
     return op(user_table, item_table, users, k, bool(sigmoid), mp, mi, hp, hi, tp, ti, user_scale, item_scale, float(shift))
 
 
+def predict_topk_weighted(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, k: int,
+                          dim_weight: torch.Tensor, logit_bias, sigmoid: bool = True, mask=None, highlight=None, truth=None):
+    """predict_topk on the scores sigmoid(sum_d dim_weight_d user_d item_d + logit_bias) (the logit itself if not sigmoid):
+    the user row times dim_weight rounded to fp32, the canonical dot product, the bias added in fp32, then mask, highlight,
+    top-k and hit labels as in predict_topk -- no [n, item_num] matrix and no other device memory.  dim_weight fp32 of
+    factor_num floats; logit_bias a number or an fp32 device tensor of one element (read when the launch runs: a captured
+    ranking follows it).  With LinearTrans-MF's predictor these are ops.lintrans_predict's scores bit
+    for bit; ties (distinct logits share fp32 sigmoids) go to the lowest item id.
+    -> (items int32[n, k], scores fp32[n, k], hits fp32[n, k]).
+    k <= 64 runs the fused scan (predict_topk_weighted); 64 < k <= 1024 the chunked form (predict_topk_weighted_wide)."""
+    _gpu(user_table, item_table, users, dim_weight)
+    k = _check_topk(k)
+    (mp, mi), (hp, hi), (tp, ti) = [(None, None) if c is None else c for c in (mask, highlight, truth)]
+    op = _o().predict_topk_weighted if k <= _capi.MAX_TOPK else _o().predict_topk_weighted_wide
+    if not isinstance(logit_bias, torch.Tensor):
+        logit_bias = torch.full((1,), float(logit_bias), dtype=torch.float32, device=users.device)
+    _gpu(logit_bias)
+    return op(user_table, item_table, users, k, bool(sigmoid), mp, mi, hp, hi, tp, ti, dim_weight.reshape(-1),
+              logit_bias.reshape(-1))
+
+
 def _check_topk(k) -> int:
     k = int(k)
     if k > _capi.MAX_TOPK_WIDE:
@@ -344,16 +366,26 @@ def device_csr(csr, n_rows: int, n_items: int, device):
 
 
 def recommend(user_table: torch.Tensor, item_table: torch.Tensor, users_id: torch.Tensor, k: int, exclude=None,
-              highlight=None, sigmoid: bool = True, *, user_scale=None, item_scale=None, shift: float = 0.0):
+              highlight=None, sigmoid: bool = True, *, user_scale=None, item_scale=None, shift: float = 0.0, dim_weight=None,
+              logit_bias=0.0):
     """The top-k items of every user in users_id by sigmoid(user . item): `exclude` items score -1024, `highlight` items
     += 1024 (evaluate.py:94-111), both CSR pairs aligned with users_id.  -> (items int64[n, k], scores fp32[n, k]).
     With user_scale (fp32 [user_num], by user id), item_scale (fp32 [item_num]) or a non-zero shift the ranking score is
-    ((sigmoid(user . item) - shift) * user_scale[user]) * item_scale[item] (predict_topk_scaled; an absent scale is ones)."""
+    ((sigmoid(user . item) - shift) * user_scale[user]) * item_scale[item] (predict_topk_scaled; an absent scale is ones).
+    With dim_weight (fp32, factor_num floats) or a logit_bias (a non-zero number, or an fp32 device tensor of one element) it is sigmoid(sum_d dim_weight_d user_d item_d +
+    logit_bias) (predict_topk_weighted; an absent weight is ones); the two families do not combine."""
     users = users_id.reshape(-1).to(torch.int64).contiguous()
     n, I = users.numel(), item_table.shape[0]
     ut, it = user_table.detach().contiguous(), item_table.detach().contiguous()
     mask, hl = device_csr(exclude, n, I, users.device), device_csr(highlight, n, I, users.device)
-    if user_scale is None and item_scale is None and float(shift) == 0.0:
+    scaled = not (user_scale is None and item_scale is None and float(shift) == 0.0)
+    if dim_weight is not None or isinstance(logit_bias, torch.Tensor) or float(logit_bias) != 0.0:
+        if scaled:
+            raise InvPrefError('recommend: user_scale / item_scale / shift and dim_weight / logit_bias do not combine')
+        w = (torch.ones(ut.shape[1], dtype=torch.float32, device=ut.device) if dim_weight is None else
+             dim_weight.detach().reshape(-1).to(torch.float32).contiguous())
+        items, scores, _ = predict_topk_weighted(ut, it, users, k, w, logit_bias, sigmoid, mask=mask, highlight=hl)
+    elif not scaled:
         items, scores, _ = predict_topk(ut, it, users, k, sigmoid, mask=mask, highlight=hl)
     else:
         us, cs = (torch.ones(t.shape[0], dtype=torch.float32, device=t.device) if s is None else
@@ -699,6 +731,39 @@ def macr_predict(user_table: torch.Tensor, item_table: torch.Tensor, users: torc
     item_branch -> fp32 [n, item_num]"""
     _gpu(user_table, item_table, users, user_branch, item_branch)
     return _o().macr_predict(user_table, item_table, users, user_branch, item_branch, float(const_c))
+
+
+# ---- LinearTrans-MF (baseline_models.py:72-136; include/invpref_lintrans.h, csrc/invpref_lintrans.hip)
+def lintrans_workspace_bytes(user_num: int, item_num: int, batch: int, factor_num: int) -> int:
+    """records + float64 partials of one gradient pass: a function of the sizes alone, non-decreasing in each; 0: not taken"""
+    return int(_capi.lib().invpref_lintrans_workspace_bytes(int(user_num), int(item_num), int(batch), int(factor_num)))
+
+
+def lintrans_grad(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], users: torch.Tensor, items: torch.Tensor,
+                  scores: torch.Tensor, index: Sequence[torch.Tensor], L2_coe: float, L1_coe: float, losses4: torch.Tensor,
+                  workspace: Optional[Workspace] = None) -> None:
+    """The gradient pass of one LinearTrans-MF step.  params / grads: the four tensors in state_dict order (user table, item
+    table, predictor weight [1, D] and bias [1]); index: macr_index's four arrays on the device.  OVERWRITES every row of every
+    gradient (rows without an interaction get zeros) and losses4 = (score_loss, L2_reg, L1_reg, loss); the regularisers cover
+    the predictor.  Bitwise reproducible, no float atomics, no host sync (capturable once the workspace is sized; a replay
+    reads ids and index as they are then).  An id outside its table: the interaction is skipped and the four losses are NaN."""
+    _gpu(users, items, scores, losses4, *params, *grads, *index)
+    P, Q = params[0], params[1]
+    nbytes = lintrans_workspace_bytes(P.shape[0], Q.shape[0], users.numel(), P.shape[1])
+    if nbytes == 0:
+        raise InvPrefError(f'lintrans_grad: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
+                           f'{users.numel()} interactions)')
+    ws = (workspace or Workspace(P.device)).get(nbytes)
+    _o().lintrans_grad_(P, Q, params[2], params[3], users, items, scores, *index, float(L2_coe), float(L1_coe), *grads,
+                        losses4, ws)
+
+
+def lintrans_predict(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, weight: torch.Tensor,
+                     bias: torch.Tensor, sigmoid: bool = True) -> torch.Tensor:
+    """LinearTrans-MF's predict (baseline_models.py:121-136) without its [n item_num, D] temporary:
+    sigmoid(sum_d weight_d Pu[users]_d Qi_d + bias) -> fp32 [n, item_num]; the score predict_topk_weighted ranks by"""
+    _gpu(user_table, item_table, users, weight, bias)
+    return _o().lintrans_predict(user_table, item_table, users, weight, bias, bool(sigmoid))
 
 
 # ---- CausE (baseline_models.py:555-649, :706-794; include/invpref_cause.h, csrc/invpref_cause.hip)
