@@ -620,6 +620,79 @@ class _DrawnTermMixin:
         raise NotImplementedError
 
 
+# ------------------------------------------------------------------------------------------------ own gradient passes
+class _OwnPassMixin:
+    """A step whose gradient pass is the model's own (the MACR, LinearTrans-MF and CausE managers below), in front of a
+    _BasicTrainManager.  Always the engine's unfused sequence: the own pass (one ops.*_grad call: every row of every gradient
+    overwritten, the reported loss terms written into the first slots of the step's losses) -> the dense / ranged Adam over
+    the whole flat state, which holds all the model's tensors.  The minibatches are static, so each one's inverted index
+    (ops.macr_index) is built once on the host and kept on the device; the pass reads ids and index when it runs, and the
+    ranged Adam launch carries the device-side schedule, so whole epochs replay as graphs.  Single process.
+
+    A manager supplies: _SINGLE (the refusal's text), _LOSS_KEYS, _workspace_bytes(), _own_pass(), and, where a caller's
+    minibatch can be one the step must refuse, _check_caller_batch()."""
+    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    _SINGLE = None                  # why the manager runs in a single process
+    _LOSS_KEYS = PURE_LOSS_KEYS     # what the pass writes into the first slots of a step's losses (train.py:399-404)
+    _require_single_process = _DrawnTermMixin._require_single_process
+
+    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, rank=None,
+                 world_size=None, process_group=None):
+        self._require_single_process(world_size)
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        self._require_single_process(self.world_size)
+        self._unfused = True        # gradient pass -> Adam, never the fused / alternating step
+        self._index = None          # per static minibatch: (user_ptr, user_pos, item_ptr, item_pos) on the device
+        self._caller = None         # train_a_batch: (users, items, index) of the caller's minibatch
+        self._ws = ops.Workspace(self.device)
+        self._ws.get(max(self._workspace_bytes(min(batch_size, self.n_total)), 16))   # sized once: capturable launches
+
+    def _workspace_bytes(self, batch: int) -> int:
+        """ops.*_workspace_bytes of the pass over a minibatch of `batch` rows"""
+        raise NotImplementedError
+
+    def _own_pass(self, users, items, scores, index, losses6: torch.Tensor) -> None:
+        """the ops.*_grad call: the gradient of one minibatch into state.g_views, its loss terms into losses6's first slots"""
+        raise NotImplementedError
+
+    def _check_caller_batch(self, batch_users_tensor, batch_items_tensor) -> None:
+        """raises on a caller's minibatch the step cannot take, before anything of it is kept"""
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        if self._index is None:
+            u, v, m = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy(), self.model
+            self._index = [ops.macr_index_device(u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], m.user_num, m.item_num, self.device)
+                           for b in self._raw_batches]
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        if k is None:
+            users, items, index = self._caller
+        else:
+            index = self._index[k]
+        self._own_pass(users, items, scores, index, losses6)
+
+    @classmethod
+    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
+        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.tolist()]
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """train.py:379-405 / baseline_train.py:674-722 on caller tensors: this minibatch's index is built here, then one
+        step."""
+        self._check_caller_batch(batch_users_tensor, batch_items_tensor)
+        dev, m = self.device, self.model
+        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        self._caller = (ud, vd, ops.macr_index_device(ud, vd, m.user_num, m.item_num, dev))
+        try:
+            return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
+        finally:
+            self._caller = None
+
+
 # ------------------------------------------------------------------------------------------------ WMF
 def wmf_distinct(users: np.ndarray, items: np.ndarray, batch_size: int) -> list:
     """per static minibatch of utils.mini_batch (unshuffled slices) the ascending distinct users and items, as torch.unique
@@ -931,27 +1004,32 @@ class LinearImplicitScorePredictor(nn.Module):
                                self.linear_map.bias.detach()).reshape(*x.shape[:-1], 1)
 
 
-class _MACRLoss(torch.autograd.Function):
-    """score_loss of MACR's forward through ops.macr_grad: the pass forms the loss and the gradients of all six tensors at
-    once, backward() scales them by the upstream scalar."""
+class _OwnPassLoss(torch.autograd.Function):
+    """score_loss of a model's forward through its own gradient pass (MACR-MF, LinearTrans-MF): the pass forms the loss and the
+    gradients of all the model's tensors at once, backward() scales them by the upstream scalar.  grad_pass(data, grads, users,
+    items, scores, index, losses4): the model's ops.*_grad call with its coefficients and L2_coe = L1_coe = 0."""
 
     @staticmethod
-    def forward(ctx, users, items, scores, user_coe, item_coe, *tables):
+    def forward(ctx, grad_pass, users, items, scores, *tables):
         data = [t.detach().contiguous() for t in tables]
         dev = data[0].device
         users, items = users.reshape(-1).long().contiguous(), items.reshape(-1).long().contiguous()
-        index = [torch.from_numpy(a).to(dev) for a in ops.macr_index(users, items, data[0].shape[0], data[1].shape[0])]
+        index = ops.macr_index_device(users, items, data[0].shape[0], data[1].shape[0], dev)
         grads = [torch.empty_like(t) for t in data]
         losses = torch.empty(4, dtype=torch.float32, device=dev)
-        ops.macr_grad(data, grads, users, items, scores.detach().reshape(-1).float().contiguous(), index, user_coe, item_coe,
-                      0., 0., losses)
+        grad_pass(data, grads, users, items, scores.detach().reshape(-1).float().contiguous(), index, losses)
         ctx.save_for_backward(*grads)
         return losses[0].clone()
 
     @staticmethod
     def backward(ctx, gs):
         scale = gs.detach().to(torch.float32)
-        return (None, None, None, None, None, *[g * scale for g in ctx.saved_tensors])
+        return (None, None, None, None, *[g * scale for g in ctx.saved_tensors])
+
+
+def _user_ids(users_id, table: torch.Tensor) -> torch.Tensor:
+    """users_id as flat, contiguous int64 on the table's device"""
+    return torch.as_tensor(users_id).to(table.device).reshape(-1).to(torch.int64).contiguous()
 
 
 class MACRMatrixFactorization(nn.Module):
@@ -987,7 +1065,9 @@ class MACRMatrixFactorization(nn.Module):
                 self.user_predictor.linear_map.bias, self.item_predictor.linear_map.weight, self.item_predictor.linear_map.bias]
 
     def forward(self, users_id, items_id, ground_truth):  # baseline_models.py:164-182: the three-branch score loss
-        return _MACRLoss.apply(users_id, items_id, ground_truth, float(self.user_coe), float(self.item_coe), *self.tables())
+        uc, ic = float(self.user_coe), float(self.item_coe)
+        return _OwnPassLoss.apply(lambda data, grads, u, v, y, index, losses: ops.macr_grad(
+            data, grads, u, v, y, index, uc, ic, 0., 0., losses), users_id, items_id, ground_truth, *self.tables())
 
     # PureMF's regularisers over the gathered embedding rows (baseline_models.py:184-208; the predictors are not covered)
     _seven = _PureMFBase._seven
@@ -1003,8 +1083,8 @@ class MACRMatrixFactorization(nn.Module):
 
     def predict(self, users_id):  # baseline_models.py:210-234
         a, c = self.branches()
-        users = torch.as_tensor(users_id).to(self.user_emb.weight.device).reshape(-1).to(torch.int64).contiguous()
-        return ops.macr_predict(self.user_emb.weight.detach(), self.item_emb.weight.detach(), users, a, c, self.const_c)
+        return ops.macr_predict(self.user_emb.weight.detach(), self.item_emb.weight.detach(),
+                                _user_ids(users_id, self.user_emb.weight), a, c, self.const_c)
 
     def rank_fn(self):
         """ImplicitTestManager's fused route: f(users, k, mask, highlight, truth) -> (items, scores, hits) ranking by the
@@ -1025,92 +1105,23 @@ class MACRMatrixFactorization(nn.Module):
                              user_scale=a, item_scale=c, shift=self.const_c)
 
 
-class MACRTrainManager(BasicImplicitTrainManager):
+class MACRTrainManager(_OwnPassMixin, BasicImplicitTrainManager):
     """MACR (baseline/special_bias/macr_mf_main.py) under the reference's plain BasicImplicitTrainManager (train.py:345-461):
-    loss = model(users, items, scores) + L2_coe * L2_reg + L1_coe * L1_reg, Adam over all six tensors.
-
-    Always the engine's unfused sequence: MACR's own gradient pass (ops.macr_grad, csrc/invpref_macr.hip: every row of every
-    gradient overwritten) -> the dense / ranged Adam over the whole flat state, which holds the six tensors.  The minibatches
-    are static, so each one's inverted index is built once on the host and kept on the device; the pass reads ids and index
-    when it runs, and the ranged Adam launch carries the device-side schedule, so whole epochs replay as graphs.  Single
-    process."""
-    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    loss = model(users, items, scores) + L2_coe * L2_reg + L1_coe * L1_reg, Adam over all six tensors.  The own-pass step of
+    _OwnPassMixin on ops.macr_grad (csrc/invpref_macr.hip)."""
     _SINGLE = 'MACR runs in a single process (a sharded form would all-reduce the gradients of all six tensors; not implemented)'
 
-    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
-                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, rank=None,
-                 world_size=None, process_group=None):
-        if world_size is not None and int(world_size) > 1:
-            raise NotImplementedError(self._SINGLE)
-        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
-                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
-        if self.world_size > 1:
-            raise NotImplementedError(self._SINGLE)
-        self._unfused = True        # gradient pass -> Adam, never the fused / alternating step
-        self._macr_index = None     # per static minibatch: (user_ptr, user_pos, item_ptr, item_pos) on the device
-        self._caller = None         # train_a_batch: (users, items, index) of the caller's minibatch
-        self._macr_ws = ops.Workspace(self.device)
-        self._macr_ws.get(max(ops.macr_workspace_bytes(model.user_num, model.item_num, min(batch_size, self.n_total),
-                                                       model.factor_num), 16))   # sized once: capturable launches
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model
+        return ops.macr_workspace_bytes(m.user_num, m.item_num, batch, m.factor_num)
 
-    def _raw_setup(self):
-        super()._raw_setup()
-        if self._macr_index is None:
-            u, v = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy()
-            self._macr_index = [tuple(torch.from_numpy(a).to(self.device) for a in ops.macr_index(
-                u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], self.model.user_num, self.model.item_num)) for b in self._raw_batches]
-
-    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
-                       losses6: torch.Tensor, sched=None) -> None:
+    def _own_pass(self, users, items, scores, index, losses6: torch.Tensor) -> None:
         st, m = self.state, self.model
-        if k is None:
-            users, items, index = self._caller
-        else:
-            index = self._macr_index[k]
         ops.macr_grad(st.p_views, st.g_views, users, items, scores, index, m.user_coe, m.item_coe, self.L2_coe, self.L1_coe,
-                      losses6[:4], self._macr_ws)
-
-    @staticmethod
-    def loss_dicts(dev_losses: torch.Tensor) -> list:
-        """the pass writes the reference's four terms (train.py:399-404) into the first four slots"""
-        return [dict(zip(PURE_LOSS_KEYS, v[:4])) for v in dev_losses.tolist()]
-
-    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
-        """train.py:379-405 on caller tensors: this minibatch's index is built here, then one step."""
-        dev = self.device
-        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
-        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
-        index = tuple(torch.from_numpy(a).to(dev) for a in ops.macr_index(ud, vd, self.model.user_num, self.model.item_num))
-        self._caller = (ud, vd, index)
-        try:
-            return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
-        finally:
-            self._caller = None
+                      losses6[:4], self._ws)
 
 
 # ------------------------------------------------------------------------------------------------ LinearTrans-MF
-class _LinearTransLoss(torch.autograd.Function):
-    """score_loss of LinearTrans-MF's forward through ops.lintrans_grad: the pass forms the loss and the gradients of all four
-    tensors at once, backward() scales them by the upstream scalar."""
-
-    @staticmethod
-    def forward(ctx, users, items, scores, *tables):
-        data = [t.detach().contiguous() for t in tables]
-        dev = data[0].device
-        users, items = users.reshape(-1).long().contiguous(), items.reshape(-1).long().contiguous()
-        index = [torch.from_numpy(a).to(dev) for a in ops.macr_index(users, items, data[0].shape[0], data[1].shape[0])]
-        grads = [torch.empty_like(t) for t in data]
-        losses = torch.empty(4, dtype=torch.float32, device=dev)
-        ops.lintrans_grad(data, grads, users, items, scores.detach().reshape(-1).float().contiguous(), index, 0., 0., losses)
-        ctx.save_for_backward(*grads)
-        return losses[0].clone()
-
-    @staticmethod
-    def backward(ctx, gs):
-        scale = gs.detach().to(torch.float32)
-        return (None, None, None, *[g * scale for g in ctx.saved_tensors])
-
-
 class LinearTransMatrixFactorization(nn.Module):
     """baseline_models.py:72-136: MF whose score is sigmoid(w . (u (*) i) + b) -- InvPref's LinearImplicitScorePredictor over the
     element-wise product of ONE pair of tables: the single-branch ablation of InvPref, trained with its predictor under the plain
@@ -1140,7 +1151,8 @@ class LinearTransMatrixFactorization(nn.Module):
                 self.linear_predictor.linear_map.bias]
 
     def forward(self, users_id, items_id, ground_truth):  # baseline_models.py:87-93: the score loss
-        return _LinearTransLoss.apply(users_id, items_id, ground_truth, *self.tables())
+        return _OwnPassLoss.apply(lambda data, grads, u, v, y, index, losses: ops.lintrans_grad(
+            data, grads, u, v, y, index, 0., 0., losses), users_id, items_id, ground_truth, *self.tables())
 
     # PureMF's regularisers over the gathered embedding rows plus the predictor's own terms (baseline_models.py:95-119,
     # models.py:237-243) -- D + 1 numbers, summed by torch as the reference does; the training pass has them in its kernels
@@ -1164,8 +1176,7 @@ class LinearTransMatrixFactorization(nn.Module):
 
     def predict(self, users_id):  # baseline_models.py:121-136
         P, Q, w, b = self._frozen()
-        users = torch.as_tensor(users_id).to(P.device).reshape(-1).to(torch.int64).contiguous()
-        return ops.lintrans_predict(P, Q, users, w, b)
+        return ops.lintrans_predict(P, Q, _user_ids(users_id, P), w, b)
 
     def rank_fn(self):
         """ImplicitTestManager's fused route: f(users, k, mask, highlight, truth) -> (items, scores, hits) ranking by the
@@ -1184,69 +1195,20 @@ class LinearTransMatrixFactorization(nn.Module):
         return ops.recommend(P, Q, users, k, exclude=exclude, highlight=highlight, dim_weight=w, logit_bias=b)
 
 
-class LinearTransTrainManager(BasicImplicitTrainManager):
+class LinearTransTrainManager(_OwnPassMixin, BasicImplicitTrainManager):
     """LinearTrans-MF under the reference's plain BasicImplicitTrainManager (train.py:345-461):
     loss = model(users, items, scores) + L2_coe * L2_reg + L1_coe * L1_reg with the predictor inside both regularisers, Adam over
-    all four tensors.
-
-    Always the engine's unfused sequence: the model's own gradient pass (ops.lintrans_grad, csrc/invpref_lintrans.hip: every row
-    of every gradient overwritten) -> the dense / ranged Adam over the whole flat state, which holds the four tensors.  The
-    minibatches are static, so each one's inverted index is built once on the host and kept on the device; the pass reads ids
-    and index when it runs, and the ranged Adam launch carries the device-side schedule, so whole epochs replay as graphs.
-    Single process."""
-    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    all four tensors.  The own-pass step of _OwnPassMixin on ops.lintrans_grad (csrc/invpref_lintrans.hip)."""
     _SINGLE = ('LinearTrans-MF runs in a single process (a sharded form would all-reduce the gradients of all four tensors; '
                'not implemented)')
 
-    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
-                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, rank=None,
-                 world_size=None, process_group=None):
-        if world_size is not None and int(world_size) > 1:
-            raise NotImplementedError(self._SINGLE)
-        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
-                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
-        if self.world_size > 1:
-            raise NotImplementedError(self._SINGLE)
-        self._unfused = True        # gradient pass -> Adam, never the fused / alternating step
-        self._lt_index = None       # per static minibatch: (user_ptr, user_pos, item_ptr, item_pos) on the device
-        self._caller = None         # train_a_batch: (users, items, index) of the caller's minibatch
-        self._lt_ws = ops.Workspace(self.device)
-        self._lt_ws.get(max(ops.lintrans_workspace_bytes(model.user_num, model.item_num, min(batch_size, self.n_total),
-                                                         model.factor_num), 16))   # sized once: capturable launches
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model
+        return ops.lintrans_workspace_bytes(m.user_num, m.item_num, batch, m.factor_num)
 
-    def _raw_setup(self):
-        super()._raw_setup()
-        if self._lt_index is None:
-            u, v = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy()
-            self._lt_index = [tuple(torch.from_numpy(a).to(self.device) for a in ops.macr_index(
-                u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], self.model.user_num, self.model.item_num)) for b in self._raw_batches]
-
-    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
-                       losses6: torch.Tensor, sched=None) -> None:
+    def _own_pass(self, users, items, scores, index, losses6: torch.Tensor) -> None:
         st = self.state
-        if k is None:
-            users, items, index = self._caller
-        else:
-            index = self._lt_index[k]
-        ops.lintrans_grad(st.p_views, st.g_views, users, items, scores, index, self.L2_coe, self.L1_coe, losses6[:4],
-                          self._lt_ws)
-
-    @staticmethod
-    def loss_dicts(dev_losses: torch.Tensor) -> list:
-        """the pass writes the reference's four terms (train.py:399-404) into the first four slots"""
-        return [dict(zip(PURE_LOSS_KEYS, v[:4])) for v in dev_losses.tolist()]
-
-    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
-        """train.py:379-405 on caller tensors: this minibatch's index is built here, then one step."""
-        dev = self.device
-        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
-        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
-        index = tuple(torch.from_numpy(a).to(dev) for a in ops.macr_index(ud, vd, self.model.user_num, self.model.item_num))
-        self._caller = (ud, vd, index)
-        try:
-            return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
-        finally:
-            self._caller = None
+        ops.lintrans_grad(st.p_views, st.g_views, users, items, scores, index, self.L2_coe, self.L1_coe, losses6[:4], self._ws)
 
 
 # ------------------------------------------------------------------------------------------------ CausE
@@ -1349,19 +1311,17 @@ class CausEExplicitMatrixFactorization(_CausEModelMixin, PureExplicitMatrixFacto
     implicit = False
 
 
-class _CausEManagerMixin(_UniformMixin):
+class _CausEManagerMixin(_OwnPassMixin, _UniformMixin):
     """CausETrainManager / CausEExplicitTrainManager (baseline_train.py:650-797):
         loss = train_score_loss + uniform_loss_coe * uniform_score_loss + L2_reg + teacher_reg_coe * teacher_reg
     with the student's score loss over the minibatch, the teacher's over the WHOLE uniform set at every step, L2_reg already
     weighted by L2_coe / teacher_L2_coe, and the student pulled towards the detached teacher ('i': item rows, 'u': user rows).
     Adam over all four tables; L1_coe is accepted and unused, like the reference's.
 
-    Always the engine's unfused sequence: CausE's own gradient pass (ops.cause_grad, csrc/invpref_cause.hip: every row of all
-    four gradients overwritten) -> the dense / ranged Adam over the whole flat state.  The minibatches are static, so each
-    one's inverted index is built once on the host and kept on the device, and the uniform set's once in the constructor; the
-    pass reads ids and index when it runs, so whole epochs replay as graphs.  Single process."""
-    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    The own-pass step of _OwnPassMixin on ops.cause_grad (csrc/invpref_cause.hip); the uniform set's inverted index is built
+    once in the constructor."""
     _SINGLE = 'CausE runs in a single process (a sharded form would all-reduce the gradients of all four tables; not implemented)'
+    _LOSS_KEYS = CAUSE_LOSS_KEYS
     _QUIRK = ('the reference\'s implicit CausE model indexes the user table ({U} rows) with item ids in get_items_reg and raises '
               'IndexError on {what} item id {i}; use item ids below user_num')
 
@@ -1371,72 +1331,40 @@ class _CausEManagerMixin(_UniformMixin):
                  teacher_reg_mode: str = 'i', teacher_L2_coe: float = 5., *, rank=None, world_size=None, process_group=None):
         if teacher_reg_mode not in ('i', 'u', 'ui'):
             raise ValueError(f'teacher_reg_mode must be \'i\', \'u\' or \'ui\', got {teacher_reg_mode!r}')
-        if world_size is not None and int(world_size) > 1:
-            raise NotImplementedError(self._SINGLE)
+        self._require_single_process(world_size)
         if uniform_data is None or uniform_data.shape[0] == 0:
             raise ValueError('CausE needs a non-empty uniform set: its teacher trains on all of it at every step')
         if self.implicit:
             self._check_item_ids(model, training_data[:, 1], 'a training')
             self._check_item_ids(model, uniform_data[:, 1], 'a uniform')
+        self._uniform_rows = int(uniform_data.shape[0])      # (the shared constructor sizes the workspace)
         super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
-        if self.world_size > 1:
-            raise NotImplementedError(self._SINGLE)
         self.uniform_loss_coe, self.teacher_reg_coe = uniform_loss_coe, teacher_reg_coe
         self.teacher_reg_mode, self.teacher_L2_coe = teacher_reg_mode, teacher_L2_coe
         self._keep_uniform(uniform_data)
         self.uniform_user, self.uniform_item = self.uniform_user.contiguous(), self.uniform_item.contiguous()
         self.uniform_score = self.uniform_score.contiguous()
-        self._unfused = True         # gradient pass -> Adam, never the fused / alternating step
-        self._cause_index = None     # per static minibatch: (user_ptr, user_pos, item_ptr, item_pos) on the device
-        self._uni_index = tuple(torch.from_numpy(a).to(self.device) for a in ops.macr_index(
-            self.uniform_user, self.uniform_item, model.user_num, model.item_num))
-        self._caller = None          # train_a_batch: (users, items, index) of the caller's minibatch
-        self._cause_ws = ops.Workspace(self.device)
-        self._cause_ws.get(max(ops.cause_workspace_bytes(model.user_num, model.item_num, min(batch_size, self.n_total),
-                                                         self.uniform_user.numel(), model.factor_num), 16))   # sized once
+        self._uni_index = ops.macr_index_device(self.uniform_user, self.uniform_item, model.user_num, model.item_num, self.device)
 
     @classmethod
     def _check_item_ids(cls, model, items, what: str) -> None:
         if items.numel() and int(items.max()) >= model.user_num:
             raise ValueError(cls._QUIRK.format(U=model.user_num, what=what, i=int(items.max())))
 
-    def _raw_setup(self):
-        super()._raw_setup()
-        if self._cause_index is None:
-            u, v = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy()
-            self._cause_index = [tuple(torch.from_numpy(a).to(self.device) for a in ops.macr_index(
-                u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], self.model.user_num, self.model.item_num)) for b in self._raw_batches]
-
-    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
-                       losses6: torch.Tensor, sched=None) -> None:
-        st = self.state
-        if k is None:
-            users, items, index = self._caller
-        else:
-            index = self._cause_index[k]
-        ops.cause_grad(st.p_views, st.g_views, users, items, scores, index, self.uniform_user, self.uniform_item,
-                       self.uniform_score, self._uni_index, self.implicit, self.teacher_reg_mode, self.L2_coe,
-                       self.teacher_L2_coe, self.uniform_loss_coe, self.teacher_reg_coe, losses6[:5], self._cause_ws)
-
-    @staticmethod
-    def loss_dicts(dev_losses: torch.Tensor) -> list:
-        """the pass writes the reference's five terms (baseline_train.py:715-721) into the first five slots"""
-        return [dict(zip(CAUSE_LOSS_KEYS, v[:5])) for v in dev_losses.tolist()]
-
-    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
-        """baseline_train.py:674-722 on caller tensors: this minibatch's index is built here, then one step."""
-        dev = self.device
+    def _check_caller_batch(self, batch_users_tensor, batch_items_tensor) -> None:
         if self.implicit:
             self._check_item_ids(self.model, batch_items_tensor, 'a minibatch')
-        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
-        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
-        index = tuple(torch.from_numpy(a).to(dev) for a in ops.macr_index(ud, vd, self.model.user_num, self.model.item_num))
-        self._caller = (ud, vd, index)
-        try:
-            return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
-        finally:
-            self._caller = None
+
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model
+        return ops.cause_workspace_bytes(m.user_num, m.item_num, batch, self._uniform_rows, m.factor_num)
+
+    def _own_pass(self, users, items, scores, index, losses6: torch.Tensor) -> None:
+        st = self.state
+        ops.cause_grad(st.p_views, st.g_views, users, items, scores, index, self.uniform_user, self.uniform_item,
+                       self.uniform_score, self._uni_index, self.implicit, self.teacher_reg_mode, self.L2_coe,
+                       self.teacher_L2_coe, self.uniform_loss_coe, self.teacher_reg_coe, losses6[:5], self._ws)
 
 
 class CausETrainManager(_CausEManagerMixin, BasicImplicitTrainManager):

@@ -700,6 +700,23 @@ def macr_index(users, items, user_num: int, item_num: int):
     return tuple(out)
 
 
+def macr_index_device(users, items, user_num: int, item_num: int, device) -> tuple:
+    """macr_index's four arrays, uploaded: what the *_grad passes take as `index`"""
+    return tuple(torch.from_numpy(a).to(device) for a in macr_index(users, items, user_num, item_num))
+
+
+def _pass_workspace(op: str, nbytes_of, workspace: Optional[Workspace], params, users, *tensors, uniform=None) -> torch.Tensor:
+    """How the three *_grad wrappers open: every tensor on the GPU, the workspace grown to the pass's bytes (0: sizes refused)"""
+    _gpu(users, uniform, *tensors, *params)
+    P, Q = params[0], params[1]
+    counts = (users.numel(),) if uniform is None else (users.numel(), uniform.numel())
+    nbytes = nbytes_of(P.shape[0], Q.shape[0], *counts, P.shape[1])
+    if nbytes == 0:
+        raise InvPrefError(f'{op}: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
+                           + (f'{counts[0]} interactions)' if uniform is None else f'{counts[0]} + {counts[1]} positions)'))
+    return (workspace or Workspace(P.device)).get(nbytes)
+
+
 def macr_grad(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], users: torch.Tensor, items: torch.Tensor,
               scores: torch.Tensor, index: Sequence[torch.Tensor], user_coe: float, item_coe: float, L2_coe: float,
               L1_coe: float, losses4: torch.Tensor, workspace: Optional[Workspace] = None) -> None:
@@ -708,15 +725,9 @@ def macr_grad(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], use
     every row of every gradient (rows without an interaction get zeros) and losses4 = (score_loss, L2_reg, L1_reg, loss).
     Bitwise reproducible, no float atomics, no host sync (capturable once the workspace is sized; a replay reads ids and
     index as they are then).  An id outside its table: the interaction is skipped and the four losses are NaN."""
-    _gpu(users, items, scores, losses4, *params, *grads, *index)
-    P, Q = params[0], params[1]
-    nbytes = macr_workspace_bytes(P.shape[0], Q.shape[0], users.numel(), P.shape[1])
-    if nbytes == 0:
-        raise InvPrefError(f'macr_grad: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
-                           f'{users.numel()} interactions)')
-    ws = (workspace or Workspace(P.device)).get(nbytes)
-    _o().macr_grad_(P, Q, params[2], params[3], params[4], params[5], users, items, scores, *index, float(user_coe),
-                    float(item_coe), float(L2_coe), float(L1_coe), *grads, losses4, ws)
+    ws = _pass_workspace('macr_grad', macr_workspace_bytes, workspace, params, users, items, scores, losses4, *grads, *index)
+    _o().macr_grad_(*params, users, items, scores, *index, float(user_coe), float(item_coe), float(L2_coe), float(L1_coe),
+                    *grads, losses4, ws)
 
 
 def macr_branch(table: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -747,15 +758,8 @@ def lintrans_grad(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor],
     gradient (rows without an interaction get zeros) and losses4 = (score_loss, L2_reg, L1_reg, loss); the regularisers cover
     the predictor.  Bitwise reproducible, no float atomics, no host sync (capturable once the workspace is sized; a replay
     reads ids and index as they are then).  An id outside its table: the interaction is skipped and the four losses are NaN."""
-    _gpu(users, items, scores, losses4, *params, *grads, *index)
-    P, Q = params[0], params[1]
-    nbytes = lintrans_workspace_bytes(P.shape[0], Q.shape[0], users.numel(), P.shape[1])
-    if nbytes == 0:
-        raise InvPrefError(f'lintrans_grad: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
-                           f'{users.numel()} interactions)')
-    ws = (workspace or Workspace(P.device)).get(nbytes)
-    _o().lintrans_grad_(P, Q, params[2], params[3], users, items, scores, *index, float(L2_coe), float(L1_coe), *grads,
-                        losses4, ws)
+    ws = _pass_workspace('lintrans_grad', lintrans_workspace_bytes, workspace, params, users, items, scores, losses4, *grads, *index)
+    _o().lintrans_grad_(*params, users, items, scores, *index, float(L2_coe), float(L1_coe), *grads, losses4, ws)
 
 
 def lintrans_predict(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, weight: torch.Tensor,
@@ -788,13 +792,8 @@ def cause_grad(params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor], 
     term indexes the USER tables with the item ids (include/invpref_cause.h).  Bitwise reproducible, no float atomics, no host
     sync (capturable once the workspace is sized; a replay reads ids and index as they are then).  An id outside its table --
     implicit: also an item id >= user_num --: the five losses are NaN."""
-    _gpu(users, items, scores, uni_users, uni_items, uni_scores, losses5, *params4, *grads4, *index, *uni_index)
-    P, Q = params4[0], params4[1]
-    nbytes = cause_workspace_bytes(P.shape[0], Q.shape[0], users.numel(), uni_users.numel(), P.shape[1])
-    if nbytes == 0:
-        raise InvPrefError(f'cause_grad: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
-                           f'{users.numel()} + {uni_users.numel()} positions)')
-    ws = (workspace or Workspace(P.device)).get(nbytes)
+    ws = _pass_workspace('cause_grad', cause_workspace_bytes, workspace, params4, users, items, scores, uni_items, uni_scores,
+                         losses5, *grads4, *index, *uni_index, uniform=uni_users)
     _o().cause_grad_(*params4, users, items, scores, *index, uni_users, uni_items, uni_scores, *uni_index, bool(implicit),
                      CAUSE_MODES[mode] if isinstance(mode, str) else int(mode), float(L2_coe), float(teacher_L2_coe),
                      float(uniform_loss_coe), float(teacher_reg_coe), *grads4, losses5, ws)

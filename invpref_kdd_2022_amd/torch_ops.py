@@ -772,6 +772,29 @@ def _pair_tables(op, user_table, item_table, grad_user=None, grad_item=None, out
     return U, I, D
 
 
+def _indexed_batch(n, U, I, users, items, scores, user_ptr, user_pos, item_ptr, item_pos, pre=''):
+    """The checks of one batch of n (user, item, score) positions and its inverted index (ops.macr_index) over tables of U and I
+    rows; pre: the prefix of the arguments' names"""
+    for t, dtype, name, rows in ((users, torch.int64, 'users', n), (items, torch.int64, 'items', n),
+                                 (scores, torch.float32, 'scores', n), (user_ptr, torch.int32, 'user_ptr', U + 1),
+                                 (item_ptr, torch.int32, 'item_ptr', I + 1), (user_pos, torch.int32, 'user_pos', n),
+                                 (item_pos, torch.int32, 'item_pos', n)):
+        _req(t, dtype, pre + name, (rows,))
+
+
+def _weight_bias(op, D, weight, bias, weight_name='weight', bias_name='bias'):
+    """The checks of a linear predictor (or its gradient): a weight of D floats and a bias of one"""
+    _f32(weight, weight_name)
+    _f32(bias, bias_name)
+    if weight.numel() != D or bias.numel() != 1:
+        raise InvPrefError(f'{op}: {weight_name} holds factor_num = {D} floats and {bias_name} one')
+
+
+def _score_matrix(users, item_table):
+    """The [n, item_num] fp32 result of a predict operator, uninitialised: what its implementation fills and its fake returns"""
+    return torch.empty(users.numel(), item_table.shape[0], dtype=torch.float32, device=users.device)
+
+
 def _expo_pass(user_table, item_table, users, n_users, mu, lam_y, eps, a, b, mu_out, prob_out, ws):
     U, I, D = _pair_tables('exposure', user_table, item_table, workspace=ws)
     _f32(mu, 'mu')

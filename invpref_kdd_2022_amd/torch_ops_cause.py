@@ -36,16 +36,8 @@ def _cause_grad(user_table, item_table, teacher_user_table, teacher_item_table, 
                        (teacher_item_table, 'teacher_item_table', I), (grad_teacher_item, 'grad_teacher_item', I)):
         _req(t, torch.float32, n, (rows, D))
     B, Nu = users.numel(), uni_users.numel()
-    for pre, n, ids_u, ids_i, y, up, upos, ip, ipos in (
-            ('', B, users, items, scores, user_ptr, user_pos, item_ptr, item_pos),
-            ('uni_', Nu, uni_users, uni_items, uni_scores, uni_user_ptr, uni_user_pos, uni_item_ptr, uni_item_pos)):
-        _req(ids_u, torch.int64, pre + 'users', (n,))
-        _req(ids_i, torch.int64, pre + 'items', (n,))
-        _req(y, torch.float32, pre + 'scores', (n,))
-        _req(up, torch.int32, pre + 'user_ptr', (U + 1,))
-        _req(ip, torch.int32, pre + 'item_ptr', (I + 1,))
-        _req(upos, torch.int32, pre + 'user_pos', (n,))
-        _req(ipos, torch.int32, pre + 'item_pos', (n,))
+    torch_ops._indexed_batch(B, U, I, users, items, scores, user_ptr, user_pos, item_ptr, item_pos)
+    torch_ops._indexed_batch(Nu, U, I, uni_users, uni_items, uni_scores, uni_user_ptr, uni_user_pos, uni_item_ptr, uni_item_pos, 'uni_')
     _req(losses5, torch.float32, 'losses5', (5,))
     call('invpref_cause_grad_hip', ptr(user_table), ptr(item_table), ptr(teacher_user_table), ptr(teacher_item_table), U, I, D,
          ptr(users), ptr(items), ptr(scores), B, ptr(user_ptr), ptr(user_pos), ptr(item_ptr), ptr(item_pos), ptr(uni_users),

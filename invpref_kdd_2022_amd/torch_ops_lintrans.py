@@ -28,27 +28,14 @@ _define('lintrans_grad_(Tensor user_table, Tensor item_table, Tensor weight, Ten
         'Tensor(f!) workspace) -> ()')
 
 
-def _predictor(op, D, weight, bias):
-    _req(weight, torch.float32, 'weight')
-    _req(bias, torch.float32, 'bias')
-    if weight.numel() != D or bias.numel() != 1:
-        raise InvPrefError(f'{op}: weight holds factor_num = {D} floats and bias one')
-
-
 @_impl('lintrans_grad_')
 def _lintrans_grad(user_table, item_table, weight, bias, users, items, scores, user_ptr, user_pos, item_ptr, item_pos, L2_coe,
                    L1_coe, grad_user, grad_item, grad_weight, grad_bias, losses4, workspace):
     U, I, D = torch_ops._pair_tables('lintrans_grad', user_table, item_table, grad_user, grad_item, workspace=workspace)
     B = users.numel()
-    _predictor('lintrans_grad', D, weight, bias)
-    _predictor('lintrans_grad (gradients)', D, grad_weight, grad_bias)
-    _req(users, torch.int64, 'users', (B,))
-    _req(items, torch.int64, 'items', (B,))
-    _req(scores, torch.float32, 'scores', (B,))
-    _req(user_ptr, torch.int32, 'user_ptr', (U + 1,))
-    _req(item_ptr, torch.int32, 'item_ptr', (I + 1,))
-    _req(user_pos, torch.int32, 'user_pos', (B,))
-    _req(item_pos, torch.int32, 'item_pos', (B,))
+    torch_ops._weight_bias('lintrans_grad', D, weight, bias)
+    torch_ops._weight_bias('lintrans_grad', D, grad_weight, grad_bias, 'grad_weight', 'grad_bias')
+    torch_ops._indexed_batch(B, U, I, users, items, scores, user_ptr, user_pos, item_ptr, item_pos)
     _req(losses4, torch.float32, 'losses4', (4,))
     call('invpref_lintrans_grad_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(weight), ptr(bias), ptr(users), ptr(items),
          ptr(scores), B, ptr(user_ptr), ptr(user_pos), ptr(item_ptr), ptr(item_pos), float(L2_coe), float(L1_coe),
@@ -60,29 +47,20 @@ _define('lintrans_predict(Tensor user_table, Tensor item_table, Tensor users, Te
         '-> Tensor')
 
 
-def _tables(op, user_table, item_table):
-    _req(user_table, torch.float32, 'user_table')
-    _req(item_table, torch.float32, 'item_table')
-    if user_table.dim() != 2 or item_table.dim() != 2 or user_table.shape[1] != item_table.shape[1]:
-        raise InvPrefError(f'{op}: user_table [U, D] and item_table [I, D] must share D')
-    return item_table.shape
-
-
 @_impl('lintrans_predict')
 def _lintrans_predict(user_table, item_table, users, weight, bias, sigmoid):
-    I, D = _tables('lintrans_predict', user_table, item_table)
-    _predictor('lintrans_predict', D, weight, bias)
+    _, I, D = torch_ops._pair_tables('lintrans_predict', user_table, item_table)
+    torch_ops._weight_bias('lintrans_predict', D, weight, bias)
     _req(users, torch.int64, 'users')
-    n = users.numel()
-    out = torch.empty(n, I, dtype=torch.float32, device=users.device)
-    call('invpref_lintrans_predict_hip', ptr(user_table), ptr(item_table), ptr(users), n, I, D, ptr(weight), ptr(bias),
+    out = torch_ops._score_matrix(users, item_table)
+    call('invpref_lintrans_predict_hip', ptr(user_table), ptr(item_table), ptr(users), users.numel(), I, D, ptr(weight), ptr(bias),
          int(bool(sigmoid)), ptr(out), stream_ptr())
     return out
 
 
 @_fake('lintrans_predict')
 def _lintrans_predict_fake(user_table, item_table, users, weight, bias, sigmoid):
-    return torch.empty(users.numel(), item_table.shape[0], dtype=torch.float32, device=users.device)
+    return torch_ops._score_matrix(users, item_table)
 
 
 _ARGS = ('(Tensor user_table, Tensor item_table, Tensor users, int k, bool sigmoid, Tensor? mask_ptr, Tensor? mask_items, '
@@ -96,7 +74,7 @@ def _weighted(name: str, entry: str, workspace_bytes: str):
 
     def impl(user_table, item_table, users, k, sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr,
              truth_items, dim_weight, logit_bias):
-        I, D = _tables(name, user_table, item_table)
+        _, I, D = torch_ops._pair_tables(name, user_table, item_table)
         n = users.numel()
         _req(dim_weight, torch.float32, 'dim_weight')
         _req(logit_bias, torch.float32, 'logit_bias')

@@ -31,23 +31,10 @@ def _macr_grad(user_table, item_table, user_w, user_b, item_w, item_b, users, it
                grad_item_b, losses4, workspace):
     U, I, D = torch_ops._pair_tables('macr_grad', user_table, item_table, grad_user, grad_item, workspace=workspace)
     B = users.numel()
-    for t, g, n in ((user_w, grad_user_w, 'user_w'), (item_w, grad_item_w, 'item_w')):
-        _req(t, torch.float32, n)
-        _req(g, torch.float32, 'grad_' + n)
-        if t.numel() != D or g.numel() != D:
-            raise InvPrefError(f'macr_grad: {n} and its gradient hold factor_num = {D} floats')
-    for t, g, n in ((user_b, grad_user_b, 'user_b'), (item_b, grad_item_b, 'item_b')):
-        _req(t, torch.float32, n)
-        _req(g, torch.float32, 'grad_' + n)
-        if t.numel() != 1 or g.numel() != 1:
-            raise InvPrefError(f'macr_grad: {n} and its gradient hold one float')
-    _req(users, torch.int64, 'users', (B,))
-    _req(items, torch.int64, 'items', (B,))
-    _req(scores, torch.float32, 'scores', (B,))
-    _req(user_ptr, torch.int32, 'user_ptr', (U + 1,))
-    _req(item_ptr, torch.int32, 'item_ptr', (I + 1,))
-    _req(user_pos, torch.int32, 'user_pos', (B,))
-    _req(item_pos, torch.int32, 'item_pos', (B,))
+    for w, b, n in ((user_w, user_b, 'user'), (item_w, item_b, 'item'), (grad_user_w, grad_user_b, 'grad_user'),
+                    (grad_item_w, grad_item_b, 'grad_item')):
+        torch_ops._weight_bias('macr_grad', D, w, b, n + '_w', n + '_b')
+    torch_ops._indexed_batch(B, U, I, users, items, scores, user_ptr, user_pos, item_ptr, item_pos)
     _req(losses4, torch.float32, 'losses4', (4,))
     call('invpref_macr_grad_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(user_w), ptr(user_b), ptr(item_w), ptr(item_b),
          ptr(users), ptr(items), ptr(scores), B, ptr(user_ptr), ptr(user_pos), ptr(item_ptr), ptr(item_pos), float(user_coe),
@@ -81,21 +68,16 @@ _define('macr_predict(Tensor user_table, Tensor item_table, Tensor users, Tensor
 
 @_impl('macr_predict')
 def _macr_predict(user_table, item_table, users, user_branch, item_branch, const_c):
-    _req(user_table, torch.float32, 'user_table')
-    _req(item_table, torch.float32, 'item_table')
-    if user_table.dim() != 2 or item_table.dim() != 2 or user_table.shape[1] != item_table.shape[1]:
-        raise InvPrefError('macr_predict: user_table [U, D] and item_table [I, D] must share D')
-    (U, D), I = user_table.shape, item_table.shape[0]
+    U, I, D = torch_ops._pair_tables('macr_predict', user_table, item_table)
     _req(users, torch.int64, 'users')
     _req(user_branch, torch.float32, 'user_branch', (U,))
     _req(item_branch, torch.float32, 'item_branch', (I,))
-    n = users.numel()
-    out = torch.empty(n, I, dtype=torch.float32, device=users.device)
-    call('invpref_macr_predict_hip', ptr(user_table), ptr(item_table), ptr(users), n, I, D, ptr(user_branch), ptr(item_branch),
-         float(const_c), ptr(out), stream_ptr())
+    out = torch_ops._score_matrix(users, item_table)
+    call('invpref_macr_predict_hip', ptr(user_table), ptr(item_table), ptr(users), users.numel(), I, D, ptr(user_branch),
+         ptr(item_branch), float(const_c), ptr(out), stream_ptr())
     return out
 
 
 @_fake('macr_predict')
 def _macr_predict_fake(user_table, item_table, users, user_branch, item_branch, const_c):
-    return torch.empty(users.numel(), item_table.shape[0], dtype=torch.float32, device=users.device)
+    return torch_ops._score_matrix(users, item_table)

@@ -15,6 +15,7 @@ Trajectories use the g7 data of pure_mf_fixture (400 x 250, 12 000 rows, 6 epoch
 tables and a seeded uniform set of a few hundred rows."""
 import numpy as np
 
+from loss64 import bce as _bce, dbce as _dbce, sigmoid as _sigmoid
 from pure_mf_fixture import pure_mf_inputs
 from wmf_fixture import Adam64, caller_pairs  # noqa: F401  (shared with the generator and the tests)
 
@@ -95,20 +96,6 @@ def block_coes(tag):
 
 
 # ---------------------------------------------------------------------------------------------- float64 statement
-def _sigmoid(x):
-    with np.errstate(over='ignore'):
-        return 1.0 / (1.0 + np.exp(-x))
-
-
-def _bce(p, y):
-    with np.errstate(divide='ignore'):
-        return -(y * np.maximum(np.log(p), -100.0) + (1.0 - y) * np.maximum(np.log1p(-p), -100.0))
-
-
-def _dbce(p, y):
-    return (p - y) / np.maximum(p * (1.0 - p), 1e-12)
-
-
 def as64(params):
     """the four tables as float64 copies, in PARAM_KEYS order"""
     return [np.array(params[k], np.float64) for k in PARAM_KEYS]

@@ -17,6 +17,7 @@ to fp32 once, everything else float64): at |argument| = 30 and beyond, an fp32 s
 gradient, which is the behaviour the block pins."""
 import numpy as np
 
+from loss64 import bce as _bce, dbce as _dbce, sigmoid as _sigmoid
 from pure_mf_fixture import pure_mf_inputs
 from wmf_fixture import Adam64, caller_pairs  # noqa: F401  (shared with the generator and the tests)
 
@@ -100,21 +101,6 @@ def predict_case():
 
 
 # ---------------------------------------------------------------------------------------------- float64 statement
-def _sigmoid(x, f32=False):
-    with np.errstate(over='ignore'):
-        s = 1.0 / (1.0 + np.exp(-x))
-    return s.astype(np.float32).astype(np.float64) if f32 else s
-
-
-def _bce(p, y):
-    with np.errstate(divide='ignore'):
-        return -(y * np.maximum(np.log(p), -100.0) + (1.0 - y) * np.maximum(np.log1p(-p), -100.0))
-
-
-def _dbce(p, y):
-    return (p - y) / np.maximum(p * (1.0 - p), 1e-12)
-
-
 def as64(params):
     """the six tensors as float64 copies, in PARAM_KEYS order"""
     return [np.array(params[k], np.float64) for k in PARAM_KEYS]

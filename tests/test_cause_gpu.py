@@ -405,6 +405,28 @@ def test_train_a_batch_caller_pairs(monkeypatch, name):
             mgr.train_a_batch(t(pairs[:, 0]), t(pairs[:, 1]) + 400, t(pairs[:, 2]).float())
 
 
+def test_train_a_batch_refusal_leaves_the_manager_usable():
+    """The implicit manager refuses a caller's minibatch with an item id >= user_num before anything of it is kept: no step is
+    counted, no caller index stays behind, and the next train_a_batch gives the bits of a manager that never refused one
+    ('driver': the smallest implicit case)."""
+    name = 'driver'
+    pairs = _golden(name)[0]['pairs'].astype(np.int64)
+    batch = t(pairs[:, 0]), t(pairs[:, 1]), t(pairs[:, 2]).float()
+    out = []
+    for refuse in (True, False):
+        mgr, model = _manager(name)
+        if refuse:
+            with pytest.raises(ValueError, match='IndexError'):
+                mgr.train_a_batch(batch[0], batch[1] + 400, batch[2])
+            assert mgr._caller is None and mgr.state.step == 0
+        d = mgr.train_a_batch(*batch)
+        assert mgr._caller is None and mgr.state.step == 1
+        out.append((d, _tensors(model)))
+    assert out[0][0] == out[1][0]
+    for k in PARAM_KEYS:
+        np.testing.assert_array_equal(out[0][1][k], out[1][1][k])
+
+
 def test_teacher_is_independent_of_the_training_set():
     """two training sets of the same size, one uniform set: the teacher tables after two epochs are bit-identical (the
     teacher's gradient and Adam state see the uniform set only), the student tables are not"""

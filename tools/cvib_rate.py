@@ -24,42 +24,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
-WINDOWS = 7
+from rate_common import Stub, plain_unfused, save, timed_us  # noqa: E402
+
 HBM_BYTES_PER_S = 8e12
 # name: (user_num, item_num, D, minibatch, interactions, epochs per timed run, time limit of the child in seconds)
 SHAPES = {'yahoo': (15400, 1000, 64, 8192, None, 8, 240), 'mind': (50000, 51283, 256, 262144, 1 << 22, 2, 420),
           'coat': (290, 300, 30, 1024, 6960, 8, 180)}
 
 
-class Stub:
-    batch_size = 2048
-
-    def evaluate(self):
-        return {}
-
-
-def timed_us(fn, reps):
-    """us per call: [median, min, max] over WINDOWS windows of `reps` calls between two HIP events"""
-    import torch
-    for _ in range(max(2, reps // 4)):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(WINDOWS):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return [float(np.median(out)), float(min(out)), float(max(out))]
-
-
 def measure(name):
     import torch
     from invpref_kdd_2022_amd import ops, synth
-    from invpref_kdd_2022_amd.baseline import BasicImplicitTrainManager, CVIBTrainManager, PureMatrixFactorization, cvib_draw
+    from invpref_kdd_2022_amd.baseline import CVIBTrainManager, PureMatrixFactorization, cvib_draw
     DEV = torch.device('cuda:0')
     U, I, D, bs, n, n_ep, _ = SHAPES[name]
     data = synth.yahoo_like() if n is None else synth.interactions(5, U, I, n, implicit=True)
@@ -108,11 +84,7 @@ def measure(name):
         if variant == 'cvib':
             mgr = CVIBTrainManager(PureMatrixFactorization(U, I, D), *args)
         else:
-            os.environ['INVPREF_FORCE_SHARDED_PATH'] = '1'
-            try:
-                mgr = BasicImplicitTrainManager(PureMatrixFactorization(U, I, D), *args)
-            finally:
-                del os.environ['INVPREF_FORCE_SHARDED_PATH']
+            mgr = plain_unfused(PureMatrixFactorization(U, I, D), *args)
         mgr.train_epochs(2)
         mgr.prepare_graphs([n_ep])
         t = timed_us(lambda: mgr.train_epochs(n_ep, sync=False), 3)
@@ -163,10 +135,7 @@ def main():
         line = [ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1]
         print(line, flush=True)
         out.append(json.loads(line))
-    if len(sys.argv) > 1:
-        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
-        with open(sys.argv[1], 'w') as fh:
-            json.dump(out, fh, indent=1)
+    save(out)
 
 
 if __name__ == '__main__':

@@ -10,30 +10,19 @@ minibatch 32 768, 2^22 synthetic interactions; baseline/special_bias/expomf_main
   - the peak device memory growth of an ExpoMF train() next to U * I * 4 bytes.
 Kernel times: run it again under `rocprofv3 --kernel-trace --stats`.
 Usage: python tools/expomf_rate.py [out.json]"""
-import json
-import os
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-from invpref_kdd_2022_amd import ops, synth  # noqa: E402
-from invpref_kdd_2022_amd.baseline import BasicImplicitTrainManager, ExpoMFTrainManager, ExposureMatrixFactorization  # noqa: E402
+from rate_common import DEV, Stub, report, save
+from invpref_kdd_2022_amd import ops, synth
+from invpref_kdd_2022_amd.baseline import BasicImplicitTrainManager, ExpoMFTrainManager, ExposureMatrixFactorization
 
-DEV = torch.device('cuda:0')
 MFMA_FLOPS = 157.3e12      # MI355X fp32 matrix peak
 VALU_LANE_OPS = 39.3e12    # 256 CUs x 4 SIMD x 16 lanes x 2.4 GHz
 VALU_PER_ENTRY = 54        # VALU instructions per (user, item) entry in the pass's epilogue (device listing, D <= 64)
 INTERVAL = 10
-
-
-class Stub:
-    batch_size = 2048
-
-    def evaluate(self):
-        return {}
 
 
 def best_ms(fn, reps, tries=5):
@@ -124,12 +113,8 @@ def main():
     for label, data, U, I, D, bs, n_ep in (('yahoo', y, 15400, 1000, 64, 8192, 20),
                                            ('mind_expomf_driver', mind, M['user_num'], M['item_num'], 40, 32768, 10)):
         for r in (kernels(label, data, U, I, D), epochs(label, data, U, I, D, bs, n_ep)):
-            print(json.dumps(r), flush=True)
-            res.append(r)
-    if len(sys.argv) > 1:
-        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
-        with open(sys.argv[1], 'w') as fh:
-            json.dump(res, fh, indent=1)
+            report(res, r)
+    save(res)
 
 
 if __name__ == '__main__':

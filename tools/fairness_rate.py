@@ -12,46 +12,17 @@
 Every figure: HIP events around `reps` calls after a warm-up, WINDOWS windows, median and [min, max] over the windows.
 Kernel times proper: run it again under `rocprofv3 --kernel-trace --stats`.
 Usage: python tools/fairness_rate.py [out.json]"""
-import json
-import os
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-from invpref_kdd_2022_amd import ops, synth  # noqa: E402
-from invpref_kdd_2022_amd.baseline import (BasicImplicitTrainManager, FairnessMFTrainManager, PureMatrixFactorization,  # noqa: E402
+from rate_common import DEV, Stub, plain_unfused, report, save, timed_us, torch_step_cost
+from invpref_kdd_2022_amd import ops, synth
+from invpref_kdd_2022_amd.baseline import (FairnessMFTrainManager, PureMatrixFactorization,
                                            fairness_draw, fairness_item_table)
 
-DEV = torch.device('cuda:0')
 MFMA_FLOPS = 157.3e12      # MI355X fp32 matrix peak
-WINDOWS = 7
-
-
-class Stub:
-    batch_size = 2048
-
-    def evaluate(self):
-        return {}
-
-
-def timed_us(fn, reps):
-    """us per call: [median, min, max] over WINDOWS windows of `reps` calls between two HIP events"""
-    for _ in range(max(2, reps // 4)):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(WINDOWS):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return [float(np.median(out)), float(min(out)), float(max(out))]
 
 
 def kernel_alone(data, U, I, D, bs, J, w):
@@ -91,11 +62,7 @@ def steps(data, U, I, D, bs, J, w, n_epochs):
             mgr = FairnessMFTrainManager(PureMatrixFactorization(U, I, D), *args, fairness_coe=1e-4, weight_smooth_coe=w,
                                          item_batch_size=J)
         else:
-            os.environ['INVPREF_FORCE_SHARDED_PATH'] = '1'
-            try:
-                mgr = BasicImplicitTrainManager(PureMatrixFactorization(U, I, D), *args)
-            finally:
-                del os.environ['INVPREF_FORCE_SHARDED_PATH']
+            mgr = plain_unfused(PureMatrixFactorization(U, I, D), *args)
         mgr.train_epochs(2)
         mgr.prepare_graphs([n_epochs])
         t = timed_us(lambda: mgr.train_epochs(n_epochs, sync=False), 3)
@@ -137,13 +104,7 @@ def torch_reference_step(data, U, I, D, bs, P0, Q0, counts, table, idx):
         loss.backward()
         opt.step()
 
-    step()
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    t = timed_us(step, 5)
-    return dict(torch_step_us=t, torch_item_matrix_resident=resident,
-                torch_step_peak_growth_MiB=(torch.cuda.max_memory_allocated() - base) / 2 ** 20)
+    return dict(torch_item_matrix_resident=resident, **torch_step_cost(step, 5))
 
 
 def main():
@@ -158,12 +119,8 @@ def main():
         r = dict(shape=label, U=U, I=I, D=D, minibatch=bs, **r)
         r.update(steps(data, U, I, D, bs, J, w, n_ep))
         r.update(torch_reference_step(data, U, I, D, bs, P, Q, counts, table, idx))
-        print(json.dumps(r), flush=True)
-        res.append(r)
-    if len(sys.argv) > 1:
-        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
-        with open(sys.argv[1], 'w') as fh:
-            json.dump(res, fh, indent=1)
+        report(res, r)
+    save(res)
 
 
 if __name__ == '__main__':

@@ -3,20 +3,16 @@ microseconds per optimiser step and interactions per second, at the Yahoo shape 
 the one-launch alternating form) and the MIND PureMF shape (50 000 x 51 283, D = 256, 2^22 interactions, minibatch 262 144:
 the wide two-launch form); plus the one-off time to form the weights on the device (counts + propensities [+ SNIPS scaling]).
 Usage: python tools/ips_rate.py [out.json]"""
-import json
-import os
-import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-from invpref_kdd_2022_amd import _capi, ops, synth  # noqa: E402
-from invpref_kdd_2022_amd.baseline import (BasicImplicitTrainManager, IPSBasicTrainManager, PureMatrixFactorization,  # noqa: E402
+from rate_common import DEV, report, save
+from invpref_kdd_2022_amd import _capi, ops, synth
+from invpref_kdd_2022_amd.baseline import (BasicImplicitTrainManager, IPSBasicTrainManager, PureMatrixFactorization,
                                            SNIPSMFTrainManager, basic_pair_propensity_func)
 
-DEV = torch.device('cuda:0')
 
 
 class Stub:
@@ -79,15 +75,10 @@ def main():
                                                ('mind_puremf', mind, M['user_num'], M['item_num'], 256, 262144, 3, 2)):
         for variant in ('plain', 'ips', 'snips'):
             r = rate(label, data, U, I, D, bs, variant, runs, ep)
-            print(json.dumps(r), flush=True)
-            res.append(r)
+            report(res, r)
         f = formation(label, data, U, I, bs)
-        print(json.dumps(f), flush=True)
-        res.append(f)
-    if len(sys.argv) > 1:
-        os.makedirs(os.path.dirname(os.path.abspath(sys.argv[1])), exist_ok=True)
-        with open(sys.argv[1], 'w') as fh:
-            json.dump(res, fh, indent=1)
+        report(res, f)
+    save(res)
 
 
 if __name__ == '__main__':

@@ -15,88 +15,24 @@ and, at the MIND test shape (50 000 test users x 51 283 items, D = 40, top-40, m
 Every figure: HIP events around `reps` calls after a warm-up, WINDOWS windows, median and [min, max] over the windows.
 Kernel times proper: run it again under `rocprofv3 --kernel-trace --stats`.
 Usage: python tools/lintrans_rate.py [out.json] [part ...]     parts: yahoo driver hot_row rank (default: all)"""
-import json
-import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-from invpref_kdd_2022_amd import ops, synth  # noqa: E402
-from invpref_kdd_2022_amd.baseline import (BasicImplicitTrainManager, LinearTransMatrixFactorization,  # noqa: E402
-                                           LinearTransTrainManager, PureMatrixFactorization)
+from rate_common import DEV, Stub, dev, grad_pass_alone, hot_row, report, save, steps, timed_us, torch_step_cost
+from invpref_kdd_2022_amd import ops, synth
+from invpref_kdd_2022_amd.baseline import LinearTransMatrixFactorization, LinearTransTrainManager
 
-DEV = torch.device('cuda:0')
-WINDOWS = 7
 COEFS = (0.01, 0.001)      # L2_coe, L1_coe
 SHAPES = {'yahoo': (64, 8192, 8), 'driver': (40, 4096, 4)}
 RANK = (50000, 51283, 40, 40, 10)     # test users, items, D, k, reps
 
 
-class Stub:
-    batch_size = 2048
-
-    def evaluate(self):
-        return {}
-
-
-def timed_us(fn, reps):
-    """us per call: [median, min, max] over WINDOWS windows of `reps` calls between two HIP events"""
-    for _ in range(max(2, reps // 4)):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(WINDOWS):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return [float(np.median(out)), float(min(out)), float(max(out))]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 def pass_alone(u, v, y, U, I, D):
     torch.manual_seed(0)
-    model = LinearTransMatrixFactorization(U, I, D).to(DEV)
-    P = [p.detach() for p in model.tables()]
-    G = [torch.empty_like(p) for p in P]
-    losses, ws = torch.empty(4, device=DEV), ops.Workspace(DEV)
-    index = [dev(a) for a in ops.macr_index(u, v, U, I)]
-    ud, vd, yd = dev(u.astype(np.int64)), dev(v.astype(np.int64)), dev(y.astype(np.float32))
-    t = timed_us(lambda: ops.lintrans_grad(P, G, ud, vd, yd, index, *COEFS, losses, ws), 100)
-    return dict(grad_pass_us=t, heaviest_user_row=int(np.bincount(u).max()), heaviest_item_row=int(np.bincount(v).max()),
-                workspace_MiB=ops.lintrans_workspace_bytes(U, I, len(u), D) / 2 ** 20), P
-
-
-def steps(data, U, I, D, bs, n_epochs):
-    td = torch.from_numpy(data).to(DEV)
-    args = (Stub(), DEV, td, bs, 10 ** 9, 10 ** 9, 0.005, *COEFS)
-    res = {}
-    for variant in ('plain_unfused', 'lintrans'):
-        torch.manual_seed(0)
-        if variant == 'lintrans':
-            mgr = LinearTransTrainManager(LinearTransMatrixFactorization(U, I, D), *args)
-        else:
-            os.environ['INVPREF_FORCE_SHARDED_PATH'] = '1'
-            try:
-                mgr = BasicImplicitTrainManager(PureMatrixFactorization(U, I, D), *args)
-            finally:
-                del os.environ['INVPREF_FORCE_SHARDED_PATH']
-        mgr.train_epochs(2)
-        mgr.prepare_graphs([n_epochs])
-        t = timed_us(lambda: mgr.train_epochs(n_epochs, sync=False), 3)
-        res[variant + '_step_us'] = [x / (n_epochs * mgr.batch_num) for x in t]
-        res['batch_num'] = mgr.batch_num
-        res['graphs'] = bool(mgr._graphs)
-        del mgr
-    return res
+    return grad_pass_alone(LinearTransMatrixFactorization(U, I, D).to(DEV), lambda P, G, ud, vd, yd, index, losses, ws: ops.lintrans_grad(
+        P, G, ud, vd, yd, index, *COEFS, losses, ws), ops.lintrans_workspace_bytes, u, v, y)
 
 
 def torch_reference_step(u, v, y, D, P0):
@@ -117,21 +53,7 @@ def torch_reference_step(u, v, y, D, P0):
         loss.backward()
         opt.step()
 
-    step()
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    t = timed_us(step, 20)
-    return dict(torch_step_us=t, torch_step_peak_growth_MiB=(torch.cuda.max_memory_allocated() - base) / 2 ** 20)
-
-
-def hot_row():
-    rs = np.random.RandomState(41)
-    U, I, D, B = 60, 70, 40, 4096
-    u, v, y = rs.randint(0, U, B), rs.randint(0, I, B), rs.randint(0, 2, B)
-    v[rs.permutation(B)[:3000]] = 3
-    r, _ = pass_alone(u, v, y, U, I, D)
-    return dict(shape='hot_row_test', U=U, I=I, D=D, minibatch=B, **r)
+    return torch_step_cost(step, 20)
 
 
 def csr(rs, n, I, per_row):
@@ -164,7 +86,6 @@ def rank():
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else None
     parts = sys.argv[2:] or list(SHAPES) + ['hot_row', 'rank']
     res = []
     data = synth.yahoo_like() if any(p in SHAPES for p in parts) else None
@@ -175,16 +96,14 @@ def main():
             u, v, y = data[:bs, 0], data[:bs, 1], data[:bs, 2]
             r, P = pass_alone(u, v, y, U, I, D)
             r = dict(shape=label, U=U, I=I, D=D, minibatch=bs, **r)
-            r.update(steps(data, U, I, D, bs, n_ep))
+            r.update(steps('lintrans', lambda td: LinearTransTrainManager(LinearTransMatrixFactorization(U, I, D), Stub(), DEV,
+                                                                          td, bs, 10 ** 9, 10 ** 9, 0.005, *COEFS),
+                           data, U, I, D, bs, n_ep, 0.005, *COEFS))
             r.update(torch_reference_step(u, v, y, D, P))
         else:
-            r = {'hot_row': hot_row, 'rank': rank}[label]()
-        print(json.dumps(r), flush=True)
-        res.append(r)
-    if out:
-        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        with open(out, 'w') as fh:
-            json.dump(res, fh, indent=1)
+            r = {'hot_row': lambda: hot_row(pass_alone, 60, 70), 'rank': rank}[label]()
+        report(res, r)
+    save(res)
 
 
 if __name__ == '__main__':

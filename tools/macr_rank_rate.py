@@ -13,39 +13,18 @@ Per shape, all enqueued on the device and timed without a read-back:
 Every figure: HIP events around `reps` calls after a warm-up, WINDOWS windows, median and [min, max] over the windows.
 Kernel times proper: run it again under `rocprofv3 --kernel-trace --stats`.
 Usage: python tools/macr_rank_rate.py [out.json] [shape ...]"""
-import json
-import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-from invpref_kdd_2022_amd import ops  # noqa: E402
-from invpref_kdd_2022_amd.baseline import MACRMatrixFactorization  # noqa: E402
-from invpref_kdd_2022_amd.evaluate import ImplicitTestManager  # noqa: E402
+from rate_common import DEV, report, save, timed_us
+from invpref_kdd_2022_amd import ops
+from invpref_kdd_2022_amd.baseline import MACRMatrixFactorization
+from invpref_kdd_2022_amd.evaluate import ImplicitTestManager
 
-DEV = torch.device('cuda:0')
-WINDOWS = 7
 SHAPES = {'driver_test': (5400, 1000, 40, [5], 200), 'mind_k40': (50000, 51283, 40, [40], 10),
           'mind_k100': (50000, 51283, 40, [20, 50, 100], 4)}
-
-
-def timed_us(fn, reps):
-    """us per call: [median, min, max] over WINDOWS windows of `reps` calls between two HIP events"""
-    for _ in range(max(2, reps // 4)):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(WINDOWS):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return [float(np.median(out)), float(min(out)), float(max(out))]
 
 
 def csr(rs, n, I, per_row):
@@ -106,15 +85,10 @@ def shape(label):
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else None
     res = []
     for label in (sys.argv[2:] or list(SHAPES)):
-        res.append(shape(label))
-        print(json.dumps(res[-1]), flush=True)
-    if out:
-        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        with open(out, 'w') as fh:
-            json.dump(res, fh, indent=1)
+        report(res, shape(label))
+    save(res)
 
 
 if __name__ == '__main__':
