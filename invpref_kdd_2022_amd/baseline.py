@@ -25,6 +25,7 @@ import torch
 from torch import nn
 
 from . import _capi, ops
+from . import plan as planlib
 from .train import _InvPrefTrainManager
 
 PURE_LOSS_KEYS = ['score_loss', 'L2_reg', 'L1_reg', 'loss']  # train.py:399-404
@@ -162,7 +163,13 @@ class _BasicTrainManager(_InvPrefTrainManager):
         st.losses6.zero_()
         st.step += 1
         self._sched_synced = False
-        if term is None:
+        if term is None and self._lazy:
+            # lazy Adam (set_lazy_adam): the gradient pass over the touched rows only, then Adam on them
+            rows = self._lazy_batch_rows(u, v)
+            self._gradient_pass(None, planlib.without_streamed_rows(dp), None, None, None, y.to(self.device), weights, len(u),
+                                self._coefs(0.), flags, st.losses6)
+            self._lazy_adam(rows)
+        elif term is None:
             ops.mstep_rows_adam(st.p_views, st.p_views_alt, st.m_views, st.v_views, dp, None, y.to(self.device), weights,
                                 len(u), self._coefs(0.), flags, st.losses6, st.step, self.lr, self.workspace,
                                 pure=True)
@@ -404,6 +411,7 @@ class ExpoMFTrainManager(BasicImplicitTrainManager):
       - the prior update after every epoch is one exposure pass whose epilogue reduces to per-item float64 column sums,
         updating the device buffer mu in place.
     ``exposure_probability`` materialises the reference's matrix from the snapshot on request only."""
+    _lazy_adam_unsupported = 'lazy Adam is not built for ExpoMF, whose posterior and prior passes surround runs of the fused step'
 
     def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
                  evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0,
@@ -532,6 +540,7 @@ class _DrawnTermMixin:
     _WHAT = None                    # what a draw is called in the size check's error
     _draw_default = None            # staticmethod: one step's draw from numpy's global generator
     _ONE_ARRAY = False              # a draw is ONE id array (the pair's second stays empty: lengths (n, 0))
+    _lazy_adam_unsupported = 'the drawn term adds gradient to rows outside the minibatch, which lazy Adam would not update'
 
     def _require_single_process(self, world_size) -> None:
         """called with the constructor's argument before the engine is built, and with the resolved size after"""
@@ -635,6 +644,7 @@ class _OwnPassMixin:
     _SINGLE = None                  # why the manager runs in a single process
     _LOSS_KEYS = PURE_LOSS_KEYS     # what the pass writes into the first slots of a step's losses (train.py:399-404)
     _require_single_process = _DrawnTermMixin._require_single_process
+    _lazy_adam_unsupported = "the model's own gradient pass stores zeros to every idle row: its cost follows the tables"
 
     def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
                  evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, rank=None,

@@ -7,6 +7,7 @@
 // 256-byte global_load_dwordx4 across the 16 lanes, dot products are a per-lane fma chain plus a
 // 4-step DPP butterfly (canon_math.hpp), and no LDS is needed for the reductions.  The E x D
 // environment table and classifier live in LDS for the whole workgroup.
+#include "adam_apply.hpp"
 #include "launch.hpp"
 
 using namespace invpref;
@@ -458,13 +459,7 @@ __global__ __launch_bounds__(1024) void mstep_finish_kernel(DevTables t, DevGrad
 // =====================================================================================
 // dense Adam over a flat buffer (torch.optim.Adam single-tensor rule; train.py:41,155-157)
 // =====================================================================================
-__device__ __forceinline__ void adam_scalar_at(float *p, float *g, float *m, float *v, int64_t i, const AdamScalars &a,
-                                               int zero_grad) {
-    float pp = p[i], mm = m[i], vv = v[i];
-    adam1(pp, g[i], mm, vv, a);
-    p[i] = pp; m[i] = mm; v[i] = vv;
-    if (zero_grad) g[i] = 0.f;
-}
+// (adam_scalar_at / adam_f4_at and the schedule hand-over of a step's last launch: adam_apply.hpp)
 // `head` (0..3, or n for buffers whose addresses are misaligned differently): leading elements handled one
 // float at a time so that the float4 body starts on a 16-byte boundary of all four buffers (a user-sharded
 // rank's row range of a table whose factor_num is not a multiple of 4 starts anywhere)
@@ -507,29 +502,13 @@ __global__ __launch_bounds__(256) void adam_ranges_kernel(float *__restrict__ p,
                                                           float *__restrict__ v, AdamRanges r, AdamScalars a, int zero_grad,
                                                           int *sched_state, const SchedRow *sched_table, int sched_n,
                                                           int sched_slot) {
-    if (sched_state) {
-        a = reinterpret_cast<const SchedRow *>(sched_state + 16 * sched_slot + 2)->ad;
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            const int *cur = sched_state + 16 * sched_slot;
-            int *nxt = sched_state + 16 * (sched_slot ^ 1);
-            const int next = cur[0] + 1, base = cur[1], idx = next - base;
-            nxt[0] = next;
-            nxt[1] = base;
-            if (idx >= 0 && idx < sched_n) *reinterpret_cast<SchedRow *>(nxt + 2) = sched_table[idx];
-        }
-    }
+    if (sched_state) a = sched_last_launch(sched_state, sched_table, sched_n, sched_slot);
     const int64_t total = r.end4[r.n - 1];
     for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < total; j += (int64_t)gridDim.x * blockDim.x) {
         int q = 0;
         while (j >= r.end4[q]) q++;
         const int64_t i = r.off4[q] + (j - (q ? r.end4[q - 1] : 0));
-        float4 pp = reinterpret_cast<float4 *>(p)[i], gg = reinterpret_cast<float4 *>(g)[i];
-        float4 mm = reinterpret_cast<float4 *>(m)[i], vv = reinterpret_cast<float4 *>(v)[i];
-        adam1(pp.x, gg.x, mm.x, vv.x, a); adam1(pp.y, gg.y, mm.y, vv.y, a);
-        adam1(pp.z, gg.z, mm.z, vv.z, a); adam1(pp.w, gg.w, mm.w, vv.w, a);
-        reinterpret_cast<float4 *>(p)[i] = pp; reinterpret_cast<float4 *>(m)[i] = mm;
-        reinterpret_cast<float4 *>(v)[i] = vv;
-        if (zero_grad) reinterpret_cast<float4 *>(g)[i] = f4zero();
+        adam_f4_at(p, g, m, v, i, a, zero_grad);
     }
 }
 

@@ -18,6 +18,7 @@ from . import torch_ops_macr  # noqa: F401  (the MACR fragment: torch.ops.invpre
 from . import torch_ops_cause  # noqa: F401  (the CausE fragment: torch.ops.invpref.cause_grad_)
 from . import torch_ops_scaled  # noqa: F401  (the scaled retrieval's fragment: torch.ops.invpref.predict_topk_scaled*)
 from . import torch_ops_lintrans  # noqa: F401  (the LinearTrans fragment: torch.ops.invpref.lintrans_*, predict_topk_weighted*)
+from . import torch_ops_adam_rows  # noqa: F401  (lazy Adam's fragment: torch.ops.invpref.adam_rows_)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -114,6 +115,19 @@ def adam_ranges_(param, grad, exp_avg, exp_avg_sq, offsets, lengths, step: int, 
     s_state, s_table, s_slot = sched if sched is not None else (None, None, 0)
     _o().adam_ranges_(param, grad, exp_avg, exp_avg_sq, [int(o) for o in offsets], [int(n) for n in lengths], int(step),
                       float(lr), float(beta1), float(beta2), float(eps), bool(zero_grad), s_state, s_table, int(s_slot))
+
+
+def adam_rows_(param, grad, exp_avg, exp_avg_sq, row_offsets: torch.Tensor, D: int, tail_offsets, tail_lengths, step: int,
+               lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, zero_grad: bool = True,
+               vec_ok: bool = True, sched=None) -> None:
+    """lazy Adam: the same rule on the rows `row_offsets` (device int64: first float of each, D floats; strictly increasing, no
+    overlap -- duplicates are undefined) and on up to four (offset, length) tail pieces of the flat buffers, one launch; every
+    other float keeps its bits.  vec_ok: every row offset is a multiple of 4.  sched: as adam_ranges_."""
+    _gpu(param, grad, exp_avg, exp_avg_sq, row_offsets)
+    s_state, s_table, s_slot = sched if sched is not None else (None, None, 0)
+    _o().adam_rows_(param, grad, exp_avg, exp_avg_sq, row_offsets, int(D), [int(o) for o in tail_offsets],
+                    [int(n) for n in tail_lengths], int(step), float(lr), float(beta1), float(beta2), float(eps),
+                    bool(zero_grad), bool(vec_ok), s_state, s_table, int(s_slot))
 
 
 def pack_rows(flat: torch.Tensor, row_offsets: torch.Tensor, D: int, tail_offset: int, tail_len: int, packed: torch.Tensor,

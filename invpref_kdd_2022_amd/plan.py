@@ -635,6 +635,24 @@ def upload(plan: dict, device) -> DevicePlan:
                       torch.tensor(meta, dtype=torch.int64))
 
 
+def without_streamed_rows(dp: DevicePlan) -> DevicePlan:
+    """The same plan with no streamed rows: the jobs of the touched rows only, so that a gradient pass costs what the
+    minibatch touches and writes nothing -- no zeros -- to any other row (lazy Adam, train.py: set_lazy_adam).  The stream list
+    and the per-class stream counts are dropped from the struct and the meta tensor; the device buffer is shared with `dp`."""
+    i, at = 0, {}
+    for name, _ in RowPlanStruct._fields_:
+        at[name] = i
+        i += _ARRAY_FIELDS.get(name, 1)
+    meta = dp.meta.clone()
+    meta[at['n_stream']] = 0
+    cls = meta[at['cls']:at['cls'] + 64].view(8, 8)
+    cls[:, [2, 3, 6, 7]] = 0
+    st = struct_from_meta(dp.buf, meta)
+    tasks = plan_workgroups(dict(n_classes=max(1, st.n_classes), cls=cls.numpy(), user_rounds_per_task=st.user_rounds_per_task,
+                                 item_rounds_per_task=st.item_rounds_per_task, rows_per_stream_task=st.rows_per_stream_task))
+    return DevicePlan(st, dp.arrays, tasks, dp.n_rounds, dp.buf, meta)
+
+
 def _meta_of(st: RowPlanStruct, offs: dict) -> list:
     """the struct as a flat list of integers (array fields expanded), pointers as int32 offsets into the buffer"""
     meta = []

@@ -61,6 +61,21 @@ def _gc_paused():
             gc.enable()
 
 
+def touched_row_offsets(users, items, offsets, user_tabs, item_tabs, D: int):
+    """First float, in the flat buffers, of every row of the user and item tables that a minibatch touches: the sorted unique
+    `offsets[table] + id * D` over the ids in `users` (tables `user_tabs`) and `items` (tables `item_tabs`).  numpy arrays give
+    an int64 numpy array (the static minibatches, listed once on the host); tensors an int64 tensor on their device
+    (caller-supplied minibatches: torch.unique there).  Tables do not overlap, so neither do the rows: what the packed
+    exchange copies and lazy Adam updates."""
+    if isinstance(users, np.ndarray):
+        tu, ti = np.unique(users.astype(np.int64, copy=False)), np.unique(items.astype(np.int64, copy=False))
+        parts = [offsets[i] + tu * D for i in user_tabs] + [offsets[i] + ti * D for i in item_tabs]
+        return np.sort(np.concatenate(parts)).astype(np.int64)
+    tu, ti = torch.unique(users.reshape(-1).long()), torch.unique(items.reshape(-1).long())
+    parts = [offsets[i] + tu * D for i in user_tabs] + [offsets[i] + ti * D for i in item_tabs]
+    return torch.sort(torch.cat(parts)).values.contiguous()
+
+
 class FlatState:
     """params / grads / exp_avg / exp_avg_sq as four flat buffers + per-table views."""
 
@@ -130,6 +145,7 @@ class RawBatch(NamedTuple):
 
 class _InvPrefTrainManager:
     implicit = True
+    _lazy_adam_unsupported = None       # a manager that cannot run lazy Adam names the reason here (set_lazy_adam)
     _pure = False                       # PureMF managers (baseline.py) reuse the epoch engine below
     _make_tables = staticmethod(_capi.make_tables)
 
@@ -270,6 +286,10 @@ class _InvPrefTrainManager:
         self._sched = None
         self._sched_synced = False
         self._alt = None
+        self._lazy = False           # set_lazy_adam()
+        self._alt_parked = None      # the alternating form's plans and workspace while lazy Adam is on
+        self._lazy_consts = None     # the tail of small tensors, the tables' roles and alignment (set_lazy_adam)
+        self._lazy_state = None      # the row lists and plans of the static minibatches under lazy Adam (_lazy_setup)
 
     # ------------------------------------------------------------------ sample weights (train.py:67, :274-278)
     @property
@@ -332,6 +352,20 @@ class _InvPrefTrainManager:
                 lo = min(self.rank * chunk, st.n)
                 self._adam_ranges = [(lo, min(chunk, st.n - lo))] if st.n > lo else []
 
+    def _row_tables(self):
+        """(user tables, item tables, (offset, length) of the flat buffers' tail that holds the small tensors): how the rows a
+        minibatch touches are addressed (touched_row_offsets) -- the packed exchange and lazy Adam"""
+        st = self.state
+        n_tabs = len(st.shapes)
+        user_tabs = self._user_tables
+        item_tabs = tuple(i + 1 for i in user_tabs)                     # (state_dict order: every user table is followed by its item table)
+        big = sorted(user_tabs + item_tabs)
+        small = [i for i in range(n_tabs) if i not in big]
+        if small and min(st.offsets[i] for i in small) < max(st.offsets[i] for i in big):
+            raise ValueError('the small tables must follow the big ones in the flat buffers')
+        tail_off = min((st.offsets[i] for i in small), default=st.n)
+        return user_tabs, item_tabs, (int(tail_off), int(st.n - tail_off))
+
     def _setup_packed(self, users_all, items_all):
         """The packed exchange of a row-sharded run (INVPREF_EXCHANGE=packed): the minibatches are static (utils.mini_batch,
         utils.py:12-19), so the rows of the four big tables that the GLOBAL minibatch k touches -- on any rank -- are known
@@ -344,21 +378,13 @@ class _InvPrefTrainManager:
         st, D = self.state, self.model.factor_num
         u = users_all.cpu().numpy().astype(np.int64)
         v = items_all.cpu().numpy().astype(np.int64)
-        n_tabs = len(st.shapes)
-        user_tabs = self._user_tables
-        item_tabs = tuple(i + 1 for i in user_tabs)                     # (state_dict order: every user table is followed by its item table)
-        big = sorted(user_tabs + item_tabs)
-        small = [i for i in range(n_tabs) if i not in big]
-        if small and min(st.offsets[i] for i in small) < max(st.offsets[i] for i in big):
-            raise ValueError('packed exchange: the small tables must follow the big ones in the flat buffers')
-        tail_off = min((st.offsets[i] for i in small), default=st.n)
-        self._packed_tail = (int(tail_off), int(st.n - tail_off))
+        user_tabs, item_tabs, self._packed_tail = self._row_tables()
+        big = user_tabs + item_tabs
         self._packed_rows, most = [], 0
         for k in range(self.batch_num):
             lo, hi = k * self.batch_size, min((k + 1) * self.batch_size, self.n_total)
-            tu, ti = np.unique(u[lo:hi]), np.unique(v[lo:hi])
-            offs = np.concatenate([st.offsets[i] + tu * D for i in user_tabs] + [st.offsets[i] + ti * D for i in item_tabs])
-            self._packed_rows.append(torch.from_numpy(np.sort(offs).astype(np.int64)).to(self.device))
+            offs = touched_row_offsets(u[lo:hi], v[lo:hi], st.offsets, user_tabs, item_tabs, D)
+            self._packed_rows.append(torch.from_numpy(offs).to(self.device))
             most = max(most, len(offs))
         self._packed_vec = D % 4 == 0 and all(st.offsets[i] % 4 == 0 for i in big)
         self._packed_buf = torch.zeros(most * D + self._packed_tail[1] + 4, dtype=torch.float32, device=self.device)
@@ -403,6 +429,70 @@ class _InvPrefTrainManager:
         """the one exchange of an optimiser step: the shared part of the flat gradient + the loss tail"""
         all_reduce_sum_(self.state.grad_ext[self._ar_lo:], self.process_group)
 
+    # ------------------------------------------------------------------ lazy Adam
+    def set_lazy_adam(self, enabled: bool) -> None:
+        """Opt in to (or out of) lazy Adam at an epoch boundary: an optimiser step updates the rows of the user and item tables
+        whose ids occur in its minibatch, and every element of the small tensors, by the usual rule with the GLOBAL step
+        counter; every other row keeps its parameters and moments bit for bit.  One step is the planned gradient pass over the
+        touched rows followed by ONE torch.ops.invpref.adam_rows_ launch, so its cost follows the minibatch and not the tables
+        (DESIGN.md §4.9).  A lazy step equals a dense step with the untouched rows put back; the trajectory therefore differs
+        from torch.optim.Adam over dense embeddings -- the reference's -- whose untouched rows keep moving on their momentum.
+        Off (the default) nothing changes: the same launches, the same bits.  Switching clears the captured epoch graphs."""
+        enabled = bool(enabled)
+        if enabled:
+            why = self._lazy_adam_unsupported
+            if why is None and (self.world_size > 1 or self._force_sharded_path):
+                why = 'lazy Adam is single-process: a sharded step exchanges and updates whole ranges of the flat buffers'
+            if why is not None:
+                raise NotImplementedError(f'{type(self).__name__}.set_lazy_adam: {why}')
+        if enabled == self._lazy:
+            return
+        if enabled:
+            self._alt_parked = self._alt if self._alt is not None else self._alt_parked
+            if self._grad_stale:
+                # dense unfused steps leave their gradient behind; a lazy step starts from -- and leaves -- an all-zero buffer
+                self.state.grad.zero_()
+                self._grad_stale = False
+        self._lazy = enabled
+        self._graphs.clear()
+        if enabled and self._lazy_consts is None:
+            st, D = self.state, self.model.factor_num
+            user_tabs, item_tabs, tail = self._row_tables()
+            self._lazy_consts = dict(tail=([tail[0]], [tail[1]]) if tail[1] else ([], []), tabs=(user_tabs, item_tabs),
+                                     vec=D % 4 == 0 and all(st.offsets[i] % 4 == 0 for i in user_tabs + item_tabs))
+        if getattr(self, '_raw_ptrs', None) is not None:
+            if enabled:
+                self._lazy_setup()
+            elif self._alt is None:
+                self._alt = self._alt_parked     # (_alt_setup keeps its plans and workspace)
+            self._alt_setup()
+
+    def _lazy_setup(self):
+        """What the static minibatches need under lazy Adam, built once and kept on the device: per minibatch the list of
+        touched row offsets and the row plan WITHOUT streamed rows (the dense plans' device buffers, shared)."""
+        if self._lazy_state is not None and self._lazy_state['plans_of'] is self._plans:
+            return
+        st, D = self.state, self.model.factor_num
+        user_tabs, item_tabs = self._lazy_consts['tabs']
+        u, v = self.users_tensor.cpu().numpy(), self.items_tensor.cpu().numpy()
+        rows = [torch.from_numpy(touched_row_offsets(u[b.lo:b.lo + b.n], v[b.lo:b.lo + b.n], st.offsets, user_tabs, item_tabs,
+                                                     D)).to(self.device) for b in self._raw_batches]
+        self._lazy_state = dict(
+            rows=rows, plans_of=self._plans,
+            plans=None if self._plans is None else [planlib.without_streamed_rows(dp) for dp in self._plans])
+
+    def _lazy_adam(self, rows: torch.Tensor, sched=None) -> None:
+        """the launch that ends a lazy step: Adam on the listed rows and the small tensors, their gradient cleared"""
+        st, L = self.state, self._lazy_consts
+        ops.adam_rows_(st.param, st.grad, st.exp_avg, st.exp_avg_sq, rows, self.model.factor_num, L['tail'][0], L['tail'][1],
+                       st.step, self.lr, zero_grad=True, vec_ok=L['vec'], sched=sched)
+
+    def _lazy_batch_rows(self, users, items) -> torch.Tensor:
+        """the touched row offsets of a caller-supplied minibatch (device tensors or host arrays of ids), on the device"""
+        user_tabs, item_tabs = self._lazy_consts['tabs']
+        dev = lambda x: (torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x.detach()).to(self.device)  # noqa: E731
+        return touched_row_offsets(dev(users), dev(items), self.state.offsets, user_tabs, item_tabs, self.model.factor_num)
+
     # ------------------------------------------------------------------ M-step
     def _coefs(self, alpha):
         return (self.invariant_coe, self.env_aware_coe, self.env_coe, self.L2_coe, self.L1_coe, alpha)
@@ -425,6 +515,9 @@ class _InvPrefTrainManager:
             self._all_reduce_step()
         st.step += 1
         self._sched_synced = False
+        if self._lazy:      # (the plan-free pass ADDED into an all-zero buffer: only the touched rows and the tail hold anything)
+            self._lazy_adam(self._lazy_batch_rows(users, items))
+            return
         for o, n in self._adam_ranges:
             ops.adam_(st.param[o:o + n], st.grad[o:o + n], st.exp_avg[o:o + n], st.exp_avg_sq[o:o + n], st.step, self.lr,
                       zero_grad=True)
@@ -445,7 +538,18 @@ class _InvPrefTrainManager:
             all_reduce_sum_(t, self.process_group)
             bn = int(t.item())
         dp = self._cached_batch_plan(batch_users_tensor, batch_items_tensor, batch_scores_tensor)
-        if dp is not None:
+        if dp is not None and self._lazy:
+            # lazy Adam: the planned gradient pass over the touched rows only, then Adam on them (a minibatch without a plan:
+            # the plan-free pass of _step, which costs what the minibatch touches as it is)
+            st = self.state
+            st.losses6.zero_()
+            st.step += 1
+            self._sched_synced = False
+            self._gradient_pass(None, planlib.without_streamed_rows(dp), None, None, batch_envs_tensor.contiguous(),
+                                batch_scores_tensor.float().contiguous(), batch_sample_weights.contiguous(), bn,
+                                self._coefs(alpha), self._flags, st.losses6)
+            self._lazy_adam(self._lazy_batch_rows(batch_users_tensor, batch_items_tensor))
+        elif dp is not None:
             # the reference's own loop (`for batch in mini_batch(...)`, train.py:204-233) hands over the same slices of
             # the same resident tensors every epoch: from their second sighting they run the planned fused step
             st = self.state
@@ -568,6 +672,8 @@ class _InvPrefTrainManager:
                                               self.model.item_num, **kw) for b in self._raw_batches]
             self._plans = [planlib.upload(pl, self.device) for pl in pls]
             self.plan_build_s = time.perf_counter() - t0     # host-side, once per run (reported by bench.py)
+        if self._lazy:
+            self._lazy_setup()
         self._alt_setup()
         if self.use_plan and self.users_tensor.is_cuda:
             # every plan shares ONE scratch (records + partial slabs; nothing carries over between steps): size it for
@@ -700,7 +806,8 @@ class _InvPrefTrainManager:
             self._sched_synced = False
         b = self._raw_batches[k]
         coefs = self._coefs(alpha)
-        multi = self.world_size > 1 or self._force_sharded_path or self._unfused
+        lazy = self._lazy
+        multi = self.world_size > 1 or self._force_sharded_path or self._unfused or lazy
         # every step's six loss terms go straight into the epoch's loss buffer (this rank's partial sums in a
         # sharded run: they are all-reduced once per epoch, not per step)
         lp = self._epoch_losses[self._loss_slot, k]
@@ -720,15 +827,22 @@ class _InvPrefTrainManager:
         sc = (self._sched['state'], self._sched['table'], st.step & 1) if sched else None
         if self.use_plan:
             wts, flags = self._step_weights(b.weights)
-            self._gradient_pass(k, self._plans[k], b.users, b.items, b.envs, b.scores, wts, b.global_n, coefs, flags, lp, sc)
+            # (lazy Adam: the plan without streamed rows -- the pass writes the touched rows and the small tensors only)
+            plan = self._lazy_state['plans'][k] if lazy else self._plans[k]
+            self._gradient_pass(k, plan, b.users, b.items, b.envs, b.scores, wts, b.global_n, coefs, flags, lp, sc)
         else:
             self._gradient_pass(k, None, b.users, b.items, b.envs, b.scores, b.weights, b.global_n, coefs, self._flags, lp, None)
-        if multi:
+        if multi and not lazy:
             if self.world_size > 1 or self._collective_ok:
                 self._exchange_gradient(k)   # all-reduce (whole or packed), or reduce-scatter (this rank keeps its slice of the sum)
         self._after_gradient_pass(k, lp)
         if mid_event is not None:
             mid_event.record()
+        if lazy:
+            # the buffer was all-zero before the pass and this launch clears exactly what the pass (and the hook) wrote: it is
+            # all-zero again, so _grad_stale never asks for a whole-buffer zero_()
+            self._lazy_adam(self._lazy_state['rows'][k], sched=sc)
+            return
         # the planned gradient pass overwrites every row it is responsible for, so the gradient buffer needs no zeroing
         zero = not self.use_plan
         if self.use_plan:
@@ -916,7 +1030,7 @@ class _InvPrefTrainManager:
 
     def _fused_seq(self) -> bool:
         """one fused M-step + Adam launch per step (single GPU, rows of at most 128 floats), parameters ping-pong"""
-        return self.world_size == 1 and not self._unfused and not self._force_sharded_path
+        return self.world_size == 1 and not self._unfused and not self._force_sharded_path and not self._lazy
 
     def graphs_enabled(self) -> bool:
         """Are whole epochs replayed as HIP graphs?  (after the first, eagerly issued, epoch)"""
