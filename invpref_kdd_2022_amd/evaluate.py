@@ -13,6 +13,8 @@ The hit labels stay on the device: the recall / precision / NDCG sums (evaluate.
 kernels (``csrc/invpref_metrics.hip``) in numpy's float64 order, and the host reads back 3 x n_k doubles.
 ``recall_precision_ndcg`` keeps the numpy statement of the formulas that order is held to.  ``evaluate_async()`` enqueues
 an evaluation without waiting for it (the training loops' deferred mode).
+``ImplicitRankTestManager`` evaluates from the exact rank of every ground-truth item in its user's full ranking
+(``csrc/invpref_truth_rank.hip``): the same three metrics at any k <= item_num, plus AUC, MRR and MAP.
 """
 from __future__ import annotations
 
@@ -199,6 +201,127 @@ class ImplicitTestManager:
 
     def evaluate(self) -> dict:
         return self.evaluate_async().result()
+
+
+class ImplicitRankTestManager(ImplicitTestManager):
+    """Rank-based evaluation: the exact position of every ground-truth item in its user's full ranking
+    (``csrc/invpref_truth_rank.hip``), and from those integers recall / precision / NDCG at ANY k <= item_num plus AUC, MRR and
+    MAP -- no [n, item_num] matrix for the models that rank by sigmoid(user table . item table) (``ops.truth_ranks``); any other
+    model's batch is ``model.predict`` + ``ops.truth_ranks_rows``, in batches bounded as ``ImplicitTestManager._step`` bounds
+    them.  -> {'ndcg': {k: ..}, 'recall': {..}, 'precision': {..}, 'auc': x, 'mrr': x, 'map': x}.  Up to k = 1024 the three
+    dictionaries are ``ImplicitTestManager``'s float for float (the hit labels are rebuilt from the ranks and summed by the same
+    ``rank_metrics`` kernels); beyond, and for auc / mrr / map, the float64 kernel of include/invpref_truth_rank.h.
+    auc counts a user's negatives as the items in neither its truth nor its mask list, which the ranks alone only give when
+    the two lists are disjoint: a user whose lists intersect raises ValueError when the CSR arrays are prepared."""
+
+    def _item_num(self) -> int:
+        tables = self._fused_tables()
+        if tables is not None:
+            return int(tables[1].shape[0])
+        if hasattr(self.model, 'item_num'):
+            return int(self.model.item_num)
+        return int(self.model.predict(self._users[:1].contiguous()).shape[1])
+
+    def _prepare(self, device):
+        from .ops import rank_metric_tables
+        dl = self.data_loader
+        users = list(dl.all_test_users_by_sorted_list)
+        if hasattr(dl, 'csr_for_eval'):
+            ev = dl.csr_for_eval()
+            (mp, mi), (tp, ti) = ev['mask'], ev['truth']
+            if self.use_item_pool:
+                hp, hi = ev['highlight']
+        else:
+            mp, mi = _csr([dl.user_mask_items(u) for u in users])
+            tp, ti = _csr(dl.get_sorted_all_test_users_ground_truth)
+            if self.use_item_pool:
+                hp, hi = _csr([dl.user_highlight_items(u) for u in users])
+        mp, mi, tp, ti = (np.ascontiguousarray(a, np.int32) for a in (mp, mi, tp, ti))
+        n = len(users)
+        if tp[0] != 0 or mp[0] != 0:
+            tp, ti, mp, mi = tp - tp[0], ti[tp[0]:], mp - mp[0], mi[mp[0]:]
+        stride = int(max(ti.max(initial=0), mi.max(initial=0))) + 1
+        rows = lambda p: np.repeat(np.arange(n, dtype=np.int64), np.diff(p))  # noqa: E731
+        both = np.intersect1d(rows(tp) * stride + ti[:tp[n]], rows(mp) * stride + mi[:mp[n]])
+        if both.size:
+            raise ValueError(f'test user {users[int(both[0] // stride)]}: item {int(both[0] % stride)} is in both the ground '
+                             'truth and the mask list; AUC from ranks needs the two lists disjoint')
+        arrs = dict(mask_ptr=mp, mask_items=mi, truth_ptr=tp, truth_items=ti)
+        if self.use_item_pool:
+            arrs.update(hl_ptr=np.ascontiguousarray(hp, np.int32), hl_items=np.ascontiguousarray(hi, np.int32))
+        self._dev = {k: torch.from_numpy(v).to(device) for k, v in arrs.items()}
+        for k in ('mask_items', 'truth_items', 'hl_items'):  # a zero-length tensor has no valid pointer
+            if k in self._dev and self._dev[k].numel() == 0:
+                self._dev[k] = torch.zeros(1, dtype=torch.int32, device=device)
+        self._users = torch.as_tensor(np.asarray(users, np.int64)).to(device)
+        self._truth_len = np.diff(tp).astype(np.float64)
+        item_num = self._item_num()
+        if any(not 1 <= int(k) <= item_num for k in self.top_k_list):
+            raise ValueError(f'top_k_list {self.top_k_list}: every k must lie in [1, item_num = {item_num}]')
+        self._n_neg = torch.from_numpy((item_num - np.diff(tp) - np.diff(mp)).astype(np.int32)).to(device)
+        # the matrix route's batches: row pointers rebased to each batch's own slice of the truth items, uploaded once
+        self._n_truth = int(tp[n])
+        step = self._step(n, 0)
+        self._batches = []
+        for lo in range(0, n, step):
+            hi = min(lo + step, n)
+            self._batches.append((lo, hi, int(tp[lo]), int(tp[hi]), torch.from_numpy(tp[lo:hi + 1] - tp[lo]).to(device)))
+        self._small = [int(k) for k in self.top_k_list if int(k) <= 1024]   # (INVPREF_MAX_TOPK_WIDE: rank_metrics' range)
+        self._big = [int(k) for k in self.top_k_list if int(k) > 1024]
+        if self._small:
+            rank_metric_tables(self._small, device)
+
+    def ranks(self) -> torch.Tensor:
+        """int32 [n_truth] on the device: the rank of every ground-truth item, in the order of the truth CSR"""
+        from . import ops
+        d = self._dev
+        tables = self._fused_tables()
+        hl = (d['hl_ptr'], d['hl_items']) if self.use_item_pool else None
+        if tables is not None:
+            return ops.truth_ranks(tables[0], tables[1], self._users, (d['truth_ptr'], d['truth_items'][:self._n_truth]), True,
+                                   mask=(d['mask_ptr'], d['mask_items']), highlight=hl)
+        parts = []
+        for lo, hi, e0, e1, tp in self._batches:
+            ratings = self.model.predict(self._users[lo:hi].contiguous())
+            hl_b = (d['hl_ptr'][lo:hi + 1], d['hl_items']) if self.use_item_pool else None
+            parts.append(ops.truth_ranks_rows(ratings, (tp, d['truth_items'][e0:e1]),
+                                              mask=(d['mask_ptr'][lo:hi + 1], d['mask_items']), highlight=hl_b))
+        if not parts:
+            return torch.empty(0, dtype=torch.int32, device=self._users.device)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def evaluate_async(self) -> 'PendingEvaluation':
+        """Enqueues the whole evaluation on the current stream and returns at once; after the first call (which uploads the
+        CSR arrays and the metric tables) nothing is copied from the host and nothing synchronises."""
+        from . import ops
+        self.model.eval()
+        device = next(self.model.parameters()).device
+        if self._dev is None:
+            self._prepare(device)
+        n_users = self._users.shape[0]
+        ranks = self.ranks()
+        tp = self._dev['truth_ptr']
+        outs = [ops.rank_metrics_from_ranks(ranks, tp, self._n_neg, self._big).reshape(-1)]
+        if self._small:
+            hits = ops.truth_rank_hits(ranks, tp, max(self._small))
+            outs.append(ops.rank_metric_sums(hits, tp, self._small, self._step(n_users, max(self.top_k_list))).reshape(-1))
+        out = torch.cat(outs)
+        small, big = list(self._small), list(self._big)
+
+        def finish(host: torch.Tensor) -> dict:
+            s = host.numpy()
+            b = s[:3 * (len(big) + 1)].reshape(3, len(big) + 1)
+            sm = s[3 * (len(big) + 1):].reshape(3, len(small))
+            nu = float(n_users)
+            res = {m: {} for m in ('ndcg', 'recall', 'precision')}
+            for row, m in ((2, 'ndcg'), (0, 'recall'), (1, 'precision')):
+                for i, k in enumerate(small):
+                    res[m][k] = float(sm[row][i] / nu)
+                for i, k in enumerate(big):
+                    res[m][k] = float(b[row][i] / nu)
+            res.update(auc=float(b[0][-1] / nu), mrr=float(b[1][-1] / nu), map=float(b[2][-1] / nu))
+            return res
+        return PendingEvaluation(out, finish)
 
 
 class PendingEvaluation:

@@ -19,6 +19,7 @@ from . import torch_ops_cause  # noqa: F401  (the CausE fragment: torch.ops.invp
 from . import torch_ops_scaled  # noqa: F401  (the scaled retrieval's fragment: torch.ops.invpref.predict_topk_scaled*)
 from . import torch_ops_lintrans  # noqa: F401  (the LinearTrans fragment: torch.ops.invpref.lintrans_*, predict_topk_weighted*)
 from . import torch_ops_adam_rows  # noqa: F401  (lazy Adam's fragment: torch.ops.invpref.adam_rows_)
+from . import torch_ops_truth_rank  # noqa: F401  (rank-based evaluation's fragment: torch.ops.invpref.truth_ranks*)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -364,6 +365,43 @@ def rank_metric_sums(hits: torch.Tensor, truth_ptr: torch.Tensor, top_k_list, pa
     ks = [int(k) for k in top_k_list]
     op = _o().rank_metrics if max(ks + [hits.shape[1]]) <= _capi.MAX_TOPK else _o().rank_metrics_wide
     return op(hits, truth_ptr, ks, disc, idcg, int(partition))
+
+
+def truth_ranks(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, truth, sigmoid: bool = True,
+                mask=None, highlight=None) -> torch.Tensor:
+    """The exact 0-based rank of every truth item in its user's full ranking by sigmoid(user . item) (the plain dot product if
+    not sigmoid), masked items at -1024 and highlighted items raised by 1024: the position topk_rows would list the item at
+    with an unbounded k -- value descending, lowest item id first among equal values -- without the [n, item_num] matrix
+    (csrc/invpref_truth_rank.hip).  truth / mask / highlight: int32 CSR pairs (indptr[n + 1], indices) over the rows of
+    `users`, every row sorted ascending and distinct, any number of items per row; indptr indexes `indices` from its start.
+    -> int32 [n_truth], entry e the rank of truth item e (item_num for an id outside the table, -1 for an entry no row covers)."""
+    _gpu(user_table, item_table, users)
+    (mp, mi), (hp, hi) = [(None, None) if c is None else c for c in (mask, highlight)]
+    return _o().truth_ranks(user_table, item_table, users, bool(sigmoid), mp, mi, hp, hi, truth[0], truth[1])
+
+
+def truth_ranks_rows(ratings: torch.Tensor, truth, mask=None, highlight=None) -> torch.Tensor:
+    """truth_ranks from a score matrix (fp32 [n, item_num], row stride allowed; not modified), any item count: the route of
+    every model that only offers predict().  For ops.predict's scores the ranks are truth_ranks', integer for integer."""
+    _gpu(ratings)
+    (mp, mi), (hp, hi) = [(None, None) if c is None else c for c in (mask, highlight)]
+    return _o().truth_ranks_rows(ratings, mp, mi, hp, hi, truth[0], truth[1])
+
+
+def truth_rank_hits(ranks: torch.Tensor, truth_ptr: torch.Tensor, k: int) -> torch.Tensor:
+    """The fp32 [n, k] 0/1 hit labels predict_topk / topk_rows give, from the ranks: hits[r, p] = 1 where a truth item of row
+    r has rank p < k."""
+    _gpu(ranks, truth_ptr)
+    return _o().truth_rank_hits(ranks, truth_ptr, int(k))
+
+
+def rank_metrics_from_ranks(ranks: torch.Tensor, truth_ptr: torch.Tensor, n_neg: torch.Tensor, top_k_list) -> torch.Tensor:
+    """The sums over the users of the ranking metrics, from the ranks alone, any 1 <= k (at most 63 of them, ascending):
+    -> float64 [3, n_k + 1] on the device, row 0 recall@k and, last, auc; row 1 precision@k and mrr; row 2 ndcg@k and map
+    (include/invpref_truth_rank.h states the formulas).  n_neg int32 [n]: per user, the items in neither its truth nor its
+    mask list.  A user without truth items contributes 0 everywhere; divide by the number of users for the means."""
+    _gpu(ranks, truth_ptr, n_neg)
+    return _o().rank_metrics_from_ranks(ranks, truth_ptr, n_neg, [int(k) for k in top_k_list])
 
 
 def device_csr(csr, n_rows: int, n_items: int, device):
