@@ -1104,6 +1104,15 @@ class MACRMatrixFactorization(nn.Module):
         return lambda users, k, mask, highlight, truth: ops.predict_topk_scaled(
             P, Q, users, k, a, c, self.const_c, True, mask=mask, highlight=highlight, truth=truth)
 
+    def truth_rank_fn(self):
+        """ImplicitRankTestManager's fused route, the counterpart of rank_fn(): f(users, truth, mask, highlight) -> int32 ranks
+        of the truth items in the ranking by the scores of predict(), without their matrix -- the two branch launches here,
+        then one scaled rank scan per call of f.  Nothing is kept between calls of truth_rank_fn()"""
+        a, c = self.branches()
+        P, Q = self.user_emb.weight.detach().contiguous(), self.item_emb.weight.detach().contiguous()
+        return lambda users, truth, mask, highlight: ops.truth_ranks_scaled(
+            P, Q, users, truth, a, c, self.const_c, True, mask=mask, highlight=highlight)
+
     def recommend(self, users_id, k: int, exclude=None, highlight=None):
         """Each user's top-k items by the scores of predict() (which may be negative), `exclude` items scoring -1024 and
         `highlight` items += 1024 (CSR pairs aligned with users_id): the branches once, then the scaled scan
@@ -1195,6 +1204,14 @@ class LinearTransMatrixFactorization(nn.Module):
         P, Q, w, b = self._frozen()
         return lambda users, k, mask, highlight, truth: ops.predict_topk_weighted(
             P, Q, users, k, w, b, True, mask=mask, highlight=highlight, truth=truth)
+
+    def truth_rank_fn(self):
+        """ImplicitRankTestManager's fused route, the counterpart of rank_fn(): f(users, truth, mask, highlight) -> int32 ranks
+        of the truth items in the ranking by the scores of predict(), without their matrix -- one weighted rank scan per call
+        of f; weight and bias stay on the device, so a captured evaluation follows them"""
+        P, Q, w, b = self._frozen()
+        return lambda users, truth, mask, highlight: ops.truth_ranks_weighted(
+            P, Q, users, truth, w, b, True, mask=mask, highlight=highlight)
 
     def recommend(self, users_id, k: int, exclude=None, highlight=None):
         """Each user's top-k items by the scores of predict(), `exclude` items scoring -1024 and `highlight` items += 1024

@@ -18,13 +18,14 @@ SOURCES = ['invpref_kernels.hip', 'invpref_step.hip', 'invpref_eval.hip', 'invpr
            'invpref_exposure.hip', 'invpref_impute.hip', 'invpref_cvib.hip', 'invpref_fairness.hip', 'invpref_macr.hip',
            'invpref_cause.hip', 'invpref_lintrans.hip', 'invpref_adam_rows.hip', 'invpref_truth_rank.hip']
 HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'adam_apply.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp',
-           'row_pass.hpp',
+           'row_pass.hpp', 'truth_rank_body.hpp',
            os.path.join('..', '..', 'include', 'invpref_hip.h'),
            os.path.join('..', '..', 'include', 'invpref_macr.h'), os.path.join('..', '..', 'include', 'invpref_cause.h'),
            os.path.join('..', '..', 'include', 'invpref_retrieve_scaled.h'),
            os.path.join('..', '..', 'include', 'invpref_lintrans.h'),
            os.path.join('..', '..', 'include', 'invpref_adam_rows.h'),
-           os.path.join('..', '..', 'include', 'invpref_truth_rank.h')]
+           os.path.join('..', '..', 'include', 'invpref_truth_rank.h'),
+           os.path.join('..', '..', 'include', 'invpref_truth_rank_scored.h')]
 # -ffp-contract=off: every fma of the canonical arithmetic is written explicitly
 FLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-ffp-contract=off',
          '-fno-fast-math', '-Wall', '-Wno-unused-function']

@@ -19,10 +19,14 @@
 // The matrix route (rows_key_kernel, rows_count_kernel) does the same from a given score matrix: 2048-item chunks of a row are
 //   staged in LDS, masked and highlighted there, and each wave counts for one truth entry at a time.
 // The metric kernels (hits_kernel, user_metrics_kernel) work from the ranks alone.
+// The scaled and the weighted form (include/invpref_truth_rank_scored.h) rank by the scores of predict_topk_scaled /
+//   predict_topk_weighted: the two kernels come three times from one text (truth_rank_body.hpp), with the epilogue and the A
+//   operands of retrieve_scan_body.hpp's second and third form; everything else -- keys, counting, walks, atomics -- is shared.
 // A text of its own: retrieve_scan_body.hpp and its three instances are not touched.
 #include "launch.hpp"
 
 #include "../../include/invpref_truth_rank.h"
+#include "../../include/invpref_truth_rank_scored.h"
 
 using namespace invpref;
 
@@ -88,227 +92,28 @@ __device__ __forceinline__ int front16(const unsigned *k, unsigned tk, int d) {
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-// ---- phase 1: 16 truth entries per wave, 64 per workgroup
-template <int DC>
-__global__ __launch_bounds__(256) void truth_key_kernel(const float *__restrict__ Pu, const float *__restrict__ Qi,
-                                                        const int64_t *__restrict__ users, int64_t n, int I, int D,
-                                                        int apply_sigmoid, const int *__restrict__ mask_ptr,
-                                                        const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
-                                                        const int *__restrict__ hl_items, const int *__restrict__ truth_ptr,
-                                                        const int *__restrict__ truth_items, int64_t n_truth,
-                                                        unsigned *__restrict__ tkeys, int *__restrict__ ranks) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int m = lane & 15, k = lane >> 4;
-    const int64_t e = ((int64_t)blockIdx.x * 4 + wave) * 16 + m;
-    const bool covered = e < n_truth && e >= (int64_t)truth_ptr[0] && e < (int64_t)truth_ptr[n];
-    const int64_t row = covered ? row_of(truth_ptr, n, e) : 0;
-    const int t = covered ? truth_items[e] : 0;
-    const bool ok = covered && t >= 0 && t < I;
-    const float *pu = Pu + users[row] * (int64_t)D;
-    const float *qi = Qi + (int64_t)(ok ? t : 0) * D;
-    // the scan's operands and chains: a[c][s] = user row m, b = item row m, element 64 c + 4 s + k, zero beyond D
-    f32x4_t acc[16];
-#pragma unroll
-    for (int s = 0; s < 16; s++) acc[s] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < DC; c++)
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-            const int el = 64 * c + 4 * s + k;
-            const float av = pu[el < D ? el : D - 1], bv = qi[el < D ? el : D - 1];
-            acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(el < D ? av : 0.f, el < D ? bv : 0.f, acc[s], 0, 0, 0);
-        }
-#pragma unroll
-    for (int s = 0; s < 16; s += 2) acc[s] = acc[s] + acc[s + 1];
-#pragma unroll
-    for (int s = 0; s < 16; s += 4) acc[s] = acc[s] + acc[s + 2];
-#pragma unroll
-    for (int s = 0; s < 16; s += 8) acc[s] = acc[s] + acc[s + 4];
-    acc[0] = acc[0] + acc[8];
-    // element (row m, column m) of the tile lives in lane (k = m / 4, m), register m % 4
-    if (k != (m >> 2) || e >= n_truth) return;
-    const int r = m & 3;
-    float p = acc[0][0];
-    p = r == 1 ? acc[0][1] : p;
-    p = r == 2 ? acc[0][2] : p;
-    p = r == 3 ? acc[0][3] : p;
-    if (apply_sigmoid) p = c_sigmoid(p);
-    tkeys[e] = ok ? masked_key(p, row, t, mask_ptr, mask_items, hl_ptr, hl_items) : 0u;
-    ranks[e] = ok ? 0 : (covered ? I : -1);
-}
-
-// ---- phase 2: the counting scan.  VEC: factor_num % 4 == 0 and 16-byte aligned tables (float4 staging)
-template <int DC, bool VEC>
-__global__ __launch_bounds__(256, 2) void truth_scan_kernel(const float *__restrict__ Pu, const float *__restrict__ Qi,
-                                                            const int64_t *__restrict__ users, int64_t n, int I, int D,
-                                                            int apply_sigmoid, const int *__restrict__ mask_ptr,
-                                                            const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
-                                                            const int *__restrict__ hl_items, const int *__restrict__ truth_ptr,
-                                                            const int *__restrict__ truth_items, int64_t n_truth, int steps_per,
-                                                            const unsigned *__restrict__ tkeys, int *__restrict__ ranks) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int DP = 64 * DC, RS = DP + 4, TILE = 16 * RS;
-    unsigned *skeys = reinterpret_cast<unsigned *>(lds + 2 * TILE);   // [2][64 users][16 items]
-    __shared__ int row_ptr[65];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int m = lane & 15, k = lane >> 4;
-    const int64_t row0 = (int64_t)blockIdx.x * 64;
-    if (threadIdx.x <= 64) {
-        const int64_t r = row0 + threadIdx.x;
-        int64_t p = truth_ptr[r < n ? r : n];
-        p = p < 0 ? 0 : (p > n_truth ? n_truth : p);
-        row_ptr[threadIdx.x] = (int)p;
-    }
-    __syncthreads();
-    const int E0 = row_ptr[0], E1 = row_ptr[64];
-    if (E0 >= E1) return;                                             // (workgroup-uniform: nothing to count)
-    // ---- A operands: a[c][s] = Pu[user m][64 c + 4 s + k], zero beyond D (loads from a clamped address, then a select)
-    const int64_t urow = row0 + wave * 16 + m;
-    const int64_t uid = users[urow < n ? urow : n - 1];
-    const float *pu = Pu + uid * (int64_t)D;
-    float a[DC][16];
-#pragma unroll
-    for (int c = 0; c < DC; c++)
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-            const int e = 64 * c + 4 * s + k;
-            const float v = pu[e < D ? e : D - 1];
-            a[c][s] = e < D ? v : 0.f;
-        }
-    const int tiles = (I + 15) / 16;
-    const int t0 = (int)blockIdx.y * steps_per, t1 = min(tiles, t0 + steps_per);
-    // ---- staging: a tile is 16 rows x DP floats; thread th moves element (or float4) th + 256 j of it
-    constexpr int EPR = VEC ? DP / 4 : DP;
-    constexpr int PER = 16 * EPR / 256;
-    int rr_[PER], col[PER], dst[PER];
-#pragma unroll
-    for (int j = 0; j < PER; j++) {
-        const int f = threadIdx.x + 256 * j;
-        rr_[j] = f / EPR;
-        col[j] = (VEC ? 4 : 1) * (f - rr_[j] * EPR);
-        dst[j] = rr_[j] * RS + col[j];
-    }
-    // every load and LDS store of the loop is unconditional: the tile after the last is the last one again, a column beyond D
-    // loads the row's last element (or float4) and stores zeros
-    auto load = [&](int t, float4 (&st)[PER]) {
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            const float *src = Qi + (int64_t)min(t * 16 + rr_[j], I - 1) * D;
-            if (VEC) {
-                const float4 v = *reinterpret_cast<const float4 *>(src + min(col[j], D - 4));
-                st[j] = col[j] < D ? v : f4zero();
-            } else {
-                const float v = src[min(col[j], D - 1)];
-                st[j].x = col[j] < D ? v : 0.f;
-            }
-        }
-    };
-    auto store = [&](int buf, const float4 (&st)[PER]) {
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            if (VEC) *reinterpret_cast<float4 *>(lds + buf * TILE + dst[j]) = st[j];
-            else lds[buf * TILE + dst[j]] = st[j].x;
-        }
-    };
-    for (int w0 = E0; w0 < E1; w0 += kWalk) {
-        // ---- this walk's truth entries: thread th carries entries w0 + th + 256 q
-        unsigned tk[kSlots];
-        int ti[kSlots], ul[kSlots], cnt[kSlots];
-        bool live[kSlots];
-#pragma unroll
-        for (int q = 0; q < kSlots; q++) {
-            const int e = w0 + (int)threadIdx.x + 256 * q;
-            live[q] = e < E1;
-            ti[q] = live[q] ? truth_items[e] : -1;
-            live[q] = live[q] && ti[q] >= 0 && ti[q] < I;
-            tk[q] = live[q] ? tkeys[e] : 0u;
-            int lo = 0, hi = 64;               // the local row: the last one with row_ptr <= e
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (row_ptr[mid] <= e) lo = mid + 1; else hi = mid; }
-            ul[q] = live[q] ? lo - 1 : 0;
-            cnt[q] = 0;
-        }
-        // ---- per-user cursors: lane (k, m) serves users 4 k + r of the wave (r = 0..3), the same for its 16 lanes
-        int mcur[4], mend[4], mnext[4], hcur[4], hend[4], hnext[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int64_t row = row0 + wave * 16 + 4 * k + r;
-            const bool valid = row < n;
-            const int64_t rr = valid ? row : 0;
-            mcur[r] = mend[r] = hcur[r] = hend[r] = 0;
-            if (mask_ptr && valid) { mend[r] = mask_ptr[rr + 1]; mcur[r] = lower_bound(mask_items, mask_ptr[rr], mend[r], t0 * 16); }
-            if (hl_ptr && valid) { hend[r] = hl_ptr[rr + 1]; hcur[r] = lower_bound(hl_items, hl_ptr[rr], hend[r], t0 * 16); }
-            mnext[r] = mcur[r] < mend[r] ? mask_items[mcur[r]] : INT32_MAX;
-            hnext[r] = hcur[r] < hend[r] ? hl_items[hcur[r]] : INT32_MAX;
-        }
-        auto count = [&](int t) {              // tile t's keys against the carried entries
-            const unsigned *sk = skeys + ((t - t0) & 1) * 1024;
-#pragma unroll
-            for (int q = 0; q < kSlots; q++)
-                if (live[q]) {
-                    unsigned kk[16];
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const uint4 x = *reinterpret_cast<const uint4 *>(sk + ul[q] * 16 + 4 * j);
-                        kk[4 * j] = x.x; kk[4 * j + 1] = x.y; kk[4 * j + 2] = x.z; kk[4 * j + 3] = x.w;
-                    }
-                    cnt[q] += front16(kk, tk[q], ti[q] - t * 16);
-                }
-        };
-        float4 st[PER];
-        load(t0, st);
-        store(0, st);
-        __syncthreads();
-        for (int t = t0; t < t1; t++) {
-            const int buf = (t - t0) & 1;
-            load(min(t + 1, t1 - 1), st);
-            const float *bt = lds + buf * TILE + m * RS + k;
-            f32x4_t acc[16];
-#pragma unroll
-            for (int s = 0; s < 16; s++) acc[s] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < DC; c++)
-#pragma unroll
-                for (int s = 0; s < 16; s++)
-                    acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][s], bt[64 * c + 4 * s], acc[s], 0, 0, 0);
-#pragma unroll
-            for (int s = 0; s < 16; s += 2) acc[s] = acc[s] + acc[s + 1];
-#pragma unroll
-            for (int s = 0; s < 16; s += 4) acc[s] = acc[s] + acc[s + 2];
-#pragma unroll
-            for (int s = 0; s < 16; s += 8) acc[s] = acc[s] + acc[s + 4];
-            acc[0] = acc[0] + acc[8];
-            const int base = t * 16, item = base + m;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float p = acc[0][r];
-                if (apply_sigmoid) p = c_sigmoid(p);
-                unsigned mb = 0u, hb = 0u;
-                while (mnext[r] < base + 16) {
-                    if (mnext[r] >= base) mb |= 1u << (mnext[r] - base);
-                    mcur[r]++;
-                    mnext[r] = mcur[r] < mend[r] ? mask_items[mcur[r]] : INT32_MAX;
-                }
-                while (hnext[r] < base + 16) {
-                    if (hnext[r] >= base) hb |= 1u << (hnext[r] - base);
-                    hcur[r]++;
-                    hnext[r] = hcur[r] < hend[r] ? hl_items[hcur[r]] : INT32_MAX;
-                }
-                float v = ((mb >> m) & 1u) ? -1024.0f : p;
-                if ((hb >> m) & 1u) v += 1024.0f;
-                // an item beyond the table stands behind every truth item (their thresholds are key + 1 >= 1 there)
-                skeys[buf * 1024 + (wave * 16 + 4 * k + r) * 16 + m] = item < I ? order_key(v) : 0u;
-            }
-            if (t > t0) count(t - 1);
-            store(buf ^ 1, st);
-            __syncthreads();
-        }
-        count(t1 - 1);
-#pragma unroll
-        for (int q = 0; q < kSlots; q++)
-            if (live[q] && cnt[q] != 0) atomicAdd(ranks + w0 + (int)threadIdx.x + 256 * q, cnt[q]);
-        __syncthreads();                       // (the next walk rewrites both key buffers)
-    }
-}
+// ---- the pair-key and counting-scan kernels, one pair per form (truth_rank_body.hpp)
+#define TRUTH_RANK_FORM 0
+#define TRUTH_KEY_NAME truth_key_kernel
+#define TRUTH_SCAN_NAME truth_scan_kernel
+#include "truth_rank_body.hpp"
+#undef TRUTH_RANK_FORM
+#undef TRUTH_KEY_NAME
+#undef TRUTH_SCAN_NAME
+#define TRUTH_RANK_FORM 1
+#define TRUTH_KEY_NAME truth_key_scaled_kernel
+#define TRUTH_SCAN_NAME truth_scan_scaled_kernel
+#include "truth_rank_body.hpp"
+#undef TRUTH_RANK_FORM
+#undef TRUTH_KEY_NAME
+#undef TRUTH_SCAN_NAME
+#define TRUTH_RANK_FORM 2
+#define TRUTH_KEY_NAME truth_key_weighted_kernel
+#define TRUTH_SCAN_NAME truth_scan_weighted_kernel
+#include "truth_rank_body.hpp"
+#undef TRUTH_RANK_FORM
+#undef TRUTH_KEY_NAME
+#undef TRUTH_SCAN_NAME
 
 // ---- the matrix route
 __global__ __launch_bounds__(256) void rows_key_kernel(const float *__restrict__ ratings, int64_t n, int I, int64_t ld,
@@ -491,6 +296,71 @@ int check_lists(const int32_t *mask_ptr, const int32_t *mask_items, const int32_
     return 0;
 }
 
+// the fused entry points' common body.  form 0: plain; 1: scaled (user_scale, item_scale, shift); 2: weighted (dim_weight,
+// logit_bias).  Every check runs before the first launch.
+int truth_ranks(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users, int64_t item_num,
+                int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr, const int32_t *mask_items,
+                const int32_t *highlight_ptr, const int32_t *highlight_items, const int32_t *truth_ptr,
+                const int32_t *truth_items, int64_t n_truth, int32_t *ranks, void *workspace, size_t workspace_bytes,
+                void *stream, int form, const float *user_scale = nullptr, const float *item_scale = nullptr, double shift = 0.0,
+                const float *dim_weight = nullptr, const float *logit_bias = nullptr) {
+    if (!user_table || !item_table || factor_num <= 0) return INVPREF_EINVAL;
+    if (form == 1 && (!user_scale || !item_scale)) return INVPREF_EINVAL;
+    if (form == 2 && (!dim_weight || !logit_bias)) return INVPREF_EINVAL;
+    if (int rc = check_lists(mask_ptr, mask_items, highlight_ptr, highlight_items, n_users, item_num, n_truth)) return rc;
+    if (factor_num > INVPREF_MAX_FACTORS) return INVPREF_EUNSUPPORTED;
+    if (n_truth == 0) return 0;
+    if (!truth_ptr || !truth_items || !ranks || (n_users > 0 && !users)) return INVPREF_EINVAL;
+    if (!workspace || workspace_bytes < keys_bytes(n_truth)) return INVPREF_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned *tkeys = reinterpret_cast<unsigned *>(workspace);
+    const int I = (int)item_num, D = (int)factor_num;
+    if (n_users == 0) {   // no row covers an entry
+        hipLaunchKernelGGL(rows_key_kernel, dim3((unsigned)((n_truth + 255) / 256)), dim3(256), 0, st, nullptr, n_users, I, 0,
+                           mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth, tkeys, ranks);
+        return (int)hipGetLastError();
+    }
+    const Geometry g = geometry(n_users, item_num);
+    const float shift_f = (float)shift;
+    return with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
+        return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
+            constexpr int DC = decltype(dc_c)::value;
+            constexpr bool VEC = decltype(vec_c)::value;
+            constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4) + (size_t)2 * 64 * 16 * 4;
+            const dim3 kgrid((unsigned)((n_truth + 63) / 64)), sgrid((unsigned)g.ux, (unsigned)g.ranges);
+            if (form == 1) {
+                const auto scan = truth_scan_scaled_kernel<DC, VEC>;
+                if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
+                hipLaunchKernelGGL(truth_key_scaled_kernel<DC>, kgrid, dim3(256), 0, st, user_table, item_table, users, n_users,
+                                   I, D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr,
+                                   truth_items, n_truth, tkeys, ranks, user_scale, item_scale, shift_f);
+                hipLaunchKernelGGL(scan, sgrid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D, apply_sigmoid,
+                                   mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth,
+                                   g.steps_per, tkeys, ranks, user_scale, item_scale, shift_f);
+            } else if (form == 2) {
+                const auto scan = truth_scan_weighted_kernel<DC, VEC>;
+                if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
+                hipLaunchKernelGGL(truth_key_weighted_kernel<DC>, kgrid, dim3(256), 0, st, user_table, item_table, users,
+                                   n_users, I, D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr,
+                                   truth_items, n_truth, tkeys, ranks, dim_weight, logit_bias);
+                hipLaunchKernelGGL(scan, sgrid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D, apply_sigmoid,
+                                   mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth,
+                                   g.steps_per, tkeys, ranks, dim_weight, logit_bias);
+            } else {
+                const auto scan = truth_scan_kernel<DC, VEC>;
+                if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
+                hipLaunchKernelGGL(truth_key_kernel<DC>, kgrid, dim3(256), 0, st, user_table, item_table, users, n_users, I, D,
+                                   apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items,
+                                   n_truth, tkeys, ranks);
+                hipLaunchKernelGGL(scan, sgrid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D, apply_sigmoid,
+                                   mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth,
+                                   g.steps_per, tkeys, ranks);
+            }
+            return (int)hipGetLastError();
+        });
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -506,37 +376,31 @@ int invpref_truth_ranks_hip(const float *user_table, const float *item_table, co
                             const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
                             const int32_t *truth_ptr, const int32_t *truth_items, int64_t n_truth, int32_t *ranks,
                             void *workspace, size_t workspace_bytes, void *stream) {
-    if (!user_table || !item_table || factor_num <= 0) return INVPREF_EINVAL;
-    if (int rc = check_lists(mask_ptr, mask_items, highlight_ptr, highlight_items, n_users, item_num, n_truth)) return rc;
-    if (factor_num > INVPREF_MAX_FACTORS) return INVPREF_EUNSUPPORTED;
-    if (n_truth == 0) return 0;
-    if (!truth_ptr || !truth_items || !ranks || (n_users > 0 && !users)) return INVPREF_EINVAL;
-    if (!workspace || workspace_bytes < keys_bytes(n_truth)) return INVPREF_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    unsigned *tkeys = reinterpret_cast<unsigned *>(workspace);
-    const int I = (int)item_num, D = (int)factor_num;
-    if (n_users == 0) {   // no row covers an entry
-        hipLaunchKernelGGL(rows_key_kernel, dim3((unsigned)((n_truth + 255) / 256)), dim3(256), 0, st, nullptr, n_users, I, 0,
-                           mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth, tkeys, ranks);
-        return (int)hipGetLastError();
-    }
-    const Geometry g = geometry(n_users, item_num);
-    return with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
-        return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
-            constexpr int DC = decltype(dc_c)::value;
-            constexpr bool VEC = decltype(vec_c)::value;
-            constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4) + (size_t)2 * 64 * 16 * 4;
-            const auto scan = truth_scan_kernel<DC, VEC>;
-            if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
-            hipLaunchKernelGGL(truth_key_kernel<DC>, dim3((unsigned)((n_truth + 63) / 64)), dim3(256), 0, st, user_table,
-                               item_table, users, n_users, I, D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr,
-                               highlight_items, truth_ptr, truth_items, n_truth, tkeys, ranks);
-            hipLaunchKernelGGL(scan, dim3((unsigned)g.ux, (unsigned)g.ranges), dim3(256), lds, st, user_table, item_table, users,
-                               n_users, I, D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr,
-                               truth_items, n_truth, g.steps_per, tkeys, ranks);
-            return (int)hipGetLastError();
-        });
-    });
+    return truth_ranks(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                       highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth, ranks, workspace, workspace_bytes, stream,
+                       0);
+}
+
+int invpref_truth_ranks_scaled_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
+                                   int64_t item_num, int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr,
+                                   const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
+                                   const int32_t *truth_ptr, const int32_t *truth_items, int64_t n_truth, int32_t *ranks,
+                                   void *workspace, size_t workspace_bytes, void *stream, const float *user_scale,
+                                   const float *item_scale, double shift) {
+    return truth_ranks(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                       highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth, ranks, workspace, workspace_bytes, stream,
+                       1, user_scale, item_scale, shift);
+}
+
+int invpref_truth_ranks_weighted_hip(const float *user_table, const float *item_table, const int64_t *users, int64_t n_users,
+                                     int64_t item_num, int64_t factor_num, int apply_sigmoid, const int32_t *mask_ptr,
+                                     const int32_t *mask_items, const int32_t *highlight_ptr, const int32_t *highlight_items,
+                                     const int32_t *truth_ptr, const int32_t *truth_items, int64_t n_truth, int32_t *ranks,
+                                     void *workspace, size_t workspace_bytes, void *stream, const float *dim_weight,
+                                     const float *logit_bias) {
+    return truth_ranks(user_table, item_table, users, n_users, item_num, factor_num, apply_sigmoid, mask_ptr, mask_items,
+                       highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth, ranks, workspace, workspace_bytes, stream,
+                       2, nullptr, nullptr, 0.0, dim_weight, logit_bias);
 }
 
 int invpref_truth_ranks_rows_hip(const float *ratings, int64_t n_users, int64_t item_num, int64_t ld, const int32_t *mask_ptr,

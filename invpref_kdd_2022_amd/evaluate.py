@@ -14,7 +14,9 @@ kernels (``csrc/invpref_metrics.hip``) in numpy's float64 order, and the host re
 ``recall_precision_ndcg`` keeps the numpy statement of the formulas that order is held to.  ``evaluate_async()`` enqueues
 an evaluation without waiting for it (the training loops' deferred mode).
 ``ImplicitRankTestManager`` evaluates from the exact rank of every ground-truth item in its user's full ranking
-(``csrc/invpref_truth_rank.hip``): the same three metrics at any k <= item_num, plus AUC, MRR and MAP.
+(``csrc/invpref_truth_rank.hip``): the same three metrics at any k <= item_num, plus AUC, MRR and MAP -- without a score
+matrix for the same models, ``MACRMatrixFactorization`` and ``LinearTransMatrixFactorization`` included (the scaled and the
+weighted form of the rank scan).
 """
 from __future__ import annotations
 
@@ -206,9 +208,10 @@ class ImplicitTestManager:
 class ImplicitRankTestManager(ImplicitTestManager):
     """Rank-based evaluation: the exact position of every ground-truth item in its user's full ranking
     (``csrc/invpref_truth_rank.hip``), and from those integers recall / precision / NDCG at ANY k <= item_num plus AUC, MRR and
-    MAP -- no [n, item_num] matrix for the models that rank by sigmoid(user table . item table) (``ops.truth_ranks``); any other
-    model's batch is ``model.predict`` + ``ops.truth_ranks_rows``, in batches bounded as ``ImplicitTestManager._step`` bounds
-    them.  -> {'ndcg': {k: ..}, 'recall': {..}, 'precision': {..}, 'auc': x, 'mrr': x, 'map': x}.  Up to k = 1024 the three
+    MAP -- no [n, item_num] matrix for the models that rank by sigmoid(user table . item table) (``ops.truth_ranks``) nor for a
+    model that offers ``truth_rank_fn()`` (``MACRMatrixFactorization``: ``ops.truth_ranks_scaled`` on its counterfactual score;
+    ``LinearTransMatrixFactorization``: ``ops.truth_ranks_weighted``); any other model's batch is ``model.predict`` +
+    ``ops.truth_ranks_rows``, in batches bounded as ``ImplicitTestManager._step`` bounds them.  -> {'ndcg': {k: ..}, 'recall': {..}, 'precision': {..}, 'auc': x, 'mrr': x, 'map': x}.  Up to k = 1024 the three
     dictionaries are ``ImplicitTestManager``'s float for float (the hit labels are rebuilt from the ranks and summed by the same
     ``rank_metrics`` kernels); beyond, and for auc / mrr / map, the float64 kernel of include/invpref_truth_rank.h.
     auc counts a user's negatives as the items in neither its truth nor its mask list, which the ranks alone only give when
@@ -272,14 +275,22 @@ class ImplicitRankTestManager(ImplicitTestManager):
             rank_metric_tables(self._small, device)
 
     def ranks(self) -> torch.Tensor:
-        """int32 [n_truth] on the device: the rank of every ground-truth item, in the order of the truth CSR"""
+        """int32 [n_truth] on the device: the rank of every ground-truth item, in the order of the truth CSR.  In this order:
+        ops.truth_ranks on _fused_tables(); the model's truth_rank_fn() -- a callable f(users, truth, mask, highlight) -> ranks,
+        asked for anew on every call (MACRMatrixFactorization: its two branch launches, then the scaled rank scan;
+        LinearTransMatrixFactorization: the weighted rank scan) -- in one call over all test users; model.predict() +
+        ops.truth_ranks_rows batch by batch"""
         from . import ops
         d = self._dev
         tables = self._fused_tables()
         hl = (d['hl_ptr'], d['hl_items']) if self.use_item_pool else None
+        truth = (d['truth_ptr'], d['truth_items'][:self._n_truth])
         if tables is not None:
-            return ops.truth_ranks(tables[0], tables[1], self._users, (d['truth_ptr'], d['truth_items'][:self._n_truth]), True,
-                                   mask=(d['mask_ptr'], d['mask_items']), highlight=hl)
+            return ops.truth_ranks(tables[0], tables[1], self._users, truth, True, mask=(d['mask_ptr'], d['mask_items']),
+                                   highlight=hl)
+        fn = getattr(self.model, 'truth_rank_fn', None)
+        if fn is not None:   # a model with scores of its own: one call over all test users, O(n_truth) device memory
+            return fn()(self._users, truth, (d['mask_ptr'], d['mask_items']), hl)
         parts = []
         for lo, hi, e0, e1, tp in self._batches:
             ratings = self.model.predict(self._users[lo:hi].contiguous())

@@ -20,6 +20,7 @@ from . import torch_ops_scaled  # noqa: F401  (the scaled retrieval's fragment: 
 from . import torch_ops_lintrans  # noqa: F401  (the LinearTrans fragment: torch.ops.invpref.lintrans_*, predict_topk_weighted*)
 from . import torch_ops_adam_rows  # noqa: F401  (lazy Adam's fragment: torch.ops.invpref.adam_rows_)
 from . import torch_ops_truth_rank  # noqa: F401  (rank-based evaluation's fragment: torch.ops.invpref.truth_ranks*)
+from . import torch_ops_truth_rank_scored  # noqa: F401  (its scaled / weighted forms: truth_ranks_scaled, truth_ranks_weighted)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -378,6 +379,35 @@ def truth_ranks(user_table: torch.Tensor, item_table: torch.Tensor, users: torch
     _gpu(user_table, item_table, users)
     (mp, mi), (hp, hi) = [(None, None) if c is None else c for c in (mask, highlight)]
     return _o().truth_ranks(user_table, item_table, users, bool(sigmoid), mp, mi, hp, hi, truth[0], truth[1])
+
+
+def truth_ranks_scaled(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, truth, user_scale: torch.Tensor,
+                       item_scale: torch.Tensor, shift: float, sigmoid: bool = True, mask=None, highlight=None) -> torch.Tensor:
+    """truth_ranks on the scores ((s - shift) * user_scale[users]) * item_scale, s = sigmoid(user . item) (the plain dot product
+    if not sigmoid): predict_topk_scaled's scores and order, so an entry with rank < k is the item predict_topk_scaled lists at
+    that position -- no [n, item_num] matrix (include/invpref_truth_rank_scored.h).  user_scale fp32 [user_num], indexed by
+    user id; item_scale fp32 [item_num].  With the two MACR branches and shift = const_c the ranks are those of
+    ops.macr_predict's matrix.  truth / mask / highlight and the result as in truth_ranks."""
+    _gpu(user_table, item_table, users, user_scale, item_scale)
+    (mp, mi), (hp, hi) = [(None, None) if c is None else c for c in (mask, highlight)]
+    return _o().truth_ranks_scaled(user_table, item_table, users, bool(sigmoid), mp, mi, hp, hi, truth[0], truth[1],
+                                   user_scale.reshape(-1), item_scale.reshape(-1), float(shift))
+
+
+def truth_ranks_weighted(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, truth, dim_weight: torch.Tensor,
+                         logit_bias, sigmoid: bool = True, mask=None, highlight=None) -> torch.Tensor:
+    """truth_ranks on the scores sigmoid(sum_d dim_weight_d user_d item_d + logit_bias) (the logit itself if not sigmoid):
+    predict_topk_weighted's scores and order -- no [n, item_num] matrix (include/invpref_truth_rank_scored.h).  dim_weight fp32
+    of factor_num floats; logit_bias a number or an fp32 device tensor of one element (read when the launch runs: a captured
+    evaluation follows it).  With LinearTrans-MF's predictor the ranks are those of ops.lintrans_predict's matrix.  truth /
+    mask / highlight and the result as in truth_ranks."""
+    _gpu(user_table, item_table, users, dim_weight)
+    (mp, mi), (hp, hi) = [(None, None) if c is None else c for c in (mask, highlight)]
+    if not isinstance(logit_bias, torch.Tensor):
+        logit_bias = torch.full((1,), float(logit_bias), dtype=torch.float32, device=users.device)
+    _gpu(logit_bias)
+    return _o().truth_ranks_weighted(user_table, item_table, users, bool(sigmoid), mp, mi, hp, hi, truth[0], truth[1],
+                                     dim_weight.reshape(-1), logit_bias.reshape(-1))
 
 
 def truth_ranks_rows(ratings: torch.Tensor, truth, mask=None, highlight=None) -> torch.Tensor:

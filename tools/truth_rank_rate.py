@@ -10,8 +10,20 @@ alternating in one process:
   - rows_us               ops.predict + ops.truth_ranks_rows in batches of at most 2^28 scores (the matrix route)
   - torch_us              a torch restatement: the score matrix in batches that fit, masked, argsorted (stable, descending),
                           the truth items' positions gathered -- with its peak device memory, as each route's
+The scaled and the weighted form (include/invpref_truth_rank_scored.h), at the same shapes:
+  mind40_scaled / mind40_weighted / mind256_scaled / mind256_weighted / yahoo_scaled / yahoo_weighted
+alternating in one process:
+  - scored_us             ops.truth_ranks_scaled / ops.truth_ranks_weighted over all test users
+  - truth_ranks_us        plain ops.truth_ranks on the same tables and lists
+  - topk_scored_us        the matching ops.predict_topk_scaled / ops.predict_topk_weighted, k = 40
+  - predict_topk_us       plain ops.predict_topk, k = 40
+  - rows_us               the matrix route: ops.macr_predict / ops.lintrans_predict + ops.truth_ranks_rows in batches of at most
+                          2^28 scores
+  overhead_rank = scored / truth_ranks - 1 next to overhead_topk = topk_scored / predict_topk - 1, and each route's peak
+  device memory.
 Every figure: HIP events around `reps` calls after a warm-up, WINDOWS windows, median and [min, max] over the windows.
-Usage: python tools/truth_rank_rate.py [out.json] [part ...]     parts: mind256 mind40 yahoo (default: all)"""
+Usage: python tools/truth_rank_rate.py [out.json] [part ...]     parts: mind256 mind40 yahoo and the six above (default: the
+plain three)"""
 import sys
 
 import numpy as np
@@ -113,10 +125,69 @@ def part(label):
     return res
 
 
+def scored_part(label, form):
+    """one of the *_scaled / *_weighted parts: the scored rank scan next to the plain one, its top-k scan and the matrix route"""
+    n, I, D, n_mask, n_truth, reps = SHAPES[label]
+    rs = np.random.RandomState(5)
+    P = dev((rs.standard_normal((n, D)) * 3.0 / np.sqrt(D)).astype(np.float32))
+    Q = dev((rs.standard_normal((I, D)) * 3.0 / np.sqrt(D)).astype(np.float32))
+    users = torch.arange(n, device=DEV)
+    truth = csr(rs, n, I, n_truth)
+    comp = np.setdiff1d(np.unique(np.arange(n, dtype=np.int64)[:, None] * I + rs.randint(0, I, (n, n_mask))),
+                        (np.repeat(np.arange(n, dtype=np.int64), np.diff(truth[0].cpu().numpy())) * I + truth[1].cpu().numpy()))
+    mptr = np.zeros(n + 1, np.int64)
+    mptr[1:] = np.cumsum(np.bincount(comp // I, minlength=n))
+    mask = (dev(mptr.astype(np.int32)), dev((comp % I).astype(np.int32)))
+    us, isc = dev(rs.uniform(0.05, 1.0, n).astype(np.float32)), dev(rs.uniform(0.05, 1.0, I).astype(np.float32))
+    w, b = dev(rs.standard_normal(D).astype(np.float32)), dev(np.array([0.1], np.float32))
+    shift = 0.3
+    step = max(1, (1 << 28) // I)
+    tp_host = truth[0].cpu().numpy()
+    batches = [(lo, min(lo + step, n)) for lo in range(0, n, step)]
+    batch_tp = [dev(tp_host[lo:hi + 1] - tp_host[lo]) for lo, hi in batches]
+    if form == 'scaled':
+        scored = lambda: ops.truth_ranks_scaled(P, Q, users, truth, us, isc, shift, True, mask=mask)  # noqa: E731
+        topk = lambda: ops.predict_topk_scaled(P, Q, users, K, us, isc, shift, True, mask=mask, truth=truth)  # noqa: E731
+        matrix = lambda u: ops.macr_predict(P, Q, u, us, isc, shift)  # noqa: E731
+    else:
+        scored = lambda: ops.truth_ranks_weighted(P, Q, users, truth, w, b, True, mask=mask)  # noqa: E731
+        topk = lambda: ops.predict_topk_weighted(P, Q, users, K, w, b, True, mask=mask, truth=truth)  # noqa: E731
+        matrix = lambda u: ops.lintrans_predict(P, Q, u, w, b)  # noqa: E731
+
+    def plain():
+        return ops.truth_ranks(P, Q, users, truth, True, mask=mask)
+
+    def plain_topk():
+        return ops.predict_topk(P, Q, users, K, True, mask=mask, truth=truth)
+
+    def rows():
+        out = []
+        for (lo, hi), tp in zip(batches, batch_tp):
+            out.append(ops.truth_ranks_rows(matrix(users[lo:hi]), (tp, truth[1][tp_host[lo]:tp_host[hi]]),
+                                            mask=(mask[0][lo:hi + 1], mask[1])))
+        return torch.cat(out)
+
+    res = dict(shape=label + '_' + form, test_users=n, items=I, D=D, truth_entries=int(truth[1].numel()),
+               mask_entries=int(mask[1].numel()), rows_equal_fused=bool(torch.equal(scored(), rows())))
+    res['truth_ranks_us'] = timed_us(plain, reps)
+    res['scored_us'] = timed_us(scored, reps)
+    res['predict_topk_us'] = timed_us(plain_topk, reps)
+    res['topk_scored_us'] = timed_us(topk, reps)
+    res['truth_ranks_again_us'] = timed_us(plain, reps)
+    res['scored_again_us'] = timed_us(scored, reps)
+    res['rows_us'] = timed_us(rows, max(1, reps // 2))
+    res['overhead_rank'] = res['scored_us'][0] / res['truth_ranks_us'][0] - 1.0
+    res['overhead_topk'] = res['topk_scored_us'][0] / res['predict_topk_us'][0] - 1.0
+    res['ratio_to_rows'] = res['scored_us'][0] / res['rows_us'][0]
+    res['peak_bytes'] = dict(scored=peak_of(scored), truth_ranks=peak_of(plain), topk_scored=peak_of(topk), rows=peak_of(rows))
+    return res
+
+
 def main():
     res = []
     for label in sys.argv[2:] or list(SHAPES):
-        report(res, part(label))
+        base, _, form = label.rpartition('_')
+        report(res, scored_part(base, form) if form in ('scaled', 'weighted') and base in SHAPES else part(label))
     save(res)
 
 
