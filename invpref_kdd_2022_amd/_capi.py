@@ -101,7 +101,7 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 # (csrc/invpref_cause.hip), the scaled retrieval (csrc/invpref_retrieve.hip, csrc/invpref_topk_wide.hip) and the LinearTrans-MF
 # baseline with its weighted retrieval (csrc/invpref_lintrans.hip and the same two files), lazy Adam
 # (csrc/invpref_adam_rows.hip), rank-based evaluation (csrc/invpref_truth_rank.hip) and its scaled and weighted forms (the same
-# file).
+# file), the catalogue metrics (csrc/invpref_catalog.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
@@ -109,6 +109,7 @@ LINTRANS_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_lintrans.h')
 ADAM_ROWS_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_adam_rows.h')
 TRUTH_RANK_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_truth_rank.h')
 TRUTH_RANK_SCORED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_truth_rank_scored.h')
+CATALOG_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_catalog.h')
 MACR_SIGNATURES, MACR_DEFINES = _read_header(MACR_HEADER_PATH)
 CAUSE_SIGNATURES, CAUSE_DEFINES = _read_header(CAUSE_HEADER_PATH)
 SCALED_SIGNATURES, SCALED_DEFINES = _read_header(SCALED_HEADER_PATH)
@@ -116,6 +117,8 @@ LINTRANS_SIGNATURES, LINTRANS_DEFINES = _read_header(LINTRANS_HEADER_PATH)
 ADAM_ROWS_SIGNATURES, ADAM_ROWS_DEFINES = _read_header(ADAM_ROWS_HEADER_PATH)
 TRUTH_RANK_SIGNATURES, TRUTH_RANK_DEFINES = _read_header(TRUTH_RANK_HEADER_PATH)
 TRUTH_RANK_SCORED_SIGNATURES, TRUTH_RANK_SCORED_DEFINES = _read_header(TRUTH_RANK_SCORED_HEADER_PATH)
+CATALOG_SIGNATURES, CATALOG_DEFINES = _read_header(CATALOG_HEADER_PATH)
+CATALOG_MAX_KS, CATALOG_MAX_GROUPS = CATALOG_DEFINES['CATALOG_MAX_KS'], CATALOG_DEFINES['CATALOG_MAX_GROUPS']
 CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 # (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
 EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
@@ -123,7 +126,8 @@ EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_H
                  (LINTRANS_HEADER_PATH, 'LINTRANS_SIGNATURES', 'LINTRANS_DEFINES'),
                  (ADAM_ROWS_HEADER_PATH, 'ADAM_ROWS_SIGNATURES', 'ADAM_ROWS_DEFINES'),
                  (TRUTH_RANK_HEADER_PATH, 'TRUTH_RANK_SIGNATURES', 'TRUTH_RANK_DEFINES'),
-                 (TRUTH_RANK_SCORED_HEADER_PATH, 'TRUTH_RANK_SCORED_SIGNATURES', 'TRUTH_RANK_SCORED_DEFINES'))
+                 (TRUTH_RANK_SCORED_HEADER_PATH, 'TRUTH_RANK_SCORED_SIGNATURES', 'TRUTH_RANK_SCORED_DEFINES'),
+                 (CATALOG_HEADER_PATH, 'CATALOG_SIGNATURES', 'CATALOG_DEFINES'))
 
 _lib = None
 

@@ -16,7 +16,8 @@ PLAN_SRC = os.path.join(CSRC, 'invpref_plan.cpp')        # host-only row-plan bu
 SOURCES = ['invpref_kernels.hip', 'invpref_step.hip', 'invpref_eval.hip', 'invpref_retrieve.hip', 'invpref_metrics.hip',
            'invpref_topk_wide.hip', 'invpref_propensity.hip',
            'invpref_exposure.hip', 'invpref_impute.hip', 'invpref_cvib.hip', 'invpref_fairness.hip', 'invpref_macr.hip',
-           'invpref_cause.hip', 'invpref_lintrans.hip', 'invpref_adam_rows.hip', 'invpref_truth_rank.hip']
+           'invpref_cause.hip', 'invpref_lintrans.hip', 'invpref_adam_rows.hip', 'invpref_truth_rank.hip',
+           'invpref_catalog.hip']
 HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'adam_apply.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp',
            'row_pass.hpp', 'truth_rank_body.hpp',
            os.path.join('..', '..', 'include', 'invpref_hip.h'),
@@ -25,7 +26,8 @@ HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'adam_apply.hpp'
            os.path.join('..', '..', 'include', 'invpref_lintrans.h'),
            os.path.join('..', '..', 'include', 'invpref_adam_rows.h'),
            os.path.join('..', '..', 'include', 'invpref_truth_rank.h'),
-           os.path.join('..', '..', 'include', 'invpref_truth_rank_scored.h')]
+           os.path.join('..', '..', 'include', 'invpref_truth_rank_scored.h'),
+           os.path.join('..', '..', 'include', 'invpref_catalog.h')]
 # -ffp-contract=off: every fma of the canonical arithmetic is written explicitly
 FLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-ffp-contract=off',
          '-fno-fast-math', '-Wall', '-Wno-unused-function']

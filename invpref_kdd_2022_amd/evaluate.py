@@ -17,6 +17,9 @@ an evaluation without waiting for it (the training loops' deferred mode).
 (``csrc/invpref_truth_rank.hip``): the same three metrics at any k <= item_num, plus AUC, MRR and MAP -- without a score
 matrix for the same models, ``MACRMatrixFactorization`` and ``LinearTransMatrixFactorization`` included (the scaled and the
 weighted form of the rank scan).
+``ImplicitCatalogTestManager`` adds what the lists are made of (``csrc/invpref_catalog.hip``): catalogue coverage, the Gini
+coefficient of exposure, the average recommended popularity and the head / tail shares of the lists and of their hits, exact
+integers counted on the device next to the same ranking.
 """
 from __future__ import annotations
 
@@ -333,6 +336,119 @@ class ImplicitRankTestManager(ImplicitTestManager):
             res.update(auc=float(b[0][-1] / nu), mrr=float(b[1][-1] / nu), map=float(b[2][-1] / nu))
             return res
         return PendingEvaluation(out, finish)
+
+
+def popularity_groups(popularity, head_fractions=(0.2,)) -> np.ndarray:
+    """int32 [I]: the popularity group of every item.  The items are ordered by popularity descending, the lower id first
+    among equals; group g ends at item rank ceil(head_fractions[g] * I) (fractions ascending, in [0, 1]) and the last group,
+    number len(head_fractions), is the tail.  A fraction that adds no item leaves its group empty.  (The product is taken in
+    float64; one within 1e-9 above an integer counts as that integer: 0.1 * 30 ends at rank 3.)"""
+    pop = np.asarray(popularity).reshape(-1)
+    n = pop.shape[0]
+    fr = [float(f) for f in head_fractions]
+    if any(not 0.0 <= f <= 1.0 for f in fr) or fr != sorted(fr):
+        raise ValueError(f'head_fractions {head_fractions}: ascending fractions in [0, 1]')
+    order = np.lexsort((np.arange(n), -pop.astype(np.int64) if pop.dtype.kind in 'iub' else -pop.astype(np.float64)))
+    ends = [min(n, max(0, int(np.ceil(f * n - 1e-9)))) for f in fr]
+    group = np.full(n, len(fr), np.int32)
+    for g in range(len(fr) - 1, -1, -1):   # (from the widest head inwards: a smaller head overwrites)
+        group[order[:ends[g]]] = g
+    return group
+
+
+class ImplicitCatalogTestManager(ImplicitTestManager):
+    """``ImplicitTestManager`` plus the catalogue metrics of its lists (``csrc/invpref_catalog.hip``): the users are ranked
+    exactly as the parent ranks them (``_fused_rank()``'s callable where the model has one, ``topk()`` batches otherwise, the
+    same batch bounds), every batch's item ids are counted next to its hit labels, and ``result()`` gives the parent's three
+    dictionaries, float for float, plus 'coverage', 'gini' and -- with ``popularity`` (int [item_num]) -- 'arp' as {k: x}, and --
+    with ``item_group`` (int [item_num], values in [0, G), G <= 16; ``popularity_groups`` makes one) -- 'group_share' and
+    'group_recall' as {k: [G floats]} (``ops.catalog_metrics`` states them; a group's recall is its hits over the ground-truth
+    entries of the test users that lie in it).  Exact integers until one division per figure.  max(top_k_list) <= 1024 and at
+    most 8 values of k."""
+
+    def __init__(self, model, data_loader, test_batch_size: int, top_k_list: list, use_item_pool: bool = False,
+                 popularity=None, item_group=None):
+        super().__init__(model, data_loader, test_batch_size, top_k_list, use_item_pool)
+        from ._capi import CATALOG_MAX_GROUPS, CATALOG_MAX_KS, MAX_TOPK_WIDE
+        ks = [int(k) for k in self.top_k_list]
+        if not ks or len(ks) > CATALOG_MAX_KS or min(ks) < 1 or max(ks) > MAX_TOPK_WIDE:
+            raise ValueError(f'top_k_list {top_k_list}: 1 to {CATALOG_MAX_KS} values of k in [1, {MAX_TOPK_WIDE}]')
+        self._popularity = None if popularity is None else np.ascontiguousarray(np.asarray(popularity).reshape(-1), np.int32)
+        self._item_group = None if item_group is None else np.ascontiguousarray(np.asarray(item_group).reshape(-1), np.int32)
+        self._n_groups = 0
+        if self._item_group is not None:
+            self._n_groups = int(self._item_group.max(initial=-1)) + 1
+            if self._item_group.min(initial=0) < 0 or not 1 <= self._n_groups <= CATALOG_MAX_GROUPS:
+                raise ValueError(f'item_group: values in [0, G) with 1 <= G <= {CATALOG_MAX_GROUPS}')
+
+    def _item_num(self) -> int:
+        tables = self._fused_tables()
+        if tables is not None:
+            return int(tables[1].shape[0])
+        if hasattr(self.model, 'item_num'):
+            return int(self.model.item_num)
+        return int(self.model.predict(self._users[:1].contiguous()).shape[1])
+
+    def _prepare(self, device):
+        super()._prepare(device)
+        I = self._n_items = self._item_num()
+        for name, a in (('popularity', self._popularity), ('item_group', self._item_group)):
+            if a is not None and a.shape[0] != I:
+                self._dev = None
+                raise ValueError(f'{name} has {a.shape[0]} entries for {I} items')
+        self._pop_dev = None if self._popularity is None else torch.from_numpy(self._popularity).to(device)
+        self._group_dev = None if self._item_group is None else torch.from_numpy(self._item_group).to(device)
+        self._truth_group_totals = None
+        if self._item_group is not None:   # T_g, once, from the truth CSR the parent uploaded
+            tp, ti = self._dev['truth_ptr'].cpu().numpy(), self._dev['truth_items'].cpu().numpy()
+            t = ti[int(tp[0]):int(tp[-1])]
+            t = t[(t >= 0) & (t < I)]
+            self._truth_group_totals = np.bincount(self._item_group[t], minlength=self._n_groups).tolist()
+
+    def evaluate_async(self) -> 'PendingEvaluation':
+        """Enqueues the ranking, one catalog_count_ per batch, catalog_summary and the parent's rank_metric_sums on the
+        current stream and returns at once; result() reads 3 x n_k doubles and n_k x (4 + 2 G) integers back in one copy.
+        After the first call nothing is copied from the host and nothing synchronises: capturable."""
+        from . import ops
+        self.model.eval()
+        device = next(self.model.parameters()).device
+        if self._dev is None:
+            self._prepare(device)
+        d = self._dev
+        n_users, k = self._users.shape[0], max(self.top_k_list)
+        ks, I, G = [int(x) for x in self.top_k_list], self._n_items, self._n_groups
+        step = self._step(n_users, k)
+        rank = self._fused_rank()
+        bounds = range(0, n_users, step if rank is None else max(1, (1 << 28) // (8 * k)))   # (the parent's batches)
+        parts, out = [], None
+        for lo in bounds:
+            hi = min(lo + bounds.step, n_users)
+            if rank is not None:
+                hl = (d['hl_ptr'][lo:hi + 1], d['hl_items']) if self.use_item_pool else None
+                items, _, hits = rank(self._users[lo:hi], k, (d['mask_ptr'][lo:hi + 1], d['mask_items']), hl,
+                                      (d['truth_ptr'][lo:hi + 1], d['truth_items']))
+            else:
+                items, hits = self.topk(lo, hi)
+            out = ops.catalog_counts(items, ks, I, hits, self._group_dev, G, out=out)
+            parts.append(hits)
+        if not parts:
+            parts = [torch.empty(0, k, dtype=torch.float32, device=device)]
+            out = ops.catalog_counts(torch.empty(0, k, dtype=torch.int32, device=device), ks, I, None, self._group_dev, G)
+        hits = parts[0] if len(parts) == 1 else torch.cat(parts)
+        cat = ops.catalog_summary(out[0], n_users, self._pop_dev, self._group_dev, G)
+        if G > 0:
+            cat = torch.cat([cat, out[1]], dim=1)
+        sums = ops.rank_metric_sums(hits, d['truth_ptr'], self.top_k_list, step)
+        both = torch.cat([sums.reshape(-1).view(torch.int64), cat.reshape(-1)])   # (one read-back: the doubles' bits travel)
+        n_k, has_pop, totals = len(ks), self._pop_dev is not None, self._truth_group_totals
+
+        def finish(host: torch.Tensor) -> dict:
+            s = host[:3 * n_k].view(torch.float64).reshape(3, n_k).numpy()
+            sums = {'ndcg': s[2], 'recall': s[0], 'precision': s[1]}
+            res = {m: {k: float(v[i] / float(n_users)) for i, k in enumerate(ks)} for m, v in sums.items()}
+            res.update(ops.catalog_figures(host[3 * n_k:].reshape(n_k, -1).tolist(), ks, I, G, has_pop, True, totals))
+            return res
+        return PendingEvaluation(both, finish)
 
 
 class PendingEvaluation:

@@ -21,6 +21,7 @@ from . import torch_ops_lintrans  # noqa: F401  (the LinearTrans fragment: torch
 from . import torch_ops_adam_rows  # noqa: F401  (lazy Adam's fragment: torch.ops.invpref.adam_rows_)
 from . import torch_ops_truth_rank  # noqa: F401  (rank-based evaluation's fragment: torch.ops.invpref.truth_ranks*)
 from . import torch_ops_truth_rank_scored  # noqa: F401  (its scaled / weighted forms: truth_ranks_scaled, truth_ranks_weighted)
+from . import torch_ops_catalog  # noqa: F401  (the catalogue metrics' fragment: torch.ops.invpref.catalog_*)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -432,6 +433,96 @@ def rank_metrics_from_ranks(ranks: torch.Tensor, truth_ptr: torch.Tensor, n_neg:
     mask list.  A user without truth items contributes 0 everywhere; divide by the number of users for the means."""
     _gpu(ranks, truth_ptr, n_neg)
     return _o().rank_metrics_from_ranks(ranks, truth_ptr, n_neg, [int(k) for k in top_k_list])
+
+
+def catalog_counts(items: torch.Tensor, ks, item_num: int, hits: Optional[torch.Tensor] = None,
+                   item_group: Optional[torch.Tensor] = None, n_groups: int = 0, out=None):
+    """Per-item exposure counts of top-k lists (include/invpref_catalog.h): items int32 [n, K] (row stride allowed), row r a
+    ranked list as predict_topk / topk_rows / recommend() give it; ks ascending, 1 <= k <= K, at most 8.
+    -> (counts int32 [n_k, item_num], group_hits int64 [n_k, n_groups] or None): counts[i][j] the entries (r, p) with
+    p < ks[i] and items[r][p] == j; group_hits[i][g] those among them with hits[r][p] == 1 (fp32, the 0/1 labels of
+    predict_topk) and item_group[j] == g (int32 [item_num]; needs both).  An id outside [0, item_num) is skipped.
+    out: the pair a previous call returned -- this batch is ADDED to it (an evaluation of many batches: one call each); without
+    it the buffers are new and cleared on the stream.  Integer atomics: the same bits on every run."""
+    _gpu(items, hits, item_group)
+    ks = [int(k) for k in ks]
+    item_num, n_groups = int(item_num), int(n_groups)
+    if item_group is None:
+        n_groups = 0
+    if out is None:
+        counts = torch.empty(len(ks), item_num, dtype=torch.int32, device=items.device)
+        group_hits = torch.empty(len(ks), n_groups, dtype=torch.int64, device=items.device) if n_groups > 0 else None
+    else:
+        counts, group_hits = out
+    _o().catalog_count_(items, hits, ks, item_group, n_groups, item_num, counts, group_hits, out is not None)
+    return counts, group_hits
+
+
+def catalog_summary(counts: torch.Tensor, n_total: int, popularity: Optional[torch.Tensor] = None,
+                    item_group: Optional[torch.Tensor] = None, n_groups: int = 0) -> torch.Tensor:
+    """int64 [n_k, 4 + n_groups] on the device, row i = (covered, N, gini_num, pop_sum, share_0 ..) of counts[i]
+    (include/invpref_catalog.h states them).  n_total: the number of list rows counted; a count above it leaves INT64_MIN as
+    gini_num.  popularity / item_group int32 [item_num], optional (pop_sum 0 without; no shares without)."""
+    _gpu(counts, popularity, item_group)
+    return _o().catalog_summary(counts, int(n_total), popularity, item_group, int(n_groups) if item_group is not None else 0)
+
+
+def catalog_figures(rows, ks, item_num: int, n_groups: int, popularity: bool, hits: bool, truth_group_totals=None) -> dict:
+    """The catalogue dictionary from the integers: rows[i] = the 4 + n_groups integers of catalog_summary's row i followed by
+    the n_groups of group_hits' (python ints), one division per figure, a zero denominator giving 0.0.  'coverage' and 'gini'
+    always (gini NaN where the numerator is INT64_MIN); 'arp' with popularity; 'group_share' with n_groups > 0;
+    'group_recall' with hits, groups and truth_group_totals."""
+    div = lambda a, b: a / b if b else 0.0  # noqa: E731
+    res = {'coverage': {}, 'gini': {}}
+    if popularity:
+        res['arp'] = {}
+    if n_groups > 0:
+        res['group_share'] = {}
+        if hits and truth_group_totals is not None:
+            res['group_recall'] = {}
+            totals = [int(t) for t in truth_group_totals]
+            if len(totals) != n_groups:
+                raise InvPrefError(f'truth_group_totals has {len(totals)} entries for {n_groups} groups')
+    for k, row in zip(ks, rows):
+        covered, N, gini_num, pop_sum = (int(x) for x in row[:4])
+        res['coverage'][k] = div(covered, item_num)
+        res['gini'][k] = float('nan') if gini_num == -(1 << 63) else div(gini_num, item_num * N)
+        if 'arp' in res:
+            res['arp'][k] = div(pop_sum, N)
+        if 'group_share' in res:
+            res['group_share'][k] = [div(int(x), N) for x in row[4:4 + n_groups]]
+        if 'group_recall' in res:
+            res['group_recall'][k] = [div(int(x), t) for x, t in zip(row[4 + n_groups:4 + 2 * n_groups], totals)]
+    return res
+
+
+def catalog_metrics(items: torch.Tensor, ks, item_num: int, hits: Optional[torch.Tensor] = None,
+                    popularity: Optional[torch.Tensor] = None, item_group: Optional[torch.Tensor] = None,
+                    truth_group_totals=None):
+    """What top-k lists from any source (predict_topk, topk_rows, recommend()) are made of, exactly: enqueues catalog_counts
+    and catalog_summary and returns at once with an evaluate.PendingEvaluation, whose result() reads n_k x (4 + 2 G) int64
+    back once and gives {'coverage': {k: x}, 'gini': {k: x}, 'arp': {k: x}, 'group_share': {k: [G floats]}, 'group_recall':
+    {k: [G floats]}}: the share of the catalogue listed at all, the Gini coefficient of the items' exposure counts (NaN if a
+    row holds the same id twice so often that a count exceeds the number of rows), the mean popularity of a listed item
+    (popularity int32 [item_num]), each group's share of the list entries (item_group int32 [item_num], values in [0, G),
+    G = the largest value below 16, plus 1 -- read back here: with groups this call waits for item_group; an item with a
+    value outside [0, 16) belongs to no group) and each group's hits over
+    truth_group_totals[g], the ground-truth entries of group g.  Entries whose input is missing are absent."""
+    from .evaluate import PendingEvaluation
+    _gpu(items, hits, popularity, item_group)
+    ks = [int(k) for k in ks]
+    G = 0
+    if item_group is not None:   # (a value outside [0, INVPREF_CATALOG_MAX_GROUPS) is no group)
+        inside = item_group[(item_group >= 0) & (item_group < _capi.CATALOG_MAX_GROUPS)]
+        G = int(inside.max()) + 1 if inside.numel() else 0
+        item_group = item_group if G > 0 else None
+    counts, group_hits = catalog_counts(items, ks, item_num, hits, item_group, G)
+    out = catalog_summary(counts, items.shape[0], popularity, item_group, G)
+    if G > 0:
+        out = torch.cat([out, group_hits], dim=1)   # (cleared by the count, so zeros without hits)
+    has_pop, has_hits, item_num = popularity is not None, hits is not None, int(item_num)
+    return PendingEvaluation(out, lambda host: catalog_figures(host.tolist(), ks, item_num, G, has_pop, has_hits,
+                                                               truth_group_totals))
 
 
 def device_csr(csr, n_rows: int, n_items: int, device):
