@@ -22,7 +22,7 @@
  * that no row covers -1.  Scores may be negative; a user whose scale is 0 has a row of ties (ranked by id, masked items
  * behind), one with a negative scale the reversed order.
  *
- * Compiled from csrc/invpref_truth_rank.hip (csrc/truth_rank_body.hpp, included once per form) into libinvpref_hip.so.  The
+ * Compiled from csrc/invpref_truth_rank.hip (csrc/truth_rank_body.hpp: the kernels are templates over the form) into libinvpref_hip.so.  The
  * error codes (INVPREF_EINVAL / EUNSUPPORTED / EWORKSPACE) and INVPREF_MAX_FACTORS of invpref_hip.h apply.  A header of its own,
  * bound through a table of its own (_capi.parse_header on this file): invpref_hip.h, invpref_truth_rank.h and the ABI version
  * do not move.

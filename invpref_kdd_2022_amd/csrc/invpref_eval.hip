@@ -3,6 +3,7 @@
 // the hit labels (evaluate.py:88-112, :11-19) -- and the error sums of the explicit evaluator
 // (evaluate.py:199-210).  The rating matrix itself comes from predict_kernel (invpref_kernels.hip).
 #include "launch.hpp"
+#include "rank_key.hpp"
 
 using namespace invpref;
 
@@ -126,13 +127,8 @@ __global__ __launch_bounds__(256) void topk_mask_big_kernel(const float *__restr
 // the k-th value than are needed, two passes over the ids of the tied items; one more pass collects the k winners, which one
 // wave ranks by (value descending, id ascending) -- exactly the order of k argmax passes with the lowest id first among equal
 // scores -- and looks up in the ground-truth list.  Same masking arithmetic as above: -1024 for a train item, += 1024 for
-// an item of the pool.
-__device__ __forceinline__ unsigned order_key(float v) {
-    v = v + 0.0f;                                   // -0 -> +0: equal values, equal keys
-    if (v != v) return 0u;                          // a NaN score is never picked (`v > best` is false for it above)
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// an item of the pool.  The key is rank_key.hpp's order_key: -0 and +0 are equal values with equal keys, and a NaN score is
+// never picked (`v > best` is false for it above).
 __global__ __launch_bounds__(256) void topk_select_kernel(const float *__restrict__ ratings, int64_t n_users, int n_items,
                                                           const int *__restrict__ mask_ptr, const int *__restrict__ mask_items,
                                                           const int *__restrict__ hl_ptr, const int *__restrict__ hl_items,

@@ -3,7 +3,7 @@
 // two tables.  The [n, I] score matrix of invpref_predict_hip + invpref_eval_topk_hip is never stored: the workspace holds
 // O(n * ranges * k) candidates.  The result is that pair's, item for item: the same canonical dot product,
 // the same masking arithmetic, the same order -- value descending, lowest item id first among equal values, a NaN never
-// ahead of a number (order_key of invpref_eval.hip).
+// ahead of a number (order_key and beats of rank_key.hpp).
 //
 // Phase 1 (retrieve_scan_kernel): predict_mm_kernel's layout -- a workgroup is 64 users (a 16-user MFMA tile per wave, the A
 // operands in registers) x one range of 16-item tiles double-buffered in LDS -- for every D <= 256: rows are zero padded to
@@ -16,15 +16,16 @@
 // Phase 2 (retrieve_merge_kernel): one wave per user merges the ranges' lists with the full (key, id) comparison and looks the
 // winners up in the sorted ground truth.
 //
-// The scaled form (include/invpref_retrieve_scaled.h; retrieve_scaled_scan_kernel, the second form of retrieve_scan_body.hpp):
-// between the sigmoid and the mask each score becomes ((p - shift) * user_scale[users[row]]) * item_scale[item] --
-// macr_epilogue_kernel's three fp32 operations, in its order, so the scores are that kernel's bit for bit.
-// retrieve_scan_kernel is the text without it: the code it was, under the signature it had.
+// The scan is one template over its form (retrieve_scan_body.hpp; FORM 0 is the plain scan described above).
+// The scaled form (include/invpref_retrieve_scaled.h; FORM 1): between the sigmoid and the mask each score becomes
+// ((p - shift) * user_scale[users[row]]) * item_scale[item] -- macr_epilogue_kernel's three fp32 operations, in its order, so
+// the scores are that kernel's bit for bit.
 //
-// The weighted form (include/invpref_lintrans.h; retrieve_weighted_scan_kernel, the third form): the A operands are the user
+// The weighted form (include/invpref_lintrans.h; FORM 2): the A operands are the user
 // rows multiplied by dim_weight as they are loaded -- fp32(Pu[u][e] * w[e]), one rounding -- and logit_bias[0] is added in front of
 // the sigmoid: LinearTrans-MF's score, bit for bit what invpref_lintrans_predict_hip writes into its matrix.
 #include "launch.hpp"
+#include "rank_key.hpp"
 
 #include "../../include/invpref_lintrans.h"
 #include "../../include/invpref_retrieve_scaled.h"
@@ -37,20 +38,6 @@ constexpr int kMaxK = 64;
 constexpr int kCand = 80;       // phase-1 candidates per user: k <= 64 kept + room for one more tile (16) before compacting
                                 // (64 users x 80 x 8 bytes + 33 KB of D = 256 item tiles: two workgroups per CU)
 constexpr int kCand2 = 128;     // phase-2 candidates per user: k kept + one 64-entry chunk
-constexpr int kEmptyId = 0x7fffffff;
-
-// (identical to invpref_eval.hip's): -0 -> +0, NaN -> 0 (below every number), otherwise order preserving
-__device__ __forceinline__ unsigned order_key(float v) {
-    v = v + 0.0f;
-    if (v != v) return 0u;
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// the value back from its key (a NaN's key gives a NaN)
-__device__ __forceinline__ float key_value(unsigned k) {
-    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ bool beats(unsigned ka, int ia, unsigned kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
 
 // One wave compacts an LDS list of c <= 128 (key, id) pairs with distinct ids to its best min(c, keep), in rank order.
 __device__ __forceinline__ void wave_compact(unsigned *keys, int *ids, int c, int keep, int lane) {
@@ -73,30 +60,7 @@ __device__ __forceinline__ void wave_compact(unsigned *keys, int *ids, int c, in
     __builtin_amdgcn_wave_barrier();
 }
 
-// first position in [lo, hi) of the sorted list whose item is >= x
-__device__ __forceinline__ int lower_bound(const int *__restrict__ a, int lo, int hi, int x) {
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < x) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// the scan kernel, in its three forms (retrieve_scan_body.hpp)
-#define RETRIEVE_SCAN_NAME retrieve_scan_kernel
-#define RETRIEVE_SCAN_SCALED 0
-#include "retrieve_scan_body.hpp"
-#undef RETRIEVE_SCAN_NAME
-#undef RETRIEVE_SCAN_SCALED
-#define RETRIEVE_SCAN_NAME retrieve_scaled_scan_kernel
-#define RETRIEVE_SCAN_SCALED 1
-#include "retrieve_scan_body.hpp"
-#undef RETRIEVE_SCAN_NAME
-#undef RETRIEVE_SCAN_SCALED
-#define RETRIEVE_SCAN_NAME retrieve_weighted_scan_kernel
-#define RETRIEVE_SCAN_SCALED 2
-#include "retrieve_scan_body.hpp"
-#undef RETRIEVE_SCAN_NAME
-#undef RETRIEVE_SCAN_SCALED
+#include "retrieve_scan_body.hpp"   // retrieve_scan_kernel<DC, VEC, FORM>
 
 // One wave per user: the ranges' lists (ranges * K entries, in any order) merged with the full (key desc, id asc) comparison,
 // then the winners' values, items and hit labels.
@@ -160,22 +124,6 @@ __global__ __launch_bounds__(256) void retrieve_merge_kernel(int64_t n, int rang
     }
 }
 
-struct Geometry {
-    int64_t ux;
-    int ranges, steps_per;
-};
-// item ranges the way invpref_predict_hip sizes its item groups: about two workgroups per CU, at least eight 16-item tiles each
-Geometry geometry(int64_t n_users, int64_t item_num) {
-    Geometry g;
-    g.ux = (n_users + 63) / 64;
-    const int64_t steps_total = (item_num + 15) / 16;
-    int64_t ig = (512 + g.ux - 1) / g.ux;
-    if (ig > (steps_total + 7) / 8) ig = (steps_total + 7) / 8;
-    if (ig < 1) ig = 1;
-    g.steps_per = (int)((steps_total + ig - 1) / ig);
-    g.ranges = (int)((steps_total + g.steps_per - 1) / g.steps_per);   // (every range holds at least one tile)
-    return g;
-}
 size_t bytes_for(int64_t n_users, int64_t item_num, int64_t k) {
     return (size_t)n_users * (size_t)geometry(n_users, item_num).ranges * (size_t)k * 8u;
 }
@@ -209,25 +157,11 @@ int predict_topk(const float *user_table, const float *item_table, const int64_t
                 constexpr bool VEC = decltype(vec_c)::value;
                 constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4) + (size_t)64 * kCand * 8;
                 const dim3 grid((unsigned)g.ux, (unsigned)g.ranges);
-                if constexpr (decltype(form_c)::value == 2) {
-                    const auto scan = retrieve_weighted_scan_kernel<DC, VEC>;
-                    if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
-                    hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D,
-                                       apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k, g.steps_per,
-                                       wk, wi, dim_weight, logit_bias);
-                } else if constexpr (decltype(form_c)::value == 1) {
-                    const auto scan = retrieve_scaled_scan_kernel<DC, VEC>;
-                    if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
-                    hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D,
-                                       apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k, g.steps_per,
-                                       wk, wi, user_scale, item_scale, (float)shift);
-                } else {
-                    const auto scan = retrieve_scan_kernel<DC, VEC>;
-                    if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
-                    hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D,
-                                       apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k, g.steps_per,
-                                       wk, wi);
-                }
+                const auto scan = retrieve_scan_kernel<DC, VEC, decltype(form_c)::value>;
+                if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
+                hipLaunchKernelGGL(scan, grid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D, apply_sigmoid,
+                                   mask_ptr, mask_items, highlight_ptr, highlight_items, (int)k, g.steps_per, wk, wi,
+                                   ScoreArgs{user_scale, item_scale, dim_weight, logit_bias, (float)shift});
                 return (int)hipGetLastError();
             });
         });

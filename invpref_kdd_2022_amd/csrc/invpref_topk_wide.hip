@@ -6,7 +6,7 @@
 // highlight are two bit sets over the items -- in LDS up to kLdsItems items, else in the caller's workspace, one pair per
 // workgroup -- and the masking arithmetic is applied on the fly (-1024 for a train item, then += 1024 for a pool item), so the
 // score row is never written.  A radix select finds the k-th best key: three histogram passes over 11 / 11 / 10 bits of the
-// order key (order_key of invpref_eval.hip: -0 == +0, NaN below every number).  When more items carry the k-th key than are
+// order key (order_key of rank_key.hpp: -0 == +0, NaN below every number).  When more items carry the k-th key than are
 // needed, three more passes over 11 / 10 / 10 bits of the ids of the tied items find the needed LOWEST ids -- the full 31
 // id bits, any item count.  One last pass collects exactly k winners into LDS as 64-bit words (key << 32 | 0x7fffffff - id),
 // a bitonic sort across the workgroup puts them in (key descending, id ascending) order, and they go out with their values
@@ -25,6 +25,7 @@
 // user_values_wide_kernel: stage 1 of invpref_rank_metrics_hip for K <= 1024: the per-user dcg row sum follows numpy's
 // pairwise recursion above 128 elements; stages 2 and 3 are invpref_metrics.hip's (invpref::rank_metrics_reduce).
 #include "launch.hpp"
+#include "rank_key.hpp"
 
 #include "../../include/invpref_lintrans.h"
 #include "../../include/invpref_retrieve_scaled.h"
@@ -54,16 +55,6 @@ constexpr int64_t kMaxGrid = 1 << 16;
 constexpr size_t kChunkBytes = (size_t)256 << 20;   // scores per predict chunk
 constexpr int kMaxNK = 64;
 constexpr int kBlock = 128;                     // numpy's pairwise-sum leaf
-
-__device__ __forceinline__ unsigned order_key(float v) {
-    v = v + 0.0f;
-    if (v != v) return 0u;
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned k) {
-    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 __global__ __launch_bounds__(kThreads) void topk_wide_kernel(const float *__restrict__ ratings, int64_t n, int I, int64_t ld,
                                                              const int *__restrict__ mask_ptr, const int *__restrict__ mask_items,

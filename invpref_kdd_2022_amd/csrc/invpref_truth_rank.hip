@@ -20,10 +20,10 @@
 //   staged in LDS, masked and highlighted there, and each wave counts for one truth entry at a time.
 // The metric kernels (hits_kernel, user_metrics_kernel) work from the ranks alone.
 // The scaled and the weighted form (include/invpref_truth_rank_scored.h) rank by the scores of predict_topk_scaled /
-//   predict_topk_weighted: the two kernels come three times from one text (truth_rank_body.hpp), with the epilogue and the A
-//   operands of retrieve_scan_body.hpp's second and third form; everything else -- keys, counting, walks, atomics -- is shared.
-// A text of its own: retrieve_scan_body.hpp and its three instances are not touched.
+//   predict_topk_weighted: the two kernels are templates over the form (truth_rank_body.hpp), with the epilogue and the A
+//   operands of retrieve_scan_body.hpp's forms 1 and 2; everything else -- keys, counting, walks, atomics -- is shared.
 #include "launch.hpp"
+#include "rank_key.hpp"
 
 #include "../../include/invpref_truth_rank.h"
 #include "../../include/invpref_truth_rank_scored.h"
@@ -44,18 +44,6 @@ constexpr int kWalk = 256 * kSlots;      // entries per workgroup and walk
 constexpr int kChunk = 2048;             // items per workgroup of the matrix route
 constexpr int kMaxNK = 64;
 
-// (identical to invpref_eval.hip's): -0 -> +0, NaN -> 0 (below every number), otherwise order preserving
-__device__ __forceinline__ unsigned order_key(float v) {
-    v = v + 0.0f;
-    if (v != v) return 0u;
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// first position in [lo, hi) of the sorted list whose item is >= x
-__device__ __forceinline__ int lower_bound(const int *__restrict__ a, int lo, int hi, int x) {
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < x) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 __device__ __forceinline__ bool holds(const int *__restrict__ a, int lo, int hi, int x) {
     const int p = lower_bound(a, lo, hi, x);
     return p < hi && a[p] == x;
@@ -90,30 +78,7 @@ __device__ __forceinline__ int front16(const unsigned *k, unsigned tk, int d) {
     return c;
 }
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// ---- the pair-key and counting-scan kernels, one pair per form (truth_rank_body.hpp)
-#define TRUTH_RANK_FORM 0
-#define TRUTH_KEY_NAME truth_key_kernel
-#define TRUTH_SCAN_NAME truth_scan_kernel
-#include "truth_rank_body.hpp"
-#undef TRUTH_RANK_FORM
-#undef TRUTH_KEY_NAME
-#undef TRUTH_SCAN_NAME
-#define TRUTH_RANK_FORM 1
-#define TRUTH_KEY_NAME truth_key_scaled_kernel
-#define TRUTH_SCAN_NAME truth_scan_scaled_kernel
-#include "truth_rank_body.hpp"
-#undef TRUTH_RANK_FORM
-#undef TRUTH_KEY_NAME
-#undef TRUTH_SCAN_NAME
-#define TRUTH_RANK_FORM 2
-#define TRUTH_KEY_NAME truth_key_weighted_kernel
-#define TRUTH_SCAN_NAME truth_scan_weighted_kernel
-#include "truth_rank_body.hpp"
-#undef TRUTH_RANK_FORM
-#undef TRUTH_KEY_NAME
-#undef TRUTH_SCAN_NAME
+#include "truth_rank_body.hpp"   // truth_key_kernel<DC, FORM>, truth_scan_kernel<DC, VEC, FORM>
 
 // ---- the matrix route
 __global__ __launch_bounds__(256) void rows_key_kernel(const float *__restrict__ ratings, int64_t n, int I, int64_t ld,
@@ -270,23 +235,6 @@ __global__ __launch_bounds__(256) void user_metrics_kernel(const int *__restrict
 
 size_t keys_bytes(int64_t n_truth) { return (size_t)up(n_truth * 4, 16); }
 
-// the scan's item ranges, sized as invpref_predict_topk_hip sizes its own
-struct Geometry {
-    int64_t ux;
-    int ranges, steps_per;
-};
-Geometry geometry(int64_t n_users, int64_t item_num) {
-    Geometry g;
-    g.ux = (n_users + 63) / 64;
-    const int64_t steps_total = (item_num + 15) / 16;
-    int64_t ig = (512 + g.ux - 1) / g.ux;
-    if (ig > (steps_total + 7) / 8) ig = (steps_total + 7) / 8;
-    if (ig < 1) ig = 1;
-    g.steps_per = (int)((steps_total + ig - 1) / ig);
-    g.ranges = (int)((steps_total + g.steps_per - 1) / g.steps_per);
-    return g;
-}
-
 int check_lists(const int32_t *mask_ptr, const int32_t *mask_items, const int32_t *highlight_ptr,
                 const int32_t *highlight_items, int64_t n_users, int64_t item_num, int64_t n_truth) {
     if (n_users < 0 || n_truth < 0 || item_num <= 0) return INVPREF_EINVAL;
@@ -321,42 +269,24 @@ int truth_ranks(const float *user_table, const float *item_table, const int64_t 
         return (int)hipGetLastError();
     }
     const Geometry g = geometry(n_users, item_num);
-    const float shift_f = (float)shift;
+    const ScoreArgs f{user_scale, item_scale, dim_weight, logit_bias, (float)shift};
     return with_int<1, 2, 4>(nc_of(D), [&](auto dc_c) {
         return with_bool(rows_vec_ok(D, user_table, item_table), [&](auto vec_c) {
-            constexpr int DC = decltype(dc_c)::value;
-            constexpr bool VEC = decltype(vec_c)::value;
-            constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4) + (size_t)2 * 64 * 16 * 4;
-            const dim3 kgrid((unsigned)((n_truth + 63) / 64)), sgrid((unsigned)g.ux, (unsigned)g.ranges);
-            if (form == 1) {
-                const auto scan = truth_scan_scaled_kernel<DC, VEC>;
+            return with_int<0, 1, 2>(form, [&](auto form_c) {
+                constexpr int DC = decltype(dc_c)::value, FORM = decltype(form_c)::value;
+                constexpr bool VEC = decltype(vec_c)::value;
+                constexpr size_t lds = sizeof(float) * 2 * 16 * (64 * DC + 4) + (size_t)2 * 64 * 16 * 4;
+                const dim3 kgrid((unsigned)((n_truth + 63) / 64)), sgrid((unsigned)g.ux, (unsigned)g.ranges);
+                const auto scan = truth_scan_kernel<DC, VEC, FORM>;
                 if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
-                hipLaunchKernelGGL(truth_key_scaled_kernel<DC>, kgrid, dim3(256), 0, st, user_table, item_table, users, n_users,
-                                   I, D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr,
-                                   truth_items, n_truth, tkeys, ranks, user_scale, item_scale, shift_f);
+                hipLaunchKernelGGL((truth_key_kernel<DC, FORM>), kgrid, dim3(256), 0, st, user_table, item_table, users, n_users, I,
+                                   D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items,
+                                   n_truth, tkeys, ranks, f);
                 hipLaunchKernelGGL(scan, sgrid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D, apply_sigmoid,
                                    mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth,
-                                   g.steps_per, tkeys, ranks, user_scale, item_scale, shift_f);
-            } else if (form == 2) {
-                const auto scan = truth_scan_weighted_kernel<DC, VEC>;
-                if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
-                hipLaunchKernelGGL(truth_key_weighted_kernel<DC>, kgrid, dim3(256), 0, st, user_table, item_table, users,
-                                   n_users, I, D, apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr,
-                                   truth_items, n_truth, tkeys, ranks, dim_weight, logit_bias);
-                hipLaunchKernelGGL(scan, sgrid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D, apply_sigmoid,
-                                   mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth,
-                                   g.steps_per, tkeys, ranks, dim_weight, logit_bias);
-            } else {
-                const auto scan = truth_scan_kernel<DC, VEC>;
-                if (hipError_t e = ensure_lds(scan, lds)) return (int)e;
-                hipLaunchKernelGGL(truth_key_kernel<DC>, kgrid, dim3(256), 0, st, user_table, item_table, users, n_users, I, D,
-                                   apply_sigmoid, mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items,
-                                   n_truth, tkeys, ranks);
-                hipLaunchKernelGGL(scan, sgrid, dim3(256), lds, st, user_table, item_table, users, n_users, I, D, apply_sigmoid,
-                                   mask_ptr, mask_items, highlight_ptr, highlight_items, truth_ptr, truth_items, n_truth,
-                                   g.steps_per, tkeys, ranks);
-            }
-            return (int)hipGetLastError();
+                                   g.steps_per, tkeys, ranks, f);
+                return (int)hipGetLastError();
+            });
         });
     });
 }

@@ -1,31 +1,29 @@
-// retrieve_scan_body.hpp -- the scan kernel of invpref_retrieve.hip, included there once per form (no include guard):
-//   RETRIEVE_SCAN_NAME    the kernel's name
-//   RETRIEVE_SCAN_SCALED  0: the plain scan; 1: three more arguments and the epilogue
-//                         p = ((p - shift) * user_scale[users[row]]) * item_scale[item] between the sigmoid and the mask;
-//                         2: the weighted scan (include/invpref_lintrans.h): two more arguments, the A operands are
-//                         fp32(Pu[user][e] * dim_weight[e]) and p = p + logit_bias[0] in front of the sigmoid
-// Three kernels from one text rather than one kernel with a third template parameter or a shared __device__ body: the plain
-// kernel keeps its name, its signature and, instruction for instruction, its code (an inlined body compiles to other
-// registers, and spills in one instance).
+// retrieve_scan_body.hpp -- the scan kernel of invpref_retrieve.hip (phase 1 of predict_topk), one template for its forms:
+//   FORM 0  the plain scan;
+//   FORM 1  the scaled scan (include/invpref_retrieve_scaled.h): the epilogue
+//           p = ((p - f.shift) * f.user_scale[users[row]]) * f.item_scale[item] between the sigmoid and the mask;
+//   FORM 2  the weighted scan (include/invpref_lintrans.h): the A operands are fp32(Pu[user][e] * f.dim_weight[e]) and
+//           p = p + f.logit_bias[0] in front of the sigmoid.
+// The extras travel in the trailing ScoreArgs (rank_key.hpp); what only one form has is declared for all and assigned under
+// `if constexpr`, in the place and the order of operations the form needs, and the compiler drops it elsewhere.
+// Against the three per-form kernels this template replaced (the same text under three names), instance by instance in the
+// gfx950 listing (tools/device_diff.py --kernels; next_free_vgpr for DC = 1, 1, 2, 2, 4, 4 with float4, element-wise staging):
+//   plain      143 148 191 182 238 240   the same in all six; the code equal instruction for instruction
+//   scaled     150 154 198 196 246 250   -> 244 in the fifth, the others the same
+//   weighted   143 148 191 188 256 256   the same in all six
+// no scratch memory and the same LDS in all eighteen, none beyond the 256 registers of two workgroups a CU.
+// Included by invpref_retrieve.hip inside its unnamed namespace, after kCand and wave_compact.
 //
 // VEC: factor_num % 4 == 0 and 16-byte aligned tables (float4 staging); otherwise one float at a time (D = 30: 120-byte rows).
-template <int DC, bool VEC>
-__global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__restrict__ Pu, const float *__restrict__ Qi,
-                                                             const int64_t *__restrict__ users, int64_t n, int I, int D,
-                                                             int apply_sigmoid, const int *__restrict__ mask_ptr,
-                                                             const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
-                                                             const int *__restrict__ hl_items, int K, int steps_per,
-                                                             unsigned *__restrict__ ws_keys, int *__restrict__ ws_ids
-#if RETRIEVE_SCAN_SCALED == 1
-                                                             ,
-                                                             const float *__restrict__ user_scale,
-                                                             const float *__restrict__ item_scale, float shift
-#endif
-#if RETRIEVE_SCAN_SCALED == 2
-                                                             ,
-                                                             const float *__restrict__ dim_weight, const float *__restrict__ logit_bias_ptr
-#endif
-) {
+#pragma once
+template <int DC, bool VEC, int FORM>
+__global__ __launch_bounds__(256, 2) void retrieve_scan_kernel(const float *__restrict__ Pu, const float *__restrict__ Qi,
+                                                               const int64_t *__restrict__ users, int64_t n, int I, int D,
+                                                               int apply_sigmoid, const int *__restrict__ mask_ptr,
+                                                               const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
+                                                               const int *__restrict__ hl_items, int K, int steps_per,
+                                                               unsigned *__restrict__ ws_keys, int *__restrict__ ws_ids,
+                                                               ScoreArgs f) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int DP = 64 * DC, RS = DP + 4, TILE = 16 * RS;
     unsigned *ckeys = reinterpret_cast<unsigned *>(lds + 2 * TILE);   // [64 users][kCand]
@@ -43,32 +41,24 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
 #pragma unroll
         for (int s = 0; s < 16; s++) {
             const int e = 64 * c + 4 * s + k;
-#if RETRIEVE_SCAN_SCALED == 2
-            const float v = pu[e < D ? e : D - 1] * dim_weight[e < D ? e : D - 1];
-#else
-            const float v = pu[e < D ? e : D - 1];
-#endif
+            float v = pu[e < D ? e : D - 1];
+            if constexpr (FORM == 2) v = v * f.dim_weight[e < D ? e : D - 1];
             a[c][s] = e < D ? v : 0.f;
         }
-#if RETRIEVE_SCAN_SCALED == 2
-    const float logit_bias = logit_bias_ptr[0];
-#endif
+    float logit_bias = 0.f;
+    if constexpr (FORM == 2) logit_bias = f.logit_bias[0];
     const int tiles = (I + 15) / 16;
     const int t0 = (int)blockIdx.y * steps_per, t1 = min(tiles, t0 + steps_per);
     // ---- per-user state: lane (k, m) serves users 4 k + r of the wave (r = 0..3), the same for its 16 lanes
     int mcur[4], mend[4], mnext[4], hcur[4], hend[4], hnext[4], cnt[4];
     unsigned tau[4];   // survivors need key >= tau
     bool valid[4];
-#if RETRIEVE_SCAN_SCALED == 1
-    float us[4];       // the four users' scales, by user id (a row beyond n reads the last user's)
-#endif
+    float us[4];       // FORM 1: the four users' scales, by user id (a row beyond n reads the last user's)
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int64_t row = (int64_t)blockIdx.x * 64 + wave * 16 + 4 * k + r;
         valid[r] = row < n;
-#if RETRIEVE_SCAN_SCALED == 1
-        us[r] = user_scale[users[valid[r] ? row : n - 1]];
-#endif
+        if constexpr (FORM == 1) us[r] = f.user_scale[users[valid[r] ? row : n - 1]];
         const int64_t rr = valid[r] ? row : 0;
         mcur[r] = mend[r] = hcur[r] = hend[r] = 0;
         if (mask_ptr && valid[r]) { mend[r] = mask_ptr[rr + 1]; mcur[r] = lower_bound(mask_items, mask_ptr[rr], mend[r], t0 * 16); }
@@ -113,19 +103,17 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
     };
     float4 st[PER];
     load(min(t0, tiles - 1), st);
-#if RETRIEVE_SCAN_SCALED == 1
-    // item_scale of this lane's item, clamped like the rows; the next tile's is issued with its rows and waited for with them
-    auto load_scale = [&](int t) { return item_scale[min(t * 16 + m, I - 1)]; };
-    float isc = load_scale(min(t0, tiles - 1)), isc_next;
-#endif
+    // FORM 1: item_scale of this lane's item, clamped like the rows; the next tile's is issued with its rows and waited for with
+    // them
+    auto load_scale = [&](int t) { return f.item_scale[min(t * 16 + m, I - 1)]; };
+    float isc = 0.f, isc_next = 0.f;
+    if constexpr (FORM == 1) isc = load_scale(min(t0, tiles - 1));
     store(0, st);
     __syncthreads();
     for (int t = t0; t < t1; t++) {
         const int buf = (t - t0) & 1;
         load(min(t + 1, t1 - 1), st);
-#if RETRIEVE_SCAN_SCALED == 1
-        isc_next = load_scale(min(t + 1, t1 - 1));
-#endif
+        if constexpr (FORM == 1) isc_next = load_scale(min(t + 1, t1 - 1));
         const float *bt = lds + buf * TILE + m * RS + k;
         f32x4_t acc[16];
 #pragma unroll
@@ -146,13 +134,9 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             float p = acc[0][r];
-#if RETRIEVE_SCAN_SCALED == 2
-            p = p + logit_bias;
-#endif
+            if constexpr (FORM == 2) p = p + logit_bias;
             if (apply_sigmoid) p = c_sigmoid(p);
-#if RETRIEVE_SCAN_SCALED == 1
-            p = ((p - shift) * us[r]) * isc;
-#endif
+            if constexpr (FORM == 1) p = ((p - f.shift) * us[r]) * isc;
             // mask / highlight bits of this tile for user 4 k + r (the 16 lanes of the group walk the same cursor)
             unsigned mb = 0u, hb = 0u;
             while (mnext[r] < base + 16) {
@@ -196,9 +180,7 @@ __global__ __launch_bounds__(256, 2) void RETRIEVE_SCAN_NAME(const float *__rest
             }
         }
         store(buf ^ 1, st);
-#if RETRIEVE_SCAN_SCALED == 1
-        isc = isc_next;
-#endif
+        if constexpr (FORM == 1) isc = isc_next;
         __syncthreads();
     }
     // ---- the range's top k of each of the wave's 16 users to the workspace, in any order (empty entries beyond the list; a

@@ -1,41 +1,39 @@
-// truth_rank_body.hpp -- the pair-key and counting-scan kernels of invpref_truth_rank.hip, included there once per form (no
-// include guard), as retrieve_scan_body.hpp is by invpref_retrieve.hip:
-//   TRUTH_KEY_NAME, TRUTH_SCAN_NAME  the two kernels' names
-//   TRUTH_RANK_FORM  0: the plain form (include/invpref_truth_rank.h);
-//                    1: the scaled form (include/invpref_truth_rank_scored.h): three more arguments and the epilogue
-//                       p = ((p - shift) * user_scale[users[row]]) * item_scale[item] between the sigmoid and the mask;
-//                    2: the weighted form: two more arguments, the A operands are fp32(Pu[user][e] * dim_weight[e]) and
-//                       p = p + logit_bias[0] in front of the sigmoid
-// The arithmetic of forms 1 and 2 is retrieve_scan_body.hpp's second and third form, operation for operation.  Three kernels
-// from one text, not a template parameter or a shared __device__ body: the plain kernels keep their names, their signatures
-// and, instruction for instruction, their code.
-// At four 64-float chunks (factor_num > 128) the plain scan already spills at two workgroups a CU.  The scans of forms 1 and 2
-// keep there, in LDS instead of registers (SLOTS_LDS), what they touch once a tile or less: the carried truth entries' key,
-// item and local row (each thread its own 4 x 3 words), the mask / highlight cursors and their ends and the users' scales (per
-// user, written and read by the 16 lanes of one wave that serve that user, all with the same value) -- 13.5 KB next to the
-// 41 KB of tiles and keys, no scratch, two workgroups a CU.  The scaled scan with element-wise staging at four chunks
-// (unaligned tables or factor_num % 4 != 0, beyond 128) still misses by nine registers and asks for one workgroup a CU.
+// truth_rank_body.hpp -- the pair-key and counting-scan kernels of invpref_truth_rank.hip, one template each for the forms:
+//   FORM 0  the plain form (include/invpref_truth_rank.h);
+//   FORM 1  the scaled form (include/invpref_truth_rank_scored.h): the epilogue
+//           p = ((p - f.shift) * f.user_scale[users[row]]) * f.item_scale[item] between the sigmoid and the mask;
+//   FORM 2  the weighted form: the A operands are fp32(Pu[user][e] * f.dim_weight[e]) and p = p + f.logit_bias[0] in front of
+//           the sigmoid.
+// The arithmetic of forms 1 and 2 is retrieve_scan_body.hpp's, operation for operation, and is written the same way: the
+// extras travel in the trailing ScoreArgs (rank_key.hpp), and what only one form has is declared for all and assigned under
+// `if constexpr`.
+// Against the per-form kernels these templates replaced, instance by instance in the gfx950 listing (tools/device_diff.py
+// --kernels; next_free_vgpr for DC = 1, 1, 2, 2, 4, 4 with float4, element-wise staging; for the key kernel DC = 1, 2, 4):
+//   scan, plain      167 173 222 229 256 256   the same; 84 / 104 bytes of scratch in the last two, 272 bytes of LDS
+//   scan, scaled     171 188 228 237 254 312   -> 308 in the last, the others the same; LDS 272, 13840 at DC = 4
+//   scan, weighted   167 173 222 229 248 251   the same; LDS 272, 13584 at DC = 4
+//   key              136 136 160 | 140 140 164 | 148 136 184 (plain | scaled | weighted)   the same in all nine
+// no scratch elsewhere; the tile loops are the old ones instruction for instruction (registers renamed), the differences sit in
+// the prologues, where the extras now come out of one struct.
+// At four 64-float chunks (factor_num > 128) the plain scan spills at two workgroups a CU (84 / 104 bytes of scratch).  The
+// scans of forms 1 and 2 keep there, in LDS instead of registers (SLOTS_LDS), what they touch once a tile or less: the carried
+// truth entries' key, item and local row (each thread its own 4 x 3 words), the mask / highlight cursors and their ends and the
+// users' scales (per user, written and read by the 16 lanes of one wave that serve that user, all with the same value) --
+// 13.5 KB next to the 41 KB of tiles and keys, no scratch, two workgroups a CU.  The scaled scan with element-wise staging at
+// four chunks (unaligned tables or factor_num % 4 != 0, beyond 128) still misses the 256 registers and asks for one
+// workgroup a CU.
+// Included by invpref_truth_rank.hip inside its unnamed namespace, after its constants and helpers.
+#pragma once
 
 // ---- phase 1: 16 truth entries per wave, 64 per workgroup
-template <int DC>
-__global__ __launch_bounds__(256) void TRUTH_KEY_NAME(const float *__restrict__ Pu, const float *__restrict__ Qi,
-                                                      const int64_t *__restrict__ users, int64_t n, int I, int D,
-                                                      int apply_sigmoid, const int *__restrict__ mask_ptr,
-                                                      const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
-                                                      const int *__restrict__ hl_items, const int *__restrict__ truth_ptr,
-                                                      const int *__restrict__ truth_items, int64_t n_truth,
-                                                      unsigned *__restrict__ tkeys, int *__restrict__ ranks
-#if TRUTH_RANK_FORM == 1
-                                                      ,
-                                                      const float *__restrict__ user_scale,
-                                                      const float *__restrict__ item_scale, float shift
-#endif
-#if TRUTH_RANK_FORM == 2
-                                                      ,
-                                                      const float *__restrict__ dim_weight,
-                                                      const float *__restrict__ logit_bias_ptr
-#endif
-) {
+template <int DC, int FORM>
+__global__ __launch_bounds__(256) void truth_key_kernel(const float *__restrict__ Pu, const float *__restrict__ Qi,
+                                                        const int64_t *__restrict__ users, int64_t n, int I, int D,
+                                                        int apply_sigmoid, const int *__restrict__ mask_ptr,
+                                                        const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
+                                                        const int *__restrict__ hl_items, const int *__restrict__ truth_ptr,
+                                                        const int *__restrict__ truth_items, int64_t n_truth,
+                                                        unsigned *__restrict__ tkeys, int *__restrict__ ranks, ScoreArgs f) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = lane & 15, k = lane >> 4;
     const int64_t e = ((int64_t)blockIdx.x * 4 + wave) * 16 + m;
@@ -54,11 +52,9 @@ __global__ __launch_bounds__(256) void TRUTH_KEY_NAME(const float *__restrict__ 
 #pragma unroll
         for (int s = 0; s < 16; s++) {
             const int el = 64 * c + 4 * s + k;
-#if TRUTH_RANK_FORM == 2
-            const float av = pu[el < D ? el : D - 1] * dim_weight[el < D ? el : D - 1], bv = qi[el < D ? el : D - 1];
-#else
-            const float av = pu[el < D ? el : D - 1], bv = qi[el < D ? el : D - 1];
-#endif
+            float av = pu[el < D ? el : D - 1];
+            if constexpr (FORM == 2) av = av * f.dim_weight[el < D ? el : D - 1];
+            const float bv = qi[el < D ? el : D - 1];
             acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(el < D ? av : 0.f, el < D ? bv : 0.f, acc[s], 0, 0, 0);
         }
 #pragma unroll
@@ -75,50 +71,29 @@ __global__ __launch_bounds__(256) void TRUTH_KEY_NAME(const float *__restrict__ 
     p = r == 1 ? acc[0][1] : p;
     p = r == 2 ? acc[0][2] : p;
     p = r == 3 ? acc[0][3] : p;
-#if TRUTH_RANK_FORM == 2
-    p = p + logit_bias_ptr[0];
-#endif
+    if constexpr (FORM == 2) p = p + f.logit_bias[0];
     if (apply_sigmoid) p = c_sigmoid(p);
-#if TRUTH_RANK_FORM == 1
-    p = ((p - shift) * user_scale[users[row]]) * item_scale[ok ? t : 0];
-#endif
+    if constexpr (FORM == 1) p = ((p - f.shift) * f.user_scale[users[row]]) * f.item_scale[ok ? t : 0];
     tkeys[e] = ok ? masked_key(p, row, t, mask_ptr, mask_items, hl_ptr, hl_items) : 0u;
     ranks[e] = ok ? 0 : (covered ? I : -1);
 }
 
 // ---- phase 2: the counting scan.  VEC: factor_num % 4 == 0 and 16-byte aligned tables (float4 staging)
-template <int DC, bool VEC>
-__global__ __launch_bounds__(256, (TRUTH_RANK_FORM == 1 && DC == 4 && !VEC) ? 1 : 2) void TRUTH_SCAN_NAME(
+template <int DC, bool VEC, int FORM>
+__global__ __launch_bounds__(256, (FORM == 1 && DC == 4 && !VEC) ? 1 : 2) void truth_scan_kernel(
     const float *__restrict__ Pu, const float *__restrict__ Qi, const int64_t *__restrict__ users, int64_t n, int I, int D,
     int apply_sigmoid, const int *__restrict__ mask_ptr, const int *__restrict__ mask_items, const int *__restrict__ hl_ptr,
     const int *__restrict__ hl_items, const int *__restrict__ truth_ptr, const int *__restrict__ truth_items, int64_t n_truth,
-    int steps_per, const unsigned *__restrict__ tkeys, int *__restrict__ ranks
-#if TRUTH_RANK_FORM == 1
-    ,
-    const float *__restrict__ user_scale, const float *__restrict__ item_scale, float shift
-#endif
-#if TRUTH_RANK_FORM == 2
-    ,
-    const float *__restrict__ dim_weight, const float *__restrict__ logit_bias_ptr
-#endif
-) {
+    int steps_per, const unsigned *__restrict__ tkeys, int *__restrict__ ranks, ScoreArgs f) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int DP = 64 * DC, RS = DP + 4, TILE = 16 * RS;
     unsigned *skeys = reinterpret_cast<unsigned *>(lds + 2 * TILE);   // [2][64 users][16 items]
     __shared__ int row_ptr[65];
-#if TRUTH_RANK_FORM != 0
-    constexpr bool SLOTS_LDS = DC == 4;   // (see the head of this file)
+    constexpr bool SLOTS_LDS = FORM != 0 && DC == 4;   // (see the head of this file)
     __shared__ unsigned s_tk[SLOTS_LDS ? kWalk : 1];
     __shared__ int s_ti[SLOTS_LDS ? kWalk : 1], s_ul[SLOTS_LDS ? kWalk : 1];
     __shared__ int s_mend[SLOTS_LDS ? 64 : 1], s_hend[SLOTS_LDS ? 64 : 1], s_mcur[SLOTS_LDS ? 64 : 1], s_hcur[SLOTS_LDS ? 64 : 1];
-#if TRUTH_RANK_FORM == 1
-    __shared__ float s_us[SLOTS_LDS ? 64 : 1];
-#endif
-#else
-    constexpr bool SLOTS_LDS = false;
-    unsigned *s_tk = nullptr;
-    int *s_ti = nullptr, *s_ul = nullptr, *s_mend = nullptr, *s_hend = nullptr, *s_mcur = nullptr, *s_hcur = nullptr;
-#endif
+    __shared__ float s_us[SLOTS_LDS && FORM == 1 ? 64 : 1];   // (the scaled form's alone: the weighted one keeps its 13584 bytes)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = lane & 15, k = lane >> 4;
     const int64_t row0 = (int64_t)blockIdx.x * 64;
@@ -141,25 +116,21 @@ __global__ __launch_bounds__(256, (TRUTH_RANK_FORM == 1 && DC == 4 && !VEC) ? 1 
 #pragma unroll
         for (int s = 0; s < 16; s++) {
             const int e = 64 * c + 4 * s + k;
-#if TRUTH_RANK_FORM == 2
-            const float v = pu[e < D ? e : D - 1] * dim_weight[e < D ? e : D - 1];
-#else
-            const float v = pu[e < D ? e : D - 1];
-#endif
+            float v = pu[e < D ? e : D - 1];
+            if constexpr (FORM == 2) v = v * f.dim_weight[e < D ? e : D - 1];
             a[c][s] = e < D ? v : 0.f;
         }
-#if TRUTH_RANK_FORM == 2
-    const float logit_bias = logit_bias_ptr[0];
-#endif
-#if TRUTH_RANK_FORM == 1
-    float us[4];       // the scales of users 4 k + r of the wave, by user id (a row beyond n reads the last user's)
+    float logit_bias = 0.f;
+    if constexpr (FORM == 2) logit_bias = f.logit_bias[0];
+    float us[4];       // FORM 1: the scales of users 4 k + r of the wave, by user id (a row beyond n reads the last user's)
+    if constexpr (FORM == 1) {
 #pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int64_t row = row0 + wave * 16 + 4 * k + r;
-        us[r] = user_scale[users[row < n ? row : n - 1]];
-        if constexpr (SLOTS_LDS) s_us[wave * 16 + 4 * k + r] = us[r];   // (the 16 lanes of a group store the same value)
+        for (int r = 0; r < 4; r++) {
+            const int64_t row = row0 + wave * 16 + 4 * k + r;
+            us[r] = f.user_scale[users[row < n ? row : n - 1]];
+            if constexpr (SLOTS_LDS) s_us[wave * 16 + 4 * k + r] = us[r];   // (the 16 lanes of a group store the same value)
+        }
     }
-#endif
     const int tiles = (I + 15) / 16;
     const int t0 = (int)blockIdx.y * steps_per, t1 = min(tiles, t0 + steps_per);
     // ---- staging: a tile is 16 rows x DP floats; thread th moves element (or float4) th + 256 j of it
@@ -195,10 +166,13 @@ __global__ __launch_bounds__(256, (TRUTH_RANK_FORM == 1 && DC == 4 && !VEC) ? 1 
             else lds[buf * TILE + dst[j]] = st[j].x;
         }
     };
-#if TRUTH_RANK_FORM == 1
-    // item_scale of this lane's item, clamped like the rows; the next tile's is issued with its rows and waited for with them
-    auto load_scale = [&](int t) { return item_scale[min(t * 16 + m, I - 1)]; };
-#endif
+    // FORM 1: item_scale of this lane's item, clamped like the rows; the next tile's is issued with its rows and waited for with
+    // them.  The first tile's is the same in every walk and is loaded here, once: the pointers of a struct carry no
+    // __restrict__, so the compiler does not move the load over the walks' atomics itself, and a load left in the walk makes
+    // every epilogue wait for the tile prefetch behind it (s_waitcnt vmcnt(1): 0.7 % of the scan at D = 40).
+    auto load_scale = [&](int t) { return f.item_scale[min(t * 16 + m, I - 1)]; };
+    float isc_first = 0.f;
+    if constexpr (FORM == 1) isc_first = load_scale(t0);
     for (int w0 = E0; w0 < E1; w0 += kWalk) {
         // ---- this walk's truth entries: thread th carries entries w0 + th + 256 q
         unsigned tk[kSlots];
@@ -257,17 +231,13 @@ __global__ __launch_bounds__(256, (TRUTH_RANK_FORM == 1 && DC == 4 && !VEC) ? 1 
         };
         float4 st[PER];
         load(t0, st);
-#if TRUTH_RANK_FORM == 1
-        float isc = load_scale(t0), isc_next;
-#endif
+        float isc = isc_first, isc_next = 0.f;
         store(0, st);
         __syncthreads();
         for (int t = t0; t < t1; t++) {
             const int buf = (t - t0) & 1;
             load(min(t + 1, t1 - 1), st);
-#if TRUTH_RANK_FORM == 1
-            isc_next = load_scale(min(t + 1, t1 - 1));
-#endif
+            if constexpr (FORM == 1) isc_next = load_scale(min(t + 1, t1 - 1));
             const float *bt = lds + buf * TILE + m * RS + k;
             f32x4_t acc[16];
 #pragma unroll
@@ -288,13 +258,9 @@ __global__ __launch_bounds__(256, (TRUTH_RANK_FORM == 1 && DC == 4 && !VEC) ? 1 
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 float p = acc[0][r];
-#if TRUTH_RANK_FORM == 2
-                p = p + logit_bias;
-#endif
+                if constexpr (FORM == 2) p = p + logit_bias;
                 if (apply_sigmoid) p = c_sigmoid(p);
-#if TRUTH_RANK_FORM == 1
-                p = ((p - shift) * (SLOTS_LDS ? s_us[wave * 16 + 4 * k + r] : us[r])) * isc;
-#endif
+                if constexpr (FORM == 1) p = ((p - f.shift) * (SLOTS_LDS ? s_us[wave * 16 + 4 * k + r] : us[r])) * isc;
                 unsigned mb = 0u, hb = 0u;
                 while (mnext[r] < base + 16) {
                     if (mnext[r] >= base) mb |= 1u << (mnext[r] - base);
@@ -325,9 +291,7 @@ __global__ __launch_bounds__(256, (TRUTH_RANK_FORM == 1 && DC == 4 && !VEC) ? 1 
             }
             if (t > t0) count(t - 1);
             store(buf ^ 1, st);
-#if TRUTH_RANK_FORM == 1
-            isc = isc_next;
-#endif
+            if constexpr (FORM == 1) isc = isc_next;
             __syncthreads();
         }
         count(t1 - 1);

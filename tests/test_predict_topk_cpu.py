@@ -91,11 +91,12 @@ def listing():
 def test_listing_is_scratch_free_and_on_the_matrix_cores(listing):
     ks = kernel_regs.kernels(listing)
     scans = [k for k in ks if k['name'].startswith('retrieve_scan_kernel')]
-    assert len(scans) == 6                                        # DC 1 / 2 / 4 x float4 / scalar staging
+    assert len(scans) == 18                                       # DC 1 / 2 / 4 x float4 / scalar staging x the three forms
+    assert len({k['name'] for k in scans}) == 18
     assert any(k['name'].startswith('retrieve_merge_kernel') for k in ks)
     for k in ks:
         assert k['scratch'] == 0 and k['scratch_ops'] == 0, k
     bodies = re.findall(r'\n(_Z\w*retrieve_scan_kernel\w*):(.*?)\.Lfunc_end', listing, re.S)
-    assert len(bodies) == 6
+    assert len(bodies) == 18
     for name, body in bodies:
         assert 'v_mfma_f32_16x16x4_f32' in body, name

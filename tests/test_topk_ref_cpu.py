@@ -128,7 +128,7 @@ def test_mirrors_match_the_sources():
     wide = open(os.path.join(CSRC, 'invpref_topk_wide.hip')).read()
     assert 'if (r >= 64) r -= r % 64;' in wide                       # chunk_rows
     assert 'grid = std::min<int64_t>(n, kGlobalSlots);' in wide      # launch_rows
-    scan = open(os.path.join(CSRC, 'invpref_retrieve.hip')).read()
+    scan = open(os.path.join(CSRC, 'rank_key.hpp')).read()           # (shared by the top-k and the truth-rank scan)
     assert 'int64_t ig = (512 + g.ux - 1) / g.ux;' in scan           # geometry()
     assert 'if (ig > (steps_total + 7) / 8) ig = (steps_total + 7) / 8;' in scan
 

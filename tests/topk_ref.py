@@ -136,8 +136,8 @@ def wide_geometry(n, I, chunked=True):
 
 
 def scan_geometry(n, I, k=None):
-    """invpref_retrieve.hip geometry(): ux workgroup columns of 64 users, `ranges` item ranges of steps_per 16-item tiles;
-    with k, whether the merge kernel compacts before its last chunk (ranges * k > K_CAND2 - 64)"""
+    """rank_key.hpp geometry() (the scans of invpref_retrieve.hip and invpref_truth_rank.hip): ux workgroup columns of 64
+    users, `ranges` item ranges of steps_per 16-item tiles; with k, whether the merge kernel compacts before its last chunk (ranges * k > K_CAND2 - 64)"""
     ux = -(-n // 64)
     steps_total = -(-I // TILE)
     ig = -(-512 // ux)

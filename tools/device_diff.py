@@ -5,7 +5,13 @@ Every translation unit of build.SOURCES is compiled in both trees with build.FLA
 listings are compared as TEXT: `identical` (line for line, the lines naming the source-derived __hip_cuid_ symbol dropped),
 `identical after reordering` (the same set of kernels, each with an equal body and descriptor once the function index in
 local labels is normalised), or the first kernel that differs.  Exit status 1 on any difference.  A host-side refactor must
-come out `identical`: the proof, without a GPU, that what the GPU executes has not changed."""
+come out `identical`: the proof, without a GPU, that what the GPU executes has not changed.
+
+tools/device_diff.py --kernels OLD_TREE NEW_TREE [OLD_NAME=NEW_NAME ...] [file.hip ...] -- the same comparison kernel by
+kernel, for a change that is meant to move device code: for each translation unit (the named ones, or all) one line per kernel
+of either tree with the verdict (`equal`, `differs`, `only old`, `only new`) and next_free_vgpr / accum_offset / scratch
+bytes / LDS bytes of both sides.  Names are demangled.  OLD_NAME=NEW_NAME pairs renamed instances by prefix; a `*` on
+both sides stands for the instance's own template arguments: 'scan_scaled_kernel<*>=scan_kernel<*, 1>'.  Always exits 0."""
 import os
 import re
 import subprocess
@@ -40,6 +46,57 @@ def kernels(lines):
     return res
 
 
+FIGURES = ('next_free_vgpr', 'accum_offset', 'private_segment_fixed_size', 'group_segment_fixed_size')
+
+
+def short_names(names):
+    """mangled -> `kernel<args>`: demangled, without the unnamed namespace, the return type and the parameter list"""
+    dem = subprocess.run(['c++filt'], input='\n'.join(names), capture_output=True, text=True).stdout.split('\n')
+    return {n: re.sub(r'\(anonymous namespace\)::|^void |\(.*', '', d) for n, d in zip(names, dem)}
+
+
+def kernel_rows(old, new, renames):
+    """[(old short name or None, new short name or None, verdict, old figures, new figures)]"""
+    sides = []
+    for lines in (old, new):
+        ks = kernels(lines)
+        short = short_names(sorted(ks))
+        # (a renamed instance names itself in labels and symbols: its own name is masked before bodies are compared)
+        sides.append({short[n]: (b.replace(n, '@'), [int(re.search(r'\.amdhsa_%s\s+(\d+)' % f, b).group(1)) for f in FIGURES])
+                      for n, b in ks.items()})
+    ko, kn = sides
+    rows, paired = [], set()
+    for name in sorted(ko):
+        to = name
+        for a, b in renames:
+            m = re.fullmatch(re.escape(a).replace(r'\*', '(.*)'), name)
+            if m:
+                to = b.replace('*', m.group(1))
+        if to in kn:
+            paired.add(to)
+            rows.append((name, to, 'equal' if ko[name][0] == kn[to][0] else 'differs', ko[name][1], kn[to][1]))
+        else:
+            rows.append((name, None, 'only old', ko[name][1], None))
+    rows += [(None, n, 'only new', None, kn[n][1]) for n in sorted(kn) if n not in paired]
+    return rows
+
+
+def main_kernels(old_tree, new_tree, rest):
+    renames = []
+    for a, b in (r.split('=', 1) for r in rest if '=' in r):
+        renames.append((a, b) if '*' in a else (a + '*', b + '*'))
+    sources = [r for r in rest if '=' not in r] or build.SOURCES
+    fig = lambda f: '%3d %3d %4d %6d' % tuple(f) if f else '%17s' % '-'  # noqa: E731
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=16) as pool:
+        jobs = [(src, pool.submit(listing, old_tree, src, tmp, 'old'), pool.submit(listing, new_tree, src, tmp, 'new'))
+                for src in sources]
+        for src, a, b in jobs:
+            print('%s    (vgpr accum scratch lds: old | new)' % src)
+            for o, n, verdict, fo, fn in kernel_rows(a.result(), b.result(), renames):
+                print('  %-9s %s | %s  %s' % (verdict, fig(fo), fig(fn), o if n in (o, None) else (n if o is None else o + ' -> ' + n)))
+    return 0
+
+
 def compare(old, new):
     if old == new:
         return 'identical'
@@ -67,6 +124,8 @@ def main(old_tree, new_tree):
 
 
 if __name__ == '__main__':
+    if len(sys.argv) >= 4 and sys.argv[1] == '--kernels':
+        sys.exit(main_kernels(sys.argv[2], sys.argv[3], sys.argv[4:]))
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     sys.exit(main(sys.argv[1], sys.argv[2]))
