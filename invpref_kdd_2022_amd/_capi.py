@@ -101,7 +101,8 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 # (csrc/invpref_cause.hip), the scaled retrieval (csrc/invpref_retrieve.hip, csrc/invpref_topk_wide.hip) and the LinearTrans-MF
 # baseline with its weighted retrieval (csrc/invpref_lintrans.hip and the same two files), lazy Adam
 # (csrc/invpref_adam_rows.hip), rank-based evaluation (csrc/invpref_truth_rank.hip) and its scaled and weighted forms (the same
-# file), the catalogue metrics (csrc/invpref_catalog.hip).
+# file), the catalogue metrics (csrc/invpref_catalog.hip), the weighted / grouped rank metrics and the bootstrap sums
+# (csrc/invpref_rank_stats.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
@@ -110,6 +111,7 @@ ADAM_ROWS_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_adam_rows.h'
 TRUTH_RANK_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_truth_rank.h')
 TRUTH_RANK_SCORED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_truth_rank_scored.h')
 CATALOG_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_catalog.h')
+RANK_STATS_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_rank_stats.h')
 MACR_SIGNATURES, MACR_DEFINES = _read_header(MACR_HEADER_PATH)
 CAUSE_SIGNATURES, CAUSE_DEFINES = _read_header(CAUSE_HEADER_PATH)
 SCALED_SIGNATURES, SCALED_DEFINES = _read_header(SCALED_HEADER_PATH)
@@ -119,6 +121,9 @@ TRUTH_RANK_SIGNATURES, TRUTH_RANK_DEFINES = _read_header(TRUTH_RANK_HEADER_PATH)
 TRUTH_RANK_SCORED_SIGNATURES, TRUTH_RANK_SCORED_DEFINES = _read_header(TRUTH_RANK_SCORED_HEADER_PATH)
 CATALOG_SIGNATURES, CATALOG_DEFINES = _read_header(CATALOG_HEADER_PATH)
 CATALOG_MAX_KS, CATALOG_MAX_GROUPS = CATALOG_DEFINES['CATALOG_MAX_KS'], CATALOG_DEFINES['CATALOG_MAX_GROUPS']
+RANK_STATS_SIGNATURES, RANK_STATS_DEFINES = _read_header(RANK_STATS_HEADER_PATH)
+RANK_STATS_MAX_KS, RANK_STATS_MAX_GROUPS, RANK_STATS_MAX_SERIES = (
+    RANK_STATS_DEFINES['RANK_STATS_' + n] for n in ('MAX_KS', 'MAX_GROUPS', 'MAX_SERIES'))   # n_k < MAX_KS; G, S <= the others
 CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 # (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
 EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
@@ -127,7 +132,8 @@ EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_H
                  (ADAM_ROWS_HEADER_PATH, 'ADAM_ROWS_SIGNATURES', 'ADAM_ROWS_DEFINES'),
                  (TRUTH_RANK_HEADER_PATH, 'TRUTH_RANK_SIGNATURES', 'TRUTH_RANK_DEFINES'),
                  (TRUTH_RANK_SCORED_HEADER_PATH, 'TRUTH_RANK_SCORED_SIGNATURES', 'TRUTH_RANK_SCORED_DEFINES'),
-                 (CATALOG_HEADER_PATH, 'CATALOG_SIGNATURES', 'CATALOG_DEFINES'))
+                 (CATALOG_HEADER_PATH, 'CATALOG_SIGNATURES', 'CATALOG_DEFINES'),
+                 (RANK_STATS_HEADER_PATH, 'RANK_STATS_SIGNATURES', 'RANK_STATS_DEFINES'))
 
 _lib = None
 

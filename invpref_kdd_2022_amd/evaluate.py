@@ -20,6 +20,9 @@ weighted form of the rank scan).
 ``ImplicitCatalogTestManager`` adds what the lists are made of (``csrc/invpref_catalog.hip``): catalogue coverage, the Gini
 coefficient of exposure, the average recommended popularity and the head / tail shares of the lists and of their hits, exact
 integers counted on the device next to the same ranking.
+``ImplicitWeightedRankTestManager`` evaluates the same exact ranks under per-entry weights (inverse propensities: the
+self-normalised estimators on a biased test split) and user groups, with bootstrap intervals over users drawn on the device
+(``csrc/invpref_rank_stats.hip``); ``paired_bootstrap`` compares two of them under the same draws.
 """
 from __future__ import annotations
 
@@ -449,6 +452,204 @@ class ImplicitCatalogTestManager(ImplicitTestManager):
             res.update(ops.catalog_figures(host[3 * n_k:].reshape(n_k, -1).tolist(), ks, I, G, has_pop, True, totals))
             return res
         return PendingEvaluation(both, finish)
+
+
+def _weighted_figures(row, ks):
+    """one row of rank_metrics_weighted's sums -> ({k: recall}, {k: dcg}, auc, covered users): each figure over the covered count"""
+    n_k, c = len(ks), float(row[-1])
+    mean = lambda x: float(x / c) if c > 0 else 0.0  # noqa: E731
+    return ({k: mean(row[i]) for i, k in enumerate(ks)}, {k: mean(row[n_k + i]) for i, k in enumerate(ks)},
+            mean(row[2 * n_k]), int(c))
+
+
+PAIRED_MAX_KS = 15   # paired_bootstrap resamples two managers' series side by side: 2 (2 n_k + 2) <= 64 series a call
+
+
+class ImplicitWeightedRankTestManager(ImplicitRankTestManager):
+    """``ImplicitRankTestManager``'s exact ranks under per-entry weights and user groups (``csrc/invpref_rank_stats.hip``):
+    self-normalised, propensity-weighted recall@k, DCG@k and AUC (Yang et al., RecSys 2018: the SNIPS estimators of the
+    metrics on a test split of the biased log), the same figures per user group, and percentile bootstrap intervals over users.
+    Keyword arguments: ``entry_weight`` (float [n_truth], one weight per ground-truth entry in the order of the truth CSR over
+    the sorted test users) or ``item_weight`` (float [item_num], gathered once; a truth id outside the table weighs 0) --
+    inverse propensities, or 0 / 1 for the metrics over a subset of the truth items (tail items only); neither: every weight
+    is 1.  ``user_group`` (int [n_test_users], values in [0, G), G <= 16; a negative value: in no group).  ``n_boot`` > 0 adds
+    intervals at ``confidence`` from ``n_boot`` resamples of the users drawn on the device from ``seed`` (group g: its own
+    users, ``seed + g``).
+    -> {'recall': {k: x}, 'dcg': {k: x}, 'auc': x, 'users': n, 'covered': c}: each figure the mean over the c covered users,
+    those whose weights sum to more than 0; with groups 'group_recall' / 'group_dcg' {k: [G floats]}, 'group_auc',
+    'group_users', 'group_covered' (a group without a covered user reports 0.0); with n_boot > 0 'interval': the same keys and
+    shapes, (lo, hi) pairs.  At most 31 values of k, any 1 <= k <= item_num."""
+
+    def __init__(self, model, data_loader, test_batch_size: int, top_k_list: list, use_item_pool: bool = False, *,
+                 entry_weight=None, item_weight=None, user_group=None, n_boot: int = 0, seed: int = 0,
+                 confidence: float = 0.95):
+        super().__init__(model, data_loader, test_batch_size, top_k_list, use_item_pool)
+        from ._capi import RANK_STATS_MAX_GROUPS, RANK_STATS_MAX_KS
+        if len(self.top_k_list) >= RANK_STATS_MAX_KS:
+            raise ValueError(f'top_k_list holds {len(self.top_k_list)} values of k: fewer than {RANK_STATS_MAX_KS}')
+        if entry_weight is not None and item_weight is not None:
+            raise ValueError('entry_weight and item_weight: one of the two')
+        f32 = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a).reshape(-1), np.float32)  # noqa: E731
+        self._entry_weight, self._item_weight = f32(entry_weight), f32(item_weight)
+        self._user_group = None if user_group is None else np.ascontiguousarray(np.asarray(user_group).reshape(-1), np.int32)
+        self._n_groups = 1
+        if self._user_group is not None:
+            self._n_groups = int(self._user_group.max(initial=-1)) + 1
+            if not 1 <= self._n_groups <= RANK_STATS_MAX_GROUPS:
+                raise ValueError(f'user_group: values in [0, G) with 1 <= G <= {RANK_STATS_MAX_GROUPS}')
+        self.n_boot, self.seed, self.confidence = int(n_boot), int(seed), float(confidence)
+        if self.n_boot < 0 or not 0.0 < self.confidence < 1.0:
+            raise ValueError('n_boot >= 0 and a confidence in (0, 1)')
+
+    def _prepare(self, device):
+        super()._prepare(device)
+        n, nt = self._users.shape[0], self._n_truth
+        try:
+            w = self._entry_weight
+            if w is not None and w.shape[0] != nt:
+                raise ValueError(f'entry_weight has {w.shape[0]} entries for {nt} ground-truth entries')
+            if self._item_weight is not None:
+                item_num = self._item_num()
+                if self._item_weight.shape[0] != item_num:
+                    raise ValueError(f'item_weight has {self._item_weight.shape[0]} entries for {item_num} items')
+                ti = self._dev['truth_items'].cpu().numpy()[:nt].astype(np.int64)
+                inside = (ti >= 0) & (ti < item_num)
+                w = np.where(inside, self._item_weight[np.where(inside, ti, 0)], np.float32(0.0)).astype(np.float32)
+            if self._user_group is not None and self._user_group.shape[0] != n:
+                raise ValueError(f'user_group has {self._user_group.shape[0]} entries for {n} test users')
+        except ValueError:
+            self._dev = None
+            raise
+        self._weights_host = w
+        self._weights_dev = None if w is None or nt == 0 else torch.from_numpy(w).to(device)
+        self._group_dev = None if self._user_group is None else torch.from_numpy(self._user_group).to(device)
+        self._group_rows, self._group_users = [], []
+        if self._user_group is not None:   # the rows of every group, for its own resampling
+            for g in range(self._n_groups):
+                rows = np.flatnonzero(self._user_group == g)
+                self._group_users.append(int(rows.size))
+                self._group_rows.append(torch.from_numpy(rows).to(device) if rows.size and self.n_boot > 0 else None)
+
+    def _ensure_prepared(self):
+        self.model.eval()
+        if self._dev is None:
+            self._prepare(next(self.model.parameters()).device)
+
+    def per_user(self):
+        """(sums float64 [G + 1, S], per-user values float64 [n, S]) on the device, enqueued on the current stream"""
+        from . import ops
+        self._ensure_prepared()
+        return ops.rank_metrics_weighted(self.ranks(), self._dev['truth_ptr'], self._n_neg, self.top_k_list, self._weights_dev,
+                                         self._group_dev, self._n_groups, True)
+
+    def evaluate_async(self) -> 'PendingEvaluation':
+        """Enqueues the ranking, one rank_metrics_weighted call and -- with n_boot > 0 -- bootstrap_sums over all users and
+        once per group on the current stream and returns at once; result() reads everything back in one copy.  After the
+        first call nothing is copied from the host and nothing synchronises: capturable."""
+        from . import ops
+        self._ensure_prepared()
+        n_users, G, ks = self._users.shape[0], self._n_groups, [int(k) for k in self.top_k_list]
+        n_k, S, n_boot = len(ks), 2 * len(ks) + 2, self.n_boot if self._users.shape[0] > 0 else 0
+        sums, vals = ops.rank_metrics_weighted(self.ranks(), self._dev['truth_ptr'], self._n_neg, ks, self._weights_dev,
+                                               self._group_dev, G, n_boot > 0)
+        outs, boot_of = [sums.reshape(-1)], []   # boot_of: -1 all users, g a group -- the order of the resampled blocks
+        if n_boot > 0:
+            outs.append(ops.bootstrap_sums(vals, n_boot, self.seed).reshape(-1))
+            boot_of.append(-1)
+            for g, rows in enumerate(self._group_rows):
+                if rows is not None:
+                    outs.append(ops.bootstrap_sums(vals.index_select(0, rows), n_boot, self.seed + g).reshape(-1))
+                    boot_of.append(g)
+        out = torch.cat(outs)
+        grouped, group_users, conf = self._user_group is not None, list(self._group_users), self.confidence
+
+        def finish(host: torch.Tensor) -> dict:
+            s = host.numpy()
+            rows = s[:(G + 1) * S].reshape(G + 1, S)
+            res = {}
+            res['recall'], res['dcg'], res['auc'], res['covered'] = _weighted_figures(rows[G], ks)
+            res['users'] = n_users
+            if grouped:
+                per = [_weighted_figures(rows[g], ks) for g in range(G)]
+                res['group_recall'] = {k: [p[0][k] for p in per] for k in ks}
+                res['group_dcg'] = {k: [p[1][k] for p in per] for k in ks}
+                res['group_auc'] = [p[2] for p in per]
+                res['group_users'], res['group_covered'] = group_users, [p[3] for p in per]
+            if self.n_boot > 0:
+                iv = {-1: np.zeros((S, 2))}
+                iv.update({g: np.zeros((S, 2)) for g in range(G)})
+                for at, g in enumerate(boot_of):
+                    lo = (G + 1) * S + at * n_boot * S
+                    iv[g] = ops.bootstrap_intervals(s[lo:lo + n_boot * S].reshape(n_boot, S), S - 1, conf)
+                pair = lambda a, i: (float(a[i][0]), float(a[i][1]))  # noqa: E731
+                res['interval'] = {'recall': {k: pair(iv[-1], i) for i, k in enumerate(ks)},
+                                   'dcg': {k: pair(iv[-1], n_k + i) for i, k in enumerate(ks)}, 'auc': pair(iv[-1], 2 * n_k)}
+                if grouped:
+                    res['interval'].update(
+                        group_recall={k: [pair(iv[g], i) for g in range(G)] for i, k in enumerate(ks)},
+                        group_dcg={k: [pair(iv[g], n_k + i) for g in range(G)] for i, k in enumerate(ks)},
+                        group_auc=[pair(iv[g], 2 * n_k) for g in range(G)])
+            return res
+        return PendingEvaluation(out, finish)
+
+
+def paired_summary(sums_ab, data_a, data_b, confidence: float = 0.95):
+    """The host half of paired_bootstrap: sums_ab [n_boot, 2 S] (the two managers' series side by side under the same draws),
+    data_a / data_b [S] (their sums on the data), the last series of each the covered count -> per series s < S - 1 the tuple
+    (diff, lo, hi, p) of the difference a - b of sum_s / covered."""
+    ab = np.asarray(sums_ab, np.float64)
+    S = ab.shape[1] // 2
+    keep = (ab[:, S - 1] > 0) & (ab[:, 2 * S - 1] > 0)
+    ab = ab[keep]
+    ratio = lambda row: row[:S - 1] / row[S - 1] if row[S - 1] > 0 else np.zeros(S - 1)  # noqa: E731
+    diff = ratio(np.asarray(data_a, np.float64)) - ratio(np.asarray(data_b, np.float64))
+    out = []
+    for s in range(S - 1):
+        if ab.shape[0] == 0:
+            out.append((float(diff[s]), 0.0, 0.0, 1.0))
+            continue
+        d = ab[:, s] / ab[:, S - 1] - ab[:, S + s] / ab[:, 2 * S - 1]
+        lo, hi = np.quantile(d, [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0])
+        share = float(np.mean(d * np.sign(diff[s]) <= 0))
+        out.append((float(diff[s]), float(lo), float(hi), min(1.0, 2.0 * share)))
+    return out
+
+
+def paired_bootstrap(mgr_a, mgr_b, n_boot: int, seed: int = 0, confidence: float = 0.95) -> dict:
+    """A paired bootstrap over users of two ``ImplicitWeightedRankTestManager`` over the same loader, k list, weights and
+    groups (else ValueError): the two per-user matrices side by side, ONE bootstrap_sums call -- both models see the same
+    draws -- and one read-back.  -> {'recall': {k: r}, 'dcg': {k: r}, 'auc': r}, r = {'diff': a - b on the data, 'lo', 'hi':
+    the percentile interval of the replicates' differences, 'p': the share of replicates whose difference has the sign
+    opposite to 'diff' or is 0, doubled and capped at 1}.  At most 15 values of k (PAIRED_MAX_KS: 2 (2 n_k + 2) series <= 64)."""
+    from . import ops
+    for m in (mgr_a, mgr_b):
+        if not isinstance(m, ImplicitWeightedRankTestManager):
+            raise ValueError('paired_bootstrap compares two ImplicitWeightedRankTestManager')
+    ks = [int(k) for k in mgr_a.top_k_list]
+    if ks != [int(k) for k in mgr_b.top_k_list]:
+        raise ValueError(f'the two managers differ in top_k_list: {mgr_a.top_k_list} and {mgr_b.top_k_list}')
+    if len(ks) > PAIRED_MAX_KS:
+        raise ValueError(f'paired_bootstrap takes at most {PAIRED_MAX_KS} values of k, got {len(ks)}')
+    if mgr_a.data_loader is not mgr_b.data_loader or mgr_a.use_item_pool != mgr_b.use_item_pool:
+        raise ValueError('the two managers differ in their loader')
+    if int(n_boot) < 1 or not 0.0 < float(confidence) < 1.0:
+        raise ValueError('n_boot >= 1 and a confidence in (0, 1)')
+    mgr_a._ensure_prepared(); mgr_b._ensure_prepared()
+    same = lambda x, y: (x is None and y is None) or (x is not None and y is not None and np.array_equal(x, y))  # noqa: E731
+    if not same(mgr_a._weights_host, mgr_b._weights_host):
+        raise ValueError('the two managers differ in their weights')
+    if not same(mgr_a._user_group, mgr_b._user_group):
+        raise ValueError('the two managers differ in their user groups')
+    if mgr_a._users.shape[0] == 0:
+        raise ValueError('no test users to resample')
+    (sums_a, vals_a), (sums_b, vals_b) = mgr_a.per_user(), mgr_b.per_user()
+    G, S, n_k = mgr_a._n_groups, 2 * len(ks) + 2, len(ks)
+    boot = ops.bootstrap_sums(torch.cat([vals_a, vals_b], dim=1), int(n_boot), seed)
+    host = torch.cat([sums_a[G], sums_b[G], boot.reshape(-1)]).cpu().numpy()
+    rows = paired_summary(host[2 * S:].reshape(int(n_boot), 2 * S), host[:S], host[S:2 * S], float(confidence))
+    r = lambda t: {'diff': t[0], 'lo': t[1], 'hi': t[2], 'p': t[3]}  # noqa: E731
+    return {'recall': {k: r(rows[i]) for i, k in enumerate(ks)}, 'dcg': {k: r(rows[n_k + i]) for i, k in enumerate(ks)},
+            'auc': r(rows[2 * n_k])}
 
 
 class PendingEvaluation:

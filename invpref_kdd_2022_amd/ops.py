@@ -22,6 +22,7 @@ from . import torch_ops_adam_rows  # noqa: F401  (lazy Adam's fragment: torch.op
 from . import torch_ops_truth_rank  # noqa: F401  (rank-based evaluation's fragment: torch.ops.invpref.truth_ranks*)
 from . import torch_ops_truth_rank_scored  # noqa: F401  (its scaled / weighted forms: truth_ranks_scaled, truth_ranks_weighted)
 from . import torch_ops_catalog  # noqa: F401  (the catalogue metrics' fragment: torch.ops.invpref.catalog_*)
+from . import torch_ops_rank_stats  # noqa: F401  (weighted / grouped rank metrics and bootstrap sums: their fragment)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -523,6 +524,50 @@ def catalog_metrics(items: torch.Tensor, ks, item_num: int, hits: Optional[torch
     has_pop, has_hits, item_num = popularity is not None, hits is not None, int(item_num)
     return PendingEvaluation(out, lambda host: catalog_figures(host.tolist(), ks, item_num, G, has_pop, has_hits,
                                                                truth_group_totals))
+
+
+def rank_metrics_weighted(ranks: torch.Tensor, truth_ptr: torch.Tensor, n_neg: torch.Tensor, top_k_list,
+                          weights: Optional[torch.Tensor] = None, user_group: Optional[torch.Tensor] = None, n_groups: int = 1,
+                          per_user: bool = False):
+    """Propensity-weighted (self-normalised) and user-grouped rank metrics from the truth ranks (include/invpref_rank_stats.h
+    states the formulas): weights float32 [n_truth], one per truth entry (an inverse propensity; 0 / 1 for a subset of the
+    truth items; a weight that is not > 0 counts as 0), without them every weight is 1; user_group int32 [n] with values in
+    [0, n_groups), n_groups <= 16 (another value: in no group), without it every user is in group 0; fewer than 32 values of
+    k, ascending.  -> (sums float64 [n_groups + 1, S], per-user values float64 [n, S], or [0, S] without per_user), S =
+    2 n_k + 2: recall_w@k .., dcg_w@k .., auc_w, covered.  Row n_groups of the sums is the sum over all users; a metric's mean
+    is its sum over the covered count of the same row.  Fixed-order float64 sums: the same bits on every run."""
+    _gpu(ranks, truth_ptr, n_neg, weights, user_group)
+    ks = [int(k) for k in top_k_list]
+    if any(k < 1 for k in ks) or ks != sorted(ks):
+        raise InvPrefError(f'top_k_list {list(top_k_list)}: ascending values of k >= 1')
+    return _o().rank_metrics_weighted(ranks, truth_ptr, n_neg, ks, weights, user_group, int(n_groups), bool(per_user))
+
+
+def bootstrap_sums(vals: torch.Tensor, n_boot: int, seed: int = 0) -> torch.Tensor:
+    """float64 [n_boot, S] on the device: out[b] = the column sums of a resample with replacement of the n rows of vals (float64
+    [n, S] on the GPU, S <= 64, a row stride allowed), the draws made on the device by Philox4x32-10 keyed by the 64 bits of
+    seed (include/invpref_rank_stats.h states the generator and the index mapping): a seed names its draws whatever the
+    launch geometry, and two tables resampled with one seed see the same rows."""
+    _gpu(vals)
+    seed = int(seed)
+    if not -(1 << 63) <= seed < 1 << 64:
+        raise InvPrefError(f'seed {seed} has more than 64 bits')
+    return _o().bootstrap_sums(vals, int(n_boot), seed - (1 << 64) if seed >= 1 << 63 else seed)
+
+
+def bootstrap_intervals(sums, covered_col: int, confidence: float = 0.95):
+    """The host half of a bootstrap of ratio metrics: sums [n_boot, S] (bootstrap_sums read back) -> float64 [S, 2], row s the
+    percentile interval (lo, hi) of sums[:, s] / sums[:, covered_col] at the given confidence -- np.quantile at (1 - c) / 2 and
+    (1 + c) / 2 -- over the replicates with a covered user (sums[:, covered_col] > 0); zeros if there is none."""
+    import numpy as np
+    a = np.asarray(sums, np.float64)
+    c = float(confidence)
+    if a.ndim != 2 or not 0.0 < c < 1.0:
+        raise ValueError('bootstrap_intervals: sums [n_boot, S] and a confidence in (0, 1)')
+    a = a[a[:, covered_col] > 0]
+    if a.shape[0] == 0:
+        return np.zeros((a.shape[1], 2))
+    return np.quantile(a / a[:, covered_col:covered_col + 1], [(1.0 - c) / 2.0, (1.0 + c) / 2.0], axis=0).T.copy()
 
 
 def device_csr(csr, n_rows: int, n_items: int, device):
