@@ -8,9 +8,11 @@ _LINTRANS = ('LinearTransMatrixFactorization', 'LinearTransTrainManager')
 
 _CAUSE = ('CausEMatrixFactorization', 'CausEExplicitMatrixFactorization', 'CausETrainManager', 'CausEExplicitTrainManager')
 
+_BPR = ('BPRTrainManager',)
+
 
 def __getattr__(name):   # resolved on first use: importing the package loads neither torch nor the HIP library
-    if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE:
+    if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE or name in _BPR:
         from . import baseline
         return getattr(baseline, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -102,7 +102,7 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 # baseline with its weighted retrieval (csrc/invpref_lintrans.hip and the same two files), lazy Adam
 # (csrc/invpref_adam_rows.hip), rank-based evaluation (csrc/invpref_truth_rank.hip) and its scaled and weighted forms (the same
 # file), the catalogue metrics (csrc/invpref_catalog.hip), the weighted / grouped rank metrics and the bootstrap sums
-# (csrc/invpref_rank_stats.hip).
+# (csrc/invpref_rank_stats.hip), BPR-MF's negative sampler and gradient pass (csrc/invpref_bpr.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
@@ -124,6 +124,9 @@ CATALOG_MAX_KS, CATALOG_MAX_GROUPS = CATALOG_DEFINES['CATALOG_MAX_KS'], CATALOG_
 RANK_STATS_SIGNATURES, RANK_STATS_DEFINES = _read_header(RANK_STATS_HEADER_PATH)
 RANK_STATS_MAX_KS, RANK_STATS_MAX_GROUPS, RANK_STATS_MAX_SERIES = (
     RANK_STATS_DEFINES['RANK_STATS_' + n] for n in ('MAX_KS', 'MAX_GROUPS', 'MAX_SERIES'))   # n_k < MAX_KS; G, S <= the others
+BPR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_bpr.h')
+BPR_SIGNATURES, BPR_DEFINES = _read_header(BPR_HEADER_PATH)
+BPR_MAX_BATCH, BPR_MAX_STEPS, BPR_MAX_ATTEMPTS = (BPR_DEFINES['BPR_' + n] for n in ('MAX_BATCH', 'MAX_STEPS', 'MAX_ATTEMPTS'))
 CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 # (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
 EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
@@ -133,7 +136,8 @@ EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_H
                  (TRUTH_RANK_HEADER_PATH, 'TRUTH_RANK_SIGNATURES', 'TRUTH_RANK_DEFINES'),
                  (TRUTH_RANK_SCORED_HEADER_PATH, 'TRUTH_RANK_SCORED_SIGNATURES', 'TRUTH_RANK_SCORED_DEFINES'),
                  (CATALOG_HEADER_PATH, 'CATALOG_SIGNATURES', 'CATALOG_DEFINES'),
-                 (RANK_STATS_HEADER_PATH, 'RANK_STATS_SIGNATURES', 'RANK_STATS_DEFINES'))
+                 (RANK_STATS_HEADER_PATH, 'RANK_STATS_SIGNATURES', 'RANK_STATS_DEFINES'),
+                 (BPR_HEADER_PATH, 'BPR_SIGNATURES', 'BPR_DEFINES'))
 
 _lib = None
 

@@ -1400,3 +1400,137 @@ class CausETrainManager(_CausEManagerMixin, BasicImplicitTrainManager):
 
 class CausEExplicitTrainManager(_CausEManagerMixin, BasicExplicitTrainManager):
     """baseline_train.py:725-797 (baseline_explicit/general_bias_with_rct/CausE_mf_main.py)"""
+
+
+# ------------------------------------------------------------------------------------------------ BPR-MF
+class BPRTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
+    """BPR-MF (Rendle et al., UAI 2009) on a plain PureMatrixFactorization: the pairwise ranking loss
+        loss = mean_p w_p (-log sigmoid(Pu[u_p] . Qi[i_p] - Pu[u_p] . Qi[j_p])) + L2_coe * L2_reg + L1_coe * L1_reg
+    over the training POSITIVES (u_p, i_p), each with a negative j_p drawn per step on the device, uniformly over the items
+    outside the user's exclusion list (include/invpref_bpr.h states the loss and the draw rule).  BasicImplicitTrainManager's
+    signature plus three keyword-only arguments:
+
+    seed      names the trajectory: with the global step counter `step_id` it keys every draw, so the same seed gives the same
+              bits whatever the run lengths, with graphs or without
+    weights   one fp32 weight per positive (per row of training_data, or per kept row), e.g. the inverse propensities of
+              ops.count_propensity: IPS-weighted BPR
+    exclude   a CSR (indptr [user_num + 1], indices) of the items never drawn for a user; default: the user's training positives
+
+    Rows of training_data with score <= 0 are dropped at construction (`n_dropped`); the static minibatches are taken over the
+    positives in file order.  Always the unfused sequence, ops.bpr_grad (every row of both gradients overwritten) -> dense /
+    ranged Adam.  Before a run of epochs is enqueued ONE ops.bpr_draw launch and ONE ops.cvib_index pass cover all its steps
+    (the staging hooks of _DrawnTermMixin, the device draw standing where the host staging is); the captured launches read
+    their row of both buffers when they run, so a replay follows new draws without re-capture.  Single process."""
+    _SINGLE = 'BPR runs in a single process (a sharded form would all-reduce the summed gradient of both tables; not implemented)'
+    _LOSS_KEYS = PURE_LOSS_KEYS     # what the pass writes into the first slots of a step's losses
+    _INDEX_BUDGET = _CVIBMixin._INDEX_BUDGET
+    _lazy_adam_unsupported = ('the BPR pass stores zeros to every idle row and Adam runs over the whole tables: a lazy form '
+                              'would update the rows the step\'s triplets touch (a follow-up)')
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, seed: int = 0,
+                 weights=None, exclude=None, rank=None, world_size=None, process_group=None):
+        self._require_single_process(world_size)
+        keep = training_data[:, 2] > 0
+        self.n_dropped = int(training_data.shape[0] - int(keep.sum()))
+        if self.n_dropped == training_data.shape[0]:
+            raise ValueError('BPR trains on positives: training_data has no row with a score > 0')
+        positives = training_data[keep]
+        super().__init__(model, evaluator, device, positives, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        self.seed, self.step_id = int(seed), 0     # step_id: the global step counter, the name of the next step's draws
+        U, I, dev = model.user_num, model.item_num, self.device
+        if exclude is None:
+            u, i = positives[:, 0].cpu().numpy().astype(np.int64), positives[:, 1].cpu().numpy().astype(np.int64)
+            ok = (u >= 0) & (u < U) & (i >= 0) & (i < I)
+            keys = np.unique(u[ok] * I + i[ok])      # (a pair that occurs twice is listed once; each user's items ascending)
+            indptr = np.zeros(U + 1, np.int64)
+            np.cumsum(np.bincount(keys // I, minlength=U), out=indptr[1:])
+            exclude = (indptr, keys % I)
+        self._excl = ops.device_csr(exclude, U, I, dev)
+        self._weights = None
+        if weights is not None:
+            w = torch.as_tensor(weights).detach().reshape(-1).to(torch.float32)
+            if w.numel() == training_data.shape[0]:
+                w = w[keep.to(w.device)]
+            if w.numel() != self.n_total:
+                raise ValueError(f'weights holds {w.numel()} values for {training_data.shape[0]} rows / {self.n_total} positives')
+            self._weights = w.contiguous().to(dev)
+        n, bs = self.n_total, self.batch_size
+        self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]
+        self._cap = max(self._batch_lens)
+        self._init_draws(None, [], self._cap, 2 * self._cap)    # a staging row: the step's users, then its negatives
+        self._draws = self._index = self._caller = None
+        self._bpr_ws = ops.Workspace(dev)
+        self._bpr_ws.get(max(ops.bpr_workspace_bytes(U, I, self._cap, model.factor_num), 16))   # sized once: capturable launches
+
+    _limit_run = _CVIBMixin._limit_run
+
+    def _staging_resized(self, rows: int) -> None:
+        dev = self.device
+        self._draws = self._staged.view(rows, 2, self._cap)
+        self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
+        lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
+        self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
+        self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
+        self._step_ramp = torch.arange(rows, dtype=torch.int64, device=dev)
+        self._step_ids = torch.zeros(rows, dtype=torch.int64, device=dev)
+        self.n_forced = torch.zeros(rows, dtype=torch.int32, device=dev)    # per step of the last staged run
+        for k, b in enumerate(self._raw_batches):       # the minibatches are static: a row's users never change
+            self._draws[k::self.batch_num, 0, :b.n] = b.users.to(torch.int32)
+
+    def _stage_draws(self, n: int) -> None:
+        """the negatives of the next n epochs' steps in one launch, then their index in one pass"""
+        steps = n * self.batch_num
+        torch.add(self._step_ramp[:steps], self.step_id, out=self._step_ids[:steps])
+        ops.bpr_draw(self.users_tensor, self._step_lo[:steps], self._step_n[:steps], self._step_ids[:steps], self._excl,
+                     self.model.item_num, self.seed, out=(self._draws[:steps, 1], self.n_forced[:steps]))
+        ops.cvib_index(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._draws[:steps],
+                       self.model.user_num, self.model.item_num, out=self._index[:steps])
+
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        before = self.epoch_cnt
+        out = super()._enqueue_epochs(want)
+        self.step_id += (self.epoch_cnt - before) * self.batch_num   # (a failed capture runs one eager epoch of the staged n)
+        return out
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        if k is None:
+            users, items, neg, index, w = self._caller
+        else:
+            b, s = self._raw_batches[k], self._loss_slot * self.batch_num + k
+            neg, index = self._draws[s, 1, :b.n], self._index[s]
+            w = None if self._weights is None else self._weights[b.lo:b.lo + b.n]
+        st = self.state
+        ops.bpr_grad(st.p_views[0], st.p_views[1], users, items, neg, index, self.L2_coe, self.L1_coe, st.g_views[0],
+                     st.g_views[1], losses6[:4], weights=w, workspace=self._bpr_ws)
+
+    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
+        """(the pass is the whole step: no further term)"""
+
+    @classmethod
+    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
+        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.tolist()]
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """one step on caller tensors: the rows with a score > 0 are the positives (weight 1), their negatives are drawn under
+        the next step id against the manager's exclusion lists, this minibatch's index is built here"""
+        dev, m = self.device, self.model
+        keep = batch_scores_tensor.detach().reshape(-1).to(dev) > 0
+        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
+        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
+        B = ud.numel()
+        if B == 0:
+            raise ValueError('BPR trains on positives: the minibatch has no row with a score > 0')
+        neg, _ = ops.bpr_draw(ud, torch.zeros(1, dtype=torch.int64, device=dev), torch.full((1,), B, dtype=torch.int32, device=dev),
+                              torch.full((1,), self.step_id, dtype=torch.int64, device=dev), self._excl, m.item_num, self.seed,
+                              batch_cap=B)
+        self._bpr_ws.get(max(ops.bpr_workspace_bytes(m.user_num, m.item_num, B, m.factor_num), 16))
+        self._caller = (ud, vd, neg[0], ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd), None)
+        try:
+            out = self._batch_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), None, lambda: None)
+        finally:
+            self._caller = None
+        self.step_id += 1
+        return out

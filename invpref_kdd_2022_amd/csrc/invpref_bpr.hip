@@ -1,0 +1,470 @@
+// invpref_bpr.hip -- BPR-MF (include/invpref_bpr.h): the negative sampler of a run of steps and the gradient pass of one step
+// over its 2B signed pairs, (u, i+, +g) and (u, j-, -g).
+//
+// The draw.  One thread per (step, position): Philox4x32-10 keyed by the seed, the counter (position, quad, step id), a word
+// per attempt, the candidate (word * item_num) >> 32, a bisection of the user's ascending exclusion list.  Quads are made as
+// they are needed -- with a short list the first word is accepted almost always.  The only atomics are integer ones, on the
+// count of forced draws.
+//
+// The pass.  CVIB's scheme (invpref_cvib.hip) with the pair's factor formed by a pairs launch instead of two means:
+//   pairs     a 16-lane group per triplet (kernel_common.hpp: a row on 16 lanes): the three rows, x = Pu[u] . Qi[i] -
+//             Pu[u] . Qi[j] with dot64 of row_pass.hpp, -log sigmoid(x) and the regulariser sums as float64, one partial per
+//             workgroup (group_sums), and the record g = -w sigmoid(-x) / B, ONE float
+//   scatter   per side (user rows, item rows) the 2B positions come sorted by destination row (the inverted index of
+//             invpref_cvib_index_hip).  A 16-lane group owns one chunk of C consecutive entries and walks it in order:
+//             index entry -> the triplet's three ids and g -> the partner row, kAhead entries in flight together;
+//             acc += +-g * partner row in float64, and at the end of a destination acc += n * regulariser gradient of the
+//             destination row, n the gathers of that row among the entries added (an item row: every entry; a user row: the
+//             entries of positions p < B, since a triplet gathers its user row once).  A destination whose entries all lie
+//             inside the chunk is stored by that group; one that continues from the previous chunk or into the next leaves its
+//             float64 partial in the chunk's head or tail slot
+//   boundary  the group of the chunk in which such a destination STARTS finds the row's last chunk by bisection, adds the
+//             partials in chunk order and stores the row
+//   fold      one wave: the partials in workgroup order -> losses4
+// Every row has one writer and every sum a fixed order: the same bits on every run.  The slots are float64, so a row is
+// rounded to fp32 once however many chunks it spans.  Both gradient tables are zero-filled on the stream in front of the
+// scatter (rows without a triplet hold zeros afterwards), so the writers store and never read the tables.
+//
+// A triplet with any id outside its table is skipped by BOTH of its positions (the scatter reads the triplet's three ids, not
+// the pair's two: the index files position p under u even when only j is bad); the pairs launch counts it and the fold makes
+// the four losses NaN.  Nothing read from the device is an address before it is range-checked.
+#include "row_pass.hpp"
+
+#include <algorithm>
+
+#include "../../include/invpref_bpr.h"
+
+using namespace invpref;
+
+namespace {
+
+constexpr int64_t kI32Max = 2147483647;
+constexpr int kMaxQuads = INVPREF_BPR_MAX_ATTEMPTS / 4;
+
+// Philox4x32-10 (Salmon et al., SC 2011; Random123's constants), as in invpref_rank_stats.hip
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&x)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
+}
+
+__global__ __launch_bounds__(256) void bpr_draw_kernel(const int64_t *__restrict__ users, int64_t n_len,
+                                                       const int64_t *__restrict__ step_lo, const int32_t *__restrict__ step_n,
+                                                       const int64_t *__restrict__ step_id, const int32_t *__restrict__ excl_ptr,
+                                                       const int32_t *__restrict__ excl_items, int excl_len, int64_t U,
+                                                       uint32_t item_num, uint32_t k0, uint32_t k1, int32_t *__restrict__ neg,
+                                                       int64_t neg_stride, int cap, int32_t *__restrict__ n_forced) {
+    const int p = (int)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (p >= cap) return;
+    int32_t out = -1;
+    const int64_t at = step_lo[s] + p;
+    if (p < step_n[s] && at >= 0 && at < n_len) {
+        const int64_t u = users[at];
+        if (u >= 0 && u < U) {
+            const int lo0 = min(max(excl_ptr[u], 0), excl_len), hi0 = min(max(excl_ptr[u + 1], lo0), excl_len);
+            const uint64_t sid = (uint64_t)step_id[s];
+            bool found = false;
+            for (int q = 0; q < kMaxQuads && !found; q++) {
+                uint32_t x[4];
+                philox4x32_10((uint32_t)p, (uint32_t)q, (uint32_t)sid, (uint32_t)(sid >> 32), k0, k1, x);
+#pragma unroll
+                for (int w = 0; w < 4; w++) {
+                    if (found) continue;
+                    const int cand = (int)(((uint64_t)x[w] * (uint64_t)item_num) >> 32);
+                    int lo = lo0, hi = hi0;          // the first entry >= cand
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (excl_items[mid] < cand) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    out = cand;
+                    found = !(lo < hi0 && excl_items[lo] == cand);
+                }
+            }
+            if (!found) atomicAdd(n_forced + s, 1);
+        }
+    }
+    neg[(int64_t)s * neg_stride + p] = out;
+}
+
+// ---- the pass
+constexpr int kRec = 4;   // float64 sums per workgroup: -log sigmoid, squares, absolute values, skipped triplets
+
+__host__ __device__ inline int chunk_of(int64_t n2) { return n2 <= 65536 ? 16 : 128; }
+
+struct Layout {
+    size_t g, partials, part, total;
+    int nwg, nchunk, C, Dp;
+};
+inline Layout layout_of(int64_t B, int64_t D) {
+    Layout L;
+    const int64_t n2 = 2 * B;
+    L.C = chunk_of(n2);
+    L.nwg = (int)((B + kGroups - 1) / kGroups);
+    L.nchunk = (int)((n2 + L.C - 1) / L.C);
+    L.Dp = (int)((D + 3) / 4 * 4);
+    Carver ws;
+    L.g = ws.take(sizeof(float) * (size_t)B);
+    L.partials = ws.take(sizeof(double) * kRec * (size_t)L.nwg);
+    // (the chunk grows from 16 to 128 entries beyond 65 536 positions: keep the size non-decreasing across that step)
+    const size_t slots = n2 <= 65536 ? (size_t)L.nchunk : (size_t)std::max(L.nchunk, 4096);
+    L.part = ws.take(sizeof(double) * 2 * slots * 2 * (size_t)L.Dp);   // two sides, head and tail
+    L.total = ws.bytes();
+    return L;
+}
+
+template <int NC>
+__device__ __forceinline__ void norms64(const float4 (&r)[NC], double &sq, double &ab) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        sq = sq + (double)r[c].x * (double)r[c].x;
+        sq = sq + (double)r[c].y * (double)r[c].y;
+        sq = sq + (double)r[c].z * (double)r[c].z;
+        sq = sq + (double)r[c].w * (double)r[c].w;
+        ab = ab + fabs((double)r[c].x);
+        ab = ab + fabs((double)r[c].y);
+        ab = ab + fabs((double)r[c].z);
+        ab = ab + fabs((double)r[c].w);
+    }
+}
+
+template <int NC, bool VEC>
+__global__ __launch_bounds__(256) void bpr_pairs_kernel(const float *__restrict__ Pu, int U, const float *__restrict__ Qi, int I,
+                                                        int D, const int64_t *__restrict__ users,
+                                                        const int64_t *__restrict__ pos_items, const int32_t *__restrict__ neg,
+                                                        const float *__restrict__ weights, int B, float *__restrict__ g,
+                                                        double *__restrict__ partials, int64_t stride) {
+    const int l16 = threadIdx.x & (kRow - 1);
+    const int p = (int)blockIdx.x * kGroups + threadIdx.x / kRow;
+    double mine[kRec] = {0.0, 0.0, 0.0, 0.0};
+    if (p < B) {                                        // (the same for the 16 lanes of a group)
+        const int64_t u = users[p], i = pos_items[p], j = neg[p];
+        const double w = weights ? (double)weights[p] : 1.0;
+        const bool valid = u >= 0 && u < U && i >= 0 && i < I && j >= 0 && j < I;
+        float4 a[NC], bi[NC], bj[NC];
+        load_row<NC, VEC>(Pu, std::min<int64_t>(std::max<int64_t>(u, 0), U - 1), D, l16, a);
+        load_row<NC, VEC>(Qi, std::min<int64_t>(std::max<int64_t>(i, 0), I - 1), D, l16, bi);
+        load_row<NC, VEC>(Qi, std::min<int64_t>(std::max<int64_t>(j, 0), I - 1), D, l16, bj);
+        const double x = dot64<NC>(a, bi) - dot64<NC>(a, bj);
+        double sq = 0.0, ab = 0.0;
+        norms64<NC>(a, sq, ab);
+        norms64<NC>(bi, sq, ab);
+        norms64<NC>(bj, sq, ab);
+        sq = row16_sum64(sq);
+        ab = row16_sum64(ab);
+        if (l16 == 0) {
+            // -log sigmoid(x) = max(-x, 0) + log1p(exp(-|x|)); sigmoid(-x) = e / (1 + e) (x >= 0), 1 / (1 + e) (x < 0), e = exp(-|x|)
+            const double e = exp(-fabs(x));
+            const double nls = fmax(-x, 0.0) + log1p(e);
+            const double sneg = x >= 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e);
+            g[p] = valid ? (float)(-w * sneg / (double)B) : 0.0f;
+            if (valid) {
+                mine[0] = w * nls;
+                mine[1] = sq;
+                mine[2] = ab;
+            } else {
+                mine[3] = 1.0;
+            }
+        }
+    }
+    group_sums<kRec>(mine, partials, stride);
+}
+
+__global__ __launch_bounds__(64) void bpr_fold_kernel(const double *__restrict__ partials, int nwg, int64_t stride, double B,
+                                                      double D, double L2_coe, double L1_coe, float *__restrict__ losses4) {
+    const double score = fold64(partials, nwg), sq = fold64(partials + stride, nwg), ab = fold64(partials + 2 * stride, nwg);
+    const double skipped = fold64(partials + 3 * stride, nwg);
+    if (threadIdx.x != 0) return;
+    const double nan = (double)__builtin_nanf("");
+    const bool bad = skipped != 0.0;
+    const double sl = score / B, l2 = sq / (B * D), l1 = ab / (B * D);
+    losses4[0] = (float)(bad ? nan : sl);
+    losses4[1] = (float)(bad ? nan : l2);
+    losses4[2] = (float)(bad ? nan : l1);
+    losses4[3] = (float)(bad ? nan : (sl + L2_coe * l2) + L1_coe * l1);
+}
+
+// a chunk slot: Dp = D rounded up to 4 floats, doubles (the entries beyond D are the zeros load_row filled in)
+template <int NC>
+__device__ __forceinline__ void slot_store(double *__restrict__ slot, int Dp, int l16, const double4_t (&v)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int i0 = (l16 + kRow * c) * 4;
+        if (i0 < Dp) {
+            slot[i0 + 0] = v[c].x; slot[i0 + 1] = v[c].y; slot[i0 + 2] = v[c].z; slot[i0 + 3] = v[c].w;
+        }
+    }
+}
+template <int NC>
+__device__ __forceinline__ void slot_add(const double *__restrict__ slot, int Dp, int l16, double4_t (&v)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int i0 = (l16 + kRow * c) * 4;
+        if (i0 < Dp) {
+            v[c].x = v[c].x + slot[i0 + 0]; v[c].y = v[c].y + slot[i0 + 1];
+            v[c].z = v[c].z + slot[i0 + 2]; v[c].w = v[c].w + slot[i0 + 3];
+        }
+    }
+}
+// a slot's values without a branch: a lane beyond Dp reads the slot's first entries and keeps zeros
+template <int NC>
+__device__ __forceinline__ void slot_load(const double *__restrict__ slot, int Dp, int l16, double4_t (&v)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int i0 = (l16 + kRow * c) * 4;
+        const bool in = i0 < Dp;
+        const double *p = slot + (in ? i0 : 0);
+        const double x = p[0], y = p[1], z = p[2], w = p[3];
+        v[c].x = in ? x : 0.0; v[c].y = in ? y : 0.0; v[c].z = in ? z : 0.0; v[c].w = in ? w : 0.0;
+    }
+}
+template <int NC>
+__device__ __forceinline__ void zero_acc(double4_t (&v)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) v[c].x = v[c].y = v[c].z = v[c].w = 0.0;
+}
+template <int NC>
+__device__ __forceinline__ void round_row(const double4_t (&v)[NC], float4 (&r)[NC]) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) r[c] = make_float4((float)v[c].x, (float)v[c].y, (float)v[c].z, (float)v[c].w);
+}
+__device__ __forceinline__ double reg_of(double x, double n2, double n1) {
+    return n2 * x + n1 * (x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0));   // (a NaN entry: n2 * NaN)
+}
+
+// entries whose index -> ids -> row chain is in flight together (8 NC + 8 registers per entry next to the 8 NC of the float64
+// accumulator: eight entries of 128-float rows took all 256 registers and left one wave per SIMD)
+template <int NC>
+constexpr int ahead_of() { return NC == 1 ? 8 : 4; }
+
+template <int NC, bool VEC>
+__global__ __launch_bounds__(256) void bpr_scatter_kernel(const float *__restrict__ Pu, int U, const float *__restrict__ Qi, int I,
+                                                          int D, const int64_t *__restrict__ users,
+                                                          const int64_t *__restrict__ pos_items, const int32_t *__restrict__ neg,
+                                                          int B, const int2 *__restrict__ index, int64_t stride, int C,
+                                                          int nchunk, const float *__restrict__ g, double r2, double r1,
+                                                          float *__restrict__ gu, float *__restrict__ gi,
+                                                          double *__restrict__ part, int Dp) {
+    const int l16 = threadIdx.x & (kRow - 1);
+    const int grp = (int)blockIdx.x * kGroups + threadIdx.x / kRow;
+    if (grp >= 2 * nchunk) return;
+    const int side = grp >= nchunk ? 1 : 0, c = grp - side * nchunk;   // side 0: user rows, partner Qi; side 1: item rows, partner Pu
+    const int n2 = 2 * B;
+    const int2 *idx = index + side * stride;
+    const int lim = side ? I : U, plim = side ? U : I;
+    const float *ptab = side ? Pu : Qi, *dtab = side ? Qi : Pu;
+    float *gtab = side ? gi : gu;
+    const int e0 = c * C, e1 = min(e0 + C, n2);
+    const int first = idx[e0].x;
+    if (first < 0 || first >= lim) return;   // the sentinel destination sorts last: nothing left in this list
+    const bool head0 = c > 0 && idx[e0 - 1].x == first;
+    const int next_id = e1 < n2 ? idx[e1].x : -1;
+    double *slot = part + ((int64_t)(side * nchunk + c) * 2) * Dp;
+    double4_t acc[NC];
+    zero_acc<NC>(acc);
+    int cur = first, cnt = 0;
+    bool cur_head = head0, live = true;
+    auto flush = [&](bool head, bool tail) {
+        float4 d[NC];
+        load_row<NC, VEC>(dtab, cur, D, l16, d);
+        const double n2r = (double)cnt * r2, n1r = (double)cnt * r1;
+#pragma unroll
+        for (int k = 0; k < NC; k++) {
+            acc[k].x = acc[k].x + reg_of((double)d[k].x, n2r, n1r);
+            acc[k].y = acc[k].y + reg_of((double)d[k].y, n2r, n1r);
+            acc[k].z = acc[k].z + reg_of((double)d[k].z, n2r, n1r);
+            acc[k].w = acc[k].w + reg_of((double)d[k].w, n2r, n1r);
+        }
+        if (!head && !tail) {
+            float4 r[NC];
+            round_row<NC>(acc, r);
+            store_row<NC, VEC>(gtab, cur, D, l16, r);
+        } else {
+            slot_store<NC>(slot + (head ? 0 : Dp), Dp, l16, acc);
+        }
+    };
+    constexpr int kAhead = ahead_of<NC>();
+    for (int e = e0; e < e1 && live; e += kAhead) {
+        int2 en[kAhead];
+        int64_t tu[kAhead], ti[kAhead];
+        int tj[kAhead];
+        float tg[kAhead];
+        float4 rows[kAhead][NC];
+#pragma unroll
+        for (int j = 0; j < kAhead; j++) en[j] = idx[min(e + j, e1 - 1)];
+#pragma unroll
+        for (int j = 0; j < kAhead; j++) {
+            const int pos = min(max(en[j].y, 0), n2 - 1), p = pos < B ? pos : pos - B;
+            tu[j] = users[p];
+            ti[j] = pos_items[p];
+            tj[j] = neg[p];
+            tg[j] = g[p];
+        }
+#pragma unroll
+        for (int j = 0; j < kAhead; j++) {
+            const int64_t pid = side ? tu[j] : (en[j].y < B ? ti[j] : (int64_t)tj[j]);
+            load_row<NC, VEC>(ptab, std::min<int64_t>(std::max<int64_t>(pid, 0), plim - 1), D, l16, rows[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < kAhead; j++) {
+            if (!live || e + j >= e1) continue;
+            const int dest = en[j].x;
+            if (dest < 0 || dest >= lim) {   // the sentinel destination, from here to the end of the list
+                live = false;
+                continue;
+            }
+            if (dest != cur) {
+                flush(cur_head, false);
+                zero_acc<NC>(acc);
+                cur = dest;
+                cnt = 0;
+                cur_head = false;
+            }
+            // the whole triplet decides, not the pair: a bad negative silences the positive's position too
+            if (en[j].y < 0 || en[j].y >= n2 || tu[j] < 0 || tu[j] >= U || ti[j] < 0 || ti[j] >= I || tj[j] < 0 || tj[j] >= I)
+                continue;
+            cnt += (side || en[j].y < B) ? 1 : 0;   // (a triplet gathers its user row once: the user side counts position p only)
+            axpy_row<NC>(acc, en[j].y < B ? tg[j] : -tg[j], rows[j]);
+        }
+    }
+    flush(cur_head, live && next_id == cur);
+}
+
+template <int NC, bool VEC>
+__global__ __launch_bounds__(256) void bpr_boundary_kernel(const int2 *__restrict__ index, int64_t stride, int B, int C, int nchunk,
+                                                           int U, int I, int D, int Dp, const double *__restrict__ part,
+                                                           float *__restrict__ gu, float *__restrict__ gi) {
+    const int l16 = threadIdx.x & (kRow - 1);
+    const int grp = (int)blockIdx.x * kGroups + threadIdx.x / kRow;
+    if (grp >= 2 * nchunk) return;
+    const int side = grp >= nchunk ? 1 : 0, c = grp - side * nchunk;
+    const int n2 = 2 * B;
+    const int2 *idx = index + side * stride;
+    const int lim = side ? I : U;
+    const int e0 = c * C, e1 = min(e0 + C, n2);
+    if (e1 >= n2) return;
+    const int last = idx[e1 - 1].x;
+    if (last < 0 || last >= lim || idx[e1].x != last) return;          // nothing continues into the next chunk
+    if (c > 0 && idx[e0].x == last && idx[e0 - 1].x == last) return;   // it started earlier: that chunk's group owns the row
+    const double *slots = part + ((int64_t)side * nchunk * 2) * Dp;
+    double4_t sum[NC];
+    zero_acc<NC>(sum);
+    slot_add<NC>(slots + ((int64_t)c * 2 + 1) * Dp, Dp, l16, sum);
+    // the last chunk that STARTS with this row (chunk starts are sorted like the entries, and chunk c + 1 does): a bisection
+    // instead of a walk, so that the head slots below are independent loads
+    int lo = c + 1, hi = nchunk - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (idx[(int64_t)mid * C].x == last) lo = mid;
+        else hi = mid - 1;
+    }
+    // the head slots in chunk order, kBatch of them loaded before the first is added: the order of the sum is the walk's, and
+    // the loads are straight-line code (slot_load: no branch around a load), so they are in flight together
+    constexpr int kBatch = 16 / NC;
+    int cc = c + 1;
+    for (; cc + kBatch - 1 <= lo; cc += kBatch) {
+        double4_t v[kBatch][NC];
+#pragma unroll
+        for (int j = 0; j < kBatch; j++) slot_load<NC>(slots + ((int64_t)(cc + j) * 2) * Dp, Dp, l16, v[j]);
+#pragma unroll
+        for (int j = 0; j < kBatch; j++) {
+#pragma unroll
+            for (int k = 0; k < NC; k++) {
+                sum[k].x = sum[k].x + v[j][k].x; sum[k].y = sum[k].y + v[j][k].y;
+                sum[k].z = sum[k].z + v[j][k].z; sum[k].w = sum[k].w + v[j][k].w;
+            }
+        }
+    }
+    for (; cc <= lo; cc++) slot_add<NC>(slots + ((int64_t)cc * 2) * Dp, Dp, l16, sum);
+    float4 r[NC];
+    round_row<NC>(sum, r);
+    store_row<NC, VEC>(side ? gi : gu, last, D, l16, r);
+}
+
+}  // namespace
+
+extern "C" {
+
+int invpref_bpr_draw_hip(const int64_t *users, int64_t n_users_len, const int64_t *step_lo, const int32_t *step_n,
+                         const int64_t *step_id, int64_t steps, const int32_t *excl_ptr, const int32_t *excl_items,
+                         int64_t excl_len, int64_t user_num, int64_t item_num, int64_t seed, int32_t *neg, int64_t neg_stride,
+                         int64_t batch_cap, int32_t *n_forced, void *stream) {
+    if (!users || !step_lo || !step_n || !step_id || !excl_ptr || !neg || !n_forced || n_users_len < 1 || steps < 1 ||
+        excl_len < 0 || (excl_len > 0 && !excl_items) || user_num < 1 || item_num < 1 || batch_cap < 1 || neg_stride < batch_cap)
+        return INVPREF_EINVAL;
+    if (item_num > kI32Max || user_num > kI32Max || excl_len > kI32Max || batch_cap > INVPREF_BPR_MAX_BATCH ||
+        steps > INVPREF_BPR_MAX_STEPS)
+        return INVPREF_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = (int)hipMemsetAsync(n_forced, 0, sizeof(int32_t) * (size_t)steps, st);
+    if (rc) return rc;
+    const uint64_t bits = (uint64_t)seed;
+    hipLaunchKernelGGL(bpr_draw_kernel, dim3((unsigned)((batch_cap + 255) / 256), (unsigned)steps), dim3(256), 0, st, users,
+                       n_users_len, step_lo, step_n, step_id, excl_ptr, excl_items, (int)excl_len, user_num, (uint32_t)item_num,
+                       (uint32_t)bits, (uint32_t)(bits >> 32), neg, neg_stride, (int)batch_cap, n_forced);
+    return (int)hipGetLastError();
+}
+
+size_t invpref_bpr_workspace_bytes(int64_t user_num, int64_t item_num, int64_t batch, int64_t factor_num) {
+    if (user_num < 1 || item_num < 1 || batch < 1 || factor_num < 1 || factor_num > INVPREF_MAX_FACTORS ||
+        batch > INVPREF_BPR_MAX_BATCH || user_num > kI32Max || item_num > kI32Max)
+        return 0;
+    return layout_of(batch, factor_num).total;
+}
+
+int invpref_bpr_grad_hip(const float *user_table, int64_t user_num, const float *item_table, int64_t item_num,
+                         int64_t factor_num, const int64_t *users, const int64_t *pos_items, const int32_t *neg,
+                         const float *weights, int64_t batch, const int32_t *index, int64_t index_stride, double L2_coe,
+                         double L1_coe, float *grad_user, float *grad_item, float *losses4, void *workspace,
+                         size_t workspace_bytes, void *stream) {
+    if (!user_table || !item_table || !users || !pos_items || !neg || !index || !grad_user || !grad_item || !losses4 ||
+        !workspace || user_num < 1 || item_num < 1 || factor_num < 1 || batch < 1 || index_stride < 2 * batch)
+        return INVPREF_EINVAL;
+    if (factor_num > INVPREF_MAX_FACTORS || batch > INVPREF_BPR_MAX_BATCH || index_stride > 2 * (int64_t)INVPREF_BPR_MAX_BATCH ||
+        user_num > kI32Max || item_num > kI32Max)
+        return INVPREF_EUNSUPPORTED;
+    if (workspace_bytes < invpref_bpr_workspace_bytes(user_num, item_num, batch, factor_num)) return INVPREF_EWORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15u) return INVPREF_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const Layout L = layout_of(batch, factor_num);
+    char *ws = reinterpret_cast<char *>(workspace);
+    float *g = reinterpret_cast<float *>(ws + L.g);
+    double *partials = reinterpret_cast<double *>(ws + L.partials);
+    double *part = reinterpret_cast<double *>(ws + L.part);
+    const int U = (int)user_num, I = (int)item_num, D = (int)factor_num, B = (int)batch;
+    const bool vec = rows_vec_ok(D, user_table, item_table, grad_user, grad_item);
+    const int2 *idx = reinterpret_cast<const int2 *>(index);
+    const unsigned sgrid = (unsigned)((2 * L.nchunk + kGroups - 1) / kGroups);
+    const double BD = (double)batch * (double)factor_num;
+    int rc;
+    if ((rc = (int)hipMemsetAsync(grad_user, 0, sizeof(float) * (size_t)user_num * (size_t)factor_num, st))) return rc;
+    if ((rc = (int)hipMemsetAsync(grad_item, 0, sizeof(float) * (size_t)item_num * (size_t)factor_num, st))) return rc;
+    return with_row_shape(D, vec, [&](auto nc_c, auto vec_c) {
+        constexpr int NC = decltype(nc_c)::value;
+        constexpr bool VEC = decltype(vec_c)::value;
+        int rc;
+        hipLaunchKernelGGL((bpr_pairs_kernel<NC, VEC>), dim3((unsigned)L.nwg), dim3(256), 0, st, user_table, U, item_table, I, D,
+                           users, pos_items, neg, weights, B, g, partials, (int64_t)L.nwg);
+        if ((rc = (int)hipGetLastError())) return rc;
+        hipLaunchKernelGGL((bpr_scatter_kernel<NC, VEC>), dim3(sgrid), dim3(256), 0, st, user_table, U, item_table, I, D, users,
+                           pos_items, neg, B, idx, index_stride, L.C, L.nchunk, g, 2.0 * L2_coe / BD, L1_coe / BD, grad_user,
+                           grad_item, part, L.Dp);
+        if ((rc = (int)hipGetLastError())) return rc;
+        hipLaunchKernelGGL((bpr_boundary_kernel<NC, VEC>), dim3(sgrid), dim3(256), 0, st, idx, index_stride, B, L.C, L.nchunk, U,
+                           I, D, L.Dp, part, grad_user, grad_item);
+        if ((rc = (int)hipGetLastError())) return rc;
+        hipLaunchKernelGGL(bpr_fold_kernel, dim3(1), dim3(64), 0, st, partials, L.nwg, (int64_t)L.nwg, (double)batch,
+                           (double)factor_num, L2_coe, L1_coe, losses4);
+        return (int)hipGetLastError();
+    });
+}
+
+}  // extern "C"

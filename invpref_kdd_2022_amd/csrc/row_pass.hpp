@@ -1,6 +1,7 @@
 // row_pass.hpp -- the gradient-pass recipe "pairs -> rows -> fold" that the MACR-MF and CausE baselines share (invpref_macr.hip,
-// invpref_cause.hip; included by those two files only -- step_wide.hpp's load_row / store_row family addresses rows differently
-// and stays apart).
+// invpref_cause.hip; invpref_lintrans.hip is on it too, and invpref_bpr.hip takes its float64 helpers -- dot64, axpy_row,
+// store_row, group_sums, fold64 -- for a pairs / scatter / boundary / fold pass; step_wide.hpp's load_row / store_row family
+// addresses rows differently and stays apart).
 //
 //   pairs   one 16-lane group per position (lane l owns the float4 chunks l, l + 16, ... of a row: kernel_common.hpp): gathers
 //           the position's two rows, forms its loss terms (float64 partials per workgroup) and a small record of the position

@@ -23,6 +23,7 @@ from . import torch_ops_truth_rank  # noqa: F401  (rank-based evaluation's fragm
 from . import torch_ops_truth_rank_scored  # noqa: F401  (its scaled / weighted forms: truth_ranks_scaled, truth_ranks_weighted)
 from . import torch_ops_catalog  # noqa: F401  (the catalogue metrics' fragment: torch.ops.invpref.catalog_*)
 from . import torch_ops_rank_stats  # noqa: F401  (weighted / grouped rank metrics and bootstrap sums: their fragment)
+from . import torch_ops_bpr  # noqa: F401  (BPR-MF's fragment: torch.ops.invpref.bpr_draw, bpr_grad_)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -1015,3 +1016,71 @@ def cause_grad(params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor], 
     _o().cause_grad_(*params4, users, items, scores, *index, uni_users, uni_items, uni_scores, *uni_index, bool(implicit),
                      CAUSE_MODES[mode] if isinstance(mode, str) else int(mode), float(L2_coe), float(teacher_L2_coe),
                      float(uniform_loss_coe), float(teacher_reg_coe), *grads4, losses5, ws)
+
+
+# ---- BPR-MF (include/invpref_bpr.h, csrc/invpref_bpr.hip)
+def _seed64(seed) -> int:
+    """a seed of up to 64 bits as the int64 the operators carry"""
+    seed = int(seed)
+    if not -(1 << 63) <= seed < 1 << 64:
+        raise InvPrefError(f'seed {seed} has more than 64 bits')
+    return seed - (1 << 64) if seed >= 1 << 63 else seed
+
+
+def bpr_draw(users: torch.Tensor, step_lo: torch.Tensor, step_n: torch.Tensor, step_id: torch.Tensor, exclude, item_num: int,
+             seed: int = 0, batch_cap: Optional[int] = None, out=None):
+    """The negatives of a run of steps in ONE launch.  Step s holds the step_n[s] (int32) positives whose users are
+    users[step_lo[s]:] (int64; step_lo int64) and draws under the name step_id[s] (int64: a global step counter, distinct for
+    every step ever issued); exclude = (excl_ptr int32 [user_num + 1], excl_items int32, ascending within a user), the form
+    device_csr returns.  -> (neg int32 [steps, batch_cap], n_forced int32 [steps]), written into `out` = (neg, n_forced) if
+    given (then nothing is allocated: capturable; neg may be rows of a wider buffer).  The draw rule is stated in
+    include/invpref_bpr.h: Philox4x32-10 keyed by seed, counter (position, quad, step_id), candidate (word * item_num) >> 32,
+    the first of 16 candidates outside the user's list -- the 16th regardless, counted in n_forced.  neg is -1 at a position
+    beyond step_n[s] and where the user id lies outside the table.  The caller guarantees step_n[s] <= batch_cap."""
+    excl_ptr, excl_items = exclude
+    _gpu(users, step_lo, step_n, step_id, excl_ptr, excl_items)
+    steps = step_lo.numel()
+    if out is None:
+        if batch_cap is None:
+            raise InvPrefError('bpr_draw: give batch_cap (the row length of neg) or out=(neg, n_forced)')
+        out = (torch.empty(steps, int(batch_cap), dtype=torch.int32, device=users.device),
+               torch.empty(steps, dtype=torch.int32, device=users.device))
+    neg, n_forced = out
+    _gpu(neg, n_forced)
+    _o().bpr_draw(users, step_lo, step_n, step_id, excl_ptr, excl_items, int(item_num), _seed64(seed), neg, n_forced)
+    return neg, n_forced
+
+
+def bpr_workspace_bytes(user_num: int, item_num: int, batch: int, factor_num: int) -> int:
+    """the records, float64 partials and chunk slots of one gradient pass: a function of the sizes alone, non-decreasing in
+    each; 0: not taken"""
+    return int(_capi.lib().invpref_bpr_workspace_bytes(int(user_num), int(item_num), int(batch), int(factor_num)))
+
+
+def bpr_index(users: torch.Tensor, neg: torch.Tensor, item_num: int, user_num: int, pos_items: torch.Tensor) -> torch.Tensor:
+    """The inverted index of ONE step's 2B signed positions, int32 [2, 2 B, 2], through cvib_index: position p is (u_p, i_p),
+    position B + p is (u_p, j_p).  For single calls; a manager indexes a whole run of steps in one cvib_index pass."""
+    B, dev = users.numel(), users.device
+    draws = torch.stack([users.to(torch.int32), neg.to(torch.int32)])[None].contiguous()
+    return cvib_index(users, pos_items, torch.zeros(1, dtype=torch.int64, device=dev),
+                      torch.full((1,), B, dtype=torch.int32, device=dev), draws, user_num, item_num)[0]
+
+
+def bpr_grad(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, pos_items: torch.Tensor, neg: torch.Tensor,
+             index: torch.Tensor, L2_coe: float, L1_coe: float, grad_user: torch.Tensor, grad_item: torch.Tensor,
+             losses4: torch.Tensor, weights: Optional[torch.Tensor] = None, workspace: Optional[Workspace] = None) -> None:
+    """The gradient pass of one BPR step over the triplets (users int64, pos_items int64, neg int32: [B]) with optional
+    per-triplet weights (fp32 [B]): loss = mean(-w log sigmoid(Pu[u] . Qi[i] - Pu[u] . Qi[j])) + L2_coe L2_reg + L1_coe L1_reg
+    (include/invpref_bpr.h).  index: the step's slice of cvib_index with (users as int32, neg) as the drawn pairs (bpr_index
+    for one step).  OVERWRITES every row of grad_user / grad_item (rows without a triplet get zeros) and losses4 =
+    (score_loss, L2_reg, L1_reg, loss).  Bitwise reproducible, no float atomics, no host sync (capturable once the workspace
+    is sized; a replay reads ids, negatives, weights and index as they are then).  A triplet with an id outside its table
+    (neg = -1 included) is skipped whole and the four losses are NaN."""
+    _gpu(user_table, item_table, users, pos_items, neg, index, grad_user, grad_item, losses4, weights)
+    nbytes = bpr_workspace_bytes(user_table.shape[0], item_table.shape[0], users.numel(), user_table.shape[1])
+    if nbytes == 0:
+        raise InvPrefError(f'bpr_grad: sizes outside the kernels\' range (tables {tuple(user_table.shape)} / '
+                           f'{tuple(item_table.shape)}, {users.numel()} triplets)')
+    ws = (workspace or Workspace(user_table.device)).get(nbytes)
+    _o().bpr_grad_(user_table, item_table, users, pos_items, neg, weights, index, float(L2_coe), float(L1_coe), grad_user,
+                   grad_item, losses4, ws)
