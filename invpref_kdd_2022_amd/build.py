@@ -19,7 +19,7 @@ SOURCES = ['invpref_kernels.hip', 'invpref_step.hip', 'invpref_eval.hip', 'invpr
            'invpref_cause.hip', 'invpref_lintrans.hip', 'invpref_adam_rows.hip', 'invpref_truth_rank.hip',
            'invpref_catalog.hip', 'invpref_rank_stats.hip', 'invpref_bpr.hip']
 HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'adam_apply.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp',
-           'row_pass.hpp', 'truth_rank_body.hpp', 'rank_key.hpp',
+           'row_pass.hpp', 'chunk_walk.hpp', 'philox.hpp', 'truth_rank_body.hpp', 'rank_key.hpp',
            os.path.join('..', '..', 'include', 'invpref_hip.h'),
            os.path.join('..', '..', 'include', 'invpref_macr.h'), os.path.join('..', '..', 'include', 'invpref_cause.h'),
            os.path.join('..', '..', 'include', 'invpref_retrieve_scaled.h'),

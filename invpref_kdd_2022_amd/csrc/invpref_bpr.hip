@@ -6,20 +6,16 @@
 // they are needed -- with a short list the first word is accepted almost always.  The only atomics are integer ones, on the
 // count of forced draws.
 //
-// The pass.  CVIB's scheme (invpref_cvib.hip) with the pair's factor formed by a pairs launch instead of two means:
+// The pass.  The chunked scatter and boundary walk that CVIB's term uses too (chunk_walk.hpp states the scheme), with the
+// pair's factor formed by a pairs launch instead of two means:
 //   pairs     a 16-lane group per triplet (kernel_common.hpp: a row on 16 lanes): the three rows, x = Pu[u] . Qi[i] -
 //             Pu[u] . Qi[j] with dot64 of row_pass.hpp, -log sigmoid(x) and the regulariser sums as float64, one partial per
 //             workgroup (group_sums), and the record g = -w sigmoid(-x) / B, ONE float
-//   scatter   per side (user rows, item rows) the 2B positions come sorted by destination row (the inverted index of
-//             invpref_cvib_index_hip).  A 16-lane group owns one chunk of C consecutive entries and walks it in order:
-//             index entry -> the triplet's three ids and g -> the partner row, kAhead entries in flight together;
-//             acc += +-g * partner row in float64, and at the end of a destination acc += n * regulariser gradient of the
+//   scatter, boundary   chunk_walk.hpp's walk with BprWalk below as its policy: an entry's operands are the triplet's three
+//             ids and g; acc += +-g * partner row, and at the end of a destination acc += n * regulariser gradient of the
 //             destination row, n the gathers of that row among the entries added (an item row: every entry; a user row: the
-//             entries of positions p < B, since a triplet gathers its user row once).  A destination whose entries all lie
-//             inside the chunk is stored by that group; one that continues from the previous chunk or into the next leaves its
-//             float64 partial in the chunk's head or tail slot
-//   boundary  the group of the chunk in which such a destination STARTS finds the row's last chunk by bisection, adds the
-//             partials in chunk order and stores the row
+//             entries of positions p < B, since a triplet gathers its user row once); float64 slots; a finished row is
+//             rounded once and stored
 //   fold      one wave: the partials in workgroup order -> losses4
 // Every row has one writer and every sum a fixed order: the same bits on every run.  The slots are float64, so a row is
 // rounded to fp32 once however many chunks it spans.  Both gradient tables are zero-filled on the stream in front of the
@@ -28,9 +24,8 @@
 // A triplet with any id outside its table is skipped by BOTH of its positions (the scatter reads the triplet's three ids, not
 // the pair's two: the index files position p under u even when only j is bad); the pairs launch counts it and the fold makes
 // the four losses NaN.  Nothing read from the device is an address before it is range-checked.
-#include "row_pass.hpp"
-
-#include <algorithm>
+#include "chunk_walk.hpp"
+#include "philox.hpp"
 
 #include "../../include/invpref_bpr.h"
 
@@ -40,21 +35,6 @@ namespace {
 
 constexpr int64_t kI32Max = 2147483647;
 constexpr int kMaxQuads = INVPREF_BPR_MAX_ATTEMPTS / 4;
-
-// Philox4x32-10 (Salmon et al., SC 2011; Random123's constants), as in invpref_rank_stats.hip
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&x)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
 
 __global__ __launch_bounds__(256) void bpr_draw_kernel(const int64_t *__restrict__ users, int64_t n_len,
                                                        const int64_t *__restrict__ step_lo, const int32_t *__restrict__ step_n,
@@ -98,25 +78,19 @@ __global__ __launch_bounds__(256) void bpr_draw_kernel(const int64_t *__restrict
 // ---- the pass
 constexpr int kRec = 4;   // float64 sums per workgroup: -log sigmoid, squares, absolute values, skipped triplets
 
-__host__ __device__ inline int chunk_of(int64_t n2) { return n2 <= 65536 ? 16 : 128; }
-
 struct Layout {
     size_t g, partials, part, total;
-    int nwg, nchunk, C, Dp;
+    int nwg;
+    ChunkGeom walk;
 };
 inline Layout layout_of(int64_t B, int64_t D) {
     Layout L;
-    const int64_t n2 = 2 * B;
-    L.C = chunk_of(n2);
     L.nwg = (int)((B + kGroups - 1) / kGroups);
-    L.nchunk = (int)((n2 + L.C - 1) / L.C);
-    L.Dp = (int)((D + 3) / 4 * 4);
+    L.walk = chunk_geom(B, D);
     Carver ws;
     L.g = ws.take(sizeof(float) * (size_t)B);
     L.partials = ws.take(sizeof(double) * kRec * (size_t)L.nwg);
-    // (the chunk grows from 16 to 128 entries beyond 65 536 positions: keep the size non-decreasing across that step)
-    const size_t slots = n2 <= 65536 ? (size_t)L.nchunk : (size_t)std::max(L.nchunk, 4096);
-    L.part = ws.take(sizeof(double) * 2 * slots * 2 * (size_t)L.Dp);   // two sides, head and tail
+    L.part = ws.take(L.walk.part_bytes<double>());
     L.total = ws.bytes();
     return L;
 }
@@ -192,58 +166,67 @@ __global__ __launch_bounds__(64) void bpr_fold_kernel(const double *__restrict__
     losses4[3] = (float)(bad ? nan : (sl + L2_coe * l2) + L1_coe * l1);
 }
 
-// a chunk slot: Dp = D rounded up to 4 floats, doubles (the entries beyond D are the zeros load_row filled in)
-template <int NC>
-__device__ __forceinline__ void slot_store(double *__restrict__ slot, int Dp, int l16, const double4_t (&v)[NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int i0 = (l16 + kRow * c) * 4;
-        if (i0 < Dp) {
-            slot[i0 + 0] = v[c].x; slot[i0 + 1] = v[c].y; slot[i0 + 2] = v[c].z; slot[i0 + 3] = v[c].w;
-        }
-    }
-}
-template <int NC>
-__device__ __forceinline__ void slot_add(const double *__restrict__ slot, int Dp, int l16, double4_t (&v)[NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int i0 = (l16 + kRow * c) * 4;
-        if (i0 < Dp) {
-            v[c].x = v[c].x + slot[i0 + 0]; v[c].y = v[c].y + slot[i0 + 1];
-            v[c].z = v[c].z + slot[i0 + 2]; v[c].w = v[c].w + slot[i0 + 3];
-        }
-    }
-}
-// a slot's values without a branch: a lane beyond Dp reads the slot's first entries and keeps zeros
-template <int NC>
-__device__ __forceinline__ void slot_load(const double *__restrict__ slot, int Dp, int l16, double4_t (&v)[NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int i0 = (l16 + kRow * c) * 4;
-        const bool in = i0 < Dp;
-        const double *p = slot + (in ? i0 : 0);
-        const double x = p[0], y = p[1], z = p[2], w = p[3];
-        v[c].x = in ? x : 0.0; v[c].y = in ? y : 0.0; v[c].z = in ? z : 0.0; v[c].w = in ? w : 0.0;
-    }
-}
-template <int NC>
-__device__ __forceinline__ void zero_acc(double4_t (&v)[NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) v[c].x = v[c].y = v[c].z = v[c].w = 0.0;
-}
-template <int NC>
-__device__ __forceinline__ void round_row(const double4_t (&v)[NC], float4 (&r)[NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) r[c] = make_float4((float)v[c].x, (float)v[c].y, (float)v[c].z, (float)v[c].w);
-}
 __device__ __forceinline__ double reg_of(double x, double n2, double n1) {
     return n2 * x + n1 * (x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0));   // (a NaN entry: n2 * NaN)
 }
 
-// entries whose index -> ids -> row chain is in flight together (8 NC + 8 registers per entry next to the 8 NC of the float64
-// accumulator: eight entries of 128-float rows took all 256 registers and left one wave per SIMD)
-template <int NC>
-constexpr int ahead_of() { return NC == 1 ? 8 : 4; }
+// what the chunked scatter and boundary walk (chunk_walk.hpp) leave to this pass
+struct BprWalk {
+    using Slot = double;   // a row is rounded to fp32 once however many chunks it spans
+    // entries whose index -> ids -> row chain is in flight together (8 NC + 8 registers per entry next to the 8 NC of the
+    // float64 accumulator: eight entries of 128-float rows took all 256 registers and left one wave per SIMD)
+    template <int NC>
+    static constexpr int ahead() { return NC == 1 ? 8 : 4; }
+    template <int NC>
+    static constexpr int batch() { return 16 / NC; }
+    struct Entry {
+        int64_t u, i;   // the triplet's three ids and its g
+        int j;
+        float g;
+    };
+    int U, I, B;
+    const int64_t *__restrict__ users, *__restrict__ pos_items;
+    const int32_t *__restrict__ neg;
+    const float *__restrict__ g;
+    double r2, r1;
+
+    __device__ __forceinline__ Entry load(int, int pos) const {
+        const int p = pos < B ? pos : pos - B;
+        return Entry{users[p], pos_items[p], neg[p], g[p]};
+    }
+    __device__ __forceinline__ int64_t partner(int side, const Entry &e, int pos) const {
+        return side ? e.u : (pos < B ? e.i : (int64_t)e.j);
+    }
+    // the whole triplet decides, not the pair: a bad negative silences the positive's position too
+    __device__ __forceinline__ bool valid(const Entry &e, int y, int n2) const {
+        return !(y < 0 || y >= n2 || e.u < 0 || e.u >= U || e.i < 0 || e.i >= I || e.j < 0 || e.j >= I);
+    }
+    // (a triplet gathers its user row once: the user side counts position p only)
+    __device__ __forceinline__ int gathers(int side, int pos) const { return (side || pos < B) ? 1 : 0; }
+    __device__ __forceinline__ float factor(const Entry &e, int pos) const { return pos < B ? e.g : -e.g; }
+    // acc += n * regulariser gradient of the destination row, n the gathers of that row among the entries added
+    template <int NC, bool VEC>
+    __device__ __forceinline__ void finish(const float *__restrict__ dtab, int row, int D, int cnt, int l16,
+                                           double4_t (&acc)[NC]) const {
+        float4 d[NC];
+        load_row<NC, VEC>(dtab, row, D, l16, d);
+        const double n2r = (double)cnt * r2, n1r = (double)cnt * r1;
+#pragma unroll
+        for (int k = 0; k < NC; k++) {
+            acc[k].x = acc[k].x + reg_of((double)d[k].x, n2r, n1r);
+            acc[k].y = acc[k].y + reg_of((double)d[k].y, n2r, n1r);
+            acc[k].z = acc[k].z + reg_of((double)d[k].z, n2r, n1r);
+            acc[k].w = acc[k].w + reg_of((double)d[k].w, n2r, n1r);
+        }
+    }
+    // rounded once and stored: the tables are zero-filled in front, the writers never read them
+    template <int NC, bool VEC>
+    static __device__ __forceinline__ void write_row(float *__restrict__ gtab, int row, int D, int l16, const double4_t (&acc)[NC]) {
+        float4 r[NC];
+        round_row<NC>(acc, r);
+        store_row<NC, VEC>(gtab, row, D, l16, r);
+    }
+};
 
 template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void bpr_scatter_kernel(const float *__restrict__ Pu, int U, const float *__restrict__ Qi, int I,
@@ -253,140 +236,15 @@ __global__ __launch_bounds__(256) void bpr_scatter_kernel(const float *__restric
                                                           int nchunk, const float *__restrict__ g, double r2, double r1,
                                                           float *__restrict__ gu, float *__restrict__ gi,
                                                           double *__restrict__ part, int Dp) {
-    const int l16 = threadIdx.x & (kRow - 1);
-    const int grp = (int)blockIdx.x * kGroups + threadIdx.x / kRow;
-    if (grp >= 2 * nchunk) return;
-    const int side = grp >= nchunk ? 1 : 0, c = grp - side * nchunk;   // side 0: user rows, partner Qi; side 1: item rows, partner Pu
-    const int n2 = 2 * B;
-    const int2 *idx = index + side * stride;
-    const int lim = side ? I : U, plim = side ? U : I;
-    const float *ptab = side ? Pu : Qi, *dtab = side ? Qi : Pu;
-    float *gtab = side ? gi : gu;
-    const int e0 = c * C, e1 = min(e0 + C, n2);
-    const int first = idx[e0].x;
-    if (first < 0 || first >= lim) return;   // the sentinel destination sorts last: nothing left in this list
-    const bool head0 = c > 0 && idx[e0 - 1].x == first;
-    const int next_id = e1 < n2 ? idx[e1].x : -1;
-    double *slot = part + ((int64_t)(side * nchunk + c) * 2) * Dp;
-    double4_t acc[NC];
-    zero_acc<NC>(acc);
-    int cur = first, cnt = 0;
-    bool cur_head = head0, live = true;
-    auto flush = [&](bool head, bool tail) {
-        float4 d[NC];
-        load_row<NC, VEC>(dtab, cur, D, l16, d);
-        const double n2r = (double)cnt * r2, n1r = (double)cnt * r1;
-#pragma unroll
-        for (int k = 0; k < NC; k++) {
-            acc[k].x = acc[k].x + reg_of((double)d[k].x, n2r, n1r);
-            acc[k].y = acc[k].y + reg_of((double)d[k].y, n2r, n1r);
-            acc[k].z = acc[k].z + reg_of((double)d[k].z, n2r, n1r);
-            acc[k].w = acc[k].w + reg_of((double)d[k].w, n2r, n1r);
-        }
-        if (!head && !tail) {
-            float4 r[NC];
-            round_row<NC>(acc, r);
-            store_row<NC, VEC>(gtab, cur, D, l16, r);
-        } else {
-            slot_store<NC>(slot + (head ? 0 : Dp), Dp, l16, acc);
-        }
-    };
-    constexpr int kAhead = ahead_of<NC>();
-    for (int e = e0; e < e1 && live; e += kAhead) {
-        int2 en[kAhead];
-        int64_t tu[kAhead], ti[kAhead];
-        int tj[kAhead];
-        float tg[kAhead];
-        float4 rows[kAhead][NC];
-#pragma unroll
-        for (int j = 0; j < kAhead; j++) en[j] = idx[min(e + j, e1 - 1)];
-#pragma unroll
-        for (int j = 0; j < kAhead; j++) {
-            const int pos = min(max(en[j].y, 0), n2 - 1), p = pos < B ? pos : pos - B;
-            tu[j] = users[p];
-            ti[j] = pos_items[p];
-            tj[j] = neg[p];
-            tg[j] = g[p];
-        }
-#pragma unroll
-        for (int j = 0; j < kAhead; j++) {
-            const int64_t pid = side ? tu[j] : (en[j].y < B ? ti[j] : (int64_t)tj[j]);
-            load_row<NC, VEC>(ptab, std::min<int64_t>(std::max<int64_t>(pid, 0), plim - 1), D, l16, rows[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < kAhead; j++) {
-            if (!live || e + j >= e1) continue;
-            const int dest = en[j].x;
-            if (dest < 0 || dest >= lim) {   // the sentinel destination, from here to the end of the list
-                live = false;
-                continue;
-            }
-            if (dest != cur) {
-                flush(cur_head, false);
-                zero_acc<NC>(acc);
-                cur = dest;
-                cnt = 0;
-                cur_head = false;
-            }
-            // the whole triplet decides, not the pair: a bad negative silences the positive's position too
-            if (en[j].y < 0 || en[j].y >= n2 || tu[j] < 0 || tu[j] >= U || ti[j] < 0 || ti[j] >= I || tj[j] < 0 || tj[j] >= I)
-                continue;
-            cnt += (side || en[j].y < B) ? 1 : 0;   // (a triplet gathers its user row once: the user side counts position p only)
-            axpy_row<NC>(acc, en[j].y < B ? tg[j] : -tg[j], rows[j]);
-        }
-    }
-    flush(cur_head, live && next_id == cur);
+    const BprWalk pol{U, I, B, users, pos_items, neg, g, r2, r1};
+    chunk_scatter<NC, VEC>(pol, Pu, U, Qi, I, D, B, index, stride, C, nchunk, gu, gi, part, Dp);
 }
 
 template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void bpr_boundary_kernel(const int2 *__restrict__ index, int64_t stride, int B, int C, int nchunk,
                                                            int U, int I, int D, int Dp, const double *__restrict__ part,
                                                            float *__restrict__ gu, float *__restrict__ gi) {
-    const int l16 = threadIdx.x & (kRow - 1);
-    const int grp = (int)blockIdx.x * kGroups + threadIdx.x / kRow;
-    if (grp >= 2 * nchunk) return;
-    const int side = grp >= nchunk ? 1 : 0, c = grp - side * nchunk;
-    const int n2 = 2 * B;
-    const int2 *idx = index + side * stride;
-    const int lim = side ? I : U;
-    const int e0 = c * C, e1 = min(e0 + C, n2);
-    if (e1 >= n2) return;
-    const int last = idx[e1 - 1].x;
-    if (last < 0 || last >= lim || idx[e1].x != last) return;          // nothing continues into the next chunk
-    if (c > 0 && idx[e0].x == last && idx[e0 - 1].x == last) return;   // it started earlier: that chunk's group owns the row
-    const double *slots = part + ((int64_t)side * nchunk * 2) * Dp;
-    double4_t sum[NC];
-    zero_acc<NC>(sum);
-    slot_add<NC>(slots + ((int64_t)c * 2 + 1) * Dp, Dp, l16, sum);
-    // the last chunk that STARTS with this row (chunk starts are sorted like the entries, and chunk c + 1 does): a bisection
-    // instead of a walk, so that the head slots below are independent loads
-    int lo = c + 1, hi = nchunk - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (idx[(int64_t)mid * C].x == last) lo = mid;
-        else hi = mid - 1;
-    }
-    // the head slots in chunk order, kBatch of them loaded before the first is added: the order of the sum is the walk's, and
-    // the loads are straight-line code (slot_load: no branch around a load), so they are in flight together
-    constexpr int kBatch = 16 / NC;
-    int cc = c + 1;
-    for (; cc + kBatch - 1 <= lo; cc += kBatch) {
-        double4_t v[kBatch][NC];
-#pragma unroll
-        for (int j = 0; j < kBatch; j++) slot_load<NC>(slots + ((int64_t)(cc + j) * 2) * Dp, Dp, l16, v[j]);
-#pragma unroll
-        for (int j = 0; j < kBatch; j++) {
-#pragma unroll
-            for (int k = 0; k < NC; k++) {
-                sum[k].x = sum[k].x + v[j][k].x; sum[k].y = sum[k].y + v[j][k].y;
-                sum[k].z = sum[k].z + v[j][k].z; sum[k].w = sum[k].w + v[j][k].w;
-            }
-        }
-    }
-    for (; cc <= lo; cc++) slot_add<NC>(slots + ((int64_t)cc * 2) * Dp, Dp, l16, sum);
-    float4 r[NC];
-    round_row<NC>(sum, r);
-    store_row<NC, VEC>(side ? gi : gu, last, D, l16, r);
+    chunk_boundary<NC, VEC, BprWalk>(index, stride, B, C, nchunk, U, I, D, Dp, part, gu, gi);
 }
 
 }  // namespace
@@ -442,7 +300,7 @@ int invpref_bpr_grad_hip(const float *user_table, int64_t user_num, const float 
     const int U = (int)user_num, I = (int)item_num, D = (int)factor_num, B = (int)batch;
     const bool vec = rows_vec_ok(D, user_table, item_table, grad_user, grad_item);
     const int2 *idx = reinterpret_cast<const int2 *>(index);
-    const unsigned sgrid = (unsigned)((2 * L.nchunk + kGroups - 1) / kGroups);
+    const ChunkGeom &W = L.walk;
     const double BD = (double)batch * (double)factor_num;
     int rc;
     if ((rc = (int)hipMemsetAsync(grad_user, 0, sizeof(float) * (size_t)user_num * (size_t)factor_num, st))) return rc;
@@ -454,12 +312,12 @@ int invpref_bpr_grad_hip(const float *user_table, int64_t user_num, const float 
         hipLaunchKernelGGL((bpr_pairs_kernel<NC, VEC>), dim3((unsigned)L.nwg), dim3(256), 0, st, user_table, U, item_table, I, D,
                            users, pos_items, neg, weights, B, g, partials, (int64_t)L.nwg);
         if ((rc = (int)hipGetLastError())) return rc;
-        hipLaunchKernelGGL((bpr_scatter_kernel<NC, VEC>), dim3(sgrid), dim3(256), 0, st, user_table, U, item_table, I, D, users,
-                           pos_items, neg, B, idx, index_stride, L.C, L.nchunk, g, 2.0 * L2_coe / BD, L1_coe / BD, grad_user,
-                           grad_item, part, L.Dp);
+        hipLaunchKernelGGL((bpr_scatter_kernel<NC, VEC>), dim3(W.grid()), dim3(256), 0, st, user_table, U, item_table, I, D,
+                           users, pos_items, neg, B, idx, index_stride, W.C, W.nchunk, g, 2.0 * L2_coe / BD, L1_coe / BD,
+                           grad_user, grad_item, part, W.Dp);
         if ((rc = (int)hipGetLastError())) return rc;
-        hipLaunchKernelGGL((bpr_boundary_kernel<NC, VEC>), dim3(sgrid), dim3(256), 0, st, idx, index_stride, B, L.C, L.nchunk, U,
-                           I, D, L.Dp, part, grad_user, grad_item);
+        hipLaunchKernelGGL((bpr_boundary_kernel<NC, VEC>), dim3(W.grid()), dim3(256), 0, st, idx, index_stride, B, W.C, W.nchunk,
+                           U, I, D, W.Dp, part, grad_user, grad_item);
         if ((rc = (int)hipGetLastError())) return rc;
         hipLaunchKernelGGL(bpr_fold_kernel, dim3(1), dim3(64), 0, st, partials, L.nwg, (int64_t)L.nwg, (double)batch,
                            (double)factor_num, L2_coe, L1_coe, losses4);

@@ -28,16 +28,10 @@
 //             order, one partial per workgroup
 //   fold      one wave: the partials in workgroup order, then the record {pbar, qbar, cA, cG, cQ, info} and
 //             loss += info_coe info
-//   scatter   per side (user rows, item rows) the 2B positions come sorted by destination row (the inverted index, built per
-//             run of epochs by the two index entry points below around ONE ascending sort of unique keys).  A 16-lane group
-//             owns one chunk of C consecutive entries and walks it in order, gathering the partner row of each entry and
-//             summing g * row per destination.  A destination whose entries all lie inside the chunk is added into the
-//             gradient table by that group -- its only writer.  A destination that continues from the previous chunk or into
-//             the next one leaves its partial sum in the chunk's slot (two slots per chunk: head and tail)
-//   boundary  the group of the chunk in which such a destination STARTS finds the row's last chunk by bisection, adds the
-//             partials of its chunks in chunk order (in float64: one fp32 chain over the 150 partials of a row with 4 900
-//             contributions was twice the PureMF pass's distance) and is the row's only writer.  A popular row is thus
-//             gathered by many groups in parallel; only its chunk partials (one per C contributions) are added serially
+//   scatter, boundary   the chunked walk of chunk_walk.hpp over the inverted index (per side the 2B positions sorted by
+//             destination row, built per run of epochs by the two index entry points below around ONE ascending sort of unique
+//             keys) with the policy CvibWalk: fp32 slots, summed per row in float64 (one fp32 chain over the 150 partials of a
+//             row with 4 900 contributions was twice the PureMF pass's distance), a finished row ADDED into the gradient table
 // Every sum has a fixed order: the same bits on every run and every device.  Rows without a contribution are not touched.
 //
 // An id outside its table is never used as an address: the pair is skipped on both sides (the index files it under a sentinel
@@ -46,10 +40,7 @@
 // p_i and log p_i are float64, so that happens below x = -745 only (NaN in `info` and in that pair's two rows, as there);
 // between the two the term is finite where the reference's is not.  A qbar of exactly 0 or 1 gives infinite coefficients in
 // both.
-#include "launch.hpp"
-
-#include <algorithm>
-#include <type_traits>
+#include "chunk_walk.hpp"
 
 using namespace invpref;
 
@@ -59,51 +50,24 @@ constexpr int kTile = 64;               // positions per workgroup of the means 
 constexpr int64_t kMaxBatch = 1 << 24;  // rows of one minibatch
 constexpr int kRec = 8;                 // float64 of the record at the head of the workspace
 
-__host__ __device__ inline int chunk_of(int64_t n2) { return n2 <= 65536 ? 16 : 128; }
-
 struct Layout {
     size_t pq, partials, part, total;
-    int nwg, nchunk, C, Dp;
+    int nwg;
+    ChunkGeom walk;
 };
 inline Layout layout_of(int64_t B, int64_t D) {
     Layout L;
     const int64_t n2 = 2 * B;
-    L.C = chunk_of(n2);
     L.nwg = (int)((n2 + kTile - 1) / kTile);
-    L.nchunk = (int)((n2 + L.C - 1) / L.C);
-    L.Dp = (int)((D + 3) / 4 * 4);
+    L.walk = chunk_geom(B, D);
     // (every part's size is a multiple of 16 bytes already)
     Carver ws;
     ws.take(sizeof(double) * kRec);   // the record, at the head
     L.pq = ws.take(sizeof(double) * 2 * (size_t)n2);
     L.partials = ws.take(sizeof(double) * 4 * (size_t)L.nwg);
-    // (the chunk grows from 16 to 128 entries beyond 65 536 positions: keep the size non-decreasing across that step)
-    const size_t slots = n2 <= 65536 ? (size_t)L.nchunk : (size_t)std::max(L.nchunk, 4096);
-    L.part = ws.take(sizeof(float) * 2 * slots * 2 * (size_t)L.Dp);
+    L.part = ws.take(L.walk.part_bytes<float>());
     L.total = ws.bytes();
     return L;
-}
-
-// the row dot in float64: the lane's chunks in increasing index, then the butterfly 1, 2, 4, 8 over the 16 lanes
-template <int NC>
-__device__ __forceinline__ double dot_f64(const float4 (&a)[NC], const float4 (&b)[NC]) {
-    double s = 0.0;
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        s = __builtin_fma((double)a[c].x, (double)b[c].x, s);
-        s = __builtin_fma((double)a[c].y, (double)b[c].y, s);
-        s = __builtin_fma((double)a[c].z, (double)b[c].z, s);
-        s = __builtin_fma((double)a[c].w, (double)b[c].w, s);
-    }
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) s = s + __shfl_xor(s, m, 16);
-    return s;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) x = x + __shfl_xor(x, m, 64);
-    return x;
 }
 
 template <int NC, bool VEC>
@@ -113,16 +77,16 @@ __global__ __launch_bounds__(256) void cvib_means_kernel(const float *__restrict
                                                          int implicit, float eps, double2 *__restrict__ wt,
                                                          double *__restrict__ partials) {
     __shared__ double red[4][4];
-    const int l16 = threadIdx.x & 15, grp = threadIdx.x >> 4, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l16 = threadIdx.x & (kRow - 1), grp = threadIdx.x / kRow, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n2 = 2 * B;
     double s[4] = {0.0, 0.0, 0.0, 0.0};   // sum p, sum q, sum p log p, skipped pairs
-    constexpr int PER = kTile / 16;
+    constexpr int PER = kTile / kGroups;
     int64_t u[PER], v[PER];
     float4 a[PER][NC], b[PER][NC];
     // the group's four pairs: ids, then rows, each as one batch of independent loads (id -> row is a dependent pair)
 #pragma unroll
     for (int it = 0; it < PER; it++) {
-        const int pos = min((int)blockIdx.x * kTile + it * 16 + grp, n2 - 1);
+        const int pos = min((int)blockIdx.x * kTile + it * kGroups + grp, n2 - 1);
         u[it] = pos < B ? mbu[pos] : (int64_t)du[pos - B];
         v[it] = pos < B ? mbv[pos] : (int64_t)dv[pos - B];
     }
@@ -133,9 +97,9 @@ __global__ __launch_bounds__(256) void cvib_means_kernel(const float *__restrict
     }
 #pragma unroll
     for (int it = 0; it < PER; it++) {
-        const int pos = (int)blockIdx.x * kTile + it * 16 + grp;
+        const int pos = (int)blockIdx.x * kTile + it * kGroups + grp;
         const bool valid = u[it] >= 0 && u[it] < U && v[it] >= 0 && v[it] < I;
-        const double x = dot_f64<NC>(a[it], b[it]);
+        const double x = dot64<NC>(a[it], b[it]);
         if (l16 == 0 && pos < n2) {
             double p, lp, w, k = 1.0;
             if (implicit) {
@@ -159,7 +123,7 @@ __global__ __launch_bounds__(256) void cvib_means_kernel(const float *__restrict
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        s[j] = wave_sum_f64(s[j]);
+        s[j] = wave_sum64(s[j]);
         if (lane == 0) red[wave][j] = s[j];
     }
     __syncthreads();
@@ -180,7 +144,7 @@ __global__ __launch_bounds__(64) void cvib_fold_kernel(const double *__restrict_
 #pragma unroll
         for (int j = 0; j < 4; j++) s[j] += partials[(int64_t)i * 4 + j];
 #pragma unroll
-    for (int j = 0; j < 4; j++) s[j] = wave_sum_f64(s[j]);
+    for (int j = 0; j < 4; j++) s[j] = wave_sum64(s[j]);
     if (threadIdx.x != 0) return;
     const double pb = s[0] / B, qb = s[1] / B, one_q = 1.0 - qb;
     const bool kq = implicit || qb >= eps, k1 = implicit || one_q >= eps;
@@ -219,30 +183,45 @@ __device__ __forceinline__ void add_into_row(float *__restrict__ dst, int D, int
         }
     }
 }
-// a chunk slot: Dp = D rounded up to 4 floats, 16-byte aligned (the entries beyond D are the zeros load_row filled in)
-template <int NC>
-__device__ __forceinline__ void slot_store(float *__restrict__ slot, int Dp, int l16, const float4 (&v)[NC]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int i0 = (l16 + kRow * c) * 4;
-        if (i0 < Dp) *reinterpret_cast<float4 *>(slot + i0) = v[c];
-    }
-}
-template <int NC>
-__device__ __forceinline__ void slot_add(const float *__restrict__ slot, int Dp, int l16, double (&v)[NC][4]) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        const int i0 = (l16 + kRow * c) * 4;
-        if (i0 < Dp) {
-            const float4 o = *reinterpret_cast<const float4 *>(slot + i0);
-            v[c][0] += (double)o.x; v[c][1] += (double)o.y; v[c][2] += (double)o.z; v[c][3] += (double)o.w;
-        }
-    }
-}
+// what the chunked scatter and boundary walk (chunk_walk.hpp) leave to this term
+struct CvibWalk {
+    using Slot = float;   // every chunk partial is rounded to fp32
+    // entries whose index -> partner id -> row chain is in flight together (rows of 256 floats: 16 registers per entry)
+    template <int NC>
+    static constexpr int ahead() { return NC == 4 ? 4 : 8; }
+    template <int NC>
+    static constexpr int batch() { return 1; }
+    struct Entry {
+        int pid;      // the partner's id
+        double2 pv;   // the pair's {w, t} of the means pass
+    };
+    const int64_t *__restrict__ mbu, *__restrict__ mbv;
+    const int32_t *__restrict__ du, *__restrict__ dv;
+    const double2 *__restrict__ wt;
+    int B;
+    double cA, cG, cQ;
 
-// entries whose index -> partner id -> row chain is in flight together (rows of 256 floats: 16 registers per entry)
-template <int NC>
-constexpr int ahead_of() { return NC == 4 ? 4 : 8; }
+    __device__ __forceinline__ Entry load(int side, int pos) const {
+        return Entry{pos < B ? (int)(side ? mbu[pos] : mbv[pos]) : (side ? du[pos - B] : dv[pos - B]), wt[pos]};
+    }
+    __device__ __forceinline__ int partner(int, const Entry &e, int) const { return e.pid; }
+    // (a skipped pair is under the sentinel on both sides: every entry the walk reaches counts)
+    __device__ __forceinline__ bool valid(const Entry &, int, int) const { return true; }
+    __device__ __forceinline__ int gathers(int, int) const { return 0; }
+    // the pair's factor: float64, rounded to fp32 once (what an fp32 evaluation of the loss would hand autograd)
+    __device__ __forceinline__ float factor(const Entry &e, int pos) const {
+        return (float)(pos < B ? cA * e.pv.x + cG * e.pv.y : cQ * e.pv.x);
+    }
+    template <int NC, bool VEC>
+    __device__ __forceinline__ void finish(const float *, int, int, int, int, double4_t (&)[NC]) const {}
+    // the row sum rounded to fp32, then ADDED into the gradient table in fp32
+    template <int NC, bool VEC>
+    static __device__ __forceinline__ void write_row(float *__restrict__ gtab, int row, int D, int l16, const double4_t (&acc)[NC]) {
+        float4 r[NC];
+        round_row<NC>(acc, r);
+        add_into_row<NC, VEC>(gtab + (int64_t)row * D, D, l16, r);
+    }
+};
 
 template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void cvib_scatter_kernel(const float *__restrict__ Pu, int U, const float *__restrict__ Qi, int I,
@@ -252,115 +231,15 @@ __global__ __launch_bounds__(256) void cvib_scatter_kernel(const float *__restri
                                                            const double *__restrict__ rec,
                                                            const double2 *__restrict__ wt, float *__restrict__ gu,
                                                            float *__restrict__ gi, float *__restrict__ part, int Dp) {
-    const int l16 = threadIdx.x & 15;
-    const int g = (int)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (g >= 2 * nchunk) return;
-    const int side = g >= nchunk ? 1 : 0, c = g - side * nchunk;   // side 0: user rows, partner Qi; side 1: item rows, partner Pu
-    const int n2 = 2 * B;
-    const int2 *idx = index + side * stride;
-    const int lim = side ? I : U, plim = side ? U : I;
-    const float *ptab = side ? Pu : Qi;
-    float *gtab = side ? gi : gu;
-    const int e0 = c * C, e1 = min(e0 + C, n2);
-    const int first = idx[e0].x;
-    if (first < 0 || first >= lim) return;   // the sentinel destination sorts last: nothing left in this list
-    const double cA = rec[2], cG = rec[3], cQ = rec[4];
-    const bool head0 = c > 0 && idx[e0 - 1].x == first;
-    const int next_id = e1 < n2 ? idx[e1].x : -1;
-    float *slot = part + ((int64_t)(side * nchunk + c) * 2) * Dp;
-    double acc[NC][4];
-#pragma unroll
-    for (int k = 0; k < NC; k++) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.0;
-    int cur = first;
-    bool cur_head = head0, live = true;
-    auto flush = [&](bool head, bool tail) {
-        float4 r[NC];
-#pragma unroll
-        for (int k = 0; k < NC; k++) r[k] = make_float4((float)acc[k][0], (float)acc[k][1], (float)acc[k][2], (float)acc[k][3]);
-        if (!head && !tail) add_into_row<NC, VEC>(gtab + (int64_t)cur * D, D, l16, r);
-        else slot_store<NC>(slot + (head ? 0 : Dp), Dp, l16, r);
-    };
-    constexpr int kAhead = ahead_of<NC>();
-    for (int e = e0; e < e1 && live; e += kAhead) {
-        int2 en[kAhead];
-        int pid[kAhead];
-        double2 pv[kAhead];
-        float4 rows[kAhead][NC];
-#pragma unroll
-        for (int j = 0; j < kAhead; j++) en[j] = idx[min(e + j, e1 - 1)];
-#pragma unroll
-        for (int j = 0; j < kAhead; j++) {
-            const int pos = min(max(en[j].y, 0), n2 - 1);
-            en[j].y = pos;
-            pid[j] = pos < B ? (int)(side ? mbu[pos] : mbv[pos]) : (side ? du[pos - B] : dv[pos - B]);
-            pv[j] = wt[pos];
-        }
-#pragma unroll
-        for (int j = 0; j < kAhead; j++) load_row<NC, VEC>(ptab, min(max(pid[j], 0), plim - 1), D, l16, rows[j]);
-#pragma unroll
-        for (int j = 0; j < kAhead; j++) {
-            if (!live || e + j >= e1) continue;
-            const int dest = en[j].x;
-            if (dest < 0 || dest >= lim) {   // the skipped pairs, from here to the end of the list
-                live = false;
-                continue;
-            }
-            if (dest != cur) {
-                flush(cur_head, false);
-#pragma unroll
-                for (int k = 0; k < NC; k++) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.0;
-                cur = dest;
-                cur_head = false;
-            }
-            // the pair's factor: float64, rounded to fp32 once (what an fp32 evaluation of the loss would hand autograd)
-            const double gf = (double)(float)(en[j].y < B ? cA * pv[j].x + cG * pv[j].y : cQ * pv[j].x);
-#pragma unroll
-            for (int k = 0; k < NC; k++) {
-                acc[k][0] = __builtin_fma(gf, (double)rows[j][k].x, acc[k][0]);
-                acc[k][1] = __builtin_fma(gf, (double)rows[j][k].y, acc[k][1]);
-                acc[k][2] = __builtin_fma(gf, (double)rows[j][k].z, acc[k][2]);
-                acc[k][3] = __builtin_fma(gf, (double)rows[j][k].w, acc[k][3]);
-            }
-        }
-    }
-    flush(cur_head, live && next_id == cur);
+    const CvibWalk pol{mbu, mbv, du, dv, wt, B, rec[2], rec[3], rec[4]};
+    chunk_scatter<NC, VEC>(pol, Pu, U, Qi, I, D, B, index, stride, C, nchunk, gu, gi, part, Dp);
 }
 
 template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void cvib_boundary_kernel(const int2 *__restrict__ index, int64_t stride, int B, int C, int nchunk,
                                                             int U, int I, int D, int Dp, const float *__restrict__ part,
                                                             float *__restrict__ gu, float *__restrict__ gi) {
-    const int l16 = threadIdx.x & 15;
-    const int g = (int)blockIdx.x * 16 + (threadIdx.x >> 4);
-    if (g >= 2 * nchunk) return;
-    const int side = g >= nchunk ? 1 : 0, c = g - side * nchunk;
-    const int n2 = 2 * B;
-    const int2 *idx = index + side * stride;
-    const int lim = side ? I : U;
-    const int e0 = c * C, e1 = min(e0 + C, n2);
-    if (e1 >= n2) return;
-    const int last = idx[e1 - 1].x;
-    if (last < 0 || last >= lim || idx[e1].x != last) return;          // nothing continues into the next chunk
-    if (c > 0 && idx[e0].x == last && idx[e0 - 1].x == last) return;   // it started earlier: that chunk's group owns the row
-    const float *slots = part + ((int64_t)side * nchunk * 2) * Dp;
-    double sum[NC][4];
-#pragma unroll
-    for (int k = 0; k < NC; k++) sum[k][0] = sum[k][1] = sum[k][2] = sum[k][3] = 0.0;
-    slot_add<NC>(slots + ((int64_t)c * 2 + 1) * Dp, Dp, l16, sum);
-    // the last chunk that STARTS with this row (chunk starts are sorted like the entries, and chunk c + 1 does): a bisection
-    // instead of a walk, so that the head slots below are independent loads -- walking 357 chunks of the most popular item of a
-    // 262 144-row minibatch, one dependent index load per chunk, was 0.5 ms
-    int lo = c + 1, hi = nchunk - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (idx[(int64_t)mid * C].x == last) lo = mid;
-        else hi = mid - 1;
-    }
-    for (int cc = c + 1; cc <= lo; cc++) slot_add<NC>(slots + ((int64_t)cc * 2) * Dp, Dp, l16, sum);
-    float4 r[NC];
-#pragma unroll
-    for (int k = 0; k < NC; k++) r[k] = make_float4((float)sum[k][0], (float)sum[k][1], (float)sum[k][2], (float)sum[k][3]);
-    add_into_row<NC, VEC>((side ? gi : gu) + (int64_t)last * D, D, l16, r);
+    chunk_boundary<NC, VEC, CvibWalk>(index, stride, B, C, nchunk, U, I, D, Dp, part, gu, gi);
 }
 
 // ---- the inverted index.  Key of (step s, side, destination id, position): ((2 s + side) (R + 1) + id) stride + position,
@@ -463,26 +342,25 @@ int invpref_cvib_grad_hip(const float *user_table, int64_t user_num, const float
     const float eps32 = (float)eps;   // the one value of every clip: the per-pair kernel and the fold both take this
     const bool vec = rows_vec_ok(D, user_table, item_table, grad_user, grad_item);
     const int2 *idx = reinterpret_cast<const int2 *>(index);
-    const unsigned sgrid = (unsigned)((2 * L.nchunk + 15) / 16);
-    auto run = [&](auto NCt, auto VECt) {
+    const ChunkGeom &W = L.walk;
+    return with_row_shape(D, vec, [&](auto nc_c, auto vec_c) {
         int rc;
-        constexpr int NC = decltype(NCt)::value;
-        constexpr bool VEC = decltype(VECt)::value;
+        constexpr int NC = decltype(nc_c)::value;
+        constexpr bool VEC = decltype(vec_c)::value;
         hipLaunchKernelGGL((cvib_means_kernel<NC, VEC>), dim3((unsigned)L.nwg), dim3(256), 0, st, user_table, U, item_table, I, D,
                            users, items, B, draw_users, draw_items, implicit, eps32, wt, partials);
         if ((rc = (int)hipGetLastError())) return rc;
         hipLaunchKernelGGL(cvib_fold_kernel, dim3(1), dim3(64), 0, st, partials, L.nwg, (double)batch, implicit, alpha, gamma,
                            info_coe, (double)eps32, rec, loss_out, info_out, pbar_out, qbar_out);
         if ((rc = (int)hipGetLastError())) return rc;
-        hipLaunchKernelGGL((cvib_scatter_kernel<NC, VEC>), dim3(sgrid), dim3(256), 0, st, user_table, U, item_table, I, D, users,
-                           items, B, draw_users, draw_items, idx, index_stride, L.C, L.nchunk, rec, wt,
-                           grad_user, grad_item, part, L.Dp);
+        hipLaunchKernelGGL((cvib_scatter_kernel<NC, VEC>), dim3(W.grid()), dim3(256), 0, st, user_table, U, item_table, I, D,
+                           users, items, B, draw_users, draw_items, idx, index_stride, W.C, W.nchunk, rec, wt, grad_user,
+                           grad_item, part, W.Dp);
         if ((rc = (int)hipGetLastError())) return rc;
-        hipLaunchKernelGGL((cvib_boundary_kernel<NC, VEC>), dim3(sgrid), dim3(256), 0, st, idx, index_stride, B, L.C, L.nchunk, U,
-                           I, D, L.Dp, part, grad_user, grad_item);
+        hipLaunchKernelGGL((cvib_boundary_kernel<NC, VEC>), dim3(W.grid()), dim3(256), 0, st, idx, index_stride, B, W.C, W.nchunk,
+                           U, I, D, W.Dp, part, grad_user, grad_item);
         return (int)hipGetLastError();
-    };
-    return with_int<1, 2, 4>(nc_of(D), [&](auto nc_c) { return with_bool(vec, [&](auto vec_c) { return run(nc_c, vec_c); }); });
+    });
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 // or one of up to 16 ranges of its quads when there are few replicates; lane partials meet in LDS and are added per series in
 // (wave, slot) order, the ranges' partials in range order by the fold kernel.
 #include "launch.hpp"
+#include "philox.hpp"
 
 #include "../../include/invpref_rank_stats.h"
 
@@ -32,12 +33,6 @@ constexpr int64_t kLimit = (int64_t)1 << 31;
 struct RankStatsKs {
     int32_t k[INVPREF_RANK_STATS_MAX_KS];
 };
-
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);      // (a fixed tree; a + b == b + a: every lane the same bits)
-    return x;
-}
 
 __global__ __launch_bounds__(256) void weighted_user_kernel(const int *__restrict__ ranks, const int *__restrict__ truth_ptr,
                                                             const float *__restrict__ weights, const int *__restrict__ n_neg,
@@ -119,21 +114,6 @@ __global__ __launch_bounds__(256) void weighted_finish_kernel(const double *__re
     for (int64_t b = lane; b < n_blocks; b += 64) sum += partial[b * n_el + e];
     sum = wave_sum_f64(sum);
     if (lane == 0) out[e] = sum;
-}
-
-// Philox4x32-10 (Salmon et al., SC 2011; Random123's constants)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&x)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
 }
 
 // dst[(b * n_split + split) * S + s]: the sum over the draws of quads [split * quads_per_split, ...) of replicate b

@@ -168,12 +168,6 @@ struct KList {
     int k[kMaxNK];
 };
 
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);      // (a fixed tree: the same bits on every run)
-    return x;
-}
-
 // One wave per user.  vals[(metric * (n_k + 1) + i) * n + u]: metric 0 recall@k_i | auc, 1 precision@k_i | mrr, 2 ndcg@k_i | map
 __global__ __launch_bounds__(256) void user_metrics_kernel(const int *__restrict__ ranks, const int *__restrict__ truth_ptr,
                                                            const int *__restrict__ n_neg, int64_t n, int64_t n_truth, KList ks,

@@ -97,6 +97,12 @@ __device__ __forceinline__ float wave_sum(float x) {
     for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
     return x;
 }
+// (a fixed tree; a + b == b + a: every lane ends with the same bits, the same on every run)
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+    return x;
+}
 
 
 

@@ -1,7 +1,8 @@
 // row_pass.hpp -- the gradient-pass recipe "pairs -> rows -> fold" that the MACR-MF and CausE baselines share (invpref_macr.hip,
-// invpref_cause.hip; invpref_lintrans.hip is on it too, and invpref_bpr.hip takes its float64 helpers -- dot64, axpy_row,
-// store_row, group_sums, fold64 -- for a pairs / scatter / boundary / fold pass; step_wide.hpp's load_row / store_row family
-// addresses rows differently and stays apart).
+// invpref_cause.hip; invpref_lintrans.hip is on it too; step_wide.hpp's load_row / store_row family addresses rows differently
+// and stays apart).  chunk_walk.hpp builds on its float64 helpers -- double4_t, axpy_row, store_row -- for the chunked scatter
+// and boundary walk of the passes whose rows no row plan knows (invpref_cvib.hip, invpref_bpr.hip), which take dot64,
+// wave_sum64, group_sums and fold64 from here too.
 //
 //   pairs   one 16-lane group per position (lane l owns the float4 chunks l, l + 16, ... of a row: kernel_common.hpp): gathers
 //           the position's two rows, forms its loss terms (float64 partials per workgroup) and a small record of the position
@@ -50,6 +51,12 @@ __device__ __forceinline__ double dbce64(double p, double y) { return (p - y) / 
 __device__ __forceinline__ double row16_sum64(double x) {
 #pragma unroll
     for (int m = 1; m < kRow; m <<= 1) x = x + __shfl_xor(x, m, 64);
+    return x;
+}
+// the same butterfly over the wave's 64 lanes, 1, 2, .. 32 (kernel_common.hpp's wave_sum_f64 runs 32, 16, .. 1: other bits)
+__device__ __forceinline__ double wave_sum64(double x) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) x = x + __shfl_xor(x, m, 64);
     return x;
 }
 struct double4_t {
@@ -133,9 +140,7 @@ static __device__ __forceinline__ void group_sums(const double (&mine)[K], doubl
 __device__ __forceinline__ double fold64(const double *__restrict__ v, int n) {
     double t = 0.0;
     for (int i = threadIdx.x; i < n; i += 64) t = t + v[i];
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) t = t + __shfl_xor(t, m, 64);
-    return t;
+    return wave_sum64(t);
 }
 
 }  // namespace invpref

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 from invpref_kdd_2022_amd import ops
 from invpref_kdd_2022_amd.baseline import PURE_LOSS_KEYS, BPRTrainManager, PureMatrixFactorization
 from invpref_kdd_2022_amd.evaluate import ImplicitRankTestManager, ImplicitTestManager
+import chunk_seams as seams
 from bpr_ref import draw, index_np, positives, run_draws, step64, trajectory64
 from eval_fixture import StubImplicitLoader, eval_fixture
 from test_bpr_cpu import _draw_case, ds_small, forced_case
@@ -205,6 +206,57 @@ def test_long_chunks():
     Measured: gradients 1.2e-10 / 1.3e-10 against 3.3e-9 / 4.0e-9, losses at most 3.9e-8 against 1.2e-7 (0.33 of the bound)."""
     P, Q, u, i, j = seeded_batch(24, 33000, 77)
     check_vs_float64(P, Q, u, i, j, np.random.RandomState(1).uniform(0.5, 2.0, 33000), COEFS, 'B=33000')
+
+
+UID, IID = (lambda k: 3 * k + 1), (lambda k: 2 * k + 5)      # the seam cases' k-th user and item (tables of 64 rows)
+# name: (triplets per user (ascending ids; a triplet is two entries of its user's run), the item side's runs over the valid
+#        triplets' 2 T items, triplets with a bad id appended by hand, the alignments (chunk_seams.facts) per side)
+SEAM_CASES = {
+    'one-chunk': ([8], [3, 5, 8], [], {'one_chunk', 'single'}, {'one_chunk'}),
+    'full-chunks': ([5, 3, 2, 17, 3, 2], [1, 31, 32], [], {'full_chunks', 'ends_at_15', 'long_then_direct'}, {'ends_at_15'}),
+    'ragged-tail': ([7, 2, 15, 9], [66], [], {'ragged_tail'}, {'ragged_tail', 'single'}),
+    'sentinel-at-0': ([10, 14], [48], [(65, IID(2), IID(3))] * 8, {'sentinel_at_0'}, {'sentinel_at_0', 'single'}),
+    # seven bad users and one bad positive, whose negative's position stays filed under user 1 and item 0 and is skipped there
+    'sentinel-at-1': ([8, 16], [48], [(-1, IID(2), IID(3))] * 7 + [(UID(1), -3, IID(0))], {'sentinel_at_1'},
+                      {'sentinel_at_1', 'single'}),
+    # a bad negative: its position is the list's last entry, its positive's stays in an early chunk of user 1 and of item 0
+    'bad-negative-far': ([3, 149, 7], [15] + [16] * 18 + [15], [(UID(1), IID(0), -1)], {'long_then_direct'}, {'ends_at_15'}),
+}
+
+
+@pytest.mark.parametrize('D', [24, 64, 256])
+@pytest.mark.parametrize('name', list(SEAM_CASES))
+def test_chunk_seams(name, D):
+    """The alignments of destinations to the 16-entry chunks at which the scatter / boundary walk (csrc/chunk_walk.hpp) decides
+    between a direct store, a head slot and a tail slot, on ids built by hand (tables of 64 rows): 2 B = 16, a multiple of 16
+    and 16 k + 2 (2 B is even: the list that ends one entry into a chunk is the one with 16 k + 1 live entries); a destination
+    that ends on a chunk's last entry; one that starts in mid-chunk, spans three chunks or more and is followed by one wholly
+    inside its last chunk; one destination with every entry of its side; the sentinel run starting on a chunk's first and
+    second entry; a bad negative whose position lies in another chunk than its positive's, which the triplet test has to
+    silence there.  The test asserts that its lists contain them.  Checks and bounds are check_vs_float64's: the float64 step
+    without the bad triplets, the torch fp32 restatement as the yardstick, NaN losses where an id is bad, zeros in idle rows."""
+    per_user, runs_i, extra, want_u, want_i = SEAM_CASES[name]
+    U = I = 64
+    T = sum(per_user)
+    assert sum(runs_i) == 2 * T
+    items = seams.ids_of([(IID(k), n) for k, n in enumerate(runs_i)])[seams.spread(2 * T, 13)]
+    trip = np.stack([seams.ids_of([(UID(k), n) for k, n in enumerate(per_user)]), items[:T], items[T:]], axis=1)
+    trip = np.concatenate([trip, np.array(extra, np.int64).reshape(-1, 3)])
+    B = len(trip)
+    u, i, j = np.empty(B, np.int64), np.empty(B, np.int64), np.empty(B, np.int64)
+    at = seams.spread(B, 7)                                            # triplet k stands at position at[k]
+    u[at], i[at], j[at] = trip[:, 0], trip[:, 1], trip[:, 2]
+    du, dv, ou, ov = seams.sorted_dest(np.concatenate([u, u]), np.concatenate([i, j]), U, I)
+    assert want_u <= seams.facts(du, U) and want_i <= seams.facts(dv, I), (seams.facts(du, U), seams.facts(dv, I))
+    if name == 'bad-negative-far':
+        p = int(at[-1])
+        for order in (ou, ov):
+            assert np.flatnonzero(order == p)[0] // seams.C != np.flatnonzero(order == B + p)[0] // seams.C
+    keep = (u >= 0) & (u < U) & (i >= 0) & (i < I) & (j >= 0) & (j < I)
+    P, Q = params(D, U, I, D)
+    grads, _ = check_vs_float64(P, Q, u, i, j, None, COEFS, f'{name} D={D}', keep=None if keep.all() else keep)
+    idle_u, idle_i = np.setdiff1d(np.arange(U), u[keep]), np.setdiff1d(np.arange(I), np.concatenate([i[keep], j[keep]]))
+    assert len(idle_u) and len(idle_i) and not grads[0][idle_u].any() and not grads[1][idle_i].any()
 
 
 # ------------------------------------------------------------------------------------------------ 4: bad ids

@@ -11,6 +11,7 @@ import torch
 from invpref_kdd_2022_amd import _capi, ops, plan as planlib
 from invpref_kdd_2022_amd.baseline import (PURE_LOSS_KEYS, CVIBExplicitTrainManager, CVIBTrainManager,
                                            PureExplicitMatrixFactorization, PureMatrixFactorization)
+import chunk_seams as seams
 from cvib_fixture import CASES, cvib_inputs, info64, recorded_draws, step64, trajectory64
 
 pytestmark = pytest.mark.gpu
@@ -169,6 +170,75 @@ def test_bad_ids_are_skipped_and_poison_the_loss():
     assert abs(k_pb - pb) <= 1e-6 and abs(k_qb - qb) <= 1e-6       # the means' divisor counts the skipped pairs
     np.testing.assert_allclose(gP, dP64, atol=2e-7 * np.abs(dP64).max() + 1e-12)
     np.testing.assert_allclose(gQ, dQ64, atol=2e-7 * np.abs(dQ64).max() + 1e-12)
+
+
+# name: (B, the user side's runs (entries per destination, ascending ids), the item side's, pairs with an id outside its table,
+#        the alignments (chunk_seams.facts) the user side and the item side must contain)
+SEAM_CASES = {
+    'one-chunk': (8, [3, 5, 8], [16], 0, {'one_chunk'}, {'one_chunk', 'single'}),
+    'full-chunks': (32, [10, 6, 4, 34, 5, 5], [1, 31, 32], 0, {'full_chunks', 'ends_at_15', 'long_then_direct'}, {'ends_at_15'}),
+    'ragged-tail': (33, [15, 2, 31, 18], [66], 0, {'ragged_tail'}, {'ragged_tail', 'single'}),
+    'sentinel-at-0': (32, [20, 28], [48], 16, {'sentinel_at_0'}, {'sentinel_at_0', 'single'}),
+    'sentinel-at-1': (32, [16, 33], [49], 15, {'sentinel_at_1'}, {'sentinel_at_1', 'single'}),
+    'hot-row': (160, [5, 300, 15], [16] * 20, 0, {'long_then_direct'}, {'full_chunks', 'ends_at_15'}),
+}
+
+
+@pytest.mark.parametrize('D', [24, 64, 256])
+@pytest.mark.parametrize('name', list(SEAM_CASES))
+def test_chunk_seams(name, D):
+    """The alignments of destinations to the 16-entry chunks at which the scatter / boundary walk (csrc/chunk_walk.hpp) decides
+    between a direct write, a head slot and a tail slot, on ids built by hand (tables of 64 rows): 2 B = 16, a multiple of 16
+    and 16 k + 2 (2 B is even: the list that ends one entry into a chunk is the one with 16 k + 1 live entries); a destination
+    that ends on a chunk's last entry; one that starts in mid-chunk, spans three chunks or more and is followed by one wholly
+    inside its last chunk; one destination with every entry of its side; the sentinel run starting on a chunk's first and
+    second entry.  The test asserts that its lists contain them.  Checks and tolerances are test_kernel_vs_float64's (the pairs
+    with a bad id left out of both float64 statements, the divisor kept), and a bad id makes info and the loss NaN."""
+    B, runs_u, runs_v, n_bad, want_u, want_v = SEAM_CASES[name]
+    U = I = 64
+    n_live = 2 * B - n_bad
+    assert sum(runs_u) == n_live and sum(runs_v) == n_live
+    uu = seams.ids_of([(3 * k + 1, n) for k, n in enumerate(runs_u)])
+    vv = seams.ids_of([(2 * k + 5, n) for k, n in enumerate(runs_v)])[seams.spread(n_live, 13)]
+    bad = np.arange(n_bad)
+    uu = np.concatenate([uu, np.where(bad % 2 == 0, U + 3, 7)])        # bad users and bad items take turns
+    vv = np.concatenate([vv, np.where(bad % 2 == 0, 9, -2)])
+    at = seams.spread(2 * B, 7)                                       # pair k stands at position at[k]
+    pu, pv = np.empty(2 * B, np.int64), np.empty(2 * B, np.int64)
+    pu[at], pv[at] = uu, vv
+    u, v, ru, rv = pu[:B], pv[:B], pu[B:], pv[B:]
+    du, dv, _, _ = seams.sorted_dest(pu, pv, U, I)
+    assert want_u <= seams.facts(du, U) and want_v <= seams.facts(dv, I), (seams.facts(du, U), seams.facts(dv, I))
+    rs = np.random.RandomState(D)
+    P = (rs.standard_normal((U, D)) * 0.95 * D ** -0.25).astype(np.float32)
+    Q = (rs.standard_normal((I, D)) * 0.95 * D ** -0.25).astype(np.float32)
+    alpha, gamma, eps = 0.1, 0.01, 0.0
+    ok = (pu >= 0) & (pu < U) & (pv >= 0) & (pv < I)
+    ok_p, ok_q = ok[:B], ok[B:]
+    info, pb, qb, dP64, dQ64, _ = info64(P, Q, u[ok_p], v[ok_p], ru[ok_q], rv[ok_q], True, alpha, gamma, eps, n=B)
+    gP, gQ, loss, (k_info, k_pb, k_qb) = run_kernel(P, Q, u, v, ru, rv, True, alpha, gamma, 1.0, eps)
+    y = (np.arange(2 * B) % 2).astype(np.float32)
+    bP, bQ, bL = pure_pass_on_pairs(P, Q, pu[ok], pv[ok], y[ok], True)
+    eP = float(np.abs(gP - dP64).max() / np.abs(dP64).max())
+    eQ = float(np.abs(gQ - dQ64).max() / np.abs(dQ64).max())
+    eS = [abs(k_pb - pb) / abs(pb), abs(k_qb - qb) / abs(qb)] + ([] if n_bad else [abs(k_info - info) / abs(info)])
+    print(f'{name} D={D}: kernel vs float64 rel dP {eP:.2e} dQ {eQ:.2e} means, info {max(eS):.2e}; PureMF pass on the pair list '
+          f'dP {bP:.2e} dQ {bQ:.2e} loss {bL:.2e}')
+    assert eP <= 2 * max(bP, 2 * F32_HALF_ULP) and eQ <= 2 * max(bQ, 2 * F32_HALF_ULP)
+    assert max(eS) <= 2 * max(bL, F32_HALF_ULP)
+    if n_bad:
+        assert np.isnan(k_info) and np.isnan(loss)
+    else:
+        assert loss == k_info
+    outU, outI = np.setdiff1d(np.arange(U), pu[ok]), np.setdiff1d(np.arange(I), pv[ok])
+    assert len(outU) and len(outI) and not gP[outU].any() and not gQ[outI].any()
+    # added into a non-zero buffer, exactly fl(g0 + row sum): one writer per row at every seam
+    g0P, g0Q = rs.standard_normal(P.shape).astype(np.float32), rs.standard_normal(Q.shape).astype(np.float32)
+    aP, aQ, _, _ = run_kernel(P, Q, u, v, ru, rv, True, alpha, gamma, 1.0, eps, g0P, g0Q)
+    np.testing.assert_array_equal(aP, g0P + gP)
+    np.testing.assert_array_equal(aQ, g0Q + gQ)
+    np.testing.assert_array_equal(aP[outU], g0P[outU])
+    np.testing.assert_array_equal(aQ[outI], g0Q[outI])
 
 
 def test_bitwise_repeat_and_graph_replay():
