@@ -12,7 +12,7 @@ classifier absent (``INVPREF_PURE_MF``: never loaded, never stored), one environ
 ``(1, 0, 0, 2*L2_coe, 2*L1_coe, alpha=0)`` the InvPref loss IS ``score_loss + L2_coe*L2_reg + L1_coe*L1_reg``
 of train.py:389-397 (the InvPref regularisers are normalised by 2*B*D, PureMF's by B*D; see
 oracle/oracle.py ``pure_mf_*`` for the CPU statement of the same mapping, pinned by goldens g7).  The
-managers reuse the epoch engine of ``train.py`` (row plans, fused Adam, HIP-graph replay, deferred read-backs).
+managers are built on the epoch engine of ``engine.py`` (row plans, fused Adam, HIP-graph replay, deferred read-backs).
 
 IPS-MF / SNIPS-MF (baseline_train.py:317-581, :800-976) are the same step with a fixed per-interaction weight on the score
 loss (``INVPREF_REWEIGHT_REC``): the inverse propensities are formed once on the device (csrc/invpref_propensity.hip), and
@@ -26,7 +26,7 @@ from torch import nn
 
 from . import _capi, ops
 from . import plan as planlib
-from .train import _InvPrefTrainManager
+from .engine import _EpochEngine
 
 PURE_LOSS_KEYS = ['score_loss', 'L2_reg', 'L1_reg', 'loss']  # train.py:399-404
 
@@ -112,10 +112,9 @@ class PureExplicitMatrixFactorization(_PureMFBase):
             return self._scores(users_id, items_id).reshape(-1)
 
 
-class _BasicTrainManager(_InvPrefTrainManager):
-    """Basic{Implicit,Explicit}TrainManager (train.py:345-461, :1022-1138) on the fused PureMF step."""
-    _pure = True
-    _make_tables = staticmethod(_capi.make_pure_tables)
+class _BasicTrainManager(_EpochEngine):
+    """Basic{Implicit,Explicit}TrainManager (train.py:345-461, :1022-1138) on the fused PureMF step: the epoch engine as it
+    is (engine.py: every hook's default is PureMF's answer) + the coefficients, the four loss keys and train_a_batch."""
 
     def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int,
                  epochs: int, evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float,
@@ -128,11 +127,6 @@ class _BasicTrainManager(_InvPrefTrainManager):
                           flags=ops.flags_of(self.implicit, False, False, True, False, dense_reg=False) | _capi.PURE_MF,
                           users_first=None,     # [user table | item table]: the shared part is last as listed
                           env_switches=False)
-        # no environments: the engine's env / weight pointers are never dereferenced under INVPREF_PURE_MF
-        self.envs = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.sample_weights = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.alpha, self.update_alpha = 0., False
-        self.cluster_interval = 1 << 62
 
     def _coefs(self, alpha):
         return (1., 0., 0., 2. * self.L2_coe, 2. * self.L1_coe, 0.)
@@ -183,16 +177,6 @@ class _BasicTrainManager(_InvPrefTrainManager):
                 ops.adam_(st.param[o:o + ln], st.grad[o:o + ln], st.exp_avg[o:o + ln], st.exp_avg_sq[o:o + ln], st.step,
                           self.lr, zero_grad=False)
         return self.loss_dicts(st.losses6[None])[0]
-
-    def train(self, silent: bool = False, auto: bool = False):
-        """train.py:428-461: ((loss dicts, epochs), (test results, epochs)) of the engine's outer loop."""
-        return self._train_span(silent, auto, initial=True)[:2]
-
-    # the InvPref-only parts of the engine do not exist here
-    def cluster(self, *a, **k):
-        raise AttributeError('PureMF has no environments')
-
-    stat_envs = cluster_a_batch = update_each_env_count = cluster
 
 
 class BasicImplicitTrainManager(_BasicTrainManager):
@@ -824,8 +808,8 @@ class _CVIBMixin(_DrawnTermMixin):
     _INDEX_BUDGET = 512 << 20
 
     def _cvib_init(self, alpha, gamma, info_coe, eps, draws):
-        # (the engine's `alpha` is InvPref's environment weight, which a PureMF step never reads: the attribute is CVIB's here,
-        #  as in the reference)
+        # (the engine's `alpha` is what _alpha_for() hands to _coefs(), which a PureMF step never reads: the attribute is CVIB's
+        #  here, as in the reference)
         self.alpha, self.gamma, self.info_coe, self.eps = float(alpha), float(gamma), float(info_coe), float(eps)
         n, bs = self.n_total, self.batch_size
         self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]

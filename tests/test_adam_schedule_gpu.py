@@ -21,7 +21,8 @@ import torch
 from invpref_kdd_2022_amd import _capi, ops, plan as planlib, synth
 from invpref_kdd_2022_amd.baseline import BasicImplicitTrainManager, PureMatrixFactorization
 from invpref_kdd_2022_amd.models import InvPrefExplicit, InvPrefImplicit
-from invpref_kdd_2022_amd.train import LOSS_KEYS, ExplicitTrainManager, ImplicitTrainManager, _InvPrefTrainManager
+from invpref_kdd_2022_amd.engine import _EpochEngine
+from invpref_kdd_2022_amd.train import LOSS_KEYS, ExplicitTrainManager, ImplicitTrainManager
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda:0')
@@ -371,7 +372,7 @@ def _train(name: str, sched_n: int, monkeypatch, no_graph: bool = False) -> dict
         monkeypatch.setenv(k, v)
     if no_graph:
         monkeypatch.setenv('INVPREF_NO_GRAPH', '1')
-    monkeypatch.setattr(_InvPrefTrainManager, '_SCHED_N', sched_n)
+    monkeypatch.setattr(_EpochEngine, '_SCHED_N', sched_n)
     U, I, E, D, n, bs, cls = (c[k] for k in ('U', 'I', 'E', 'D', 'n', 'bs', 'cls'))
     pure = cls is BasicImplicitTrainManager
     data = synth.interactions(41 + D, U, I, n, implicit=cls.implicit)
@@ -499,7 +500,7 @@ def test_eager_epochs_equal_replayed_ones_alternating_form(monkeypatch):
 def test_a_run_longer_than_the_table_is_refused(monkeypatch):
     """_sched_prepare(steps_ahead) refills when a run does not fit; a run longer than the table itself cannot be made to fit
     (its last steps would reuse stale scalars): InvPrefError, before anything is launched."""
-    monkeypatch.setattr(_InvPrefTrainManager, '_SCHED_N', 16)
+    monkeypatch.setattr(_EpochEngine, '_SCHED_N', 16)
     for k in _SWITCHES:
         monkeypatch.delenv(k, raising=False)
     U, I, E, D = 300, 40, 4, 64

@@ -11,6 +11,7 @@ import torch
 from invpref_kdd_2022_amd import _capi, build, ops, plan as planlib, synth, torch_ops, torch_ops_adam_rows
 from invpref_kdd_2022_amd import baseline as B
 from invpref_kdd_2022_amd.models import InvPrefImplicit
+from invpref_kdd_2022_amd.engine import _EpochEngine
 from invpref_kdd_2022_amd.train import ImplicitTrainManager, _InvPrefTrainManager, touched_row_offsets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -213,11 +214,11 @@ def test_world_size_two_raises():
 def test_switch_is_a_method_of_every_manager_and_off_by_default():
     U, I, D, n, bs = _SHAPE
     data = synth.interactions(1, U, I, n)
-    assert 'set_lazy_adam' in vars(_InvPrefTrainManager)
-    for cls in (B.BasicImplicitTrainManager, B.BasicExplicitTrainManager, B.BasicUniformImplicitTrainManager,
+    assert 'set_lazy_adam' in vars(_EpochEngine)
+    for cls in (_InvPrefTrainManager, B.BasicImplicitTrainManager, B.BasicExplicitTrainManager, B.BasicUniformImplicitTrainManager,
                 B.BasicUniformExplicitTrainManager, B.IPSBasicTrainManager, B.SNIPSMFTrainManager,
                 B.IPSBasicExplicitTrainManager, B.SNIPSExplicitMFTrainManager):
-        assert cls.set_lazy_adam is _InvPrefTrainManager.set_lazy_adam and cls._lazy_adam_unsupported is None
+        assert cls.set_lazy_adam is _EpochEngine.set_lazy_adam and cls._lazy_adam_unsupported is None
     mgr = _implicit(U, I, 4, D, data, bs)
     assert mgr._lazy is False and mgr._fused_seq()
     mgr.set_lazy_adam(True)

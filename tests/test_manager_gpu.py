@@ -770,3 +770,47 @@ def test_explicit_evaluator_matches_reference():
 
     res = ExplicitTestManager(model, L()).evaluate()
     np.testing.assert_allclose([res['mse'], res['rmse'], res['mae']], z['explicit'], rtol=2e-6)
+
+
+@pytest.mark.parametrize('cls', [ImplicitTrainManager, ExplicitTrainManager])
+def test_train_returns_its_three_tuples_through_the_engine_hooks(cls):
+    """train() on the engine's outer loop (engine.py) with the cluster events as its hooks: two minibatches, two epochs, a
+    cluster event after each -- the initial evaluation and stat_envs, a run, the event, the deferred read-back.  The three
+    tuples have the reference's shapes (train.py:282-342), silent or printing, and hold the same values either way; a PureMF
+    manager returns the first two."""
+    import contextlib
+    import io
+    from invpref_kdd_2022_amd.baseline import BasicImplicitTrainManager, PureMatrixFactorization
+    U, I, E, D, n, bs = 60, 40, 3, 16, 256, 128
+    implicit = cls is ImplicitTrainManager
+    data = torch.from_numpy(synth.interactions(3, U, I, n, implicit=implicit)).to(DEV)
+    tabs = synth.tables(4, U, I, E, D, std=0.2)
+    results = []
+    for silent in (True, False):
+        model = (InvPrefImplicit if implicit else InvPrefExplicit)(U, I, E, D)
+        model.load_state_dict({k: torch.from_numpy(tabs[k]) for k in O.PARAM_NAMES})
+        np.random.seed(9)
+        mgr = cls(model=model, evaluator=StubEvaluator(), device=DEV, training_data=data, batch_size=bs, epochs=2,
+                  cluster_interval=1, evaluate_interval=1, lr=0.01, invariant_coe=1., env_aware_coe=1., env_coe=1., L2_coe=0.1,
+                  L1_coe=0.01, cluster_use_random_sort=False)
+        assert mgr.batch_num == 2
+        out = io.StringIO()
+        with contextlib.redirect_stdout(out):
+            res = mgr.train(silent=silent)
+        assert (out.getvalue() == '') == silent and (silent or out.getvalue().count('cluster at epoch:') == 2)
+        assert isinstance(res, tuple) and len(res) == 3
+        (losses, loss_epochs), (tests, test_epochs), (diffs, cnts, cluster_epochs) = res
+        assert loss_epochs == [1, 2] and [list(d) for d in losses] == [list(LOSS_KEYS)] * 2
+        assert all(type(v) is float for d in losses for v in d.values())
+        assert test_epochs == [0, 1, 2] and tests == [{'stub': 0.0}] * 3
+        assert cluster_epochs == [1, 2] and len(diffs) == 2 and all(type(d) is int and 0 <= d <= n for d in diffs)
+        assert all(type(c) is dict and list(c) == list(range(E)) and all(type(x) is int for x in c.values())
+                   and sum(c.values()) == n for c in cnts) and len(cnts) == 2
+        assert mgr.epoch_cnt == 2 and mgr._cluster_events is None
+        results.append(res)
+    assert results[0] == results[1]
+    pure = PureMatrixFactorization(U, I, D)
+    res = BasicImplicitTrainManager(pure, StubEvaluator(), DEV, torch.from_numpy(synth.interactions(3, U, I, n)).to(DEV), bs, 2,
+                                    1, 0.01, 0., 0.).train(silent=True)
+    assert len(res) == 2 and res[0][1] == [1, 2] and res[1] == ([{'stub': 0.0}] * 3, [0, 1, 2])
+    assert [list(d) for d in res[0][0]] == [['score_loss', 'L2_reg', 'L1_reg', 'loss']] * 2
