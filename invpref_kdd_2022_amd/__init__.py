@@ -10,9 +10,11 @@ _CAUSE = ('CausEMatrixFactorization', 'CausEExplicitMatrixFactorization', 'CausE
 
 _BPR = ('BPRTrainManager',)
 
+_DR = ('DRMatrixFactorization', 'DRExplicitMatrixFactorization', 'DRTrainManager', 'DRExplicitTrainManager')
+
 
 def __getattr__(name):   # resolved on first use: importing the package loads neither torch nor the HIP library
-    if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE or name in _BPR:
+    if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE or name in _BPR or name in _DR:
         from . import baseline
         return getattr(baseline, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

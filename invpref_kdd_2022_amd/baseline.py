@@ -1,6 +1,6 @@
 """PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF,
-CVIB-MF and fairness-MF; and MACR-MF, LinearTrans-MF and CausE, whose steps are gradient passes of their own
-(csrc/invpref_macr.hip, csrc/invpref_lintrans.hip, csrc/invpref_cause.hip).
+CVIB-MF and fairness-MF; and MACR-MF, LinearTrans-MF, CausE, BPR-MF and doubly robust MF, whose steps are gradient passes of
+their own (csrc/invpref_macr.hip, csrc/invpref_lintrans.hip, csrc/invpref_cause.hip, csrc/invpref_bpr.hip, csrc/invpref_dr.hip).
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -1518,3 +1518,189 @@ class BPRTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
             self._caller = None
         self.step_id += 1
         return out
+
+
+# ------------------------------------------------------------------------------------------------ doubly robust MF
+DR_LOSS_KEYS = ('score_loss', 'imputation_loss', 'L2_reg', 'L1_reg', 'loss')
+
+
+class _DRModelMixin:
+    """What DRMatrixFactorization and its explicit twin add to a PureMF model: the imputation pair imp_user_emb / imp_item_emb,
+    an MF of the same shape that predicts the prediction model's error (include/invpref_dr.h), initialised N(0, 0.01) after
+    the prediction pair (state_dict order: user_emb, item_emb, imp_user_emb, imp_item_emb)."""
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int):
+        super().__init__(user_num, item_num, factor_num)
+        self.imp_user_emb = nn.Embedding(user_num, factor_num)
+        self.imp_item_emb = nn.Embedding(item_num, factor_num)
+        nn.init.normal_(self.imp_user_emb.weight, std=0.01)
+        nn.init.normal_(self.imp_item_emb.weight, std=0.01)
+
+    def tables(self):
+        """the four tables in state_dict order: the prediction pair first, so whatever ranks tables()[0] . tables()[1] ranks
+        the prediction model"""
+        return [self.user_emb.weight, self.item_emb.weight, self.imp_user_emb.weight, self.imp_item_emb.weight]
+
+    def imputation(self, users_id, items_id):
+        """the imputation model at the pairs: the soft pseudo-label sigmoid(z) (implicit) or the imputed score z (explicit),
+        z = imp_user_emb[u] . imp_item_emb[i]; a plain tensor expression"""
+        z = (self.imp_user_emb(users_id) * self.imp_item_emb(items_id)).sum(-1)
+        return torch.sigmoid(z) if self.implicit else z
+
+
+class DRMatrixFactorization(_DRModelMixin, PureMatrixFactorization):
+    """A PureMatrixFactorization with an imputation pair: predict(), recommend() and the Implicit*TestManagers' fused routes rank
+    the prediction pair."""
+    implicit = True
+
+
+class DRExplicitMatrixFactorization(_DRModelMixin, PureExplicitMatrixFactorization):
+    """A PureExplicitMatrixFactorization with an imputation pair; predict(users, items) scores the prediction pair."""
+    implicit = False
+
+
+class _DRManagerMixin(_DrawnTermMixin):
+    """Doubly robust joint learning (Wang et al., ICML 2019) on a DR*MatrixFactorization: per step, over the B rows of a
+    minibatch with inverse propensities w and as many pairs drawn uniformly from the whole user x item grid,
+        loss = score_loss + imputation_loss + L2_coe * L2_reg + L1_coe * L1_reg
+        score_loss      = [sum_observed w d + sum_drawn e^] / B        imputation_loss = [sum_observed w d^2] / B
+    with e^ the error the imputation model predicts and d = e - e^ (include/invpref_dr.h states both forms, the factors and
+    the draw rule).  JOINT learning with SIMULTANEOUS updates: both gradients are taken at the same parameters, the cross terms
+    detached (score_loss sees the imputation tables as constants and imputation_loss the prediction tables, as CausE's step
+    detaches its teacher), and ONE Adam step moves all four tables.  It is not the paper's alternating two-optimiser loop; it
+    keeps the engine's one-Adam-per-step sequence and its device-side schedule as they are.
+
+    Basic*TrainManager's signature plus keyword-only arguments:
+
+    seed             names the trajectory: with the global step counter `step_id` it keys every draw, so the same seed gives
+                     the same bits whatever the run lengths, with graphs or without
+    weights          one fp32 inverse propensity per row of training_data
+    propensity_func  basic_item_ / basic_user_ / basic_pair_propensity_func: the weights are formed on the device from the
+                     interaction counts (smooth_weight_coe their exponent), as the IPS managers form theirs, and kept as
+                     inverse_propensity_tensor.  Neither given: every weight is 1.  Both given: ValueError.
+
+    Always the unfused sequence, ops.dr_grad (every row of the four gradients overwritten) -> dense / ranged Adam.  Before a
+    run of epochs is enqueued ONE ops.dr_draw launch and ONE ops.cvib_index pass cover all its steps (the staging hooks of
+    _DrawnTermMixin, the device draw standing where the host staging is); the captured launches read their row of both
+    buffers when they run, so a replay follows new draws without re-capture.  Single process."""
+    _SINGLE = ('doubly robust MF runs in a single process (a sharded form would all-reduce the summed gradient of all four '
+               'tables; not implemented)')
+    _LOSS_KEYS = DR_LOSS_KEYS       # what the pass writes into the first slots of a step's losses
+    _INDEX_BUDGET = _CVIBMixin._INDEX_BUDGET
+    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    _lazy_adam_unsupported = ('the doubly robust pass stores zeros to every idle row, its drawn pairs reach rows outside the '
+                              'minibatch and Adam runs over the whole tables: a lazy form is not built')
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, seed: int = 0,
+                 weights=None, propensity_func=None, smooth_weight_coe: float = 1.0, rank=None, world_size=None,
+                 process_group=None):
+        self._require_single_process(world_size)
+        if weights is not None and propensity_func is not None:
+            raise ValueError('give weights or propensity_func, not both')
+        if propensity_func is not None and propensity_func not in _COUNT_KINDS:
+            raise ValueError('propensity_func must be basic_item_propensity_func, basic_user_propensity_func or '
+                             'basic_pair_propensity_func')
+        if len(model.tables()) != 4:
+            raise TypeError(f'{type(self).__name__} needs a model with an imputation pair (DRMatrixFactorization / '
+                            'DRExplicitMatrixFactorization)')
+        if weights is not None:
+            weights = torch.as_tensor(weights).detach().reshape(-1).to(torch.float32)
+            if weights.numel() != training_data.shape[0]:
+                raise ValueError(f'weights holds {weights.numel()} values for {training_data.shape[0]} rows')
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        self.seed, self.step_id = int(seed), 0     # step_id: the global step counter, the name of the next step's draws
+        self.smooth_weight_coe, self.propensity_func = smooth_weight_coe, propensity_func
+        U, I, dev = model.user_num, model.item_num, self.device
+        self.inverse_propensity_tensor = None
+        if weights is not None:
+            self.inverse_propensity_tensor = weights.contiguous().to(dev)
+        elif propensity_func is not None:
+            cnt = ops.interaction_counts(self.users_tensor, self.items_tensor, U, I)
+            self.inverse_propensity_tensor = ops.count_propensity(*cnt, self.users_tensor, self.items_tensor,
+                                                                  _COUNT_KINDS[propensity_func], smooth_weight_coe)
+        n, bs = self.n_total, self.batch_size
+        self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]
+        self._cap = max(self._batch_lens)
+        self._init_draws(None, [], self._cap, 2 * self._cap)    # a staging row: the step's drawn users, then its drawn items
+        self._draws = self._index = self._caller = None
+        self._dr_ws = ops.Workspace(dev)
+        self._dr_ws.get(max(ops.dr_workspace_bytes(U, I, self._cap, model.factor_num), 16))   # sized once: capturable launches
+
+    _limit_run = _CVIBMixin._limit_run
+
+    def _staging_resized(self, rows: int) -> None:
+        dev = self.device
+        self._draws = self._staged.view(rows, 2, self._cap)
+        self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
+        lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
+        self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
+        self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
+        self._step_ramp = torch.arange(rows, dtype=torch.int64, device=dev)
+        self._step_ids = torch.zeros(rows, dtype=torch.int64, device=dev)
+
+    def _stage_draws(self, n: int) -> None:
+        """the drawn pairs of the next n epochs' steps in one launch, then their index in one pass"""
+        steps, m = n * self.batch_num, self.model
+        torch.add(self._step_ramp[:steps], self.step_id, out=self._step_ids[:steps])
+        ops.dr_draw(self._step_n[:steps], self._step_ids[:steps], m.user_num, m.item_num, self.seed, out=self._draws[:steps])
+        ops.cvib_index(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._draws[:steps],
+                       m.user_num, m.item_num, out=self._index[:steps])
+
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        before = self.epoch_cnt
+        out = super()._enqueue_epochs(want)
+        self.step_id += (self.epoch_cnt - before) * self.batch_num   # (a failed capture runs one eager epoch of the staged n)
+        return out
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        if k is None:
+            users, items, du, di, index, w = self._caller
+        else:
+            b, s = self._raw_batches[k], self._loss_slot * self.batch_num + k
+            du, di, index = self._draws[s, 0, :b.n], self._draws[s, 1, :b.n], self._index[s]
+            w = None if self.inverse_propensity_tensor is None else self.inverse_propensity_tensor[b.lo:b.lo + b.n]
+        st = self.state
+        ops.dr_grad(0 if self.implicit else 1, st.p_views, st.g_views, users, items, scores, du, di, index, self.L2_coe,
+                    self.L1_coe, losses6[:5], weights=w, workspace=self._dr_ws)
+
+    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
+        """(the pass is the whole step: no further term)"""
+
+    @classmethod
+    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
+        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.tolist()]
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, weight_tensor=None) -> dict:
+        """one step on caller tensors (weight_tensor: the rows' inverse propensities, None: 1): as many pairs as the minibatch
+        has rows are drawn under the next step id, this minibatch's index is built here"""
+        dev, m = self.device, self.model
+        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64).contiguous()
+        B = ud.numel()
+        if B == 0:
+            raise ValueError('an empty minibatch')
+        w = None if weight_tensor is None else weight_tensor.detach().to(dev).float().reshape(-1).contiguous()
+        if w is not None and w.numel() != B:
+            raise ValueError(f'weight_tensor holds {w.numel()} values for {B} rows')
+        draws = ops.dr_draw(torch.full((1,), B, dtype=torch.int32, device=dev),
+                            torch.full((1,), self.step_id, dtype=torch.int64, device=dev), m.user_num, m.item_num, self.seed,
+                            batch_cap=B)
+        self._dr_ws.get(max(ops.dr_workspace_bytes(m.user_num, m.item_num, B, m.factor_num), 16))
+        self._caller = (ud, vd, draws[0, 0], draws[0, 1], ops.dr_index(ud, vd, draws[0, 0], draws[0, 1], m.user_num, m.item_num), w)
+        try:
+            out = self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
+        finally:
+            self._caller = None
+        self.step_id += 1
+        return out
+
+
+class DRTrainManager(_DRManagerMixin, BasicImplicitTrainManager):
+    """doubly robust MF on implicit feedback (form 0: BCE against the soft pseudo-label) over a DRMatrixFactorization"""
+
+
+class DRExplicitTrainManager(_DRManagerMixin, BasicExplicitTrainManager):
+    """doubly robust MF on explicit feedback (form 1: squared error) over a DRExplicitMatrixFactorization"""

@@ -24,6 +24,7 @@ from . import torch_ops_truth_rank_scored  # noqa: F401  (its scaled / weighted 
 from . import torch_ops_catalog  # noqa: F401  (the catalogue metrics' fragment: torch.ops.invpref.catalog_*)
 from . import torch_ops_rank_stats  # noqa: F401  (weighted / grouped rank metrics and bootstrap sums: their fragment)
 from . import torch_ops_bpr  # noqa: F401  (BPR-MF's fragment: torch.ops.invpref.bpr_draw, bpr_grad_)
+from . import torch_ops_dr  # noqa: F401  (doubly robust MF's fragment: torch.ops.invpref.dr_draw, dr_grad_)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -1084,3 +1085,65 @@ def bpr_grad(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Te
     ws = (workspace or Workspace(user_table.device)).get(nbytes)
     _o().bpr_grad_(user_table, item_table, users, pos_items, neg, weights, index, float(L2_coe), float(L1_coe), grad_user,
                    grad_item, losses4, ws)
+
+
+# ---- doubly robust MF (include/invpref_dr.h, csrc/invpref_dr.hip)
+DR_FORMS = {'implicit': 0, 'explicit': 1}
+
+
+def dr_draw(step_n: torch.Tensor, step_id: torch.Tensor, user_num: int, item_num: int, seed: int = 0,
+            batch_cap: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The drawn (user, item) pairs of a run of steps in ONE launch.  Step s draws step_n[s] (int32) pairs under the name
+    step_id[s] (int64: a global step counter, distinct for every step ever issued).  -> draws int32 [steps, 2, batch_cap] in
+    cvib_index's layout (draws[s, 0]: users, draws[s, 1]: items), written into `out` if given (then nothing is allocated:
+    capturable; out may be rows of a wider buffer).  The draw rule is stated in include/invpref_dr.h: Philox4x32-10 keyed by
+    seed, counter (position, 0, step_id), u = (word0 * user_num) >> 32, i = (word1 * item_num) >> 32 -- uniform over the whole
+    grid, with replacement, no rejection.  Both halves are -1 at a position beyond step_n[s].  The caller guarantees
+    step_n[s] <= batch_cap."""
+    _gpu(step_n, step_id, out)
+    if out is None:
+        if batch_cap is None:
+            raise InvPrefError('dr_draw: give batch_cap (the row length of draws) or out=draws')
+        out = torch.empty(step_n.numel(), 2, int(batch_cap), dtype=torch.int32, device=step_n.device)
+    _o().dr_draw(step_n, step_id, int(user_num), int(item_num), _seed64(seed), out)
+    return out
+
+
+def dr_workspace_bytes(user_num: int, item_num: int, batch: int, factor_num: int) -> int:
+    """the records, float64 partials and chunk slots of one gradient pass: a function of the sizes alone, non-decreasing in
+    each; 0: not taken"""
+    return int(_capi.lib().invpref_dr_workspace_bytes(int(user_num), int(item_num), int(batch), int(factor_num)))
+
+
+def dr_index(users: torch.Tensor, items: torch.Tensor, draw_users: torch.Tensor, draw_items: torch.Tensor, user_num: int,
+             item_num: int) -> torch.Tensor:
+    """The inverted index of ONE step's 2B positions, int32 [2, 2 B, 2], through cvib_index: position p is the observed pair p,
+    position B + p the drawn pair p.  For single calls; a manager indexes a whole run of steps in one cvib_index pass."""
+    B, dev = users.numel(), users.device
+    draws = torch.stack([draw_users.to(torch.int32), draw_items.to(torch.int32)])[None].contiguous()
+    return cvib_index(users, items, torch.zeros(1, dtype=torch.int64, device=dev),
+                      torch.full((1,), B, dtype=torch.int32, device=dev), draws, user_num, item_num)[0]
+
+
+def dr_grad(form, params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor], users: torch.Tensor, items: torch.Tensor,
+            scores: torch.Tensor, draw_users: torch.Tensor, draw_items: torch.Tensor, index: torch.Tensor, L2_coe: float,
+            L1_coe: float, losses5: torch.Tensor, weights: Optional[torch.Tensor] = None,
+            workspace: Optional[Workspace] = None) -> None:
+    """The gradient pass of one doubly robust step (include/invpref_dr.h states it).  form: 'implicit' / 0 (BCE against the
+    soft pseudo-label sigmoid(z)) or 'explicit' / 1 (squared error); params4 / grads4: (prediction user table, prediction item
+    table, imputation user table, imputation item table) and their gradients; users / items int64 [B], scores fp32 [B],
+    weights fp32 [B] (inverse propensities; None: 1), draw_users / draw_items int32 [B]; index: the step's slice of cvib_index
+    with the drawn pairs as its draws (dr_index for one step).  The two losses are differentiated at the same parameters with
+    the cross terms detached.  OVERWRITES every row of the four gradients (rows without a position get zeros) and losses5 =
+    (score_loss, imputation_loss, L2_reg, L1_reg, loss).  Bitwise reproducible, no float atomics, no host sync (capturable once
+    the workspace is sized; a replay reads ids, scores, weights, draws and index as they are then).  A position with an id
+    outside its table (a drawn -1 included) is skipped and the five losses are NaN."""
+    _gpu(users, items, scores, draw_users, draw_items, index, losses5, weights, *params4, *grads4)
+    P, Q = params4[0], params4[1]
+    nbytes = dr_workspace_bytes(P.shape[0], Q.shape[0], users.numel(), P.shape[1])
+    if nbytes == 0:
+        raise InvPrefError(f'dr_grad: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
+                           f'{users.numel()} observed rows)')
+    ws = (workspace or Workspace(P.device)).get(nbytes)
+    _o().dr_grad_(DR_FORMS[form] if isinstance(form, str) else int(form), *params4, users, items, scores, weights, draw_users,
+                  draw_items, index, float(L2_coe), float(L1_coe), *grads4, losses5, ws)
