@@ -12,8 +12,13 @@ _BPR = ('BPRTrainManager',)
 
 _DR = ('DRMatrixFactorization', 'DRExplicitMatrixFactorization', 'DRTrainManager', 'DRExplicitTrainManager')
 
+_EVALUATE = ('ExplicitRankTestManager',)
+
 
 def __getattr__(name):   # resolved on first use: importing the package loads neither torch nor the HIP library
+    if name in _EVALUATE:
+        from . import evaluate
+        return getattr(evaluate, name)
     if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE or name in _BPR or name in _DR:
         from . import baseline
         return getattr(baseline, name)

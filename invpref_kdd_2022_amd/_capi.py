@@ -103,7 +103,8 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 # (csrc/invpref_adam_rows.hip), rank-based evaluation (csrc/invpref_truth_rank.hip) and its scaled and weighted forms (the same
 # file), the catalogue metrics (csrc/invpref_catalog.hip), the weighted / grouped rank metrics and the bootstrap sums
 # (csrc/invpref_rank_stats.hip), BPR-MF's negative sampler and gradient pass (csrc/invpref_bpr.hip), doubly
-# robust MF's pair sampler and gradient pass (csrc/invpref_dr.hip).
+# robust MF's pair sampler and gradient pass (csrc/invpref_dr.hip), the segment ranks and AUC pair counts of explicit evaluation
+# (csrc/invpref_segment_rank.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
@@ -131,6 +132,8 @@ BPR_MAX_BATCH, BPR_MAX_STEPS, BPR_MAX_ATTEMPTS = (BPR_DEFINES['BPR_' + n] for n 
 DR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_dr.h')
 DR_SIGNATURES, DR_DEFINES = _read_header(DR_HEADER_PATH)
 DR_MAX_BATCH, DR_MAX_STEPS = DR_DEFINES['DR_MAX_BATCH'], DR_DEFINES['DR_MAX_STEPS']
+SEGMENT_RANK_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_segment_rank.h')
+SEGMENT_RANK_SIGNATURES, SEGMENT_RANK_DEFINES = _read_header(SEGMENT_RANK_HEADER_PATH)
 CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 # (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
 EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
@@ -141,7 +144,8 @@ EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_H
                  (TRUTH_RANK_SCORED_HEADER_PATH, 'TRUTH_RANK_SCORED_SIGNATURES', 'TRUTH_RANK_SCORED_DEFINES'),
                  (CATALOG_HEADER_PATH, 'CATALOG_SIGNATURES', 'CATALOG_DEFINES'),
                  (RANK_STATS_HEADER_PATH, 'RANK_STATS_SIGNATURES', 'RANK_STATS_DEFINES'),
-                 (BPR_HEADER_PATH, 'BPR_SIGNATURES', 'BPR_DEFINES'), (DR_HEADER_PATH, 'DR_SIGNATURES', 'DR_DEFINES'))
+                 (BPR_HEADER_PATH, 'BPR_SIGNATURES', 'BPR_DEFINES'), (DR_HEADER_PATH, 'DR_SIGNATURES', 'DR_DEFINES'),
+                 (SEGMENT_RANK_HEADER_PATH, 'SEGMENT_RANK_SIGNATURES', 'SEGMENT_RANK_DEFINES'))
 
 _lib = None
 

@@ -23,6 +23,9 @@ integers counted on the device next to the same ranking.
 ``ImplicitWeightedRankTestManager`` evaluates the same exact ranks under per-entry weights (inverse propensities: the
 self-normalised estimators on a biased test split) and user groups, with bootstrap intervals over users drawn on the device
 (``csrc/invpref_rank_stats.hip``); ``paired_bootstrap`` compares two of them under the same draws.
+``ExplicitRankTestManager`` adds the ranking metrics of explicit feedback to ``ExplicitTestManager``'s errors: the AUC over all
+test pairs and, per user among that user's test ratings, gAUC, NDCG / recall / precision at any k, MRR and MAP
+(``csrc/invpref_segment_rank.hip``).
 """
 from __future__ import annotations
 
@@ -697,3 +700,91 @@ class ExplicitTestManager:
 
     def evaluate(self) -> dict:
         return self.evaluate_async().result()
+
+
+class ExplicitRankTestManager(ExplicitTestManager):
+    """Ranking metrics on explicit test ratings, next to the errors of ``ExplicitTestManager``: the global AUC over all test
+    pairs and, per user among the items that user rated in the test set, gAUC, NDCG / recall / precision at any k, MRR and MAP
+    (``csrc/invpref_segment_rank.hip``; the metric formulas are include/invpref_truth_rank.h's).  A test entry is positive
+    where its score is >= ``positive_threshold``; gains are binary.  Works with every explicit model that offers
+    ``predict(users, items)``.  -> {'mse', 'rmse', 'mae', 'auc', 'gauc', 'ndcg': {k: ..}, 'recall': {..}, 'precision': {..},
+    'mrr', 'map', 'users': {'ranked': .., 'gauc': ..}}: 'auc' is NaN where a class is empty; the per-user figures are means
+    over the users with at least one positive ('ranked'), 'gauc' over those that also have a negative ('gauc'); a mean over
+    no user is NaN.  ``ranks()`` gives the integers ``ops.rank_metrics_weighted`` and ``ops.bootstrap_sums`` take."""
+
+    def __init__(self, model, data_loader, top_k_list: list, positive_threshold: float):
+        super().__init__(model, data_loader)
+        ks = [int(k) for k in top_k_list]
+        if any(k < 1 for k in ks) or ks != sorted(ks) or len(ks) > 63:
+            raise ValueError(f'top_k_list {list(top_k_list)}: at most 63 ascending values of k >= 1')
+        self.top_k_list = ks
+        self.positive_threshold = float(positive_threshold)
+
+    def _grouped(self, device) -> dict:
+        """The test pairs grouped by user (a stable sort: a user's entries keep the loader's order) and what the ranks need,
+        built once on the host and kept until the loader's tensors are replaced or written in place (identity + _version)"""
+        pairs, scores = self.data_loader.all_test_pairs_tensor, self.data_loader.all_test_scores_tensor
+        c = getattr(self, '_rank_cache', None)
+        if c is None or c[0] is not pairs or c[1] is not scores or c[2] != (pairs._version, scores._version, device):
+            p = pairs.cpu().numpy().reshape(-1, 2)
+            order = np.argsort(p[:, 0], kind='stable')
+            users, items = p[order, 0].astype(np.int64), p[order, 1].astype(np.int64)
+            target = scores.cpu().float().numpy().reshape(-1)[order]
+            n = len(users)
+            if n >= 1 << 31:
+                raise ValueError(f'{n} test pairs: segment positions are int32')
+            starts = np.flatnonzero(np.r_[True, users[1:] != users[:-1]]) if n else np.zeros(0, np.int64)
+            seg_ptr = np.r_[starts, n].astype(np.int32)
+            labels = (target >= np.float32(self.positive_threshold)).astype(np.uint8)
+            seg_len = np.diff(seg_ptr)
+            n_pos = np.add.reduceat(labels.astype(np.int64), starts) if n else np.zeros(0, np.int64)
+            truth_ptr = np.r_[0, np.cumsum(n_pos)].astype(np.int32)
+            n_neg = (seg_len - n_pos).astype(np.int32)
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+            g = dict(users=dev(users), items=dev(items), target=dev(target), seg_ptr=dev(seg_ptr), labels=dev(labels),
+                     entries=dev(np.flatnonzero(labels).astype(np.int32)), truth_ptr=dev(truth_ptr), n_neg=dev(n_neg),
+                     max_seg_len=int(seg_len.max(initial=0)), n=n, ranked=int((n_pos > 0).sum()),
+                     gauc=int(((n_pos > 0) & (n_neg > 0)).sum()))
+            self._rank_cache = c = (pairs, scores, (pairs._version, scores._version, device), g)
+        return c[3]
+
+    def _ranks(self, g, pred):
+        from . import ops
+        return ops.segment_ranks(pred, g['seg_ptr'], g['entries'], g['max_seg_len'])
+
+    def ranks(self):
+        """(ranks int32 [n_positive], truth_ptr int32 [n_users + 1], n_neg int32 [n_users]) on the device: the place of every
+        positive test entry among its user's test entries, users in ascending id order -- what ops.rank_metrics_from_ranks,
+        ops.rank_metrics_weighted and ops.bootstrap_sums take"""
+        self.model.eval()
+        g = self._grouped(next(self.model.parameters()).device)
+        pred = self.model.predict(g['users'], g['items']).float().contiguous()
+        return self._ranks(g, pred), g['truth_ptr'], g['n_neg']
+
+    def evaluate_async(self) -> PendingEvaluation:
+        """Enqueues the prediction on the grouped pairs, the error sums, the segment ranks, the metric sums and the AUC pair
+        counts; every figure lands in one float64 buffer (the three pair counts bit for bit, as int64), read back once"""
+        from . import ops
+        self.model.eval()
+        device = next(self.model.parameters()).device
+        g = self._grouped(device)
+        pred = self.model.predict(g['users'], g['items']).float().contiguous()
+        err = torch.empty(2, dtype=torch.float64, device=device)
+        call('invpref_eval_error_sums_hip', ptr(pred), ptr(g['target']), pred.numel(), ptr(err), stream_ptr())
+        sums = ops.rank_metrics_from_ranks(self._ranks(g, pred), g['truth_ptr'], g['n_neg'], self.top_k_list)
+        pair = ops.auc_pairs(pred, g['labels'])
+        out = torch.cat([err, sums.reshape(-1), pair.view(torch.float64)])
+        ks, n, ranked, gauc = list(self.top_k_list), float(g['n']), g['ranked'], g['gauc']
+
+        def finish(host: torch.Tensor) -> dict:
+            s2, s1 = host[:2].tolist()
+            m = host[2:-3].numpy().reshape(3, len(ks) + 1)
+            C, P, Nn = host[-3:].view(torch.int64).tolist()
+            mean = lambda x, d: float(x) / d if d else float('nan')  # noqa: E731
+            res = {'mse': s2 / n, 'rmse': float(np.sqrt(s2 / n)), 'mae': s1 / n,
+                   'auc': C / (2 * P * Nn) if P and Nn else float('nan'), 'gauc': mean(m[0][-1], gauc)}
+            for row, name in ((2, 'ndcg'), (0, 'recall'), (1, 'precision')):
+                res[name] = {k: mean(m[row][i], ranked) for i, k in enumerate(ks)}
+            res.update(mrr=mean(m[1][-1], ranked), map=mean(m[2][-1], ranked), users={'ranked': ranked, 'gauc': gauc})
+            return res
+        return PendingEvaluation(out, finish)

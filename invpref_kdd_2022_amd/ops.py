@@ -25,6 +25,7 @@ from . import torch_ops_catalog  # noqa: F401  (the catalogue metrics' fragment:
 from . import torch_ops_rank_stats  # noqa: F401  (weighted / grouped rank metrics and bootstrap sums: their fragment)
 from . import torch_ops_bpr  # noqa: F401  (BPR-MF's fragment: torch.ops.invpref.bpr_draw, bpr_grad_)
 from . import torch_ops_dr  # noqa: F401  (doubly robust MF's fragment: torch.ops.invpref.dr_draw, dr_grad_)
+from . import torch_ops_segment_rank  # noqa: F401  (explicit evaluation's ranks: torch.ops.invpref.segment_ranks, auc_pairs)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -555,6 +556,27 @@ def bootstrap_sums(vals: torch.Tensor, n_boot: int, seed: int = 0) -> torch.Tens
     if not -(1 << 63) <= seed < 1 << 64:
         raise InvPrefError(f'seed {seed} has more than 64 bits')
     return _o().bootstrap_sums(vals, int(n_boot), seed - (1 << 64) if seed >= 1 << 63 else seed)
+
+
+def segment_ranks(values: torch.Tensor, seg_ptr: torch.Tensor, entries: Optional[torch.Tensor] = None,
+                  max_seg_len: int = 0) -> torch.Tensor:
+    """int32 [n_entries] on the device: the 0-based place of every wanted position among the values of its own segment
+    (include/invpref_segment_rank.h): values fp32 [n]; seg_ptr int32 [n_seg + 1], non-decreasing in [0, n], segment s the
+    positions [seg_ptr[s], seg_ptr[s + 1]); entries int32, ascending, the wanted positions, None for every position.  The
+    order is value descending (-0 equals +0, a NaN below every number), position ascending among equal values; a position
+    that no segment covers gets -1.  max_seg_len is a speed hint (0: unknown) and never changes a result.  With the
+    positives of every segment as entries these are the ranks rank_metrics_from_ranks, rank_metrics_weighted and
+    bootstrap_sums take."""
+    _gpu(values, seg_ptr, entries)
+    return _o().segment_ranks(values, seg_ptr, entries, int(max_seg_len))
+
+
+def auc_pairs(values: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """int64 [3] = {C, P, Nn} on the device: labels uint8 [n], 1 positive, 0 negative, anything else left out; P and Nn the
+    class counts, C = sum over the positives of 2 #{negatives with a lower value} + #{negatives with an equal value}, exact
+    integers.  AUC = C / (2 P Nn): the Mann-Whitney statistic with midranks for ties.  The pair count is quadratic in n."""
+    _gpu(values, labels)
+    return _o().auc_pairs(values, labels)
 
 
 def bootstrap_intervals(sums, covered_col: int, confidence: float = 0.95):
