@@ -12,6 +12,8 @@ _BPR = ('BPRTrainManager',)
 
 _DR = ('DRMatrixFactorization', 'DRExplicitMatrixFactorization', 'DRTrainManager', 'DRExplicitTrainManager')
 
+_ALS = ('ALSTrainManager',)
+
 _EVALUATE = ('ExplicitRankTestManager',)
 
 
@@ -19,7 +21,8 @@ def __getattr__(name):   # resolved on first use: importing the package loads ne
     if name in _EVALUATE:
         from . import evaluate
         return getattr(evaluate, name)
-    if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE or name in _BPR or name in _DR:
+    if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE or name in _BPR or name in _DR \
+            or name in _ALS:
         from . import baseline
         return getattr(baseline, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -1704,3 +1704,201 @@ class DRTrainManager(_DRManagerMixin, BasicImplicitTrainManager):
 
 class DRExplicitTrainManager(_DRManagerMixin, BasicExplicitTrainManager):
     """doubly robust MF on explicit feedback (form 1: squared error) over a DRExplicitMatrixFactorization"""
+
+
+ALS_LOSS_KEYS = ['fit_loss', 'L2_reg', 'loss']
+
+
+class ALSTrainManager:
+    """Weighted matrix factorization solved as Hu, Koren and Volinsky (ICDM 2008) solve it: alternating least squares on a
+    plain PureMatrixFactorization (include/invpref_als.h states the model).  Row e of training_data is the entry (user, item,
+    label): preference p_e = 1 if label > 0 else 0 (a listed 0 is an observed negative), confidence c_e = 1 + alpha * w_e with w_e the label or the caller's `weights` (one value per
+    row, >= 0); every other user x item pair carries confidence 1 and preference 0, and a row listed twice counts twice.  One
+    sweep solves every user row exactly against the item table, then every item row against the new user table
+    (ops.als_gram / ops.als_solve: float64 normal equations and Cholesky, one rounding to fp32), then evaluates
+        loss = fit_loss + reg * L2_reg      L2_reg = |X|^2 + |Y|^2
+    with ops.als_objective.  No learning rate, no negative sampling, no minibatches: not an epoch-engine manager (no row plans,
+    no Adam); an "epoch" is a sweep.  Single process.
+
+    The tables are the model's own parameters, written in place.  Negative weights, non-finite tables and ids outside the
+    tables are refused at construction, on the host; the device's sticky error word (a failed pivot: a NaN that reached a
+    table) is checked at every read-back and raises InvPrefError.
+
+    Fold-in: `fold_in(item_lists)` solves users that were not in training against the trained item table, e.g.
+        rows = mgr.fold_in([[3, 17, 4], [8]])                                     # fp32 [2, D]
+        items, scores = ops.recommend(rows, model.item_emb.weight, torch.arange(2, device=rows.device), k=10)
+    """
+
+    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, epochs: int, evaluate_interval: int,
+                 reg: float, alpha: float, *, weights=None, test_begin_epoch: int = 0):
+        if not isinstance(model, PureMatrixFactorization):
+            raise TypeError('ALSTrainManager takes a PureMatrixFactorization')
+        if model.factor_num > _capi.ALS_MAX_FACTORS:
+            raise _capi.InvPrefError(f'factor_num {model.factor_num}: the ALS solve takes at most {_capi.ALS_MAX_FACTORS} factors')
+        if not reg > 0:
+            raise ValueError('reg must be > 0: it is what keeps every normal matrix positive definite')
+        data = torch.as_tensor(training_data).detach().cpu()
+        if data.dim() != 2 or data.shape[1] < 3 or data.shape[0] < 1:
+            raise ValueError('training_data holds rows of (user, item, label)')
+        users, items, label = data[:, 0].to(torch.int64), data[:, 1].to(torch.int64), data[:, 2].to(torch.float32)
+        w = label if weights is None else torch.as_tensor(weights).detach().cpu().reshape(-1).to(torch.float32)
+        if w.numel() != data.shape[0]:
+            raise ValueError(f'weights holds {w.numel()} values for {data.shape[0]} rows')
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError('weights (the labels by default) must be finite and >= 0: a confidence below 1 can lose positive '
+                             'definiteness')
+        for t in model.tables():
+            if not bool(torch.isfinite(t.detach()).all()):
+                raise ValueError('the model\'s tables hold non-finite values')
+        self.model, self.evaluator, self.device = model.to(device), evaluator, torch.device(device)
+        self.epochs, self.evaluate_interval, self.test_begin_epoch = int(epochs), int(evaluate_interval), int(test_begin_epoch)
+        self.reg, self.alpha = float(reg), float(alpha)
+        self.epoch_cnt, self.n_total = 0, int(data.shape[0])
+        dev = self.device
+        conf = 1.0 + self.alpha * w
+        pref = (label > 0).to(torch.float32)
+        self.by_user, self.by_item = ops.als_csr(users.to(dev), items.to(dev), pref.to(dev), conf.to(dev), model.user_num,
+                                                 model.item_num)
+        D = model.factor_num
+        self._gram = torch.zeros(D, D, dtype=torch.float64, device=dev)
+        self.n_skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.error_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._ws = ops.Workspace(dev)
+        if dev.type == 'cuda':      # sized once: every later launch is capturable
+            U, I, n = model.user_num, model.item_num, self.n_total
+            self._ws.get(max(ops.als_workspace_bytes(U, I, n, D), ops.als_workspace_bytes(I, U, n, D), 16))
+
+    def _tables(self):
+        return self.model.user_emb.weight.detach(), self.model.item_emb.weight.detach()
+
+    # ---- the launches; nothing here reads back
+    def train_user_half(self) -> None:
+        """every user row against the item table as it is"""
+        X, Y = self._tables()
+        ops.als_gram(Y, self.reg, out=self._gram, workspace=self._ws)
+        ops.als_solve(Y, self._gram, self.by_user, X, n_skipped=self.n_skipped, error_word=self.error_word, workspace=self._ws)
+
+    def train_item_half(self) -> None:
+        X, Y = self._tables()
+        ops.als_gram(X, self.reg, out=self._gram, workspace=self._ws)
+        ops.als_solve(X, self._gram, self.by_item, Y, n_skipped=self.n_skipped, error_word=self.error_word, workspace=self._ws)
+
+    def objective_into(self, out3: torch.Tensor) -> torch.Tensor:
+        """float64 (fit_loss, L2_reg, loss) of the tables as they are, into out3 on the device"""
+        X, Y = self._tables()
+        ops.als_gram(Y, self.reg, out=self._gram, workspace=self._ws)
+        return ops.als_objective(X, Y, self._gram, self.reg, self.by_user, out=out3, workspace=self._ws)
+
+    def enqueue_sweep(self, out3: torch.Tensor) -> None:
+        """one sweep -- user half, item half, objective -- enqueued on the current stream (capturable)"""
+        self.train_user_half()
+        self.train_item_half()
+        self.objective_into(out3)
+
+    # ---- read-backs
+    def read_back(self, dev_losses: torch.Tensor) -> list:
+        """the loss dicts of a [n, 3] device tensor, after the check of the sticky error word"""
+        self.check_error()
+        return self.loss_dicts(dev_losses)
+
+    def check_error(self) -> None:
+        word = int(self.error_word.item())
+        if word:
+            raise _capi.InvPrefError(f'ALS: a row\'s normal matrix was not positive definite or its solution not finite (error word '
+                                     f'{word}): a NaN reached a table, or a confidence was below 1; the affected rows are NaN')
+
+    @staticmethod
+    def loss_dicts(dev_losses: torch.Tensor) -> list:
+        return [dict(zip(ALS_LOSS_KEYS, v)) for v in dev_losses.reshape(-1, 3).tolist()]
+
+    def objective(self) -> dict:
+        out = self.objective_into(torch.empty(3, dtype=torch.float64, device=self.device))
+        return self.read_back(out)[0]
+
+    def train_a_sweep(self) -> dict:
+        return self.train_epochs(1)[0]
+
+    train_a_epoch = train_a_sweep
+
+    def train_epochs(self, n: int, sync: bool = True):
+        """n sweeps enqueued back to back.  sync: ONE read-back -> the n loss dicts; otherwise the float64 [n, 3] device tensor
+        (read it with read_back)."""
+        losses = torch.empty(max(int(n), 0), 3, dtype=torch.float64, device=self.device)
+        for k in range(int(n)):
+            self.enqueue_sweep(losses[k])
+            self.epoch_cnt += 1
+        return self.read_back(losses) if sync else losses
+
+    def train(self, silent: bool = False, auto: bool = False):
+        """((loss dicts, epochs), (test results, epochs)): the outer loop of the epoch engine's train() -- the epoch-0
+        evaluation first, the sweeps up to the next evaluation enqueued together, nothing read back inside the loop when
+        nothing is printed (an evaluator with evaluate_async is then called through it)."""
+        from .engine import transfer_loss_dict_to_line_str
+        test_result_list, test_epoch_list = [], []
+        loss_result_list, train_epoch_index_list = [], []
+        defer = bool(silent or auto)
+        evaluate = getattr(self.evaluator, 'evaluate_async', None) if defer else None
+        pending = evaluate is not None
+        evaluate = evaluate or self.evaluator.evaluate
+
+        def test():
+            result = evaluate()
+            test_result_list.append(result)
+            test_epoch_list.append(self.epoch_cnt)
+            if not defer:
+                print('test at epoch:', self.epoch_cnt)
+                print(transfer_loss_dict_to_line_str(result))
+        test()
+        while self.epoch_cnt < self.epochs:
+            first = self.epoch_cnt + 1
+            to_event = self.evaluate_interval - self.epoch_cnt % self.evaluate_interval
+            run = self.train_epochs(min(to_event, self.epochs - self.epoch_cnt), sync=not defer)
+            for i in range(len(run)):
+                train_epoch_index_list.append(first + i)
+                loss_result_list.append(run[i])
+                if not defer:
+                    print('train epoch:', first + i)
+                    print(transfer_loss_dict_to_line_str(run[i]))
+            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
+                test()
+        if defer:  # one read-back for everything
+            loss_result_list = self.read_back(torch.stack(loss_result_list)) if loss_result_list else []
+            if pending:
+                test_result_list = [p.result() for p in test_result_list]
+        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
+
+    # ---- fold-in
+    def fold_in(self, item_lists, pref=None, conf=None) -> torch.Tensor:
+        """The vectors of users given by their item lists, solved against the item table as it is and its Gram matrix: the user
+        half-sweep on a batch of arbitrary lists (the row_ids form of the same kernel) -> fp32 [n, D].  pref / conf: per list, one
+        value per item; default preference 1 and confidence 1 + alpha.  A user without items gets zeros."""
+        n = len(item_lists)
+        lens = [len(l) for l in item_lists]
+        total = sum(lens)
+        D, dev = self.model.factor_num, self.device
+        if n < 1 or total < 1:
+            return torch.zeros(n, D, dtype=torch.float32, device=dev)
+
+        def flat(values, default):
+            if values is None:
+                return torch.full((total,), default, dtype=torch.float32)
+            v = torch.cat([torch.as_tensor(x, dtype=torch.float32).reshape(-1) for x in values])
+            if v.numel() != total:
+                raise ValueError('fold_in: pref / conf hold one value per listed item')
+            return v
+        cols = torch.cat([torch.as_tensor(l, dtype=torch.int64).reshape(-1) for l in item_lists])
+        if int(cols.min()) < 0 or int(cols.max()) >= self.model.item_num:
+            raise ValueError('fold_in: an item id lies outside the item table')
+        p, c = flat(pref, 1.0), flat(conf, 1.0 + self.alpha)
+        if bool((c < 1).any()) or not bool(torch.isfinite(c).all() and torch.isfinite(p).all()):
+            raise ValueError('fold_in: confidences must be finite and >= 1, preferences finite')
+        row_ptr = torch.zeros(n + 1, dtype=torch.int64)
+        row_ptr[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
+        csr = (row_ptr.to(dev), cols.to(torch.int32).to(dev), c.to(dev), p.to(dev))
+        _, Y = self._tables()
+        gram = ops.als_gram(Y, self.reg)
+        out = torch.empty(n, D, dtype=torch.float32, device=dev)
+        ops.als_solve(Y, gram, csr, out, row_ids=torch.arange(n, dtype=torch.int32, device=dev), n_skipped=self.n_skipped,
+                      error_word=self.error_word)
+        self.check_error()
+        return out

@@ -25,6 +25,7 @@ from . import torch_ops_catalog  # noqa: F401  (the catalogue metrics' fragment:
 from . import torch_ops_rank_stats  # noqa: F401  (weighted / grouped rank metrics and bootstrap sums: their fragment)
 from . import torch_ops_bpr  # noqa: F401  (BPR-MF's fragment: torch.ops.invpref.bpr_draw, bpr_grad_)
 from . import torch_ops_dr  # noqa: F401  (doubly robust MF's fragment: torch.ops.invpref.dr_draw, dr_grad_)
+from . import torch_ops_als  # noqa: F401  (WMF by alternating least squares: torch.ops.invpref.als_gram, als_solve_, als_objective)
 from . import torch_ops_segment_rank  # noqa: F401  (explicit evaluation's ranks: torch.ops.invpref.segment_ranks, auc_pairs)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
@@ -1169,3 +1170,86 @@ def dr_grad(form, params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor
     ws = (workspace or Workspace(P.device)).get(nbytes)
     _o().dr_grad_(DR_FORMS[form] if isinstance(form, str) else int(form), *params4, users, items, scores, weights, draw_users,
                   draw_items, index, float(L2_coe), float(L1_coe), *grads4, losses5, ws)
+
+
+# ---- WMF by alternating least squares (include/invpref_als.h, csrc/invpref_als.hip)
+def als_workspace_bytes(rows: int, other_rows: int, entries: int, factor_num: int) -> int:
+    """the float64 partials of one half-sweep (pieces of long rows), of the other table's Gram product and of the objective: a
+    function of the sizes alone, non-decreasing in each; 0: not taken (factor_num > 128 included)"""
+    return int(_capi.lib().invpref_als_workspace_bytes(int(rows), int(other_rows), int(entries), int(factor_num)))
+
+
+def _als_ws(op, rows, other_rows, entries, D, device, workspace):
+    nbytes = als_workspace_bytes(rows, other_rows, entries, D)
+    if nbytes == 0:
+        raise InvPrefError(f'{op}: sizes outside the kernels\' range ({rows} x {other_rows} rows, {entries} entries, '
+                           f'factor_num {D}; at most {_capi.ALS_MAX_FACTORS} factors)')
+    return (workspace or Workspace(device)).get(nbytes)
+
+
+def als_gram(table: torch.Tensor, lam: float, out: Optional[torch.Tensor] = None,
+             workspace: Optional[Workspace] = None) -> torch.Tensor:
+    """table^T table + lam I as float64 [D, D] from an fp32 table [n, D]: fixed chunks of rows, float64 partials added in chunk
+    order, no float atomics -- the same bits on every run.  Written into `out` if given (then, with a sized workspace, nothing
+    is allocated: capturable)."""
+    _gpu(table, out)
+    D = table.shape[1]
+    if out is None:
+        out = torch.empty(D, D, dtype=torch.float64, device=table.device)
+    _o().als_gram(table, float(lam), out, _als_ws('als_gram', 1, table.shape[0], 1, D, table.device, workspace))
+    return out
+
+
+def als_solve(other_table: torch.Tensor, gram: torch.Tensor, csr, out: torch.Tensor, row_ids: Optional[torch.Tensor] = None,
+              n_skipped: Optional[torch.Tensor] = None, error_word: Optional[torch.Tensor] = None,
+              workspace: Optional[Workspace] = None):
+    """One half-sweep of alternating least squares (include/invpref_als.h states it): every list of csr = (row_ptr int64
+    [rows + 1], cols int32, conf fp32, pref fp32) is solved exactly against other_table and gram = als_gram(other_table, lam)
+    -- float64 normal equations, Cholesky factor and triangular solves, one rounding to fp32 -- into row r of `out` [rows, D],
+    or into row row_ids[r] (int32) of `out` [any, D].  Without row_ids every row of out is overwritten, a row without entries
+    with zeros.  An entry with a column outside other_table is skipped and counted in n_skipped (int32 [1], ADDED to); a failed
+    pivot or a non-finite result writes the row as NaN and sets bit 0 of error_word (int32 [1], sticky).  Both words are
+    allocated zeroed when absent.  -> (out, n_skipped, error_word).  Bitwise reproducible; no host sync."""
+    row_ptr, cols, conf, pref = csr
+    _gpu(other_table, gram, row_ptr, cols, conf, pref, out, row_ids, n_skipped, error_word)
+    dev = other_table.device
+    if n_skipped is None:
+        n_skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+    if error_word is None:
+        error_word = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _als_ws('als_solve', row_ptr.numel() - 1, other_table.shape[0], cols.numel(), other_table.shape[1], dev, workspace)
+    _o().als_solve_(other_table, gram, row_ptr, cols, conf, pref, row_ids, out, n_skipped, error_word, ws)
+    return out, n_skipped, error_word
+
+
+def als_objective(table: torch.Tensor, other_table: torch.Tensor, gram: torch.Tensor, lam: float, csr,
+                  out: Optional[torch.Tensor] = None, workspace: Optional[Workspace] = None) -> torch.Tensor:
+    """float64 [3] = (fit, reg, J) of the WMF objective (include/invpref_als.h): csr lists the entries by the rows of `table`,
+    gram = als_gram(other_table, lam).  reg = |table|^2 + |other_table|^2, J = fit + lam reg.  Fixed summation order."""
+    row_ptr, cols, conf, pref = csr
+    _gpu(table, other_table, gram, row_ptr, cols, conf, pref, out)
+    if out is None:
+        out = torch.empty(3, dtype=torch.float64, device=table.device)
+    ws = _als_ws('als_objective', table.shape[0], other_table.shape[0], cols.numel(), table.shape[1], table.device, workspace)
+    _o().als_objective(table, other_table, gram, float(lam), row_ptr, cols, conf, pref, out, ws)
+    return out
+
+
+def als_csr(users: torch.Tensor, items: torch.Tensor, pref: torch.Tensor, conf: torch.Tensor, user_num: int, item_num: int):
+    """The two CSRs of a list of entries (users, items: integer ids; pref, conf: per entry), built once on the tensors' device
+    with torch's stable sorts: -> (by_user, by_item), each (row_ptr int64 [rows + 1], cols int32, conf fp32, pref fp32), the
+    entries of a row in their input order.  Ids outside the tables are refused here, on the host."""
+    users, items = users.reshape(-1).to(torch.int64), items.reshape(-1).to(torch.int64)
+    n = users.numel()
+    if n < 1 or items.numel() != n or pref.numel() != n or conf.numel() != n:
+        raise InvPrefError('als_csr: users, items, pref and conf hold one value per entry, at least one entry')
+    if int(users.min()) < 0 or int(users.max()) >= user_num or int(items.min()) < 0 or int(items.max()) >= item_num:
+        raise InvPrefError('als_csr: an id lies outside its table')
+    pref, conf = pref.reshape(-1).to(torch.float32), conf.reshape(-1).to(torch.float32)
+
+    def one(rows, cols, n_rows):
+        order = torch.sort(rows, stable=True)[1]
+        row_ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
+        row_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), 0)
+        return row_ptr, cols[order].to(torch.int32).contiguous(), conf[order].contiguous(), pref[order].contiguous()
+    return one(users, items, int(user_num)), one(items, users, int(item_num))
