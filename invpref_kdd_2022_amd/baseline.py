@@ -504,44 +504,84 @@ class ExpoMFTrainManager(BasicImplicitTrainManager):
 
 
 # ------------------------------------------------------------------------------------------------ drawn terms
-class _DrawnTermMixin:
-    """A PureMF step with one further loss term over ids DRAWN per step on the host (the WMF and CVIB managers below), in
-    front of a _BasicTrainManager.  The step is the engine's unfused sequence with one call between the gradient pass and
-    Adam: planned PureMF gradient pass -> the term (adds into the same gradient buffer and into the step's `loss`) -> dense /
-    ranged Adam.  Single process.
-
-    A draw is a pair of id arrays (one array under _ONE_ARRAY).  The minibatches are static, so what every step draws from is listed once (_draw_specs);
-    before a run of epochs is enqueued every step's draw is made on the host in the reference's order and the run's draws go
-    to the device in one stream-ordered copy into ONE int32 buffer, row = the step's position in the run.  The launches read
-    their row when they run, so a captured run of epochs is replayed with new draws without re-capture.
-
-    The draw source replaces numpy's global generator: a callable taking _draw_default's arguments, called once per step in
-    order, or an iterable of pairs consumed in that order (recorded draws).
-
-    A manager supplies: _SINGLE and _WHAT (the error texts), _draw_default, _draw_specs, _row_layout, _term(), and, where the
-    staged rows need a pass of their own on the device, _limit_run() / _staging_resized() / _after_staging()."""
+class _SingleProcessMixin:
     _SINGLE = None                  # why the manager runs in a single process
-    _WHAT = None                    # what a draw is called in the size check's error
-    _draw_default = None            # staticmethod: one step's draw from numpy's global generator
-    _ONE_ARRAY = False              # a draw is ONE id array (the pair's second stays empty: lengths (n, 0))
-    _lazy_adam_unsupported = 'the drawn term adds gradient to rows outside the minibatch, which lazy Adam would not update'
 
     def _require_single_process(self, world_size) -> None:
         """called with the constructor's argument before the engine is built, and with the resolved size after"""
         if world_size is not None and int(world_size) > 1:
             raise NotImplementedError(self._SINGLE)
 
+
+class _StagedRunMixin(_SingleProcessMixin):
+    """A step that reads ids DRAWN anew for every step, in front of a _BasicTrainManager: always the engine's unfused sequence,
+    gradient pass -> _after_gradient_pass -> dense / ranged Adam.  Single process.  Before a run of epochs is enqueued the
+    draws of all its steps are staged in ONE device int32 buffer, row = the step's position in the run.  The launches read
+    their row when they run, so a captured run of epochs is replayed with new draws without re-capture.
+
+    A layer above supplies _stage_draws(n), the draws of the next n epochs' steps into the first rows, stream-ordered (a copy
+    of host draws: _DrawnTermMixin; a draw launch: _DeviceDrawnMixin), and _draws_consumed(steps), told how many were issued."""
+
+    def _init_staging(self, width: int) -> None:
+        self._require_single_process(self.world_size)
+        self._unfused = True        # (never the fused / alternating step)
+        self._row_width = width
+        self._staged = None         # device int32 [steps of the longest run, width]
+
+    def _limit_run(self) -> None:
+        """may lower self._graph_epochs before the staging buffer is sized for it"""
+
+    def _staging_resized(self, rows: int) -> None:
+        """the staging buffer was (re)allocated with `rows` rows: size what goes with it"""
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        self._limit_run()
+        rows = self._graph_epochs * self.batch_num
+        if self._staged is None or self._staged.shape[0] != rows:
+            self._staged = torch.zeros(rows, self._row_width, dtype=torch.int32, device=self.device)
+            self._staging_resized(rows)
+
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        n = min(want, self._graph_epochs) if (self.graphs_enabled() and self._graph_warm) else 1
+        self._stage_draws(n)
+        before = self.epoch_cnt
+        out = super()._enqueue_epochs(want)
+        self._draws_consumed((self.epoch_cnt - before) * self.batch_num)   # (a failed capture runs one eager epoch of the n)
+        return out
+
+    def prepare_graphs(self, run_lengths) -> None:
+        if self._staged is None:
+            raise RuntimeError('prepare_graphs(): run one epoch first (train_epochs(1))')
+        super().prepare_graphs(run_lengths)
+
+
+class _DrawnTermMixin(_StagedRunMixin):
+    """A PureMF step with one further loss term over ids drawn per step on the HOST (the WMF, fairness and CVIB managers
+    below): the staged step of _StagedRunMixin with one call between the gradient pass and Adam, planned PureMF gradient pass
+    -> the term (adds into the same gradient buffer and into the step's `loss`) -> Adam.
+
+    A draw is a pair of id arrays (one array under _ONE_ARRAY).  The minibatches are static, so what every step draws from is
+    listed once (_draw_specs); a run's draws are made on the host in the reference's order and go to the device in one copy.
+    The draw source replaces numpy's global generator: a callable taking _draw_default's arguments, called once per step in
+    order, or an iterable of pairs consumed in that order (recorded draws).
+
+    A manager supplies: _SINGLE and _WHAT (the error texts), _draw_default, _draw_specs, _row_layout, _term(), and, where the
+    staged rows need a pass of their own on the device, _after_staging()."""
+    _WHAT = None                    # what a draw is called in the size check's error
+    _draw_default = None            # staticmethod: one step's draw from numpy's global generator
+    _ONE_ARRAY = False              # a draw is ONE id array (the pair's second stays empty: lengths (n, 0))
+    _lazy_adam_unsupported = 'the drawn term adds gradient to rows outside the minibatch, which lazy Adam would not update'
+
     def _init_draws(self, source, specs, second_at: int, width: int) -> None:
         """source: the constructor's keyword; specs: per static minibatch (the arguments of its draw, the lengths (first,
         second) a draw of it must have); second_at / width: a staging row holds the first array from 0 and the second from
         second_at, zero-padded to width"""
-        self._require_single_process(self.world_size)
-        self._unfused = True        # always gradient pass -> _after_gradient_pass -> Adam (never the fused / alternating step)
+        self._init_staging(width)
         self._draw_source = source
         self._draw_iter = iter(source) if source is not None and not callable(source) else None
         self._draw_specs, self._row_layout = specs, (second_at, width)
         self._queue = []            # drawn, not yet consumed: whole epochs of pairs in step order
-        self._staged = None         # device int32 [steps of the longest run, width]
 
     def _draw(self, args, want):
         if self._draw_source is None:
@@ -558,22 +598,8 @@ class _DrawnTermMixin:
             raise ValueError(f'a {self._WHAT} of {len(a)} and {len(b)} ids where the step takes {want[0]} and {want[1]}')
         return a.astype(np.int32), b.astype(np.int32)
 
-    def _limit_run(self) -> None:
-        """may lower self._graph_epochs before the staging buffer is sized for it"""
-
-    def _staging_resized(self, rows: int) -> None:
-        """the staging buffer was (re)allocated with `rows` rows: size what goes with it"""
-
     def _after_staging(self, steps: int) -> None:
         """enqueued behind the copy of a run's first `steps` rows"""
-
-    def _raw_setup(self):
-        super()._raw_setup()
-        self._limit_run()
-        rows = self._graph_epochs * self.batch_num
-        if self._staged is None or self._staged.shape[0] != rows:
-            self._staged = torch.zeros(rows, self._row_layout[1], dtype=torch.int32, device=self.device)
-            self._staging_resized(rows)
 
     def _stage_draws(self, n: int):
         """the draws of the next n epochs: made (those not yet made), laid out one row per step, one copy"""
@@ -592,18 +618,8 @@ class _DrawnTermMixin:
         self._staged[:steps].copy_(src, non_blocking=True)
         self._after_staging(steps)
 
-    def _enqueue_epochs(self, want: int) -> torch.Tensor:
-        n = min(want, self._graph_epochs) if (self.graphs_enabled() and self._graph_warm) else 1
-        self._stage_draws(n)
-        before = self.epoch_cnt
-        out = super()._enqueue_epochs(want)
-        del self._queue[:(self.epoch_cnt - before) * self.batch_num]   # (a failed capture runs one eager epoch of the n)
-        return out
-
-    def prepare_graphs(self, run_lengths) -> None:
-        if self._staged is None:
-            raise RuntimeError('prepare_graphs(): run one epoch first (train_epochs(1))')
-        super().prepare_graphs(run_lengths)
+    def _draws_consumed(self, steps: int) -> None:
+        del self._queue[:steps]
 
     def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
         self._term(k, self._loss_slot * self.batch_num + k, losses6[5:6])
@@ -613,8 +629,59 @@ class _DrawnTermMixin:
         raise NotImplementedError
 
 
+class _RunIndexMixin(_StagedRunMixin):
+    """A run's drawn PAIRS and their inverted index on the device, for the passes built on csrc/chunk_walk.hpp (CVIB, BPR,
+    doubly robust MF): a step takes as many drawn pairs as its minibatch has rows.  A staging row is the pair's two id arrays
+    of `_cap` entries each, the longest minibatch's rows: `_draws` views the buffer as [rows, 2, _cap].  Behind the staging of
+    a run's draws _index_run() indexes them in ONE batched pass (ops.cvib_index: destination row -> positions of the
+    minibatch's pairs and the drawn pairs together) into `_index`, [rows, 2, 2 _cap, 2]; `_step_lo` / `_step_n` say which rows
+    of the training data a step's minibatch is.  The captured launches read their row of both buffers when they run.
+
+    A manager supplies _workspace_bytes(batch), the ops.*_workspace_bytes of its pass over a minibatch of `batch` rows."""
+    # bytes of the run's index: longer runs are replayed as several shorter graphs.  Building it takes four to five times as
+    # much for a moment (keys, sorted keys, the sort's permutation and temporaries: ops.cvib_index), freed before the run starts
+    _INDEX_BUDGET = 512 << 20
+
+    def _init_run_index(self) -> None:
+        n, bs = self.n_total, self.batch_size
+        self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]
+        self._cap = max(self._batch_lens)
+        self._draws = self._index = None
+        self._ws = ops.Workspace(self.device)
+        self._ws.get(max(self._workspace_bytes(self._cap), 16))   # sized once: capturable launches
+
+    def _limit_run(self) -> None:
+        per_epoch = self.batch_num * self._cap * 32          # int32 (row, position) x two sides x 2 B entries per step
+        self._graph_epochs = max(1, min(self._graph_epochs, self._INDEX_BUDGET // per_epoch))
+
+    def _staging_resized(self, rows: int) -> None:
+        dev = self.device
+        self._draws = self._staged.view(rows, 2, self._cap)
+        self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
+        lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
+        self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
+        self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
+
+    def _index_run(self, steps: int) -> None:
+        """the index of a run's first `steps` steps from their staged draws"""
+        ops.cvib_index(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._draws[:steps],
+                       self.model.user_num, self.model.item_num, out=self._index[:steps])
+
+
 # ------------------------------------------------------------------------------------------------ own gradient passes
-class _OwnPassMixin:
+class _WholePassMixin(_SingleProcessMixin):
+    """What the managers share whose gradient pass is ONE ops.*_grad call that is the whole step's loss (_OwnPassMixin,
+    _DeviceDrawnMixin): the pass writes the reported loss terms, named by _LOSS_KEYS, into the first slots of the step's
+    losses, and the engine's row-plan scratch is sized for the first two tables of the flat state."""
+    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))
+    _LOSS_KEYS = PURE_LOSS_KEYS     # (train.py:399-404)
+
+    @classmethod
+    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
+        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.tolist()]
+
+
+class _OwnPassMixin(_WholePassMixin):
     """A step whose gradient pass is the model's own (the MACR, LinearTrans-MF and CausE managers below), in front of a
     _BasicTrainManager.  Always the engine's unfused sequence: the own pass (one ops.*_grad call: every row of every gradient
     overwritten, the reported loss terms written into the first slots of the step's losses) -> the dense / ranged Adam over
@@ -624,10 +691,6 @@ class _OwnPassMixin:
 
     A manager supplies: _SINGLE (the refusal's text), _LOSS_KEYS, _workspace_bytes(), _own_pass(), and, where a caller's
     minibatch can be one the step must refuse, _check_caller_batch()."""
-    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
-    _SINGLE = None                  # why the manager runs in a single process
-    _LOSS_KEYS = PURE_LOSS_KEYS     # what the pass writes into the first slots of a step's losses (train.py:399-404)
-    _require_single_process = _DrawnTermMixin._require_single_process
     _lazy_adam_unsupported = "the model's own gradient pass stores zeros to every idle row: its cost follows the tables"
 
     def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
@@ -669,10 +732,6 @@ class _OwnPassMixin:
             index = self._index[k]
         self._own_pass(users, items, scores, index, losses6)
 
-    @classmethod
-    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
-        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.tolist()]
-
     def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
         """train.py:379-405 / baseline_train.py:674-722 on caller tensors: this minibatch's index is built here, then one
         step."""
@@ -685,6 +744,74 @@ class _OwnPassMixin:
             return self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
         finally:
             self._caller = None
+
+
+class _DeviceDrawnMixin(_RunIndexMixin, _WholePassMixin):
+    """A step whose gradient pass is the model's own over the minibatch's rows and as many pairs drawn per step ON THE DEVICE
+    (the BPR and doubly robust managers below), in front of a _BasicTrainManager.  Always the engine's unfused sequence: the
+    pass (one ops.*_grad call: every row of every gradient overwritten) -> dense / ranged Adam; the pass is the whole step,
+    so nothing stands between them (the engine's _after_gradient_pass as it is).
+
+    `seed` names the trajectory and `step_id`, the global step counter, the next step's draws: together they key every draw,
+    so the same seed gives the same bits whatever the run lengths, with graphs or without.  Before a run of epochs is enqueued
+    its steps are named (step_id + 0, 1, ... into `_step_ids`), ONE draw launch fills their staging rows and ONE ops.cvib_index
+    pass indexes them (_RunIndexMixin); step_id moves on by the steps actually issued.  A caller's minibatch
+    (train_a_batch) is one step under the next step id.
+
+    A manager supplies: _SINGLE, _LOSS_KEYS, _workspace_bytes(),
+      _draw_run(steps)   the draw launch: the staging rows of a run's first `steps` steps, named _step_ids[:steps]
+      _own_pass(users, items, scores, draws, index, weights, losses6)   the ops.*_grad call: the gradient of one step into
+                         state.g_views, its loss terms into losses6's first slots; draws: the step's staging row as [2, B] (a
+                         caller's step: what train_a_batch handed to _caller_step)
+      _row_weights()     one fp32 weight per training row on the device, or None
+    Its constructor validates its arguments and ends with _init_device_draws(); its train_a_batch draws and indexes the
+    caller's step and ends with _caller_step()."""
+
+    def _init_device_draws(self, seed) -> None:
+        self.seed, self.step_id = int(seed), 0
+        self._caller = None         # train_a_batch: (users, items, draws, index, weights) of the caller's minibatch
+        self._init_run_index()
+        self._init_staging(2 * self._cap)
+
+    def _staging_resized(self, rows: int) -> None:
+        super()._staging_resized(rows)
+        self._step_ramp = torch.arange(rows, dtype=torch.int64, device=self.device)
+        self._step_ids = torch.zeros(rows, dtype=torch.int64, device=self.device)
+
+    def _stage_draws(self, n: int) -> None:
+        steps = n * self.batch_num
+        torch.add(self._step_ramp[:steps], self.step_id, out=self._step_ids[:steps])
+        self._draw_run(steps)
+        self._index_run(steps)
+
+    def _draws_consumed(self, steps: int) -> None:
+        self.step_id += steps
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        if k is None:
+            users, items, draws, index, w = self._caller
+        else:
+            b, s = self._raw_batches[k], self._loss_slot * self.batch_num + k
+            draws, index, w = self._draws[s, :, :b.n], self._index[s], self._row_weights()
+            w = None if w is None else w[b.lo:b.lo + b.n]
+        self._own_pass(users, items, scores, draws, index, w, losses6)
+
+    def _step_name(self, B: int):
+        """(step_n, step_id) of a caller's step of B rows, as the draw launches take them"""
+        return (torch.full((1,), B, dtype=torch.int32, device=self.device),
+                torch.full((1,), self.step_id, dtype=torch.int64, device=self.device))
+
+    def _caller_step(self, users, items, scores, draws, index, weights) -> dict:
+        """one step on a caller's minibatch whose draws were made under step_id"""
+        self._ws.get(max(self._workspace_bytes(users.numel()), 16))
+        self._caller = (users, items, draws, index, weights)
+        try:
+            out = self._batch_step(users, items, scores, None, lambda: None)
+        finally:
+            self._caller = None
+        self.step_id += 1
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ WMF
@@ -786,7 +913,7 @@ def cvib_draw_epochs(user_num: int, item_num: int, batch_lens, epochs: int) -> l
     return [cvib_draw(user_num, item_num, n) for _ in range(epochs) for n in batch_lens]
 
 
-class _CVIBMixin(_DrawnTermMixin):
+class _CVIBMixin(_RunIndexMixin, _DrawnTermMixin):
     """CVIBTrainManager / CVIBExplicitTrainManager (baseline_train.py:584-647, :978-1044): the PureMF step plus
     info_coe * info, info = alpha * (-pbar log qbar - (1 - pbar) log(1 - qbar)) + gamma * mean(p log p), p the predictions at
     the minibatch's pairs, qbar the mean prediction at as many uniformly drawn (user, item) pairs (the explicit form clips the
@@ -794,8 +921,7 @@ class _CVIBMixin(_DrawnTermMixin):
 
     The term is torch.ops.invpref.cvib_grad_ (csrc/invpref_cvib.hip: means, fold, scatter, boundary) on the drawn-term step of
     _DrawnTermMixin.  A step's draw: np.random.randint, users then items, B = the minibatch's rows.  Behind the copy of a
-    run's draws they are indexed on the device in one batched pass (ops.cvib_index: destination row -> pair positions of the
-    minibatch and drawn pairs together); the captured launches read their row of both buffers when they run.
+    run's draws they are indexed on the device (_RunIndexMixin).
 
     draws= (keyword-only) is the mixin's draw source: a callable (user_num, item_num, n) -> (ru, rv), or an iterable of
     (ru, rv) pairs."""
@@ -803,44 +929,26 @@ class _CVIBMixin(_DrawnTermMixin):
               'not implemented)'
     _WHAT = 'draw'
     _draw_default = staticmethod(cvib_draw)
-    # bytes of the run's index: longer runs are replayed as several shorter graphs.  Building it takes four to five times as
-    # much for a moment (keys, sorted keys, the sort's permutation and temporaries: ops.cvib_index), freed before the run starts
-    _INDEX_BUDGET = 512 << 20
 
     def _cvib_init(self, alpha, gamma, info_coe, eps, draws):
         # (the engine's `alpha` is what _alpha_for() hands to _coefs(), which a PureMF step never reads: the attribute is CVIB's
         #  here, as in the reference)
         self.alpha, self.gamma, self.info_coe, self.eps = float(alpha), float(gamma), float(info_coe), float(eps)
-        n, bs = self.n_total, self.batch_size
-        self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]
-        self._cap = max(self._batch_lens)
+        self._init_run_index()
         self._init_draws(draws, [((self.model.user_num, self.model.item_num, b), (b, b)) for b in self._batch_lens],
                          self._cap, 2 * self._cap)
-        self._draws = self._index = None
-        self._cvib_ws = ops.Workspace(self.device)
-        self._cvib_ws.get(max(ops.cvib_workspace_bytes(self._cap, self.model.factor_num), 16))   # sized once: capturable launches
 
-    def _limit_run(self) -> None:
-        per_epoch = self.batch_num * self._cap * 32          # int32 (row, position) x two sides x 2 B entries per step
-        self._graph_epochs = max(1, min(self._graph_epochs, self._INDEX_BUDGET // per_epoch))
-
-    def _staging_resized(self, rows: int) -> None:
-        dev = self.device
-        self._draws = self._staged.view(rows, 2, self._cap)
-        self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
-        lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
-        self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
-        self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
+    def _workspace_bytes(self, batch: int) -> int:
+        return ops.cvib_workspace_bytes(batch, self.model.factor_num)
 
     def _after_staging(self, steps: int) -> None:
-        ops.cvib_index(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._draws[:steps],
-                       self.model.user_num, self.model.item_num, out=self._index[:steps])
+        self._index_run(steps)
 
     def _info_term(self, users, items, draw_users, draw_items, index, loss_slot):
         st = self.state
         ops.cvib_grad_(st.p_views[0], st.p_views[1], users, items, draw_users, draw_items, index, self.implicit, self.alpha,
                        self.gamma, self.info_coe, self.eps, st.g_views[0], st.g_views[1], loss_slot, None, None, None,
-                       self._cvib_ws)
+                       self._ws)
 
     def _term(self, k: int, s: int, loss: torch.Tensor) -> None:
         b = self._raw_batches[k]
@@ -854,13 +962,11 @@ class _CVIBMixin(_DrawnTermMixin):
         dev = self.device
         ud = torch.from_numpy(np.ascontiguousarray(u, dtype=np.int64)).to(dev)
         vd = torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64)).to(dev)
-        draws = torch.from_numpy(np.stack([ru, rv])[None]).to(dev)
-        index = ops.cvib_index(ud, vd, torch.zeros(1, dtype=torch.int64, device=dev),
-                               torch.full((1,), len(u), dtype=torch.int32, device=dev), draws, self.model.user_num,
-                               self.model.item_num)
-        self._cvib_ws.get(max(ops.cvib_workspace_bytes(len(u), self.model.factor_num), 16))
+        rud, rvd = torch.from_numpy(np.stack([ru, rv])).to(dev)
+        index = ops.step_index(ud, vd, rud, rvd, self.model.user_num, self.model.item_num)
+        self._ws.get(max(self._workspace_bytes(len(u)), 16))
         return self._batch_step(u, v, batch_scores_tensor, None, lambda: self._info_term(
-            ud, vd, draws[0, 0], draws[0, 1], index[0], self.state.losses6[5:6]))
+            ud, vd, rud, rvd, index, self.state.losses6[5:6]))
 
 
 class CVIBTrainManager(_CVIBMixin, BasicImplicitTrainManager):
@@ -1387,7 +1493,7 @@ class CausEExplicitTrainManager(_CausEManagerMixin, BasicExplicitTrainManager):
 
 
 # ------------------------------------------------------------------------------------------------ BPR-MF
-class BPRTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
+class BPRTrainManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
     """BPR-MF (Rendle et al., UAI 2009) on a plain PureMatrixFactorization: the pairwise ranking loss
         loss = mean_p w_p (-log sigmoid(Pu[u_p] . Qi[i_p] - Pu[u_p] . Qi[j_p])) + L2_coe * L2_reg + L1_coe * L1_reg
     over the training POSITIVES (u_p, i_p), each with a negative j_p drawn per step on the device, uniformly over the items
@@ -1401,13 +1507,9 @@ class BPRTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
     exclude   a CSR (indptr [user_num + 1], indices) of the items never drawn for a user; default: the user's training positives
 
     Rows of training_data with score <= 0 are dropped at construction (`n_dropped`); the static minibatches are taken over the
-    positives in file order.  Always the unfused sequence, ops.bpr_grad (every row of both gradients overwritten) -> dense /
-    ranged Adam.  Before a run of epochs is enqueued ONE ops.bpr_draw launch and ONE ops.cvib_index pass cover all its steps
-    (the staging hooks of _DrawnTermMixin, the device draw standing where the host staging is); the captured launches read
-    their row of both buffers when they run, so a replay follows new draws without re-capture.  Single process."""
+    positives in file order.  The device-drawn step of _DeviceDrawnMixin on ops.bpr_draw and ops.bpr_grad
+    (csrc/invpref_bpr.hip); a staging row holds the step's users, then its negatives.  Single process."""
     _SINGLE = 'BPR runs in a single process (a sharded form would all-reduce the summed gradient of both tables; not implemented)'
-    _LOSS_KEYS = PURE_LOSS_KEYS     # what the pass writes into the first slots of a step's losses
-    _INDEX_BUDGET = _CVIBMixin._INDEX_BUDGET
     _lazy_adam_unsupported = ('the BPR pass stores zeros to every idle row and Adam runs over the whole tables: a lazy form '
                               'would update the rows the step\'s triplets touch (a follow-up)')
 
@@ -1422,7 +1524,6 @@ class BPRTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
         positives = training_data[keep]
         super().__init__(model, evaluator, device, positives, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
-        self.seed, self.step_id = int(seed), 0     # step_id: the global step counter, the name of the next step's draws
         U, I, dev = model.user_num, model.item_num, self.device
         if exclude is None:
             u, i = positives[:, 0].cpu().numpy().astype(np.int64), positives[:, 1].cpu().numpy().astype(np.int64)
@@ -1440,62 +1541,29 @@ class BPRTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
             if w.numel() != self.n_total:
                 raise ValueError(f'weights holds {w.numel()} values for {training_data.shape[0]} rows / {self.n_total} positives')
             self._weights = w.contiguous().to(dev)
-        n, bs = self.n_total, self.batch_size
-        self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]
-        self._cap = max(self._batch_lens)
-        self._init_draws(None, [], self._cap, 2 * self._cap)    # a staging row: the step's users, then its negatives
-        self._draws = self._index = self._caller = None
-        self._bpr_ws = ops.Workspace(dev)
-        self._bpr_ws.get(max(ops.bpr_workspace_bytes(U, I, self._cap, model.factor_num), 16))   # sized once: capturable launches
+        self._init_device_draws(seed)
 
-    _limit_run = _CVIBMixin._limit_run
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model
+        return ops.bpr_workspace_bytes(m.user_num, m.item_num, batch, m.factor_num)
+
+    def _row_weights(self):
+        return self._weights
 
     def _staging_resized(self, rows: int) -> None:
-        dev = self.device
-        self._draws = self._staged.view(rows, 2, self._cap)
-        self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
-        lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
-        self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
-        self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
-        self._step_ramp = torch.arange(rows, dtype=torch.int64, device=dev)
-        self._step_ids = torch.zeros(rows, dtype=torch.int64, device=dev)
-        self.n_forced = torch.zeros(rows, dtype=torch.int32, device=dev)    # per step of the last staged run
+        super()._staging_resized(rows)
+        self.n_forced = torch.zeros(rows, dtype=torch.int32, device=self.device)    # per step of the last staged run
         for k, b in enumerate(self._raw_batches):       # the minibatches are static: a row's users never change
             self._draws[k::self.batch_num, 0, :b.n] = b.users.to(torch.int32)
 
-    def _stage_draws(self, n: int) -> None:
-        """the negatives of the next n epochs' steps in one launch, then their index in one pass"""
-        steps = n * self.batch_num
-        torch.add(self._step_ramp[:steps], self.step_id, out=self._step_ids[:steps])
+    def _draw_run(self, steps: int) -> None:
         ops.bpr_draw(self.users_tensor, self._step_lo[:steps], self._step_n[:steps], self._step_ids[:steps], self._excl,
                      self.model.item_num, self.seed, out=(self._draws[:steps, 1], self.n_forced[:steps]))
-        ops.cvib_index(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._draws[:steps],
-                       self.model.user_num, self.model.item_num, out=self._index[:steps])
 
-    def _enqueue_epochs(self, want: int) -> torch.Tensor:
-        before = self.epoch_cnt
-        out = super()._enqueue_epochs(want)
-        self.step_id += (self.epoch_cnt - before) * self.batch_num   # (a failed capture runs one eager epoch of the staged n)
-        return out
-
-    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
-                       losses6: torch.Tensor, sched=None) -> None:
-        if k is None:
-            users, items, neg, index, w = self._caller
-        else:
-            b, s = self._raw_batches[k], self._loss_slot * self.batch_num + k
-            neg, index = self._draws[s, 1, :b.n], self._index[s]
-            w = None if self._weights is None else self._weights[b.lo:b.lo + b.n]
-        st = self.state
-        ops.bpr_grad(st.p_views[0], st.p_views[1], users, items, neg, index, self.L2_coe, self.L1_coe, st.g_views[0],
-                     st.g_views[1], losses6[:4], weights=w, workspace=self._bpr_ws)
-
-    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
-        """(the pass is the whole step: no further term)"""
-
-    @classmethod
-    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
-        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.tolist()]
+    def _own_pass(self, users, items, scores, draws, index, weights, losses6: torch.Tensor) -> None:
+        st = self.state     # (draws[-1]: the negatives, of a staging row and of a caller's step, which stages them alone)
+        ops.bpr_grad(st.p_views[0], st.p_views[1], users, items, draws[-1], index, self.L2_coe, self.L1_coe, st.g_views[0],
+                     st.g_views[1], losses6[:4], weights=weights, workspace=self._ws)
 
     def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
         """one step on caller tensors: the rows with a score > 0 are the positives (weight 1), their negatives are drawn under
@@ -1507,17 +1575,10 @@ class BPRTrainManager(_DrawnTermMixin, BasicImplicitTrainManager):
         B = ud.numel()
         if B == 0:
             raise ValueError('BPR trains on positives: the minibatch has no row with a score > 0')
-        neg, _ = ops.bpr_draw(ud, torch.zeros(1, dtype=torch.int64, device=dev), torch.full((1,), B, dtype=torch.int32, device=dev),
-                              torch.full((1,), self.step_id, dtype=torch.int64, device=dev), self._excl, m.item_num, self.seed,
-                              batch_cap=B)
-        self._bpr_ws.get(max(ops.bpr_workspace_bytes(m.user_num, m.item_num, B, m.factor_num), 16))
-        self._caller = (ud, vd, neg[0], ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd), None)
-        try:
-            out = self._batch_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), None, lambda: None)
-        finally:
-            self._caller = None
-        self.step_id += 1
-        return out
+        neg, _ = ops.bpr_draw(ud, torch.zeros(1, dtype=torch.int64, device=dev), *self._step_name(B), self._excl, m.item_num,
+                              self.seed, batch_cap=B)
+        index = ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd)
+        return self._caller_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), neg, index, None)
 
 
 # ------------------------------------------------------------------------------------------------ doubly robust MF
@@ -1559,7 +1620,7 @@ class DRExplicitMatrixFactorization(_DRModelMixin, PureExplicitMatrixFactorizati
     implicit = False
 
 
-class _DRManagerMixin(_DrawnTermMixin):
+class _DRManagerMixin(_DeviceDrawnMixin):
     """Doubly robust joint learning (Wang et al., ICML 2019) on a DR*MatrixFactorization: per step, over the B rows of a
     minibatch with inverse propensities w and as many pairs drawn uniformly from the whole user x item grid,
         loss = score_loss + imputation_loss + L2_coe * L2_reg + L1_coe * L1_reg
@@ -1579,15 +1640,11 @@ class _DRManagerMixin(_DrawnTermMixin):
                      interaction counts (smooth_weight_coe their exponent), as the IPS managers form theirs, and kept as
                      inverse_propensity_tensor.  Neither given: every weight is 1.  Both given: ValueError.
 
-    Always the unfused sequence, ops.dr_grad (every row of the four gradients overwritten) -> dense / ranged Adam.  Before a
-    run of epochs is enqueued ONE ops.dr_draw launch and ONE ops.cvib_index pass cover all its steps (the staging hooks of
-    _DrawnTermMixin, the device draw standing where the host staging is); the captured launches read their row of both
-    buffers when they run, so a replay follows new draws without re-capture.  Single process."""
+    The device-drawn step of _DeviceDrawnMixin on ops.dr_draw and ops.dr_grad (csrc/invpref_dr.hip; every row of the four
+    gradients overwritten); a staging row holds the step's drawn users, then its drawn items.  Single process."""
     _SINGLE = ('doubly robust MF runs in a single process (a sharded form would all-reduce the summed gradient of all four '
                'tables; not implemented)')
-    _LOSS_KEYS = DR_LOSS_KEYS       # what the pass writes into the first slots of a step's losses
-    _INDEX_BUDGET = _CVIBMixin._INDEX_BUDGET
-    _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))   # (the engine's row-plan scratch: two tables)
+    _LOSS_KEYS = DR_LOSS_KEYS
     _lazy_adam_unsupported = ('the doubly robust pass stores zeros to every idle row, its drawn pairs reach rows outside the '
                               'minibatch and Adam runs over the whole tables: a lazy form is not built')
 
@@ -1610,7 +1667,6 @@ class _DRManagerMixin(_DrawnTermMixin):
                 raise ValueError(f'weights holds {weights.numel()} values for {training_data.shape[0]} rows')
         super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
-        self.seed, self.step_id = int(seed), 0     # step_id: the global step counter, the name of the next step's draws
         self.smooth_weight_coe, self.propensity_func = smooth_weight_coe, propensity_func
         U, I, dev = model.user_num, model.item_num, self.device
         self.inverse_propensity_tensor = None
@@ -1620,58 +1676,23 @@ class _DRManagerMixin(_DrawnTermMixin):
             cnt = ops.interaction_counts(self.users_tensor, self.items_tensor, U, I)
             self.inverse_propensity_tensor = ops.count_propensity(*cnt, self.users_tensor, self.items_tensor,
                                                                   _COUNT_KINDS[propensity_func], smooth_weight_coe)
-        n, bs = self.n_total, self.batch_size
-        self._batch_lens = [min(bs, n - lo) for lo in range(0, n, bs)]
-        self._cap = max(self._batch_lens)
-        self._init_draws(None, [], self._cap, 2 * self._cap)    # a staging row: the step's drawn users, then its drawn items
-        self._draws = self._index = self._caller = None
-        self._dr_ws = ops.Workspace(dev)
-        self._dr_ws.get(max(ops.dr_workspace_bytes(U, I, self._cap, model.factor_num), 16))   # sized once: capturable launches
+        self._init_device_draws(seed)
 
-    _limit_run = _CVIBMixin._limit_run
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model
+        return ops.dr_workspace_bytes(m.user_num, m.item_num, batch, m.factor_num)
 
-    def _staging_resized(self, rows: int) -> None:
-        dev = self.device
-        self._draws = self._staged.view(rows, 2, self._cap)
-        self._index = torch.zeros(rows, 2, 2 * self._cap, 2, dtype=torch.int32, device=dev)
-        lo = np.arange(self.batch_num, dtype=np.int64) * self.batch_size
-        self._step_lo = torch.from_numpy(np.tile(lo, self._graph_epochs)).to(dev)
-        self._step_n = torch.from_numpy(np.tile(np.asarray(self._batch_lens, np.int32), self._graph_epochs)).to(dev)
-        self._step_ramp = torch.arange(rows, dtype=torch.int64, device=dev)
-        self._step_ids = torch.zeros(rows, dtype=torch.int64, device=dev)
+    def _row_weights(self):
+        return self.inverse_propensity_tensor
 
-    def _stage_draws(self, n: int) -> None:
-        """the drawn pairs of the next n epochs' steps in one launch, then their index in one pass"""
-        steps, m = n * self.batch_num, self.model
-        torch.add(self._step_ramp[:steps], self.step_id, out=self._step_ids[:steps])
+    def _draw_run(self, steps: int) -> None:
+        m = self.model
         ops.dr_draw(self._step_n[:steps], self._step_ids[:steps], m.user_num, m.item_num, self.seed, out=self._draws[:steps])
-        ops.cvib_index(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._draws[:steps],
-                       m.user_num, m.item_num, out=self._index[:steps])
 
-    def _enqueue_epochs(self, want: int) -> torch.Tensor:
-        before = self.epoch_cnt
-        out = super()._enqueue_epochs(want)
-        self.step_id += (self.epoch_cnt - before) * self.batch_num   # (a failed capture runs one eager epoch of the staged n)
-        return out
-
-    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
-                       losses6: torch.Tensor, sched=None) -> None:
-        if k is None:
-            users, items, du, di, index, w = self._caller
-        else:
-            b, s = self._raw_batches[k], self._loss_slot * self.batch_num + k
-            du, di, index = self._draws[s, 0, :b.n], self._draws[s, 1, :b.n], self._index[s]
-            w = None if self.inverse_propensity_tensor is None else self.inverse_propensity_tensor[b.lo:b.lo + b.n]
+    def _own_pass(self, users, items, scores, draws, index, weights, losses6: torch.Tensor) -> None:
         st = self.state
-        ops.dr_grad(0 if self.implicit else 1, st.p_views, st.g_views, users, items, scores, du, di, index, self.L2_coe,
-                    self.L1_coe, losses6[:5], weights=w, workspace=self._dr_ws)
-
-    def _after_gradient_pass(self, k: int, losses6: torch.Tensor) -> None:
-        """(the pass is the whole step: no further term)"""
-
-    @classmethod
-    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
-        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.tolist()]
+        ops.dr_grad(0 if self.implicit else 1, st.p_views, st.g_views, users, items, scores, draws[0], draws[1], index,
+                    self.L2_coe, self.L1_coe, losses6[:5], weights=weights, workspace=self._ws)
 
     def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, weight_tensor=None) -> dict:
         """one step on caller tensors (weight_tensor: the rows' inverse propensities, None: 1): as many pairs as the minibatch
@@ -1685,17 +1706,9 @@ class _DRManagerMixin(_DrawnTermMixin):
         w = None if weight_tensor is None else weight_tensor.detach().to(dev).float().reshape(-1).contiguous()
         if w is not None and w.numel() != B:
             raise ValueError(f'weight_tensor holds {w.numel()} values for {B} rows')
-        draws = ops.dr_draw(torch.full((1,), B, dtype=torch.int32, device=dev),
-                            torch.full((1,), self.step_id, dtype=torch.int64, device=dev), m.user_num, m.item_num, self.seed,
-                            batch_cap=B)
-        self._dr_ws.get(max(ops.dr_workspace_bytes(m.user_num, m.item_num, B, m.factor_num), 16))
-        self._caller = (ud, vd, draws[0, 0], draws[0, 1], ops.dr_index(ud, vd, draws[0, 0], draws[0, 1], m.user_num, m.item_num), w)
-        try:
-            out = self._batch_step(ud, vd, batch_scores_tensor, None, lambda: None)
-        finally:
-            self._caller = None
-        self.step_id += 1
-        return out
+        draws = ops.dr_draw(*self._step_name(B), m.user_num, m.item_num, self.seed, batch_cap=B)[0]
+        index = ops.dr_index(ud, vd, draws[0], draws[1], m.user_num, m.item_num)
+        return self._caller_step(ud, vd, batch_scores_tensor, draws, index, w)
 
 
 class DRTrainManager(_DRManagerMixin, BasicImplicitTrainManager):

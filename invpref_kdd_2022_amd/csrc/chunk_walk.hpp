@@ -1,7 +1,11 @@
 // chunk_walk.hpp -- the chunked scatter and its boundary walk: per-pair gradients summed per destination row, deterministically,
-// for rows no row plan knows.  CVIB's information term (invpref_cvib.hip) and BPR-MF's gradient pass (invpref_bpr.hip) are
-// built on it; each states what is its own in a policy struct (below) and keeps its kernels' names, arguments and launch
-// geometry.  This comment is the one statement of the scheme.
+// for rows no row plan knows.  CVIB's information term (invpref_cvib.hip), BPR-MF's gradient pass (invpref_bpr.hip) and the
+// doubly robust pass (invpref_dr.hip) are built on it; each states what is its own in a policy struct (below) and keeps its
+// kernels' names, arguments and launch geometry.  This comment is the one statement of the scheme.
+//
+// What it offers: the geometry (chunk_of, ChunkGeom, chunk_geom, slot_of), the slot and accumulator helpers, clamp_id, the two
+// kernel bodies chunk_scatter / chunk_boundary, and -- for the passes that carry the L2 / L1 regularisers, BPR's and DR's --
+// norms64, reg_of and RegWalk, the policy base that holds everything of a policy but the entries themselves.
 //
 // The input.  Per side (0: user rows, partner table Qi; 1: item rows, partner table Pu) the step's n2 = 2 B positions come
 // sorted by destination row as (row, position) entries: the inverted index of invpref_cvib_index_hip, `stride` entries per
@@ -250,5 +254,62 @@ __device__ __forceinline__ void chunk_boundary(const int2 *__restrict__ index, i
     for (; cc <= lo; cc++) slot_add<NC>(slot_of(part, nchunk, Dp, side, cc, 0), Dp, l16, sum);
     Policy::template write_row<NC, VEC>(side ? gi : gu, last, D, l16, sum);
 }
+
+// ---- the regularised walk: what the passes with L2_coe * L2_reg + L1_coe * L1_reg in their loss share (BPR, doubly robust)
+// a row's squares and absolute values added to the pairs launch's float64 sums, each lane's chunks in order
+template <int NC>
+__device__ __forceinline__ void norms64(const float4 (&r)[NC], double &sq, double &ab) {
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        sq = sq + (double)r[c].x * (double)r[c].x;
+        sq = sq + (double)r[c].y * (double)r[c].y;
+        sq = sq + (double)r[c].z * (double)r[c].z;
+        sq = sq + (double)r[c].w * (double)r[c].w;
+        ab = ab + fabs((double)r[c].x);
+        ab = ab + fabs((double)r[c].y);
+        ab = ab + fabs((double)r[c].z);
+        ab = ab + fabs((double)r[c].w);
+    }
+}
+// one entry's regulariser gradient: n2 = n * 2 L2_coe / (B D), n1 = n * L1_coe / (B D)
+__device__ __forceinline__ double reg_of(double x, double n2, double n1) {
+    return n2 * x + n1 * (x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0));   // (a NaN entry: n2 * NaN)
+}
+
+// The policy base of such a pass.  The pass's own struct derives from it and adds Entry, load, partner, valid, gathers, factor
+// and the fields they read; gathers() says which of the entries added gather the destination row, and so count for `cnt` below.
+struct RegWalk {
+    using Slot = double;   // a row is rounded to fp32 once however many chunks it spans
+    // entries whose index -> ids -> row chain is in flight together (8 NC + 8 registers per entry next to the 8 NC of the
+    // float64 accumulator: eight entries of 128-float rows took all 256 registers and left one wave per SIMD)
+    template <int NC>
+    static constexpr int ahead() { return NC == 1 ? 8 : 4; }
+    template <int NC>
+    static constexpr int batch() { return 16 / NC; }
+    double r2, r1;   // 2 L2_coe / (B D), L1_coe / (B D)
+
+    // acc += cnt * regulariser gradient of the destination row
+    template <int NC, bool VEC>
+    __device__ __forceinline__ void finish(const float *__restrict__ dtab, int row, int D, int cnt, int l16,
+                                           double4_t (&acc)[NC]) const {
+        float4 d[NC];
+        load_row<NC, VEC>(dtab, row, D, l16, d);
+        const double n2r = (double)cnt * r2, n1r = (double)cnt * r1;
+#pragma unroll
+        for (int k = 0; k < NC; k++) {
+            acc[k].x = acc[k].x + reg_of((double)d[k].x, n2r, n1r);
+            acc[k].y = acc[k].y + reg_of((double)d[k].y, n2r, n1r);
+            acc[k].z = acc[k].z + reg_of((double)d[k].z, n2r, n1r);
+            acc[k].w = acc[k].w + reg_of((double)d[k].w, n2r, n1r);
+        }
+    }
+    // rounded once and stored: the tables are zero-filled in front, the writers never read them
+    template <int NC, bool VEC>
+    static __device__ __forceinline__ void write_row(float *__restrict__ gtab, int row, int D, int l16, const double4_t (&acc)[NC]) {
+        float4 r[NC];
+        round_row<NC>(acc, r);
+        store_row<NC, VEC>(gtab, row, D, l16, r);
+    }
+};
 
 }  // namespace invpref

@@ -12,10 +12,11 @@
 //             Pu[u] . Qi[j] with dot64 of row_pass.hpp, -log sigmoid(x) and the regulariser sums as float64, one partial per
 //             workgroup (group_sums), and the record g = -w sigmoid(-x) / B, ONE float
 //   scatter, boundary   chunk_walk.hpp's walk with BprWalk below as its policy: an entry's operands are the triplet's three
-//             ids and g; acc += +-g * partner row, and at the end of a destination acc += n * regulariser gradient of the
-//             destination row, n the gathers of that row among the entries added (an item row: every entry; a user row: the
-//             entries of positions p < B, since a triplet gathers its user row once); float64 slots; a finished row is
-//             rounded once and stored
+//             ids and g; acc += +-g * partner row.  The rest is chunk_walk.hpp's RegWalk, the base the doubly robust pass
+//             derives its policy from too: at the end of a destination acc += n * regulariser gradient of the destination
+//             row, n the gathers of that row among the entries added (an item row: every entry; a user row: the entries of
+//             positions p < B, since a triplet gathers its user row once); float64 slots; a finished row is rounded once
+//             and stored
 //   fold      one wave: the partials in workgroup order -> losses4
 // Every row has one writer and every sum a fixed order: the same bits on every run.  The slots are float64, so a row is
 // rounded to fp32 once however many chunks it spans.  Both gradient tables are zero-filled on the stream in front of the
@@ -33,7 +34,6 @@ using namespace invpref;
 
 namespace {
 
-constexpr int64_t kI32Max = 2147483647;
 constexpr int kMaxQuads = INVPREF_BPR_MAX_ATTEMPTS / 4;
 
 __global__ __launch_bounds__(256) void bpr_draw_kernel(const int64_t *__restrict__ users, int64_t n_len,
@@ -95,21 +95,6 @@ inline Layout layout_of(int64_t B, int64_t D) {
     return L;
 }
 
-template <int NC>
-__device__ __forceinline__ void norms64(const float4 (&r)[NC], double &sq, double &ab) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        sq = sq + (double)r[c].x * (double)r[c].x;
-        sq = sq + (double)r[c].y * (double)r[c].y;
-        sq = sq + (double)r[c].z * (double)r[c].z;
-        sq = sq + (double)r[c].w * (double)r[c].w;
-        ab = ab + fabs((double)r[c].x);
-        ab = ab + fabs((double)r[c].y);
-        ab = ab + fabs((double)r[c].z);
-        ab = ab + fabs((double)r[c].w);
-    }
-}
-
 template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void bpr_pairs_kernel(const float *__restrict__ Pu, int U, const float *__restrict__ Qi, int I,
                                                         int D, const int64_t *__restrict__ users,
@@ -124,9 +109,9 @@ __global__ __launch_bounds__(256) void bpr_pairs_kernel(const float *__restrict_
         const double w = weights ? (double)weights[p] : 1.0;
         const bool valid = u >= 0 && u < U && i >= 0 && i < I && j >= 0 && j < I;
         float4 a[NC], bi[NC], bj[NC];
-        load_row<NC, VEC>(Pu, std::min<int64_t>(std::max<int64_t>(u, 0), U - 1), D, l16, a);
-        load_row<NC, VEC>(Qi, std::min<int64_t>(std::max<int64_t>(i, 0), I - 1), D, l16, bi);
-        load_row<NC, VEC>(Qi, std::min<int64_t>(std::max<int64_t>(j, 0), I - 1), D, l16, bj);
+        load_row<NC, VEC>(Pu, clamp_id(u, U), D, l16, a);
+        load_row<NC, VEC>(Qi, clamp_id(i, I), D, l16, bi);
+        load_row<NC, VEC>(Qi, clamp_id(j, I), D, l16, bj);
         const double x = dot64<NC>(a, bi) - dot64<NC>(a, bj);
         double sq = 0.0, ab = 0.0;
         norms64<NC>(a, sq, ab);
@@ -166,19 +151,8 @@ __global__ __launch_bounds__(64) void bpr_fold_kernel(const double *__restrict__
     losses4[3] = (float)(bad ? nan : (sl + L2_coe * l2) + L1_coe * l1);
 }
 
-__device__ __forceinline__ double reg_of(double x, double n2, double n1) {
-    return n2 * x + n1 * (x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0));   // (a NaN entry: n2 * NaN)
-}
-
-// what the chunked scatter and boundary walk (chunk_walk.hpp) leave to this pass
-struct BprWalk {
-    using Slot = double;   // a row is rounded to fp32 once however many chunks it spans
-    // entries whose index -> ids -> row chain is in flight together (8 NC + 8 registers per entry next to the 8 NC of the
-    // float64 accumulator: eight entries of 128-float rows took all 256 registers and left one wave per SIMD)
-    template <int NC>
-    static constexpr int ahead() { return NC == 1 ? 8 : 4; }
-    template <int NC>
-    static constexpr int batch() { return 16 / NC; }
+// what the chunked scatter and boundary walk and their regularised policy base (chunk_walk.hpp) leave to this pass
+struct BprWalk : RegWalk {
     struct Entry {
         int64_t u, i;   // the triplet's three ids and its g
         int j;
@@ -188,7 +162,6 @@ struct BprWalk {
     const int64_t *__restrict__ users, *__restrict__ pos_items;
     const int32_t *__restrict__ neg;
     const float *__restrict__ g;
-    double r2, r1;
 
     __device__ __forceinline__ Entry load(int, int pos) const {
         const int p = pos < B ? pos : pos - B;
@@ -204,28 +177,6 @@ struct BprWalk {
     // (a triplet gathers its user row once: the user side counts position p only)
     __device__ __forceinline__ int gathers(int side, int pos) const { return (side || pos < B) ? 1 : 0; }
     __device__ __forceinline__ float factor(const Entry &e, int pos) const { return pos < B ? e.g : -e.g; }
-    // acc += n * regulariser gradient of the destination row, n the gathers of that row among the entries added
-    template <int NC, bool VEC>
-    __device__ __forceinline__ void finish(const float *__restrict__ dtab, int row, int D, int cnt, int l16,
-                                           double4_t (&acc)[NC]) const {
-        float4 d[NC];
-        load_row<NC, VEC>(dtab, row, D, l16, d);
-        const double n2r = (double)cnt * r2, n1r = (double)cnt * r1;
-#pragma unroll
-        for (int k = 0; k < NC; k++) {
-            acc[k].x = acc[k].x + reg_of((double)d[k].x, n2r, n1r);
-            acc[k].y = acc[k].y + reg_of((double)d[k].y, n2r, n1r);
-            acc[k].z = acc[k].z + reg_of((double)d[k].z, n2r, n1r);
-            acc[k].w = acc[k].w + reg_of((double)d[k].w, n2r, n1r);
-        }
-    }
-    // rounded once and stored: the tables are zero-filled in front, the writers never read them
-    template <int NC, bool VEC>
-    static __device__ __forceinline__ void write_row(float *__restrict__ gtab, int row, int D, int l16, const double4_t (&acc)[NC]) {
-        float4 r[NC];
-        round_row<NC>(acc, r);
-        store_row<NC, VEC>(gtab, row, D, l16, r);
-    }
 };
 
 template <int NC, bool VEC>
@@ -236,7 +187,7 @@ __global__ __launch_bounds__(256) void bpr_scatter_kernel(const float *__restric
                                                           int nchunk, const float *__restrict__ g, double r2, double r1,
                                                           float *__restrict__ gu, float *__restrict__ gi,
                                                           double *__restrict__ part, int Dp) {
-    const BprWalk pol{U, I, B, users, pos_items, neg, g, r2, r1};
+    const BprWalk pol{{r2, r1}, U, I, B, users, pos_items, neg, g};
     chunk_scatter<NC, VEC>(pol, Pu, U, Qi, I, D, B, index, stride, C, nchunk, gu, gi, part, Dp);
 }
 

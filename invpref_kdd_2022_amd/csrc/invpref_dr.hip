@@ -14,8 +14,9 @@
 //             y = 1, the imputation pair -- the factor is h, valid() takes the positions below B, the tables are (Au, Ai)
 //             (as two launches each the Yahoo-shape pass measured 87.8 us against 65.8 us: kernels of 5 - 12 us in a row;
 //             the pairs share nothing but the index and the records, so each has a slot region of its own)
-//             in both, at the end of a destination acc += n * regulariser gradient of the destination row, n the OBSERVED
-//             positions among the entries added; float64 slots; a finished row is rounded once and stored
+//             in both, the rest is chunk_walk.hpp's RegWalk, the policy base shared with BPR's pass: at the end of a
+//             destination acc += n * regulariser gradient of the destination row, n the OBSERVED positions among the entries
+//             added (gathers()); float64 slots; a finished row is rounded once and stored
 //   fold      five waves, one per sum: the partials in workgroup order -> losses5
 // Every row has one writer and every sum a fixed order: the same bits on every run.  All four gradient tables are zero-filled
 // on the stream in front of the scatters (rows without a position hold zeros afterwards), so the writers store and never read
@@ -31,8 +32,6 @@
 using namespace invpref;
 
 namespace {
-
-constexpr int64_t kI32Max = 2147483647;
 
 __global__ __launch_bounds__(256) void dr_draw_kernel(const int32_t *__restrict__ step_n, const int64_t *__restrict__ step_id,
                                                       uint32_t user_num, uint32_t item_num, uint32_t k0, uint32_t k1,
@@ -70,21 +69,6 @@ inline Layout layout_of(int64_t B, int64_t D) {
     L.part = ws.take(2 * L.walk.part_bytes<double>());   // a slot region per pair of tables
     L.total = ws.bytes();
     return L;
-}
-
-template <int NC>
-__device__ __forceinline__ void norms64(const float4 (&r)[NC], double &sq, double &ab) {
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        sq = sq + (double)r[c].x * (double)r[c].x;
-        sq = sq + (double)r[c].y * (double)r[c].y;
-        sq = sq + (double)r[c].z * (double)r[c].z;
-        sq = sq + (double)r[c].w * (double)r[c].w;
-        ab = ab + fabs((double)r[c].x);
-        ab = ab + fabs((double)r[c].y);
-        ab = ab + fabs((double)r[c].z);
-        ab = ab + fabs((double)r[c].w);
-    }
 }
 
 // sigmoid(x) in float64 without overflow: e = exp(-|x|), 1 / (1 + e) (x >= 0), e / (1 + e) (x < 0)
@@ -208,20 +192,10 @@ __global__ __launch_bounds__(64 * kRec) void dr_fold_kernel(const double *__rest
     losses5[4] = (float)(bad ? nan : ((sl + il) + L2_coe * l2) + L1_coe * l1);
 }
 
-__device__ __forceinline__ double reg_of(double x, double n2, double n1) {
-    return n2 * x + n1 * (x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0));   // (a NaN entry: n2 * NaN)
-}
-
-// what the chunked scatter and boundary walk (chunk_walk.hpp) leave to this pass.  imp false: the prediction pair, factor g,
+// what the chunked scatter and boundary walk and their regularised policy base (chunk_walk.hpp) leave to this pass.  imp false: the prediction pair, factor g,
 // every position; imp true: the imputation pair, factor h, the observed positions (ylim = B).  A kernel argument's worth of
 // fields, chosen per workgroup (blockIdx.y): ONE instance of the walk serves both pairs of tables in one launch
-struct DrWalk {
-    using Slot = double;   // a row is rounded to fp32 once however many chunks it spans
-    // (BprWalk's figures: the entry is the same size and the accumulator too)
-    template <int NC>
-    static constexpr int ahead() { return NC == 1 ? 8 : 4; }
-    template <int NC>
-    static constexpr int batch() { return 16 / NC; }
+struct DrWalk : RegWalk {
     struct Entry {
         int64_t u, i;   // the position's two ids and its factor
         float f;
@@ -231,7 +205,6 @@ struct DrWalk {
     const int64_t *__restrict__ users, *__restrict__ items;
     const int32_t *__restrict__ draw_users, *__restrict__ draw_items;
     const float2 *__restrict__ rec;
-    double r2, r1;
 
     __device__ __forceinline__ Entry load(int, int pos) const {
         const bool obs = pos < B;
@@ -248,28 +221,6 @@ struct DrWalk {
     // (the regularisers run over the observed rows)
     __device__ __forceinline__ int gathers(int, int pos) const { return pos < B ? 1 : 0; }
     __device__ __forceinline__ float factor(const Entry &e, int) const { return e.f; }
-    // acc += n * regulariser gradient of the destination row, n the observed positions among the entries added
-    template <int NC, bool VEC>
-    __device__ __forceinline__ void finish(const float *__restrict__ dtab, int row, int D, int cnt, int l16,
-                                           double4_t (&acc)[NC]) const {
-        float4 d[NC];
-        load_row<NC, VEC>(dtab, row, D, l16, d);
-        const double n2r = (double)cnt * r2, n1r = (double)cnt * r1;
-#pragma unroll
-        for (int k = 0; k < NC; k++) {
-            acc[k].x = acc[k].x + reg_of((double)d[k].x, n2r, n1r);
-            acc[k].y = acc[k].y + reg_of((double)d[k].y, n2r, n1r);
-            acc[k].z = acc[k].z + reg_of((double)d[k].z, n2r, n1r);
-            acc[k].w = acc[k].w + reg_of((double)d[k].w, n2r, n1r);
-        }
-    }
-    // rounded once and stored: the tables are zero-filled in front, the writers never read them
-    template <int NC, bool VEC>
-    static __device__ __forceinline__ void write_row(float *__restrict__ gtab, int row, int D, int l16, const double4_t (&acc)[NC]) {
-        float4 r[NC];
-        round_row<NC>(acc, r);
-        store_row<NC, VEC>(gtab, row, D, l16, r);
-    }
 };
 
 // blockIdx.y: 0 the prediction pair (Pu, Qi -> gu, gi), 1 the imputation pair (Au, Ai -> gau, gai); each has a slot region of
@@ -287,7 +238,7 @@ __global__ __launch_bounds__(256) void dr_scatter_kernel(const float *__restrict
                                                          float *__restrict__ gau, float *__restrict__ gai,
                                                          double *__restrict__ part, int64_t part_half, int Dp) {
     const bool imp = blockIdx.y != 0;
-    const DrWalk pol{U, I, B, imp ? B : 2 * B, imp, users, items, draw_users, draw_items, rec, r2, r1};
+    const DrWalk pol{{r2, r1}, U, I, B, imp ? B : 2 * B, imp, users, items, draw_users, draw_items, rec};
     chunk_scatter<NC, VEC>(pol, imp ? Au : Pu, U, imp ? Ai : Qi, I, D, B, index, stride, C, nchunk, imp ? gau : gu,
                            imp ? gai : gi, part + (imp ? part_half : 0), Dp);
 }

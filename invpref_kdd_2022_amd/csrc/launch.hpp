@@ -31,6 +31,9 @@ hipError_t ensure_lds(K kernel, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// the largest row count or list length an entry point that indexes with int takes
+constexpr int64_t kI32Max = 2147483647;
+
 inline int check_tables(const InvPrefTables *t, bool pure_mf = false) {
     if (!t) return INVPREF_EINVAL;
     if (t->user_num <= 0 || t->item_num <= 0 || t->env_num <= 0 || t->factor_num <= 0) return INVPREF_EINVAL;

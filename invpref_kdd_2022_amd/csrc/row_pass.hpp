@@ -1,7 +1,7 @@
 // row_pass.hpp -- the gradient-pass recipe "pairs -> rows -> fold" that the MACR-MF and CausE baselines share (invpref_macr.hip,
 // invpref_cause.hip; invpref_lintrans.hip is on it too; step_wide.hpp's load_row / store_row family addresses rows differently
 // and stays apart).  chunk_walk.hpp builds on its float64 helpers -- double4_t, axpy_row, store_row -- for the chunked scatter
-// and boundary walk of the passes whose rows no row plan knows (invpref_cvib.hip, invpref_bpr.hip), which take dot64,
+// and boundary walk of the passes whose rows no row plan knows (invpref_cvib.hip, invpref_bpr.hip, invpref_dr.hip), which take dot64,
 // wave_sum64, group_sums and fold64 from here too.
 //
 //   pairs   one 16-lane group per position (lane l owns the float4 chunks l, l + 16, ... of a row: kernel_common.hpp): gathers

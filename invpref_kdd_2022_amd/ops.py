@@ -901,6 +901,17 @@ def cvib_index(users: torch.Tensor, items: torch.Tensor, step_lo: torch.Tensor, 
     return out
 
 
+def step_index(users: torch.Tensor, items: torch.Tensor, draw_users: torch.Tensor, draw_items: torch.Tensor, user_num: int,
+               item_num: int) -> torch.Tensor:
+    """The inverted index of ONE step's 2B positions, int32 [2, 2 B, 2], through cvib_index: position p is the pair (users[p],
+    items[p]), position B + p the drawn pair p.  For single calls; a manager indexes a whole run of steps in one cvib_index
+    pass."""
+    B, dev = users.numel(), users.device
+    draws = torch.stack([draw_users.to(torch.int32), draw_items.to(torch.int32)])[None].contiguous()
+    return cvib_index(users, items, torch.zeros(1, dtype=torch.int64, device=dev),
+                      torch.full((1,), B, dtype=torch.int32, device=dev), draws, user_num, item_num)[0]
+
+
 def cvib_grad_(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, items: torch.Tensor,
                draw_users: torch.Tensor, draw_items: torch.Tensor, index: torch.Tensor, implicit: bool, alpha: float,
                gamma: float, info_coe: float, eps: float, grad_user: torch.Tensor, grad_item: torch.Tensor,
@@ -948,15 +959,17 @@ def macr_index_device(users, items, user_num: int, item_num: int, device) -> tup
     return tuple(torch.from_numpy(a).to(device) for a in macr_index(users, items, user_num, item_num))
 
 
-def _pass_workspace(op: str, nbytes_of, workspace: Optional[Workspace], params, users, *tensors, uniform=None) -> torch.Tensor:
-    """How the three *_grad wrappers open: every tensor on the GPU, the workspace grown to the pass's bytes (0: sizes refused)"""
+def _pass_workspace(op: str, nbytes_of, workspace: Optional[Workspace], params, users, *tensors, uniform=None,
+                    what: str = 'interactions') -> torch.Tensor:
+    """How the *_grad wrappers of the own passes open: every tensor on the GPU, the workspace grown to the pass's bytes (0: sizes
+    refused).  params: the tables, the user and item table first; what: what the error calls a minibatch's rows"""
     _gpu(users, uniform, *tensors, *params)
     P, Q = params[0], params[1]
     counts = (users.numel(),) if uniform is None else (users.numel(), uniform.numel())
     nbytes = nbytes_of(P.shape[0], Q.shape[0], *counts, P.shape[1])
     if nbytes == 0:
         raise InvPrefError(f'{op}: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
-                           + (f'{counts[0]} interactions)' if uniform is None else f'{counts[0]} + {counts[1]} positions)'))
+                           + (f'{counts[0]} {what})' if uniform is None else f'{counts[0]} + {counts[1]} positions)'))
     return (workspace or Workspace(P.device)).get(nbytes)
 
 
@@ -1082,12 +1095,9 @@ def bpr_workspace_bytes(user_num: int, item_num: int, batch: int, factor_num: in
 
 
 def bpr_index(users: torch.Tensor, neg: torch.Tensor, item_num: int, user_num: int, pos_items: torch.Tensor) -> torch.Tensor:
-    """The inverted index of ONE step's 2B signed positions, int32 [2, 2 B, 2], through cvib_index: position p is (u_p, i_p),
-    position B + p is (u_p, j_p).  For single calls; a manager indexes a whole run of steps in one cvib_index pass."""
-    B, dev = users.numel(), users.device
-    draws = torch.stack([users.to(torch.int32), neg.to(torch.int32)])[None].contiguous()
-    return cvib_index(users, pos_items, torch.zeros(1, dtype=torch.int64, device=dev),
-                      torch.full((1,), B, dtype=torch.int32, device=dev), draws, user_num, item_num)[0]
+    """The inverted index of ONE step's 2B signed positions, int32 [2, 2 B, 2]: step_index with (users, neg) as the drawn
+    pairs -- position p is (u_p, i_p), position B + p is (u_p, j_p)."""
+    return step_index(users, pos_items, users, neg, user_num, item_num)
 
 
 def bpr_grad(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, pos_items: torch.Tensor, neg: torch.Tensor,
@@ -1100,12 +1110,8 @@ def bpr_grad(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Te
     (score_loss, L2_reg, L1_reg, loss).  Bitwise reproducible, no float atomics, no host sync (capturable once the workspace
     is sized; a replay reads ids, negatives, weights and index as they are then).  A triplet with an id outside its table
     (neg = -1 included) is skipped whole and the four losses are NaN."""
-    _gpu(user_table, item_table, users, pos_items, neg, index, grad_user, grad_item, losses4, weights)
-    nbytes = bpr_workspace_bytes(user_table.shape[0], item_table.shape[0], users.numel(), user_table.shape[1])
-    if nbytes == 0:
-        raise InvPrefError(f'bpr_grad: sizes outside the kernels\' range (tables {tuple(user_table.shape)} / '
-                           f'{tuple(item_table.shape)}, {users.numel()} triplets)')
-    ws = (workspace or Workspace(user_table.device)).get(nbytes)
+    ws = _pass_workspace('bpr_grad', bpr_workspace_bytes, workspace, (user_table, item_table), users, pos_items, neg, index,
+                         grad_user, grad_item, losses4, weights, what='triplets')
     _o().bpr_grad_(user_table, item_table, users, pos_items, neg, weights, index, float(L2_coe), float(L1_coe), grad_user,
                    grad_item, losses4, ws)
 
@@ -1140,12 +1146,9 @@ def dr_workspace_bytes(user_num: int, item_num: int, batch: int, factor_num: int
 
 def dr_index(users: torch.Tensor, items: torch.Tensor, draw_users: torch.Tensor, draw_items: torch.Tensor, user_num: int,
              item_num: int) -> torch.Tensor:
-    """The inverted index of ONE step's 2B positions, int32 [2, 2 B, 2], through cvib_index: position p is the observed pair p,
-    position B + p the drawn pair p.  For single calls; a manager indexes a whole run of steps in one cvib_index pass."""
-    B, dev = users.numel(), users.device
-    draws = torch.stack([draw_users.to(torch.int32), draw_items.to(torch.int32)])[None].contiguous()
-    return cvib_index(users, items, torch.zeros(1, dtype=torch.int64, device=dev),
-                      torch.full((1,), B, dtype=torch.int32, device=dev), draws, user_num, item_num)[0]
+    """The inverted index of ONE step's 2B positions, int32 [2, 2 B, 2]: step_index -- position p is the observed pair p,
+    position B + p the drawn pair p."""
+    return step_index(users, items, draw_users, draw_items, user_num, item_num)
 
 
 def dr_grad(form, params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor], users: torch.Tensor, items: torch.Tensor,
@@ -1161,13 +1164,8 @@ def dr_grad(form, params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor
     (score_loss, imputation_loss, L2_reg, L1_reg, loss).  Bitwise reproducible, no float atomics, no host sync (capturable once
     the workspace is sized; a replay reads ids, scores, weights, draws and index as they are then).  A position with an id
     outside its table (a drawn -1 included) is skipped and the five losses are NaN."""
-    _gpu(users, items, scores, draw_users, draw_items, index, losses5, weights, *params4, *grads4)
-    P, Q = params4[0], params4[1]
-    nbytes = dr_workspace_bytes(P.shape[0], Q.shape[0], users.numel(), P.shape[1])
-    if nbytes == 0:
-        raise InvPrefError(f'dr_grad: sizes outside the kernels\' range (tables {tuple(P.shape)} / {tuple(Q.shape)}, '
-                           f'{users.numel()} observed rows)')
-    ws = (workspace or Workspace(P.device)).get(nbytes)
+    ws = _pass_workspace('dr_grad', dr_workspace_bytes, workspace, params4, users, items, scores, draw_users, draw_items, index,
+                         losses5, weights, *grads4, what='observed rows')
     _o().dr_grad_(DR_FORMS[form] if isinstance(form, str) else int(form), *params4, users, items, scores, weights, draw_users,
                   draw_items, index, float(L2_coe), float(L1_coe), *grads4, losses5, ws)
 
