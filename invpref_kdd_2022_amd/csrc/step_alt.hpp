@@ -279,6 +279,17 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         const bool rpend = has_prev && (meta < 0);            // bit 31: some row of the round has pending rows
         const int cnt_i = (meta >> 9) & 0x3fffff;
         const int nsmp = (active && has_cur) ? (mode == 7 ? dd.w - dd.z : mode) : 0;
+        // What the wave's four descriptors say together, in scalar registers: a load is issued where SOME group of the wave
+        // has the data it carries, behind a scalar branch -- a wave of one-interaction slices gathers one slot and refills
+        // nothing, a wave of idle slots loads no rows.  A group that has less than its wave keeps the clamped form (entry
+        // 0's rows, unused): no per-lane branch around a load
+        int w_n = 0;
+#pragma unroll
+        for (int g = 0; g < 64 / LG; g++) w_n = max(w_n, __builtin_amdgcn_readlane(nsmp, g * LG));
+        const bool w_act = __builtin_amdgcn_ballot_w64(active) != 0;
+        // (the descriptor's second half arrives with the first: it passes through here, so that no later use of it -- behind
+        //  branches some of which request nothing -- becomes a wait for everything in flight)
+        asm volatile("" : "+v"(d1.x), "+v"(d1.y), "+v"(d1.z), "+v"(d1.w));
         if (r == r0 + STAMP_ROUND) ASTAMP(2);
         const int s_lo = dd.z, s_hi1 = max(dd.w - 1, dd.z);
         const int *dwords = reinterpret_cast<const int *>(a.desc + (r * NG + grp) * 2);
@@ -296,13 +307,24 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         };
         // ---- everything that depends only on the descriptor goes out together: own rows + moments, the first pending
         // rows, the first interactions' ids (listed ones) -- then their partner rows
+        // (the wave's pending count is formed in front of the own rows' loads: the wait for the pending ranges, which came with
+        //  the descriptor, is then a wait for them alone -- behind the own rows, which a wave of idle slots does not
+        //  request, it would be a wait for everything in flight, in front of the gathers)
+        const int npend = (active && has_prev) ? pdd.y - pdd.x : 0;
+        int n_wave = 0;
+        if (rpend) {
+#pragma unroll
+            for (int g = 0; g < 64 / LG; g++) n_wave = max(n_wave, __builtin_amdgcn_readlane(npend, g * LG));
+        }
         const int rowc = active ? row : 0;
-        float4 oi = row4<VEC, FULL>(own0, rowc, D, lg), oe = f4zero();
-        float4 mi = row4<VEC, FULL>(a.own_m[0], rowc, D, lg), vi = row4<VEC, FULL>(a.own_v[0], rowc, D, lg);
-        float4 me = f4zero(), ve = f4zero();
-        if (!pure) {
-            oe = row4<VEC, FULL>(own1, rowc, D, lg);
-            me = row4<VEC, FULL>(a.own_m[1], rowc, D, lg); ve = row4<VEC, FULL>(a.own_v[1], rowc, D, lg);
+        float4 oi = f4zero(), oe = f4zero(), mi = f4zero(), vi = f4zero(), me = f4zero(), ve = f4zero();
+        if (w_act) {   // (a wave of idle slots: nothing is stored from it, zeros do)
+            oi = row4<VEC, FULL>(own0, rowc, D, lg);
+            mi = row4<VEC, FULL>(a.own_m[0], rowc, D, lg); vi = row4<VEC, FULL>(a.own_v[0], rowc, D, lg);
+            if (!pure) {
+                oe = row4<VEC, FULL>(own1, rowc, D, lg);
+                me = row4<VEC, FULL>(a.own_m[1], rowc, D, lg); ve = row4<VEC, FULL>(a.own_v[1], rowc, D, lg);
+            }
         }
         // pending contribution rows of this slice: contiguous pairs [pa, pb).  They land in the wave's own four partial-sum
         // rows, read as [pair][table][64 lanes x 16 B]: each lane sends its 16-byte piece of a pair the slice HAS straight
@@ -310,7 +332,6 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         // nothing), up to kAltPendBatch pairs at once
         constexpr int PB = kAltPendBatch;
         static_assert(PB * 2 * 64 * 4 <= 4 * G::SLAB && (4 * G::SLAB) % 4 == 0 && G::red % 4 == 0, "landing block: the wave's four slab rows");
-        const int npend = (active && has_prev) ? pdd.y - pdd.x : 0;
         const float *pbase = a.pend_rows + (unsigned)(npend > 0 ? pdd.x : 0) * (unsigned)(2 * DP) + lg * 4;
         float *land = red + wave * 4 * G::SLAB;
         auto pland = [&](int s0) {
@@ -328,13 +349,7 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         };
         float4 gpi = f4zero(), gpe = f4zero();
         // (a round with nothing pending -- most user-side rounds -- adds no loads to the launch's first burst)
-        int n_wave = 0;
-        if (rpend) {
-            n_wave = npend;
-#pragma unroll
-            for (int g = 0; g < 64 / LG; g++) n_wave = max(n_wave, __builtin_amdgcn_readlane(npend, g * LG));
-            pland(0);
-        }
+        if (rpend) pland(0);
 
         struct Slot {
             float4 qi, qa;
@@ -380,9 +395,16 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
                 if (__builtin_amdgcn_ballot_w64(mode == 7) != 0) {
 #pragma unroll
                     for (int j = 0; j < 2 * UE; j++) {
-                        const int4 q = a.list[mode == 7 ? min(s_lo + j, s_hi1) : 0];
-                        ls[j] = USample{q.x, q.y, __builtin_bit_cast(float, q.z)};
+                        // (a list slice has three interactions or more: only the fourth entry can be nobody's)
+                        if (j < 3 || w_n > j) {
+                            const int4 q = a.list[mode == 7 ? min(s_lo + j, s_hi1) : 0];
+                            ls[j] = USample{q.x, q.y, __builtin_bit_cast(float, q.z)};
+                        }
                     }
+                    // (waited for HERE, where the parent's code waited too: behind the join the wait would count the
+                    //  loads of the shortest path -- none -- and hold up the waves without a list slice as well)
+#pragma unroll
+                    for (int j = 0; j < 2 * UE; j++) asm volatile("" : "+v"(ls[j].oth), "+v"(ls[j].ps), "+v"(ls[j].y));
                 }
             } else {
 #pragma unroll
@@ -412,18 +434,29 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         };
         if (n_wave > 0) psum(0);
         if (has_cur) {
-#pragma unroll
-            for (int j = 0; j < UE; j++) {
-                if (FULL) {
-                    USample sm = ls[j];
-                    if (mode != 7) sm = j == 0 ? USample{dd.z, dd.w, __builtin_bit_cast(float, dd1.x)} : USample{dd1.y, dd1.z, __builtin_bit_cast(float, dd1.w)};
-                    if (mode == 0 || !active) sm = USample{0, 0, 0.f};   // (a job without interactions: entry 0's rows, unused)
-                    gather(sl[j], sm);
-                } else if (j < nsmp) {
-                    gather(sl[j], ls[j]);
+            static_assert(UE == 2, "the nested form below: two slots");
+            if (FULL) {
+                // both slots' ids are chosen in front of the branches (selects on values that have arrived, kept here): chosen
+                // inside, the second slot's choice was a wait for everything the first slot had just requested
+                USample sm0 = ls[0], sm1 = ls[1];
+                if (mode != 7) {
+                    sm0 = USample{d.z, d.w, __builtin_bit_cast(float, d1.x)};
+                    sm1 = USample{d1.y, d1.z, __builtin_bit_cast(float, d1.w)};
                 }
-                idn[j] = ls[UE + j];
+                if (mode == 0 || !active) sm0 = sm1 = USample{0, 0, 0.f};   // (a job without interactions: entry 0's rows, unused)
+                asm volatile("" : "+v"(sm0.oth), "+v"(sm0.ps), "+v"(sm0.y), "+v"(sm1.oth), "+v"(sm1.ps), "+v"(sm1.y));
+                // slot j of a wave whose groups all have j interactions or fewer is not gathered (nested: one join)
+                if (w_n > 0) {
+                    gather(sl[0], sm0);
+                    if (w_n > 1) gather(sl[1], sm1);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < UE; j++)
+                    if (j < nsmp) gather(sl[j], ls[j]);
             }
+#pragma unroll
+            for (int j = 0; j < UE; j++) idn[j] = ls[UE + j];
         }
         // (this step's small tables, (ii) below; requested in front of the previous step's update instead: no gain, git history)
         AltStage stg;
@@ -584,13 +617,53 @@ __device__ __forceinline__ void alt_task(const AltArgs &a, int r0, int slab_inde
         };
         // (Tried in round 5: the slice's interactions evaluated two at a time in one basic block at two workgroups per CU, so
         //  that both chains interleave -- item-side launches 17.4 us against 16.7: one wave's evaluation is bound by vector
-        //  instruction ISSUE, ~340 VALU instructions per interaction, not by dependent latencies; nothing to interleave)
-        for (int s = 0; s < nsmp; s += UE) {
+        //  instruction ISSUE, ~340 VALU instructions per interaction, not by dependent latencies; nothing to interleave.
+        //  Round 8, stamps: a user-side job spent 3.08 us here (median) while every wave gathered and refilled both slots
+        //  whatever its slices held, 2.22 us with the loads below -- so the phase was not ALL issue.  Supposed cause: the
+        //  refills of nothing stood in the memory queue in front of the push stores, whose acknowledgements a stamp waits for)
+        if (FULL) {
+            // The trip count is the wave's (a scalar), a group with fewer interactions sits its steps out.  While BOTH slots
+            // have a successor somewhere in the wave (slices of four or more: hot rows) they are refilled unconditionally
+            // (their ids too: entries past the slice's last are loaded clamped, as before); the last one to three
+            // interactions are straight-line code per case, so that no refill that does not exist is issued and none joins
+            // in front of an evaluation that does not need it.
+            // Waits that are NOT counted here (profiles/r08/EXPERIMENTS.md): an evaluation is skipped PER LANE, and hipcc
+            // counts a wait behind such a join by the path with the fewest operations in flight -- the one that skipped,
+            // without the two push stores (stores count in vmcnt).  So the second evaluation of a two-interaction wave
+            // waits vmcnt(2), vmcnt(0) for its slot: the slot came in with the first burst, what the wait really waits for
+            // is the acknowledgement of the first evaluation's push stores.  The third evaluation of a three-interaction
+            // wave waits vmcnt(0) for its refill, the second one's stores included (the parent's loop header did that on
+            // every trip).  Passing the slots through an empty asm in front of the first evaluation removes the first
+            // wait; measured in one job it gains 0.15 us on the user-side launch and LOSES 0.15 us on the item-side one
+            // (eight waves per workgroup, whose stores then leave back to back), 0.5 % in all: left as it is.
+            static_assert(UE == 2, "the tail below: two slots");
+            int s = 0;
+            for (; s + 2 * UE <= w_n; s += UE) {
 #pragma unroll
-            for (int j = 0; j < UE; j++) {
-                if (s + j < nsmp) step(sl[j], true);
-                if (FULL || s + UE + j < nsmp) gather(sl[j], idn[j]);
-                if (FULL || s + 2 * UE + j < nsmp) idn[j] = sample_at(s + 2 * UE + j);
+                for (int j = 0; j < UE; j++) {
+                    if (s + j < nsmp) step(sl[j], true);
+                    gather(sl[j], idn[j]);
+                    idn[j] = sample_at(s + 2 * UE + j);
+                }
+            }
+            const int rest = w_n - s;   // 0 (a wave without interactions) .. 3
+            if (rest == 3) {
+                if (s < nsmp) step(sl[0], true);
+                gather(sl[0], idn[0]);
+                if (s + 1 < nsmp) step(sl[1], true);
+                if (s + 2 < nsmp) step(sl[0], true);
+            } else if (rest > 0) {
+                if (s < nsmp) step(sl[0], true);
+                if (rest == 2 && s + 1 < nsmp) step(sl[1], true);
+            }
+        } else {
+            for (int s = 0; s < nsmp; s += UE) {
+#pragma unroll
+                for (int j = 0; j < UE; j++) {
+                    if (s + j < nsmp) step(sl[j], true);
+                    if (s + UE + j < nsmp) gather(sl[j], idn[j]);
+                    if (s + 2 * UE + j < nsmp) idn[j] = sample_at(s + 2 * UE + j);
+                }
             }
         }
         if (r == r0 + STAMP_ROUND) ASTAMP(5);

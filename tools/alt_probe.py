@@ -95,6 +95,52 @@ print(f'shape U={U} I={I} E={E} D={D} B={B}, {nb} steps; slots per round (users,
       ' '.join(f'{"UI"[p["side"]]}{planlib.alt_workgroups(p) + 40}' for p in apl[:4]) + ' ... flush ' +
       f'{planlib.alt_workgroups(apl[-1]) + 40}; two-launch {planlib.launch_workgroups(pls[0], 0)} + {planlib.launch_workgroups(pls[0], 1)}')
 
+
+def load_counts(pl):
+    """Where an alternating launch's loads carry data (csrc/step_alt.hpp issues them per WAVE: four group slots of a job round,
+    eight rows of a stream iteration; a fold thread issues chunks of 32 partials)."""
+    ng, spt = pl['slots_per_round'], pl['rows_per_stream_task']
+    d = pl['desc']
+    act = d[:, :, 0] >= 0
+    mode = (d[:, :, 1] >> 6) & 7
+    nsmp = np.where(act & bool(pl['has_cur']), np.where(mode == 7, d[:, :, 3] - d[:, :, 2], mode), 0).reshape(len(d), ng // 4, 4)
+    w_n, actw = nsmp.max(axis=2), act.reshape(len(d), ng // 4, 4)
+    nw = max(w_n.size, 1)
+    print(f'  job waves {w_n.size}: all groups one interaction {(nsmp == 1).all(axis=2).sum() / nw:.3f}, by the wave\'s longest slice '
+          + ' '.join(f'{k}:{(w_n == k).sum() / nw:.3f}' for k in range(4)) + f' 4+:{(w_n >= 4).sum() / nw:.3f}'
+          + f' | idle slots {1 - act.mean() if act.size else 0:.3f}, waves of idle slots only {(~actw.any(axis=2)).sum() / nw:.3f}'
+          + f', waves with a list slice {(mode.reshape(len(d), ng // 4, 4) == 7).any(axis=2).sum() / nw:.3f}')
+    # gather slots a wave issues (D = 64; four or five loads each): the wave's longest slice (up to round 7: both slots and two
+    # refills per loop trip, whatever the wave held); own-row sets (six loads): waves with an active slot (round 7: every wave)
+    print(f'  gather slots issued: {int(w_n.sum())} (every wave both slots and both refills per trip: {int((2 + 2 * -(-w_n // 2)).sum())}); '
+          f'own-row sets {int(actw.any(axis=2).sum())} (every wave: {w_n.size})')
+    st = pl['stream'].reshape(-1, 4)
+    cls = np.asarray(pl['cls'])
+    waves = with_pend = 0
+    for c in range(int(pl['n_classes'])):
+        rows = st[cls[c, 2]:cls[c, 2] + cls[c, 3], 3]
+        for t0 in range(0, len(rows), spt):
+            task = rows[t0:t0 + spt]
+            iters = -(-len(task) // (2 * ng))
+            pad = np.zeros(iters * 2 * ng, np.int64)
+            pad[:len(task)] = task
+            per_wave = pad.reshape(iters, 2, ng // 4, 4).max(axis=(1, 3))      # [iteration][wave]
+            live = np.zeros(iters * 2 * ng, bool)
+            live[:len(task)] = True
+            lw = live.reshape(iters, 2, ng // 4, 4).any(axis=(1, 3))
+            waves += int(lw.sum())
+            with_pend += int((per_wave[lw] > 0).sum())
+    print(f'  streamed rows {len(st)}: with pending pairs {(st[:, 3] > 0).mean() if len(st) else 0:.3f}; wave iterations {waves}, '
+          f'with a pending pair {with_pend / max(waves, 1):.3f}')
+    npv, need = pl['n_partials_prev'], -(-pl['n_partials_prev'] // ng)
+    print(f'  fold: {npv} partials over {ng} sub-rows: {need} loads per thread needed, {32 * -(-need // 32)} issued (chunks of 32, clamped)')
+
+
+for c_ in (int(os.environ.get('PROBE_STAMP_STEP', '10')), int(os.environ.get('PROBE_STAMP_STEP', '10')) + 1):
+    if c_ < len(apl):
+        print(f'load counts, launch {c_} (side {"UI"[apl[c_]["side"]]}):')
+        load_counts(apl[c_])
+
 if os.environ.get('PROBE_STEPWISE'):
     # every step of the two-launch trajectory redone from the SAME state by the alternating form (one evaluating launch +
     # the flush), from either side: separates a wrong update from the drift of two correct trajectories
