@@ -105,7 +105,7 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 # (csrc/invpref_rank_stats.hip), BPR-MF's negative sampler and gradient pass (csrc/invpref_bpr.hip), doubly
 # robust MF's pair sampler and gradient pass (csrc/invpref_dr.hip), the segment ranks and AUC pair counts of explicit evaluation
 # (csrc/invpref_segment_rank.hip), WMF by alternating least squares: the Gram matrix, the exact row solves and the objective
-# (csrc/invpref_als.hip).
+# (csrc/invpref_als.hip), the keys-only radix sort and the sort-based AUC (csrc/invpref_key_sort.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
@@ -139,7 +139,10 @@ ALS_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_als.h')
 ALS_SIGNATURES, ALS_DEFINES = _read_header(ALS_HEADER_PATH)
 ALS_MAX_FACTORS, ALS_CHUNK, ALS_SPLIT, ALS_GRAM_ROWS = (
     ALS_DEFINES['ALS_' + n] for n in ('MAX_FACTORS', 'CHUNK', 'SPLIT', 'GRAM_ROWS'))
-CAUSE_MODE_ITEM, CAUSE_MODE_USER = CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
+KEY_SORT_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_key_sort.h')
+KEY_SORT_SIGNATURES, KEY_SORT_DEFINES = _read_header(KEY_SORT_HEADER_PATH)
+KEY_SORT_TILE, AUC_SORT_MIN = KEY_SORT_DEFINES['KEY_SORT_TILE'], KEY_SORT_DEFINES['AUC_SORT_MIN']
+CAUSE_MODE_ITEM, CAUSE_MODE_USER =CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 # (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
 EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
                  (SCALED_HEADER_PATH, 'SCALED_SIGNATURES', 'SCALED_DEFINES'),
@@ -151,7 +154,8 @@ EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_H
                  (RANK_STATS_HEADER_PATH, 'RANK_STATS_SIGNATURES', 'RANK_STATS_DEFINES'),
                  (BPR_HEADER_PATH, 'BPR_SIGNATURES', 'BPR_DEFINES'), (DR_HEADER_PATH, 'DR_SIGNATURES', 'DR_DEFINES'),
                  (SEGMENT_RANK_HEADER_PATH, 'SEGMENT_RANK_SIGNATURES', 'SEGMENT_RANK_DEFINES'),
-                 (ALS_HEADER_PATH, 'ALS_SIGNATURES', 'ALS_DEFINES'))
+                 (ALS_HEADER_PATH, 'ALS_SIGNATURES', 'ALS_DEFINES'),
+                 (KEY_SORT_HEADER_PATH, 'KEY_SORT_SIGNATURES', 'KEY_SORT_DEFINES'))
 
 _lib = None
 

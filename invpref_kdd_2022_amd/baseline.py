@@ -638,8 +638,8 @@ class _RunIndexMixin(_StagedRunMixin):
     of the training data a step's minibatch is.  The captured launches read their row of both buffers when they run.
 
     A manager supplies _workspace_bytes(batch), the ops.*_workspace_bytes of its pass over a minibatch of `batch` rows."""
-    # bytes of the run's index: longer runs are replayed as several shorter graphs.  Building it takes four to five times as
-    # much for a moment (keys, sorted keys, the sort's permutation and temporaries: ops.cvib_index), freed before the run starts
+    # bytes of the run's index: longer runs are replayed as several shorter graphs.  Building it takes twice as much for a
+    # moment (the keys and the alternate buffer of their in-place sort: ops.cvib_index), freed before the run starts
     _INDEX_BUDGET = 512 << 20
 
     def _init_run_index(self) -> None:

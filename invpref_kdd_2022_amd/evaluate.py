@@ -710,7 +710,12 @@ class ExplicitRankTestManager(ExplicitTestManager):
     ``predict(users, items)``.  -> {'mse', 'rmse', 'mae', 'auc', 'gauc', 'ndcg': {k: ..}, 'recall': {..}, 'precision': {..},
     'mrr', 'map', 'users': {'ranked': .., 'gauc': ..}}: 'auc' is NaN where a class is empty; the per-user figures are means
     over the users with at least one positive ('ranked'), 'gauc' over those that also have a negative ('gauc'); a mean over
-    no user is NaN.  ``ranks()`` gives the integers ``ops.rank_metrics_weighted`` and ``ops.bootstrap_sums`` take."""
+    no user is NaN.  ``ranks()`` gives the integers ``ops.rank_metrics_weighted`` and ``ops.bootstrap_sums`` take.
+    ``auc_route`` ('auto', 'pairs' or 'sorted': ``ops.auc_counts``) picks how the global AUC's pair counts are computed --
+    the quadratic pair count or the sort-based one, the same integers either way and so the same dictionary; an attribute,
+    set on the instance (``mgr.auc_route = 'sorted'``) or on the class, because the constructor's parameter list is pinned."""
+
+    auc_route = 'auto'
 
     def __init__(self, model, data_loader, top_k_list: list, positive_threshold: float):
         super().__init__(model, data_loader)
@@ -772,7 +777,7 @@ class ExplicitRankTestManager(ExplicitTestManager):
         err = torch.empty(2, dtype=torch.float64, device=device)
         call('invpref_eval_error_sums_hip', ptr(pred), ptr(g['target']), pred.numel(), ptr(err), stream_ptr())
         sums = ops.rank_metrics_from_ranks(self._ranks(g, pred), g['truth_ptr'], g['n_neg'], self.top_k_list)
-        pair = ops.auc_pairs(pred, g['labels'])
+        pair = ops.auc_counts(pred, g['labels'], route=self.auc_route)
         out = torch.cat([err, sums.reshape(-1), pair.view(torch.float64)])
         ks, n, ranked, gauc = list(self.top_k_list), float(g['n']), g['ranked'], g['gauc']
 

@@ -27,6 +27,7 @@ from . import torch_ops_bpr  # noqa: F401  (BPR-MF's fragment: torch.ops.invpref
 from . import torch_ops_dr  # noqa: F401  (doubly robust MF's fragment: torch.ops.invpref.dr_draw, dr_grad_)
 from . import torch_ops_als  # noqa: F401  (WMF by alternating least squares: torch.ops.invpref.als_gram, als_solve_, als_objective)
 from . import torch_ops_segment_rank  # noqa: F401  (explicit evaluation's ranks: torch.ops.invpref.segment_ranks, auc_pairs)
+from . import torch_ops_key_sort  # noqa: F401  (the library's own sort: torch.ops.invpref.sort_keys_, auc_sorted)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -580,6 +581,37 @@ def auc_pairs(values: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return _o().auc_pairs(values, labels)
 
 
+def auc_sorted(values: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """auc_pairs' int64 [3] = {C, P, Nn}, integer for integer, in O(n log n) (include/invpref_key_sort.h): the negatives' order
+    keys are sorted by sort_keys' radix passes, and every positive searches its lower and upper bound among them."""
+    _gpu(values, labels)
+    return _o().auc_sorted(values, labels)
+
+
+AUC_ROUTES = ('auto', 'pairs', 'sorted')
+
+
+def auc_counts(values: torch.Tensor, labels: torch.Tensor, route: str = 'auto') -> torch.Tensor:
+    """{C, P, Nn} of the global AUC by one of two routes that give the same integers: 'pairs' (auc_pairs: quadratic, ahead on
+    small inputs), 'sorted' (auc_sorted), or 'auto': the sorted route from INVPREF_AUC_SORT_MIN entries on (a measured
+    crossover: include/invpref_key_sort.h)."""
+    if route not in AUC_ROUTES:
+        raise InvPrefError(f'auc_counts: route {route!r} is none of {AUC_ROUTES}')
+    if route == 'auto':
+        route = 'sorted' if values.numel() >= _capi.AUC_SORT_MIN else 'pairs'
+    return auc_sorted(values, labels) if route == 'sorted' else auc_pairs(values, labels)
+
+
+def sort_keys(keys: torch.Tensor, key_bits: Optional[int] = None) -> torch.Tensor:
+    """Sorts an int32 / int64 vector on the device IN PLACE, ascending, its bits read as unsigned integers, and returns it
+    (include/invpref_key_sort.h).  key_bits: the caller's bound on the significant low bits (None: the full width); it sets
+    the number of 8-bit radix passes.  Keys that break the bound are ordered by their low key_bits bits, equal ones in input
+    order.  Allocates one alternate buffer of the keys' size plus 1/16 of it for histograms (u32 keys; 1/32 for u64)."""
+    _gpu(keys)
+    _o().sort_keys_(keys, 8 * keys.element_size() if key_bits is None else int(key_bits))
+    return keys
+
+
 def bootstrap_intervals(sums, covered_col: int, confidence: float = 0.95):
     """The host half of a bootstrap of ratio metrics: sums [n_boot, S] (bootstrap_sums read back) -> float64 [S, 2], row s the
     percentile interval (lo, hi) of sums[:, s] / sums[:, covered_col] at the given confidence -- np.quantile at (1 - c) / 2 and
@@ -891,9 +923,9 @@ def cvib_index(users: torch.Tensor, items: torch.Tensor, step_lo: torch.Tensor, 
     Returns int32 [steps, 2, 2 * batch_cap, 2]: per step and side (0: user rows, 1: item rows) the positions sorted by
     destination row, as (row, position); written into `out` if given (the buffer captured launches read).  The caller
     guarantees step_n[s] <= batch_cap and step_lo[s] + step_n[s] <= len(users) (device values: not checked here).  Allocates:
-    the keys, their sorted copy and the sort's int64 permutation -- three arrays of the index's own size (8 bytes per entry)
-    -- plus the radix sort's temporaries are alive at once, so the transient peak is four to five times the index.  Call it
-    outside a graph capture."""
+    the int64 keys and the workspace of the in-place keys-only sort (sort_keys: an alternate buffer of the keys' size plus
+    1/32 of it) -- two arrays of the index's own size (8 bytes per entry), so the transient peak is two times the index
+    (measured: DESIGN.md §4.6.3).  Call it outside a graph capture."""
     _gpu(users, items, step_lo, step_n, draws, out)
     if out is None:
         out = torch.empty(draws.shape[0], 2, 2 * draws.shape[2], 2, dtype=torch.int32, device=draws.device)

@@ -927,9 +927,11 @@ def _cvib_index(users, items, step_lo, step_n, draws, user_num, item_num, index)
     keys = torch.empty(steps * 2 * 2 * cap, dtype=torch.int64, device=users.device)
     call('invpref_cvib_index_keys_hip', ptr(users), ptr(items), ptr(step_lo), ptr(step_n), steps, ptr(draws), cap,
          int(user_num), int(item_num), ptr(keys), stream_ptr())
-    # unique keys: the result does not depend on the sort.  torch.sort also returns an int64 permutation, which nothing here
-    # needs: it is dropped at once, but it and the unsorted keys are alive during the sort (see ops.cvib_index)
-    keys = torch.sort(keys).values
+    # unique, non-negative keys below 2 steps (R + 1) stride (csrc/invpref_cvib.hip): the result does not depend on the sort.
+    # The library's keys-only sort orders them in place, in as many 8-bit passes as that bound has bytes (see ops.cvib_index)
+    from . import torch_ops_key_sort  # noqa: F401  (registers sort_keys_; it imports this module)
+    bound = 2 * steps * (max(int(user_num), int(item_num)) + 1) * 2 * cap
+    torch.ops.invpref.sort_keys_(keys, (bound - 1).bit_length())
     call('invpref_cvib_index_hip', ptr(keys), steps, cap, int(user_num), int(item_num), ptr(index), stream_ptr())
 
 
