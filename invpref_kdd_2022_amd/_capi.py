@@ -105,7 +105,8 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 # (csrc/invpref_rank_stats.hip), BPR-MF's negative sampler and gradient pass (csrc/invpref_bpr.hip), doubly
 # robust MF's pair sampler and gradient pass (csrc/invpref_dr.hip), the segment ranks and AUC pair counts of explicit evaluation
 # (csrc/invpref_segment_rank.hip), WMF by alternating least squares: the Gram matrix, the exact row solves and the objective
-# (csrc/invpref_als.hip), the keys-only radix sort and the sort-based AUC (csrc/invpref_key_sort.hip).
+# (csrc/invpref_als.hip), the keys-only radix sort and the sort-based AUC (csrc/invpref_key_sort.hip), sampled-softmax MF's
+# shared-negative sampler and gradient pass (csrc/invpref_ssm.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
@@ -142,6 +143,9 @@ ALS_MAX_FACTORS, ALS_CHUNK, ALS_SPLIT, ALS_GRAM_ROWS = (
 KEY_SORT_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_key_sort.h')
 KEY_SORT_SIGNATURES, KEY_SORT_DEFINES = _read_header(KEY_SORT_HEADER_PATH)
 KEY_SORT_TILE, AUC_SORT_MIN = KEY_SORT_DEFINES['KEY_SORT_TILE'], KEY_SORT_DEFINES['AUC_SORT_MIN']
+SSM_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_ssm.h')
+SSM_SIGNATURES, SSM_DEFINES = _read_header(SSM_HEADER_PATH)
+SSM_MAX_NEG, SSM_MAX_STEPS, SSM_MAX_BATCH = (SSM_DEFINES['SSM_' + n] for n in ('MAX_NEG', 'MAX_STEPS', 'MAX_BATCH'))
 CAUSE_MODE_ITEM, CAUSE_MODE_USER =CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 # (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
 EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
@@ -155,7 +159,8 @@ EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_H
                  (BPR_HEADER_PATH, 'BPR_SIGNATURES', 'BPR_DEFINES'), (DR_HEADER_PATH, 'DR_SIGNATURES', 'DR_DEFINES'),
                  (SEGMENT_RANK_HEADER_PATH, 'SEGMENT_RANK_SIGNATURES', 'SEGMENT_RANK_DEFINES'),
                  (ALS_HEADER_PATH, 'ALS_SIGNATURES', 'ALS_DEFINES'),
-                 (KEY_SORT_HEADER_PATH, 'KEY_SORT_SIGNATURES', 'KEY_SORT_DEFINES'))
+                 (KEY_SORT_HEADER_PATH, 'KEY_SORT_SIGNATURES', 'KEY_SORT_DEFINES'),
+                 (SSM_HEADER_PATH, 'SSM_SIGNATURES', 'SSM_DEFINES'))
 
 _lib = None
 

@@ -1,6 +1,7 @@
 """PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF,
 CVIB-MF and fairness-MF; and MACR-MF, LinearTrans-MF, CausE, BPR-MF and doubly robust MF, whose steps are gradient passes of
-their own (csrc/invpref_macr.hip, csrc/invpref_lintrans.hip, csrc/invpref_cause.hip, csrc/invpref_bpr.hip, csrc/invpref_dr.hip).
+their own (csrc/invpref_macr.hip, csrc/invpref_lintrans.hip, csrc/invpref_cause.hip, csrc/invpref_bpr.hip, csrc/invpref_dr.hip),
+and sampled-softmax MF (csrc/invpref_ssm.hip).
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -1579,6 +1580,136 @@ class BPRTrainManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
                               self.seed, batch_cap=B)
         index = ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd)
         return self._caller_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), neg, index, None)
+
+
+# ------------------------------------------------------------------------------------------------ sampled-softmax MF
+class SSMTrainManager(_StagedRunMixin, _WholePassMixin, BasicImplicitTrainManager):
+    """Sampled-softmax MF on a plain PureMatrixFactorization: the softmax loss over a positive and M sampled negatives
+        loss = mean_p w_p (logsumexp(x_p+, x_p0 .. x_pM-1) - x_p+) + L2_coe * L2_reg + L1_coe * L1_reg
+        x_p+ = Pu[u_p] . Qi[i_p] / temperature      x_pk = Pu[u_p] . Qi[n_k] / temperature + item_bias[n_k]
+    over the training POSITIVES (u_p, i_p); the M negatives n_k are drawn per step on the device and SHARED by all positions of
+    the step (include/invpref_ssm.h states the loss, the accidental-hit mask and the draw rule).  BasicImplicitTrainManager's
+    signature plus keyword-only arguments:
+
+    n_neg        M, the negatives of a step
+    temperature  tau > 0
+    beta         the negatives are drawn with probability q proportional to (training count + 1) ** beta; 0: uniformly
+    correct      add the sampling correction -log(n_neg q) to the negatives' logits (the importance-sampling estimate of the
+                 full-catalogue softmax); False: plain sampled softmax, which penalises what the proposal draws often
+    proposal     an explicit (cum, item_bias) in the form of ops.ssm_proposal (either may be None) instead of beta / correct
+    seed         names the trajectory: with the global step counter `step_id` it keys every draw, so the same seed gives the
+                 same bits whatever the run lengths, with graphs or without
+    weights      one fp32 weight per positive (per row of training_data, or per kept row)
+
+    Rows of training_data with score <= 0 are dropped at construction (`n_dropped`); the static minibatches are taken over the
+    positives in file order, and each one's inverted index (ops.ssm_index) is built once.  A staging row of _StagedRunMixin is
+    the step's M negatives: before a run of epochs is enqueued its steps are named step_id + 0, 1, ... and ONE ops.ssm_draw
+    launch fills their rows; the pass (ops.ssm_grad, csrc/invpref_ssm.hip) reads its row when it runs, so whole epochs
+    replay as graphs with new negatives.  A caller's minibatch (train_a_batch) is one step under the next step id.  Single
+    process."""
+    _SINGLE = ('sampled-softmax MF runs in a single process (a sharded form would all-reduce the summed gradient of both '
+               'tables; not implemented)')
+    _lazy_adam_unsupported = ('the sampled-softmax pass stores zeros to every idle row and Adam runs over the whole tables: a '
+                              'lazy form would update the rows the step\'s positives and negatives touch (a follow-up)')
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, n_neg: int = 256,
+                 temperature: float = 1.0, beta: float = 0.0, correct: bool = True, proposal=None, seed: int = 0, weights=None,
+                 rank=None, world_size=None, process_group=None):
+        self._require_single_process(world_size)
+        if not 1 <= int(n_neg) <= _capi.SSM_MAX_NEG:
+            raise ValueError(f'n_neg must lie in [1, {_capi.SSM_MAX_NEG}], got {n_neg}')
+        if not (float(temperature) > 0.0 and np.isfinite(float(temperature))):
+            raise ValueError(f'temperature must be a positive finite number, got {temperature}')
+        keep = training_data[:, 2] > 0
+        self.n_dropped = int(training_data.shape[0] - int(keep.sum()))
+        if self.n_dropped == training_data.shape[0]:
+            raise ValueError('sampled softmax trains on positives: training_data has no row with a score > 0')
+        positives = training_data[keep]
+        super().__init__(model, evaluator, device, positives, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
+        I, dev = model.item_num, self.device
+        self.n_neg, self.temperature, self.beta, self.correct = int(n_neg), float(temperature), float(beta), bool(correct)
+        if proposal is None:
+            i = positives[:, 1].cpu().numpy().astype(np.int64)
+            counts = np.bincount(i[(i >= 0) & (i < I)], minlength=I)
+            proposal = ops.ssm_proposal(counts, self.beta, self.n_neg, self.correct)
+        cum, bias = proposal
+        self._cum = None if cum is None else torch.as_tensor(cum).detach().reshape(-1).to(torch.int32).contiguous().to(dev)
+        self._bias = None if bias is None else torch.as_tensor(bias).detach().reshape(-1).to(torch.float32).contiguous().to(dev)
+        for t, what in ((self._cum, 'cum'), (self._bias, 'item_bias')):
+            if t is not None and t.numel() != I:
+                raise ValueError(f'proposal: {what} holds {t.numel()} entries for {I} items')
+        self._weights = None
+        if weights is not None:
+            w = torch.as_tensor(weights).detach().reshape(-1).to(torch.float32)
+            if w.numel() == training_data.shape[0]:
+                w = w[keep.to(w.device)]
+            if w.numel() != self.n_total:
+                raise ValueError(f'weights holds {w.numel()} values for {training_data.shape[0]} rows / {self.n_total} positives')
+            self._weights = w.contiguous().to(dev)
+        self.seed, self.step_id = int(seed), 0
+        self._caller = None         # train_a_batch: (users, items, negatives, index) of the caller's minibatch
+        self._pos_index = None      # per static minibatch: ops.ssm_index of its positives
+        self._ws = ops.Workspace(dev)
+        self._ws.get(max(self._workspace_bytes(min(batch_size, self.n_total)), 16))   # sized once: capturable launches
+        self._init_staging(self.n_neg)
+
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model
+        return ops.ssm_workspace_bytes(m.user_num, m.item_num, batch, self.n_neg, m.factor_num)
+
+    def _staging_resized(self, rows: int) -> None:
+        self._step_ramp = torch.arange(rows, dtype=torch.int64, device=self.device)
+        self._step_ids = torch.zeros(rows, dtype=torch.int64, device=self.device)
+
+    def _raw_setup(self):
+        super()._raw_setup()
+        if self._pos_index is None:
+            m = self.model
+            self._pos_index = [ops.ssm_index(b.users, b.items, m.user_num, m.item_num) for b in self._raw_batches]
+
+    def _stage_draws(self, n: int) -> None:
+        steps = n * self.batch_num
+        torch.add(self._step_ramp[:steps], self.step_id, out=self._step_ids[:steps])
+        ops.ssm_draw(self._step_ids[:steps], self.model.item_num, cum=self._cum, seed=self.seed, out=self._staged[:steps])
+
+    def _draws_consumed(self, steps: int) -> None:
+        self.step_id += steps
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        if k is None:
+            users, items, neg, index = self._caller
+            w = None
+        else:
+            b, w = self._raw_batches[k], self._weights
+            neg, index = self._staged[self._loss_slot * self.batch_num + k], self._pos_index[k]
+            w = None if w is None else w[b.lo:b.lo + b.n]
+        st = self.state
+        ops.ssm_grad(st.p_views[0], st.p_views[1], users, items, neg, index, self.temperature, self.L2_coe, self.L1_coe,
+                     st.g_views[0], st.g_views[1], losses6[:4], weights=w, item_bias=self._bias, workspace=self._ws)
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """one step on caller tensors: the rows with a score > 0 are the positives (weight 1), the negatives are drawn under
+        the next step id, this minibatch's index is built here"""
+        dev, m = self.device, self.model
+        keep = batch_scores_tensor.detach().reshape(-1).to(dev) > 0
+        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
+        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
+        B = ud.numel()
+        if B == 0:
+            raise ValueError('sampled softmax trains on positives: the minibatch has no row with a score > 0')
+        neg = ops.ssm_draw(torch.full((1,), self.step_id, dtype=torch.int64, device=dev), m.item_num, self.n_neg, cum=self._cum,
+                           seed=self.seed)[0]
+        self._ws.get(max(self._workspace_bytes(B), 16))
+        self._caller = (ud, vd, neg, ops.ssm_index(ud, vd, m.user_num, m.item_num))
+        try:
+            out = self._batch_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), None, lambda: None)
+        finally:
+            self._caller = None
+        self.step_id += 1
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ doubly robust MF

@@ -25,6 +25,7 @@ from . import torch_ops_catalog  # noqa: F401  (the catalogue metrics' fragment:
 from . import torch_ops_rank_stats  # noqa: F401  (weighted / grouped rank metrics and bootstrap sums: their fragment)
 from . import torch_ops_bpr  # noqa: F401  (BPR-MF's fragment: torch.ops.invpref.bpr_draw, bpr_grad_)
 from . import torch_ops_dr  # noqa: F401  (doubly robust MF's fragment: torch.ops.invpref.dr_draw, dr_grad_)
+from . import torch_ops_ssm  # noqa: F401  (sampled-softmax MF's fragment: torch.ops.invpref.ssm_draw, ssm_grad_)
 from . import torch_ops_als  # noqa: F401  (WMF by alternating least squares: torch.ops.invpref.als_gram, als_solve_, als_objective)
 from . import torch_ops_segment_rank  # noqa: F401  (explicit evaluation's ranks: torch.ops.invpref.segment_ranks, auc_pairs)
 from . import torch_ops_key_sort  # noqa: F401  (the library's own sort: torch.ops.invpref.sort_keys_, auc_sorted)
@@ -1200,6 +1201,94 @@ def dr_grad(form, params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor
                          losses5, weights, *grads4, what='observed rows')
     _o().dr_grad_(DR_FORMS[form] if isinstance(form, str) else int(form), *params4, users, items, scores, weights, draw_users,
                   draw_items, index, float(L2_coe), float(L1_coe), *grads4, losses5, ws)
+
+
+# ---- sampled-softmax MF (include/invpref_ssm.h, csrc/invpref_ssm.hip)
+def ssm_proposal(item_counts, beta: float, n_neg: int, correct: bool = True):
+    """The proposal of the shared negatives, q proportional to (count + 1) ** beta formed in float64, as what ssm_draw and
+    ssm_grad take: -> (cum, item_bias).  cum: the int32 [item_num] table of cumulative thresholds whose bits are read unsigned,
+    cum[j] = min(floor(2^32 sum_{t <= j} q_t), 2^32 - 1) (include/invpref_ssm.h), or None for beta == 0 (the uniform draw);
+    item_bias: fp32 [item_num], -log(n_neg q) -- the sampling correction that makes the sum over the negatives an
+    importance-sampling estimate of the full-catalogue partition sum -- or None when `correct` is false.  Both on the device
+    of item_counts if it is a tensor, else on the CPU."""
+    import numpy as np
+    dev = item_counts.device if isinstance(item_counts, torch.Tensor) else torch.device('cpu')
+    cnt = (item_counts.detach().cpu().numpy() if isinstance(item_counts, torch.Tensor) else np.asarray(item_counts))
+    cnt = cnt.reshape(-1).astype(np.float64)
+    if cnt.size < 1 or int(n_neg) < 1:
+        raise InvPrefError('ssm_proposal: item_counts and n_neg must not be empty')
+    q = (cnt + 1.0) ** float(beta)
+    q = q / q.sum()
+    cum = None
+    if float(beta) != 0.0:
+        t = np.minimum(np.floor(np.cumsum(q) * 4294967296.0), 4294967295.0).astype(np.uint64)
+        cum = torch.from_numpy(t.astype(np.uint32).view(np.int32).copy()).to(dev)
+    bias = torch.from_numpy((-np.log(int(n_neg) * q)).astype(np.float32)).to(dev) if correct else None
+    return cum, bias
+
+
+def ssm_draw(step_id: torch.Tensor, item_num: int, n_neg: Optional[int] = None, cum: Optional[torch.Tensor] = None,
+             seed: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The shared negatives of a run of steps in ONE launch.  Step s draws under the name step_id[s] (int64: a global step
+    counter, distinct for every step ever issued).  -> neg int32 [steps, n_neg], written into `out` if given (then nothing is
+    allocated: capturable; out may be rows of a wider buffer, whose other entries stay).  The draw rule is stated in
+    include/invpref_ssm.h: word k & 3 of Philox4x32-10 keyed by seed with the counter (k >> 2, 0, step_id); the item is
+    (word * item_num) >> 32, or, with cum (ssm_proposal), the number of thresholds <= word.  With replacement, no rejection."""
+    _gpu(step_id, cum, out)
+    if out is None:
+        if n_neg is None:
+            raise InvPrefError('ssm_draw: give n_neg or out=neg')
+        out = torch.empty(step_id.numel(), int(n_neg), dtype=torch.int32, device=step_id.device)
+    _o().ssm_draw(step_id, cum, int(item_num), _seed64(seed), out)
+    return out
+
+
+def ssm_workspace_bytes(user_num: int, item_num: int, batch: int, n_neg: int, factor_num: int) -> int:
+    """one row and one record per position, the column pass's segment partials, float64 partials and chunk slots of one
+    gradient pass -- no [batch, n_neg] array: a function of the sizes alone, non-decreasing in each; 0: not taken"""
+    return int(_capi.lib().invpref_ssm_workspace_bytes(int(user_num), int(item_num), int(batch), int(n_neg), int(factor_num)))
+
+
+def ssm_geometry(batch: int, n_neg: int):
+    """(segments, positions per segment) of the column pass over `batch` positions and `n_neg` negatives; the last segment
+    holds batch - (segments - 1) * positions per segment.  (0, 0): sizes not taken"""
+    rows = int(_capi.lib().invpref_ssm_segment_rows(int(batch), int(n_neg)))
+    return ((int(batch) + rows - 1) // rows, rows) if rows else (0, 0)
+
+
+def ssm_index(users: torch.Tensor, pos_items: torch.Tensor, user_num: int, item_num: int) -> torch.Tensor:
+    """The inverted index of a step's B positives, int32 [3, 2 B, 2], as ssm_grad takes it: list 0 the positions by user row,
+    list 2 by positive item row (step_index's two lists with no drawn pairs: their half is filed under the sentinel, like a
+    position with an id outside its table), list 1 sentinel entries only.  The negatives need no index.  Allocates (step_index):
+    call it outside a graph capture -- a manager's minibatches are static, so it builds each one's once."""
+    B, dev = users.numel(), users.device
+    none = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    two = step_index(users, pos_items, none, none, user_num, item_num)
+    out = torch.full((3, 2 * B, 2), -1, dtype=torch.int32, device=dev)
+    out[0], out[2] = two[0], two[1]
+    return out
+
+
+def ssm_grad(user_table: torch.Tensor, item_table: torch.Tensor, users: torch.Tensor, pos_items: torch.Tensor, neg: torch.Tensor,
+             index: torch.Tensor, temperature: float, L2_coe: float, L1_coe: float, grad_user: torch.Tensor,
+             grad_item: torch.Tensor, losses4: torch.Tensor, weights: Optional[torch.Tensor] = None,
+             item_bias: Optional[torch.Tensor] = None, workspace: Optional[Workspace] = None) -> None:
+    """The gradient pass of one sampled-softmax step over the positives (users, pos_items: int64 [B]; optional weights fp32
+    [B]) and the M negatives they share (neg int32 [M]; optional item_bias fp32 [item_num] added to the negatives' logits):
+    loss = mean_p w_p (logsumexp(x_p+, x_p0 .. x_pM-1) - x_p+) + L2_coe L2_reg + L1_coe L1_reg with x = Pu[u] . Qi[.] /
+    temperature, a negative equal to the row's positive masked (include/invpref_ssm.h).  index: ssm_index of the positives.
+    OVERWRITES every row of grad_user / grad_item (idle rows get zeros) and losses4 = (score_loss, L2_reg, L1_reg, loss).  No
+    [B, M] array is formed.  Bitwise reproducible, no float atomics, no host sync (capturable once the workspace is sized; a
+    replay reads ids, negatives, weights, bias and index as they are then).  A position with an id outside its table is
+    skipped, a negative outside the table (-1 included) is masked for every row, and either makes the four losses NaN."""
+    _gpu(users, pos_items, neg, index, grad_user, grad_item, losses4, weights, item_bias, user_table, item_table)
+    nbytes = ssm_workspace_bytes(user_table.shape[0], item_table.shape[0], users.numel(), neg.numel(), user_table.shape[1])
+    if nbytes == 0:
+        raise InvPrefError(f'ssm_grad: sizes outside the kernels\' range (tables {tuple(user_table.shape)} / '
+                           f'{tuple(item_table.shape)}, {users.numel()} positives, {neg.numel()} negatives)')
+    ws = (workspace or Workspace(user_table.device)).get(nbytes)
+    _o().ssm_grad_(user_table, item_table, users, pos_items, neg, weights, item_bias, float(temperature), index, float(L2_coe),
+                   float(L1_coe), grad_user, grad_item, losses4, ws)
 
 
 # ---- WMF by alternating least squares (include/invpref_als.h, csrc/invpref_als.hip)
