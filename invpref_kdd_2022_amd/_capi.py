@@ -106,7 +106,8 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 # robust MF's pair sampler and gradient pass (csrc/invpref_dr.hip), the segment ranks and AUC pair counts of explicit evaluation
 # (csrc/invpref_segment_rank.hip), WMF by alternating least squares: the Gram matrix, the exact row solves and the objective
 # (csrc/invpref_als.hip), the keys-only radix sort and the sort-based AUC (csrc/invpref_key_sort.hip), sampled-softmax MF's
-# shared-negative sampler and gradient pass (csrc/invpref_ssm.hip).
+# shared-negative sampler and gradient pass (csrc/invpref_ssm.hip), LightGCN's propagation and ego regulariser
+# (csrc/invpref_lgcn.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
@@ -146,6 +147,9 @@ KEY_SORT_TILE, AUC_SORT_MIN = KEY_SORT_DEFINES['KEY_SORT_TILE'], KEY_SORT_DEFINE
 SSM_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_ssm.h')
 SSM_SIGNATURES, SSM_DEFINES = _read_header(SSM_HEADER_PATH)
 SSM_MAX_NEG, SSM_MAX_STEPS, SSM_MAX_BATCH = (SSM_DEFINES['SSM_' + n] for n in ('MAX_NEG', 'MAX_STEPS', 'MAX_BATCH'))
+LGCN_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_lgcn.h')
+LGCN_SIGNATURES, LGCN_DEFINES = _read_header(LGCN_HEADER_PATH)
+LGCN_PIECE, LGCN_MAX_LAYERS = LGCN_DEFINES['LGCN_PIECE'], LGCN_DEFINES['LGCN_MAX_LAYERS']
 CAUSE_MODE_ITEM, CAUSE_MODE_USER =CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 # (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
 EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
@@ -160,7 +164,7 @@ EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_H
                  (SEGMENT_RANK_HEADER_PATH, 'SEGMENT_RANK_SIGNATURES', 'SEGMENT_RANK_DEFINES'),
                  (ALS_HEADER_PATH, 'ALS_SIGNATURES', 'ALS_DEFINES'),
                  (KEY_SORT_HEADER_PATH, 'KEY_SORT_SIGNATURES', 'KEY_SORT_DEFINES'),
-                 (SSM_HEADER_PATH, 'SSM_SIGNATURES', 'SSM_DEFINES'))
+                 (SSM_HEADER_PATH, 'SSM_SIGNATURES', 'SSM_DEFINES'), (LGCN_HEADER_PATH, 'LGCN_SIGNATURES', 'LGCN_DEFINES'))
 
 _lib = None
 

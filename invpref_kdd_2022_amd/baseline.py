@@ -1,7 +1,7 @@
 """PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF,
 CVIB-MF and fairness-MF; and MACR-MF, LinearTrans-MF, CausE, BPR-MF and doubly robust MF, whose steps are gradient passes of
 their own (csrc/invpref_macr.hip, csrc/invpref_lintrans.hip, csrc/invpref_cause.hip, csrc/invpref_bpr.hip, csrc/invpref_dr.hip),
-and sampled-softmax MF (csrc/invpref_ssm.hip).
+sampled-softmax MF (csrc/invpref_ssm.hip), and LightGCN, whose propagation is csrc/invpref_lgcn.hip and whose step is BPR's.
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -1494,25 +1494,13 @@ class CausEExplicitTrainManager(_CausEManagerMixin, BasicExplicitTrainManager):
 
 
 # ------------------------------------------------------------------------------------------------ BPR-MF
-class BPRTrainManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
-    """BPR-MF (Rendle et al., UAI 2009) on a plain PureMatrixFactorization: the pairwise ranking loss
-        loss = mean_p w_p (-log sigmoid(Pu[u_p] . Qi[i_p] - Pu[u_p] . Qi[j_p])) + L2_coe * L2_reg + L1_coe * L1_reg
-    over the training POSITIVES (u_p, i_p), each with a negative j_p drawn per step on the device, uniformly over the items
-    outside the user's exclusion list (include/invpref_bpr.h states the loss and the draw rule).  BasicImplicitTrainManager's
-    signature plus three keyword-only arguments:
-
-    seed      names the trajectory: with the global step counter `step_id` it keys every draw, so the same seed gives the same
-              bits whatever the run lengths, with graphs or without
-    weights   one fp32 weight per positive (per row of training_data, or per kept row), e.g. the inverse propensities of
-              ops.count_propensity: IPS-weighted BPR
-    exclude   a CSR (indptr [user_num + 1], indices) of the items never drawn for a user; default: the user's training positives
-
-    Rows of training_data with score <= 0 are dropped at construction (`n_dropped`); the static minibatches are taken over the
-    positives in file order.  The device-drawn step of _DeviceDrawnMixin on ops.bpr_draw and ops.bpr_grad
-    (csrc/invpref_bpr.hip); a staging row holds the step's users, then its negatives.  Single process."""
-    _SINGLE = 'BPR runs in a single process (a sharded form would all-reduce the summed gradient of both tables; not implemented)'
-    _lazy_adam_unsupported = ('the BPR pass stores zeros to every idle row and Adam runs over the whole tables: a lazy form '
-                              'would update the rows the step\'s triplets touch (a follow-up)')
+class _TripletDrawnManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
+    """What the managers share that train on (user, positive item, negative item drawn on the device) triplets -- BPR-MF and
+    LightGCN: BasicImplicitTrainManager's signature plus `seed`, `weights` and `exclude` (BPRTrainManager states them), the
+    positives kept at construction, the exclusion lists, the draw launch (ops.bpr_draw), the staging rows (the step's users,
+    then its negatives) and train_a_batch on caller tensors.  A manager supplies _SINGLE, _lazy_adam_unsupported,
+    _workspace_bytes(), _own_pass() and, for what its pass needs beside the tables, _prepare_pass(positives), called once the
+    engine stands and before the workspace is sized."""
 
     def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
                  evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, seed: int = 0,
@@ -1542,11 +1530,11 @@ class BPRTrainManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
             if w.numel() != self.n_total:
                 raise ValueError(f'weights holds {w.numel()} values for {training_data.shape[0]} rows / {self.n_total} positives')
             self._weights = w.contiguous().to(dev)
+        self._prepare_pass(positives)
         self._init_device_draws(seed)
 
-    def _workspace_bytes(self, batch: int) -> int:
-        m = self.model
-        return ops.bpr_workspace_bytes(m.user_num, m.item_num, batch, m.factor_num)
+    def _prepare_pass(self, positives: torch.Tensor) -> None:
+        """what the pass needs beside the tables, from the kept positives"""
 
     def _row_weights(self):
         return self._weights
@@ -1560,11 +1548,6 @@ class BPRTrainManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
     def _draw_run(self, steps: int) -> None:
         ops.bpr_draw(self.users_tensor, self._step_lo[:steps], self._step_n[:steps], self._step_ids[:steps], self._excl,
                      self.model.item_num, self.seed, out=(self._draws[:steps, 1], self.n_forced[:steps]))
-
-    def _own_pass(self, users, items, scores, draws, index, weights, losses6: torch.Tensor) -> None:
-        st = self.state     # (draws[-1]: the negatives, of a staging row and of a caller's step, which stages them alone)
-        ops.bpr_grad(st.p_views[0], st.p_views[1], users, items, draws[-1], index, self.L2_coe, self.L1_coe, st.g_views[0],
-                     st.g_views[1], losses6[:4], weights=weights, workspace=self._ws)
 
     def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
         """one step on caller tensors: the rows with a score > 0 are the positives (weight 1), their negatives are drawn under
@@ -1580,6 +1563,172 @@ class BPRTrainManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
                               self.seed, batch_cap=B)
         index = ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd)
         return self._caller_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), neg, index, None)
+
+
+class BPRTrainManager(_TripletDrawnManager):
+    """BPR-MF (Rendle et al., UAI 2009) on a plain PureMatrixFactorization: the pairwise ranking loss
+        loss = mean_p w_p (-log sigmoid(Pu[u_p] . Qi[i_p] - Pu[u_p] . Qi[j_p])) + L2_coe * L2_reg + L1_coe * L1_reg
+    over the training POSITIVES (u_p, i_p), each with a negative j_p drawn per step on the device, uniformly over the items
+    outside the user's exclusion list (include/invpref_bpr.h states the loss and the draw rule).  BasicImplicitTrainManager's
+    signature plus three keyword-only arguments:
+
+    seed      names the trajectory: with the global step counter `step_id` it keys every draw, so the same seed gives the same
+              bits whatever the run lengths, with graphs or without
+    weights   one fp32 weight per positive (per row of training_data, or per kept row), e.g. the inverse propensities of
+              ops.count_propensity: IPS-weighted BPR
+    exclude   a CSR (indptr [user_num + 1], indices) of the items never drawn for a user; default: the user's training positives
+
+    Rows of training_data with score <= 0 are dropped at construction (`n_dropped`); the static minibatches are taken over the
+    positives in file order.  The device-drawn step of _DeviceDrawnMixin on ops.bpr_draw and ops.bpr_grad
+    (csrc/invpref_bpr.hip); a staging row holds the step's users, then its negatives.  Single process."""
+    _SINGLE = 'BPR runs in a single process (a sharded form would all-reduce the summed gradient of both tables; not implemented)'
+    _lazy_adam_unsupported = ('the BPR pass stores zeros to every idle row and Adam runs over the whole tables: a lazy form '
+                              'would update the rows the step\'s triplets touch (a follow-up)')
+
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model
+        return ops.bpr_workspace_bytes(m.user_num, m.item_num, batch, m.factor_num)
+
+    def _own_pass(self, users, items, scores, draws, index, weights, losses6: torch.Tensor) -> None:
+        st = self.state     # (draws[-1]: the negatives, of a staging row and of a caller's step, which stages them alone)
+        ops.bpr_grad(st.p_views[0], st.p_views[1], users, items, draws[-1], index, self.L2_coe, self.L1_coe, st.g_views[0],
+                     st.g_views[1], losses6[:4], weights=weights, workspace=self._ws)
+
+
+# ------------------------------------------------------------------------------------------------ LightGCN
+class LightGCNMatrixFactorization(nn.Module):
+    """LightGCN (He et al., SIGIR 2020): the ego tables user_emb / item_emb (initialised as PureMF's) and the FINAL tables
+        (F_user; F_item) = (1 / (K + 1)) sum_{k = 0 .. K} A^k (user_emb; item_emb),   K = n_layers,
+    A the symmetrically normalised user-item graph handed in by set_graph() (ops.lgcn_graph; csrc/invpref_lgcn.hip).  A pair is
+    scored by sigmoid(F_user[u] . F_item[i]).
+
+    Not a PureMatrixFactorization: the evaluators must not take the ego tables for ranking tables.  They rank through rank_fn()
+    / truth_rank_fn(), which are ops.predict_topk / ops.truth_ranks on final_tables() -- no score matrix.
+
+    final_tables() keeps its result and recomputes it when set_graph() or touch() was called since, or when the ego parameters
+    were replaced or written in place through torch (their data pointers and torch version counters are compared).  The
+    kernels of this package write the tables through raw pointers, which torch's counters do not see: LightGCNTrainManager
+    calls touch() behind every run of epochs and every train_a_batch; whoever else writes the tables that way calls it too.
+    The result is written into the same two buffers every time, so a pair returned earlier follows the model."""
+    implicit = True
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int, n_layers: int = 3):
+        super().__init__()
+        if not 0 <= int(n_layers) <= _capi.LGCN_MAX_LAYERS:
+            raise ValueError(f'n_layers must lie in 0 .. {_capi.LGCN_MAX_LAYERS}')
+        self.user_num, self.item_num, self.factor_num, self.n_layers = user_num, item_num, factor_num, int(n_layers)
+        self.user_emb = nn.Embedding(user_num, factor_num)
+        self.item_emb = nn.Embedding(item_num, factor_num)
+        nn.init.normal_(self.user_emb.weight, std=0.01)
+        nn.init.normal_(self.item_emb.weight, std=0.01)
+        self.graph = None
+        self._changes, self._final, self._final_key, self._ws = 0, None, None, None
+
+    def tables(self):
+        """the EGO pair, the flat state of a manager (not what ranks: final_tables())"""
+        return [self.user_emb.weight, self.item_emb.weight]
+
+    def set_graph(self, graph) -> None:
+        if (graph.user_num, graph.item_num) != (self.user_num, self.item_num):
+            raise ValueError(f'a graph of {graph.user_num} x {graph.item_num} for tables of {self.user_num} x {self.item_num}')
+        self.graph = graph
+        self.touch()
+
+    def touch(self) -> None:
+        """the ego tables were written behind torch's back: the next final_tables() propagates again"""
+        self._changes += 1
+
+    def final_tables(self):
+        """(F_user, F_item), detached; see the class docstring for when they are recomputed"""
+        if self.graph is None:
+            raise RuntimeError('LightGCNMatrixFactorization: set_graph(ops.lgcn_graph(...)) first')
+        P, Q = self.user_emb.weight, self.item_emb.weight
+        key = (self._changes, P.data_ptr(), Q.data_ptr(), P._version, Q._version)
+        if key != self._final_key:
+            if self.graph.device != P.device:
+                self.graph = self.graph.to(P.device)
+            if self._final is None or self._final[0].device != P.device:
+                self._final = (torch.empty_like(P.detach()), torch.empty_like(Q.detach()))
+                self._ws = ops.Workspace(P.device)
+            ops.lgcn_propagate(self.graph, P.detach().contiguous(), Q.detach().contiguous(), self.n_layers, out=self._final,
+                               workspace=self._ws)
+            self._final_key = key
+        return self._final
+
+    def predict(self, users_id):
+        """sigmoid(F_user[users] @ F_item^T) -> fp32 [n, item_num]"""
+        F = self.final_tables()
+        return ops.predict(F[0], F[1], _user_ids(users_id, F[0]), True)
+
+    def rank_fn(self):
+        """ImplicitTestManager's fused route: f(users, k, mask, highlight, truth) -> (items, scores, hits), ops.predict_topk on
+        final_tables() as they are when rank_fn() is called"""
+        F = self.final_tables()
+        return lambda users, k, mask, highlight, truth: ops.predict_topk(F[0], F[1], users, k, True, mask=mask,
+                                                                         highlight=highlight, truth=truth)
+
+    def truth_rank_fn(self):
+        """ImplicitRankTestManager's fused route: f(users, truth, mask, highlight) -> int32 ranks, ops.truth_ranks on
+        final_tables()"""
+        F = self.final_tables()
+        return lambda users, truth, mask, highlight: ops.truth_ranks(F[0], F[1], users, truth, True, mask=mask,
+                                                                     highlight=highlight)
+
+    def recommend(self, users_id, k: int, exclude=None, highlight=None):
+        """Each user's top-k items by the scores of predict() (InvPrefImplicit.recommend), on final_tables()"""
+        F = self.final_tables()
+        return ops.recommend(F[0], F[1], users_id, k, exclude, highlight)
+
+
+class LightGCNTrainManager(_TripletDrawnManager):
+    """LightGCN trained with BPR: BPRTrainManager's loss with the scores taken on the model's FINAL tables and the regulariser
+    on its EGO tables,
+        loss = mean_p w_p (-log sigmoid(F_u[u_p] . F_i[i_p] - F_u[u_p] . F_i[j_p])) + L2_coe * L2_reg + L1_coe * L1_reg,
+    BPRTrainManager's signature (seed, weights, exclude), draws, staging rows and run index.  The graph is built from the kept
+    positives at construction (ops.lgcn_graph: the distinct in-range pairs) and handed to the model.  One step is four enqueued
+    calls, all capturable: ops.lgcn_propagate (ego -> F), ops.bpr_grad on F without a regulariser (-> GF), ops.lgcn_propagate
+    (GF -> the ego gradient: the operator is its own adjoint), ops.lgcn_reg into the same gradient and losses; then the
+    engine's dense / ranged Adam.  F, GF and the workspace are sized once at construction.  Single process."""
+    _SINGLE = ('LightGCN runs in a single process (a sharded form would exchange every layer\'s tables between the ranks; '
+               'not implemented)')
+    _lazy_adam_unsupported = ('lazy Adam updates the rows a minibatch names, but the propagation reaches every row: the '
+                              'gradient of the ego tables is dense')
+
+    def _prepare_pass(self, positives: torch.Tensor) -> None:
+        m, dev = self.model, self.device
+        u, i = positives[:, 0].cpu().to(torch.int64), positives[:, 1].cpu().to(torch.int64)
+        ok = (u >= 0) & (u < m.user_num) & (i >= 0) & (i < m.item_num)
+        self.graph = ops.lgcn_graph(u[ok], i[ok], m.user_num, m.item_num, device=dev)
+        m.set_graph(self.graph)
+        shape = lambda rows: torch.zeros(rows, m.factor_num, dtype=torch.float32, device=dev)   # noqa: E731
+        self._F = (shape(m.user_num), shape(m.item_num))       # the final tables of the step
+        self._GF = (shape(m.user_num), shape(m.item_num))      # the gradient of the final tables
+
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model     # (the four calls of a step follow each other on one stream and carry nothing in the workspace)
+        sizes = (ops.bpr_workspace_bytes(m.user_num, m.item_num, batch, m.factor_num),
+                 ops.lgcn_workspace_bytes(self.graph, m.factor_num), ops.lgcn_reg_workspace_bytes(m.user_num, m.item_num))
+        return 0 if 0 in sizes else max(sizes)
+
+    def _own_pass(self, users, items, scores, draws, index, weights, losses6: torch.Tensor) -> None:
+        st, K, F, GF = self.state, self.model.n_layers, self._F, self._GF
+        ops.lgcn_propagate(self.graph, st.p_views[0], st.p_views[1], K, out=F, workspace=self._ws)
+        ops.bpr_grad(F[0], F[1], users, items, draws[-1], index, 0.0, 0.0, GF[0], GF[1], losses6[:4], weights=weights,
+                     workspace=self._ws)
+        ops.lgcn_propagate(self.graph, GF[0], GF[1], K, out=(st.g_views[0], st.g_views[1]), workspace=self._ws)
+        ops.lgcn_reg(users, items, draws[-1], st.p_views[0], st.p_views[1], self.L2_coe, self.L1_coe, st.g_views[0],
+                     st.g_views[1], losses6[:4], workspace=self._ws)
+
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        out = super()._enqueue_epochs(want)
+        self.model.touch()
+        return out
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        try:
+            return super().train_a_batch(batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args)
+        finally:
+            self.model.touch()
 
 
 # ------------------------------------------------------------------------------------------------ sampled-softmax MF

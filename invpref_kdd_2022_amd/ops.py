@@ -29,6 +29,7 @@ from . import torch_ops_ssm  # noqa: F401  (sampled-softmax MF's fragment: torch
 from . import torch_ops_als  # noqa: F401  (WMF by alternating least squares: torch.ops.invpref.als_gram, als_solve_, als_objective)
 from . import torch_ops_segment_rank  # noqa: F401  (explicit evaluation's ranks: torch.ops.invpref.segment_ranks, auc_pairs)
 from . import torch_ops_key_sort  # noqa: F401  (the library's own sort: torch.ops.invpref.sort_keys_, auc_sorted)
+from . import torch_ops_lgcn  # noqa: F401  (LightGCN's fragment: torch.ops.invpref.lgcn_propagate, lgcn_reg_)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -1372,3 +1373,140 @@ def als_csr(users: torch.Tensor, items: torch.Tensor, pref: torch.Tensor, conf: 
         row_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), 0)
         return row_ptr, cols[order].to(torch.int32).contiguous(), conf[order].contiguous(), pref[order].contiguous()
     return one(users, items, int(user_num)), one(items, users, int(item_num))
+
+
+# ---- LightGCN (include/invpref_lgcn.h, csrc/invpref_lgcn.hip)
+class LgcnGraph:
+    """The static graph of ops.lgcn_propagate: both CSRs and both piece plans.  user_side / item_side: the eight tensors of
+    torch_ops_lgcn.SIDE_FIELDS (row_ptr int64 [rows + 1], cols int32, w fp32, piece_row int32, piece_at int64 [pieces + 1],
+    piece_slot int32, cut_row int32, cut_slot int32), `piece` the length the rows were cut at."""
+
+    def __init__(self, user_side, item_side, user_num: int, item_num: int, piece: int):
+        self.user_side, self.item_side = list(user_side), list(item_side)
+        self.user_num, self.item_num, self.piece = int(user_num), int(item_num), int(piece)
+
+    @property
+    def n_edges(self) -> int:
+        return self.user_side[1].numel()
+
+    @property
+    def slots(self):
+        """(user side's, item side's) float64 partial slots: the pieces of their cut rows"""
+        return torch_ops_lgcn.side_counts(self.user_side)[4], torch_ops_lgcn.side_counts(self.item_side)[4]
+
+    @property
+    def device(self):
+        return self.user_side[0].device
+
+    def to(self, device) -> 'LgcnGraph':
+        return LgcnGraph([t.to(device) for t in self.user_side], [t.to(device) for t in self.item_side], self.user_num,
+                         self.item_num, self.piece)
+
+
+def lgcn_pieces(row_ptr, piece: int):
+    """The piece plan of one CSR (numpy int64 row_ptr): a row longer than `piece` entries is cut into consecutive pieces of that
+    length, any other row (an empty one included) is one piece.  -> (piece_row int32, piece_at int64 [pieces + 1], piece_slot
+    int32, cut_row int32, cut_slot int32 [cuts + 1]) as include/invpref_lgcn.h lays them out."""
+    import numpy as np
+    row_ptr = np.asarray(row_ptr, np.int64)
+    rows, piece = len(row_ptr) - 1, int(piece)
+    if piece < 1:
+        raise InvPrefError('lgcn_pieces: a piece holds at least one entry')
+    per_row = np.maximum(1, (np.diff(row_ptr) + piece - 1) // piece)
+    first = np.cumsum(per_row) - per_row
+    piece_row = np.repeat(np.arange(rows, dtype=np.int64), per_row)
+    within = np.arange(len(piece_row), dtype=np.int64) - first[piece_row]
+    piece_at = np.concatenate([row_ptr[piece_row] + within * piece, row_ptr[-1:]])
+    cut = per_row > 1
+    cut_row = np.nonzero(cut)[0]
+    piece_slot = np.full(len(piece_row), -1, np.int32)
+    in_cut = cut[piece_row]
+    piece_slot[in_cut] = np.arange(int(in_cut.sum()), dtype=np.int32)
+    cut_slot = np.concatenate([[0], np.cumsum(per_row[cut_row])]).astype(np.int32)
+    return piece_row.astype(np.int32), piece_at, piece_slot, cut_row.astype(np.int32), cut_slot
+
+
+def lgcn_graph(users, items, user_num: int, item_num: int, weights=None, device=None, piece: Optional[int] = None) -> LgcnGraph:
+    """LightGCN's graph of a list of (user, item) pairs, built once on the host: the DISTINCT pairs are the edges (a pair that
+    occurs twice is one edge), each row's columns ascending, w = fp32(1 / sqrt((double)deg_u (double)deg_i)) on both sides, or
+    `weights` (one value per given pair; of a repeated pair the first occurrence's) for another propagation.  Both CSRs, user
+    rows -> item columns and item rows -> user columns, and both piece plans (lgcn_pieces; piece: INVPREF_LGCN_PIECE unless
+    given).  -> LgcnGraph on `device` (default: the device of `users`; CPU tensors give a CPU graph, which the kernels do not
+    take but tests can read).  Ids outside the tables are refused here, on the host."""
+    import numpy as np
+    src = users
+    u = torch.as_tensor(users).detach().reshape(-1).cpu().numpy().astype(np.int64)
+    i = torch.as_tensor(items).detach().reshape(-1).cpu().numpy().astype(np.int64)
+    U, I = int(user_num), int(item_num)
+    if U < 1 or I < 1 or len(u) != len(i):
+        raise InvPrefError('lgcn_graph: users and items hold one id per pair, the tables at least one row')
+    if len(u) and (u.min() < 0 or u.max() >= U or i.min() < 0 or i.max() >= I):
+        raise InvPrefError('lgcn_graph: an id lies outside its table')
+    keys, first = np.unique(u * I + i, return_index=True)        # by user, then by item
+    eu, ei = keys // I, keys % I
+    deg_u, deg_i = np.bincount(eu, minlength=U), np.bincount(ei, minlength=I)
+    if weights is None:
+        w = (1.0 / np.sqrt(deg_u[eu].astype(np.float64) * deg_i[ei].astype(np.float64))).astype(np.float32)
+    else:
+        w = torch.as_tensor(weights).detach().reshape(-1).cpu().numpy().astype(np.float32)
+        if len(w) != len(u):
+            raise InvPrefError(f'lgcn_graph: {len(w)} weights for {len(u)} pairs')
+        w = w[first]
+    by_item = np.argsort(ei, kind='stable')                     # (stable: the users of an item stay ascending)
+    piece = _capi.LGCN_PIECE if piece is None else int(piece)
+    if device is None:
+        device = src.device if isinstance(src, torch.Tensor) else torch.device('cpu')
+
+    def side(deg, cols, wts):
+        row_ptr = np.zeros(len(deg) + 1, np.int64)
+        np.cumsum(deg, out=row_ptr[1:])
+        arrays = (row_ptr, cols.astype(np.int32), wts) + lgcn_pieces(row_ptr, piece)
+        return [torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in arrays]
+    return LgcnGraph(side(deg_u, ei, w), side(deg_i, eu[by_item], w[by_item]), U, I, piece)
+
+
+def lgcn_workspace_bytes(graph: LgcnGraph, factor_num: int) -> int:
+    """the two ping-pong layer tables and the float64 piece partials of one propagation over `graph`; 0: sizes not taken"""
+    su, si = graph.slots
+    return int(_capi.lib().invpref_lgcn_workspace_bytes(graph.user_num, graph.item_num, int(factor_num), su, si))
+
+
+def lgcn_propagate(graph: LgcnGraph, x_user: torch.Tensor, x_item: torch.Tensor, n_layers: int, out=None,
+                   workspace: Optional[Workspace] = None):
+    """(out_user, out_item) = (1 / (K + 1)) sum_{k = 0 .. K} A^k (x_user; x_item), K = n_layers, over the graph's weighted
+    edges -- LightGCN's final embeddings of the ego tables, and, A being symmetric, the gradient of the ego tables from the
+    gradient of the final ones.  Written into `out` = (out_user, out_item) if given (then, with a sized workspace, nothing is
+    allocated: capturable; a replay reads x as it is then).  The arithmetic is stated in include/invpref_lgcn.h: float64 sums
+    in CSR order, one rounding per stored layer and per update of out.  Bitwise reproducible, no float atomics, no host sync."""
+    _gpu(x_user, x_item, *graph.user_side, *graph.item_side)
+    if out is None:
+        out = (torch.empty_like(x_user), torch.empty_like(x_item))
+    _gpu(*out)
+    nbytes = lgcn_workspace_bytes(graph, x_user.shape[1]) if x_user.dim() == 2 else 0
+    if nbytes == 0:
+        raise InvPrefError(f'lgcn_propagate: sizes outside the kernels\' range (tables {tuple(x_user.shape)} / {tuple(x_item.shape)})')
+    ws = (workspace or Workspace(x_user.device)).get(nbytes)
+    _o().lgcn_propagate(graph.user_side, graph.item_side, x_user, x_item, int(n_layers), out[0], out[1], ws)
+    return out
+
+
+def lgcn_reg_workspace_bytes(user_num: int, item_num: int) -> int:
+    """the two count tables and the float64 partials of lgcn_reg; 0: sizes not taken"""
+    return int(_capi.lib().invpref_lgcn_reg_workspace_bytes(int(user_num), int(item_num)))
+
+
+def lgcn_reg(users: torch.Tensor, pos_items: torch.Tensor, neg: torch.Tensor, ego_user: torch.Tensor, ego_item: torch.Tensor,
+             L2_coe: float, L1_coe: float, grad_user: torch.Tensor, grad_item: torch.Tensor, losses4: torch.Tensor,
+             workspace: Optional[Workspace] = None) -> None:
+    """The ego regulariser of one LightGCN step over the triplets (users int64, pos_items int64, neg int32: [B]), which the BPR
+    pass cannot supply because it sees the propagated tables: BPR's L2_reg / L1_reg taken on the ego tables (include/invpref_lgcn.h).
+    ADDS every gather's (2 L2_coe row + L1_coe sign(row)) / (B D) into grad_user / grad_item, overwrites losses4[1] = L2_reg and
+    losses4[2] = L1_reg, sets losses4[3] = losses4[0] + L2_coe L2_reg + L1_coe L1_reg and leaves losses4[0] alone.  A triplet
+    with an id outside its table (neg = -1 included) is skipped whole and the three values are NaN.  Bitwise reproducible,
+    integer atomics only, no host sync (capturable once the workspace is sized)."""
+    _gpu(users, pos_items, neg, ego_user, ego_item, grad_user, grad_item, losses4)
+    nbytes = lgcn_reg_workspace_bytes(ego_user.shape[0], ego_item.shape[0])
+    if nbytes == 0:
+        raise InvPrefError(f'lgcn_reg: sizes outside the kernels\' range (tables {tuple(ego_user.shape)} / {tuple(ego_item.shape)})')
+    ws = (workspace or Workspace(ego_user.device)).get(nbytes)
+    _o().lgcn_reg_(users, pos_items, neg, ego_user, ego_item, float(L2_coe), float(L1_coe), grad_user, grad_item, losses4, ws)
