@@ -18,6 +18,8 @@ _SSM = ('SSMTrainManager',)
 
 _LGCN = ('LightGCNMatrixFactorization', 'LightGCNTrainManager')
 
+_DICE = ('DICEMatrixFactorization', 'DICETrainManager')
+
 _EVALUATE = ('ExplicitRankTestManager',)
 
 
@@ -26,7 +28,7 @@ def __getattr__(name):   # resolved on first use: importing the package loads ne
         from . import evaluate
         return getattr(evaluate, name)
     if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE or name in _BPR or name in _DR \
-            or name in _ALS or name in _SSM or name in _LGCN:
+            or name in _ALS or name in _SSM or name in _LGCN or name in _DICE:
         from . import baseline
         return getattr(baseline, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

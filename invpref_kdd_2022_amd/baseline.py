@@ -1,7 +1,8 @@
 """PureMF baselines on the same fused HIP step: plain, propensity-weighted (IPS-MF, SNIPS-MF), ExpoMF, WMF,
 CVIB-MF and fairness-MF; and MACR-MF, LinearTrans-MF, CausE, BPR-MF and doubly robust MF, whose steps are gradient passes of
 their own (csrc/invpref_macr.hip, csrc/invpref_lintrans.hip, csrc/invpref_cause.hip, csrc/invpref_bpr.hip, csrc/invpref_dr.hip),
-sampled-softmax MF (csrc/invpref_ssm.hip), and LightGCN, whose propagation is csrc/invpref_lgcn.hip and whose step is BPR's.
+sampled-softmax MF (csrc/invpref_ssm.hip), LightGCN, whose propagation is csrc/invpref_lgcn.hip and whose step is BPR's, and
+DICE, whose popularity-margin draw and four-table pass are csrc/invpref_dice.hip.
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -1729,6 +1730,218 @@ class LightGCNTrainManager(_TripletDrawnManager):
             return super().train_a_batch(batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args)
         finally:
             self.model.touch()
+
+
+# ------------------------------------------------------------------------------------------------ DICE
+DICE_LOSS_KEYS = ('click_loss', 'int_loss', 'con_loss', 'dis', 'L2_reg', 'loss')
+_DICE_LOSS_PICK = (0, 1, 2, 3, 4, 6)        # their places in the pass's losses8 (include/invpref_dice.h)
+
+
+class DICEMatrixFactorization(nn.Module):
+    """DICE (Zheng et al., WWW 2021): an interest pair int_user_emb / int_item_emb and a conformity pair con_user_emb /
+    con_item_emb, all four initialised as PureMF's.  A pair is scored by sigmoid(F_user[u] . F_item[i]) on the FINAL tables,
+
+    rank_by='interest'   the interest pair alone: the paper's choice under intervened test data
+    rank_by='both'       [Iu | Cu] and [Ii | Ci], width 2 factor_num: the click score, interest + conformity; the ranking
+                         kernels take rows of at most INVPREF_MAX_FACTORS floats, so factor_num <= 128
+
+    Not a PureMatrixFactorization: the evaluators rank through rank_fn() / truth_rank_fn(), which are ops.predict_topk /
+    ops.truth_ranks on final_tables() -- no score matrix.  For 'both', final_tables() keeps the concatenation and rebuilds it
+    when touch() was called since, or when the parameters were replaced or written in place through torch (their data pointers
+    and torch version counters are compared), as LightGCNMatrixFactorization does: DICETrainManager calls touch() behind every
+    run of epochs and every train_a_batch, since the kernels write the tables through raw pointers.  The concatenation is
+    written into the same two buffers every time, so a pair returned earlier follows the model."""
+    implicit = True
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int, rank_by: str = 'both'):
+        super().__init__()
+        if rank_by not in ('interest', 'both'):
+            raise ValueError(f"rank_by must be 'interest' or 'both', got {rank_by!r}")
+        if rank_by == 'both' and 2 * int(factor_num) > _capi.DEFINES['MAX_FACTORS']:
+            raise ValueError(f"rank_by='both' ranks rows of 2 factor_num = {2 * int(factor_num)} floats and the ranking kernels "
+                             f"take at most {_capi.DEFINES['MAX_FACTORS']}: factor_num <= {_capi.DEFINES['MAX_FACTORS'] // 2}, "
+                             "or rank_by='interest'")
+        self.user_num, self.item_num, self.factor_num, self.rank_by = user_num, item_num, factor_num, rank_by
+        self.int_user_emb = nn.Embedding(user_num, factor_num)
+        self.int_item_emb = nn.Embedding(item_num, factor_num)
+        self.con_user_emb = nn.Embedding(user_num, factor_num)
+        self.con_item_emb = nn.Embedding(item_num, factor_num)
+        for e in (self.int_user_emb, self.int_item_emb, self.con_user_emb, self.con_item_emb):
+            nn.init.normal_(e.weight, std=0.01)
+        self._changes, self._final, self._final_key = 0, None, None
+
+    def tables(self):
+        """Iu, Ii, Cu, Ci: the flat state of a manager (not what ranks: final_tables())"""
+        return [self.int_user_emb.weight, self.int_item_emb.weight, self.con_user_emb.weight, self.con_item_emb.weight]
+
+    def touch(self) -> None:
+        """the tables were written behind torch's back: the next final_tables() concatenates again"""
+        self._changes += 1
+
+    def final_tables(self):
+        """(F_user, F_item), detached; see the class docstring"""
+        T = self.tables()
+        if self.rank_by == 'interest':
+            return T[0].detach(), T[1].detach()
+        key = (self._changes,) + tuple(x for t in T for x in (t.data_ptr(), t._version))
+        if key != self._final_key:
+            D = self.factor_num
+            if self._final is None or self._final[0].device != T[0].device:
+                self._final = tuple(torch.empty(t.shape[0], 2 * D, dtype=torch.float32, device=t.device) for t in T[:2])
+            for F, a, b in zip(self._final, T[:2], T[2:]):
+                F[:, :D].copy_(a.detach())
+                F[:, D:].copy_(b.detach())
+            self._final_key = key
+        return self._final
+
+    def predict(self, users_id):
+        """sigmoid(F_user[users] @ F_item^T) -> fp32 [n, item_num]"""
+        F = self.final_tables()
+        return ops.predict(F[0], F[1], _user_ids(users_id, F[0]), True)
+
+    def rank_fn(self):
+        """ImplicitTestManager's fused route: f(users, k, mask, highlight, truth) -> (items, scores, hits), ops.predict_topk on
+        final_tables() as they are when rank_fn() is called"""
+        F = self.final_tables()
+        return lambda users, k, mask, highlight, truth: ops.predict_topk(F[0], F[1], users, k, True, mask=mask,
+                                                                         highlight=highlight, truth=truth)
+
+    def truth_rank_fn(self):
+        """ImplicitRankTestManager's fused route: f(users, truth, mask, highlight) -> int32 ranks, ops.truth_ranks on
+        final_tables()"""
+        F = self.final_tables()
+        return lambda users, truth, mask, highlight: ops.truth_ranks(F[0], F[1], users, truth, True, mask=mask,
+                                                                     highlight=highlight)
+
+    def recommend(self, users_id, k: int, exclude=None, highlight=None):
+        """Each user's top-k items by the scores of predict() (InvPrefImplicit.recommend), on final_tables()"""
+        F = self.final_tables()
+        return ops.recommend(F[0], F[1], users_id, k, exclude, highlight)
+
+
+def dice_schedule(epoch: int, margin: float, int_weight: float, con_weight: float, dis_pen: float, margin_decay: float,
+                  loss_decay: float):
+    """(margin, (int_w, con_w, dis_pen)) of epoch `epoch`, counted from 0: margin and the two loss weights decay per epoch"""
+    return margin * margin_decay ** epoch, (int_weight * loss_decay ** epoch, con_weight * loss_decay ** epoch, dis_pen)
+
+
+class DICETrainManager(_TripletDrawnManager):
+    """DICE on a DICEMatrixFactorization: per step, over the training POSITIVES (u_p, i_p), each with a negative j_p drawn on
+    the device CONDITIONED ON THE POSITIVE'S POPULARITY (the popularity-margin sampler),
+        loss = click_loss + int_w * int_loss + con_w * con_loss - dis_pen * dis + L2_coe * L2_reg + L1_coe * L1_reg
+    with the click loss on interest + conformity, the interest loss on the triplets whose negative is the more popular item,
+    the conformity loss following popularity and the discrepancy between the two pairs over the step's distinct rows
+    (include/invpref_dice.h states the terms, the factors and the draw rule).  BPRTrainManager's signature (seed, weights,
+    exclude) plus keyword-only arguments:
+
+    margin, pool     the sampler's popularity margin and the least size of a candidate range
+    int_weight, con_weight, dis_pen   the three coefficients
+    dis_form         'L1' or 'L2': the discrepancy's phi
+    margin_decay, loss_decay   epoch e, counted from the manager's first, uses margin * margin_decay ** e, int_weight *
+                     loss_decay ** e and con_weight * loss_decay ** e
+
+    The per-epoch values of a run's steps are written to device rows (`_step_margin`, `_step_coefs`) before the run is enqueued,
+    next to the step ids; the draw launch and the passes read their rows when they run, so a captured run is replayed at
+    the current values without re-capture.  A caller's step (train_a_batch) runs at the current epoch's.  The popularity
+    arrays are built from the kept positives (ops.dice_popularity).  The device-drawn step of _DeviceDrawnMixin on
+    ops.dice_draw and ops.dice_grad (csrc/invpref_dice.hip); a staging row holds the step's users, then its negatives.  Single
+    process."""
+    _SINGLE = ('DICE runs in a single process (a sharded form would all-reduce the summed gradient of all four tables and the '
+               'counts of distinct rows; not implemented)')
+    _LOSS_KEYS = DICE_LOSS_KEYS
+    _lazy_adam_unsupported = ('the DICE pass stores zeros to every idle row and Adam runs over the whole tables: a lazy form '
+                              'would update the rows the step\'s triplets touch (not built)')
+
+    def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, seed: int = 0,
+                 weights=None, exclude=None, margin: float = 40.0, pool: int = 40, int_weight: float = 0.1,
+                 con_weight: float = 0.1, dis_pen: float = 0.01, dis_form: str = 'L1', margin_decay: float = 0.9,
+                 loss_decay: float = 0.9, rank=None, world_size=None, process_group=None):
+        self._require_single_process(world_size)
+        if not callable(getattr(model, 'tables', None)) or len(model.tables()) != 4:
+            raise TypeError('DICETrainManager needs a model with an interest and a conformity pair (DICEMatrixFactorization)')
+        if dis_form not in ops.DICE_FORMS:
+            raise ValueError(f'dis_form must be one of {sorted(ops.DICE_FORMS)}, got {dis_form!r}')
+        if int(pool) < 1:
+            raise ValueError(f'pool must be at least 1, got {pool}')
+        for name, v in (('margin', margin), ('int_weight', int_weight), ('con_weight', con_weight), ('dis_pen', dis_pen),
+                        ('margin_decay', margin_decay), ('loss_decay', loss_decay)):
+            if not (np.isfinite(float(v)) and float(v) >= 0.0):
+                raise ValueError(f'{name} must be a finite number >= 0, got {v}')
+        self.margin, self.pool, self.dis_form = float(margin), int(pool), dis_form
+        self.int_weight, self.con_weight, self.dis_pen = float(int_weight), float(con_weight), float(dis_pen)
+        self.margin_decay, self.loss_decay = float(margin_decay), float(loss_decay)
+        self._row = self._caller_coefs = None
+        super().__init__(model, evaluator, device, training_data, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
+                         test_begin_epoch, seed=seed, weights=weights, exclude=exclude, rank=rank, world_size=world_size,
+                         process_group=process_group)
+
+    def schedule_of(self, epoch: int):
+        """(margin, (int_w, con_w, dis_pen)) of epoch `epoch`, counted from the manager's first"""
+        return dice_schedule(epoch, self.margin, self.int_weight, self.con_weight, self.dis_pen, self.margin_decay,
+                             self.loss_decay)
+
+    def _prepare_pass(self, positives: torch.Tensor) -> None:
+        self._pop = ops.dice_popularity(positives[:, 1], self.model.item_num, self.device)
+        self._losses8 = torch.zeros(8, dtype=torch.float32, device=self.device)
+        self._loss_pick = torch.tensor(_DICE_LOSS_PICK, dtype=torch.int64, device=self.device)
+
+    def _workspace_bytes(self, batch: int) -> int:
+        m = self.model
+        return ops.dice_workspace_bytes(m.user_num, m.item_num, batch, m.factor_num)
+
+    def _staging_resized(self, rows: int) -> None:
+        super()._staging_resized(rows)
+        self._step_margin = torch.zeros(rows, dtype=torch.float64, device=self.device)
+        self._step_coefs = torch.zeros(rows, 3, dtype=torch.float64, device=self.device)
+
+    def _draw_run(self, steps: int) -> None:
+        # the run's epochs start at epoch_cnt: their margins and coefficients into the steps' rows, then the draw launch
+        sched = [self.schedule_of(self.epoch_cnt + e) for e in range(steps // self.batch_num)]
+        self._step_margin[:steps].copy_(torch.from_numpy(np.repeat([m for m, _ in sched], self.batch_num)))
+        self._step_coefs[:steps].copy_(torch.from_numpy(np.repeat(np.array([c for _, c in sched], np.float64), self.batch_num, 0)))
+        ops.dice_draw(self.users_tensor, self.items_tensor, self._step_lo[:steps], self._step_n[:steps], self._step_ids[:steps],
+                      self._excl, self._pop, self.pool, self._step_margin[:steps], self.seed,
+                      out=(self._draws[:steps, 1], self.n_forced[:steps]))
+
+    def _gradient_pass(self, k, plan, users, items, envs, scores, weights, batch_norm: int, coefs, flags: int,
+                       losses6: torch.Tensor, sched=None) -> None:
+        self._row = None if k is None else self._loss_slot * self.batch_num + k     # the step's row of _step_coefs
+        super()._gradient_pass(k, plan, users, items, envs, scores, weights, batch_norm, coefs, flags, losses6, sched)
+
+    def _own_pass(self, users, items, scores, draws, index, weights, losses6: torch.Tensor) -> None:
+        st = self.state
+        coefs3 = self._caller_coefs if self._row is None else self._step_coefs[self._row]
+        ops.dice_grad(st.p_views, st.g_views, users, items, draws[-1], self._pop[0], index, coefs3, self.dis_form, self.L2_coe,
+                      self.L1_coe, self._losses8, weights=weights, workspace=self._ws)
+        torch.index_select(self._losses8, 0, self._loss_pick, out=losses6)
+
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        out = super()._enqueue_epochs(want)
+        self.model.touch()
+        return out
+
+    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
+        """one step on caller tensors at the current epoch's margin and coefficients: the rows with a score > 0 are the
+        positives (weight 1), their negatives are drawn under the next step id against the manager's exclusion lists and
+        popularity arrays, this minibatch's index is built here"""
+        dev, m = self.device, self.model
+        keep = batch_scores_tensor.detach().reshape(-1).to(dev) > 0
+        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
+        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
+        B = ud.numel()
+        if B == 0:
+            raise ValueError('DICE trains on positives: the minibatch has no row with a score > 0')
+        margin, coefs3 = self.schedule_of(self.epoch_cnt)
+        self._caller_coefs = torch.tensor(coefs3, dtype=torch.float64, device=dev)
+        neg, _ = ops.dice_draw(ud, vd, torch.zeros(1, dtype=torch.int64, device=dev), *self._step_name(B), self._excl, self._pop,
+                               self.pool, torch.full((1,), margin, dtype=torch.float64, device=dev), self.seed, batch_cap=B)
+        index = ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd)
+        try:
+            return self._caller_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), neg, index, None)
+        finally:
+            self._caller_coefs = None
+            m.touch()
 
 
 # ------------------------------------------------------------------------------------------------ sampled-softmax MF

@@ -39,9 +39,14 @@
 //   valid(entry, y, n2)           does the entry count?  y is the position as the index holds it, unclamped
 //   gathers(side, pos), factor(entry, pos)   what a counted entry adds to the destination's count; its partner row's fp32 factor
 //   finish<NC, VEC>(table, row, D, count, l16, acc)   at the end of a destination; table: the destination's own
+//   StartsRows, finish_row<NC, VEC>(table, side, starts, row, D, count, l16, acc)   optional, in finish's place where the
+//                                 policy declares the member type StartsRows: `starts` says that the destination's FIRST
+//                                 entry lies in this chunk -- true in exactly one of the chunks a destination spans, so what a
+//                                 row must receive once whatever its length goes there (DICE's discrepancy gradient)
 //   write_row<NC, VEC>(table, row, D, l16, acc)       static: a finished row into the gradient table (scatter and boundary)
 #pragma once
 #include <algorithm>
+#include <type_traits>
 
 #include "row_pass.hpp"
 
@@ -136,6 +141,12 @@ __device__ __forceinline__ void fma_row(double4_t (&acc)[NC], float k, const flo
     }
 }
 
+// does the policy ask which chunk a destination STARTS in?  (a member type StartsRows: DICE's pass alone)
+template <typename Policy, typename = void>
+struct starts_rows : std::false_type {};
+template <typename Policy>
+struct starts_rows<Policy, std::void_t<typename Policy::StartsRows>> : std::true_type {};
+
 __device__ __forceinline__ int clamp_id(int id, int n) { return min(max(id, 0), n - 1); }
 __device__ __forceinline__ int64_t clamp_id(int64_t id, int n) { return std::min<int64_t>(std::max<int64_t>(id, 0), n - 1); }
 
@@ -165,7 +176,8 @@ __device__ __forceinline__ void chunk_scatter(const Policy &pol, const float *__
     int cur = first, cnt = 0;
     bool cur_head = head0, live = true;
     auto flush = [&](bool head, bool tail) {
-        pol.template finish<NC, VEC>(dtab, cur, D, cnt, l16, acc);
+        if constexpr (starts_rows<Policy>::value) pol.template finish_row<NC, VEC>(dtab, side, !head, cur, D, cnt, l16, acc);
+        else pol.template finish<NC, VEC>(dtab, cur, D, cnt, l16, acc);
         if (!head && !tail) Policy::template write_row<NC, VEC>(gtab, cur, D, l16, acc);
         else slot_store<NC>(slot_of(part, nchunk, Dp, side, c, head ? 0 : 1), Dp, l16, acc);
     };

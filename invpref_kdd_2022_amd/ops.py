@@ -25,6 +25,7 @@ from . import torch_ops_catalog  # noqa: F401  (the catalogue metrics' fragment:
 from . import torch_ops_rank_stats  # noqa: F401  (weighted / grouped rank metrics and bootstrap sums: their fragment)
 from . import torch_ops_bpr  # noqa: F401  (BPR-MF's fragment: torch.ops.invpref.bpr_draw, bpr_grad_)
 from . import torch_ops_dr  # noqa: F401  (doubly robust MF's fragment: torch.ops.invpref.dr_draw, dr_grad_)
+from . import torch_ops_dice  # noqa: F401  (DICE's fragment: torch.ops.invpref.dice_draw, dice_grad_)
 from . import torch_ops_ssm  # noqa: F401  (sampled-softmax MF's fragment: torch.ops.invpref.ssm_draw, ssm_grad_)
 from . import torch_ops_als  # noqa: F401  (WMF by alternating least squares: torch.ops.invpref.als_gram, als_solve_, als_objective)
 from . import torch_ops_segment_rank  # noqa: F401  (explicit evaluation's ranks: torch.ops.invpref.segment_ranks, auc_pairs)
@@ -1202,6 +1203,89 @@ def dr_grad(form, params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor
                          losses5, weights, *grads4, what='observed rows')
     _o().dr_grad_(DR_FORMS[form] if isinstance(form, str) else int(form), *params4, users, items, scores, weights, draw_users,
                   draw_items, index, float(L2_coe), float(L1_coe), *grads4, losses5, ws)
+
+
+# ---- DICE (include/invpref_dice.h, csrc/invpref_dice.hip)
+DICE_FORMS = {'L1': 0, 'L2': 1}
+
+
+def dice_popularity(items, item_num: int, device=None):
+    """The popularity arrays of DICE's draw and pass from the training positives' item ids (any integer array or tensor; ids
+    outside [0, item_num) are not counted): -> (item_count, pop_order, sorted_count), int32 [item_num] each on `device` --
+    item_count the items' occurrences, pop_order the items ascending by (item_count, id), sorted_count = item_count[pop_order]."""
+    import numpy as np
+    ids = (items.detach().cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)).reshape(-1).astype(np.int64)
+    item_num = int(item_num)
+    if item_num < 1 or item_num > 2 ** 31 - 1:
+        raise InvPrefError(f'dice_popularity: item_num must lie in [1, 2^31 - 1], got {item_num}')
+    count = np.bincount(ids[(ids >= 0) & (ids < item_num)], minlength=item_num)
+    if count.max(initial=0) > 2 ** 31 - 1:
+        raise InvPrefError('dice_popularity: an item count beyond int32')
+    order = np.argsort(count, kind='stable')                         # (stable: ties ascending by id)
+    return tuple(torch.from_numpy(a.astype(np.int32)).to(device) for a in (count, order, count[order]))
+
+
+def dice_draw(users: torch.Tensor, pos_items: torch.Tensor, step_lo: torch.Tensor, step_n: torch.Tensor, step_id: torch.Tensor,
+              exclude, popularity, pool: int, step_margin: torch.Tensor, seed: int = 0, batch_cap: Optional[int] = None,
+              out=None):
+    """The popularity-margin negatives (PNSM) of a run of steps in ONE launch.  bpr_draw's arguments plus pos_items (int64,
+    aligned with users), popularity = (item_count, pop_order, sorted_count) as dice_popularity returns them, pool >= 1 and
+    step_margin (float64 [steps], >= 0).  -> (neg int32 [steps, batch_cap], n_forced int32 [steps]), written into `out` =
+    (neg, n_forced) if given (then nothing is allocated: capturable; neg may be rows of a wider buffer).  The draw rule is
+    stated in include/invpref_dice.h: with c the positive's count, the candidates are the items more popular than c + margin
+    or those less popular than c - margin (a coin where both ranges hold at least `pool` items; the whole catalogue where
+    neither does), the first of 15 candidates outside the user's list -- the 15th regardless, counted in n_forced.  neg is -1
+    at a position beyond step_n[s] and where the user or the positive lies outside its table.  The caller guarantees
+    step_n[s] <= batch_cap."""
+    excl_ptr, excl_items = exclude
+    item_count, pop_order, sorted_count = popularity
+    if int(pool) < 1:
+        raise InvPrefError(f'dice_draw: pool must be at least 1, got {pool}')
+    if pos_items.numel() != users.numel():
+        raise InvPrefError(f'dice_draw: {users.numel()} users for {pos_items.numel()} positive items')
+    _gpu(users, pos_items, step_lo, step_n, step_id, excl_ptr, excl_items, item_count, pop_order, sorted_count, step_margin)
+    steps = step_lo.numel()
+    if out is None:
+        if batch_cap is None:
+            raise InvPrefError('dice_draw: give batch_cap (the row length of neg) or out=(neg, n_forced)')
+        out = (torch.empty(steps, int(batch_cap), dtype=torch.int32, device=users.device),
+               torch.empty(steps, dtype=torch.int32, device=users.device))
+    neg, n_forced = out
+    _gpu(neg, n_forced)
+    _o().dice_draw(users, pos_items, step_lo, step_n, step_id, excl_ptr, excl_items, pop_order, sorted_count, item_count,
+                   int(pool), step_margin, _seed64(seed), neg, n_forced)
+    return neg, n_forced
+
+
+def dice_workspace_bytes(user_num: int, item_num: int, batch: int, factor_num: int) -> int:
+    """the records, float64 partials, chunk slots and row marks of one gradient pass: a function of the sizes alone,
+    non-decreasing in each; 0: not taken"""
+    return int(_capi.lib().invpref_dice_workspace_bytes(int(user_num), int(item_num), int(batch), int(factor_num)))
+
+
+def dice_grad(params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor], users: torch.Tensor, pos_items: torch.Tensor,
+              neg: torch.Tensor, item_count: torch.Tensor, index: torch.Tensor, coefs3: torch.Tensor, dis_form, L2_coe: float,
+              L1_coe: float, losses8: torch.Tensor, weights: Optional[torch.Tensor] = None,
+              workspace: Optional[Workspace] = None) -> None:
+    """The gradient pass of one DICE step (include/invpref_dice.h states it).  params4 / grads4: (interest user table, interest
+    item table, conformity user table, conformity item table) and their gradients; users / pos_items int64 [B], neg int32 [B],
+    weights fp32 [B] (None: 1), item_count int32 [item_num]; index: bpr_index of the step; coefs3: float64 [3] ON THE DEVICE,
+    (int_weight, con_weight, dis_pen), read when the pass runs; dis_form: 'L1' / 0 or 'L2' / 1.  OVERWRITES every row of the
+    four gradients (rows without a triplet get zeros) and losses8 = (click_loss, int_loss, con_loss, dis, L2_reg, L1_reg, loss,
+    n_masked).  Bitwise reproducible, no float atomics, no host sync (capturable once the workspace is sized; a replay reads
+    ids, negatives, weights, counts, coefficients and index as they are then).  A triplet with an id outside its table (neg =
+    -1 included) is skipped whole and the seven losses are NaN."""
+    if isinstance(dis_form, str) and dis_form not in DICE_FORMS:
+        raise InvPrefError(f'dice_grad: dis_form must be one of {sorted(DICE_FORMS)} (or 0 / 1), got {dis_form!r}')
+    form = DICE_FORMS[dis_form] if isinstance(dis_form, str) else int(dis_form)
+    if form not in (0, 1):
+        raise InvPrefError(f'dice_grad: dis_form must be 0 (L1) or 1 (L2), got {dis_form!r}')
+    if len(params4) != 4 or len(grads4) != 4:
+        raise InvPrefError('dice_grad: four tables (Iu, Ii, Cu, Ci) and four gradients')
+    ws = _pass_workspace('dice_grad', dice_workspace_bytes, workspace, params4, users, pos_items, neg, item_count, index, coefs3,
+                         losses8, weights, *grads4, what='triplets')
+    _o().dice_grad_(*params4, users, pos_items, neg, weights, item_count, index, coefs3, form, float(L2_coe), float(L1_coe),
+                    *grads4, losses8, ws)
 
 
 # ---- sampled-softmax MF (include/invpref_ssm.h, csrc/invpref_ssm.hip)
