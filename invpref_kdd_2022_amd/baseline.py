@@ -1494,6 +1494,36 @@ class CausEExplicitTrainManager(_CausEManagerMixin, BasicExplicitTrainManager):
     """baseline_train.py:725-797 (baseline_explicit/general_bias_with_rct/CausE_mf_main.py)"""
 
 
+# ------------------------------------------------------------------------------------------------ training on positives
+def _kept_positives(training_data: torch.Tensor, weights, subject: str):
+    """What a manager that trains on positives keeps of its constructor's data: -> (positives, keep, n_dropped, weights), the
+    rows with a score > 0, their mask, the number of rows dropped and the fp32 weights (one per row of training_data, or per
+    kept row) cut to the kept rows, or None"""
+    keep = training_data[:, 2] > 0
+    n_dropped = int(training_data.shape[0] - int(keep.sum()))
+    if n_dropped == training_data.shape[0]:
+        raise ValueError(f'{subject} trains on positives: training_data has no row with a score > 0')
+    positives = training_data[keep]
+    if weights is not None:
+        w = torch.as_tensor(weights).detach().reshape(-1).to(torch.float32)
+        if w.numel() == training_data.shape[0]:
+            w = w[keep.to(w.device)]
+        if w.numel() != positives.shape[0]:
+            raise ValueError(f'weights holds {w.numel()} values for {training_data.shape[0]} rows / {len(positives)} positives')
+        weights = w.contiguous()
+    return positives, keep, n_dropped, weights
+
+
+def _caller_positives(dev, batch_users_tensor, batch_items_tensor, batch_scores_tensor, subject: str):
+    """The positives of a caller's minibatch, the rows with a score > 0: -> (users, items, B), int64 on `dev`"""
+    keep = batch_scores_tensor.detach().reshape(-1).to(dev) > 0
+    ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
+    vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
+    if ud.numel() == 0:
+        raise ValueError(f'{subject} trains on positives: the minibatch has no row with a score > 0')
+    return ud, vd, ud.numel()
+
+
 # ------------------------------------------------------------------------------------------------ BPR-MF
 class _TripletDrawnManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
     """What the managers share that train on (user, positive item, negative item drawn on the device) triplets -- BPR-MF and
@@ -1501,17 +1531,17 @@ class _TripletDrawnManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
     positives kept at construction, the exclusion lists, the draw launch (ops.bpr_draw), the staging rows (the step's users,
     then its negatives) and train_a_batch on caller tensors.  A manager supplies _SINGLE, _lazy_adam_unsupported,
     _workspace_bytes(), _own_pass() and, for what its pass needs beside the tables, _prepare_pass(positives), called once the
-    engine stands and before the workspace is sized."""
+    engine stands and before the workspace is sized.  It may set _CALLER_SUBJECT, override _draw_caller() and _after_caller()
+    (a caller's step: its draw; what follows however it ends) and set _TOUCHES where its model keeps final_tables(): the kernels
+    write the parameters through raw pointers, so the model is told (touch()) behind every run of epochs and train_a_batch."""
+    _CALLER_SUBJECT = 'BPR'     # who "trains on positives" in train_a_batch's error
+    _TOUCHES = False
 
     def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
                  evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, seed: int = 0,
                  weights=None, exclude=None, rank=None, world_size=None, process_group=None):
         self._require_single_process(world_size)
-        keep = training_data[:, 2] > 0
-        self.n_dropped = int(training_data.shape[0] - int(keep.sum()))
-        if self.n_dropped == training_data.shape[0]:
-            raise ValueError('BPR trains on positives: training_data has no row with a score > 0')
-        positives = training_data[keep]
+        positives, _, self.n_dropped, weights = _kept_positives(training_data, weights, 'BPR')
         super().__init__(model, evaluator, device, positives, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
         U, I, dev = model.user_num, model.item_num, self.device
@@ -1523,14 +1553,7 @@ class _TripletDrawnManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
             np.cumsum(np.bincount(keys // I, minlength=U), out=indptr[1:])
             exclude = (indptr, keys % I)
         self._excl = ops.device_csr(exclude, U, I, dev)
-        self._weights = None
-        if weights is not None:
-            w = torch.as_tensor(weights).detach().reshape(-1).to(torch.float32)
-            if w.numel() == training_data.shape[0]:
-                w = w[keep.to(w.device)]
-            if w.numel() != self.n_total:
-                raise ValueError(f'weights holds {w.numel()} values for {training_data.shape[0]} rows / {self.n_total} positives')
-            self._weights = w.contiguous().to(dev)
+        self._weights = None if weights is None else weights.to(dev)
         self._prepare_pass(positives)
         self._init_device_draws(seed)
 
@@ -1550,20 +1573,33 @@ class _TripletDrawnManager(_DeviceDrawnMixin, BasicImplicitTrainManager):
         ops.bpr_draw(self.users_tensor, self._step_lo[:steps], self._step_n[:steps], self._step_ids[:steps], self._excl,
                      self.model.item_num, self.seed, out=(self._draws[:steps, 1], self.n_forced[:steps]))
 
+    def _enqueue_epochs(self, want: int) -> torch.Tensor:
+        out = super()._enqueue_epochs(want)
+        if self._TOUCHES:
+            self.model.touch()
+        return out
+
+    def _draw_caller(self, ud: torch.Tensor, vd: torch.Tensor, B: int) -> torch.Tensor:
+        """the negatives of a caller's step, int32 [1, B], drawn under the next step id"""
+        return ops.bpr_draw(ud, torch.zeros(1, dtype=torch.int64, device=self.device), *self._step_name(B), self._excl,
+                            self.model.item_num, self.seed, batch_cap=B)[0]
+
     def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
         """one step on caller tensors: the rows with a score > 0 are the positives (weight 1), their negatives are drawn under
-        the next step id against the manager's exclusion lists, this minibatch's index is built here"""
+        the next step id against the manager's exclusion lists (_draw_caller), this minibatch's index is built here"""
         dev, m = self.device, self.model
-        keep = batch_scores_tensor.detach().reshape(-1).to(dev) > 0
-        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
-        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
-        B = ud.numel()
-        if B == 0:
-            raise ValueError('BPR trains on positives: the minibatch has no row with a score > 0')
-        neg, _ = ops.bpr_draw(ud, torch.zeros(1, dtype=torch.int64, device=dev), *self._step_name(B), self._excl, m.item_num,
-                              self.seed, batch_cap=B)
-        index = ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd)
-        return self._caller_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), neg, index, None)
+        try:
+            ud, vd, B = _caller_positives(dev, batch_users_tensor, batch_items_tensor, batch_scores_tensor, self._CALLER_SUBJECT)
+            neg = self._draw_caller(ud, vd, B)
+            index = ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd)
+            return self._caller_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), neg, index, None)
+        finally:
+            self._after_caller()
+
+    def _after_caller(self) -> None:
+        """behind a caller's step, however it ended: what _draw_caller set aside is dropped, the model is told"""
+        if self._TOUCHES:
+            self.model.touch()
 
 
 class BPRTrainManager(_TripletDrawnManager):
@@ -1596,65 +1632,17 @@ class BPRTrainManager(_TripletDrawnManager):
                      st.g_views[1], losses6[:4], weights=weights, workspace=self._ws)
 
 
-# ------------------------------------------------------------------------------------------------ LightGCN
-class LightGCNMatrixFactorization(nn.Module):
-    """LightGCN (He et al., SIGIR 2020): the ego tables user_emb / item_emb (initialised as PureMF's) and the FINAL tables
-        (F_user; F_item) = (1 / (K + 1)) sum_{k = 0 .. K} A^k (user_emb; item_emb),   K = n_layers,
-    A the symmetrically normalised user-item graph handed in by set_graph() (ops.lgcn_graph; csrc/invpref_lgcn.hip).  A pair is
-    scored by sigmoid(F_user[u] . F_item[i]).
-
-    Not a PureMatrixFactorization: the evaluators must not take the ego tables for ranking tables.  They rank through rank_fn()
-    / truth_rank_fn(), which are ops.predict_topk / ops.truth_ranks on final_tables() -- no score matrix.
-
-    final_tables() keeps its result and recomputes it when set_graph() or touch() was called since, or when the ego parameters
-    were replaced or written in place through torch (their data pointers and torch version counters are compared).  The
-    kernels of this package write the tables through raw pointers, which torch's counters do not see: LightGCNTrainManager
-    calls touch() behind every run of epochs and every train_a_batch; whoever else writes the tables that way calls it too.
-    The result is written into the same two buffers every time, so a pair returned earlier follows the model."""
+# ------------------------------------------------------------------------------------------------ models ranked on derived tables
+class _FinalTablesModel:
+    """In front of nn.Module: a model scored on FINAL tables derived from its parameters (LightGCN's propagated tables, DICE's
+    concatenation).  The model supplies final_tables() -> (F_user, F_item), detached, rebuilt when touch() was called since
+    (the counter `_changes`, 0 from the model's constructor) or torch saw the parameters change.  The evaluators rank through
+    rank_fn() / truth_rank_fn(): ops.predict_topk / ops.truth_ranks on final_tables(), no score matrix."""
     implicit = True
 
-    def __init__(self, user_num: int, item_num: int, factor_num: int, n_layers: int = 3):
-        super().__init__()
-        if not 0 <= int(n_layers) <= _capi.LGCN_MAX_LAYERS:
-            raise ValueError(f'n_layers must lie in 0 .. {_capi.LGCN_MAX_LAYERS}')
-        self.user_num, self.item_num, self.factor_num, self.n_layers = user_num, item_num, factor_num, int(n_layers)
-        self.user_emb = nn.Embedding(user_num, factor_num)
-        self.item_emb = nn.Embedding(item_num, factor_num)
-        nn.init.normal_(self.user_emb.weight, std=0.01)
-        nn.init.normal_(self.item_emb.weight, std=0.01)
-        self.graph = None
-        self._changes, self._final, self._final_key, self._ws = 0, None, None, None
-
-    def tables(self):
-        """the EGO pair, the flat state of a manager (not what ranks: final_tables())"""
-        return [self.user_emb.weight, self.item_emb.weight]
-
-    def set_graph(self, graph) -> None:
-        if (graph.user_num, graph.item_num) != (self.user_num, self.item_num):
-            raise ValueError(f'a graph of {graph.user_num} x {graph.item_num} for tables of {self.user_num} x {self.item_num}')
-        self.graph = graph
-        self.touch()
-
     def touch(self) -> None:
-        """the ego tables were written behind torch's back: the next final_tables() propagates again"""
+        """the parameters were written behind torch's back: the next final_tables() derives them again"""
         self._changes += 1
-
-    def final_tables(self):
-        """(F_user, F_item), detached; see the class docstring for when they are recomputed"""
-        if self.graph is None:
-            raise RuntimeError('LightGCNMatrixFactorization: set_graph(ops.lgcn_graph(...)) first')
-        P, Q = self.user_emb.weight, self.item_emb.weight
-        key = (self._changes, P.data_ptr(), Q.data_ptr(), P._version, Q._version)
-        if key != self._final_key:
-            if self.graph.device != P.device:
-                self.graph = self.graph.to(P.device)
-            if self._final is None or self._final[0].device != P.device:
-                self._final = (torch.empty_like(P.detach()), torch.empty_like(Q.detach()))
-                self._ws = ops.Workspace(P.device)
-            ops.lgcn_propagate(self.graph, P.detach().contiguous(), Q.detach().contiguous(), self.n_layers, out=self._final,
-                               workspace=self._ws)
-            self._final_key = key
-        return self._final
 
     def predict(self, users_id):
         """sigmoid(F_user[users] @ F_item^T) -> fp32 [n, item_num]"""
@@ -1681,6 +1669,61 @@ class LightGCNMatrixFactorization(nn.Module):
         return ops.recommend(F[0], F[1], users_id, k, exclude, highlight)
 
 
+# ------------------------------------------------------------------------------------------------ LightGCN
+class LightGCNMatrixFactorization(_FinalTablesModel, nn.Module):
+    """LightGCN (He et al., SIGIR 2020): the ego tables user_emb / item_emb (initialised as PureMF's) and the FINAL tables
+        (F_user; F_item) = (1 / (K + 1)) sum_{k = 0 .. K} A^k (user_emb; item_emb),   K = n_layers,
+    A the symmetrically normalised user-item graph handed in by set_graph() (ops.lgcn_graph; csrc/invpref_lgcn.hip).  A pair is
+    scored by sigmoid(F_user[u] . F_item[i]).
+
+    Not a PureMatrixFactorization: the evaluators must not take the ego tables for ranking tables (_FinalTablesModel's routes).
+
+    final_tables() keeps its result and recomputes it when set_graph() or touch() was called since, or when the ego parameters
+    were replaced or written in place through torch (their data pointers and torch version counters are compared).  The
+    kernels of this package write the tables through raw pointers, which torch's counters do not see: LightGCNTrainManager
+    calls touch() behind every run of epochs and every train_a_batch; whoever else writes the tables that way calls it too.
+    The result is written into the same two buffers every time, so a pair returned earlier follows the model."""
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int, n_layers: int = 3):
+        super().__init__()
+        if not 0 <= int(n_layers) <= _capi.LGCN_MAX_LAYERS:
+            raise ValueError(f'n_layers must lie in 0 .. {_capi.LGCN_MAX_LAYERS}')
+        self.user_num, self.item_num, self.factor_num, self.n_layers = user_num, item_num, factor_num, int(n_layers)
+        self.user_emb = nn.Embedding(user_num, factor_num)
+        self.item_emb = nn.Embedding(item_num, factor_num)
+        nn.init.normal_(self.user_emb.weight, std=0.01)
+        nn.init.normal_(self.item_emb.weight, std=0.01)
+        self.graph = None
+        self._changes, self._final, self._final_key, self._ws = 0, None, None, None
+
+    def tables(self):
+        """the EGO pair, the flat state of a manager (not what ranks: final_tables())"""
+        return [self.user_emb.weight, self.item_emb.weight]
+
+    def set_graph(self, graph) -> None:
+        if (graph.user_num, graph.item_num) != (self.user_num, self.item_num):
+            raise ValueError(f'a graph of {graph.user_num} x {graph.item_num} for tables of {self.user_num} x {self.item_num}')
+        self.graph = graph
+        self.touch()
+
+    def final_tables(self):
+        """(F_user, F_item), detached; see the class docstring for when they are recomputed"""
+        if self.graph is None:
+            raise RuntimeError('LightGCNMatrixFactorization: set_graph(ops.lgcn_graph(...)) first')
+        P, Q = self.user_emb.weight, self.item_emb.weight
+        key = (self._changes, P.data_ptr(), Q.data_ptr(), P._version, Q._version)
+        if key != self._final_key:
+            if self.graph.device != P.device:
+                self.graph = self.graph.to(P.device)
+            if self._final is None or self._final[0].device != P.device:
+                self._final = (torch.empty_like(P.detach()), torch.empty_like(Q.detach()))
+                self._ws = ops.Workspace(P.device)
+            ops.lgcn_propagate(self.graph, P.detach().contiguous(), Q.detach().contiguous(), self.n_layers, out=self._final,
+                               workspace=self._ws)
+            self._final_key = key
+        return self._final
+
+
 class LightGCNTrainManager(_TripletDrawnManager):
     """LightGCN trained with BPR: BPRTrainManager's loss with the scores taken on the model's FINAL tables and the regulariser
     on its EGO tables,
@@ -1694,6 +1737,7 @@ class LightGCNTrainManager(_TripletDrawnManager):
                'not implemented)')
     _lazy_adam_unsupported = ('lazy Adam updates the rows a minibatch names, but the propagation reaches every row: the '
                               'gradient of the ego tables is dense')
+    _TOUCHES = True
 
     def _prepare_pass(self, positives: torch.Tensor) -> None:
         m, dev = self.model, self.device
@@ -1720,24 +1764,13 @@ class LightGCNTrainManager(_TripletDrawnManager):
         ops.lgcn_reg(users, items, draws[-1], st.p_views[0], st.p_views[1], self.L2_coe, self.L1_coe, st.g_views[0],
                      st.g_views[1], losses6[:4], workspace=self._ws)
 
-    def _enqueue_epochs(self, want: int) -> torch.Tensor:
-        out = super()._enqueue_epochs(want)
-        self.model.touch()
-        return out
-
-    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
-        try:
-            return super().train_a_batch(batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args)
-        finally:
-            self.model.touch()
-
 
 # ------------------------------------------------------------------------------------------------ DICE
 DICE_LOSS_KEYS = ('click_loss', 'int_loss', 'con_loss', 'dis', 'L2_reg', 'loss')
 _DICE_LOSS_PICK = (0, 1, 2, 3, 4, 6)        # their places in the pass's losses8 (include/invpref_dice.h)
 
 
-class DICEMatrixFactorization(nn.Module):
+class DICEMatrixFactorization(_FinalTablesModel, nn.Module):
     """DICE (Zheng et al., WWW 2021): an interest pair int_user_emb / int_item_emb and a conformity pair con_user_emb /
     con_item_emb, all four initialised as PureMF's.  A pair is scored by sigmoid(F_user[u] . F_item[i]) on the FINAL tables,
 
@@ -1745,13 +1778,11 @@ class DICEMatrixFactorization(nn.Module):
     rank_by='both'       [Iu | Cu] and [Ii | Ci], width 2 factor_num: the click score, interest + conformity; the ranking
                          kernels take rows of at most INVPREF_MAX_FACTORS floats, so factor_num <= 128
 
-    Not a PureMatrixFactorization: the evaluators rank through rank_fn() / truth_rank_fn(), which are ops.predict_topk /
-    ops.truth_ranks on final_tables() -- no score matrix.  For 'both', final_tables() keeps the concatenation and rebuilds it
-    when touch() was called since, or when the parameters were replaced or written in place through torch (their data pointers
-    and torch version counters are compared), as LightGCNMatrixFactorization does: DICETrainManager calls touch() behind every
-    run of epochs and every train_a_batch, since the kernels write the tables through raw pointers.  The concatenation is
-    written into the same two buffers every time, so a pair returned earlier follows the model."""
-    implicit = True
+    Not a PureMatrixFactorization: _FinalTablesModel's routes rank it.  For 'both', final_tables() keeps the concatenation
+    and rebuilds it when touch() was called since, or when the parameters were replaced or written in place through torch
+    (their data pointers and torch version counters are compared), as LightGCNMatrixFactorization does: DICETrainManager calls
+    touch() behind every run of epochs and every train_a_batch, since the kernels write the tables through raw pointers.  The
+    concatenation is written into the same two buffers every time, so a pair returned earlier follows the model."""
 
     def __init__(self, user_num: int, item_num: int, factor_num: int, rank_by: str = 'both'):
         super().__init__()
@@ -1774,10 +1805,6 @@ class DICEMatrixFactorization(nn.Module):
         """Iu, Ii, Cu, Ci: the flat state of a manager (not what ranks: final_tables())"""
         return [self.int_user_emb.weight, self.int_item_emb.weight, self.con_user_emb.weight, self.con_item_emb.weight]
 
-    def touch(self) -> None:
-        """the tables were written behind torch's back: the next final_tables() concatenates again"""
-        self._changes += 1
-
     def final_tables(self):
         """(F_user, F_item), detached; see the class docstring"""
         T = self.tables()
@@ -1793,30 +1820,6 @@ class DICEMatrixFactorization(nn.Module):
                 F[:, D:].copy_(b.detach())
             self._final_key = key
         return self._final
-
-    def predict(self, users_id):
-        """sigmoid(F_user[users] @ F_item^T) -> fp32 [n, item_num]"""
-        F = self.final_tables()
-        return ops.predict(F[0], F[1], _user_ids(users_id, F[0]), True)
-
-    def rank_fn(self):
-        """ImplicitTestManager's fused route: f(users, k, mask, highlight, truth) -> (items, scores, hits), ops.predict_topk on
-        final_tables() as they are when rank_fn() is called"""
-        F = self.final_tables()
-        return lambda users, k, mask, highlight, truth: ops.predict_topk(F[0], F[1], users, k, True, mask=mask,
-                                                                         highlight=highlight, truth=truth)
-
-    def truth_rank_fn(self):
-        """ImplicitRankTestManager's fused route: f(users, truth, mask, highlight) -> int32 ranks, ops.truth_ranks on
-        final_tables()"""
-        F = self.final_tables()
-        return lambda users, truth, mask, highlight: ops.truth_ranks(F[0], F[1], users, truth, True, mask=mask,
-                                                                     highlight=highlight)
-
-    def recommend(self, users_id, k: int, exclude=None, highlight=None):
-        """Each user's top-k items by the scores of predict() (InvPrefImplicit.recommend), on final_tables()"""
-        F = self.final_tables()
-        return ops.recommend(F[0], F[1], users_id, k, exclude, highlight)
 
 
 def dice_schedule(epoch: int, margin: float, int_weight: float, con_weight: float, dis_pen: float, margin_decay: float,
@@ -1851,6 +1854,8 @@ class DICETrainManager(_TripletDrawnManager):
     _LOSS_KEYS = DICE_LOSS_KEYS
     _lazy_adam_unsupported = ('the DICE pass stores zeros to every idle row and Adam runs over the whole tables: a lazy form '
                               'would update the rows the step\'s triplets touch (not built)')
+    _CALLER_SUBJECT = 'DICE'
+    _TOUCHES = True
 
     def __init__(self, model, evaluator, device, training_data: torch.Tensor, batch_size: int, epochs: int,
                  evaluate_interval: int, lr: float, L2_coe: float, L1_coe: float, test_begin_epoch: int = 0, *, seed: int = 0,
@@ -1916,32 +1921,17 @@ class DICETrainManager(_TripletDrawnManager):
                       self.L1_coe, self._losses8, weights=weights, workspace=self._ws)
         torch.index_select(self._losses8, 0, self._loss_pick, out=losses6)
 
-    def _enqueue_epochs(self, want: int) -> torch.Tensor:
-        out = super()._enqueue_epochs(want)
-        self.model.touch()
-        return out
-
-    def train_a_batch(self, batch_users_tensor, batch_items_tensor, batch_scores_tensor, *args) -> dict:
-        """one step on caller tensors at the current epoch's margin and coefficients: the rows with a score > 0 are the
-        positives (weight 1), their negatives are drawn under the next step id against the manager's exclusion lists and
-        popularity arrays, this minibatch's index is built here"""
-        dev, m = self.device, self.model
-        keep = batch_scores_tensor.detach().reshape(-1).to(dev) > 0
-        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
-        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
-        B = ud.numel()
-        if B == 0:
-            raise ValueError('DICE trains on positives: the minibatch has no row with a score > 0')
+    def _draw_caller(self, ud: torch.Tensor, vd: torch.Tensor, B: int) -> torch.Tensor:
+        """at the current epoch's margin; its coefficients are set aside for the pass (_own_pass: a step without a row)"""
+        dev = self.device
         margin, coefs3 = self.schedule_of(self.epoch_cnt)
         self._caller_coefs = torch.tensor(coefs3, dtype=torch.float64, device=dev)
-        neg, _ = ops.dice_draw(ud, vd, torch.zeros(1, dtype=torch.int64, device=dev), *self._step_name(B), self._excl, self._pop,
-                               self.pool, torch.full((1,), margin, dtype=torch.float64, device=dev), self.seed, batch_cap=B)
-        index = ops.bpr_index(ud, neg[0], m.item_num, m.user_num, vd)
-        try:
-            return self._caller_step(ud, vd, torch.ones(B, dtype=torch.float32, device=dev), neg, index, None)
-        finally:
-            self._caller_coefs = None
-            m.touch()
+        return ops.dice_draw(ud, vd, torch.zeros(1, dtype=torch.int64, device=dev), *self._step_name(B), self._excl, self._pop,
+                             self.pool, torch.full((1,), margin, dtype=torch.float64, device=dev), self.seed, batch_cap=B)[0]
+
+    def _after_caller(self) -> None:
+        self._caller_coefs = None
+        super()._after_caller()
 
 
 # ------------------------------------------------------------------------------------------------ sampled-softmax MF
@@ -1983,11 +1973,7 @@ class SSMTrainManager(_StagedRunMixin, _WholePassMixin, BasicImplicitTrainManage
             raise ValueError(f'n_neg must lie in [1, {_capi.SSM_MAX_NEG}], got {n_neg}')
         if not (float(temperature) > 0.0 and np.isfinite(float(temperature))):
             raise ValueError(f'temperature must be a positive finite number, got {temperature}')
-        keep = training_data[:, 2] > 0
-        self.n_dropped = int(training_data.shape[0] - int(keep.sum()))
-        if self.n_dropped == training_data.shape[0]:
-            raise ValueError('sampled softmax trains on positives: training_data has no row with a score > 0')
-        positives = training_data[keep]
+        positives, _, self.n_dropped, weights = _kept_positives(training_data, weights, 'sampled softmax')
         super().__init__(model, evaluator, device, positives, batch_size, epochs, evaluate_interval, lr, L2_coe, L1_coe,
                          test_begin_epoch, rank=rank, world_size=world_size, process_group=process_group)
         I, dev = model.item_num, self.device
@@ -2002,14 +1988,7 @@ class SSMTrainManager(_StagedRunMixin, _WholePassMixin, BasicImplicitTrainManage
         for t, what in ((self._cum, 'cum'), (self._bias, 'item_bias')):
             if t is not None and t.numel() != I:
                 raise ValueError(f'proposal: {what} holds {t.numel()} entries for {I} items')
-        self._weights = None
-        if weights is not None:
-            w = torch.as_tensor(weights).detach().reshape(-1).to(torch.float32)
-            if w.numel() == training_data.shape[0]:
-                w = w[keep.to(w.device)]
-            if w.numel() != self.n_total:
-                raise ValueError(f'weights holds {w.numel()} values for {training_data.shape[0]} rows / {self.n_total} positives')
-            self._weights = w.contiguous().to(dev)
+        self._weights = None if weights is None else weights.to(dev)
         self.seed, self.step_id = int(seed), 0
         self._caller = None         # train_a_batch: (users, items, negatives, index) of the caller's minibatch
         self._pos_index = None      # per static minibatch: ops.ssm_index of its positives
@@ -2056,12 +2035,7 @@ class SSMTrainManager(_StagedRunMixin, _WholePassMixin, BasicImplicitTrainManage
         """one step on caller tensors: the rows with a score > 0 are the positives (weight 1), the negatives are drawn under
         the next step id, this minibatch's index is built here"""
         dev, m = self.device, self.model
-        keep = batch_scores_tensor.detach().reshape(-1).to(dev) > 0
-        ud = batch_users_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
-        vd = batch_items_tensor.detach().to(dev).reshape(-1).to(torch.int64)[keep].contiguous()
-        B = ud.numel()
-        if B == 0:
-            raise ValueError('sampled softmax trains on positives: the minibatch has no row with a score > 0')
+        ud, vd, B = _caller_positives(dev, batch_users_tensor, batch_items_tensor, batch_scores_tensor, 'sampled softmax')
         neg = ops.ssm_draw(torch.full((1,), self.step_id, dtype=torch.int64, device=dev), m.item_num, self.n_neg, cum=self._cum,
                            seed=self.seed)[0]
         self._ws.get(max(self._workspace_bytes(B), 16))

@@ -20,7 +20,7 @@ SOURCES = ['invpref_kernels.hip', 'invpref_step.hip', 'invpref_eval.hip', 'invpr
            'invpref_catalog.hip', 'invpref_rank_stats.hip', 'invpref_bpr.hip', 'invpref_dr.hip', 'invpref_segment_rank.hip',
            'invpref_als.hip', 'invpref_key_sort.hip', 'invpref_ssm.hip', 'invpref_lgcn.hip', 'invpref_dice.hip']
 HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'adam_apply.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp',
-           'row_pass.hpp', 'chunk_walk.hpp', 'philox.hpp', 'truth_rank_body.hpp', 'rank_key.hpp',
+           'row_pass.hpp', 'chunk_walk.hpp', 'philox.hpp', 'neg_draw.hpp', 'truth_rank_body.hpp', 'rank_key.hpp',
            os.path.join('..', '..', 'include', 'invpref_hip.h'),
            os.path.join('..', '..', 'include', 'invpref_macr.h'), os.path.join('..', '..', 'include', 'invpref_cause.h'),
            os.path.join('..', '..', 'include', 'invpref_retrieve_scaled.h'),

@@ -1,11 +1,15 @@
 // chunk_walk.hpp -- the chunked scatter and its boundary walk: per-pair gradients summed per destination row, deterministically,
-// for rows no row plan knows.  CVIB's information term (invpref_cvib.hip), BPR-MF's gradient pass (invpref_bpr.hip) and the
-// doubly robust pass (invpref_dr.hip) are built on it; each states what is its own in a policy struct (below) and keeps its
-// kernels' names, arguments and launch geometry.  This comment is the one statement of the scheme.
+// for rows no row plan knows.  Built on it: CVIB's information term (invpref_cvib.hip), BPR-MF's gradient pass
+// (invpref_bpr.hip; LightGCN, invpref_lgcn.hip, trains through that pass on its final tables), the doubly robust pass
+// (invpref_dr.hip), sampled-softmax MF's two scatters (invpref_ssm.hip) and DICE's four-table pass (invpref_dice.hip).  Each
+// states what is its own in a policy struct (below) and keeps its kernels' names, arguments and launch geometry.  This comment
+// is the one statement of the scheme.
 //
 // What it offers: the geometry (chunk_of, ChunkGeom, chunk_geom, slot_of), the slot and accumulator helpers, clamp_id, the two
-// kernel bodies chunk_scatter / chunk_boundary, and -- for the passes that carry the L2 / L1 regularisers, BPR's and DR's --
-// norms64, reg_of and RegWalk, the policy base that holds everything of a policy but the entries themselves.
+// kernel bodies chunk_scatter / chunk_boundary, and -- for the passes that carry the L2 / L1 regularisers, all but CVIB's --
+// norms64, reg_of and RegWalk, the policy base that holds everything of a policy but the entries themselves; on top of it
+// triplet_ok and TripletWalk, the entries of a pass over signed (u, i+, j-) triplets (BPR's, DICE's) but for where a
+// triplet's factor is read.
 //
 // The input.  Per side (0: user rows, partner table Qi; 1: item rows, partner table Pu) the step's n2 = 2 B positions come
 // sorted by destination row as (row, position) entries: the inverted index of invpref_cvib_index_hip, `stride` entries per
@@ -322,6 +326,42 @@ struct RegWalk {
         round_row<NC>(acc, r);
         store_row<NC, VEC>(gtab, row, D, l16, r);
     }
+};
+
+// ---- the triplet walk: the policy of a pass over 2 B signed positions, (u, i+, +g) at p and (u, j-, -g) at B + p -- BPR's
+// pass (LightGCN trains through it too) and, per pair of tables, DICE's
+// do all three ids of a triplet lie in their tables?  The passes skip a triplet whole (neg = -1 included) where they do not
+__device__ __forceinline__ bool triplet_ok(int64_t u, int64_t i, int j, int U, int I) {
+    return u >= 0 && u < U && i >= 0 && i < I && j >= 0 && j < I;
+}
+// Fetch: a functor of kernel arguments, fetch(p) the factor g of triplet p as its pairs launch recorded it
+template <typename Fetch>
+struct TripletWalk : RegWalk {
+    struct Entry {
+        int64_t u, i;   // the triplet's three ids and its g
+        int j;
+        float g;
+    };
+    int U, I, B;
+    const int64_t *__restrict__ users, *__restrict__ pos_items;
+    const int32_t *__restrict__ neg;
+    Fetch fetch;
+
+    __device__ __forceinline__ Entry load(int, int pos) const {
+        const int p = pos < B ? pos : pos - B;
+        return Entry{users[p], pos_items[p], neg[p], fetch(p)};
+    }
+    __device__ __forceinline__ int64_t partner(int side, const Entry &e, int pos) const {
+        return side ? e.u : (pos < B ? e.i : (int64_t)e.j);
+    }
+    // the whole triplet decides, not the pair: a bad negative silences the positive's position too.  (!triplet_ok() written
+    // out in one chain with the position's range: through the call the scatter kernels are compiled to other code)
+    __device__ __forceinline__ bool valid(const Entry &e, int y, int n2) const {
+        return !(y < 0 || y >= n2 || e.u < 0 || e.u >= U || e.i < 0 || e.i >= I || e.j < 0 || e.j >= I);
+    }
+    // (a triplet gathers its user row once: the user side counts position p only)
+    __device__ __forceinline__ int gathers(int side, int pos) const { return (side || pos < B) ? 1 : 0; }
+    __device__ __forceinline__ float factor(const Entry &e, int pos) const { return pos < B ? e.g : -e.g; }
 };
 
 }  // namespace invpref

@@ -1,40 +1,33 @@
 // invpref_bpr.hip -- BPR-MF (include/invpref_bpr.h): the negative sampler of a run of steps and the gradient pass of one step
 // over its 2B signed pairs, (u, i+, +g) and (u, j-, -g).
 //
-// The draw.  One thread per (step, position): Philox4x32-10 keyed by the seed, the counter (position, quad, step id), a word
-// per attempt, the candidate (word * item_num) >> 32, a bisection of the user's ascending exclusion list.  Quads are made as
-// they are needed -- with a short list the first word is accepted almost always.  The only atomics are integer ones, on the
-// count of forced draws.
+// The draw.  neg_draw.hpp's rejection draw, one thread per (step, position): INVPREF_BPR_MAX_ATTEMPTS candidates from the
+// stream's word 0 on, the candidate (word * item_num) >> 32 -- with a short list the first word is accepted almost always.
 //
-// The pass.  The chunked scatter and boundary walk that CVIB's term uses too (chunk_walk.hpp states the scheme), with the
-// pair's factor formed by a pairs launch instead of two means:
+// The pass.  The chunked scatter and boundary walk of chunk_walk.hpp, with the pair's factor formed by a pairs launch:
 //   pairs     a 16-lane group per triplet (kernel_common.hpp: a row on 16 lanes): the three rows, x = Pu[u] . Qi[i] -
-//             Pu[u] . Qi[j] with dot64 of row_pass.hpp, -log sigmoid(x) and the regulariser sums as float64, one partial per
+//             Pu[u] . Qi[j] with dot64 of row_pass.hpp, its logsig64 and the regulariser sums as float64, one partial per
 //             workgroup (group_sums), and the record g = -w sigmoid(-x) / B, ONE float
-//   scatter, boundary   chunk_walk.hpp's walk with BprWalk below as its policy: an entry's operands are the triplet's three
-//             ids and g; acc += +-g * partner row.  The rest is chunk_walk.hpp's RegWalk, the base the doubly robust pass
-//             derives its policy from too: at the end of a destination acc += n * regulariser gradient of the destination
-//             row, n the gathers of that row among the entries added (an item row: every entry; a user row: the entries of
-//             positions p < B, since a triplet gathers its user row once); float64 slots; a finished row is rounded once
-//             and stored
+//   scatter, boundary   the walk with chunk_walk.hpp's TripletWalk as its policy, the factor read from g: acc += +-g *
+//             partner row; at the end of a destination RegWalk adds n * regulariser gradient of the destination row, n the
+//             gathers of that row among the entries added (an item row: every entry; a user row: the entries of positions
+//             p < B, since a triplet gathers its user row once)
 //   fold      one wave: the partials in workgroup order -> losses4
-// Every row has one writer and every sum a fixed order: the same bits on every run.  The slots are float64, so a row is
-// rounded to fp32 once however many chunks it spans.  Both gradient tables are zero-filled on the stream in front of the
-// scatter (rows without a triplet hold zeros afterwards), so the writers store and never read the tables.
+// Every row has one writer and every sum a fixed order: the same bits on every run.  Both gradient tables are zero-filled on
+// the stream in front of the scatter (rows without a triplet hold zeros afterwards), so the writers store and never read the
+// tables.
 //
 // A triplet with any id outside its table is skipped by BOTH of its positions (the scatter reads the triplet's three ids, not
 // the pair's two: the index files position p under u even when only j is bad); the pairs launch counts it and the fold makes
 // the four losses NaN.  Nothing read from the device is an address before it is range-checked.
 #include "chunk_walk.hpp"
-#include "philox.hpp"
+#include "neg_draw.hpp"
 
 #include "../../include/invpref_bpr.h"
 
 using namespace invpref;
 
 namespace {
-
-constexpr int kMaxQuads = INVPREF_BPR_MAX_ATTEMPTS / 4;
 
 __global__ __launch_bounds__(256) void bpr_draw_kernel(const int64_t *__restrict__ users, int64_t n_len,
                                                        const int64_t *__restrict__ step_lo, const int32_t *__restrict__ step_n,
@@ -45,32 +38,12 @@ __global__ __launch_bounds__(256) void bpr_draw_kernel(const int64_t *__restrict
     const int p = (int)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
     if (p >= cap) return;
     int32_t out = -1;
-    const int64_t at = step_lo[s] + p;
-    if (p < step_n[s] && at >= 0 && at < n_len) {
-        const int64_t u = users[at];
-        if (u >= 0 && u < U) {
-            const int lo0 = min(max(excl_ptr[u], 0), excl_len), hi0 = min(max(excl_ptr[u + 1], lo0), excl_len);
-            const uint64_t sid = (uint64_t)step_id[s];
-            bool found = false;
-            for (int q = 0; q < kMaxQuads && !found; q++) {
-                uint32_t x[4];
-                philox4x32_10((uint32_t)p, (uint32_t)q, (uint32_t)sid, (uint32_t)(sid >> 32), k0, k1, x);
-#pragma unroll
-                for (int w = 0; w < 4; w++) {
-                    if (found) continue;
-                    const int cand = (int)(((uint64_t)x[w] * (uint64_t)item_num) >> 32);
-                    int lo = lo0, hi = hi0;          // the first entry >= cand
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (excl_items[mid] < cand) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    out = cand;
-                    found = !(lo < hi0 && excl_items[lo] == cand);
-                }
-            }
-            if (!found) atomicAdd(n_forced + s, 1);
-        }
+    DrawSite d;
+    if (draw_site(p, s, users, n_len, step_lo, step_n, excl_ptr, excl_len, U, d)) {
+        uint32_t x[4];
+        out = draw_unlisted<INVPREF_BPR_MAX_ATTEMPTS, 0>(
+            p, (uint64_t)step_id[s], k0, k1, x, excl_items, d,
+            [&](uint32_t word) { return (int32_t)(((uint64_t)word * (uint64_t)item_num) >> 32); }, n_forced + s);
     }
     neg[(int64_t)s * neg_stride + p] = out;
 }
@@ -105,9 +78,10 @@ __global__ __launch_bounds__(256) void bpr_pairs_kernel(const float *__restrict_
     const int p = (int)blockIdx.x * kGroups + threadIdx.x / kRow;
     double mine[kRec] = {0.0, 0.0, 0.0, 0.0};
     if (p < B) {                                        // (the same for the 16 lanes of a group)
-        const int64_t u = users[p], i = pos_items[p], j = neg[p];
+        const int64_t u = users[p], i = pos_items[p];
+        const int j = neg[p];
         const double w = weights ? (double)weights[p] : 1.0;
-        const bool valid = u >= 0 && u < U && i >= 0 && i < I && j >= 0 && j < I;
+        const bool valid = triplet_ok(u, i, j, U, I);
         float4 a[NC], bi[NC], bj[NC];
         load_row<NC, VEC>(Pu, clamp_id(u, U), D, l16, a);
         load_row<NC, VEC>(Qi, clamp_id(i, I), D, l16, bi);
@@ -120,13 +94,10 @@ __global__ __launch_bounds__(256) void bpr_pairs_kernel(const float *__restrict_
         sq = row16_sum64(sq);
         ab = row16_sum64(ab);
         if (l16 == 0) {
-            // -log sigmoid(x) = max(-x, 0) + log1p(exp(-|x|)); sigmoid(-x) = e / (1 + e) (x >= 0), 1 / (1 + e) (x < 0), e = exp(-|x|)
-            const double e = exp(-fabs(x));
-            const double nls = fmax(-x, 0.0) + log1p(e);
-            const double sneg = x >= 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e);
-            g[p] = valid ? (float)(-w * sneg / (double)B) : 0.0f;
+            const LogSig64 t = logsig64(x);
+            g[p] = valid ? (float)(-w * t.sneg / (double)B) : 0.0f;
             if (valid) {
-                mine[0] = w * nls;
+                mine[0] = w * t.nls;
                 mine[1] = sq;
                 mine[2] = ab;
             } else {
@@ -151,33 +122,12 @@ __global__ __launch_bounds__(64) void bpr_fold_kernel(const double *__restrict__
     losses4[3] = (float)(bad ? nan : (sl + L2_coe * l2) + L1_coe * l1);
 }
 
-// what the chunked scatter and boundary walk and their regularised policy base (chunk_walk.hpp) leave to this pass
-struct BprWalk : RegWalk {
-    struct Entry {
-        int64_t u, i;   // the triplet's three ids and its g
-        int j;
-        float g;
-    };
-    int U, I, B;
-    const int64_t *__restrict__ users, *__restrict__ pos_items;
-    const int32_t *__restrict__ neg;
+// chunk_walk.hpp's triplet walk with the pairs launch's ONE float per triplet as the factor
+struct BprRec {
     const float *__restrict__ g;
-
-    __device__ __forceinline__ Entry load(int, int pos) const {
-        const int p = pos < B ? pos : pos - B;
-        return Entry{users[p], pos_items[p], neg[p], g[p]};
-    }
-    __device__ __forceinline__ int64_t partner(int side, const Entry &e, int pos) const {
-        return side ? e.u : (pos < B ? e.i : (int64_t)e.j);
-    }
-    // the whole triplet decides, not the pair: a bad negative silences the positive's position too
-    __device__ __forceinline__ bool valid(const Entry &e, int y, int n2) const {
-        return !(y < 0 || y >= n2 || e.u < 0 || e.u >= U || e.i < 0 || e.i >= I || e.j < 0 || e.j >= I);
-    }
-    // (a triplet gathers its user row once: the user side counts position p only)
-    __device__ __forceinline__ int gathers(int side, int pos) const { return (side || pos < B) ? 1 : 0; }
-    __device__ __forceinline__ float factor(const Entry &e, int pos) const { return pos < B ? e.g : -e.g; }
+    __device__ __forceinline__ float operator()(int p) const { return g[p]; }
 };
+using BprWalk = TripletWalk<BprRec>;
 
 template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void bpr_scatter_kernel(const float *__restrict__ Pu, int U, const float *__restrict__ Qi, int I,
@@ -187,7 +137,7 @@ __global__ __launch_bounds__(256) void bpr_scatter_kernel(const float *__restric
                                                           int nchunk, const float *__restrict__ g, double r2, double r1,
                                                           float *__restrict__ gu, float *__restrict__ gi,
                                                           double *__restrict__ part, int Dp) {
-    const BprWalk pol{{r2, r1}, U, I, B, users, pos_items, neg, g};
+    const BprWalk pol{{r2, r1}, U, I, B, users, pos_items, neg, {g}};
     chunk_scatter<NC, VEC>(pol, Pu, U, Qi, I, D, B, index, stride, C, nchunk, gu, gi, part, Dp);
 }
 
@@ -206,19 +156,15 @@ int invpref_bpr_draw_hip(const int64_t *users, int64_t n_users_len, const int64_
                          const int64_t *step_id, int64_t steps, const int32_t *excl_ptr, const int32_t *excl_items,
                          int64_t excl_len, int64_t user_num, int64_t item_num, int64_t seed, int32_t *neg, int64_t neg_stride,
                          int64_t batch_cap, int32_t *n_forced, void *stream) {
-    if (!users || !step_lo || !step_n || !step_id || !excl_ptr || !neg || !n_forced || n_users_len < 1 || steps < 1 ||
-        excl_len < 0 || (excl_len > 0 && !excl_items) || user_num < 1 || item_num < 1 || batch_cap < 1 || neg_stride < batch_cap)
-        return INVPREF_EINVAL;
-    if (item_num > kI32Max || user_num > kI32Max || excl_len > kI32Max || batch_cap > INVPREF_BPR_MAX_BATCH ||
-        steps > INVPREF_BPR_MAX_STEPS)
-        return INVPREF_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    int rc = (int)hipMemsetAsync(n_forced, 0, sizeof(int32_t) * (size_t)steps, st);
+    dim3 grid;
+    const int rc = draw_prepare(users, step_lo, step_n, step_id, excl_ptr, excl_items, neg, n_forced, n_users_len, steps, excl_len,
+                                user_num, item_num, neg_stride, batch_cap, INVPREF_BPR_MAX_BATCH, INVPREF_BPR_MAX_STEPS, st, grid);
     if (rc) return rc;
     const uint64_t bits = (uint64_t)seed;
-    hipLaunchKernelGGL(bpr_draw_kernel, dim3((unsigned)((batch_cap + 255) / 256), (unsigned)steps), dim3(256), 0, st, users,
-                       n_users_len, step_lo, step_n, step_id, excl_ptr, excl_items, (int)excl_len, user_num, (uint32_t)item_num,
-                       (uint32_t)bits, (uint32_t)(bits >> 32), neg, neg_stride, (int)batch_cap, n_forced);
+    hipLaunchKernelGGL(bpr_draw_kernel, grid, dim3(256), 0, st, users, n_users_len, step_lo, step_n, step_id, excl_ptr,
+                       excl_items, (int)excl_len, user_num, (uint32_t)item_num, (uint32_t)bits, (uint32_t)(bits >> 32), neg,
+                       neg_stride, (int)batch_cap, n_forced);
     return (int)hipGetLastError();
 }
 

@@ -2,24 +2,23 @@
 // pass of one step over its 2B signed pairs, (u, i+, +g) and (u, j-, -g), into FOUR tables, interest (Iu, Ii) and conformity
 // (Cu, Ci).
 //
-// The draw.  One thread per (step, position): c = item_count[i_p], two bisections of the popularity-sorted catalogue for the
-// prefix of items less popular than c - margin and the suffix of items more popular than c + margin, the branch coin, then
-// BPR's rejection loop over the chosen range: a Philox word per attempt, the candidate pop_order[lo + ((word * len) >> 32)], a
-// bisection of the user's ascending exclusion list.  Quads are made as they are needed.  The only atomics are integer ones,
-// on the count of forced draws.
+// The draw.  neg_draw.hpp's rejection draw, one thread per (step, position), over a range of the popularity-sorted catalogue:
+// c = item_count[i_p], two bisections for the prefix of items less popular than c - margin and the suffix of items more
+// popular than c + margin, the branch coin (word 0 of the stream), then INVPREF_DICE_MAX_ATTEMPTS candidates from word 1 on,
+// the candidate pop_order[lo + ((word * len) >> 32)].  A position whose positive lies outside the table stores -1 too.
 //
 // The pass.  chunk_walk.hpp's chunked scatter and boundary walk for two pairs of tables over the same index, as the doubly
 // robust pass runs it (blockIdx.y chooses the pair), with BPR's signed positions:
 //   pairs     a 16-lane group per triplet (kernel_common.hpp: a row on 16 lanes): the six rows as one batch, xI and xC with
-//             dot64 of row_pass.hpp, the mask from item_count, the three loss terms and the regulariser sums as float64, one
-//             partial per workgroup (group_sums), and the record (gT + gI, gT + gC), TWO floats
+//             dot64 of row_pass.hpp, the mask from item_count, the three loss terms (logsig64) and the regulariser sums as
+//             float64, one partial per workgroup (group_sums), and the record (gT + gI, gT + gC), TWO floats
 //   count     a workgroup per 256 consecutive index entries of a side.  A thread per entry: is it the first entry of an
 //             in-table row, and does the row hold an entry of a non-skipped triplet (almost always the first: the walk to the
 //             next one ends there)?  Such a row is in R: its mark is set, the workgroup's count goes to |R| of the side by ONE
 //             integer atomic, and the workgroup's 16-lane groups take the marked rows in turn -- group k rows k, k + 16, ... of
 //             the workgroup's starts, in that order -- for sum_d phi(a - b), float64, one partial per workgroup
-//   scatter, boundary   the walk with DiceWalk as its policy: BprWalk's entries with the pair's own factor from the record.
-//             At the end of a destination RegWalk adds the regulariser gradient; the chunk in which a marked destination
+//   scatter, boundary   the walk with DiceWalk as its policy: TripletWalk with the pair's own factor from the record.  At
+//             the end of a destination RegWalk adds the regulariser gradient; the chunk in which a marked destination
 //             STARTS (chunk_walk.hpp's StartsRows hook) adds -+ dis_pen phi'(a - b) / (|R| D) from the destination's row and
 //             its sibling's, so the row receives it once however many chunks it spans
 //   fold      nine waves, one per sum -> losses8
@@ -30,24 +29,13 @@
 // the pairs launch counts it and the fold makes the losses NaN.  Nothing read from the device is an address before it is
 // range-checked.
 #include "chunk_walk.hpp"
-#include "philox.hpp"
+#include "neg_draw.hpp"
 
 #include "../../include/invpref_dice.h"
 
 using namespace invpref;
 
 namespace {
-
-// the first entry of the user's ascending list [lo0, hi0) that is >= cand: is it cand?
-__device__ __forceinline__ bool listed(const int32_t *__restrict__ excl_items, int lo0, int hi0, int cand) {
-    int lo = lo0, hi = hi0;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (excl_items[mid] < cand) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < hi0 && excl_items[lo] == cand;
-}
 
 __global__ __launch_bounds__(256) void dice_draw_kernel(
     const int64_t *__restrict__ users, const int64_t *__restrict__ pos_items, int64_t n_len, const int64_t *__restrict__ step_lo,
@@ -59,11 +47,10 @@ __global__ __launch_bounds__(256) void dice_draw_kernel(
     const int p = (int)blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
     if (p >= cap) return;
     int32_t out = -1;
-    const int64_t at = step_lo[s] + p;
-    if (p < step_n[s] && at >= 0 && at < n_len) {
-        const int64_t u = users[at], ip = pos_items[at];
-        if (u >= 0 && u < U && ip >= 0 && ip < I) {
-            const int lo0 = min(max(excl_ptr[u], 0), excl_len), hi0 = min(max(excl_ptr[u + 1], lo0), excl_len);
+    DrawSite d;
+    if (draw_site(p, s, users, n_len, step_lo, step_n, excl_ptr, excl_len, U, d)) {
+        const int64_t ip = pos_items[d.at];
+        if (ip >= 0 && ip < I) {
             const double mg = step_margin[s], margin = mg > 0.0 ? mg : 0.0;
             const double c = (double)item_count[ip], below = c - margin, above = c + margin;
             int lo = 0, hi = I;                       // n_un: the first t with sorted_count[t] >= c - margin
@@ -87,16 +74,11 @@ __global__ __launch_bounds__(256) void dice_draw_kernel(
             int r_lo = 0, r_len = I;
             if (n_pop >= pool && (n_un < pool || coin)) r_lo = I - n_pop, r_len = n_pop;
             else if (n_un >= pool) r_len = n_un;
-            bool found = false;
-            for (int a = 0; a < INVPREF_DICE_MAX_ATTEMPTS && !found; a++) {
-                const int w = (a + 1) & 3;
-                if (w == 0) philox4x32_10((uint32_t)p, (uint32_t)((a + 1) >> 2), (uint32_t)sid, (uint32_t)(sid >> 32), k0, k1, x);
-                const uint32_t word = w == 0 ? x[0] : (w == 1 ? x[1] : (w == 2 ? x[2] : x[3]));
-                const int t = r_lo + (int)(((uint64_t)word * (uint64_t)(uint32_t)r_len) >> 32);   // inside [0, I)
-                out = pop_order[t];
-                found = !listed(excl_items, lo0, hi0, out);
-            }
-            if (!found) atomicAdd(n_forced + s, 1);
+            // (word 0 of quad 0 was the coin: the attempts start at word 1; t lies inside [0, I))
+            out = draw_unlisted<INVPREF_DICE_MAX_ATTEMPTS, 1>(
+                p, sid, k0, k1, x, excl_items, d,
+                [&](uint32_t word) { return pop_order[r_lo + (int)(((uint64_t)word * (uint64_t)(uint32_t)r_len) >> 32)]; },
+                n_forced + s);
         }
     }
     neg[(int64_t)s * neg_stride + p] = out;
@@ -132,14 +114,6 @@ inline Layout layout_of(int64_t U, int64_t I, int64_t B, int64_t D) {
     return L;
 }
 
-// sigmoid(x) in float64 without overflow: e = exp(-|x|), 1 / (1 + e) (x >= 0), e / (1 + e) (x < 0)
-__device__ __forceinline__ double sig64(double x) {
-    const double e = exp(-fabs(x));
-    return x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
-}
-// -log sigmoid(x) = max(-x, 0) + log1p(exp(-|x|))
-__device__ __forceinline__ double nls64(double x) { return fmax(-x, 0.0) + log1p(exp(-fabs(x))); }
-
 template <int NC, bool VEC>
 __global__ __launch_bounds__(256) void dice_pairs_kernel(const float *__restrict__ Iu, const float *__restrict__ Ii,
                                                          const float *__restrict__ Cu, const float *__restrict__ Ci, int U, int I,
@@ -153,9 +127,10 @@ __global__ __launch_bounds__(256) void dice_pairs_kernel(const float *__restrict
     const int p = (int)blockIdx.x * kGroups + threadIdx.x / kRow;
     double mine[kRec] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (p < B) {                                        // (the same for the 16 lanes of a group)
-        const int64_t u = users[p], i = pos_items[p], j = neg[p];
+        const int64_t u = users[p], i = pos_items[p];
+        const int j = neg[p];
         const double w = weights ? (double)weights[p] : 1.0;
-        const bool valid = u >= 0 && u < U && i >= 0 && i < I && j >= 0 && j < I;
+        const bool valid = triplet_ok(u, i, j, U, I);
         const int64_t uc = clamp_id(u, U), ic = clamp_id(i, I), jc = clamp_id(j, I);
         // the six gathers as one batch, in front of the first use
         float4 iu[NC], cu[NC], ii[NC], ij[NC], ci[NC], cj[NC];
@@ -178,15 +153,17 @@ __global__ __launch_bounds__(256) void dice_pairs_kernel(const float *__restrict
         ab = row16_sum64(ab);
         if (l16 == 0) {
             const double int_w = coefs3[0], con_w = coefs3[1], invB = 1.0 / (double)B;
-            const double xT = xI + xC;
-            const double gT = -w * sig64(-xT) * invB;
-            const double gI = m ? -int_w * w * sig64(-xI) * invB : 0.0;
-            const double gC = con_w * w * (m ? sig64(xC) : -sig64(-xC)) * invB;
+            // click on xT, interest on xI (masked triplets), conformity on y = -xC where the negative is the more popular item:
+            // sigmoid(xC) = sigmoid(-y) there, so the factor is +-sigmoid(-y)
+            const LogSig64 tT = logsig64(xI + xC), tI = logsig64(xI), tC = logsig64(m ? -xC : xC);
+            const double gT = -w * tT.sneg * invB;
+            const double gI = m ? -int_w * w * tI.sneg * invB : 0.0;
+            const double gC = con_w * w * (m ? tC.sneg : -tC.sneg) * invB;
             rec[p] = valid ? make_float2((float)(gT + gI), (float)(gT + gC)) : make_float2(0.0f, 0.0f);
             if (valid) {
-                mine[0] = w * nls64(xT);
-                mine[1] = m ? w * nls64(xI) : 0.0;
-                mine[2] = w * nls64(m ? -xC : xC);
+                mine[0] = w * tT.nls;
+                mine[1] = m ? w * tI.nls : 0.0;
+                mine[2] = w * tC.nls;
                 mine[3] = sq;
                 mine[4] = ab;
                 mine[6] = m ? 1.0 : 0.0;
@@ -199,13 +176,11 @@ __global__ __launch_bounds__(256) void dice_pairs_kernel(const float *__restrict
 }
 
 // does position y of the index (unclamped) belong to a non-skipped triplet?
-__device__ __forceinline__ bool triplet_ok(int y, int B, int U, int I, const int64_t *__restrict__ users,
-                                           const int64_t *__restrict__ pos_items, const int32_t *__restrict__ neg) {
+__device__ __forceinline__ bool position_ok(int y, int B, int U, int I, const int64_t *__restrict__ users,
+                                            const int64_t *__restrict__ pos_items, const int32_t *__restrict__ neg) {
     if (y < 0 || y >= 2 * B) return false;
     const int p = y < B ? y : y - B;
-    const int64_t u = users[p], i = pos_items[p];
-    const int j = neg[p];
-    return u >= 0 && u < U && i >= 0 && i < I && j >= 0 && j < I;
+    return triplet_ok(users[p], pos_items[p], neg[p], U, I);
 }
 
 // phi(a - b) over a row, each lane's chunks in order, then the 16 lanes by the fixed butterfly
@@ -249,7 +224,7 @@ __global__ __launch_bounds__(256) void dice_count_kernel(const float *__restrict
             for (int k = e; k < n2 && !in; k++) {
                 const int2 en = idx[k];
                 if (en.x != r) break;
-                in = triplet_ok(en.y, B, U, I, users, pos_items, neg);
+                in = position_ok(en.y, B, U, I, users, pos_items, neg);
             }
             if (in) row = r;
         }
@@ -276,23 +251,8 @@ __global__ __launch_bounds__(256) void dice_count_kernel(const float *__restrict
     group_sums<2>(mine, dpart, stride);
 }
 
-// fold64's sum (row_pass.hpp) with kFoldAhead loads issued before the first add: the order, and so the bits, are fold64's
-constexpr int kFoldAhead = 8;
-__device__ __forceinline__ double fold64_ahead(const double *__restrict__ v, int n) {
-    double t = 0.0;
-    int i = threadIdx.x & 63;
-    for (; i + 64 * (kFoldAhead - 1) < n; i += 64 * kFoldAhead) {
-        double x[kFoldAhead];
-#pragma unroll
-        for (int j = 0; j < kFoldAhead; j++) x[j] = v[i + 64 * j];
-#pragma unroll
-        for (int j = 0; j < kFoldAhead; j++) t = t + x[j];
-    }
-    for (; i < n; i += 64) t = t + v[i];
-    return wave_sum64(t);
-}
-
-// kSums waves, one per sum: the pairs launch's seven over nwg workgroups, the count launch's two over 2 ncw
+// kSums waves, one per sum (row_pass.hpp's fold64_ahead): the pairs launch's seven over nwg workgroups, the count launch's two
+// over 2 ncw
 __global__ __launch_bounds__(64 * kSums) void dice_fold_kernel(const double *__restrict__ partials, int nwg,
                                                                const double *__restrict__ dpart, int ncw2,
                                                                const int *__restrict__ counts, const double *__restrict__ coefs3,
@@ -322,42 +282,31 @@ __global__ __launch_bounds__(64 * kSums) void dice_fold_kernel(const double *__r
     losses8[7] = (float)sums[6];
 }
 
-// what the chunked scatter and boundary walk and their regularised policy base (chunk_walk.hpp) leave to this pass: BPR's
-// entries, the factor of the pair of tables the workgroup serves (blockIdx.y: con false the interest pair, record .x; con true
-// the conformity pair, record .y) and, through the StartsRows hook, the discrepancy gradient of a marked row in the chunk
-// where the row starts.  sib_u / sib_i: the OTHER pair's tables, for a - b
-struct DiceWalk : RegWalk {
-    using StartsRows = void;
-    struct Entry {
-        int64_t u, i;   // the triplet's three ids and its factor
-        int j;
-        float g;
-    };
-    int U, I, B, form;
-    bool con;
-    const int64_t *__restrict__ users, *__restrict__ pos_items;
-    const int32_t *__restrict__ neg;
+// chunk_walk.hpp's triplet walk with the factor of the pair of tables the workgroup serves (blockIdx.y: con false the interest
+// pair, record .x; con true the conformity pair, record .y) and, through the StartsRows hook, the discrepancy gradient of a
+// marked row in the chunk where the row starts.  sib_u / sib_i: the OTHER pair's tables, for a - b
+struct DiceRec {
     const float2 *__restrict__ rec;
+    bool con;
+    __device__ __forceinline__ float operator()(int p) const {
+        const float2 r = rec[p];
+        return con ? r.y : r.x;
+    }
+};
+struct DiceWalk : TripletWalk<DiceRec> {
+    using StartsRows = void;
+    int form;
     const float *__restrict__ sib_u, *__restrict__ sib_i;
     const unsigned char *__restrict__ marks;
     const int *__restrict__ counts;
     const double *__restrict__ coefs3;
 
+    // (TripletWalk's, with the record's load in front of the ids' as this pass has always issued it: the same kernels)
     __device__ __forceinline__ Entry load(int, int pos) const {
         const int p = pos < B ? pos : pos - B;
-        const float2 r = rec[p];
-        return Entry{users[p], pos_items[p], neg[p], con ? r.y : r.x};
+        const float g = fetch(p);
+        return Entry{users[p], pos_items[p], neg[p], g};
     }
-    __device__ __forceinline__ int64_t partner(int side, const Entry &e, int pos) const {
-        return side ? e.u : (pos < B ? e.i : (int64_t)e.j);
-    }
-    // the whole triplet decides, not the pair: a bad negative silences the positive's position too
-    __device__ __forceinline__ bool valid(const Entry &e, int y, int n2) const {
-        return !(y < 0 || y >= n2 || e.u < 0 || e.u >= U || e.i < 0 || e.i >= I || e.j < 0 || e.j >= I);
-    }
-    // (a triplet gathers its user rows once: the user side counts position p only)
-    __device__ __forceinline__ int gathers(int side, int pos) const { return (side || pos < B) ? 1 : 0; }
-    __device__ __forceinline__ float factor(const Entry &e, int pos) const { return pos < B ? e.g : -e.g; }
 
     template <int NC, bool VEC>
     __device__ __forceinline__ void finish_row(const float *__restrict__ dtab, int side, bool starts, int row, int D, int cnt,
@@ -401,7 +350,7 @@ __global__ __launch_bounds__(256) void dice_scatter_kernel(const float *__restri
                                                            float *__restrict__ gcu, float *__restrict__ gci,
                                                            double *__restrict__ part, int64_t part_half, int Dp) {
     const bool con = blockIdx.y != 0;
-    const DiceWalk pol{{r2, r1}, U, I, B, form, con, users, pos_items, neg, rec, con ? Iu : Cu, con ? Ii : Ci, marks, counts,
+    const DiceWalk pol{{{r2, r1}, U, I, B, users, pos_items, neg, {rec, con}}, form, con ? Iu : Cu, con ? Ii : Ci, marks, counts,
                        coefs3};
     chunk_scatter<NC, VEC>(pol, con ? Cu : Iu, U, con ? Ci : Ii, I, D, B, index, stride, C, nchunk, con ? gcu : giu,
                            con ? gci : gii, part + (con ? part_half : 0), Dp);
@@ -428,21 +377,18 @@ int invpref_dice_draw_hip(const int64_t *users, const int64_t *pos_items, int64_
                           const int32_t *pop_order, const int32_t *sorted_count, const int32_t *item_count, int64_t pool,
                           const double *step_margin, int64_t seed, int32_t *neg, int64_t neg_stride, int64_t batch_cap,
                           int32_t *n_forced, void *stream) {
-    if (!users || !pos_items || !step_lo || !step_n || !step_id || !excl_ptr || !pop_order || !sorted_count || !item_count ||
-        !step_margin || !neg || !n_forced || n_users_len < 1 || steps < 1 || excl_len < 0 || (excl_len > 0 && !excl_items) ||
-        user_num < 1 || item_num < 1 || pool < 1 || batch_cap < 1 || neg_stride < batch_cap)
-        return INVPREF_EINVAL;
-    if (item_num > kI32Max || user_num > kI32Max || excl_len > kI32Max || batch_cap > INVPREF_DICE_MAX_BATCH ||
-        steps > INVPREF_DICE_MAX_STEPS)
-        return INVPREF_EUNSUPPORTED;
+    if (!pos_items || !pop_order || !sorted_count || !item_count || !step_margin || pool < 1) return INVPREF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    int rc = (int)hipMemsetAsync(n_forced, 0, sizeof(int32_t) * (size_t)steps, st);
+    dim3 grid;
+    const int rc = draw_prepare(users, step_lo, step_n, step_id, excl_ptr, excl_items, neg, n_forced, n_users_len, steps, excl_len,
+                                user_num, item_num, neg_stride, batch_cap, INVPREF_DICE_MAX_BATCH, INVPREF_DICE_MAX_STEPS, st,
+                                grid);
     if (rc) return rc;
     const uint64_t bits = (uint64_t)seed;
-    hipLaunchKernelGGL(dice_draw_kernel, dim3((unsigned)((batch_cap + 255) / 256), (unsigned)steps), dim3(256), 0, st, users,
-                       pos_items, n_users_len, step_lo, step_n, step_id, excl_ptr, excl_items, (int)excl_len, user_num,
-                       (int)item_num, pop_order, sorted_count, item_count, (int)std::min<int64_t>(pool, kI32Max), step_margin,
-                       (uint32_t)bits, (uint32_t)(bits >> 32), neg, neg_stride, (int)batch_cap, n_forced);
+    hipLaunchKernelGGL(dice_draw_kernel, grid, dim3(256), 0, st, users, pos_items, n_users_len, step_lo, step_n, step_id, excl_ptr,
+                       excl_items, (int)excl_len, user_num, (int)item_num, pop_order, sorted_count, item_count,
+                       (int)std::min<int64_t>(pool, kI32Max), step_margin, (uint32_t)bits, (uint32_t)(bits >> 32), neg, neg_stride,
+                       (int)batch_cap, n_forced);
     return (int)hipGetLastError();
 }
 

@@ -14,10 +14,9 @@
 //             y = 1, the imputation pair -- the factor is h, valid() takes the positions below B, the tables are (Au, Ai)
 //             (as two launches each the Yahoo-shape pass measured 87.8 us against 65.8 us: kernels of 5 - 12 us in a row;
 //             the pairs share nothing but the index and the records, so each has a slot region of its own)
-//             in both, the rest is chunk_walk.hpp's RegWalk, the policy base shared with BPR's pass: at the end of a
-//             destination acc += n * regulariser gradient of the destination row, n the OBSERVED positions among the entries
-//             added (gathers()); float64 slots; a finished row is rounded once and stored
-//   fold      five waves, one per sum: the partials in workgroup order -> losses5
+//             in both, the rest is chunk_walk.hpp's RegWalk: the regulariser gradient at the end of a destination counts
+//             the OBSERVED positions among the entries added (gathers())
+//   fold      five waves, one per sum (row_pass.hpp's fold64_ahead): the partials in workgroup order -> losses5
 // Every row has one writer and every sum a fixed order: the same bits on every run.  All four gradient tables are zero-filled
 // on the stream in front of the scatters (rows without a position hold zeros afterwards), so the writers store and never read
 // the gradient tables.  A row that only drawn positions name is stored by the imputation walk too: zeros.
@@ -69,12 +68,6 @@ inline Layout layout_of(int64_t B, int64_t D) {
     L.part = ws.take(2 * L.walk.part_bytes<double>());   // a slot region per pair of tables
     L.total = ws.bytes();
     return L;
-}
-
-// sigmoid(x) in float64 without overflow: e = exp(-|x|), 1 / (1 + e) (x >= 0), e / (1 + e) (x < 0)
-__device__ __forceinline__ double sig64(double x) {
-    const double e = exp(-fabs(x));
-    return x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
 }
 
 template <int NC, bool VEC, int FORM>
@@ -153,25 +146,9 @@ __global__ __launch_bounds__(256) void dr_pairs_kernel(const float *__restrict__
     group_sums<kRec>(mine, partials, stride);
 }
 
-// fold64's sum (row_pass.hpp: lane l adds entries l, l + 64, ... in order, then the fixed butterfly) with kFoldAhead loads
-// issued before the first add: the order, and so the bits, are fold64's; the loads no longer wait for one another
-constexpr int kFoldAhead = 8;
-__device__ __forceinline__ double fold64_ahead(const double *__restrict__ v, int n) {
-    double t = 0.0;
-    int i = threadIdx.x & 63;
-    for (; i + 64 * (kFoldAhead - 1) < n; i += 64 * kFoldAhead) {
-        double x[kFoldAhead];
-#pragma unroll
-        for (int j = 0; j < kFoldAhead; j++) x[j] = v[i + 64 * j];
-#pragma unroll
-        for (int j = 0; j < kFoldAhead; j++) t = t + x[j];
-    }
-    for (; i < n; i += 64) t = t + v[i];
-    return wave_sum64(t);
-}
-
-// kRec waves, one per sum.  (One wave folding the five sums one after the other, a dependent load per step, took 982 us of the
-// 2 278 us pass at the MIND shape, where a sum has 32 768 partials: 2 560 load latencies in a row.)
+// kRec waves, one per sum, each by row_pass.hpp's fold64_ahead.  (One wave folding the five sums one after the other, a
+// dependent load per step, took 982 us of the 2 278 us pass at the MIND shape, where a sum has 32 768 partials: 2 560 load
+// latencies in a row.)
 __global__ __launch_bounds__(64 * kRec) void dr_fold_kernel(const double *__restrict__ partials, int nwg, int64_t stride, double B,
                                                             double D, double L2_coe, double L1_coe,
                                                             float *__restrict__ losses5) {

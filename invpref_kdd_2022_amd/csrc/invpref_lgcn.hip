@@ -14,9 +14,9 @@
 // A kernel boundary is the only synchronisation between workgroups; every row has one writer and every sum a fixed order: the
 // same bits on every run.  Nothing read from the device -- plan, row_ptr, columns -- is an address before it is range-checked.
 //
-// The regulariser.  Gather counts per row by integer atomics (a triplet with a bad id counts nowhere), then one group per
-// table row over the rows with a count: grad += n (2 L2_coe x + L1_coe sign(x)) / (B D), n |x|^2 and n |x|_1 as float64
-// partials per workgroup (row_pass.hpp's group_sums), folded in workgroup order.
+// The regulariser.  Gather counts per row by integer atomics (a triplet that fails chunk_walk.hpp's triplet_ok, the BPR pass's
+// own test, counts nowhere), then one group per table row over the rows with a count: grad += n (2 L2_coe x + L1_coe sign(x))
+// / (B D), n |x|^2 and n |x|_1 as float64 partials per workgroup (row_pass.hpp's group_sums), folded in workgroup order.
 #include "chunk_walk.hpp"
 
 #include "../../include/invpref_lgcn.h"
@@ -231,8 +231,9 @@ __global__ __launch_bounds__(256) void lgcn_count_kernel(const int64_t *__restri
                                                          int32_t *__restrict__ skipped) {
     const int p = (int)blockIdx.x * 256 + threadIdx.x;
     if (p >= B) return;
-    const int64_t u = users[p], i = pos_items[p], j = neg[p];
-    if (u >= 0 && u < U && i >= 0 && i < I && j >= 0 && j < I) {
+    const int64_t u = users[p], i = pos_items[p];
+    const int j = neg[p];
+    if (triplet_ok(u, i, j, U, I)) {
         atomicAdd(cnt_user + u, 1);
         atomicAdd(cnt_item + i, 1);
         atomicAdd(cnt_item + j, 1);

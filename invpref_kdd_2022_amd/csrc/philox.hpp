@@ -1,5 +1,6 @@
-// philox.hpp -- the counter-based generator of the device-side draws (invpref_rank_stats.hip's bootstrap, invpref_bpr.hip's
-// negatives): the same words for the same (counter, key) on every device and in the tests' numpy restatement.
+// philox.hpp -- the counter-based generator of the device-side draws (invpref_rank_stats.hip's bootstrap, neg_draw.hpp's
+// negatives, the doubly robust and sampled-softmax draws): the same words for the same (counter, key) on every device and in
+// the tests' numpy restatement.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

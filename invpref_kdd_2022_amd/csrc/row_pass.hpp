@@ -1,8 +1,9 @@
 // row_pass.hpp -- the gradient-pass recipe "pairs -> rows -> fold" that the MACR-MF and CausE baselines share (invpref_macr.hip,
 // invpref_cause.hip; invpref_lintrans.hip is on it too; step_wide.hpp's load_row / store_row family addresses rows differently
 // and stays apart).  chunk_walk.hpp builds on its float64 helpers -- double4_t, axpy_row, store_row -- for the chunked scatter
-// and boundary walk of the passes whose rows no row plan knows (invpref_cvib.hip, invpref_bpr.hip, invpref_dr.hip), which take dot64,
-// wave_sum64, group_sums and fold64 from here too.
+// and boundary walk of the passes whose rows no row plan knows (invpref_cvib.hip, invpref_bpr.hip, invpref_dr.hip,
+// invpref_ssm.hip, invpref_dice.hip), which take dot64, wave_sum64, group_sums, fold64 / fold64_ahead and the logistic terms
+// sig64 / logsig64 from here too.
 //
 //   pairs   one 16-lane group per position (lane l owns the float4 chunks l, l + 16, ... of a row: kernel_common.hpp): gathers
 //           the position's two rows, forms its loss terms (float64 partials per workgroup) and a small record of the position
@@ -47,6 +48,22 @@ __device__ __forceinline__ double bce64(double p, double y) {
     return (y - 1.0) * a - y * b;
 }
 __device__ __forceinline__ double dbce64(double p, double y) { return (p - y) / fmax((1.0 - p) * p, 1e-12); }
+
+// ---- the logistic terms of the pairwise passes (BPR, DICE, doubly robust), float64 without overflow, from e = exp(-|x|)
+// sigmoid(x): 1 / (1 + e) (x >= 0), e / (1 + e) (x < 0)
+__device__ __forceinline__ double sig64(double x) {
+    const double e = exp(-fabs(x));
+    return x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+}
+// a pair's loss and the factor of its gradient from ONE e: nls = -log sigmoid(x) = max(-x, 0) + log1p(e) and sneg =
+// sigmoid(-x) = e / (1 + e) (x >= 0), 1 / (1 + e) (x < 0) -- sig64(-x) bit for bit (0.5 at +-0, NaN stays NaN)
+struct LogSig64 {
+    double nls, sneg;
+};
+__device__ __forceinline__ LogSig64 logsig64(double x) {
+    const double e = exp(-fabs(x));
+    return LogSig64{fmax(-x, 0.0) + log1p(e), x >= 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e)};
+}
 
 __device__ __forceinline__ double row16_sum64(double x) {
 #pragma unroll
@@ -140,6 +157,22 @@ static __device__ __forceinline__ void group_sums(const double (&mine)[K], doubl
 __device__ __forceinline__ double fold64(const double *__restrict__ v, int n) {
     double t = 0.0;
     for (int i = threadIdx.x; i < n; i += 64) t = t + v[i];
+    return wave_sum64(t);
+}
+// fold64's sum by the wave the thread is in, with kFoldAhead loads issued before the first add: the order, and so the bits, are
+// fold64's; the loads no longer wait for one another
+constexpr int kFoldAhead = 8;
+__device__ __forceinline__ double fold64_ahead(const double *__restrict__ v, int n) {
+    double t = 0.0;
+    int i = threadIdx.x & 63;
+    for (; i + 64 * (kFoldAhead - 1) < n; i += 64 * kFoldAhead) {
+        double x[kFoldAhead];
+#pragma unroll
+        for (int j = 0; j < kFoldAhead; j++) x[j] = v[i + 64 * j];
+#pragma unroll
+        for (int j = 0; j < kFoldAhead; j++) t = t + x[j];
+    }
+    for (; i < n; i += 64) t = t + v[i];
     return wave_sum64(t);
 }
 

@@ -1099,6 +1099,18 @@ def _seed64(seed) -> int:
     return seed - (1 << 64) if seed >= 1 << 63 else seed
 
 
+def _draw_out(op: str, out, steps: int, batch_cap, device):
+    """(neg int32 [steps, batch_cap], n_forced int32 [steps]) of a rejection draw: `out` if given, else allocated"""
+    if out is None:
+        if batch_cap is None:
+            raise InvPrefError(f'{op}: give batch_cap (the row length of neg) or out=(neg, n_forced)')
+        out = (torch.empty(steps, int(batch_cap), dtype=torch.int32, device=device),
+               torch.empty(steps, dtype=torch.int32, device=device))
+    neg, n_forced = out
+    _gpu(neg, n_forced)
+    return neg, n_forced
+
+
 def bpr_draw(users: torch.Tensor, step_lo: torch.Tensor, step_n: torch.Tensor, step_id: torch.Tensor, exclude, item_num: int,
              seed: int = 0, batch_cap: Optional[int] = None, out=None):
     """The negatives of a run of steps in ONE launch.  Step s holds the step_n[s] (int32) positives whose users are
@@ -1111,14 +1123,7 @@ def bpr_draw(users: torch.Tensor, step_lo: torch.Tensor, step_n: torch.Tensor, s
     beyond step_n[s] and where the user id lies outside the table.  The caller guarantees step_n[s] <= batch_cap."""
     excl_ptr, excl_items = exclude
     _gpu(users, step_lo, step_n, step_id, excl_ptr, excl_items)
-    steps = step_lo.numel()
-    if out is None:
-        if batch_cap is None:
-            raise InvPrefError('bpr_draw: give batch_cap (the row length of neg) or out=(neg, n_forced)')
-        out = (torch.empty(steps, int(batch_cap), dtype=torch.int32, device=users.device),
-               torch.empty(steps, dtype=torch.int32, device=users.device))
-    neg, n_forced = out
-    _gpu(neg, n_forced)
+    neg, n_forced = _draw_out('bpr_draw', out, step_lo.numel(), batch_cap, users.device)
     _o().bpr_draw(users, step_lo, step_n, step_id, excl_ptr, excl_items, int(item_num), _seed64(seed), neg, n_forced)
     return neg, n_forced
 
@@ -1244,14 +1249,7 @@ def dice_draw(users: torch.Tensor, pos_items: torch.Tensor, step_lo: torch.Tenso
     if pos_items.numel() != users.numel():
         raise InvPrefError(f'dice_draw: {users.numel()} users for {pos_items.numel()} positive items')
     _gpu(users, pos_items, step_lo, step_n, step_id, excl_ptr, excl_items, item_count, pop_order, sorted_count, step_margin)
-    steps = step_lo.numel()
-    if out is None:
-        if batch_cap is None:
-            raise InvPrefError('dice_draw: give batch_cap (the row length of neg) or out=(neg, n_forced)')
-        out = (torch.empty(steps, int(batch_cap), dtype=torch.int32, device=users.device),
-               torch.empty(steps, dtype=torch.int32, device=users.device))
-    neg, n_forced = out
-    _gpu(neg, n_forced)
+    neg, n_forced = _draw_out('dice_draw', out, step_lo.numel(), batch_cap, users.device)
     _o().dice_draw(users, pos_items, step_lo, step_n, step_id, excl_ptr, excl_items, pop_order, sorted_count, item_count,
                    int(pool), step_margin, _seed64(seed), neg, n_forced)
     return neg, n_forced

@@ -772,6 +772,51 @@ def _pair_tables(op, user_table, item_table, grad_user=None, grad_item=None, out
     return U, I, D
 
 
+def _step_index(op, index, B, sides=2, source='one step of cvib_index_'):
+    """The check of one step's inverted index over 2 B positions, int32 [sides, at least 2 B, 2]; -> its stride"""
+    _capi._req(index, torch.int32, 'index')
+    if index.dim() != 3 or index.shape[0] != sides or index.shape[2] != 2 or index.shape[1] < 2 * B:
+        raise InvPrefError(f'{op}: index must be int32 [{sides}, at least {2 * B}, 2] ({source})')
+    return index.shape[1]
+
+
+def _step_triplets(users, pos_items, neg, weights):
+    """The checks of one step's triplets (users int64, pos_items int64, neg int32, optional fp32 weights: [B]); -> B"""
+    B = users.numel()
+    _req(users, torch.int64, 'users', (B,))
+    _req(pos_items, torch.int64, 'pos_items', (B,))
+    _req(neg, torch.int32, 'neg', (B,))
+    if weights is not None:
+        _req(weights, torch.float32, 'weights', (B,))
+    return B
+
+
+def _run_draw(op, users, step_lo, step_n, step_id, excl_ptr, excl_items, neg, n_forced, per_row=(), per_step=(), tables=()):
+    """The checks of a rejection draw over a run of steps (neg_draw.hpp) -> (steps, (neg_stride, batch_cap)), the pair as the C
+    entry takes it; neg may be rows of a wider buffer (the managers' staging rows).  per_row / per_step (tensor, dtype, name)
+    and tables (tensor, dtype, name, shape): a sampler's further checks, made where its own list had them"""
+    _req(users, torch.int64, 'users')
+    for x, dtype, name in per_row:
+        _req(x, dtype, name, (users.numel(),))
+    steps = step_lo.numel()
+    _req(step_lo, torch.int64, 'step_lo', (steps,))
+    _req(step_n, torch.int32, 'step_n', (steps,))
+    _req(step_id, torch.int64, 'step_id', (steps,))
+    for x, dtype, name in per_step:
+        _req(x, dtype, name, (steps,))
+    _req(excl_ptr, torch.int32, 'excl_ptr')
+    _req(excl_items, torch.int32, 'excl_items')
+    _req(n_forced, torch.int32, 'n_forced', (steps,))
+    for x, dtype, name, shape in tables:
+        _req(x, dtype, name, shape)
+    if not neg.is_cuda or neg.dtype != torch.int32 or neg.dim() != 2 or neg.shape[0] != steps or neg.shape[1] < 1 or \
+            (neg.stride(1) != 1 and neg.shape[1] > 1) or (steps > 1 and neg.stride(0) < neg.shape[1]):
+        raise InvPrefError(f'{op}: neg must be int32 [{steps}, batch_cap] on the GPU with unit stride inside a row')
+    if excl_ptr.numel() < 2:
+        raise InvPrefError(f'{op}: excl_ptr holds user_num + 1 entries')
+    return steps, (neg.stride(0) if steps > 1 else neg.shape[1], neg.shape[1])
+
+
 def _indexed_batch(n, U, I, users, items, scores, user_ptr, user_pos, item_ptr, item_pos, pre=''):
     """The checks of one batch of n (user, item, score) positions and its inverted index (ops.macr_index) over tables of U and I
     rows; pre: the prefix of the arguments' names"""
@@ -951,13 +996,11 @@ def _cvib_grad(user_table, item_table, users, items, draw_users, draw_items, ind
     _ids(items, 'items')
     _capi._req(draw_users, torch.int32, 'draw_users')
     _capi._req(draw_items, torch.int32, 'draw_items')
-    _capi._req(index, torch.int32, 'index')
     B = users.numel()
     if items.numel() != B or draw_users.numel() != B or draw_items.numel() != B:
         raise InvPrefError(f'cvib_grad: items, draw_users and draw_items must have the {B} entries of users')
-    if index.dim() != 3 or index.shape[0] != 2 or index.shape[2] != 2 or index.shape[1] < 2 * B:
-        raise InvPrefError(f'cvib_grad: index must be int32 [2, at least {2 * B}, 2] (one step of cvib_index_)')
+    stride = _step_index('cvib_grad', index, B)
     call('invpref_cvib_grad_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(items), B, ptr(draw_users),
-         ptr(draw_items), ptr(index), index.shape[1], _capi.IMPLICIT if implicit else 0, float(alpha), float(gamma),
+         ptr(draw_items), ptr(index), stride, _capi.IMPLICIT if implicit else 0, float(alpha), float(gamma),
          float(info_coe), float(eps), ptr(grad_user), ptr(grad_item), ptr(loss_out), ptr(info_out), ptr(pbar_out),
          ptr(qbar_out), ptr(workspace), workspace.numel(), stream_ptr())

@@ -13,8 +13,8 @@ from __future__ import annotations
 
 import torch
 
-from . import _capi, torch_ops
-from ._capi import InvPrefError, call, ptr, stream_ptr
+from . import torch_ops
+from ._capi import call, ptr, stream_ptr
 from .torch_ops import _req
 
 NAMES, _define, _impl, _fake = torch_ops.fragment()
@@ -25,23 +25,10 @@ _define('bpr_draw(Tensor users, Tensor step_lo, Tensor step_n, Tensor step_id, T
 
 @_impl('bpr_draw')
 def _bpr_draw(users, step_lo, step_n, step_id, excl_ptr, excl_items, item_num, seed, neg, n_forced):
-    _req(users, torch.int64, 'users')
-    steps = step_lo.numel()
-    _req(step_lo, torch.int64, 'step_lo', (steps,))
-    _req(step_n, torch.int32, 'step_n', (steps,))
-    _req(step_id, torch.int64, 'step_id', (steps,))
-    _req(excl_ptr, torch.int32, 'excl_ptr')
-    _req(excl_items, torch.int32, 'excl_items')
-    _req(n_forced, torch.int32, 'n_forced', (steps,))
-    # neg: [steps, batch_cap] rows of a wider buffer are welcome (the managers' staging rows), the entries of a row adjacent
-    if not neg.is_cuda or neg.dtype != torch.int32 or neg.dim() != 2 or neg.shape[0] != steps or neg.shape[1] < 1 or \
-            (neg.stride(1) != 1 and neg.shape[1] > 1) or (steps > 1 and neg.stride(0) < neg.shape[1]):
-        raise InvPrefError(f'bpr_draw: neg must be int32 [{steps}, batch_cap] on the GPU with unit stride inside a row')
-    if excl_ptr.numel() < 2:
-        raise InvPrefError('bpr_draw: excl_ptr holds user_num + 1 entries')
+    steps, neg_row = torch_ops._run_draw('bpr_draw', users, step_lo, step_n, step_id, excl_ptr, excl_items, neg, n_forced)
     call('invpref_bpr_draw_hip', ptr(users), users.numel(), ptr(step_lo), ptr(step_n), ptr(step_id), steps, ptr(excl_ptr),
          ptr(excl_items) if excl_items.numel() else None, excl_items.numel(), excl_ptr.numel() - 1, int(item_num), int(seed),
-         ptr(neg), neg.stride(0) if steps > 1 else neg.shape[1], neg.shape[1], ptr(n_forced), stream_ptr())
+         ptr(neg), *neg_row, ptr(n_forced), stream_ptr())
 
 
 _define('bpr_grad_(Tensor user_table, Tensor item_table, Tensor users, Tensor pos_items, Tensor neg, Tensor? weights, '
@@ -53,16 +40,9 @@ _define('bpr_grad_(Tensor user_table, Tensor item_table, Tensor users, Tensor po
 def _bpr_grad(user_table, item_table, users, pos_items, neg, weights, index, L2_coe, L1_coe, grad_user, grad_item, losses4,
               workspace):
     U, I, D = torch_ops._pair_tables('bpr_grad', user_table, item_table, grad_user, grad_item, workspace=workspace)
-    B = users.numel()
-    _req(users, torch.int64, 'users', (B,))
-    _req(pos_items, torch.int64, 'pos_items', (B,))
-    _req(neg, torch.int32, 'neg', (B,))
-    if weights is not None:
-        _req(weights, torch.float32, 'weights', (B,))
-    _capi._req(index, torch.int32, 'index')
-    if index.dim() != 3 or index.shape[0] != 2 or index.shape[2] != 2 or index.shape[1] < 2 * B:
-        raise InvPrefError(f'bpr_grad: index must be int32 [2, at least {2 * B}, 2] (one step of cvib_index_)')
+    B = torch_ops._step_triplets(users, pos_items, neg, weights)
+    stride = torch_ops._step_index('bpr_grad', index, B)
     _req(losses4, torch.float32, 'losses4', (4,))
     call('invpref_bpr_grad_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(pos_items), ptr(neg), ptr(weights),
-         B, ptr(index), index.shape[1], float(L2_coe), float(L1_coe), ptr(grad_user), ptr(grad_item), ptr(losses4),
+         B, ptr(index), stride, float(L2_coe), float(L1_coe), ptr(grad_user), ptr(grad_item), ptr(losses4),
          ptr(workspace), workspace.numel(), stream_ptr())

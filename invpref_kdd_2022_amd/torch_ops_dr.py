@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _capi, torch_ops
+from . import torch_ops
 from ._capi import InvPrefError, call, ptr, stream_ptr
 from .torch_ops import _req
 
@@ -58,11 +58,9 @@ def _dr_grad(form, user_table, item_table, imp_user_table, imp_item_table, users
         _req(weights, torch.float32, 'weights', (B,))
     _req(draw_users, torch.int32, 'draw_users', (B,))
     _req(draw_items, torch.int32, 'draw_items', (B,))
-    _capi._req(index, torch.int32, 'index')
-    if index.dim() != 3 or index.shape[0] != 2 or index.shape[2] != 2 or index.shape[1] < 2 * B:
-        raise InvPrefError(f'dr_grad: index must be int32 [2, at least {2 * B}, 2] (one step of cvib_index_)')
+    stride = torch_ops._step_index('dr_grad', index, B)
     _req(losses5, torch.float32, 'losses5', (5,))
     call('invpref_dr_grad_hip', int(form), ptr(user_table), U, ptr(item_table), I, ptr(imp_user_table), ptr(imp_item_table), D,
-         ptr(users), ptr(items), ptr(scores), ptr(weights), ptr(draw_users), ptr(draw_items), B, ptr(index), index.shape[1],
+         ptr(users), ptr(items), ptr(scores), ptr(weights), ptr(draw_users), ptr(draw_items), B, ptr(index), stride,
          float(L2_coe), float(L1_coe), ptr(grad_user), ptr(grad_item), ptr(grad_imp_user), ptr(grad_imp_item), ptr(losses5),
          ptr(workspace), workspace.numel(), stream_ptr())

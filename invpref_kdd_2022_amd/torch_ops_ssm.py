@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _capi, torch_ops
+from . import torch_ops
 from ._capi import InvPrefError, call, ptr, stream_ptr
 from .torch_ops import _req
 
@@ -53,10 +53,8 @@ def _ssm_grad(user_table, item_table, users, pos_items, neg, weights, item_bias,
         _req(weights, torch.float32, 'weights', (B,))
     if item_bias is not None:
         _req(item_bias, torch.float32, 'item_bias', (I,))
-    _capi._req(index, torch.int32, 'index')
-    if index.dim() != 3 or index.shape[0] != 3 or index.shape[2] != 2 or index.shape[1] < 2 * B:
-        raise InvPrefError(f'ssm_grad: index must be int32 [3, at least {2 * B}, 2] (ops.ssm_index)')
+    stride = torch_ops._step_index('ssm_grad', index, B, sides=3, source='ops.ssm_index')
     _req(losses4, torch.float32, 'losses4', (4,))
     call('invpref_ssm_grad_hip', ptr(user_table), U, ptr(item_table), I, D, ptr(users), ptr(pos_items), B, ptr(neg), M,
-         ptr(weights), ptr(item_bias), float(temperature), ptr(index), index.shape[1], float(L2_coe), float(L1_coe),
+         ptr(weights), ptr(item_bias), float(temperature), ptr(index), stride, float(L2_coe), float(L1_coe),
          ptr(grad_user), ptr(grad_item), ptr(losses4), ptr(workspace), workspace.numel(), stream_ptr())
