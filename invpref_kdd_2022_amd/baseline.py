@@ -2,7 +2,8 @@
 CVIB-MF and fairness-MF; and MACR-MF, LinearTrans-MF, CausE, BPR-MF and doubly robust MF, whose steps are gradient passes of
 their own (csrc/invpref_macr.hip, csrc/invpref_lintrans.hip, csrc/invpref_cause.hip, csrc/invpref_bpr.hip, csrc/invpref_dr.hip),
 sampled-softmax MF (csrc/invpref_ssm.hip), LightGCN, whose propagation is csrc/invpref_lgcn.hip and whose step is BPR's, and
-DICE, whose popularity-margin draw and four-table pass are csrc/invpref_dice.hip.
+DICE, whose popularity-margin draw and four-table pass are csrc/invpref_dice.hip; and EASE, the item-item ridge model in closed
+form (csrc/invpref_ease.hip), which has no embedding tables at all.
 
 Drop-in for the reference's ``PureMatrixFactorization`` / ``PureExplicitMatrixFactorization``
 (baseline_models.py:12-69, :652-704) and ``Basic{Implicit,Explicit}TrainManager`` /
@@ -2382,3 +2383,160 @@ class ALSTrainManager:
                       error_word=self.error_word)
         self.check_error()
         return out
+
+
+class EASEModel(nn.Module):
+    """EASE (Steck, WWW 2019): the item-item ridge model, score(u, .) = x_u . B with x_u the user's training counts and B fp32
+    [item_num, item_num] of zero diagonal (include/invpref_ease.h states the model).  `weight` is B, a parameter without
+    gradient: zeros until EASETrainManager.fit() has written it.  The training lists by user are buffers (`hist_ptr` int64
+    [user_num + 1], `hist_cols` int32), so that the model scores its training users from its state_dict alone.  Ranking is by
+    the raw score, no sigmoid: the evaluators take the model through predict()."""
+
+    def __init__(self, user_num: int, item_num: int):
+        super().__init__()
+        if not 1 <= int(item_num) <= _capi.EASE_MAX_ITEMS or int(user_num) < 1:
+            raise _capi.InvPrefError(f'EASEModel: {user_num} users x {item_num} items; EASE takes 1 .. {_capi.EASE_MAX_ITEMS} items')
+        self.user_num, self.item_num = int(user_num), int(item_num)
+        self.weight = nn.Parameter(torch.zeros(self.item_num, self.item_num), requires_grad=False)
+        self.register_buffer('hist_ptr', torch.zeros(self.user_num + 1, dtype=torch.int64))
+        self.register_buffer('hist_cols', torch.zeros(0, dtype=torch.int32))
+
+    def set_history(self, by_user) -> None:
+        """the training lists by user, as ops.ease_lists gives them"""
+        row_ptr, cols = by_user
+        if row_ptr.numel() != self.user_num + 1:
+            raise ValueError(f'the lists name {row_ptr.numel() - 1} users, the model has {self.user_num}')
+        dev = self.weight.device
+        self.hist_ptr = row_ptr.to(dev, torch.int64).contiguous()
+        self.hist_cols = cols.to(dev, torch.int32).contiguous()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        cols = state_dict.get(prefix + 'hist_cols')
+        if cols is not None and cols.shape != self.hist_cols.shape:   # (the one buffer whose length is the data's)
+            self.hist_cols = torch.zeros(cols.shape, dtype=torch.int32, device=self.hist_cols.device)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def predict(self, users_id) -> torch.Tensor:
+        """fp32 [n, item_num]: the raw scores of the training users `users_id` (an id outside the table scores zero)"""
+        users = users_id.reshape(-1).to(torch.int32)
+        return ops.ease_scores(self.weight.detach(), (self.hist_ptr, self.hist_cols), list_ids=users)
+
+    def predict_lists(self, item_lists) -> torch.Tensor:
+        """Fold-in: fp32 [n, item_num], the scores of users given by their item lists (an item listed twice counts twice) -- the
+        same kernel on arbitrary lists, nothing refitted."""
+        n = len(item_lists)
+        dev = self.weight.device
+        if n < 1:
+            return torch.zeros(0, self.item_num, dtype=torch.float32, device=dev)
+        lens = torch.tensor([len(l) for l in item_lists], dtype=torch.int64)
+        cols = torch.cat([torch.as_tensor(l, dtype=torch.int64).reshape(-1) for l in item_lists]) if int(lens.sum()) else \
+            torch.zeros(0, dtype=torch.int64)
+        if cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= self.item_num):
+            raise ValueError('predict_lists: an item id lies outside the item table')
+        row_ptr = torch.zeros(n + 1, dtype=torch.int64)
+        row_ptr[1:] = torch.cumsum(lens, 0)
+        return ops.ease_scores(self.weight.detach(), (row_ptr.to(dev), cols.to(torch.int32).to(dev)))
+
+    def _history_of(self, users):
+        """(ptr int32 [n + 1], items int32) of the training lists of `users`, gathered on the device"""
+        start = self.hist_ptr[users]
+        lens = self.hist_ptr[users + 1] - start
+        ptr = torch.zeros(users.numel() + 1, dtype=torch.int64, device=users.device)
+        ptr[1:] = torch.cumsum(lens, 0)
+        at = torch.arange(int(ptr[-1]), device=users.device) + torch.repeat_interleave(start - ptr[:-1], lens)
+        items = self.hist_cols[at] if at.numel() else torch.zeros(1, dtype=torch.int32, device=users.device)
+        return ptr.to(torch.int32), items.contiguous()
+
+    def recommend(self, users_id, k: int, exclude=True):
+        """Each user's top-k items by predict()'s scores -> (items int32 [n, k], scores fp32 [n, k]).  exclude: True leaves out
+        the user's training items.  Score matrices of at most 1 GiB at a time, as the evaluators bound theirs."""
+        users = users_id.reshape(-1).to(torch.int64)
+        n, k = users.numel(), int(k)
+        step = max(1, min(n, (1 << 28) // max(1, self.item_num + (3 * k if k > _capi.MAX_TOPK else 0))))
+        items, scores = [], []
+        for lo in range(0, n, step):
+            batch = users[lo:lo + step]
+            got = ops.topk_rows(self.predict(batch), k, mask=self._history_of(batch) if exclude else None)
+            items.append(got[0])
+            scores.append(got[1])
+        if not items:
+            dev = self.weight.device
+            return torch.empty(0, k, dtype=torch.int32, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
+        return (items[0], scores[0]) if len(items) == 1 else (torch.cat(items), torch.cat(scores))
+
+
+class EASETrainManager:
+    """Fits an EASEModel in closed form: row e of training_data is (user, item, label), and x_ui counts the rows of (u, i) with
+    label > 0 (a pair listed twice counts twice).  fit() is three launches -- ops.ease_gram (X^T X + reg I, exact integers),
+    ops.spd_inverse (float64, blocked, in place) and ops.ease_weights (one rounding to fp32 into the model's weight) -- with one
+    hyper-parameter, no learning rate and no sampling: not an epoch-engine manager, an "epoch" is the fit.  Single process.
+
+    reg <= 0, ids outside the tables, non-finite labels and counts beyond the Gram kernel's counters are refused at
+    construction, on the host; the device's sticky error word (a pivot that was not positive) is read after the fit and raises
+    InvPrefError.  keep_inverse keeps the float64 inverse of X^T X + reg I in `inverse` (8 item_num^2 bytes)."""
+
+    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, reg: float, *,
+                 keep_inverse: bool = False):
+        if not isinstance(model, EASEModel):
+            raise TypeError('EASETrainManager takes an EASEModel')
+        reg = float(reg)
+        if not (reg > 0 and reg < float('inf')):
+            raise ValueError('reg must be finite and > 0: it is what keeps X^T X + reg I positive definite')
+        data = torch.as_tensor(training_data).detach().cpu()
+        if data.dim() != 2 or data.shape[1] < 3 or data.shape[0] < 1:
+            raise ValueError('training_data holds rows of (user, item, label)')
+        if not bool(torch.isfinite(data.to(torch.float64)).all()):
+            raise ValueError('training_data holds non-finite values')
+        self.model, self.evaluator, self.device = model.to(device), evaluator, torch.device(device)
+        self.reg, self.keep_inverse = reg, bool(keep_inverse)
+        self.epoch_cnt, self.epochs, self.n_total = 0, 1, int(data.shape[0])
+        dev = self.device
+        self.lists = ops.ease_lists(data[:, 0].to(torch.int64).to(dev), data[:, 1].to(torch.int64).to(dev), data[:, 2].to(dev),
+                                    model.user_num, model.item_num)
+        self.model.set_history(self.lists[0])
+        self.n_skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.error_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.inverse = None
+
+    def enqueue_fit(self) -> None:
+        """the three launches on the current stream; nothing is read back"""
+        _, _, _, self.inverse = ops.ease_fit(self.lists, self.reg, out=self.model.weight.detach(), keep_inverse=self.keep_inverse,
+                                             n_skipped=self.n_skipped, error_word=self.error_word)
+        self.epoch_cnt = 1
+
+    def check_error(self) -> None:
+        word = int(self.error_word.item())
+        if word:
+            raise _capi.InvPrefError(f'EASE: X^T X + reg I was not positive definite in float64 or its inverse not finite (error '
+                                     f'word {word}); the weights are NaN')
+
+    def fit(self) -> None:
+        self.enqueue_fit()
+        self.check_error()
+
+    def train(self, silent: bool = False):
+        """((loss dicts, epochs), (test results, epochs)), the shape of ALSTrainManager.train(): the evaluation at "epoch" 0 (the
+        zero weights), the fit, the evaluation at epoch 1.  The closed form has no loss to report: the one loss dict is empty.
+        silent: nothing is printed and an evaluator with evaluate_async is called through it, its results read at the end."""
+        from .engine import transfer_loss_dict_to_line_str
+        evaluate = getattr(self.evaluator, 'evaluate_async', None) if silent else None
+        pending = evaluate is not None
+        evaluate = evaluate or self.evaluator.evaluate
+        tests, test_epochs = [], []
+
+        def test():
+            result = evaluate()
+            tests.append(result)
+            test_epochs.append(self.epoch_cnt)
+            if not silent:
+                print('test at epoch:', self.epoch_cnt)
+                print(transfer_loss_dict_to_line_str(result))
+        test()
+        self.enqueue_fit()
+        if not silent:
+            print('train epoch:', self.epoch_cnt)
+        test()
+        self.check_error()
+        if pending:
+            tests = [p.result() for p in tests]
+        return ([{}], [1]), (tests, test_epochs)

@@ -31,6 +31,7 @@ from . import torch_ops_als  # noqa: F401  (WMF by alternating least squares: to
 from . import torch_ops_segment_rank  # noqa: F401  (explicit evaluation's ranks: torch.ops.invpref.segment_ranks, auc_pairs)
 from . import torch_ops_key_sort  # noqa: F401  (the library's own sort: torch.ops.invpref.sort_keys_, auc_sorted)
 from . import torch_ops_lgcn  # noqa: F401  (LightGCN's fragment: torch.ops.invpref.lgcn_propagate, lgcn_reg_)
+from . import torch_ops_ease  # noqa: F401  (EASE's fragment: torch.ops.invpref.ease_gram, spd_inverse_, ease_weights, ease_scores)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -1455,6 +1456,126 @@ def als_csr(users: torch.Tensor, items: torch.Tensor, pref: torch.Tensor, conf: 
         row_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), 0)
         return row_ptr, cols[order].to(torch.int32).contiguous(), conf[order].contiguous(), pref[order].contiguous()
     return one(users, items, int(user_num)), one(items, users, int(item_num))
+
+
+# ---- EASE (include/invpref_ease.h, csrc/invpref_ease.hip)
+def ease_workspace_bytes(n: int) -> int:
+    """the scratch of spd_inverse on an n x n matrix (the inverse of the triangular factor, float64 [n, n]): a function of n
+    alone, non-decreasing; 0: not taken (n < 1, n > 65 536)"""
+    return int(_capi.lib().invpref_ease_workspace_bytes(int(n)))
+
+
+def ease_lists(users: torch.Tensor, items: torch.Tensor, labels: torch.Tensor, user_num: int, item_num: int):
+    """The two CSRs of the POSITIVE entries (label > 0) of a list of (user, item, label) rows, built once on the tensors' device:
+    -> (by_user, by_item), each (row_ptr int64 [rows + 1], cols int32), sorted by (row, column); a pair listed twice is kept
+    twice (it counts twice).  Refused here, on the host: ids outside the tables, non-finite labels, no positive entry, more than
+    INVPREF_EASE_MAX_ITEMS items, and data whose largest diagonal count sum_u x_ui^2 -- which bounds every entry of X^T X -- does
+    not fit the int32 counters of ease_gram."""
+    users, items = users.reshape(-1).to(torch.int64), items.reshape(-1).to(torch.int64)
+    labels = labels.reshape(-1)
+    n = users.numel()
+    user_num, item_num = int(user_num), int(item_num)
+    if n < 1 or items.numel() != n or labels.numel() != n:
+        raise InvPrefError('ease_lists: users, items and labels hold one value per entry, at least one entry')
+    if user_num < 1 or item_num < 1 or item_num > _capi.EASE_MAX_ITEMS:
+        raise InvPrefError(f'ease_lists: {user_num} users x {item_num} items; EASE takes 1 .. {_capi.EASE_MAX_ITEMS} items')
+    if int(users.min()) < 0 or int(users.max()) >= user_num or int(items.min()) < 0 or int(items.max()) >= item_num:
+        raise InvPrefError('ease_lists: an id lies outside its table')
+    if not bool(torch.isfinite(labels.to(torch.float64)).all()):
+        raise InvPrefError('ease_lists: a label is not finite')
+    keep = labels > 0
+    users, items = users[keep], items[keep]
+    if users.numel() < 1:
+        raise InvPrefError('ease_lists: no entry with a label > 0')
+    if users.numel() > 2 ** 31 - 1:
+        raise InvPrefError('ease_lists: more than 2^31 - 1 positive entries')
+    pairs, mult = torch.unique(users * item_num + items, return_counts=True)
+    diag = torch.zeros(item_num, dtype=torch.int64, device=users.device).index_add_(0, pairs % item_num, mult * mult)
+    if int(diag.max()) >= 1 << _capi.EASE_COUNT_BITS:
+        raise InvPrefError(f'ease_lists: the largest diagonal count of X^T X, {int(diag.max())}, does not fit the '
+                           f'{_capi.EASE_COUNT_BITS}-bit counters of ease_gram (INVPREF_EASE_COUNT_BITS)')
+
+    def one(rows, cols, n_rows, n_cols):
+        key = torch.sort(rows * n_cols + cols)[0]
+        row_ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
+        row_ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), 0)
+        return row_ptr, (key % n_cols).to(torch.int32).contiguous()
+    return one(users, items, user_num, item_num), one(items, users, item_num, user_num)
+
+
+def ease_gram(lists, lam: float, out: Optional[torch.Tensor] = None, n_skipped: Optional[torch.Tensor] = None):
+    """X^T X + lam I as float64 [I, I], full and symmetric, from lists = ease_lists(...): exact integer counts (LDS integer adds,
+    one writer per element), lam added once on the diagonal -- the bits of numpy's integer product.  A column outside its table
+    is skipped and counted in n_skipped (int32 [1], ADDED to; allocated zeroed when absent).  -> (out, n_skipped)."""
+    (user_ptr, user_cols), (item_ptr, item_cols) = lists
+    _gpu(user_ptr, user_cols, item_ptr, item_cols, out, n_skipped)
+    I, dev = item_ptr.numel() - 1, item_ptr.device
+    if out is None:
+        out = torch.empty(I, I, dtype=torch.float64, device=dev)
+    if n_skipped is None:
+        n_skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+    _o().ease_gram(user_ptr, user_cols, item_ptr, item_cols, float(lam), out, n_skipped)
+    return out, n_skipped
+
+
+def spd_inverse(a: torch.Tensor, error_word: Optional[torch.Tensor] = None, workspace: Optional[Workspace] = None):
+    """a <- a^-1 IN PLACE: a float64 [n, n], symmetric positive definite, n <= 65 536 (only the lower triangle is read; the
+    result is full and equal to its transpose bit for bit).  A blocked Cholesky factor, its inverse and their product, float64
+    MFMA tile products throughout, every sum in a fixed order.  A pivot that is not > 0: the result is NaN and bit 0 of
+    error_word (int32 [1], sticky; allocated zeroed when absent) is set.  -> (a, error_word).  No host sync; with a sized
+    workspace nothing is allocated: capturable."""
+    _gpu(a, error_word)
+    if a.dim() != 2 or a.shape[0] != a.shape[1]:
+        raise InvPrefError('spd_inverse: a must be a square float64 matrix')
+    nbytes = ease_workspace_bytes(a.shape[0])
+    if nbytes == 0:
+        raise InvPrefError(f'spd_inverse: n = {a.shape[0]} outside the kernels\' range (1 .. {_capi.EASE_MAX_ITEMS})')
+    if error_word is None:
+        error_word = torch.zeros(1, dtype=torch.int32, device=a.device)
+    _o().spd_inverse_(a, error_word, (workspace or Workspace(a.device)).get(nbytes))
+    return a, error_word
+
+
+def ease_weights(p: torch.Tensor, out: Optional[torch.Tensor] = None, error_word: Optional[torch.Tensor] = None):
+    """B fp32 [I, I] from P = A^-1 float64 [I, I]: B[i, j] = fp32(-P[i, j] / P[j, j]), B[j, j] = 0.  A column whose P[j, j] is
+    not finite and positive is NaN and sets bit 0 of error_word.  -> (out, error_word)."""
+    _gpu(p, out, error_word)
+    if out is None:
+        out = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+    if error_word is None:
+        error_word = torch.zeros(1, dtype=torch.int32, device=p.device)
+    _o().ease_weights(p, out, error_word)
+    return out, error_word
+
+
+def ease_scores(weight: torch.Tensor, csr, out: Optional[torch.Tensor] = None, row_ids: Optional[torch.Tensor] = None,
+                list_ids: Optional[torch.Tensor] = None):
+    """out[r, :] = fp32(sum over the r-th list, in CSR order, of float64(weight[cols[e], :])) for csr = (row_ptr int64
+    [lists + 1], cols int32): fp32 [rows, I].  The r-th list is list r, or with list_ids (int32 [rows]) list list_ids[r] -- a
+    batch of users against the CSR of all of them, an id outside it an empty list; with row_ids (int32 [rows]) it goes into row
+    row_ids[r] of `out` [any, I].  Without row_ids every row of out is written, an empty list with zeros.  One writer per
+    element, a fixed order: the bits of the numpy restatement."""
+    row_ptr, cols = csr
+    _gpu(weight, row_ptr, cols, out, row_ids, list_ids)
+    if out is None:
+        if row_ids is not None:
+            raise InvPrefError('ease_scores: the row_ids form writes into an `out` of the caller\'s')
+        rows = row_ptr.numel() - 1 if list_ids is None else list_ids.numel()
+        out = torch.empty(rows, weight.shape[0], dtype=torch.float32, device=weight.device)
+    _o().ease_scores(weight, row_ptr, cols, list_ids, row_ids, out)
+    return out
+
+
+def ease_fit(lists, reg: float, out: Optional[torch.Tensor] = None, keep_inverse: bool = False,
+             n_skipped: Optional[torch.Tensor] = None, error_word: Optional[torch.Tensor] = None,
+             workspace: Optional[Workspace] = None):
+    """EASE in closed form from lists = ease_lists(...): the three launches ease_gram, spd_inverse, ease_weights, enqueued back
+    to back with nothing read back -> (weight fp32 [I, I], n_skipped, error_word, inverse): the float64 inverse of X^T X + reg I
+    with keep_inverse, else None (its 8 I^2 bytes are freed).  The caller reads error_word when it wants to."""
+    a, n_skipped = ease_gram(lists, reg, n_skipped=n_skipped)
+    a, error_word = spd_inverse(a, error_word=error_word, workspace=workspace)
+    out, error_word = ease_weights(a, out=out, error_word=error_word)
+    return out, n_skipped, error_word, (a if keep_inverse else None)
 
 
 # ---- LightGCN (include/invpref_lgcn.h, csrc/invpref_lgcn.hip)
