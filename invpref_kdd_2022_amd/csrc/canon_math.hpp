@@ -119,14 +119,31 @@ __device__ __forceinline__ float c_sign(float x) { return (float)((x > 0.0f) - (
 // ---- M-step arithmetic: hardware transcendental units (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1 ulp).
 // The M-step is held to 1e-5 relative on the losses (north_star), not to bit equality -- float sums
 // over a minibatch reorder anyway -- so it does not pay for the canonical polynomials: a sigmoid is
-// 4 instructions here against ~40.  (The E-step and forward() keep the canonical forms.)
+// 5 instructions here against ~40.  (The E-step and forward() keep the canonical forms.)
 __device__ __forceinline__ float f_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float f_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504f); }
-__device__ __forceinline__ float f_log(float x) { return __builtin_amdgcn_logf(x) * 0.693147181f; }
-__device__ __forceinline__ float f_sigmoid(float x) { return f_rcp(1.0f + f_exp(-x)); }
+// The bare units read a subnormal argument as 0 and return 0 for a subnormal result; fp32 subnormals are otherwise kept (the
+// build passes no flush flag), and aten keeps them.  Two values of the chain depend on one, so these two scale around the unit
+// as the compiler's own log2f / division lowering does (IEEE multiplies, which honour subnormals):
+//   f_log      a subnormal argument -- sv = sp * sq for p + q in about (-103.3, -87.3), sp for p in (-88.7, -87.3) -- is
+//              scaled by 2^32 and 32 ln 2 taken off the result (unscaled: log(0), the clamp 100 for a loss of 87 .. 103).
+//              The product with ln 2 is an fma with that offset, 0 for a normal argument: the same float as the plain product.
+//   f_sigmoid  denominator and quotient are scaled by 2^-32, always: exact for every quotient that is a normal number (the
+//              denominator lies in [1, 2^128); fma(e, 2^-32, 2^-32) is fp32(1 + e) * 2^-32, the power of two commuting with
+//              the rounding), and one rounding into the subnormal range for x in (-88.7, -87.3), where the unscaled
+//              reciprocal returns 0
+// f_exp still returns 0 for a result below 2^-126: its users add it to values of order 1 (1 + exp(-x), a softmax sum).
+__device__ __forceinline__ float f_log(float x) {
+    const bool tiny = x < 1.17549435e-38f;
+    const float l2 = __builtin_amdgcn_logf(tiny ? x * 4294967296.0f : x);
+    return __builtin_fmaf(l2, 0.693147181f, tiny ? -22.1807098f : 0.0f);
+}
+__device__ __forceinline__ float f_sigmoid(float x) {
+    return f_rcp(__builtin_fmaf(f_exp(-x), 2.32830644e-10f, 2.32830644e-10f)) * 2.32830644e-10f;
+}
 // -log(s) and -log(1-s) with the reference's clamp at 100 (aten binary_cross_entropy)
 __device__ __forceinline__ float f_bce(float s, float y) {
-    float a = f_log(1.0f - s);
+    float a = __builtin_amdgcn_logf(1.0f - s) * 0.693147181f;   // (1 - s is 0 or at least 2^-24: never subnormal)
     a = a > -100.0f ? a : -100.0f;
     float b = f_log(s);
     b = b > -100.0f ? b : -100.0f;

@@ -121,6 +121,14 @@ def test_saturated_scores_follow_aten_clamps():
     og, ol = O.mstep(tab, u, v, e, y, None, COEFS, O.flags_of(True, False, False, True, False))
     assert np.isfinite(losses.cpu().numpy()).all()
     np.testing.assert_allclose(losses.cpu().numpy(), ol, rtol=1e-4)
+    # the gradients too: per interaction the canonical chain is the oracle's bit for bit, clamped denominators included, so an
+    # entry differs only by the order of its fp32 sum of at most B terms -- (B - 1) roundings of at most B max|term| on
+    # either side
+    tol = 2 * B * (B - 1) * 2.0 ** -24
+    for k, g, o in zip(O.PARAM_NAMES, G, og):
+        g = g.cpu().numpy()
+        assert np.isfinite(g).all() and np.isfinite(o).all(), k
+        assert relerr(g, o.reshape(g.shape)) <= tol, (k, relerr(g, o.reshape(g.shape)), tol)
 
 
 def test_train_loop_end_to_end_with_device_evaluator():
