@@ -21,6 +21,7 @@ _LGCN = ('LightGCNMatrixFactorization', 'LightGCNTrainManager')
 _DICE = ('DICEMatrixFactorization', 'DICETrainManager')
 
 _EASE = ('EASEModel', 'EASETrainManager')
+_MULTDAE = ('MultDAEModel', 'MultDAETrainManager')
 
 _EVALUATE = ('ExplicitRankTestManager',)
 
@@ -30,7 +31,7 @@ def __getattr__(name):   # resolved on first use: importing the package loads ne
         from . import evaluate
         return getattr(evaluate, name)
     if name in _FAIRNESS or name in _MACR or name in _LINTRANS or name in _CAUSE or name in _BPR or name in _DR \
-            or name in _ALS or name in _SSM or name in _LGCN or name in _DICE or name in _EASE:
+            or name in _ALS or name in _SSM or name in _LGCN or name in _DICE or name in _EASE or name in _MULTDAE:
         from . import baseline
         return getattr(baseline, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -108,7 +108,8 @@ FAIRNESS_TABLE_LDS = DEFINES['FAIRNESS_TABLE_LDS']   # distance-table entries th
 # (csrc/invpref_als.hip), the keys-only radix sort and the sort-based AUC (csrc/invpref_key_sort.hip), sampled-softmax MF's
 # shared-negative sampler and gradient pass (csrc/invpref_ssm.hip), LightGCN's propagation and ego regulariser
 # (csrc/invpref_lgcn.hip), DICE's popularity-margin negative sampler and four-table gradient pass (csrc/invpref_dice.hip), EASE's Gram matrix,
-# blocked SPD inverse, weights and scores (csrc/invpref_ease.hip).
+# blocked SPD inverse, weights and scores (csrc/invpref_ease.hip), Mult-DAE's encoder and full-catalogue gradient pass
+# (csrc/invpref_multdae.hip).
 MACR_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_macr.h')
 CAUSE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_cause.h')
 SCALED_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_retrieve_scaled.h')
@@ -158,6 +159,9 @@ EASE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_ease.h')
 EASE_SIGNATURES, EASE_DEFINES = _read_header(EASE_HEADER_PATH)
 EASE_MAX_ITEMS, EASE_BLOCK, EASE_GRAM_SLICE, EASE_COUNT_BITS = (
     EASE_DEFINES['EASE_' + n] for n in ('MAX_ITEMS', 'BLOCK', 'GRAM_SLICE', 'COUNT_BITS'))
+MULTDAE_HEADER_PATH = os.path.join(PKG, '..', 'include', 'invpref_multdae.h')
+MULTDAE_SIGNATURES, MULTDAE_DEFINES = _read_header(MULTDAE_HEADER_PATH)
+MULTDAE_MAX_BATCH, MULTDAE_MAX_ENTRIES = MULTDAE_DEFINES['MULTDAE_MAX_BATCH'], MULTDAE_DEFINES['MULTDAE_MAX_ENTRIES']
 CAUSE_MODE_ITEM, CAUSE_MODE_USER =CAUSE_DEFINES['CAUSE_MODE_ITEM'], CAUSE_DEFINES['CAUSE_MODE_USER']
 # (header, the names of its signature and define dicts in this module): lib() looks the dicts up when it runs
 EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_HEADER_PATH, 'CAUSE_SIGNATURES', 'CAUSE_DEFINES'),
@@ -173,7 +177,8 @@ EXTRA_HEADERS = ((MACR_HEADER_PATH, 'MACR_SIGNATURES', 'MACR_DEFINES'), (CAUSE_H
                  (ALS_HEADER_PATH, 'ALS_SIGNATURES', 'ALS_DEFINES'),
                  (KEY_SORT_HEADER_PATH, 'KEY_SORT_SIGNATURES', 'KEY_SORT_DEFINES'),
                  (SSM_HEADER_PATH, 'SSM_SIGNATURES', 'SSM_DEFINES'), (LGCN_HEADER_PATH, 'LGCN_SIGNATURES', 'LGCN_DEFINES'),
-                 (DICE_HEADER_PATH, 'DICE_SIGNATURES', 'DICE_DEFINES'), (EASE_HEADER_PATH, 'EASE_SIGNATURES', 'EASE_DEFINES'))
+                 (DICE_HEADER_PATH, 'DICE_SIGNATURES', 'DICE_DEFINES'), (EASE_HEADER_PATH, 'EASE_SIGNATURES', 'EASE_DEFINES'),
+                 (MULTDAE_HEADER_PATH, 'MULTDAE_SIGNATURES', 'MULTDAE_DEFINES'))
 
 _lib = None
 

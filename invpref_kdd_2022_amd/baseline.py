@@ -2187,10 +2187,53 @@ class DRExplicitTrainManager(_DRManagerMixin, BasicExplicitTrainManager):
     """doubly robust MF on explicit feedback (form 1: squared error) over a DRExplicitMatrixFactorization"""
 
 
+class _EnqueuedEpochsLoop:
+    """train() of the managers that are not epoch-engine managers (ALS, Mult-DAE): they offer train_epochs(n, sync), read_back(),
+    epoch_cnt, epochs, evaluate_interval, test_begin_epoch and an evaluator."""
+
+    def train(self, silent: bool = False, auto: bool = False):
+        """((loss dicts, epochs), (test results, epochs)): the outer loop of the epoch engine's train() -- the epoch-0
+        evaluation first, the sweeps up to the next evaluation enqueued together, nothing read back inside the loop when
+        nothing is printed (an evaluator with evaluate_async is then called through it)."""
+        from .engine import transfer_loss_dict_to_line_str
+        test_result_list, test_epoch_list = [], []
+        loss_result_list, train_epoch_index_list = [], []
+        defer = bool(silent or auto)
+        evaluate = getattr(self.evaluator, 'evaluate_async', None) if defer else None
+        pending = evaluate is not None
+        evaluate = evaluate or self.evaluator.evaluate
+
+        def test():
+            result = evaluate()
+            test_result_list.append(result)
+            test_epoch_list.append(self.epoch_cnt)
+            if not defer:
+                print('test at epoch:', self.epoch_cnt)
+                print(transfer_loss_dict_to_line_str(result))
+        test()
+        while self.epoch_cnt < self.epochs:
+            first = self.epoch_cnt + 1
+            to_event = self.evaluate_interval - self.epoch_cnt % self.evaluate_interval
+            run = self.train_epochs(min(to_event, self.epochs - self.epoch_cnt), sync=not defer)
+            for i in range(len(run)):
+                train_epoch_index_list.append(first + i)
+                loss_result_list.append(run[i])
+                if not defer:
+                    print('train epoch:', first + i)
+                    print(transfer_loss_dict_to_line_str(run[i]))
+            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
+                test()
+        if defer:  # one read-back for everything
+            loss_result_list = self.read_back(torch.stack(loss_result_list)) if loss_result_list else []
+            if pending:
+                test_result_list = [p.result() for p in test_result_list]
+        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
+
+
 ALS_LOSS_KEYS = ['fit_loss', 'L2_reg', 'loss']
 
 
-class ALSTrainManager:
+class ALSTrainManager(_EnqueuedEpochsLoop):
     """Weighted matrix factorization solved as Hu, Koren and Volinsky (ICDM 2008) solve it: alternating least squares on a
     plain PureMatrixFactorization (include/invpref_als.h states the model).  Row e of training_data is the entry (user, item,
     label): preference p_e = 1 if label > 0 else 0 (a listed 0 is an observed negative), confidence c_e = 1 + alpha * w_e with w_e the label or the caller's `weights` (one value per
@@ -2310,44 +2353,6 @@ class ALSTrainManager:
             self.epoch_cnt += 1
         return self.read_back(losses) if sync else losses
 
-    def train(self, silent: bool = False, auto: bool = False):
-        """((loss dicts, epochs), (test results, epochs)): the outer loop of the epoch engine's train() -- the epoch-0
-        evaluation first, the sweeps up to the next evaluation enqueued together, nothing read back inside the loop when
-        nothing is printed (an evaluator with evaluate_async is then called through it)."""
-        from .engine import transfer_loss_dict_to_line_str
-        test_result_list, test_epoch_list = [], []
-        loss_result_list, train_epoch_index_list = [], []
-        defer = bool(silent or auto)
-        evaluate = getattr(self.evaluator, 'evaluate_async', None) if defer else None
-        pending = evaluate is not None
-        evaluate = evaluate or self.evaluator.evaluate
-
-        def test():
-            result = evaluate()
-            test_result_list.append(result)
-            test_epoch_list.append(self.epoch_cnt)
-            if not defer:
-                print('test at epoch:', self.epoch_cnt)
-                print(transfer_loss_dict_to_line_str(result))
-        test()
-        while self.epoch_cnt < self.epochs:
-            first = self.epoch_cnt + 1
-            to_event = self.evaluate_interval - self.epoch_cnt % self.evaluate_interval
-            run = self.train_epochs(min(to_event, self.epochs - self.epoch_cnt), sync=not defer)
-            for i in range(len(run)):
-                train_epoch_index_list.append(first + i)
-                loss_result_list.append(run[i])
-                if not defer:
-                    print('train epoch:', first + i)
-                    print(transfer_loss_dict_to_line_str(run[i]))
-            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
-                test()
-        if defer:  # one read-back for everything
-            loss_result_list = self.read_back(torch.stack(loss_result_list)) if loss_result_list else []
-            if pending:
-                test_result_list = [p.result() for p in test_result_list]
-        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
-
     # ---- fold-in
     def fold_in(self, item_lists, pref=None, conf=None) -> torch.Tensor:
         """The vectors of users given by their item lists, solved against the item table as it is and its Gram matrix: the user
@@ -2385,19 +2390,13 @@ class ALSTrainManager:
         return out
 
 
-class EASEModel(nn.Module):
-    """EASE (Steck, WWW 2019): the item-item ridge model, score(u, .) = x_u . B with x_u the user's training counts and B fp32
-    [item_num, item_num] of zero diagonal (include/invpref_ease.h states the model).  `weight` is B, a parameter without
-    gradient: zeros until EASETrainManager.fit() has written it.  The training lists by user are buffers (`hist_ptr` int64
-    [user_num + 1], `hist_cols` int32), so that the model scores its training users from its state_dict alone.  Ranking is by
-    the raw score, no sigmoid: the evaluators take the model through predict()."""
+class _HistoryModel:
+    """What the models that score a user from the list of its training items share (EASE, Mult-DAE), in front of nn.Module: the
+    training lists by user as buffers (`hist_ptr` int64 [user_num + 1], `hist_cols` int32), so that the model scores its
+    training users from its state_dict alone; arbitrary lists as a CSR (fold-in); recommend() in bounded batches over the
+    model's predict()."""
 
-    def __init__(self, user_num: int, item_num: int):
-        super().__init__()
-        if not 1 <= int(item_num) <= _capi.EASE_MAX_ITEMS or int(user_num) < 1:
-            raise _capi.InvPrefError(f'EASEModel: {user_num} users x {item_num} items; EASE takes 1 .. {_capi.EASE_MAX_ITEMS} items')
-        self.user_num, self.item_num = int(user_num), int(item_num)
-        self.weight = nn.Parameter(torch.zeros(self.item_num, self.item_num), requires_grad=False)
+    def _init_history(self) -> None:
         self.register_buffer('hist_ptr', torch.zeros(self.user_num + 1, dtype=torch.int64))
         self.register_buffer('hist_cols', torch.zeros(0, dtype=torch.int32))
 
@@ -2406,7 +2405,7 @@ class EASEModel(nn.Module):
         row_ptr, cols = by_user
         if row_ptr.numel() != self.user_num + 1:
             raise ValueError(f'the lists name {row_ptr.numel() - 1} users, the model has {self.user_num}')
-        dev = self.weight.device
+        dev = self.hist_ptr.device
         self.hist_ptr = row_ptr.to(dev, torch.int64).contiguous()
         self.hist_cols = cols.to(dev, torch.int32).contiguous()
 
@@ -2416,26 +2415,18 @@ class EASEModel(nn.Module):
             self.hist_cols = torch.zeros(cols.shape, dtype=torch.int32, device=self.hist_cols.device)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    def predict(self, users_id) -> torch.Tensor:
-        """fp32 [n, item_num]: the raw scores of the training users `users_id` (an id outside the table scores zero)"""
-        users = users_id.reshape(-1).to(torch.int32)
-        return ops.ease_scores(self.weight.detach(), (self.hist_ptr, self.hist_cols), list_ids=users)
-
-    def predict_lists(self, item_lists) -> torch.Tensor:
-        """Fold-in: fp32 [n, item_num], the scores of users given by their item lists (an item listed twice counts twice) -- the
-        same kernel on arbitrary lists, nothing refitted."""
-        n = len(item_lists)
-        dev = self.weight.device
-        if n < 1:
-            return torch.zeros(0, self.item_num, dtype=torch.float32, device=dev)
+    def _lists_csr(self, item_lists):
+        """(row_ptr int64 [n + 1], cols int32) on the model's device of users given by their item lists; ids outside the item
+        table are refused"""
+        dev = self.hist_ptr.device
         lens = torch.tensor([len(l) for l in item_lists], dtype=torch.int64)
         cols = torch.cat([torch.as_tensor(l, dtype=torch.int64).reshape(-1) for l in item_lists]) if int(lens.sum()) else \
             torch.zeros(0, dtype=torch.int64)
         if cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= self.item_num):
             raise ValueError('predict_lists: an item id lies outside the item table')
-        row_ptr = torch.zeros(n + 1, dtype=torch.int64)
+        row_ptr = torch.zeros(len(item_lists) + 1, dtype=torch.int64)
         row_ptr[1:] = torch.cumsum(lens, 0)
-        return ops.ease_scores(self.weight.detach(), (row_ptr.to(dev), cols.to(torch.int32).to(dev)))
+        return row_ptr.to(dev), cols.to(torch.int32).to(dev)
 
     def _history_of(self, users):
         """(ptr int32 [n + 1], items int32) of the training lists of `users`, gathered on the device"""
@@ -2460,9 +2451,37 @@ class EASEModel(nn.Module):
             items.append(got[0])
             scores.append(got[1])
         if not items:
-            dev = self.weight.device
+            dev = self.hist_ptr.device
             return torch.empty(0, k, dtype=torch.int32, device=dev), torch.empty(0, k, dtype=torch.float32, device=dev)
         return (items[0], scores[0]) if len(items) == 1 else (torch.cat(items), torch.cat(scores))
+
+
+class EASEModel(_HistoryModel, nn.Module):
+    """EASE (Steck, WWW 2019): the item-item ridge model, score(u, .) = x_u . B with x_u the user's training counts and B fp32
+    [item_num, item_num] of zero diagonal (include/invpref_ease.h states the model).  `weight` is B, a parameter without
+    gradient: zeros until EASETrainManager.fit() has written it.  The training lists by user are buffers (`hist_ptr` int64
+    [user_num + 1], `hist_cols` int32), so that the model scores its training users from its state_dict alone.  Ranking is by
+    the raw score, no sigmoid: the evaluators take the model through predict()."""
+
+    def __init__(self, user_num: int, item_num: int):
+        super().__init__()
+        if not 1 <= int(item_num) <= _capi.EASE_MAX_ITEMS or int(user_num) < 1:
+            raise _capi.InvPrefError(f'EASEModel: {user_num} users x {item_num} items; EASE takes 1 .. {_capi.EASE_MAX_ITEMS} items')
+        self.user_num, self.item_num = int(user_num), int(item_num)
+        self.weight = nn.Parameter(torch.zeros(self.item_num, self.item_num), requires_grad=False)
+        self._init_history()
+
+    def predict(self, users_id) -> torch.Tensor:
+        """fp32 [n, item_num]: the raw scores of the training users `users_id` (an id outside the table scores zero)"""
+        users = users_id.reshape(-1).to(torch.int32)
+        return ops.ease_scores(self.weight.detach(), (self.hist_ptr, self.hist_cols), list_ids=users)
+
+    def predict_lists(self, item_lists) -> torch.Tensor:
+        """Fold-in: fp32 [n, item_num], the scores of users given by their item lists (an item listed twice counts twice) -- the
+        same kernel on arbitrary lists, nothing refitted."""
+        if len(item_lists) < 1:
+            return torch.zeros(0, self.item_num, dtype=torch.float32, device=self.weight.device)
+        return ops.ease_scores(self.weight.detach(), self._lists_csr(item_lists))
 
 
 class EASETrainManager:
@@ -2540,3 +2559,169 @@ class EASETrainManager:
         if pending:
             tests = [p.result() for p in tests]
         return ([{}], [1]), (tests, test_epochs)
+
+
+# ------------------------------------------------------------------------------------------------ Mult-DAE
+MULTDAE_LOSS_KEYS = ['score_loss', 'L2_reg', 'loss']
+
+
+class MultDAEModel(_HistoryModel, nn.Module):
+    """Mult-DAE (Liang, Krishnan, Hoffman and Jebara, WWW 2018) with the paper's architecture [I -> D -> I]: z_u = tanh(enc_bias +
+    s_u sum of the rows of `enc` the user's list names), scores z_u . dec[j] + dec_bias[j] over the whole catalogue
+    (include/invpref_multdae.h states the model).  No user table: a user is the list of its items, so predict_lists() scores
+    users that were not in training.  The training lists by user are buffers (`hist_ptr`, `hist_cols`), as EASEModel's.  Xavier-
+    normal tables and zero biases from torch's generator.  Ranking is by the raw logit: the evaluators take the model through
+    predict()."""
+
+    def __init__(self, user_num: int, item_num: int, factor_num: int):
+        super().__init__()
+        if int(user_num) < 1 or int(item_num) < 1 or not 1 <= int(factor_num) <= _capi.DEFINES['MAX_FACTORS']:
+            raise _capi.InvPrefError(f'MultDAEModel: {user_num} users x {item_num} items, factor_num {factor_num}; the kernels '
+                                     f'take 1 .. {_capi.DEFINES["MAX_FACTORS"]} factors')
+        self.user_num, self.item_num, self.factor_num = int(user_num), int(item_num), int(factor_num)
+        self.enc = nn.Parameter(nn.init.xavier_normal_(torch.empty(self.item_num, self.factor_num)), requires_grad=False)
+        self.enc_bias = nn.Parameter(torch.zeros(self.factor_num), requires_grad=False)
+        self.dec = nn.Parameter(nn.init.xavier_normal_(torch.empty(self.item_num, self.factor_num)), requires_grad=False)
+        self.dec_bias = nn.Parameter(torch.zeros(self.item_num), requires_grad=False)
+        self._init_history()
+
+    def tables(self):
+        return [self.enc, self.enc_bias, self.dec, self.dec_bias]
+
+    def _scores(self, lists, list_ids: torch.Tensor) -> torch.Tensor:
+        """the encoder at p = 0, the score product, the bias"""
+        z = ops.multdae_encode(self.enc.detach(), self.enc_bias.detach(), lists, list_ids)
+        scores = ops.predict(z, self.dec.detach(), torch.arange(z.shape[0], device=z.device), sigmoid=False)
+        return scores.add_(self.dec_bias.detach())
+
+    def predict(self, users_id) -> torch.Tensor:
+        """fp32 [n, item_num]: the raw logits of the training users `users_id` (an id outside the table scores as an empty
+        list)"""
+        return self._scores((self.hist_ptr, self.hist_cols), users_id.reshape(-1).to(torch.int32))
+
+    def predict_lists(self, item_lists) -> torch.Tensor:
+        """Fold-in: fp32 [n, item_num], the logits of users given by their item lists (an item listed twice counts twice) -- the
+        same kernels on arbitrary lists, nothing refitted."""
+        n = len(item_lists)
+        if n < 1:
+            return torch.zeros(0, self.item_num, dtype=torch.float32, device=self.enc.device)
+        return self._scores(self._lists_csr(item_lists), torch.arange(n, dtype=torch.int32, device=self.enc.device))
+
+
+class MultDAETrainManager(_EnqueuedEpochsLoop, _SingleProcessMixin):
+    """Trains a MultDAEModel by gradient steps on the multinomial likelihood over the WHOLE catalogue (ops.multdae_grad: no [B, I]
+    array) with Adam.  Row e of training_data is (user, item, label); rows with label <= 0 are dropped, a pair listed twice
+    counts twice (the lists come from ops.ease_lists, so at most INVPREF_EASE_MAX_ITEMS items and its count limit: refused
+    here by name).  Not an epoch-engine manager: its minibatches are USERS, batch_size consecutive ones, static, each one's
+    inverted index built once.  One flat buffer holds the four parameters (the model's parameters are views of it), likewise
+    the gradients and Adam's two moments: a step is the pass plus ONE ops.adam_ launch.  The dropout mask of a step is named by
+    (seed, the global step counter): the same seed gives the same bits whatever the run lengths.  Single process."""
+    _SINGLE = 'Mult-DAE trains in a single process: its step sweeps the whole catalogue per user and shares no row plan to shard'
+
+    def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
+                 evaluate_interval: int, lr: float, L2_coe: float, *, dropout: float = 0.5, seed: int = 0,
+                 test_begin_epoch: int = 0, world_size=None):
+        self._require_single_process(world_size)
+        if not isinstance(model, MultDAEModel):
+            raise TypeError('MultDAETrainManager takes a MultDAEModel')
+        if model.item_num > _capi.EASE_MAX_ITEMS:   # (ops.ease_lists, which builds the training lists, stops there)
+            raise _capi.InvPrefError(f'MultDAETrainManager: {model.item_num} items; the training lists come from ops.ease_lists, '
+                                     f'which takes at most {_capi.EASE_MAX_ITEMS} (the pass itself takes any catalogue: '
+                                     f'ops.multdae_grad on lists of the caller\'s)')
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError('dropout must lie in [0, 1)')
+        if int(batch_size) < 1 or int(batch_size) > _capi.MULTDAE_MAX_BATCH:
+            raise ValueError(f'batch_size must lie in 1 .. {_capi.MULTDAE_MAX_BATCH} users')
+        if not (float(lr) > 0 and float(L2_coe) >= 0):
+            raise ValueError('lr must be > 0 and L2_coe >= 0')
+        data = torch.as_tensor(training_data).detach().cpu()
+        if data.dim() != 2 or data.shape[1] < 3 or data.shape[0] < 1:
+            raise ValueError('training_data holds rows of (user, item, label)')
+        for t in model.tables():
+            if not bool(torch.isfinite(t.detach()).all()):
+                raise ValueError('the model\'s tables hold non-finite values')
+        self.model, self.evaluator, self.device = model.to(device), evaluator, torch.device(device)
+        self.batch_size, self.epochs, self.evaluate_interval = int(batch_size), int(epochs), int(evaluate_interval)
+        self.test_begin_epoch, self.lr, self.L2_coe = int(test_begin_epoch), float(lr), float(L2_coe)
+        self.dropout, self.seed = float(dropout), int(seed)
+        self.epoch_cnt, self.step_cnt = 0, 0
+        dev = self.device
+        by_user, _ = ops.ease_lists(data[:, 0].to(torch.int64).to(dev), data[:, 1].to(torch.int64).to(dev), data[:, 2].to(dev),
+                                    model.user_num, model.item_num)
+        self.lists = by_user
+        self.model.set_history(by_user)
+        # one flat buffer, each tensor from a multiple of four floats: the tables' rows stay 16-byte aligned
+        shapes = [tuple(t.shape) for t in model.tables()]
+        sizes = [int(np.prod(s)) for s in shapes]
+        offsets = np.cumsum([0] + [(n + 3) // 4 * 4 for n in sizes])
+        self._flat = torch.zeros(int(offsets[-1]), dtype=torch.float32, device=dev)
+        self._grad, self._exp_avg, self._exp_avg_sq = (torch.zeros_like(self._flat) for _ in range(3))
+        self._params, self._grads = [], []
+        for t, o, n, s in zip(model.tables(), offsets, sizes, shapes):
+            view = self._flat[int(o):int(o) + n].view(s)
+            view.copy_(t.detach())
+            t.data = view
+            self._params.append(view)
+            self._grads.append(self._grad[int(o):int(o) + n].view(s))
+        self.batches = []
+        for lo in range(0, model.user_num, self.batch_size):
+            users = torch.arange(lo, min(lo + self.batch_size, model.user_num), dtype=torch.int32, device=dev)
+            self.batches.append((users, ops.multdae_index(self.lists, users, model.item_num)))
+        self._ws = ops.Workspace(dev)
+        self._ws.get(max(self._workspace_bytes(users, index) for users, index in self.batches))
+
+    def _workspace_bytes(self, users, index) -> int:
+        n2 = (index.numel() - users.numel() - 1) // 5
+        return ops.multdae_workspace_bytes(self.model.item_num, users.numel(), n2, self.model.factor_num)
+
+    def _step(self, users, index, step_word: torch.Tensor, losses3: torch.Tensor) -> None:
+        """the pass and ONE Adam launch over the flat buffers"""
+        ops.multdae_grad(self._params, self._grads, self.lists, users, index, self.dropout, self.seed, step_word, self.L2_coe,
+                         losses3, workspace=self._ws)
+        self.step_cnt += 1
+        ops.adam_(self._flat, self._grad, self._exp_avg, self._exp_avg_sq, self.step_cnt, self.lr)
+
+    @staticmethod
+    def loss_dicts(dev_losses: torch.Tensor) -> list:
+        return [dict(zip(MULTDAE_LOSS_KEYS, v)) for v in dev_losses.reshape(-1, 3).tolist()]
+
+    def read_back(self, dev_losses: torch.Tensor) -> list:
+        """the loss dicts of a [n, 3] device tensor: an epoch's terms are the means over its steps"""
+        return self.loss_dicts(dev_losses)
+
+    def train_epochs(self, n: int, sync: bool = True):
+        """n epochs over the static minibatches, enqueued back to back; the steps' ids are one arange on the device.  sync: ONE
+        read-back -> the n loss dicts; otherwise the fp32 [n, 3] device tensor (read it with read_back)."""
+        n, nb = max(int(n), 0), len(self.batches)
+        step_ids = torch.arange(self.step_cnt, self.step_cnt + n * nb, dtype=torch.int64, device=self.device)
+        losses = torch.empty(n, nb, 3, dtype=torch.float32, device=self.device)
+        for k in range(n):
+            for b, (users, index) in enumerate(self.batches):
+                self._step(users, index, step_ids[k * nb + b:k * nb + b + 1], losses[k, b])
+            self.epoch_cnt += 1
+        out = losses.mean(1) if n else losses.reshape(0, 3)
+        return self.read_back(out) if sync else out
+
+    def train_a_epoch(self) -> dict:
+        return self.train_epochs(1)[0]
+
+    @staticmethod
+    def caller_users(users, user_num: int) -> torch.Tensor:
+        """a caller's list of users as int32 list ids, checked on the host: 1 .. INVPREF_MULTDAE_MAX_BATCH ids inside the lists"""
+        users = torch.as_tensor(users).detach().cpu().reshape(-1)
+        if users.numel() < 1 or users.numel() > _capi.MULTDAE_MAX_BATCH:
+            raise ValueError(f'train_a_batch takes 1 .. {_capi.MULTDAE_MAX_BATCH} users')
+        if users.dtype.is_floating_point or users.dtype == torch.bool:
+            raise ValueError('train_a_batch takes integer user ids')
+        if int(users.min()) < 0 or int(users.max()) >= int(user_num):
+            raise ValueError('train_a_batch: a user id lies outside the training lists')
+        return users.to(torch.int32)
+
+    def train_a_batch(self, users) -> dict:
+        """one step on a caller's list of users (list ids of the training lists); its index is built here"""
+        users = self.caller_users(users, self.model.user_num).to(self.device)
+        index = ops.multdae_index(self.lists, users, self.model.item_num)
+        self._ws.get(self._workspace_bytes(users, index))
+        losses = torch.empty(3, dtype=torch.float32, device=self.device)
+        self._step(users, index, torch.tensor([self.step_cnt], dtype=torch.int64, device=self.device), losses)
+        return self.loss_dicts(losses)[0]

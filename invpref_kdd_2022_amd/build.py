@@ -19,9 +19,9 @@ SOURCES = ['invpref_kernels.hip', 'invpref_step.hip', 'invpref_eval.hip', 'invpr
            'invpref_cause.hip', 'invpref_lintrans.hip', 'invpref_adam_rows.hip', 'invpref_truth_rank.hip',
            'invpref_catalog.hip', 'invpref_rank_stats.hip', 'invpref_bpr.hip', 'invpref_dr.hip', 'invpref_segment_rank.hip',
            'invpref_als.hip', 'invpref_key_sort.hip', 'invpref_ssm.hip', 'invpref_lgcn.hip', 'invpref_dice.hip',
-           'invpref_ease.hip']
+           'invpref_ease.hip', 'invpref_multdae.hip']
 HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'adam_apply.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp',
-           'row_pass.hpp', 'chunk_walk.hpp', 'philox.hpp', 'neg_draw.hpp', 'truth_rank_body.hpp', 'rank_key.hpp',
+           'row_pass.hpp', 'chunk_walk.hpp', 'softmax_tiles.hpp', 'philox.hpp', 'neg_draw.hpp', 'truth_rank_body.hpp', 'rank_key.hpp',
            os.path.join('..', '..', 'include', 'invpref_hip.h'),
            os.path.join('..', '..', 'include', 'invpref_macr.h'), os.path.join('..', '..', 'include', 'invpref_cause.h'),
            os.path.join('..', '..', 'include', 'invpref_retrieve_scaled.h'),
@@ -38,7 +38,8 @@ HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'adam_apply.hpp'
            os.path.join('..', '..', 'include', 'invpref_ssm.h'),
            os.path.join('..', '..', 'include', 'invpref_lgcn.h'),
            os.path.join('..', '..', 'include', 'invpref_dice.h'),
-           os.path.join('..', '..', 'include', 'invpref_ease.h')]
+           os.path.join('..', '..', 'include', 'invpref_ease.h'),
+           os.path.join('..', '..', 'include', 'invpref_multdae.h')]
 # -ffp-contract=off: every fma of the canonical arithmetic is written explicitly
 FLAGS = ['-O3', '--offload-arch=gfx950', '-std=c++17', '-fPIC', '-ffp-contract=off',
          '-fno-fast-math', '-Wall', '-Wno-unused-function']

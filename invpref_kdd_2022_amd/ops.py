@@ -32,6 +32,7 @@ from . import torch_ops_segment_rank  # noqa: F401  (explicit evaluation's ranks
 from . import torch_ops_key_sort  # noqa: F401  (the library's own sort: torch.ops.invpref.sort_keys_, auc_sorted)
 from . import torch_ops_lgcn  # noqa: F401  (LightGCN's fragment: torch.ops.invpref.lgcn_propagate, lgcn_reg_)
 from . import torch_ops_ease  # noqa: F401  (EASE's fragment: torch.ops.invpref.ease_gram, spd_inverse_, ease_weights, ease_scores)
+from . import torch_ops_multdae  # (Mult-DAE's fragment: torch.ops.invpref.multdae_encode, multdae_index, multdae_grad_)
 from ._capi import (DENSE_REG, IMPLICIT, REG_ENV_EMBED, REG_ONLY_EMBED, REWEIGHT_CLS, REWEIGHT_REC, WEIGHTS_BY_ENV, Coefs,
                     InvPrefError, call, lib, make_tables, ptr, stream_ptr)
 
@@ -1576,6 +1577,81 @@ def ease_fit(lists, reg: float, out: Optional[torch.Tensor] = None, keep_inverse
     a, error_word = spd_inverse(a, error_word=error_word, workspace=workspace)
     out, error_word = ease_weights(a, out=out, error_word=error_word)
     return out, n_skipped, error_word, (a if keep_inverse else None)
+
+
+# ---- Mult-DAE (include/invpref_multdae.h, csrc/invpref_multdae.hip)
+def _multdae_users(op: str, users) -> torch.Tensor:
+    if users.dtype not in (torch.int32, torch.int64) or users.dim() != 1 or users.numel() < 1:
+        raise InvPrefError(f'{op}: users must be a vector of int32 / int64 list ids, at least one')
+    return users if users.dtype == torch.int32 else users.to(torch.int32)
+
+
+def multdae_encode(enc: torch.Tensor, enc_bias: torch.Tensor, lists, users: torch.Tensor, dropout: float = 0.0, seed: int = 0,
+                   step_id: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """z fp32 [B, D] of the lists `users` (int32 list ids) of lists = (ptr int64 [user_num + 1], cols int32): row b =
+    fp32(tanh(enc_bias + s_u / (1 - dropout) sum of the kept rows enc[cols[e]])), s_u = 1 / sqrt(list length), float64 sums in
+    CSR order (include/invpref_multdae.h).  With dropout > 0 entry e is kept iff its Philox word, named by (seed, step_id, e),
+    is >= floor(dropout 2^32); step_id is an int64 [1] word on the device.  dropout == 0 is inference: nothing is drawn.  A list
+    id outside the CSR is an empty list, a column outside enc adds nothing.  Written into `out` if given (then nothing is
+    allocated: capturable)."""
+    hist_ptr, hist_cols = lists
+    users = _multdae_users('multdae_encode', users)
+    _gpu(enc, enc_bias, hist_ptr, hist_cols, users, step_id, out)
+    if out is None:
+        out = torch.empty(users.numel(), enc.shape[1], dtype=torch.float32, device=enc.device)
+    _o().multdae_encode(enc, enc_bias, hist_ptr, hist_cols, users, float(dropout), _seed64(seed), step_id, out)
+    return out
+
+
+def multdae_index(lists, users: torch.Tensor, item_num: int) -> torch.Tensor:
+    """The inverted index of one step's entries as multdae_grad takes it (include/invpref_multdae.h): the entries of the lists
+    of `users` sorted by item and then by their place in the step (ops.sort_keys' radix sort), each entry's position in the
+    step, and the positions' first entries; int32 [5 n2 + B + 1], n2 the step's entries rounded up to an even number >= 2.
+    Allocates and reads the number of entries back: call it outside a graph capture -- a manager's minibatches are static, so
+    it builds each one's once."""
+    hist_ptr, hist_cols = lists
+    users = _multdae_users('multdae_index', users)
+    _gpu(hist_ptr, hist_cols, users)
+    return _o().multdae_index(hist_ptr, hist_cols, users, int(item_num))
+
+
+def multdae_workspace_bytes(item_num: int, batch: int, index_entries: int, factor_num: int) -> int:
+    """z, da and the positives' sums per user, the column pass's segment partials, float64 partials and chunk slots of one
+    gradient pass -- no [batch, item_num] array: a function of the sizes alone, non-decreasing in each; 0: not taken"""
+    return int(_capi.lib().invpref_multdae_workspace_bytes(int(item_num), int(batch), int(index_entries), int(factor_num)))
+
+
+def multdae_geometry(item_num: int, batch: int, index_entries: int):
+    """(users per workgroup of the rows launches, items per LDS tile, users per segment of the column pass, entries per chunk
+    of the item-side walk, items per split of the rows launches) for these sizes: the seams of the pass.  index_entries: even,
+    >= 2 (multdae_index pads to that)."""
+    g = (C.c_int64 * 5)()
+    _capi.call('invpref_multdae_geometry', int(item_num), int(batch), int(index_entries), C.cast(g, C.c_void_p))
+    return tuple(int(x) for x in g)
+
+
+def multdae_grad(params4: Sequence[torch.Tensor], grads4: Sequence[torch.Tensor], lists, users: torch.Tensor,
+                 index: torch.Tensor, dropout: float, seed: int, step_id: torch.Tensor, L2_coe: float, losses3: torch.Tensor,
+                 workspace: Optional[Workspace] = None) -> None:
+    """The gradient pass of one Mult-DAE step over the lists `users` (int32 list ids; index = multdae_index of them):
+    params4 = (enc [I, D], enc_bias [D], dec [I, D], dec_bias [I]), loss = (1 / B) sum_u sum_{e in list u} (logsumexp_j l_uj -
+    l_{u, cols[e]}) + L2_coe (|enc|^2 + |dec|^2) with l_uj = z_u . dec[j] + dec_bias[j] over the WHOLE catalogue and z_u the
+    encoder's output under the step's dropout mask (include/invpref_multdae.h).  OVERWRITES every element of grads4 and
+    losses3 = (score_loss, L2_reg, loss).  No [B, I] array is formed.  Bitwise reproducible, no float atomics, no host sync
+    (capturable once the workspace is sized; a replay reads ids, lists, index and the step_id word as they are then).  A list id
+    outside the CSR is an empty list, a column outside the tables adds nothing, and either makes the three losses NaN."""
+    hist_ptr, hist_cols = lists
+    enc, enc_bias, dec, dec_bias = params4
+    users = _multdae_users('multdae_grad', users)
+    n2 = torch_ops_multdae.index_entries(index, users.numel())
+    nbytes = multdae_workspace_bytes(enc.shape[0], users.numel(), n2, enc.shape[1]) if enc.dim() == 2 else 0
+    if nbytes == 0:
+        raise InvPrefError(f'multdae_grad: sizes outside the kernels\' range (tables {tuple(enc.shape)}, {users.numel()} users, '
+                           f'{n2} index entries)')
+    _gpu(*params4, *grads4, hist_ptr, hist_cols, users, index, step_id, losses3)
+    ws = (workspace or Workspace(enc.device)).get(nbytes)
+    _o().multdae_grad_(enc, enc_bias, dec, dec_bias, hist_ptr, hist_cols, users, index, float(dropout), _seed64(seed), step_id,
+                       float(L2_coe), *grads4, losses3, ws)
 
 
 # ---- LightGCN (include/invpref_lgcn.h, csrc/invpref_lgcn.hip)
