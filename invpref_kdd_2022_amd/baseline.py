@@ -29,7 +29,7 @@ from torch import nn
 
 from . import _capi, ops
 from . import plan as planlib
-from .engine import _EpochEngine
+from .engine import _EpochEngine, _OuterLoop
 
 PURE_LOSS_KEYS = ['score_loss', 'L2_reg', 'L1_reg', 'loss']  # train.py:399-404
 
@@ -130,6 +130,8 @@ class _BasicTrainManager(_EpochEngine):
                           flags=ops.flags_of(self.implicit, False, False, True, False, dense_reg=False) | _capi.PURE_MF,
                           users_first=None,     # [user table | item table]: the shared part is last as listed
                           env_switches=False)
+
+    _LOSS_KEYS = PURE_LOSS_KEYS     # (train.py:399-404)
 
     def _coefs(self, alpha):
         return (1., 0., 0., 2. * self.L2_coe, 2. * self.L1_coe, 0.)
@@ -677,11 +679,7 @@ class _WholePassMixin(_SingleProcessMixin):
     _DeviceDrawnMixin): the pass writes the reported loss terms, named by _LOSS_KEYS, into the first slots of the step's
     losses, and the engine's row-plan scratch is sized for the first two tables of the flat state."""
     _make_tables = staticmethod(lambda views: _capi.make_pure_tables(views[:2]))
-    _LOSS_KEYS = PURE_LOSS_KEYS     # (train.py:399-404)
-
-    @classmethod
-    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
-        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.tolist()]
+    loss_dicts = _OuterLoop.__dict__['loss_dicts']      # the plain zip, in front of _BasicTrainManager's arithmetic
 
 
 class _OwnPassMixin(_WholePassMixin):
@@ -2187,53 +2185,42 @@ class DRExplicitTrainManager(_DRManagerMixin, BasicExplicitTrainManager):
     """doubly robust MF on explicit feedback (form 1: squared error) over a DRExplicitMatrixFactorization"""
 
 
-class _EnqueuedEpochsLoop:
-    """train() of the managers that are not epoch-engine managers (ALS, Mult-DAE): they offer train_epochs(n, sync), read_back(),
-    epoch_cnt, epochs, evaluate_interval, test_begin_epoch and an evaluator."""
+# ------------------------------------------------------------------------------------------------ list-based managers
+# ALS, EASE and Mult-DAE are not epoch-engine managers (no row plans, no minibatches of interactions): each sits directly on the
+# engine's outer loop and shares what follows.
+def _interactions(training_data):
+    """training_data -> CPU (users int64, items int64, label as stored), rows of (user, item, label)"""
+    data = torch.as_tensor(training_data).detach().cpu()
+    if data.dim() != 2 or data.shape[1] < 3 or data.shape[0] < 1:
+        raise ValueError('training_data holds rows of (user, item, label)')
+    return data[:, 0].to(torch.int64), data[:, 1].to(torch.int64), data[:, 2]
 
-    def train(self, silent: bool = False, auto: bool = False):
-        """((loss dicts, epochs), (test results, epochs)): the outer loop of the epoch engine's train() -- the epoch-0
-        evaluation first, the sweeps up to the next evaluation enqueued together, nothing read back inside the loop when
-        nothing is printed (an evaluator with evaluate_async is then called through it)."""
-        from .engine import transfer_loss_dict_to_line_str
-        test_result_list, test_epoch_list = [], []
-        loss_result_list, train_epoch_index_list = [], []
-        defer = bool(silent or auto)
-        evaluate = getattr(self.evaluator, 'evaluate_async', None) if defer else None
-        pending = evaluate is not None
-        evaluate = evaluate or self.evaluator.evaluate
 
-        def test():
-            result = evaluate()
-            test_result_list.append(result)
-            test_epoch_list.append(self.epoch_cnt)
-            if not defer:
-                print('test at epoch:', self.epoch_cnt)
-                print(transfer_loss_dict_to_line_str(result))
-        test()
-        while self.epoch_cnt < self.epochs:
-            first = self.epoch_cnt + 1
-            to_event = self.evaluate_interval - self.epoch_cnt % self.evaluate_interval
-            run = self.train_epochs(min(to_event, self.epochs - self.epoch_cnt), sync=not defer)
-            for i in range(len(run)):
-                train_epoch_index_list.append(first + i)
-                loss_result_list.append(run[i])
-                if not defer:
-                    print('train epoch:', first + i)
-                    print(transfer_loss_dict_to_line_str(run[i]))
-            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
-                test()
-        if defer:  # one read-back for everything
-            loss_result_list = self.read_back(torch.stack(loss_result_list)) if loss_result_list else []
-            if pending:
-                test_result_list = [p.result() for p in test_result_list]
-        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
+def _require_finite_tables(model) -> None:
+    for t in model.tables():
+        if not bool(torch.isfinite(t.detach()).all()):
+            raise ValueError('the model\'s tables hold non-finite values')
+
+
+class _ErrorWordMixin:
+    """The device's sticky error word of a manager whose kernels report a failed pivot there (and count, in n_skipped, the
+    entries they left out): both zeroed at construction, never cleared; check_error() reads the word and raises."""
+    _ERROR = None                   # the manager's message, around {word}
+
+    def _init_error_word(self, device) -> None:
+        self.n_skipped = torch.zeros(1, dtype=torch.int32, device=device)
+        self.error_word = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def check_error(self) -> None:
+        word = int(self.error_word.item())
+        if word:
+            raise _capi.InvPrefError(self._ERROR.format(word=word))
 
 
 ALS_LOSS_KEYS = ['fit_loss', 'L2_reg', 'loss']
 
 
-class ALSTrainManager(_EnqueuedEpochsLoop):
+class ALSTrainManager(_ErrorWordMixin, _OuterLoop):
     """Weighted matrix factorization solved as Hu, Koren and Volinsky (ICDM 2008) solve it: alternating least squares on a
     plain PureMatrixFactorization (include/invpref_als.h states the model).  Row e of training_data is the entry (user, item,
     label): preference p_e = 1 if label > 0 else 0 (a listed 0 is an observed negative), confidence c_e = 1 + alpha * w_e with w_e the label or the caller's `weights` (one value per
@@ -2242,7 +2229,7 @@ class ALSTrainManager(_EnqueuedEpochsLoop):
     (ops.als_gram / ops.als_solve: float64 normal equations and Cholesky, one rounding to fp32), then evaluates
         loss = fit_loss + reg * L2_reg      L2_reg = |X|^2 + |Y|^2
     with ops.als_objective.  No learning rate, no negative sampling, no minibatches: not an epoch-engine manager (no row plans,
-    no Adam); an "epoch" is a sweep.  Single process.
+    no Adam), only the engine's outer loop; an "epoch" is a sweep.  Single process.
 
     The tables are the model's own parameters, written in place.  Negative weights, non-finite tables and ids outside the
     tables are refused at construction, on the host; the device's sticky error word (a failed pivot: a NaN that reached a
@@ -2253,6 +2240,10 @@ class ALSTrainManager(_EnqueuedEpochsLoop):
         items, scores = ops.recommend(rows, model.item_emb.weight, torch.arange(2, device=rows.device), k=10)
     """
 
+    _LOSS_KEYS = ALS_LOSS_KEYS
+    _ERROR = ('ALS: a row\'s normal matrix was not positive definite or its solution not finite (error word {word}): a NaN '
+              'reached a table, or a confidence was below 1; the affected rows are NaN')
+
     def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, epochs: int, evaluate_interval: int,
                  reg: float, alpha: float, *, weights=None, test_begin_epoch: int = 0):
         if not isinstance(model, PureMatrixFactorization):
@@ -2261,23 +2252,19 @@ class ALSTrainManager(_EnqueuedEpochsLoop):
             raise _capi.InvPrefError(f'factor_num {model.factor_num}: the ALS solve takes at most {_capi.ALS_MAX_FACTORS} factors')
         if not reg > 0:
             raise ValueError('reg must be > 0: it is what keeps every normal matrix positive definite')
-        data = torch.as_tensor(training_data).detach().cpu()
-        if data.dim() != 2 or data.shape[1] < 3 or data.shape[0] < 1:
-            raise ValueError('training_data holds rows of (user, item, label)')
-        users, items, label = data[:, 0].to(torch.int64), data[:, 1].to(torch.int64), data[:, 2].to(torch.float32)
+        users, items, label = _interactions(training_data)
+        label = label.to(torch.float32)
         w = label if weights is None else torch.as_tensor(weights).detach().cpu().reshape(-1).to(torch.float32)
-        if w.numel() != data.shape[0]:
-            raise ValueError(f'weights holds {w.numel()} values for {data.shape[0]} rows')
+        if w.numel() != label.numel():
+            raise ValueError(f'weights holds {w.numel()} values for {label.numel()} rows')
         if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
             raise ValueError('weights (the labels by default) must be finite and >= 0: a confidence below 1 can lose positive '
                              'definiteness')
-        for t in model.tables():
-            if not bool(torch.isfinite(t.detach()).all()):
-                raise ValueError('the model\'s tables hold non-finite values')
+        _require_finite_tables(model)
         self.model, self.evaluator, self.device = model.to(device), evaluator, torch.device(device)
         self.epochs, self.evaluate_interval, self.test_begin_epoch = int(epochs), int(evaluate_interval), int(test_begin_epoch)
         self.reg, self.alpha = float(reg), float(alpha)
-        self.epoch_cnt, self.n_total = 0, int(data.shape[0])
+        self.epoch_cnt, self.n_total = 0, int(label.numel())
         dev = self.device
         conf = 1.0 + self.alpha * w
         pref = (label > 0).to(torch.float32)
@@ -2285,8 +2272,7 @@ class ALSTrainManager(_EnqueuedEpochsLoop):
                                                  model.item_num)
         D = model.factor_num
         self._gram = torch.zeros(D, D, dtype=torch.float64, device=dev)
-        self.n_skipped = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.error_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._init_error_word(dev)
         self._ws = ops.Workspace(dev)
         if dev.type == 'cuda':      # sized once: every later launch is capturable
             U, I, n = model.user_num, model.item_num, self.n_total
@@ -2325,16 +2311,6 @@ class ALSTrainManager(_EnqueuedEpochsLoop):
         self.check_error()
         return self.loss_dicts(dev_losses)
 
-    def check_error(self) -> None:
-        word = int(self.error_word.item())
-        if word:
-            raise _capi.InvPrefError(f'ALS: a row\'s normal matrix was not positive definite or its solution not finite (error word '
-                                     f'{word}): a NaN reached a table, or a confidence was below 1; the affected rows are NaN')
-
-    @staticmethod
-    def loss_dicts(dev_losses: torch.Tensor) -> list:
-        return [dict(zip(ALS_LOSS_KEYS, v)) for v in dev_losses.reshape(-1, 3).tolist()]
-
     def objective(self) -> dict:
         out = self.objective_into(torch.empty(3, dtype=torch.float64, device=self.device))
         return self.read_back(out)[0]
@@ -2358,9 +2334,7 @@ class ALSTrainManager(_EnqueuedEpochsLoop):
         """The vectors of users given by their item lists, solved against the item table as it is and its Gram matrix: the user
         half-sweep on a batch of arbitrary lists (the row_ids form of the same kernel) -> fp32 [n, D].  pref / conf: per list, one
         value per item; default preference 1 and confidence 1 + alpha.  A user without items gets zeros."""
-        n = len(item_lists)
-        lens = [len(l) for l in item_lists]
-        total = sum(lens)
+        n, total = len(item_lists), sum(len(l) for l in item_lists)
         D, dev = self.model.factor_num, self.device
         if n < 1 or total < 1:
             return torch.zeros(n, D, dtype=torch.float32, device=dev)
@@ -2372,15 +2346,11 @@ class ALSTrainManager(_EnqueuedEpochsLoop):
             if v.numel() != total:
                 raise ValueError('fold_in: pref / conf hold one value per listed item')
             return v
-        cols = torch.cat([torch.as_tensor(l, dtype=torch.int64).reshape(-1) for l in item_lists])
-        if int(cols.min()) < 0 or int(cols.max()) >= self.model.item_num:
-            raise ValueError('fold_in: an item id lies outside the item table')
+        row_ptr, cols = ops.lists_csr(item_lists, self.model.item_num, dev, 'fold_in')
         p, c = flat(pref, 1.0), flat(conf, 1.0 + self.alpha)
         if bool((c < 1).any()) or not bool(torch.isfinite(c).all() and torch.isfinite(p).all()):
             raise ValueError('fold_in: confidences must be finite and >= 1, preferences finite')
-        row_ptr = torch.zeros(n + 1, dtype=torch.int64)
-        row_ptr[1:] = torch.cumsum(torch.tensor(lens, dtype=torch.int64), 0)
-        csr = (row_ptr.to(dev), cols.to(torch.int32).to(dev), c.to(dev), p.to(dev))
+        csr = (row_ptr, cols, c.to(dev), p.to(dev))
         _, Y = self._tables()
         gram = ops.als_gram(Y, self.reg)
         out = torch.empty(n, D, dtype=torch.float32, device=dev)
@@ -2416,17 +2386,8 @@ class _HistoryModel:
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def _lists_csr(self, item_lists):
-        """(row_ptr int64 [n + 1], cols int32) on the model's device of users given by their item lists; ids outside the item
-        table are refused"""
-        dev = self.hist_ptr.device
-        lens = torch.tensor([len(l) for l in item_lists], dtype=torch.int64)
-        cols = torch.cat([torch.as_tensor(l, dtype=torch.int64).reshape(-1) for l in item_lists]) if int(lens.sum()) else \
-            torch.zeros(0, dtype=torch.int64)
-        if cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= self.item_num):
-            raise ValueError('predict_lists: an item id lies outside the item table')
-        row_ptr = torch.zeros(len(item_lists) + 1, dtype=torch.int64)
-        row_ptr[1:] = torch.cumsum(lens, 0)
-        return row_ptr.to(dev), cols.to(torch.int32).to(dev)
+        """(row_ptr int64 [n + 1], cols int32) on the model's device of users given by their item lists"""
+        return ops.lists_csr(item_lists, self.item_num, self.hist_ptr.device, 'predict_lists')
 
     def _history_of(self, users):
         """(ptr int32 [n + 1], items int32) of the training lists of `users`, gathered on the device"""
@@ -2484,15 +2445,20 @@ class EASEModel(_HistoryModel, nn.Module):
         return ops.ease_scores(self.weight.detach(), self._lists_csr(item_lists))
 
 
-class EASETrainManager:
+class EASETrainManager(_ErrorWordMixin, _OuterLoop):
     """Fits an EASEModel in closed form: row e of training_data is (user, item, label), and x_ui counts the rows of (u, i) with
     label > 0 (a pair listed twice counts twice).  fit() is three launches -- ops.ease_gram (X^T X + reg I, exact integers),
     ops.spd_inverse (float64, blocked, in place) and ops.ease_weights (one rounding to fp32 into the model's weight) -- with one
-    hyper-parameter, no learning rate and no sampling: not an epoch-engine manager, an "epoch" is the fit.  Single process.
+    hyper-parameter, no learning rate and no sampling: not an epoch-engine manager, only the engine's outer loop, whose one
+    "epoch" is the fit.  Single process.
 
     reg <= 0, ids outside the tables, non-finite labels and counts beyond the Gram kernel's counters are refused at
     construction, on the host; the device's sticky error word (a pivot that was not positive) is read after the fit and raises
     InvPrefError.  keep_inverse keeps the float64 inverse of X^T X + reg I in `inverse` (8 item_num^2 bytes)."""
+
+    _ERROR = ('EASE: X^T X + reg I was not positive definite in float64 or its inverse not finite (error word {word}); the '
+              'weights are NaN')
+    epochs, evaluate_interval, test_begin_epoch = 1, 1, 0       # the outer loop's: evaluate, fit, evaluate
 
     def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, reg: float, *,
                  keep_inverse: bool = False):
@@ -2501,20 +2467,16 @@ class EASETrainManager:
         reg = float(reg)
         if not (reg > 0 and reg < float('inf')):
             raise ValueError('reg must be finite and > 0: it is what keeps X^T X + reg I positive definite')
-        data = torch.as_tensor(training_data).detach().cpu()
-        if data.dim() != 2 or data.shape[1] < 3 or data.shape[0] < 1:
-            raise ValueError('training_data holds rows of (user, item, label)')
-        if not bool(torch.isfinite(data.to(torch.float64)).all()):
+        users, items, label = _interactions(training_data)
+        if not bool(torch.isfinite(torch.as_tensor(training_data).to(torch.float64)).all()):
             raise ValueError('training_data holds non-finite values')
         self.model, self.evaluator, self.device = model.to(device), evaluator, torch.device(device)
         self.reg, self.keep_inverse = reg, bool(keep_inverse)
-        self.epoch_cnt, self.epochs, self.n_total = 0, 1, int(data.shape[0])
+        self.epoch_cnt, self.n_total = 0, int(label.numel())
         dev = self.device
-        self.lists = ops.ease_lists(data[:, 0].to(torch.int64).to(dev), data[:, 1].to(torch.int64).to(dev), data[:, 2].to(dev),
-                                    model.user_num, model.item_num)
+        self.lists = ops.ease_lists(users.to(dev), items.to(dev), label.to(dev), model.user_num, model.item_num)
         self.model.set_history(self.lists[0])
-        self.n_skipped = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.error_word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._init_error_word(dev)
         self.inverse = None
 
     def enqueue_fit(self) -> None:
@@ -2523,42 +2485,23 @@ class EASETrainManager:
                                              n_skipped=self.n_skipped, error_word=self.error_word)
         self.epoch_cnt = 1
 
-    def check_error(self) -> None:
-        word = int(self.error_word.item())
-        if word:
-            raise _capi.InvPrefError(f'EASE: X^T X + reg I was not positive definite in float64 or its inverse not finite (error '
-                                     f'word {word}); the weights are NaN')
-
     def fit(self) -> None:
         self.enqueue_fit()
         self.check_error()
 
-    def train(self, silent: bool = False):
-        """((loss dicts, epochs), (test results, epochs)), the shape of ALSTrainManager.train(): the evaluation at "epoch" 0 (the
-        zero weights), the fit, the evaluation at epoch 1.  The closed form has no loss to report: the one loss dict is empty.
-        silent: nothing is printed and an evaluator with evaluate_async is called through it, its results read at the end."""
-        from .engine import transfer_loss_dict_to_line_str
-        evaluate = getattr(self.evaluator, 'evaluate_async', None) if silent else None
-        pending = evaluate is not None
-        evaluate = evaluate or self.evaluator.evaluate
-        tests, test_epochs = [], []
-
-        def test():
-            result = evaluate()
-            tests.append(result)
-            test_epochs.append(self.epoch_cnt)
-            if not silent:
-                print('test at epoch:', self.epoch_cnt)
-                print(transfer_loss_dict_to_line_str(result))
-        test()
+    # ---- train(): the engine's outer loop around the fit -- the evaluation at "epoch" 0 (the zero weights), the fit, the
+    # evaluation at epoch 1 -> ([{}], [1]), (tests, [0, 1]).  The closed form has no loss to report: the one loss dict is empty.
+    def train_epochs(self, n: int = 1, sync: bool = True):
+        """the fit, enqueued; the error word is read at the end of train()"""
         self.enqueue_fit()
-        if not silent:
-            print('train epoch:', self.epoch_cnt)
-        test()
+        losses = torch.empty(1, 0, device=self.device)
+        return self.read_back(losses) if sync else losses
+
+    def read_back(self, dev_losses: torch.Tensor) -> list:
+        return [{} for _ in range(dev_losses.shape[0])]
+
+    def _after_training(self) -> None:
         self.check_error()
-        if pending:
-            tests = [p.result() for p in tests]
-        return ([{}], [1]), (tests, test_epochs)
 
 
 # ------------------------------------------------------------------------------------------------ Mult-DAE
@@ -2608,14 +2551,16 @@ class MultDAEModel(_HistoryModel, nn.Module):
         return self._scores(self._lists_csr(item_lists), torch.arange(n, dtype=torch.int32, device=self.enc.device))
 
 
-class MultDAETrainManager(_EnqueuedEpochsLoop, _SingleProcessMixin):
+class MultDAETrainManager(_OuterLoop, _SingleProcessMixin):
     """Trains a MultDAEModel by gradient steps on the multinomial likelihood over the WHOLE catalogue (ops.multdae_grad: no [B, I]
     array) with Adam.  Row e of training_data is (user, item, label); rows with label <= 0 are dropped, a pair listed twice
     counts twice (the lists come from ops.ease_lists, so at most INVPREF_EASE_MAX_ITEMS items and its count limit: refused
-    here by name).  Not an epoch-engine manager: its minibatches are USERS, batch_size consecutive ones, static, each one's
-    inverted index built once.  One flat buffer holds the four parameters (the model's parameters are views of it), likewise
-    the gradients and Adam's two moments: a step is the pass plus ONE ops.adam_ launch.  The dropout mask of a step is named by
-    (seed, the global step counter): the same seed gives the same bits whatever the run lengths.  Single process."""
+    here by name).  Not an epoch-engine manager, only the engine's outer loop: its minibatches are USERS, batch_size
+    consecutive ones, static, each one's inverted index built once.  One flat buffer holds the four parameters (the model's
+    parameters are views of it), likewise the gradients and Adam's two moments: a step is the pass plus ONE ops.adam_ launch.
+    The dropout mask of a step is named by (seed, the global step counter): the same seed gives the same bits whatever the run
+    lengths.  Single process."""
+    _LOSS_KEYS = MULTDAE_LOSS_KEYS
     _SINGLE = 'Mult-DAE trains in a single process: its step sweeps the whole catalogue per user and shares no row plan to shard'
 
     def __init__(self, model, evaluator, device: torch.device, training_data: torch.Tensor, batch_size: int, epochs: int,
@@ -2634,20 +2579,15 @@ class MultDAETrainManager(_EnqueuedEpochsLoop, _SingleProcessMixin):
             raise ValueError(f'batch_size must lie in 1 .. {_capi.MULTDAE_MAX_BATCH} users')
         if not (float(lr) > 0 and float(L2_coe) >= 0):
             raise ValueError('lr must be > 0 and L2_coe >= 0')
-        data = torch.as_tensor(training_data).detach().cpu()
-        if data.dim() != 2 or data.shape[1] < 3 or data.shape[0] < 1:
-            raise ValueError('training_data holds rows of (user, item, label)')
-        for t in model.tables():
-            if not bool(torch.isfinite(t.detach()).all()):
-                raise ValueError('the model\'s tables hold non-finite values')
+        users, items, label = _interactions(training_data)
+        _require_finite_tables(model)
         self.model, self.evaluator, self.device = model.to(device), evaluator, torch.device(device)
         self.batch_size, self.epochs, self.evaluate_interval = int(batch_size), int(epochs), int(evaluate_interval)
         self.test_begin_epoch, self.lr, self.L2_coe = int(test_begin_epoch), float(lr), float(L2_coe)
         self.dropout, self.seed = float(dropout), int(seed)
         self.epoch_cnt, self.step_cnt = 0, 0
         dev = self.device
-        by_user, _ = ops.ease_lists(data[:, 0].to(torch.int64).to(dev), data[:, 1].to(torch.int64).to(dev), data[:, 2].to(dev),
-                                    model.user_num, model.item_num)
+        by_user, _ = ops.ease_lists(users.to(dev), items.to(dev), label.to(dev), model.user_num, model.item_num)
         self.lists = by_user
         self.model.set_history(by_user)
         # one flat buffer, each tensor from a multiple of four floats: the tables' rows stay 16-byte aligned
@@ -2680,14 +2620,6 @@ class MultDAETrainManager(_EnqueuedEpochsLoop, _SingleProcessMixin):
                          losses3, workspace=self._ws)
         self.step_cnt += 1
         ops.adam_(self._flat, self._grad, self._exp_avg, self._exp_avg_sq, self.step_cnt, self.lr)
-
-    @staticmethod
-    def loss_dicts(dev_losses: torch.Tensor) -> list:
-        return [dict(zip(MULTDAE_LOSS_KEYS, v)) for v in dev_losses.reshape(-1, 3).tolist()]
-
-    def read_back(self, dev_losses: torch.Tensor) -> list:
-        """the loss dicts of a [n, 3] device tensor: an epoch's terms are the means over its steps"""
-        return self.loss_dicts(dev_losses)
 
     def train_epochs(self, n: int, sync: bool = True):
         """n epochs over the static minibatches, enqueued back to back; the steps' ids are one arange on the device.  sync: ONE

@@ -21,7 +21,8 @@ SOURCES = ['invpref_kernels.hip', 'invpref_step.hip', 'invpref_eval.hip', 'invpr
            'invpref_als.hip', 'invpref_key_sort.hip', 'invpref_ssm.hip', 'invpref_lgcn.hip', 'invpref_dice.hip',
            'invpref_ease.hip', 'invpref_multdae.hip']
 HEADERS = ['canon_math.hpp', 'kernel_common.hpp', 'launch.hpp', 'adam_apply.hpp', 'step_wide.hpp', 'retrieve_scan_body.hpp',
-           'row_pass.hpp', 'chunk_walk.hpp', 'softmax_tiles.hpp', 'philox.hpp', 'neg_draw.hpp', 'truth_rank_body.hpp', 'rank_key.hpp',
+           'row_pass.hpp', 'chunk_walk.hpp', 'csr_rows.hpp', 'softmax_tiles.hpp', 'philox.hpp', 'neg_draw.hpp',
+           'truth_rank_body.hpp', 'rank_key.hpp',
            os.path.join('..', '..', 'include', 'invpref_hip.h'),
            os.path.join('..', '..', 'include', 'invpref_macr.h'), os.path.join('..', '..', 'include', 'invpref_cause.h'),
            os.path.join('..', '..', 'include', 'invpref_retrieve_scaled.h'),

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "csr_rows.hpp"
 #include "launch.hpp"
 #include "../../include/invpref_als.h"
 
@@ -28,6 +29,8 @@ namespace {
 
 using invpref::Carver;
 using invpref::ensure_lds;
+using invpref::find_row;
+using invpref::row_bounds;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = 4;
@@ -75,22 +78,6 @@ __device__ inline void tile_of(int t, int &I, int &J) {
     I = 0;
     while ((I + 1) * (I + 2) / 2 <= t) ++I;
     J = t - I * (I + 1) / 2;
-}
-
-__device__ inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// the entries of list r, clamped into the entry arrays
-__device__ inline void row_bounds(const int64_t *row_ptr, int64_t r, int64_t entries, int64_t &s, int64_t &e) {
-    s = clamp64(row_ptr[r], 0, entries);
-    e = clamp64(row_ptr[r + 1], s, entries);
-}
-// the last list whose (clamped) start is <= pos; 0 if there is none (the caller checks the bounds of what it gets)
-__device__ inline int64_t find_row(const int64_t *row_ptr, int64_t rows, int64_t entries, int64_t pos) {
-    int64_t lo = 0, hi = rows - 1;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (clamp64(row_ptr[mid], 0, entries) <= pos) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 // ---- THE rank-k accumulation: acc += sum_e w_e t_e t_e^T (lower tiles) and acc.b += sum_e cp_e t_e over entries [e0, e1) in

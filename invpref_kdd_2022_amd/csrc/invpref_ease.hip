@@ -23,10 +23,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "csr_rows.hpp"
 #include "launch.hpp"
 #include "../../include/invpref_ease.h"
 
 namespace {
+
+using invpref::row_bounds;
 
 constexpr int kThreads = 256;
 constexpr int kB = INVPREF_EASE_BLOCK;
@@ -39,13 +42,6 @@ static_assert(kB == 64, "the tile maps below are written for 64 x 64 blocks: 4 w
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 enum Mode { kPanel = 0, kTrail = 1, kPremul = 2, kRow = 3, kGram = 4 };
-
-__device__ inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// the entries of list r, clamped into the entry arrays
-__device__ inline void row_bounds(const int64_t *row_ptr, int64_t r, int64_t entries, int64_t &s, int64_t &e) {
-    s = clamp64(row_ptr[r], 0, entries);
-    e = clamp64(row_ptr[r + 1], s, entries);
-}
 
 // ------------------------------------------------------------------------------------------------------------ the Gram matrix
 __global__ __launch_bounds__(kThreads) void ease_skipped_kernel(const int32_t *user_cols, const int32_t *item_cols, int64_t entries,

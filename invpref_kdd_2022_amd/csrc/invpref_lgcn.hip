@@ -18,6 +18,7 @@
 // own test, counts nowhere), then one group per table row over the rows with a count: grad += n (2 L2_coe x + L1_coe sign(x))
 // / (B D), n |x|^2 and n |x|_1 as float64 partials per workgroup (row_pass.hpp's group_sums), folded in workgroup order.
 #include "chunk_walk.hpp"
+#include "csr_rows.hpp"
 
 #include "../../include/invpref_lgcn.h"
 
@@ -64,9 +65,6 @@ __device__ __forceinline__ SideDev pick(const SideDev &u, const SideDev &i, bool
     r.n_slots = s ? i.n_slots : u.n_slots;
     return r;
 }
-__device__ __forceinline__ int clamp64(int64_t v, int lo, int hi) {
-    return (int)std::min<int64_t>(std::max<int64_t>(v, lo), hi);
-}
 
 // the row of layer k + 1 is complete in acc: store it and bring the row of `out` up to date
 template <int NC, bool VEC, bool FIRST>
@@ -103,8 +101,9 @@ __global__ __launch_bounds__(256) void lgcn_piece_kernel(const LayerArgs a) {
     if (row < 0 || row >= S.rows) return;
     const int plim = s ? a.user.rows : a.item.rows;          // rows of the partner table
     const float *ptab = s ? a.cur_user : a.cur_item;
-    const int lo = clamp64(S.row_ptr[row], 0, S.nnz), hi = clamp64(S.row_ptr[row + 1], lo, S.nnz);
-    const int e0 = clamp64(S.piece_at[p], lo, hi), e1 = clamp64(S.piece_at[p + 1], e0, hi);
+    int64_t lo, hi;
+    row_bounds(S.row_ptr, row, S.nnz, lo, hi);
+    const int e0 = (int)clamp64(S.piece_at[p], lo, hi), e1 = (int)clamp64(S.piece_at[p + 1], e0, hi);
     double4_t acc[NC];
     zero_acc<NC>(acc);
     // entries whose column -> partner row chain is in flight together (registers: RegWalk::ahead of chunk_walk.hpp)

@@ -31,6 +31,7 @@
 // The splits, segments and chunks are functions of the sizes alone, so is the order of every sum.  An id outside its table is
 // never an address: such a list is empty, such a column adds nothing, and the losses are NaN.
 #include "chunk_walk.hpp"
+#include "csr_rows.hpp"
 #include "philox.hpp"
 #include "softmax_tiles.hpp"
 
@@ -112,8 +113,7 @@ struct Dropout {
 __device__ __forceinline__ bool list_of(const int64_t *__restrict__ ptr, int u, int U, int64_t nnz, int64_t &lo, int64_t &hi) {
     lo = hi = 0;
     if (u < 0 || u >= U) return false;
-    lo = std::min<int64_t>(std::max<int64_t>(ptr[u], 0), nnz);
-    hi = std::min<int64_t>(std::max<int64_t>(ptr[u + 1], lo), nnz);
+    row_bounds(ptr, u, nnz, lo, hi);
     return true;
 }
 

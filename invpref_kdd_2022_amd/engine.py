@@ -1,9 +1,10 @@
-"""The epoch engine every train manager is built on: ``_EpochEngine``.
+"""The epoch engine the minibatch train managers are built on, ``_EpochEngine``, and the outer loop under it, ``_OuterLoop``.
 
 It owns what a run of optimiser steps over STATIC minibatches needs and nothing about what the steps mean: this rank's share
 of the interactions, the flat parameter / gradient / moment buffers (``FlatState``), the row plans, the per-minibatch
 arguments (``RawBatch``), the fused, unfused, alternating and lazy step sequences, the device-side Adam schedule, whole-epoch
-HIP graphs, the sharded exchanges, ``train_epochs()`` and the evaluate-and-epochs skeleton of the outer loop.
+HIP graphs, the sharded exchanges and ``train_epochs()``.  train(), the evaluate-and-epochs loop around train_epochs(), is
+``_OuterLoop``'s: the managers that are not epoch-engine managers (baseline.py: ALS, EASE, Mult-DAE) derive from that alone.
 
 A manager derives from it and answers a few questions through methods the engine calls (DESIGN.md §4.6 lists them); every
 default is the answer of a plain PureMF step.  ``train._InvPrefTrainManager`` adds the environments, their weights, the
@@ -137,11 +138,129 @@ class RawBatch(NamedTuple):
         return self.envs
 
 
-class _EpochEngine:
+class _OuterLoop:
+    """train(): the outer loop of every manager (train.py:428-461; InvPref's: :282-342) -- the evaluation in front of the first
+    epoch, runs of epochs up to the next evaluation or event enqueued together, the records, the printed lines, and ONE
+    read-back at the end when nothing is printed.  It knows nothing about what an epoch is.  A manager supplies
+        epoch_cnt, epochs, evaluate_interval, test_begin_epoch, evaluator
+        train_epochs(n, sync)   n epochs enqueued, epoch_cnt moved on: their loss dicts (sync), else a device tensor with one
+                                row per epoch, which read_back() takes later
+        _LOSS_KEYS              the names of a row's leading values
+    and may override the hooks below, each of which does nothing by default."""
+    _LOSS_KEYS = ()
+
+    @classmethod
+    def loss_dicts(cls, dev_losses: torch.Tensor) -> list:
+        """the loss dicts of a device tensor [n, terms] (or [terms]): _LOSS_KEYS over each row's leading values"""
+        return [dict(zip(cls._LOSS_KEYS, v)) for v in dev_losses.reshape(-1, dev_losses.shape[-1]).tolist()]
+
+    def read_back(self, dev_losses: torch.Tensor) -> list:
+        """what the deferred loop reads at its end: loss_dicts, behind whatever check the manager makes at a read-back"""
+        return self.loss_dicts(dev_losses)
+
+    def _before_run(self) -> None:
+        """enqueued in front of every run of epochs (baseline.py: ExpoMFTrainManager)"""
+
+    def _after_run(self) -> None:
+        """enqueued behind every run of epochs, before its records are taken"""
+
+    def _ends_run(self, e: int) -> bool:
+        """does an event of the manager's own follow epoch e?  (the run of epochs ends there)"""
+        return False
+
+    def _before_evaluation(self) -> None:
+        """in front of every evaluation: the model is brought to where the evaluator reads it"""
+
+    def _after_first_evaluation(self) -> None:
+        """behind the evaluation in front of the first epoch"""
+
+    def _after_run_events(self, defer: bool) -> None:
+        """behind every run of epochs and its evaluation, where _ends_run() or another event ended it; defer: read nothing back
+        (results are collected by the manager's own _train_span)"""
+
+    def _after_training(self) -> None:
+        """behind the last run, in front of the deferred read-back: a manager's sticky errors raise here"""
+
+    def _epochs_to_next_event(self) -> int:
+        """How many epochs train() may enqueue before the next evaluation, event of the manager's own or end of training."""
+        r = 1
+        while r < 64:
+            e = self.epoch_cnt + r
+            if e >= self.epochs or self._ends_run(e) \
+                    or (e % self.evaluate_interval == 0 and e >= self.test_begin_epoch):
+                break
+            r += 1
+        return r
+
+    def train(self, silent: bool = False, auto: bool = False):
+        """((loss dicts, epochs), (test results, epochs)) of the outer loop"""
+        return self._train_span(silent, auto, initial=True)
+
+    def _train_span(self, silent: bool, auto: bool, initial: bool):
+        """The outer loop from the current epoch up to self.epochs; `initial` runs the epoch-0 evaluation (and what the
+        manager does behind it) first."""
+        test_result_list, test_epoch_list = [], []
+        loss_result_list, train_epoch_index_list = [], []
+        # nothing printed -> nothing is read back inside the loop (losses, the results of the manager's own events and -- from
+        # an evaluator with evaluate_async -- the evaluations stay on the device until the end): the GPU never waits for the
+        # host between epochs, events and evaluations.  An evaluator without evaluate_async is called synchronously.
+        defer = bool(silent or auto)
+        evaluate = getattr(self.evaluator, 'evaluate_async', None) if defer else None
+        pending = evaluate is not None
+        evaluate = evaluate or self.evaluator.evaluate
+
+        def test():
+            self._before_evaluation()
+            result = evaluate()
+            test_result_list.append(result)
+            test_epoch_list.append(self.epoch_cnt)
+            return result
+
+        def show_test(result) -> None:
+            if not defer:
+                print('test at epoch:', self.epoch_cnt)
+                print(transfer_loss_dict_to_line_str(result))
+
+        if initial:
+            result = test()
+            self._after_first_evaluation()
+            show_test(result)
+
+        while self.epoch_cnt < self.epochs:
+            # the epochs up to the next evaluation or event are enqueued together (one read-back);
+            # the records and the printed lines are the same, in the same order, as one epoch at a time
+            first = self.epoch_cnt + 1
+            self._before_run()
+            run = self.train_epochs(self._epochs_to_next_event(), sync=not defer)
+            self._after_run()
+            for i in range(len(run)):
+                train_epoch_index_list.append(first + i)
+                loss_result_list.append(run[i])
+                if not defer:
+                    print('train epoch:', first + i)
+                    if run[i]:      # (a closed form has no loss to report: its dict is empty, and gets no line)
+                        print(transfer_loss_dict_to_line_str(run[i]))
+
+            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
+                show_test(test())
+
+            self._after_run_events(defer)
+
+        self._after_training()
+        if defer:  # one read-back for everything
+            loss_result_list = self.read_back(torch.stack(loss_result_list)) if loss_result_list else []
+            if pending:
+                test_result_list = [p.result() for p in test_result_list]
+
+        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)
+
+
+class _EpochEngine(_OuterLoop):
     """See the module's docstring.  What a manager may override, each default being plain PureMF's answer: _batch_inputs,
     _resident, _setup_stale, _before_epochs, _step_weights, _graph_key_extra, _alpha_for, _alpha_scheduled, _sched_alphas,
-    _after_replay, _env_count, _ends_run, _after_first_evaluation, _after_run_events; and, as before, _coefs, _pure_weights,
-    _gradient_pass, _after_gradient_pass, _before_run, _after_run."""
+    _after_replay, _env_count; and, as before, _coefs, _pure_weights, _gradient_pass, _after_gradient_pass; and the hooks of
+    _OuterLoop."""
+    _LOSS_KEYS = LOSS_KEYS
     implicit = True
     _lazy_adam_unsupported = None       # a manager that cannot run lazy Adam names the reason here (set_lazy_adam)
     _pure = True                        # the step's kernel form: PureMF's two tables (False: InvPref's seven)
@@ -294,17 +413,6 @@ class _EpochEngine:
     def _after_replay(self, n: int) -> None:
         """n epochs were replayed (epoch_cnt not yet moved on): host-side values that eagerly issued steps leave behind"""
 
-    def _ends_run(self, e: int) -> bool:
-        """does an event of the manager's own follow epoch e in the outer loop?  (the run of epochs ends there)"""
-        return False
-
-    def _after_first_evaluation(self) -> None:
-        """outer loop: behind the evaluation in front of the first epoch"""
-
-    def _after_run_events(self, defer: bool) -> None:
-        """outer loop: behind every run of epochs and its evaluation, where _ends_run() or another event ended it; defer: read
-        nothing back (results are collected by the manager's own _train_span)"""
-
     def _setup_ranges(self, model):
         """What one optimiser step exchanges and updates on this rank: `_ar_lo` = first float of the flat
         gradient that is all-reduced (through the loss tail), `_adam_ranges` = (offset, length) pieces of the
@@ -399,6 +507,13 @@ class _EpochEngine:
             tmp[lo:hi] = view[lo:hi]
             all_reduce_sum_(tmp, self.process_group)
             view.copy_(tmp)
+
+    def _before_evaluation(self) -> None:
+        self.sync_parameters()
+
+    def _after_training(self) -> None:
+        self.sync_parameters()  # (user-sharded runs: every rank ends with the complete model)
+        self._check_alt_error()
 
     def _all_reduce_step(self):
         """the one exchange of an optimiser step: the shared part of the flat gradient + the loss tail"""
@@ -844,10 +959,6 @@ class _EpochEngine:
             self._check_alt_error()
         return self.loss_dicts(out) if sync else out
 
-    @staticmethod
-    def loss_dicts(dev_losses: torch.Tensor) -> list:
-        return [dict(zip(LOSS_KEYS, v)) for v in dev_losses.tolist()]
-
     def _enqueue_epochs(self, want: int) -> torch.Tensor:
         """Issues up to `want` epochs on the current stream and returns their mean losses as a device
         tensor [n_issued, 6].  On one GPU with a fixed alpha, runs of whole epochs (batch_num fused steps
@@ -980,82 +1091,3 @@ class _EpochEngine:
                     self.state.swap()
                 self.state.step += 1
             self.state.step = step0
-
-    def _before_run(self) -> None:
-        """Hook of the outer loop: enqueued in front of every run of epochs (baseline.py: ExpoMFTrainManager)."""
-
-    def _after_run(self) -> None:
-        """Hook of the outer loop: enqueued behind every run of epochs, before its records are taken."""
-
-    def _epochs_to_next_event(self) -> int:
-        """How many epochs train() may enqueue before the next evaluation, event of the manager's own or end of training."""
-        r = 1
-        while r < 64:
-            e = self.epoch_cnt + r
-            if e >= self.epochs or self._ends_run(e) \
-                    or (e % self.evaluate_interval == 0 and e >= self.test_begin_epoch):
-                break
-            r += 1
-        return r
-
-    # ------------------------------------------------------------------ outer loop (train.py:428-461; InvPref's: :282-342)
-    def train(self, silent: bool = False, auto: bool = False):
-        """((loss dicts, epochs), (test results, epochs)) of the outer loop"""
-        return self._train_span(silent, auto, initial=True)
-
-    def _train_span(self, silent: bool, auto: bool, initial: bool):
-        """The outer loop from the current epoch up to self.epochs; `initial` runs the epoch-0 evaluation (and what the
-        manager does behind it) first."""
-        test_result_list, test_epoch_list = [], []
-        loss_result_list, train_epoch_index_list = [], []
-        # nothing printed -> nothing is read back inside the loop (losses, the results of the manager's own events and -- from
-        # an evaluator with evaluate_async -- the evaluations stay on the device until the end): the GPU never waits for the
-        # host between epochs, events and evaluations.  An evaluator without evaluate_async is called synchronously.
-        defer = bool(silent or auto)
-        evaluate = getattr(self.evaluator, 'evaluate_async', None) if defer else None
-        pending = evaluate is not None
-        evaluate = evaluate or self.evaluator.evaluate
-
-        if initial:
-            self.sync_parameters()
-            temp_eval_result = evaluate()
-            test_result_list.append(temp_eval_result)
-            test_epoch_list.append(self.epoch_cnt)
-            self._after_first_evaluation()
-            if not silent and not auto:
-                print('test at epoch:', self.epoch_cnt)
-                print(transfer_loss_dict_to_line_str(temp_eval_result))
-
-        while self.epoch_cnt < self.epochs:
-            # the epochs up to the next evaluation or event are enqueued together (one read-back);
-            # the records and the printed lines are the same, in the same order, as one epoch at a time
-            first = self.epoch_cnt + 1
-            self._before_run()
-            run = self.train_epochs(self._epochs_to_next_event(), sync=not defer)
-            self._after_run()
-            for i in range(len(run)):
-                train_epoch_index_list.append(first + i)
-                loss_result_list.append(run[i])
-                if not defer:
-                    print('train epoch:', first + i)
-                    print(transfer_loss_dict_to_line_str(run[i]))
-
-            if (self.epoch_cnt % self.evaluate_interval) == 0 and self.epoch_cnt >= self.test_begin_epoch:
-                self.sync_parameters()
-                temp_eval_result = evaluate()
-                test_result_list.append(temp_eval_result)
-                test_epoch_list.append(self.epoch_cnt)
-                if not silent and not auto:
-                    print('test at epoch:', self.epoch_cnt)
-                    print(transfer_loss_dict_to_line_str(temp_eval_result))
-
-            self._after_run_events(defer)
-
-        self.sync_parameters()  # (user-sharded runs: every rank ends with the complete model)
-        self._check_alt_error()
-        if defer:  # one read-back for everything
-            loss_result_list = self.loss_dicts(torch.stack(loss_result_list)) if loss_result_list else []
-            if pending:
-                test_result_list = [p.result() for p in test_result_list]
-
-        return (loss_result_list, train_epoch_index_list), (test_result_list, test_epoch_list)

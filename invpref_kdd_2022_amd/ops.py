@@ -1459,6 +1459,19 @@ def als_csr(users: torch.Tensor, items: torch.Tensor, pref: torch.Tensor, conf: 
     return one(users, items, int(user_num)), one(items, users, int(item_num))
 
 
+def lists_csr(item_lists, item_num: int, device, op: str):
+    """Users given by their item lists (a Python list of lists of ids; fold-in) -> (row_ptr int64 [n + 1], cols int32) on
+    `device`, the ids in list order.  An id outside the item table is refused here, on the host, in the name of `op`."""
+    lens = torch.tensor([len(l) for l in item_lists], dtype=torch.int64)
+    cols = torch.cat([torch.as_tensor(l, dtype=torch.int64).reshape(-1) for l in item_lists]) if int(lens.sum()) else \
+        torch.zeros(0, dtype=torch.int64)
+    if cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= item_num):
+        raise ValueError(f'{op}: an item id lies outside the item table')
+    row_ptr = torch.zeros(len(item_lists) + 1, dtype=torch.int64)
+    row_ptr[1:] = torch.cumsum(lens, 0)
+    return row_ptr.to(device), cols.to(torch.int32).to(device)
+
+
 # ---- EASE (include/invpref_ease.h, csrc/invpref_ease.hip)
 def ease_workspace_bytes(n: int) -> int:
     """the scratch of spd_inverse on an n x n matrix (the inverse of the triangular factor, float64 [n, n]): a function of n
