@@ -404,6 +404,83 @@ __device__ __forceinline__ void first_desc(const int4 *desc, int r0, int grp, in
     d1 = desc[(r0 * NG + grp) * 2 + 1];
 }
 
+// ---- what the task bodies share (narrow and wide rows alike, step_alt.hpp aside): the step's scalars, the moment rows' trip
+// through LDS, the slices' meeting.  The signatures are what keeps the device program the written-out bodies had
+// (tools/device_diff.py): a helper is optimised on its own before it is inlined, so a predicate is formed at the call site,
+// in the body's own order, and `pure` -- which the bodies' lambdas hold by reference -- comes by reference here too.
+
+// Adam's scalars of this step: the schedule slot's under graph replay (device-side schedule), else the launch's own
+__device__ __forceinline__ AdamScalars adam_of(const StepArgs &a) {
+    return a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+}
+// the step's scalars, with the scheduled alpha (train.py:214-217) under graph replay: a NaN in the slot keeps a.k.alpha
+// (filled in place: returned by value, the NaN test becomes a select inside the helper and the callers' code moves)
+__device__ __forceinline__ void scalars_of(const StepArgs &a, StepScalars &k, AdamScalars &ad) {
+    k = a.k;
+    if (a.sched_state) {
+        const float al = sched_slot_ptr(a.sched_state, a.sched_slot)->alpha;
+        if (al == al) k.alpha = al;
+    }
+    ad = adam_of(a);
+}
+
+// The Adam moments of row `row` of side SIDE (0: user tables, 1: item tables) are needed last, so they are sent straight to
+// LDS (LDS-DMA, no registers held across the interaction loop): each lane of a leader group sends its 16-byte piece of the
+// row's four moment rows; the destination of a wave instruction is one contiguous 1 KiB block, lane-major.
+// `mine`: a leader's lane inside the row (active && leader && lg * 4 < D).
+template <int SIDE>
+__device__ __forceinline__ void moments_to_lds(const DevTables &t, const StepArgs &a, float4 *mv_wave, bool mine, const bool &pure, int row,
+                                               int lg) {
+#pragma unroll
+    for (int tn = 0; tn < 4; tn++) {
+        const float *src_tab = (tn & 1) ? a.v[(tn >> 1) * 2 + SIDE] : a.m[(tn >> 1) * 2 + SIDE];
+        if (mine && !(pure && tn >= 2))
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) void *)(src_tab + ((unsigned)row * (unsigned)t.D + (unsigned)lg * 4u)),
+                (__attribute__((address_space(3))) void *)(mv_wave + tn * 64), 16, 0, 0);
+    }
+}
+
+// ... and out of the landing area again, once the LDS-DMA pieces have landed
+__device__ __forceinline__ void moments_from_lds(const float4 *mv_wave, int lane, const bool &pure, float4 &mi, float4 &vi, float4 &me,
+                                                 float4 &ve) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    mi = mv_wave[0 * 64 + lane]; vi = mv_wave[1 * 64 + lane];
+    if (!pure) { me = mv_wave[2 * 64 + lane]; ve = mv_wave[3 * 64 + lane]; }
+}
+
+// Slices of one row meet through LDS: every group parks its partial sums in its slot (plain stores), the leader adds the
+// other slices' in slice order.  `slices` is the same for every slot of a round, idle slots included, so every thread of
+// the workgroup reaches both barriers; the second one -- the slots are rewritten by the next round -- only if `more` rounds
+// follow.
+template <int DP>
+__device__ __forceinline__ void join_slices(float *slots, int grp, int lg, int slices, bool active, bool leader, bool more, float4 &gi,
+                                            float4 &ge) {
+    if (slices > 1) {
+        float *mine = slots + grp * 2 * DP;
+        *reinterpret_cast<float4 *>(mine + lg * 4) = gi;
+        *reinterpret_cast<float4 *>(mine + DP + lg * 4) = ge;
+        __syncthreads();
+        if (active && leader) {
+#pragma unroll 4
+            for (int s = 1; s < slices; s++) {
+                const float *oth_slot = slots + (grp + s) * 2 * DP;
+                f4add(gi, *reinterpret_cast<const float4 *>(oth_slot + lg * 4));
+                f4add(ge, *reinterpret_cast<const float4 *>(oth_slot + DP + lg * 4));
+            }
+        }
+        if (more) __syncthreads();
+    }
+}
+
+// the regulariser's share of a finished row's gradients: the row counts once per interaction, `cnt` of them
+__device__ __forceinline__ void add_regulariser(float4 &gi, float4 &ge, const float4 &oi, const float4 &oe, float cnt, const StepScalars &k) {
+    if (cnt != 0.f) {
+        f4fma(gi, cnt, reg_term(oi, k.r2, k.r1));
+        f4fma(ge, cnt, reg_term(oe, k.r2, k.r1));
+    }
+}
+
 struct USample {
     int oth, ps;
     float y;
@@ -443,12 +520,9 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
     const bool dma = VEC && a.fused && G::REG;
     const bool push = a.push_slot != nullptr;
     float *sdE = lds + L::mv;   // E > 8: [EMAX][DP] embed_env partial sums of the workgroup, rows indexed by the environment
-    StepScalars k = a.k;
-    if (a.sched_state) {  // scheduled alpha (train.py:214-217) under graph replay
-        const float al = sched_slot_ptr(a.sched_state, a.sched_slot)->alpha;
-        if (al == al) k.alpha = al;
-    }
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    StepScalars k;
+    AdamScalars ad;
+    scalars_of(a, k, ad);
 
     STAMP(0);
     // the first round's descriptor goes out before anything else: every gather below hangs on it
@@ -592,19 +666,7 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
             for (int j = 0; j < UE; j++)
                 if (UE + j < nsmp) idn[j] = sample_at(UE + j);
         }
-        if (dma) {
-            // each lane sends its 16-byte piece of the row's four moment rows straight to LDS; the destination of a
-            // wave instruction is one contiguous 1 KiB block, lane-major
-            const bool mine = active && leader && lg * 4 < t.D;
-#pragma unroll
-            for (int tn = 0; tn < 4; tn++) {
-                const float *src_tab = (tn & 1) ? a.v[(tn >> 1) * 2] : a.m[(tn >> 1) * 2];
-                if (mine && !(pure && tn >= 2))
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) void *)(src_tab + ((unsigned)row * (unsigned)t.D + (unsigned)lg * 4u)),
-                        (__attribute__((address_space(3))) void *)(mv_wave + tn * 64), 16, 0, 0);
-            }
-        }
+        if (dma) moments_to_lds<0>(t, a, mv_wave, active && leader && lg * 4 < t.D, pure, row, lg);
         if (r == r0) {
             if (FULL) {
                 // the two small tables are staged HERE, behind the first round's gathers: their load -> LDS-store loop in
@@ -797,9 +859,7 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
         };
         float4 mi = f4zero(), vi = f4zero(), me = f4zero(), ve = f4zero();
         if (L::ALIAS && dma && active && leader) {   // (the slices' partials overwrite the landing area next)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA pieces have landed
-            mi = mv_wave[0 * 64 + lane]; vi = mv_wave[1 * 64 + lane];
-            if (!pure) { me = mv_wave[2 * 64 + lane]; ve = mv_wave[3 * 64 + lane]; }
+            moments_from_lds(mv_wave, lane, pure, mi, vi, me, ve);
         }
         // (the reads above and the stores below are ordered ACROSS lanes only by instruction order: keep the compiler from
         //  moving one over the other)
@@ -840,19 +900,14 @@ __device__ __forceinline__ void user_task(const DevTables &t, const StepArgs &a,
         if (r == r0 + STAMP_ROUND) STAMP(5);
         // ---- the leader finishes the row
         if (active && leader) {
-            if (cnt != 0.f) {
-                f4fma(gi, cnt, reg_term(oi, k.r2, k.r1));
-                f4fma(ge, cnt, reg_term(oe, k.r2, k.r1));
-            }
+            add_regulariser(gi, ge, oi, oe, cnt, k);
             if (!a.fused) {
                 put4<VEC, 0, FULL>(a.np[0], row, t.D, lg, gi);
                 if (!pure) put4<VEC, 0, FULL>(a.np[2], row, t.D, lg, ge);
             } else {
                 if (dma && L::ALIAS) {   // (taken out of the landing area above)
                 } else if (dma) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA pieces have landed
-                    mi = mv_wave[0 * 64 + lane]; vi = mv_wave[1 * 64 + lane];
-                    if (!pure) { me = mv_wave[2 * 64 + lane]; ve = mv_wave[3 * 64 + lane]; }
+                    moments_from_lds(mv_wave, lane, pure, mi, vi, me, ve);
                 } else {
                     mi = row4<VEC, FULL>(a.m[0], row, t.D, lg); vi = row4<VEC, FULL>(a.v[0], row, t.D, lg);
                     if (!pure) { me = row4<VEC, FULL>(a.m[2], row, t.D, lg); ve = row4<VEC, FULL>(a.v[2], row, t.D, lg); }
@@ -891,12 +946,9 @@ __device__ __forceinline__ void item_task(const DevTables &t, const StepArgs &a,
     float4 *mv_wave = mv + wave * 4 * 64;
     const bool pure = a.flags & INVPREF_PURE_MF;
     const bool dma = VEC && a.fused;
-    StepScalars k = a.k;
-    if (a.sched_state) {
-        const float al = sched_slot_ptr(a.sched_state, a.sched_slot)->alpha;
-        if (al == al) k.alpha = al;
-    }
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    StepScalars k;
+    AdamScalars ad;
+    scalars_of(a, k, ad);
     STAMP(0);
     int4 d, d1;
     first_desc<LG>(a.desc, r0, grp, d, d1);
@@ -970,17 +1022,7 @@ __device__ __forceinline__ void item_task(const DevTables &t, const StepArgs &a,
 #pragma unroll
         for (int j = 0; j < U; j++)
             if (U + j < nsmp) idn[j] = ids_at(U + j);
-        if (dma) {   // the row's Adam moments: needed last, sent straight to LDS (no registers held across the loop)
-            const bool mine = active && leader && lg * 4 < t.D;
-#pragma unroll
-            for (int tn = 0; tn < 4; tn++) {
-                const float *src_tab = (tn & 1) ? a.v[(tn >> 1) * 2 + 1] : a.m[(tn >> 1) * 2 + 1];
-                if (mine && !(pure && tn >= 2))
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) void *)(src_tab + ((unsigned)row * (unsigned)t.D + (unsigned)lg * 4u)),
-                        (__attribute__((address_space(3))) void *)(mv_wave + tn * 64), 16, 0, 0);
-            }
-        }
+        if (dma) moments_to_lds<1>(t, a, mv_wave, active && leader && lg * 4 < t.D, pure, row, lg);
         if (r == r0) { __syncthreads(); STAMP(3); }  // staged tables visible
         for (int s = 0; s < nsmp; s += U) {
 #pragma unroll
@@ -991,37 +1033,18 @@ __device__ __forceinline__ void item_task(const DevTables &t, const StepArgs &a,
             }
         }
         if (r == r0 + STAMP_ROUND) STAMP(4);
-        if (slices > 1) {
-            float *mine = slots + grp * 2 * DP;
-            *reinterpret_cast<float4 *>(mine + lg * 4) = gi;
-            *reinterpret_cast<float4 *>(mine + DP + lg * 4) = ge;
-            __syncthreads();
-            if (active && leader) {
-#pragma unroll 4
-                for (int s = 1; s < slices; s++) {
-                    const float *oth_slot = slots + (grp + s) * 2 * DP;
-                    f4add(gi, *reinterpret_cast<const float4 *>(oth_slot + lg * 4));
-                    f4add(ge, *reinterpret_cast<const float4 *>(oth_slot + DP + lg * 4));
-                }
-            }
-            if (r + 1 < r0 + nr) __syncthreads();
-        }
+        join_slices<DP>(slots, grp, lg, slices, active, leader, r + 1 < r0 + nr, gi, ge);
         if (r == r0 + STAMP_ROUND) STAMP(5);
         if (active && leader) {
             const float cnt = (float)(meta >> 9);
-            if (cnt != 0.f) {
-                f4fma(gi, cnt, reg_term(oi, k.r2, k.r1));
-                f4fma(ge, cnt, reg_term(oe, k.r2, k.r1));
-            }
+            add_regulariser(gi, ge, oi, oe, cnt, k);
             if (!a.fused) {
                 put4<VEC, 0, FULL>(a.np[1], row, t.D, lg, gi);
                 if (!pure) put4<VEC, 0, FULL>(a.np[3], row, t.D, lg, ge);
             } else {
                 float4 mi = f4zero(), vi = f4zero(), me = f4zero(), ve = f4zero();
                 if (dma) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA pieces have landed
-                    mi = mv_wave[0 * 64 + lane]; vi = mv_wave[1 * 64 + lane];
-                    if (!pure) { me = mv_wave[2 * 64 + lane]; ve = mv_wave[3 * 64 + lane]; }
+                    moments_from_lds(mv_wave, lane, pure, mi, vi, me, ve);
                 } else {
                     mi = row4<VEC, FULL>(a.m[1], row, t.D, lg); vi = row4<VEC, FULL>(a.v[1], row, t.D, lg);
                     if (!pure) { me = row4<VEC, FULL>(a.m[3], row, t.D, lg); ve = row4<VEC, FULL>(a.v[3], row, t.D, lg); }
@@ -1058,7 +1081,7 @@ __device__ __forceinline__ void item_task_push(const DevTables &t, const StepArg
     const bool pure = a.flags & INVPREF_PURE_MF;
     const bool dma = VEC && a.fused;
     const StepScalars k = a.k;
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    const AdamScalars ad = adam_of(a);
     STAMP(0);
     int4 d, d1_unused;
     first_desc<LG>(a.desc, r0, grp, d, d1_unused);
@@ -1105,17 +1128,7 @@ __device__ __forceinline__ void item_task_push(const DevTables &t, const StepArg
         };
         fetch(0, 0);
         fetch(1, H);
-        if (dma) {   // the row's Adam moments: needed last, sent straight to LDS
-            const bool mine = active && leader && lg * 4 < t.D;
-#pragma unroll
-            for (int tn = 0; tn < 4; tn++) {
-                const float *src_tab = (tn & 1) ? a.v[(tn >> 1) * 2 + 1] : a.m[(tn >> 1) * 2 + 1];
-                if (mine && !(pure && tn >= 2))
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) void *)(src_tab + ((unsigned)row * (unsigned)t.D + (unsigned)lg * 4u)),
-                        (__attribute__((address_space(3))) void *)(mv_wave + tn * 64), 16, 0, 0);
-            }
-        }
+        if (dma) moments_to_lds<1>(t, a, mv_wave, active && leader && lg * 4 < t.D, pure, row, lg);
         if (r == r0 + STAMP_ROUND) STAMP(3);
         int n_wave = nsmp;   // the wave's longest slice
 #pragma unroll
@@ -1127,37 +1140,18 @@ __device__ __forceinline__ void item_task_push(const DevTables &t, const StepArg
             if (s0 + PCH + H < n_wave) fetch(1, s0 + PCH + H);
         }
         if (r == r0 + STAMP_ROUND) STAMP(4);
-        if (slices > 1) {
-            float *mine = slots + grp * 2 * DP;
-            *reinterpret_cast<float4 *>(mine + lg * 4) = gi;
-            *reinterpret_cast<float4 *>(mine + DP + lg * 4) = ge;
-            __syncthreads();
-            if (active && leader) {
-#pragma unroll 4
-                for (int s = 1; s < slices; s++) {
-                    const float *oth_slot = slots + (grp + s) * 2 * DP;
-                    f4add(gi, *reinterpret_cast<const float4 *>(oth_slot + lg * 4));
-                    f4add(ge, *reinterpret_cast<const float4 *>(oth_slot + DP + lg * 4));
-                }
-            }
-            if (r + 1 < r0 + nr) __syncthreads();
-        }
+        join_slices<DP>(slots, grp, lg, slices, active, leader, r + 1 < r0 + nr, gi, ge);
         if (r == r0 + STAMP_ROUND) STAMP(5);
         if (active && leader) {
             const float cnt = (float)(meta >> 9);
-            if (cnt != 0.f) {
-                f4fma(gi, cnt, reg_term(oi, k.r2, k.r1));
-                f4fma(ge, cnt, reg_term(oe, k.r2, k.r1));
-            }
+            add_regulariser(gi, ge, oi, oe, cnt, k);
             if (!a.fused) {
                 put4<VEC, 0, FULL>(a.np[1], row, t.D, lg, gi);
                 if (!pure) put4<VEC, 0, FULL>(a.np[3], row, t.D, lg, ge);
             } else {
                 float4 mi = f4zero(), vi = f4zero(), me = f4zero(), ve = f4zero();
                 if (dma) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA pieces have landed
-                    mi = mv_wave[0 * 64 + lane]; vi = mv_wave[1 * 64 + lane];
-                    if (!pure) { me = mv_wave[2 * 64 + lane]; ve = mv_wave[3 * 64 + lane]; }
+                    moments_from_lds(mv_wave, lane, pure, mi, vi, me, ve);
                 } else {
                     mi = row4<VEC, FULL>(a.m[1], row, t.D, lg); vi = row4<VEC, FULL>(a.v[1], row, t.D, lg);
                     if (!pure) { me = row4<VEC, FULL>(a.m[3], row, t.D, lg); ve = row4<VEC, FULL>(a.v[3], row, t.D, lg); }
@@ -1199,7 +1193,7 @@ template <int LG, bool VEC, bool FULL>
 __device__ __forceinline__ void stream_task(const DevTables &t, const StepArgs &a, const int *rows, int n) {
     constexpr int R = 2, NG = kThreads / LG;
     const int lg = threadIdx.x & (LG - 1), grp = threadIdx.x / LG;
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    const AdamScalars ad = adam_of(a);
     const bool pure = a.flags & INVPREF_PURE_MF;
     if (!a.fused) {   // gradient form: the untouched rows' gradient is a row of zeros
         for (int i = grp; i < n; i += NG) {
@@ -1286,7 +1280,7 @@ __device__ __forceinline__ void fold_block(const DevTables &t, const StepArgs &a
     const int idx = fb * kFoldCols + colx;
     const bool pure = a.flags & INVPREF_PURE_MF;
     const bool dense = (a.flags & INVPREF_DENSE_REG) && !(a.flags & INVPREF_REG_ONLY_EMBED) && !pure;
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    const AdamScalars ad = adam_of(a);
     const bool mine = idx < SLAB;
     // which output this column is
     const bool isLoss = idx >= 2 * EDP + EMAX, isB = !isLoss && idx >= 2 * EDP, isW = !isLoss && !isB && idx >= EDP;

@@ -332,12 +332,9 @@ __device__ __forceinline__ void user_task_wide(const DevTables &t, const StepArg
     const bool reg_env = a.flags & INVPREF_REG_ENV_EMBED;
     const bool pure = a.flags & INVPREF_PURE_MF;
     const bool push = a.push_slot != nullptr;
-    StepScalars k = a.k;
-    if (a.sched_state) {  // scheduled alpha (train.py:214-217) under graph replay
-        const float al = sched_slot_ptr(a.sched_state, a.sched_slot)->alpha;
-        if (al == al) k.alpha = al;
-    }
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    StepScalars k;
+    AdamScalars ad;
+    scalars_of(a, k, ad);
 
     STAMP(0);
     // both halves of the descriptor: row | meta | list range or inline interactions | a list slice's leading interaction
@@ -680,12 +677,9 @@ __device__ __forceinline__ void item_task_wide(const DevTables &t, const StepArg
     const int lg = threadIdx.x & (LG - 1), grp = threadIdx.x / LG, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const bool pure = a.flags & INVPREF_PURE_MF;
     const bool reg_env = a.flags & INVPREF_REG_ENV_EMBED;
-    StepScalars k = a.k;
-    if (a.sched_state) {
-        const float al = sched_slot_ptr(a.sched_state, a.sched_slot)->alpha;
-        if (al == al) k.alpha = al;
-    }
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    StepScalars k;
+    AdamScalars ad;
+    scalars_of(a, k, ad);
     STAMP(0);
     int4 d = a.desc[(r0 * NG + grp) * 2];   // (the inline interactions of the descriptor's second half are read back from memory)
     STAMP(1);
@@ -882,7 +876,7 @@ __device__ __forceinline__ void item_task_push_wide(const DevTables &t, const St
     const int lg = threadIdx.x & (LG - 1), grp = threadIdx.x / LG;
     const bool pure = a.flags & INVPREF_PURE_MF;
     const StepScalars k = a.k;
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    const AdamScalars ad = adam_of(a);
     STAMP(0);
     int4 d = a.desc[(r0 * NG + grp) * 2];
     STAMP(1);
@@ -1003,7 +997,7 @@ template <int LG, int NC, bool VEC, int THREADS = kThreads>
 __device__ __forceinline__ void stream_task_wide(const DevTables &t, const StepArgs &a, const int *rows, int n) {
     constexpr int NG = THREADS / LG;
     const int lg = threadIdx.x & (LG - 1), grp = threadIdx.x / LG;
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    const AdamScalars ad = adam_of(a);
     const bool pure = a.flags & INVPREF_PURE_MF;
     float4 z[NC];
 #pragma unroll

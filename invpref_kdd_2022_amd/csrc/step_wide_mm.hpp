@@ -99,12 +99,9 @@ __device__ __forceinline__ void user_task_wide_mm(const DevTables &t, const Step
     const bool reg_env = a.flags & INVPREF_REG_ENV_EMBED;
     const bool push = a.push_slot != nullptr;
     const int E = t.E;
-    StepScalars k = a.k;
-    if (a.sched_state) {  // scheduled alpha (train.py:214-217) under graph replay
-        const float al = sched_slot_ptr(a.sched_state, a.sched_slot)->alpha;
-        if (al == al) k.alpha = al;
-    }
-    const AdamScalars ad = a.sched_state ? sched_slot_ptr(a.sched_state, a.sched_slot)->ad : a.ad;
+    StepScalars k;
+    AdamScalars ad;
+    scalars_of(a, k, ad);
 
     STAMP(0);
     int4 d = a.desc[(r0 * NG + grp) * 2], d2 = a.desc[(r0 * NG + grp) * 2 + 1];
